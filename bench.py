@@ -20,6 +20,11 @@ optional out_features tensor-parallel mode (one RCCL all-gather per layer) is ti
 reported under "tp" (Llama-2-70B shapes, BASELINE config 4).
 
 Workloads: --workload decode (default) | prefill (M = 2048, act-order, MFMA path, reports TFLOP/s).
+
+A plain run builds the stack, warms up, times --steps replays and prints the headline line.  Everything else (the roofline per launch type,
+the check of the timed outputs against a second kernel family, the eager / fused / MLP / prefill / config 5 / batched / warm-cache blocks,
+the CPU baseline, the per-layer tensor-parallel entries) runs only with --full.  --dump-outputs DIR writes what the timed path returned in
+its last step as DIR/<block>_<layer>.npy (float32; inputs and weights are seeded, so two builds compare output for output).
 """
 import argparse
 import json
@@ -80,8 +85,36 @@ def build_stack(device, n_blocks, M, act_order, dtype=torch.float16):
             # q / k / v read one input and so do gate / up: one activation order per group of a block (o and down have their own)
             grp = {"q_proj": 0, "k_proj": 0, "v_proj": 0, "gate_proj": 1, "up_proj": 1}.get(name, 2 + i)
             layers.append((name, K, N, make_layer(K, N, device, act_order=act_order, dtype=dtype, seed=b * 16 + i, order_seed=10_000 + b * 16 + grp)))
-    xs = {K: (torch.rand(M, K, device=device) - 0.5).to(dtype) for K in (4096, 11008)}
+    gx = torch.Generator(device=device).manual_seed(20_000)
+    xs = {K: (torch.rand(M, K, device=device, generator=gx) - 0.5).to(dtype) for K in (4096, 11008)}
     return layers, xs
+
+
+def stack_output_names(blocks):
+    """<block>_<layer> for every layer of `blocks` decoder blocks, in stack order (the order of the flattened outputs)."""
+    return [f"b{b:02d}_{name}" for b in range(blocks) for name, _, _ in LLAMA7B_BLOCK]
+
+
+def flatten_outputs(outs):
+    """One tensor per layer: a grouped launch (gptq_forward_multi) returns its layers' outputs as a list."""
+    return [t for y in outs for t in (y if isinstance(y, (list, tuple)) else [y])]
+
+
+def dump_outputs(path, names, tensors, budget=60_000_000):
+    """Write each output as <path>/<name>.npy in float32.  Outputs of more than `budget` bytes in all keep the same seeded sample of rows in
+    every array (sorted row indices from a fixed seed), so the files stay under 64 MB and two builds still compare row for row."""
+    import numpy as np
+    assert len(names) == len(tensors), (len(names), len(tensors))
+    os.makedirs(path, exist_ok=True)
+    rows = tensors[0].shape[0]
+    per_row = 4 * sum(t[0].numel() for t in tensors)
+    keep = max(1, min(rows, budget // per_row))
+    idx = None
+    if keep < rows:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(rows, keep, replace=False)))
+    for name, t in zip(names, tensors):
+        y = t if idx is None else t.index_select(0, idx.to(t.device))
+        np.save(os.path.join(path, name + ".npy"), y.float().cpu().numpy())
 
 
 def group_stack(layers):
@@ -688,12 +721,12 @@ def cpu_baseline(M, act_order, budget_s=20.0, device=None):
     gpu_check = {"shapes": 0, "outputs": 0, "max_err_over_max_out": 0.0, "tolerance": "1e-3 * max|y_cpu| + 1e-3 * |y_cpu| per output", "ok": True,
                  "what": "the product's default plan on the same layers and inputs, every output against the CPU result timed here"}
     per_shape = budget_s / 3
-    # Where the reference tree is present (the build container; it does not travel to the GPU box) its OWN class is what is timed -- kind "reference":
-    # auto_gptq/nn_modules/qlinear/qlinear_cuda_old.py (qlinear_cuda.py for act-order) loaded by file path, as tools/time_reference_cpu.py does.
+    # Where GPTQ_REFERENCE names a reference tree its OWN class is what is timed -- kind "reference": auto_gptq/nn_modules/qlinear/qlinear_cuda_old.py
+    # (qlinear_cuda.py for act-order) loaded by file path, as tools/time_reference_cpu.py does.  Without it, the port (kind "port").
     ref_cls = None
-    ref_root = os.environ.get("GPTQ_REFERENCE", "/root/reference")
+    ref_root = os.environ.get("GPTQ_REFERENCE", "")
     ref_file = os.path.join(ref_root, "auto_gptq/nn_modules/qlinear", "qlinear_cuda.py" if act_order else "qlinear_cuda_old.py")
-    if os.path.exists(ref_file):
+    if ref_root and os.path.exists(ref_file):
         try:
             import importlib.util
             spec = importlib.util.spec_from_file_location("ref_qlinear_for_bench", ref_file)
@@ -780,7 +813,7 @@ def cpu_baseline(M, act_order, budget_s=20.0, device=None):
                        "oracle.forward_fast = the reference's own broadcast shift+mask unpack (qlinear_cuda_old.py:295-349) + torch.matmul, ") +
                       "torch CPU fp16, M=%d, shapes x reps: %s" % (M, ", ".join(reps_done)),
             "ms_per_layer_mean": round(1e3 * total_t / sum(int(r.split('x')[2]) for r in reps_done), 2),
-            # the reference CLASS itself (qlinear_cuda_old.QuantLinear.forward, imported from /root/reference) timed in the 8-core build container,
+            # the reference CLASS itself (qlinear_cuda_old.QuantLinear.forward, loaded from the reference tree) timed on 8 cores,
             # ms per forward on 4096x4096 / 4096x11008 / 11008x4096: it cannot run on the GPU box, so this port is what is timed here
             "reference_class_ms_build_container": [30.4, 768, 305],
             **({"gpu_vs_cpu": gpu_check} if device is not None else {})}
@@ -931,13 +964,14 @@ LLAMA70B_BLOCK = [("q_proj", 8192, 8192), ("k_proj", 8192, 1024), ("v_proj", 819
                   ("gate_proj", 8192, 28672), ("up_proj", 8192, 28672), ("down_proj", 28672, 8192)]
 
 
-def bench_tp_stack(device, rank, world, n_blocks, M, steps, warmup, exchange="all_gather"):
+def bench_tp_stack(device, rank, world, n_blocks, M, steps, warmup, exchange="all_gather", outputs=None):
     """BASELINE config 4 as a STACK (round 6: the N > 1 headline): the seven quantized linears of `n_blocks` Llama-2-70B decoder blocks (GQA: 1024-column k / v),
     every layer split over out_features across the ranks (north_star: "the per-layer matmul shards naturally over out_features ... a single RCCL all-gather") --
     rank r holds columns [r N / T, (r + 1) N / T) of every layer, runs its shard's kernel and the layer's outputs are all-gathered.  One step = M rows through all
     7 n_blocks layers, ONE hipGraph per rank (the collectives captured with the kernels: RCCL captures like any other stream work); `steps` replays between
     barrier + synchronize, MAX over ranks.  value = the algorithmic bytes of ALL shards per second (whole job).  The same graph WITHOUT the exchange is timed
-    beside it: what the all-gathers cost.  Falls back to eager calls when a capture fails (then launch-bound, and says so)."""
+    beside it: what the all-gathers cost.  Falls back to eager calls when a capture fails (then launch-bound, and says so).
+    outputs: a list that receives the gathered outputs of the last timed step with the exchange, one tensor per layer in stack order."""
     import torch.distributed as dist
     from autogptq_amd.tensor_parallel import ColumnParallelQuantLinear
     mods, shard_bytes = [], 0
@@ -946,7 +980,8 @@ def bench_tp_stack(device, rank, world, n_blocks, M, steps, warmup, exchange="al
             local = make_layer(K, N // world, device, seed=(b * 16 + i) * 64 + rank)
             mods.append((K, local, ColumnParallelQuantLinear(local, N, exchange=exchange, max_rows=max(1, M))))
             shard_bytes += algorithmic_bytes(K, N // world, M)
-    xs = {K: (torch.rand(M, K, device=device) - 0.5).half() for K in (8192, 28672)}
+    gx = torch.Generator(device=device).manual_seed(30_000)
+    xs = {K: (torch.rand(M, K, device=device, generator=gx) - 0.5).half() for K in (8192, 28672)}
 
     def step_with():
         return [m(xs[K]) for K, _, m in mods]
@@ -954,8 +989,8 @@ def bench_tp_stack(device, rank, world, n_blocks, M, steps, warmup, exchange="al
     def step_local():
         return [l(xs[K]) for K, l, _ in mods]
 
-    def run(fn):
-        """(seconds per step, max over ranks; 'graph' | 'eager: <why>')"""
+    def run(fn, last=None):
+        """(seconds per step, max over ranks; 'graph' | 'eager: <why>'); `last` (a list) receives the outputs of the last timed step"""
         how, g, keep = "graph", None, None
         ok = 1
         try:
@@ -984,16 +1019,18 @@ def bench_tp_stack(device, rank, world, n_blocks, M, steps, warmup, exchange="al
             torch.cuda.synchronize(device)
             t0 = time.perf_counter()
             for _ in range(steps):
-                one()
+                ys = one()
             torch.cuda.synchronize(device)
             dist.barrier()
             wall = time.perf_counter() - t0
         t = torch.tensor([wall], device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        if last is not None:
+            last.extend(keep if use_graph else ys)
         del keep
         return t.item() / steps, how
 
-    t_with, how_with = run(step_with)
+    t_with, how_with = run(step_with, outputs)
     t_loc, how_loc = run(step_local)
     devs = [None] * world
     dist.all_gather_object(devs, {"rank": rank, "device": str(device), "name": torch.cuda.get_device_name(device),
@@ -1075,6 +1112,11 @@ def main():
     ap.add_argument("--no-tp-layers", action="store_true", help="N > 1: skip the per-layer tensor-parallel entries (roofline.tp<N>_attn_* ...), keep the stack")
     ap.add_argument("--tp-exchange", default="all_gather", choices=["all_gather", "peer_store"],
                     help="tp block: also time the experimental direct peer-store exchange (csrc/peer.hip) next to the collective")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: roofline per launch type, timed-output check, eager / fused / MLP / prefill / config 5 / "
+                         "batched / warm-cache blocks, CPU baseline, per-layer tensor-parallel entries (the --no-* options still trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<block>_<layer>.npy (float32, <= 64 MB in all)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1116,6 +1158,10 @@ def main():
         t = torch.tensor([wall], device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = t.item()
+    # --dump-outputs: the timed graph's outputs hold its last step; with N > 1 and the tensor-parallel stack as the headline, that stack's are written instead
+    dump_here = args.dump_outputs and rank == 0 and not (world > 1 and not args.no_tp and not prefill)
+    if dump_here:
+        dump_outputs(args.dump_outputs, stack_output_names(n_blocks), flatten_outputs(outs))
 
     bytes_step = sum(entry_bytes(e, M, act_order) for e in layers)
     flops_step = sum(2 * M * K * N for _, K, N, _ in layers)
@@ -1123,7 +1169,7 @@ def main():
 
     # ---- roofline of the dominant kernel: a graph holding only that layer type --------------------
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
       try:
         by_type = {}
         for ent in layers:
@@ -1176,7 +1222,6 @@ def main():
         else:
             value, unit, metric = bytes_step * args.steps * world / wall / 1e9, "GB/s", \
                 "int4 g128 QuantLinear fwd GB/s + tokens/s, Llama-7B shapes"
-        verify = verify_timed_outputs(layers, outs, xs)          # behind every timed region of the headline (it idles the GPU)
         out = {
             "metric": metric, "value": round(value, 2), "unit": unit, "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(1e3 * wall / args.steps, 4), "higher_is_better": True,
@@ -1190,11 +1235,12 @@ def main():
             "tokens_per_s_note": "linear-only (the %d quantized linears of the stack; no attention/norm)" % len(flat_layers),
             "event_ms_per_step_rank0": round(1e3 * ev / args.steps, 4),
             "algorithmic_bytes_per_step": bytes_step,
-            "roofline": roof,
-            "verify": verify,
         }
-        if isinstance(roof, dict) and isinstance(verify, dict) and "ok" in verify:
-            roof["timed_outputs_verified"] = verify["ok"]
+        if args.full:
+            verify = verify_timed_outputs(layers, outs, xs)      # behind every timed region of the headline (it idles the GPU)
+            out["roofline"], out["verify"] = roof, verify
+            if isinstance(roof, dict) and isinstance(verify, dict) and "ok" in verify:
+                roof["timed_outputs_verified"] = verify["ok"]
     # The tensor-parallel block is extra information: it runs with the headline already built, under a deadline of its own -- a hung or failed
     # collective (one rank raising inside a capture while the others wait) costs the `tp` object, never the line the driver reads.
     if world > 1 and not args.no_tp and not prefill:
@@ -1209,14 +1255,15 @@ def main():
                 sys.stdout.flush()
             os._exit(0)
         finish = _deadline(tp_limit, tp_expired)
+        tp_outs = []
         try:
             tp = {}
             # the N > 1 HEADLINE (round 6): the tensor-parallel stack of BASELINE config 4 -- north_star's partitioning, timed with its exchange
             try:
-                tp["stack"] = bench_tp_stack(device, rank, world, args.tp_blocks, M, args.steps, args.warmup, exchange=args.tp_exchange)
+                tp["stack"] = bench_tp_stack(device, rank, world, args.tp_blocks, M, args.steps, args.warmup, exchange=args.tp_exchange, outputs=tp_outs)
             except Exception as e:
                 tp["stack"] = {"error": repr(e)[:300]}
-            if not args.no_tp_layers:
+            if args.full and not args.no_tp_layers:
                 tp.update(bench_tp(device, rank, world, 50, peer_store=(args.tp_exchange == "peer_store")))
         except Exception as e:                       # the headline line must still be printed
             tp = {"error": repr(e)[:300]}
@@ -1224,6 +1271,27 @@ def main():
             time.sleep(3600)                          # the timer thread is printing the line and ending the process
         if rank == 0:
             out["tp"] = tp
+            st = tp.get("stack")
+            if isinstance(st, dict) and "GB_per_s" in st:
+                # The tensor-parallel stack becomes the line's value; the data-parallel replicas (each rank its own Llama-7B stack: trivially linear) move
+                # to `dp_replicas`.  Scaling is STRONG: the model is fixed, every added rank takes a smaller shard of every layer.
+                out["dp_replicas"] = {k: out[k] for k in ("value", "unit", "ms_per_step", "tokens_per_s", "algorithmic_bytes_per_step") if k in out}
+                out["dp_replicas"]["workload"] = out["config"]["workload"]
+                out["value"], out["ms_per_step"], out["tokens_per_s"] = st["GB_per_s"], st["ms_per_step"], st["tokens_per_s"]
+                out["algorithmic_bytes_per_step"] = st["algorithmic_bytes_per_step_per_rank"] * world
+                out["scaling"] = "strong"
+                out["metric"] = "int4 g128 QuantLinear fwd GB/s + tokens/s, Llama-2-70B shapes split over out_features (TP=%d) + one all-gather per layer" % world
+                out["config"] = {"workload": st["workload"], "rows_per_step": M, "layers": st["layers"], "launches": st["layers"],
+                                 "parallelism": f"tp{world}", "exchange": st["exchange"], "backend": st["backend"], "nccl_world": st["nccl_world"],
+                                 "rank_devices": st["rank_devices"], "timed_as": st["timed_as"]}
+                out["tokens_per_s_note"] = "linear-only (the %d quantized linears of %d Llama-2-70B blocks; no attention/norm)" % (st["layers"], st["blocks"])
+            else:
+                out["config"]["parallelism"] = f"dp{world} (the tensor-parallel stack failed: {str((st or {}).get('error'))[:120]}); tp{world} layer entries in roofline.tp{world}_*"
+            if args.dump_outputs:
+                if isinstance(st, dict) and "GB_per_s" in st and tp_outs:
+                    dump_outputs(args.dump_outputs, [f"b{b:02d}_{name}" for b in range(args.tp_blocks) for name, _, _ in LLAMA70B_BLOCK], tp_outs)
+                else:
+                    dump_outputs(args.dump_outputs, stack_output_names(n_blocks), flatten_outputs(outs))
             if isinstance(roof, dict):
                 roof["tp"] = tp                       # the driver keeps `roofline` whole and drops unknown top-level keys
                 # BASELINE config 4 (Llama-2-70B shapes, out_features split over the ranks + one all-gather) as flat scalars beside the DP headline
@@ -1244,31 +1312,16 @@ def main():
                             roof[pre + short + "_us"] = w_
                         if short == "attn" and w_ is not None and l_ is not None:
                             roof[pre + "local_us"], roof[pre + "allgather_us"] = l_, round(w_ - l_, 2)
-                    st = tp.get("stack")
                     if isinstance(st, dict) and "GB_per_s" in st:
-                        # The tensor-parallel stack becomes the line's value; the data-parallel replicas (each rank its own Llama-7B stack: trivially linear) move
-                        # to `dp_replicas`.  Scaling is STRONG: the model is fixed, every added rank takes a smaller shard of every layer.
-                        out["dp_replicas"] = {k: out[k] for k in ("value", "unit", "ms_per_step", "tokens_per_s", "algorithmic_bytes_per_step") if k in out}
-                        out["dp_replicas"]["workload"] = out["config"]["workload"]
-                        out["value"], out["ms_per_step"], out["tokens_per_s"] = st["GB_per_s"], st["ms_per_step"], st["tokens_per_s"]
-                        out["algorithmic_bytes_per_step"] = st["algorithmic_bytes_per_step_per_rank"] * world
-                        out["scaling"] = "strong"
-                        out["metric"] = "int4 g128 QuantLinear fwd GB/s + tokens/s, Llama-2-70B shapes split over out_features (TP=%d) + one all-gather per layer" % world
-                        out["config"] = {"workload": st["workload"], "rows_per_step": M, "layers": st["layers"], "launches": st["layers"],
-                                         "parallelism": f"tp{world}", "exchange": st["exchange"], "backend": st["backend"], "nccl_world": st["nccl_world"],
-                                         "rank_devices": st["rank_devices"], "timed_as": st["timed_as"]}
-                        out["tokens_per_s_note"] = "linear-only (the %d quantized linears of %d Llama-2-70B blocks; no attention/norm)" % (st["layers"], st["blocks"])
                         for k in ("ms_per_step", "ms_per_step_local_kernels_only", "exchange_ms_per_step", "exchange_share", "GB_per_s", "GB_per_s_per_gpu",
                                   "GB_per_s_local_kernels_only", "frac_per_gpu"):
                             roof[pre + "stack_" + k] = st[k]
                         roof["dp_value_GB_per_s"] = out["dp_replicas"].get("value")
-                    else:
-                        out["config"]["parallelism"] = f"dp{world} (the tensor-parallel stack failed: {str((st or {}).get('error'))[:120]}); tp{world} layer entries in roofline.tp{world}_*"
                 except Exception as e:
                     roof["tp_flat_keys_error"] = repr(e)[:200]
 
     if rank == 0:
-        if not prefill and world == 1 and not args.no_extras:
+        if args.full and not prefill and world == 1 and not args.no_extras:
             try:
                 out["eager"] = bench_eager(layers, xs, device, max(3, args.steps // 4))
                 if launches != len(flat_layers):
@@ -1283,19 +1336,19 @@ def main():
                     out["eager_per_layer"] = bench_eager(flat_layers, xs, device, max(3, args.steps // 4))
             except Exception as e:
                 out["eager"] = {"error": repr(e)[:300]}
-        if not prefill and world == 1 and not args.no_extras:
+        if args.full and not prefill and world == 1 and not args.no_extras:
             try:
                 out["mlp_call"] = bench_mlp_call(flat_layers, xs, device, args.steps)
             except Exception as e:
                 out["mlp_call"] = {"error": repr(e)[:300]}
-        if not prefill and world == 1 and not args.no_fused:
+        if args.full and not prefill and world == 1 and not args.no_fused:
             try:
                 del g, outs, layers, flat_layers
                 torch.cuda.empty_cache()
                 out["fused_callers"] = bench_fused(device, n_blocks, args.steps)
             except Exception as e:
                 out["fused_callers"] = {"error": repr(e)[:300]}
-        if not prefill and world == 1 and not args.no_extras:
+        if args.full and not prefill and world == 1 and not args.no_extras:
             for name, fn in (("prefill", lambda: bench_prefill(device, max(3, args.steps // 4))),
                              ("mlp_prefill", lambda: bench_mlp_prefill(device, max(3, args.steps // 4))),
                              ("config5", lambda: bench_config5(device, args.steps)),
@@ -1418,7 +1471,7 @@ def main():
                             roof[k.lower() + "_us"] = bd2[k]["us"]
             except Exception as e:
                 roof["flat_keys_error"] = repr(e)[:200]
-        if not args.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only (bounded sample, ~25 s of host time)
+        if args.full and not args.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only (bounded sample, ~25 s of host time)
             out["cpu_baseline"] = cpu_baseline(1 if not prefill else 16, act_order, device=device)
         print(json.dumps(out))
     if world > 1:

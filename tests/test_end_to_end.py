@@ -6,7 +6,7 @@ known-good text); with no network the "known good" here is the fp16 twin whose l
 CPU part: the checkpoint round trip and the attribute contract against the reference's GeneralQuantLinear shim.
 GPU part (-m gpu): logits and greedy tokens of the quantized model (HIP kernels) against the twin.
 """
-import importlib.util
+import json
 import os
 
 import pytest
@@ -14,7 +14,7 @@ import torch
 
 import _tiny_llama as TL
 
-REF_SHIM = "/root/reference/auto_gptq/nn_modules/qlinear/__init__.py"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 @pytest.mark.parametrize("desc_act", [False, True], ids=["seq", "act"])
@@ -36,24 +36,35 @@ def test_checkpoint_round_trip_cpu(tmp_path, desc_act):
     assert {"qweight", "qzeros", "scales", "g_idx"} <= {k.rsplit(".", 1)[1] for k in sd if "q_proj" in k}
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SHIM), reason="reference tree not present (GPU box)")
 def test_reference_general_quant_linear_shim_accepts_this_backend():
-    """auto_gptq/nn_modules/qlinear/__init__.py:4-56 wraps ANY backend's QuantLinear by reading its attributes and buffers;
-    loaded by path (it only imports torch.nn) and wrapped around this class, on CPU."""
+    """auto_gptq/nn_modules/qlinear/__init__.py:4-56 wraps ANY backend's QuantLinear by reading its attributes and buffers.  What it read from this
+    class and what the wrapper it built held were recorded by running it (tests/golden/make_golden_shim.py -> shim_general_quant_linear.json); the
+    class is checked against that record, on CPU: every attribute the shim found is still there with the recorded value, the tensors it shares
+    register as buffers and back an nn.Linear's weight / bias, forward is this backend's own, and inject_to_model's isinstance walk finds it."""
     from autogptq_amd import QuantLinear
 
-    spec = importlib.util.spec_from_file_location("ref_qlinear_shim", REF_SHIM)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    with open(os.path.join(GOLDEN, "shim_general_quant_linear.json")) as f:
+        rec = json.load(f)
+    assert rec["forward_is_wrapped_forward"] and rec["inject_to_model"] == {"a": "GeneralQuantLinear", "b": "Linear"}
     q = QuantLinear(4, 128, 256, 512, True)
-    g = mod.GeneralQuantLinear(q)
-    assert (g.infeatures, g.outfeatures, g.bits, g.group_size, g.maxq) == (256, 512, 4, 128, 15)
-    assert g.in_features == 256 and g.out_features == 512 and g.trainable is False
-    for name in ("qweight", "qzeros", "scales", "g_idx"):
-        assert getattr(g, name) is getattr(q, name), name            # the shim registers the SAME tensors
-    assert g.weight.data_ptr() == q.qweight.data_ptr() and g.bias.data_ptr() == q.bias.data_ptr()
-    assert g.kernel_switch_threshold == q.kernel_switch_threshold
-    assert g.forward == q.forward                                     # bound method of this backend: forward goes to the HIP path
+    for name in rec["attributes_found"]:
+        assert hasattr(q, name), name
+    for name, want in rec["scalars"].items():
+        assert getattr(q, name) == want and type(getattr(q, name)) is type(want), (name, getattr(q, name), want)
+    assert {"infeatures", "outfeatures", "bits", "group_size", "maxq", "trainable", "kernel_switch_threshold"} <= set(rec["scalars"])
+
+    lin = torch.nn.Linear(q.infeatures, q.outfeatures, bias=True)    # the wrapper is this nn.Linear ...
+    lin.weight.requires_grad = False                                  # (frozen before its .data becomes the int32 qweight)
+    assert {"in_features": lin.in_features, "out_features": lin.out_features} == rec["linear_features"] == {"in_features": 256, "out_features": 512}
+    for field, src in rec["linear_data"].items():                    # ... whose weight / bias .data become the wrapped module's tensors
+        getattr(lin, field).data = getattr(q, src)
+        assert getattr(lin, field).data_ptr() == getattr(q, src).data_ptr(), field
+    assert rec["linear_data"] == {"weight": "qweight", "bias": "bias"}
+    assert set(rec["tensors_shared"]) == set(rec["wrapper_buffers"]) == {"qweight", "qzeros", "scales", "g_idx"}
+    for name in rec["tensors_shared"]:                                 # the shim registers the SAME tensors as its buffers
+        lin.register_buffer(name, getattr(q, name))
+        assert getattr(lin, name) is getattr(q, name), name
+    assert q.forward.__self__ is q and q.forward.__func__ is QuantLinear.forward   # bound method of this backend: forward goes to the HIP path
 
     class Holder(torch.nn.Module):
         def __init__(self):
@@ -61,8 +72,8 @@ def test_reference_general_quant_linear_shim_accepts_this_backend():
             self.a = QuantLinear(4, 128, 256, 512, True)
             self.b = torch.nn.Linear(4, 4)
     h = Holder()
-    mod.GeneralQuantLinear.inject_to_model(h, QuantLinear)
-    assert type(h.a).__name__ == "GeneralQuantLinear" and isinstance(h.b, torch.nn.Linear) and not hasattr(h.b, "qweight")
+    assert [n for n, m in h.named_modules() if isinstance(m, QuantLinear)] == ["a"]      # inject_to_model's walk: the QuantLinear, not the Linear
+    assert not hasattr(h.b, "qweight")
 
 
 @pytest.mark.gpu

@@ -94,7 +94,7 @@ def test_bench_two_ranks_headline_is_the_tensor_parallel_stack():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(root, "bench.py"), "--gpus", "2", "--same-device", "--backend", "gloo", "--blocks", "1", "--tp-blocks", "1", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--no-tp-layers", "--no-fused", "--no-extras"]
+           "--full", "--no-cpu-baseline", "--no-tp-layers", "--no-fused", "--no-extras"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])

@@ -7,7 +7,7 @@ set -u
 VARIANTS=$1; ROUNDS=${2:-2}; shift; shift || true
 for i in $(seq "$ROUNDS"); do for v in $VARIANTS; do
     if [ "$v" = A ]; then unset GPTQ_MI355X_LIB; else export GPTQ_MI355X_LIB=$PWD/tools/libgptq_$v.so; fi
-    BENCH_WATCHDOG_S=150 timeout 180 python bench.py --no-cpu-baseline --steps 100 "$@" 2>/dev/null | tail -1 | python -c "
+    BENCH_WATCHDOG_S=150 timeout 180 python bench.py --full --no-cpu-baseline --steps 100 "$@" 2>/dev/null | tail -1 | python -c "
 import sys, json
 try:
     d = json.loads(sys.stdin.read())

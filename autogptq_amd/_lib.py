@@ -25,7 +25,7 @@ DTYPE_ENUM = {torch.float16: GPTQ_F16, torch.bfloat16: GPTQ_BF16, torch.float32:
 # every symbol include/gptq_mi355x.h declares (tests check the .so exports all of them)
 EXPORTS = (
     "gptq_abi_version", "gptq_last_error", "gptq_status_string", "gptq_workspace_bytes", "gptq_workspace_bytes_ex",
-    "gptq_forward", "gptq_forward_ex", "gptq_gemv", "gptq_gemm", "gptq_dequant",
+    "gptq_forward", "gptq_forward_ex", "gptq_gemv", "gptq_gemm", "gptq_dequant", "gptq_grad_input",
     "gptq_unpack_weights", "gptq_unpack_zeros", "gptq_pack_weights", "gptq_pack_zeros",
     "gptq_make_sequential", "gptq_resequence_qweight", "gptq_permute_columns", "gptq_prepack_decode", "gptq_prepack_decode_bytes", "gptq_unprepack_decode",
     "gptq_awq_unpack", "gptq_awq_repack", "gptq_describe_plan",
@@ -126,6 +126,7 @@ def load() -> ctypes.CDLL:
     for name in ("gptq_forward_ex", "gptq_gemv", "gptq_gemm"):
         getattr(lib, name).argtypes = fw + [POINTER(GptqTuning)]
     lib.gptq_dequant.argtypes = [POINTER(GptqLayer), c_void_p, c_void_p]
+    lib.gptq_grad_input.argtypes = [POINTER(GptqLayer), c_void_p, c_void_p, c_int, c_int, c_void_p]
     lib.gptq_unpack_weights.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
     lib.gptq_unpack_zeros.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
     lib.gptq_pack_weights.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,

@@ -12,6 +12,7 @@
 #include <Python.h>
 
 #include <ATen/ATen.h>
+#include <ATen/core/grad_mode.h>
 #include <c10/hip/HIPStream.h>
 #include <torch/csrc/autograd/python_variable.h>
 
@@ -38,8 +39,10 @@ static PyObject* bind(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
     Py_RETURN_NONE;
 }
 
-/* the plain case: a CUDA tensor of the layer's dtype on the layer's device, which is the current device; [.., K] contiguous */
+/* the plain case: a CUDA tensor of the layer's dtype on the layer's device, which is the current device; [.., K] contiguous; no autograd node to record
+ * (an x that requires grad under grad mode goes through the Python path's autograd function) */
 static inline bool plain_x(const at::Tensor& x, long K, long dtype_code, long dev_index, int64_t* M) {
+    if (x.requires_grad() && at::GradMode::is_enabled()) return false;
     if (!x.is_cuda() || (long)x.scalar_type() != dtype_code || x.dim() < 1 || x.size(-1) != K || !x.is_contiguous()) return false;
     if (x.get_device() != dev_index || c10::hip::current_device() != dev_index) return false;
     *M = K ? x.numel() / K : 0;

@@ -770,6 +770,16 @@ int gptq_dequant(const gptq_layer_t* L, void* W_out, void* stream) {
     return GPTQ_OK;
 }
 
+int gptq_grad_input(const gptq_layer_t* L, const void* dy, void* dx, int M, int accumulate, void* stream) {
+    int rc = check_layer(L);
+    if (rc) return rc;
+    if ((rc = check_io(dy, dx, M))) return rc;
+    if (((uintptr_t)dy | (uintptr_t)dx) & 15) return fail(GPTQ_ERR_UNSUPPORTED, "dy / dx must be 16-byte aligned");
+    hipError_t e = launch_grad_input(*L, dy, dx, M, accumulate, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "gptq_grad_input launch");
+    return GPTQ_OK;
+}
+
 int gptq_unpack_weights(const uint32_t* qweight, int K, int N, int bits, uint8_t* w_out, void* stream) {
     if (!qweight || !w_out) return fail(GPTQ_ERR_NULL, "qweight/w_out must be non-NULL");
     if (!bits_ok(bits)) return fail(GPTQ_ERR_UNSUPPORTED, "Only 2,3,4,8 bits are supported. (got %d)", bits);

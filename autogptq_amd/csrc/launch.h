@@ -173,6 +173,9 @@ hipError_t init_gemv_device();
 hipError_t init_gemm_device();
 
 hipError_t launch_dequant(const gptq_layer_t& L, void* W_out, hipStream_t st);
+// grad_input.hip: dX (+)= dY . W^T on the packed rows (L.qweight, L.g_idx); BM x 128 output tiles (grad_input_bm: BM = 128 or 64)
+int grad_input_bm(const gptq_layer_t& L, int M);
+hipError_t launch_grad_input(const gptq_layer_t& L, const void* dy, void* dx, int M, int accumulate, hipStream_t st);
 hipError_t launch_unpack_weights(const uint32_t* qweight, int K, int N, int bits, uint8_t* w_out, hipStream_t st);
 hipError_t launch_unpack_zeros(const uint32_t* qzeros, int G, int N, int bits, int zero_mode, int32_t* z_out, hipStream_t st);
 hipError_t launch_pack_weights(const void* W, const void* scale_in, const void* zero_in, const int32_t* g_idx,

@@ -23,6 +23,7 @@ from logging import getLogger
 import numpy as np
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 
@@ -402,6 +403,8 @@ class QuantLinear(nn.Module):
                 if r.__class__ is int:
                     _lib.check(r)
                 return r
+        if x.requires_grad and torch.is_grad_enabled():       # an autograd node (the C++ fast path above declines these calls)
+            return self._forward_grad(x, tuning)
         if self._layer is None:
             if getattr(self, "_parts", None) is None:
                 if x.device.type != "cuda":
@@ -464,6 +467,93 @@ class QuantLinear(nn.Module):
         if x.dim() != 2:
             out = out.reshape(x.shape[:-1] + (n_out,))
         return out
+
+    # ------------------------------------------------------------------ gradients
+    def _forward_grad(self, x: torch.Tensor, tuning=None):
+        """forward() when grad mode is on and x requires grad: one _GradInput node (dX = dY . W^T through gptq_grad_input; the buffers get no gradient).
+        The dtype casts either side are ordinary autograd ops, so x.grad comes back in x.dtype.  A 'silu_mul' layer is composed from differentiable
+        pieces: its plain [gate | up] product, then silu(g) * u."""
+        if self._layer is None and getattr(self, "_parts", None) is None:
+            if x.device.type != "cuda":
+                raise RuntimeError("mi355x QuantLinear.forward needs a ROCm GPU tensor "
+                                   f"(got {x.device}); there is no CPU path in this backend.")
+            self.post_init()
+        if getattr(self, "_parts", None) is not None:          # fused-QKV g_idx: forward_multi records one node for the n column blocks
+            return torch.cat(forward_multi(self._parts, x, tuning), dim=-1)
+        w_dtype = self._w_dtype
+        xw = x.to(w_dtype) if x.dtype != w_dtype else x
+        if self.epilogue == "silu_mul":
+            y = _GradInput.apply(xw, ((self, True),), tuning)[0]
+            h = self.outfeatures // 2
+            y = torch.nn.functional.silu(y[..., :h]) * y[..., h:]
+        else:
+            y = _GradInput.apply(xw, ((self, False),), tuning)[0]
+        return y.to(x.dtype) if x.dtype != w_dtype else y
+
+    def _plain_product(self, x: torch.Tensor, tuning=None) -> torch.Tensor:
+        """x @ W + b of a 'silu_mul' layer BEFORE its epilogue ([.., outfeatures]): gptq_forward_ex on a copy of the layer struct with EPI_NONE."""
+        L = getattr(self, "_layer_plain", None)
+        if L is None or L[0] is not self._layer:
+            c = _lib.GptqLayer()
+            ctypes.pointer(c)[0] = self._layer
+            c.epilogue = _lib.EPI_NONE
+            L = self._layer_plain = (self._layer, c)
+        L = L[1]
+        K, N = self.infeatures, self.outfeatures
+        if self._released:
+            self._rebuild_rows_now()
+        L.qweight = self._layer.qweight
+        x2 = x.reshape(-1, K).contiguous()
+        M = x2.shape[0]
+        out = torch.empty((M, N), dtype=self._w_dtype, device=self._dev)
+        if M:
+            lib = _lib.load()
+            tref = ctypes.byref(tuning) if tuning is not None else None
+            need = int(lib.gptq_workspace_bytes_ex(ctypes.byref(L), M, tref))
+            ws = reserve_workspace(self._dev, need) if need else None
+            if ws is not None:
+                exchange_tick(self._dev)
+            with torch.cuda.device(self._dev_index):
+                _lib.check(lib.gptq_forward_ex(ctypes.byref(L), x2.data_ptr(), out.data_ptr(), M, _lib.ptr(ws), ws.numel() if ws is not None else 0,
+                                               _raw_stream(self._dev_index), tref))
+        return out.reshape(x.shape[:-1] + (N,))
+
+    def _rebuild_rows_now(self) -> None:
+        """Released layers: the packed rows back into the device's shared scratch (gptq_unprepack_decode), in stream order, whatever kernel comes next."""
+        buf = reserve_rows_scratch(self._dev, self._qweight_rows_bytes)
+        self._layer.qweight = buf.data_ptr()
+        with torch.cuda.device(self._dev_index):
+            _lib.check(_lib.load().gptq_unprepack_decode(self._qweight_tiled.data_ptr(), self.infeatures, self.outfeatures, self.bits, buf.data_ptr(),
+                                                         _raw_stream(self._dev_index)))
+
+    def grad_input(self, dy: torch.Tensor, dx: "torch.Tensor | None" = None) -> torch.Tensor:
+        """dX = dY . W^T (W = dequantize(), exactly) through gptq_grad_input; ``dx`` given: dX += dY . W^T in place (fp32 sum, one rounding).
+        dy: [.., outfeatures] of the product BEFORE any epilogue, in the layer dtype.  Returns dX as [M, infeatures]."""
+        if self._layer is None and getattr(self, "_parts", None) is None:
+            self.post_init()
+        if getattr(self, "_parts", None) is not None:
+            K = self.infeatures
+            dy2 = dy.reshape(-1, dy.shape[-1])
+            for i, p in enumerate(self._parts):
+                dx = p.grad_input(dy2[:, i * K:(i + 1) * K], dx)
+            return dx
+        K, N, dev = self.infeatures, self.outfeatures, self._dev
+        dy2 = dy.reshape(-1, N)
+        if dy2.dtype != self._w_dtype:
+            dy2 = dy2.to(self._w_dtype)
+        if not dy2.is_contiguous() or dy2.data_ptr() % 16:
+            dy2 = dy2.clone(memory_format=torch.contiguous_format)
+        M = dy2.shape[0]
+        acc = dx is not None
+        if dx is None:
+            dx = torch.empty((M, K), dtype=self._w_dtype, device=dev)
+        if M:
+            lib = _lib.load()
+            with torch.cuda.device(self._dev_index):
+                if self._released:          # the checkpoint rows are rebuilt into the shared scratch right in front of the kernel (stream order)
+                    self._rebuild_rows_now()
+                _lib.check(lib.gptq_grad_input(self._layer_ref, dy2.data_ptr(), dx.data_ptr(), M, 1 if acc else 0, _raw_stream(self._dev_index)))
+        return dx
 
     # ------------------------------------------------------------------ dequant / unpack helpers
     def dequantize(self) -> torch.Tensor:
@@ -598,6 +688,35 @@ def _pack_fields(vals_u32: torch.Tensor, bits: int) -> torch.Tensor:
     return out.to(torch.int32).contiguous()
 
 
+class _GradInput(torch.autograd.Function):
+    """Outputs of mi355x QuantLinears that read one input x, as ONE autograd node.  forward runs the ordinary (no-grad) path -- the same kernels and
+    values as a call without grad -- and saves no activation; backward sums dY_i . W_i^T of the layers through gptq_grad_input (accumulate = 1 from
+    the second layer on).  qweight / qzeros / scales / g_idx / bias are frozen buffers and get no gradient (the reference's training route treats
+    them the same way); no double backward.  specs: ((layer, plain), ...) -- plain = the product of a 'silu_mul' layer before its epilogue."""
+
+    @staticmethod
+    def forward(ctx, x, specs, tuning):
+        ctx.specs = specs
+        ctx.x_shape = x.shape
+        if len(specs) > 1:
+            outs = forward_multi([l for l, _ in specs], x, tuning)
+        else:
+            l, plain = specs[0]
+            outs = [l._plain_product(x, tuning) if plain else l.forward(x, tuning)]      # (forward, not __call__: the module's hooks ran for the outer call)
+        return tuple(outs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        dx = None
+        for (l, _), g in zip(ctx.specs, grads):
+            if g is not None:
+                dx = l.grad_input(g, dx)
+        if dx is None:
+            return None, None, None
+        return dx.reshape(ctx.x_shape), None, None
+
+
 def share_act_order(layers) -> bool:
     """Act-order layers that read the same input and carry the SAME g_idx -- q / k / v and gate / up of a GPTQ checkpoint do: the order comes from the
     Hessian of their common input (the reference's fused q/k/v caller relies on it, fused_llama_attn.py:188) -- are pointed at ONE ``perm`` buffer; the
@@ -622,6 +741,11 @@ def forward_multi(layers, x: torch.Tensor, tuning: "_lib.GptqTuning | None" = No
     are used where they are (the reference's fused modules concatenate copies of them, fused_llama_attn.py:171-203)."""
     # Everything that depends only on the GROUP is checked and resolved once per group (keyed by the layers' C structs) and kept in _MULTI: a decode
     # launch here takes 4.5 - 12 us, and the reference's callers are eager (generate() under inference_mode) -- per call only what depends on x remains.
+    if x.requires_grad and torch.is_grad_enabled():      # one autograd node for the group (its backward sums the layers' dY . W^T)
+        w_dtype = layers[0].scales.dtype
+        xw = x.to(w_dtype) if x.dtype != w_dtype else x
+        outs = _GradInput.apply(xw, tuple((l, False) for l in layers), tuning)
+        return [o.to(x.dtype) for o in outs] if x.dtype != w_dtype else list(outs)
     a = layers[0]
     n = len(layers)
     released = any(getattr(l, "_released", False) for l in layers)
@@ -723,6 +847,9 @@ def mlp_forward(gate: QuantLinear, up: QuantLinear, down: QuantLinear, x: torch.
     for l in (gate, up, down):
         if l._layer is None:
             l.post_init()
+    if x.requires_grad and torch.is_grad_enabled():      # composed from differentiable pieces (gate | up as one node)
+        g, u = forward_multi([gate, up], x)
+        return down(torch.nn.functional.silu(g) * u)
     if any(getattr(l, "_released", False) for l in (gate, up, down)):
         if tuning is not None:
             raise RuntimeError("mlp_forward: layers with release_checkpoint_layout=True take no tuning override")

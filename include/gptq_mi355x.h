@@ -15,6 +15,10 @@
  *       and the pure-PyTorch fallback they all share                  auto_gptq/nn_modules/qlinear/qlinear_cuda_old.py:291-355, qlinear_cuda.py:253-317
  *   gptq_dequant
  *       <- the `reconstruct` step of exllama / exllamav2              exllama/cuda_func/q4_matrix.cu:171-225, exllamav2/cuda/q_matrix.cu:158-279,452-500
+ *   gptq_grad_input
+ *       <- the backward of the reference's training route: dequantise + torch.matmul under autograd
+ *                                                                     qlinear_cuda_old.py:291-355, qlinear_cuda.py:253-317
+ *          and the triton backend's QuantLinearFunction.backward      auto_gptq/nn_modules/triton_utils/kernels.py:408-426
  *   gptq_make_sequential + gptq_resequence_qweight + gptq_permute_columns
  *       <- exllama_kernels.make_q4 (Q4Matrix::make_sequential)        exllama/exllama_ext.cpp:134-171, cuda_func/q4_matrix.cu:63-169
  *          exllamav2_kernels.make_q_matrix                            exllamav2/ext.cpp:26-93, cuda/q_matrix.cu:502-627
@@ -237,6 +241,12 @@ int gptq_gemm(const gptq_layer_t *layer, const void *x, void *out, int M,
 /* W_out[K,N] (dtype) = scales[g(k),n] * (w[k,n] - z[g(k),n]); bit-exact vs the reference's
  * `weights` tensor (one rounding of the exact product). */
 int gptq_dequant(const gptq_layer_t *layer, void *W_out, void *stream);
+
+/* dX[M, K] (+)= dY[M, N] . W^T, W = gptq_dequant(layer) exactly; dY / dX in the layer dtype, row-major, on the layer's device.
+ * The layer's epilogue is ignored: dY is the gradient of the product BEFORE any epilogue ([M, N], N = layer->N).  accumulate = 1 adds to dX.
+ * Caller's stream, no allocation, no workspace, capturable in a graph.  GPTQ_ERR_NULL / _SHAPE / _UNSUPPORTED as for gptq_forward
+ * (dy and dx must also be 16-byte aligned).  Products and sums in fp32, one rounding at the store (accumulate: dX + the sum in fp32, one rounding). */
+int gptq_grad_input(const gptq_layer_t *layer, const void *dy, void *dx, int M, int accumulate, void *stream);
 
 /* Integer unpack (bit-exact targets). w_out uint8 [K,N]; z_out int32 [G,N] (zero-point as used). */
 int gptq_unpack_weights(const uint32_t *qweight, int K, int N, int bits, uint8_t *w_out, void *stream);

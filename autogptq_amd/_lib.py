@@ -33,6 +33,7 @@ EXPORTS = (
     "gptq_forward_multi", "gptq_workspace_bytes_multi", "gptq_forward_multi_ex", "gptq_workspace_bytes_multi_ex",
     "gptq_peer_scatter", "gptq_peer_collect", "gptq_peer_gather", "gptq_forward_scatter", "gptq_forward_gather", "gptq_peer_publish",
     "gptq_mlp_forward", "gptq_mlp_forward_ex", "gptq_workspace_bytes_mlp", "gptq_workspace_bytes_mlp_ex", "gptq_describe_mlp_plan",
+    "gptq_moe_table_bytes", "gptq_moe_build_table", "gptq_moe_workspace_bytes", "gptq_moe_forward", "gptq_describe_moe_plan",
 )
 WS_HEADER_BYTES = 65536
 STRIP_COLS = 16          # GPTQ_STRIP_COLS: columns per strip of the decode copy (gptq_prepack_decode)
@@ -52,6 +53,11 @@ class GptqLayer(Structure):
 class GptqTuning(Structure):
     _fields_ = [("lanes_n", c_int32), ("waves", c_int32), ("ksplit", c_int32), ("path", c_int32),
                 ("reserved", c_int32 * 4)]
+
+
+class GptqMoe(Structure):
+    """gptq_moe_t: E experts, each a gate / up / down layer (arrays of E layer pointers)."""
+    _fields_ = [("E", c_int32), ("reserved", c_int32), ("gate", c_void_p), ("up", c_void_p), ("down", c_void_p)]
 
 
 PEER_MAX = 8
@@ -149,6 +155,14 @@ def load() -> ctypes.CDLL:
     lib.gptq_mlp_forward.argtypes = [LP, LP, LP, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]
     lib.gptq_mlp_forward_ex.argtypes = lib.gptq_mlp_forward.argtypes + [POINTER(GptqTuning)]
     lib.gptq_describe_mlp_plan.argtypes = [LP, LP, LP, c_int, POINTER(GptqTuning), c_char_p, c_size_t]
+    MP = POINTER(GptqMoe)
+    lib.gptq_moe_table_bytes.restype = c_size_t
+    lib.gptq_moe_table_bytes.argtypes = [c_int]
+    lib.gptq_moe_build_table.argtypes = [MP, c_void_p, c_void_p]
+    lib.gptq_moe_workspace_bytes.restype = c_size_t
+    lib.gptq_moe_workspace_bytes.argtypes = [MP, c_int, c_int]
+    lib.gptq_moe_forward.argtypes = [MP, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.gptq_describe_moe_plan.argtypes = [MP, c_int, c_int, c_char_p, c_size_t]
     lib.gptq_peer_scatter.argtypes = [POINTER(GptqPeerGroup), c_void_p, c_int, c_int, c_int, c_void_p]
     lib.gptq_peer_collect.argtypes = [POINTER(GptqPeerGroup), c_void_p, c_int, c_int, ctypes.c_uint32, c_void_p]
     lib.gptq_peer_gather.argtypes = [POINTER(GptqPeerGroup), c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_uint32, c_void_p]
@@ -158,7 +172,7 @@ def load() -> ctypes.CDLL:
     for name in EXPORTS:
         if name not in ("gptq_last_error", "gptq_status_string", "gptq_workspace_bytes", "gptq_workspace_bytes_ex",
                         "gptq_workspace_bytes_max", "gptq_workspace_bytes_multi", "gptq_workspace_bytes_multi_ex",
-                        "gptq_workspace_bytes_mlp", "gptq_workspace_bytes_mlp_ex"):
+                        "gptq_workspace_bytes_mlp", "gptq_workspace_bytes_mlp_ex", "gptq_moe_table_bytes", "gptq_moe_workspace_bytes"):
             getattr(lib, name).restype = c_int
     got = lib.gptq_abi_version()
     if got != ABI_VERSION:
@@ -237,6 +251,18 @@ def describe_mlp_plan(gate: "GptqLayer", up: "GptqLayer", down: "GptqLayer", M: 
     buf = ctypes.create_string_buffer(512)
     check(lib.gptq_describe_mlp_plan(ctypes.byref(gate), ctypes.byref(up), ctypes.byref(down), M,
                                      ctypes.byref(tuning) if tuning is not None else None, buf, len(buf)))
+    out = {}
+    for kv in buf.value.decode().split():
+        k, v = kv.split("=", 1)
+        out[k] = int(v) if v.lstrip("-").isdigit() else v
+    return out
+
+
+def describe_moe_plan(moe: "GptqMoe", T: int, topk: int) -> dict:
+    """What gptq_moe_forward would run for (moe, T, topk): path=grouped with its tile geometry, or path=per_expert with the reason (host-only query)."""
+    lib = load()
+    buf = ctypes.create_string_buffer(512)
+    check(lib.gptq_describe_moe_plan(ctypes.byref(moe), T, topk, buf, len(buf)))
     out = {}
     for kv in buf.value.decode().split():
         k, v = kv.split("=", 1)

@@ -780,6 +780,109 @@ int gptq_grad_input(const gptq_layer_t* L, const void* dy, void* dx, int M, int 
     return GPTQ_OK;
 }
 
+// ---- routed mixture-of-experts layers (moe.hip) ----
+static int moe_check_proj(const gptq_layer_t* const* Ls, int E, int K, int N, int dtype, const char* name) {
+    if (!Ls) return fail(GPTQ_ERR_NULL, "moe->%s is NULL", name);
+    for (int e = 0; e < E; ++e) {
+        const gptq_layer_t* L = Ls[e];
+        if (int rc = check_layer(L)) return rc;
+        const gptq_layer_t* A = Ls[0];
+        if (L->K != K || L->N != N)
+            return fail(GPTQ_ERR_SHAPE, "expert %d %s is [%d -> %d], expected [%d -> %d]", e, name, L->K, L->N, K, N);
+        if (L->bits != A->bits || L->group_size != A->group_size || L->dtype != dtype || L->zero_mode != A->zero_mode)
+            return fail(GPTQ_ERR_UNSUPPORTED, "the %s layers of all experts must share bits, group_size, dtype and zero_mode (expert %d differs)", name, e);
+        if (L->bias || L->epilogue != GPTQ_EPI_NONE)
+            return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s: the grouped path takes no bias and no epilogue", e, name);
+        if (L->g_idx && !L->qweight_seq)
+            return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s: raw act-order (no re-sequenced rows) is not taken by the grouped path", e, name);
+    }
+    const gptq_layer_t* A = Ls[0];
+    if (A->bits != 4 && A->bits != 8) return fail(GPTQ_ERR_UNSUPPORTED, "%d-bit experts: the grouped path takes 4 or 8 bits", A->bits);
+    if (A->group_size % 32 && A->group_size < K)
+        return fail(GPTQ_ERR_UNSUPPORTED, "group_size %d: the grouped path takes multiples of 32 (or one group)", A->group_size);
+    return GPTQ_OK;
+}
+
+static int moe_check(const gptq_moe_t* m, int T, int topk) {
+    if (!m) return fail(GPTQ_ERR_NULL, "moe is NULL");
+    if (m->E < 1 || m->E > 256) return fail(GPTQ_ERR_UNSUPPORTED, "E = %d experts: the grouped path takes 1..256", m->E);
+    if (topk < 1 || topk > 8) return fail(GPTQ_ERR_UNSUPPORTED, "topk = %d: the grouped path takes 1..8", topk);
+    if (T < 0) return fail(GPTQ_ERR_SHAPE, "T must be >= 0, got %d", T);
+    if (!m->gate || !m->up || !m->down || !m->gate[0]) return fail(GPTQ_ERR_NULL, "moe->gate / up / down must be non-NULL");
+    const gptq_layer_t* G = m->gate[0];
+    if (int rc = check_layer(G)) return rc;
+    if (G->dtype != GPTQ_F16 && G->dtype != GPTQ_BF16) return fail(GPTQ_ERR_UNSUPPORTED, "fp32 experts: the grouped path takes fp16 / bf16");
+    const int H = G->K, I = G->N;
+    if (H % 64 || I % 64) return fail(GPTQ_ERR_UNSUPPORTED, "hidden (%d) and intermediate (%d) sizes must be multiples of 64", H, I);
+    if ((long)T * topk > 0x3fffffffL / 4) return fail(GPTQ_ERR_SHAPE, "T = %d is too large", T);
+    if (int rc = moe_check_proj(m->gate, m->E, H, I, G->dtype, "gate")) return rc;
+    if (int rc = moe_check_proj(m->up, m->E, H, I, G->dtype, "up")) return rc;
+    const gptq_layer_t* U = m->up[0];
+    if (U->bits != G->bits || U->group_size != G->group_size || U->zero_mode != G->zero_mode)
+        return fail(GPTQ_ERR_UNSUPPORTED, "gate and up layers must share bits, group_size and zero_mode");
+    return moe_check_proj(m->down, m->E, I, H, G->dtype, "down");
+}
+
+size_t gptq_moe_table_bytes(int E) { return E > 0 ? 3 * (size_t)E * moe_table_entry_bytes() : 0; }
+
+int gptq_moe_build_table(const gptq_moe_t* m, void* table, void* stream) {
+    if (int rc = moe_check(m, 0, 1)) return rc;
+    if (!table) return fail(GPTQ_ERR_NULL, "table is NULL");
+    const size_t eb = moe_table_entry_bytes(), E = (size_t)m->E;
+    std::vector<char> host(gptq_moe_table_bytes(m->E));
+    for (size_t e = 0; e < E; ++e) {
+        moe_table_entry(*m->gate[e], host.data() + e * eb);
+        moe_table_entry(*m->up[e], host.data() + (E + e) * eb);
+        moe_table_entry(*m->down[e], host.data() + (2 * E + e) * eb);
+    }
+    hipError_t e = hipMemcpyAsync(table, host.data(), host.size(), hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);      // the host copy dies with this call
+    if (e != hipSuccess) return hip_fail(e, "gptq_moe_build_table copy");
+    return GPTQ_OK;
+}
+
+size_t gptq_moe_workspace_bytes(const gptq_moe_t* m, int T, int topk) {
+    if (moe_check(m, T, topk)) return 0;
+    const gptq_layer_t* G = m->gate[0];
+    return plan_moe(m->E, T, topk, G->K, G->N, G->dtype).bytes;
+}
+
+int gptq_moe_forward(const gptq_moe_t* m, const void* table, const void* x, const int64_t* idx, const float* w, int T, int topk, void* out, void* h_out,
+                     void* ws, size_t ws_bytes, void* stream) {
+    if (int rc = moe_check(m, T, topk)) return rc;
+    if (T == 0) return GPTQ_OK;
+    if (!table || !x || !idx || !w || !out) return fail(GPTQ_ERR_NULL, "table / x / topk_idx / topk_w / out must be non-NULL");
+    if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)ws) & 15) return fail(GPTQ_ERR_UNSUPPORTED, "x / out / workspace must be 16-byte aligned");
+    const gptq_layer_t* G = m->gate[0];
+    const MoePlan pl = plan_moe(m->E, T, topk, G->K, G->N, G->dtype);
+    if (!ws || ws_bytes < pl.bytes) return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", pl.bytes, ws ? ws_bytes : (size_t)0);
+    hipError_t e = launch_moe(*m, table, pl, x, idx, w, T, topk, out, (char*)ws, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "gptq_moe_forward launch");
+    if (h_out) {
+        const size_t R = (size_t)T * topk, hb = R * G->N * dtype_size(G->dtype);
+        e = hipMemcpyAsync(h_out, (char*)ws + pl.off_h, hb, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+        if (e == hipSuccess) e = hipMemcpyAsync((char*)h_out + hb, (char*)ws + pl.off_pos, 4 * R, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+        if (e != hipSuccess) return hip_fail(e, "gptq_moe_forward h_out copy");
+    }
+    return GPTQ_OK;
+}
+
+int gptq_describe_moe_plan(const gptq_moe_t* m, int T, int topk, char* out, size_t out_bytes) {
+    if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out is NULL");
+    if (moe_check(m, T, topk)) {
+        char reason[sizeof(g_err)];
+        snprintf(reason, sizeof(reason), "%s", g_err);
+        for (char* c = reason; *c; ++c)
+            if (*c == ' ' || *c == '=') *c = '_';
+        snprintf(out, out_bytes, "path=per_expert reason=%s", reason);
+        return GPTQ_OK;
+    }
+    const gptq_layer_t* G = m->gate[0];
+    const MoePlan pl = plan_moe(m->E, T, topk, G->K, G->N, G->dtype);
+    snprintf(out, out_bytes, "path=grouped bm=%d bn=%d tiles=%d ksplit=%d launches=%d", pl.bm, pl.bn, pl.tiles, pl.ksplit, T > 0 ? 4 : 0);
+    return GPTQ_OK;
+}
+
 int gptq_unpack_weights(const uint32_t* qweight, int K, int N, int bits, uint8_t* w_out, void* stream) {
     if (!qweight || !w_out) return fail(GPTQ_ERR_NULL, "qweight/w_out must be non-NULL");
     if (!bits_ok(bits)) return fail(GPTQ_ERR_UNSUPPORTED, "Only 2,3,4,8 bits are supported. (got %d)", bits);

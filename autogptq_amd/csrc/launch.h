@@ -176,6 +176,17 @@ hipError_t launch_dequant(const gptq_layer_t& L, void* W_out, hipStream_t st);
 // grad_input.hip: dX (+)= dY . W^T on the packed rows (L.qweight, L.g_idx); BM x 128 output tiles (grad_input_bm: BM = 128 or 64)
 int grad_input_bm(const gptq_layer_t& L, int M);
 hipError_t launch_grad_input(const gptq_layer_t& L, const void* dy, void* dx, int M, int accumulate, hipStream_t st);
+
+// moe.hip: routed mixture-of-experts layers (gptq_moe_forward): routing table, grouped W1 / W3 + silu * mul, grouped W2, combine -- four launches
+struct MoePlan {
+    int bm, bn, tiles, ksplit, steps_per_split;     // tile height, column block, tile bound, K slices of the down projection and their 32-deep steps
+    size_t off_offsets, off_tile_count, off_tiles, off_pos, off_rows, off_h, off_y, bytes;   // workspace layout (from GPTQ_WORKSPACE_HEADER_BYTES on)
+};
+MoePlan plan_moe(int E, int T, int topk, int H, int I, int dtype);
+size_t moe_table_entry_bytes();
+void moe_table_entry(const gptq_layer_t& L, void* dst);
+hipError_t launch_moe(const gptq_moe_t& m, const void* table, const MoePlan& pl, const void* x, const int64_t* idx, const float* w, int T, int topk,
+                      void* out, char* ws, hipStream_t st);
 hipError_t launch_unpack_weights(const uint32_t* qweight, int K, int N, int bits, uint8_t* w_out, hipStream_t st);
 hipError_t launch_unpack_zeros(const uint32_t* qzeros, int G, int N, int bits, int zero_mode, int32_t* z_out, hipStream_t st);
 hipError_t launch_pack_weights(const void* W, const void* scale_in, const void* zero_in, const int32_t* g_idx,

@@ -92,11 +92,24 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
     Memory (the model-level switches for what post_init keeps next to the checkpoint tensors): ``decode_copy=False`` builds no decode copy (1x the packed
     bytes, the round-1..3 kernels); ``release_checkpoint_layout=True`` keeps the copy and moves ``qweight`` of plain layers to pinned host memory (1x on
     the device again; ``state_dict()`` unchanged; row counts whose kernel reads packed rows rebuild them per call into one shared scratch).  Default: both
-    layouts on the device (2x; act-order layers 3x with their re-sequenced rows) -- 288 GB of HBM is what makes that the default."""
+    layouts on the device (2x; act-order layers 3x with their re-sequenced rows) -- 288 GB of HBM is what makes that the default.
+    Mixture-of-experts layers (``QuantMoEExperts``) are post-initialised without a decode copy (1x the packed bytes, + the re-sequenced rows of act-order
+    experts; ``release_checkpoint_layout`` does not apply to them), get their pointer table, and the scratch covers ``gptq_moe_workspace_bytes`` of
+    ``max_input_length`` tokens at the module's ``top_k``."""
+    from .moe import QuantMoEExperts
     rows = max_input_length or 2048
     need: Dict[torch.device, int] = {}
+    in_experts = set()
     for _, sub in model.named_modules():
-        if getattr(sub, "QUANT_TYPE", None) != QuantLinear.QUANT_TYPE:
+        # mixture-of-experts layers: their QuantLinears are post-initialised by the module (no decode copy; a checkpoint-layout release does not apply)
+        if isinstance(sub, QuantMoEExperts) and sub[0].layers()[0].qweight.device.type == "cuda":
+            dev = sub[0].layers()[0].qweight.device
+            sub.post_init()
+            for e in range(sub.num_experts):
+                in_experts.update(id(l) for l in sub[e].layers())
+            need[dev] = max(need.get(dev, 0), sub.workspace_bytes(rows, sub.top_k))
+    for _, sub in model.named_modules():
+        if getattr(sub, "QUANT_TYPE", None) != QuantLinear.QUANT_TYPE or id(sub) in in_experts:
             continue
         if sub.qweight.device.type != "cuda":
             continue
@@ -141,7 +154,8 @@ def load_packed_layers(model: nn.Module, state_dict: Dict[str, torch.Tensor], bi
         if bits != 4:
             raise ValueError("Marlin and AWQ checkpoints are 4-bit")
     probe = "B" if checkpoint_format == "marlin" else "qweight"
-    names = sorted(k[: -len(probe) - 1] for k in state_dict if k.endswith("." + probe))
+    state_dict, expert_names = _load_experts(model, state_dict, bits, group_size, probe, quant_method, checkpoint_format)
+    names = sorted(k[: -len(probe) - 1] for k in state_dict if k.endswith("." + probe) and k[: -len(probe) - 1] not in expert_names)
     linears = find_layers(model)
     missing = [n for n in names if n not in linears]
     if missing:
@@ -176,10 +190,66 @@ def load_packed_layers(model: nn.Module, state_dict: Dict[str, torch.Tensor], bi
             q.bias = state_dict[f"{name}.bias"].to(device=q.bias.device, dtype=q.bias.dtype)
             used.add(f"{name}.bias")
         q._invalidate()
+    used |= {f"{n}.{sfx}" for n in expert_names for sfx in ("qweight", "qzeros", "scales", "g_idx")}
     rest = {k: v for k, v in state_dict.items() if k not in used and not k.endswith(".workspace")}
     if rest:
         model.load_state_dict(rest, strict=False)
     return model
+
+
+_EXPERT_KEY = __import__("re").compile(r"^(.*\.experts)\.(\d+)\.([A-Za-z_0-9]+)$")
+
+
+def _load_experts(model, state_dict, bits, group_size, probe, quant_method, checkpoint_format):
+    """Expert tensors of a mixture-of-experts checkpoint (``<...>.block_sparse_moe.experts.{e}.w1.qweight`` as AutoGPTQ saves Mixtral, or the same under
+    ``.mlp.``, the name transformers 5 gives the block at load time): every MixtralExperts-like module they name becomes a QuantMoEExperts filled from
+    them.  Returns the state dict with ``.block_sparse_moe.`` renamed where the model has no such module, and the set of expert layer names."""
+    from .moe import QuantMoEExperts, _is_dense_experts, make_quant_experts
+    modules = dict(model.named_modules())
+    if not any(".block_sparse_moe." in k for k in modules) and any(".block_sparse_moe." in k for k in state_dict):
+        state_dict = {k.replace(".block_sparse_moe.", ".mlp."): v for k, v in state_dict.items()}
+    groups: dict = {}
+    for k in state_dict:
+        if not k.endswith("." + probe):
+            continue
+        m = _EXPERT_KEY.match(k[: -len(probe) - 1])
+        if m and m.group(1) in modules and (_is_dense_experts(modules[m.group(1)]) or isinstance(modules[m.group(1)], QuantMoEExperts)):
+            groups.setdefault(m.group(1), {}).setdefault(int(m.group(2)), []).append(m.group(3))
+    if groups and (quant_method, checkpoint_format) != ("gptq", "gptq"):
+        raise ValueError("mixture-of-experts layers are loaded from GPTQ-format checkpoints only")
+    expert_names = set()
+    for path, by_e in groups.items():
+        mod = modules[path]
+        names = tuple(sorted(by_e[0])) if 0 in by_e else ()
+        if isinstance(mod, QuantMoEExperts):
+            q = mod
+        else:
+            gate_up = [n for n in names if n in ("w1", "w3", "gate_proj", "up_proj")]
+            if set(names) == {"w1", "w2", "w3"}:
+                order = ("w1", "w3", "w2")
+            elif set(names) == {"gate_proj", "up_proj", "down_proj"}:
+                order = ("gate_proj", "up_proj", "down_proj")
+            else:
+                raise KeyError(f"{path}: expert projections {names} are neither (w1, w3, w2) nor (gate_proj, up_proj, down_proj) ({gate_up})")
+            q = make_quant_experts(model, path, bits, group_size, order)
+        if set(by_e) != set(range(q.num_experts)):
+            raise KeyError(f"{path}: the checkpoint has experts {sorted(by_e)[:8]}..., the model {q.num_experts}")
+        for e in range(q.num_experts):
+            for nm in q.names:
+                name = f"{path}.{e}.{nm}"
+                lin = getattr(q[e], nm)
+                take = lambda suffix: state_dict[f"{name}.{suffix}"]                       # noqa: E731
+                for attr in ("qweight", "qzeros", "scales"):
+                    t, cur = take(attr), getattr(lin, attr)
+                    if tuple(t.shape) != tuple(cur.shape):
+                        raise ValueError(f"{name}.{attr}: checkpoint has shape {tuple(t.shape)}, the layer expects {tuple(cur.shape)}")
+                    setattr(lin, attr, t.to(device=cur.device, dtype=cur.dtype).contiguous())
+                if f"{name}.g_idx" in state_dict:
+                    lin.g_idx = take("g_idx").to(torch.int32).to(lin.g_idx.device)
+                lin._invalidate()
+                expert_names.add(name)
+        q._invalidate()
+    return state_dict, expert_names
 
 
 class DecodeStepGraph:

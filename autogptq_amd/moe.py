@@ -1,0 +1,264 @@
+"""Quantised mixture-of-experts layers: the experts of a Mixtral block (the reference quantises them as per-expert linears,
+``block_sparse_moe.experts.{e}.w1 / w3 / w2``, auto_gptq/modeling/mixtral.py) as ONE routed call into the HIP library.
+
+* ``QuantMoEExperts``   drop-in for a transformers-5 ``MixtralExperts`` (3-D ``gate_up_proj`` / ``down_proj``): same
+                        ``forward(hidden_states, top_k_index, top_k_weights)``; its children are per-expert ``QuantLinear``s whose
+                        state_dict keys are ``<path>.{e}.w1 / w3 / w2.{qweight, qzeros, scales, g_idx}``
+* ``moe_forward``       the grouped path (gptq_moe_forward: routing table, grouped W1 / W3 + silu * mul, grouped W2, combine -- four
+                        launches, no host round trip, capturable), or the per-expert composition of differentiable ``QuantLinear`` calls
+* ``pack_moe_experts``  pack the dense 3-D expert parameters of a model (``quantizers`` keyed ``...mlp.experts.{e}.w1`` as ``pack_model`` takes)
+
+The per-expert composition serves what the grouped kernels do not take (2- / 3-bit or fp32 experts, odd group sizes, raw act-order), CPU tensors (which
+``QuantLinear`` refuses), and calls under grad where ``hidden_states`` or ``top_k_weights`` require grad: training through the experts gets dX and the
+router-weight gradient from the existing backward of ``QuantLinear``.
+"""
+from __future__ import annotations
+
+import ctypes
+import types
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib
+from .qlinear_mi355x import QuantLinear, _raw_stream, exchange_tick, forward_multi, reserve_workspace
+
+DEFAULT_NAMES = ("w1", "w3", "w2")          # gate, up, down (AutoGPTQ's Mixtral names)
+
+
+class _Expert(nn.Module):
+    """One expert: three QuantLinears under the projection names (gate, up, down)."""
+
+    def __init__(self, names, bits, group_size, hidden, inter, weight_dtype, zero_mode):
+        super().__init__()
+        self.names = tuple(names)
+        for nm, (k, n) in zip(self.names, ((hidden, inter), (hidden, inter), (inter, hidden))):
+            self.add_module(nm, QuantLinear(bits, group_size, k, n, False, weight_dtype=weight_dtype, zero_mode=zero_mode))
+
+    def layers(self):
+        return tuple(getattr(self, nm) for nm in self.names)
+
+
+class QuantMoEExperts(nn.Module):
+    """E quantised experts behind the forward of transformers' ``MixtralExperts``: ``out[t] = sum_j w[t, j] * down(silu(gate(x_t)) * up(x_t))`` over the
+    experts ``top_k_index[t, j]`` (indices outside [0, E) are dropped).  ``post_init`` (or ``autogptq_post_init``) prepares the experts' layers without a
+    decode copy and builds the device table of per-expert pointers the grouped kernels read."""
+
+    QUANT_TYPE = "mi355x_moe"
+
+    def __init__(self, num_experts, hidden_dim, intermediate_dim, bits, group_size, top_k=2, weight_dtype=torch.float16, names=DEFAULT_NAMES,
+                 zero_mode="auto"):
+        super().__init__()
+        if len(names) != 3:
+            raise ValueError("names: the (gate, up, down) projection names, e.g. ('w1', 'w3', 'w2')")
+        self.num_experts = num_experts
+        self.hidden_dim = hidden_dim
+        self.intermediate_dim = intermediate_dim
+        self.top_k = top_k
+        self.bits = bits
+        self.names = tuple(names)
+        for e in range(num_experts):
+            self.add_module(str(e), _Expert(self.names, bits, group_size, hidden_dim, intermediate_dim, weight_dtype, zero_mode))
+        self._invalidate()
+
+    def __getitem__(self, e) -> _Expert:
+        return getattr(self, str(e))
+
+    def __len__(self):
+        return self.num_experts
+
+    def _invalidate(self):
+        self._moe = None
+        self._keep = ()
+        self._plans = {}
+        self.last_plan = None
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        self._invalidate()
+        return out
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        super()._load_from_state_dict(*args, **kwargs)
+        self._invalidate()
+
+    def projections(self):
+        """([gate layers], [up layers], [down layers]) in expert order."""
+        ls = [self[e].layers() for e in range(self.num_experts)]
+        return [l[0] for l in ls], [l[1] for l in ls], [l[2] for l in ls]
+
+    # ------------------------------------------------------------------ post_init
+    def post_init(self):
+        """post_init every expert layer WITHOUT a decode copy (1x the packed bytes; act-order layers add their re-sequenced rows) and build the pointer
+        table.  The decode copy is not read by the grouped kernels, and a checkpoint-layout release does not apply to expert layers."""
+        dev = self[0].layers()[0].qweight.device
+        if dev.type != "cuda":
+            raise RuntimeError(f"mi355x QuantMoEExperts.post_init needs the module on a ROCm GPU device (got {dev}); there is no CPU path.")
+        for e in range(self.num_experts):
+            for l in self[e].layers():
+                l.post_init(tiled=False, release_checkpoint_layout=False)
+        lib = _lib.load()
+        gate, up, down = self.projections()
+        arrs = [(ctypes.POINTER(_lib.GptqLayer) * self.num_experts)(*[ctypes.pointer(l._layer) for l in ls]) for ls in (gate, up, down)]
+        m = _lib.GptqMoe()
+        m.E = self.num_experts
+        m.gate, m.up, m.down = (ctypes.addressof(a) for a in arrs)
+        table = torch.zeros(max(1, int(lib.gptq_moe_table_bytes(self.num_experts))), dtype=torch.uint8, device=dev)
+        self._moe, self._keep, self._plans = m, (arrs, table, gate, up, down), {}
+        self._table = table
+        self._dev = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
+        self._w_dtype = gate[0].scales.dtype
+        if self.plan(1, self.top_k)["path"] == "grouped":          # (a declined layer set has no valid table: it runs per expert)
+            with torch.cuda.device(self._dev):
+                _lib.check(lib.gptq_moe_build_table(ctypes.byref(m), table.data_ptr(), _lib.current_stream_handle(self._dev)))
+        return self
+
+    def workspace_bytes(self, T: int, top_k: "int | None" = None) -> int:
+        if self._moe is None:
+            self.post_init()
+        return int(_lib.load().gptq_moe_workspace_bytes(ctypes.byref(self._moe), T, top_k or self.top_k))
+
+    def plan(self, T: int, top_k: "int | None" = None) -> dict:
+        """{"path": "grouped" | "per_expert", "reason": ...} (+ the tile geometry) for T tokens: what moe_forward runs without grad."""
+        top_k = top_k or self.top_k
+        if self[0].layers()[0].qweight.device.type != "cuda":
+            return {"path": "per_expert", "reason": "cpu tensors"}
+        if self._moe is None:
+            self.post_init()
+        key = (T, top_k)
+        d = self._plans.get(key)
+        if d is None:
+            d = _lib.describe_moe_plan(self._moe, T, top_k)
+            d.setdefault("reason", "")
+            if isinstance(d["reason"], str):
+                d["reason"] = d["reason"].replace("_", " ")
+            self._plans[key] = d
+        return dict(d)
+
+    def forward(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor) -> torch.Tensor:
+        return moe_forward(self, hidden_states, top_k_index, top_k_weights)
+
+
+def moe_forward(experts: QuantMoEExperts, x: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor, return_intermediate: bool = False):
+    """``experts(x, top_k_index, top_k_weights)``: x [T, H] (or [..., H]), top_k_index [T, topk] (int64 as torch.topk returns it), top_k_weights [T, topk].
+    The grouped path: one gptq_moe_forward call (workspace from the per-stream scratch, nothing allocated but the output).  ``return_intermediate``:
+    also (H_sorted [T topk, I], pos [T, topk] int32) -- the kernel's silu * mul rows grouped by expert and the row of each assignment (-1: dropped)."""
+    H = experts.hidden_dim
+    lead = x.shape[:-1]
+    x2 = x.reshape(-1, H)
+    T = x2.shape[0]
+    topk = top_k_index.shape[-1] if top_k_index.dim() else 1
+    grad = torch.is_grad_enabled() and (x.requires_grad or top_k_weights.requires_grad)
+    if x.device.type != "cuda":
+        experts.last_plan = {"path": "per_expert", "reason": "cpu tensors"}
+    elif grad:
+        experts.last_plan = {"path": "per_expert", "reason": "grad enabled and hidden_states / top_k_weights require grad"}
+    else:
+        experts.last_plan = experts.plan(T, topk)
+    if experts.last_plan["path"] != "grouped":
+        if return_intermediate:
+            raise RuntimeError(f"moe_forward: return_intermediate needs the grouped path ({experts.last_plan['reason']})")
+        return _per_expert(experts, x2, top_k_index.reshape(T, topk), top_k_weights.reshape(T, topk)).reshape(lead + (H,))
+    dev, w_dtype = experts._dev, experts._w_dtype
+    if x.device != dev:
+        raise RuntimeError(f"mi355x moe_forward: input is on {x.device}, the experts on {dev}")
+    xw = x2.to(w_dtype) if x2.dtype != w_dtype else x2
+    if not xw.is_contiguous():
+        xw = xw.contiguous()
+    idx = top_k_index.reshape(T, topk)
+    if idx.dtype != torch.int64:
+        idx = idx.to(torch.int64)
+    idx = idx.contiguous()
+    w = top_k_weights.reshape(T, topk)
+    if w.dtype != torch.float32:
+        w = w.to(torch.float32)
+    w = w.contiguous()
+    out = torch.empty((T, H), dtype=w_dtype, device=dev)
+    h_out = None
+    if return_intermediate:
+        R, I = T * topk, experts.intermediate_dim
+        es = torch.tensor([], dtype=w_dtype).element_size()
+        h_out = torch.empty(R * I * es + 4 * R, dtype=torch.uint8, device=dev)
+    if T:
+        need = experts._plans.get(("ws", T, topk))
+        if need is None:
+            need = experts._plans[("ws", T, topk)] = experts.workspace_bytes(T, topk)
+        buf = reserve_workspace(dev, need)
+        exchange_tick(dev)
+        idx_dev = experts._dev.index
+        with torch.cuda.device(idx_dev):
+            rc = _lib.load().gptq_moe_forward(ctypes.byref(experts._moe), experts._table.data_ptr(), xw.data_ptr(), idx.data_ptr(), w.data_ptr(), T, topk,
+                                              out.data_ptr(), _lib.ptr(h_out), buf.data_ptr(), buf.numel(), _raw_stream(idx_dev))
+        if rc:
+            _lib.check(rc)
+    res = out.to(x.dtype) if x.dtype != w_dtype else out
+    res = res.reshape(lead + (H,))
+    if not return_intermediate:
+        return res
+    R, I = T * topk, experts.intermediate_dim
+    es = torch.tensor([], dtype=w_dtype).element_size()
+    hs = h_out[:R * I * es].view(w_dtype).view(R, I)
+    pos = h_out[R * I * es:].view(torch.int32).view(T, topk)
+    return res, hs, pos
+
+
+def _per_expert(experts: QuantMoEExperts, x: torch.Tensor, idx: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """The composition of per-expert QuantLinear calls (the shape of transformers' expert loop): differentiable in x and w, host syncs per call."""
+    T, H = x.shape
+    out = torch.zeros((T, H), dtype=torch.float32, device=x.device)
+    for e in range(experts.num_experts):
+        tok, j = torch.where(idx == e)
+        if tok.numel() == 0:
+            continue
+        gate, up, down = experts[e].layers()
+        xs = x[tok]
+        g, u = forward_multi([gate, up], xs)
+        y = down(F.silu(g) * u).float() * w[tok, j, None].float()
+        out = out.index_add(0, tok, y)
+    return out.to(x.dtype)
+
+
+def _is_dense_experts(m: nn.Module) -> bool:
+    gu, dn = getattr(m, "gate_up_proj", None), getattr(m, "down_proj", None)
+    return torch.is_tensor(gu) and torch.is_tensor(dn) and gu.dim() == 3 and dn.dim() == 3 and hasattr(m, "num_experts")
+
+
+def dense_expert_modules(model: nn.Module) -> dict:
+    """{path: module} of the MixtralExperts-like modules (3-D gate_up_proj / down_proj and num_experts) of a model."""
+    return {n: m for n, m in model.named_modules() if _is_dense_experts(m)}
+
+
+def make_quant_experts(model: nn.Module, path: str, bits: int, group_size: int, names=DEFAULT_NAMES) -> QuantMoEExperts:
+    """Swap the dense experts module at ``path`` for a QuantMoEExperts of the same shape (same device and weight dtype) and return it."""
+    from .model_utils import _recurse_setattr
+    m = model.get_submodule(path)
+    E, I2, H = m.gate_up_proj.shape
+    top_k = getattr(getattr(model, "config", None), "num_experts_per_tok", None) or 2
+    q = QuantMoEExperts(E, H, I2 // 2, bits, group_size, top_k=top_k, weight_dtype=m.gate_up_proj.dtype, names=names)
+    q = q.to(m.gate_up_proj.device)
+    _recurse_setattr(model, path, q)
+    return q
+
+
+def pack_moe_experts(model: nn.Module, quantizers: dict, bits: int, group_size: int, desc_act: bool = False, names=DEFAULT_NAMES) -> None:
+    """Quantise the dense experts of ``model`` in place: every MixtralExperts-like module whose experts appear in ``quantizers`` (keyed
+    ``<path>.{e}.<name>``, values ``(quantizer, scale, zero, g_idx)`` as ``pack_model`` takes them) becomes a QuantMoEExperts packed from
+    w1 = gate_up_proj[e, :I], w3 = gate_up_proj[e, I:], w2 = down_proj[e]."""
+    for path, m in list(dense_expert_modules(model).items()):
+        if not any(k.startswith(path + ".") for k in quantizers):
+            continue
+        gu, dn = m.gate_up_proj.data, m.down_proj.data
+        I = gu.shape[1] // 2
+        q = make_quant_experts(model, path, bits, group_size, names)
+        for e in range(q.num_experts):
+            for nm, W in zip(names, (gu[e, :I], gu[e, I:], dn[e])):
+                key = f"{path}.{e}.{nm}"
+                if key not in quantizers:
+                    raise KeyError(f"pack_moe_experts: no quantizer for {key}")
+                _, scale, zero, g_idx = quantizers[key]
+                getattr(q[e], nm).pack(types.SimpleNamespace(weight=W, bias=None), scale, zero, g_idx)
+        q._invalidate()
+
+
+__all__ = ["QuantMoEExperts", "moe_forward", "pack_moe_experts", "dense_expert_modules", "make_quant_experts"]

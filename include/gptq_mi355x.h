@@ -15,6 +15,8 @@
  *       and the pure-PyTorch fallback they all share                  auto_gptq/nn_modules/qlinear/qlinear_cuda_old.py:291-355, qlinear_cuda.py:253-317
  *   gptq_dequant
  *       <- the `reconstruct` step of exllama / exllamav2              exllama/cuda_func/q4_matrix.cu:171-225, exllamav2/cuda/q_matrix.cu:158-279,452-500
+ *   gptq_moe_forward
+ *       <- the expert loop of the reference's Mixtral (per-expert QuantLinears, auto_gptq/modeling/mixtral.py) as one routed, grouped call
  *   gptq_grad_input
  *       <- the backward of the reference's training route: dequantise + torch.matmul under autograd
  *                                                                     qlinear_cuda_old.py:291-355, qlinear_cuda.py:253-317
@@ -247,6 +249,39 @@ int gptq_dequant(const gptq_layer_t *layer, void *W_out, void *stream);
  * Caller's stream, no allocation, no workspace, capturable in a graph.  GPTQ_ERR_NULL / _SHAPE / _UNSUPPORTED as for gptq_forward
  * (dy and dx must also be 16-byte aligned).  Products and sums in fp32, one rounding at the store (accumulate: dX + the sum in fp32, one rounding). */
 int gptq_grad_input(const gptq_layer_t *layer, const void *dy, void *dx, int M, int accumulate, void *stream);
+
+/* Routed mixture-of-experts layer (the experts of a Mixtral block: auto_gptq/modeling/mixtral.py, block_sparse_moe.experts.{e}.w1 / w3 / w2).  E experts,
+ * each three plain layers: gate (w1) and up (w3) [H -> I], down (w2) [I -> H].  For token t and its topk assignments (t, j) to experts
+ * e = topk_idx[t, j] (int64, the dtype of torch.topk; values outside [0, E) are dropped):
+ *   h = T(silu(x_t . W1_e) * (x_t . W3_e))   fp32 sums and silu, one rounding;   out[t] = T(sum_j topk_w[t, j] * (h . W2_e))   fp32, ascending j, one rounding
+ * (a token with no valid expert gets 0).  Every W is gptq_dequant of its layer, bit for bit.  Grouped path: 4- or 8-bit fp16 / bf16 experts, group_size a
+ * multiple of 32 (or >= K), plain or act-order with qweight_seq / perm (re-sequenced rows), H and I multiples of 64, no bias, no epilogue, E <= 256,
+ * topk <= 8; all experts of one projection share K, N, bits, group_size, dtype and zero_mode, and gate / up share them too.  Anything else:
+ * GPTQ_ERR_UNSUPPORTED with the reason (the caller composes the layer from per-expert gptq_forward calls instead). */
+typedef struct gptq_moe_t {
+    int32_t E;
+    int32_t reserved;                  /* 0 */
+    const gptq_layer_t *const *gate;   /* [E] */
+    const gptq_layer_t *const *up;     /* [E] */
+    const gptq_layer_t *const *down;   /* [E] */
+} gptq_moe_t;
+/* The device table of per-expert pointers the kernels read (the launch arguments cannot hold E x 12 pointers): built once (post_init) into
+ * gptq_moe_table_bytes(E) caller-owned device bytes; it synchronises `stream` (not capturable).  Rebuild it whenever a layer's buffers move. */
+size_t gptq_moe_table_bytes(int E);
+int gptq_moe_build_table(const gptq_moe_t *moe, void *table, void *stream);
+/* Workspace of one call with T tokens:  GPTQ_WORKSPACE_HEADER_BYTES (left untouched: a workspace shared with the other entry points keeps its header)
+ *   + a256(4 (E + 1)) + 256 + a256(16 tiles) + 2 a256(4 T topk) + a256(T topk I sizeof(T)) + a256(4 ksplit T topk H),   a256 = round up to 256;
+ * tiles = floor(T topk / bm) + min(E, T topk) and bm / ksplit as gptq_describe_moe_plan reports them.  0 when the call is declined. */
+size_t gptq_moe_workspace_bytes(const gptq_moe_t *moe, int T, int topk);
+/* out[T, H] (layer dtype).  x [T, H] layer dtype, topk_idx [T, topk] int64, topk_w [T, topk] fp32, all contiguous, 16-byte aligned, on the experts' device.
+ * h_out (optional, for tests): the sorted intermediate H_sorted [T topk, I] (layer dtype; rows grouped by expert in ascending order, each expert's rows in
+ * the order of their assignments t topk + j) followed by pos [T, topk] int32 (the row of assignment (t, j), or -1), copied in stream order.
+ * Four launches on the caller's stream, no allocation, no synchronisation, legal inside hipGraph capture; T = 0 launches nothing. */
+int gptq_moe_forward(const gptq_moe_t *moe, const void *table, const void *x, const int64_t *topk_idx, const float *topk_w, int T, int topk, void *out,
+                     void *h_out, void *workspace, size_t workspace_bytes, void *stream);
+/* Host-only: "path=grouped bm=16 bn=64 tiles=2 ksplit=4 launches=4" or "path=per_expert reason=...", for (moe, T, topk).  GPTQ_OK either way
+ * (GPTQ_ERR_NULL for a NULL out). */
+int gptq_describe_moe_plan(const gptq_moe_t *moe, int T, int topk, char *out, size_t out_bytes);
 
 /* Integer unpack (bit-exact targets). w_out uint8 [K,N]; z_out int32 [G,N] (zero-point as used). */
 int gptq_unpack_weights(const uint32_t *qweight, int K, int N, int bits, uint8_t *w_out, void *stream);

@@ -40,6 +40,40 @@ template <int LN> __device__ __forceinline__ float row_slot_sum(float v) {
     return v;
 }
 
+// The same two last steps for the tail of a kernel whose lanes 0..15 alone go on (gemv_tiled_kernel): (v + v[l ^ 16]) + (the same of l ^ 32), the association of
+// the two shuffles, through the gfx950 row / half swaps -- register to register, where __shfl_xor is a ds_bpermute_b32: an LDS round trip behind index arithmetic.
+__device__ __forceinline__ float kslot_sum_swap(float v) {
+    const unsigned u = __builtin_bit_cast(unsigned, v);
+    const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);         // [0]: rows 0 0 2 2 of v, [1]: rows 1 1 3 3
+    const unsigned a0 = a[0], a1 = a[1];                                          // (scalars first: __builtin_bit_cast applied to a[1] itself reads element 0 -- hipcc of ROCm 7.2)
+    const unsigned s = as_u32(as_f32(a0) + as_f32(a1));
+    const auto b = __builtin_amdgcn_permlane32_swap(s, s, false, false);         // [0]: the low half of s twice, [1]: the high half twice
+    const unsigned b0 = b[0], b1 = b[1];
+    return as_f32(b0) + as_f32(b1);
+}
+// Cross-wave sums of one entry of the LDS slabs (r[w * STRIDE] = the partial of wave w), the wave count known where the code is generated: every read is issued
+// before the first add -- ONE LDS round trip, no run-time loop.  tree_sum: the xor tree of stream_finish -- (0,1) (2,3) .., then pairs of pairs; seq_sum: waves in
+// ascending order from 0.f (the multi-strip and pair forms).  Same pairs in the same order as the run-time loops they replace: the same bits.
+template <int WN, int STRIDE> __device__ __forceinline__ float tree_sum(const float* r) {
+    float a[WN];
+#pragma unroll
+    for (int w = 0; w < WN; ++w) a[w] = r[w * STRIDE];
+#pragma unroll
+    for (int off = 1; off < WN; off <<= 1)
+#pragma unroll
+        for (int i = 0; i < WN; i += 2 * off) a[i] += a[i + off];
+    return a[0];
+}
+template <int WN, int STRIDE> __device__ __forceinline__ float seq_sum(const float* r) {
+    float a[WN];
+#pragma unroll
+    for (int w = 0; w < WN; ++w) a[w] = r[w * STRIDE];
+    float t = 0.f;
+#pragma unroll
+    for (int w = 0; w < WN; ++w) t += a[w];
+    return t;
+}
+
 // 4x4x4 matrix-core step on packed 2-byte operands (u32x2 = 4 values) for both fp16 and bf16
 template <typename T> struct Mma4;
 template <> struct Mma4<f16> {

@@ -26,7 +26,8 @@
 //   * per chunk and lane: 16 bytes of weights (registers, nontemporal), x fragments by 4 ds_read_b128 (lane i of a 4-lane group reads x row i: the A
 //     operand of v_mfma_f32_4x4x4), scale + zero-point by ds_read_u16 / ds_read_u8; w - z exactly in packed fp16, 8 matrix-core steps into one fp32
 //     group sum, times the scale: the arithmetic of every other decode kernel here (one-hot rows return the reference's exact scales * (w - z));
-//   * a lane owns ONE column: k-slots by two shuffles, waves through LDS, K slices through {fp32, tag} granules (stream_finish, gemv_shared.cuh);
+//   * a lane owns ONE column: k-slots by two register swaps, waves through LDS in one round trip (a launch without K slices ends in straight-line code:
+//     gemv_tiled_kernel.cuh), K slices through {fp32, tag} granules in a cold block (stream_finish, gemv_shared.cuh);
 //   * up to four layers that share x in one launch (gptq_forward_multi).
 #include "gemv_tiled_kernel.cuh"
 
@@ -237,6 +238,12 @@ hipError_t launch_tiled(const gptq_layer_t* const* Ls, const TiledPlan& pl, cons
     p.gran = (unsigned long long*)ws_body;
     p.epochs = ws_header ? (unsigned*)((char*)ws_header + WS_HEADER_EPOCH_OFFSET) : nullptr;
     p.err = ws_header ? (unsigned*)((char*)ws_header + WS_HEADER_BYTES - WS_HEADER_TAIL_BYTES) + 2 : nullptr;
+#ifdef GPTQ_TILED_STAMPS                                                          // lab (gemv_tiled_kernel.cuh): unsplit launches write their wave stamps where the tool says
+    if (pl.ksplit == 1) {
+        const char* const e = getenv("GPTQ_TILED_STAMPS_PTR");
+        p.gran = e ? (unsigned long long*)strtoull(e, nullptr, 0) : nullptr;
+    }
+#endif
     p.max_spins = 1u << 20;
     p.nseg = pl.nseg; p.M = M; p.K = A.K;
     p.chunks = pl.chunks_total; p.chunks_per_split = pl.chunks_per_split; p.ksplit = pl.ksplit;

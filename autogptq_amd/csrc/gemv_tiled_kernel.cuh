@@ -53,6 +53,20 @@ template <> struct TiledFmt<8> { static constexpr int WPL = 4, KPL = 16, REC = 6
 template <> struct TiledFmt<3> { static constexpr int WPL = 3, KPL = 32, REC = 48, ZB = 1; };
 template <> struct TiledFmt<2> { static constexpr int WPL = 2, KPL = 32, REC = 48, ZB = 1; };      // (round 6) 2 words = 32 k; word w: pair p = (k 16w + 2p, k 16w + 2p + 1) at bit 2p of its halves
 
+// Lab (tools/ab_tiled.sh STAMPS -DGPTQ_TILED_STAMPS -> tools/libgptq_STAMPS.so, read by tools/tail_timeline.py; never in the product library): every wave of four
+// workgroups of an unsplit launch keeps s_memtime (shader cycles; a per-XCD counter: only differences on one wave's own clock mean anything) at 0 entry,
+// 1 first weight loads issued, 2 staging barrier passed, 3 last weight chunk landed, 4 K loop left, 5 reduction barrier passed, 6 output store issued,
+// and s_memrealtime (100 MHz) at entry and exit for the clock; lane 0 writes them with ordinary vector stores to the buffer the lab launch code puts in p.gran.
+#ifdef GPTQ_TILED_STAMPS
+#define TILED_STAMP(i) (st_[i] = __builtin_amdgcn_s_memtime() | vz_)          /* (| a zero the compiler cannot see: the stamp is a vector value from the start -- kept scalar across divergent code, hipcc of ROCm 7.2 ends in "illegal VGPR to SGPR copy") */
+#define TILED_STAMPS_OUT() stamps_out()
+#define TILED_HOT_END() return                                                    /* (the stamp stores in front of an s_endpgm in the middle of the kernel: hipcc of ROCm 7.2 fails in the backend) */
+#else
+#define TILED_HOT_END() __builtin_amdgcn_endpgm()
+#define TILED_STAMP(i) ((void)0)
+#define TILED_STAMPS_OUT() ((void)0)
+#endif
+
 template <int N_> struct WordsOf { typedef unsigned type __attribute__((ext_vector_type(N_))); };
 
 // XM = 1 (ACT): an act-order layer -- the decode copy holds the re-sequenced rows (position i = original k perm[i], groups in sequence); the workgroup DMAs the raw
@@ -61,6 +75,23 @@ template <int N_> struct WordsOf { typedef unsigned type __attribute__((ext_vect
 // removed (20.6 against 20.0 us per Llama-7B MLP: every workgroup repeats the activation); not kept.)
 template <int BITS, int MT, int U, typename T, int MAXW, int XM = 0, int ZM2 = 0>
 __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kernel(TiledParams p) {
+#ifdef GPTQ_TILED_STAMPS
+    unsigned long long st_[9] = {};
+    unsigned vz_;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(vz_));
+    st_[7] = __builtin_amdgcn_s_memrealtime() | vz_;
+    TILED_STAMP(0);
+    auto stamps_out = [&]() {
+        st_[8] = __builtin_amdgcn_s_memrealtime() | vz_;
+        unsigned long long* const dbg = p.gran;
+        const int b = (int)blockIdx.x, nb = (int)gridDim.x;
+        const int slot = b == 0 ? 0 : (b == 1 ? 1 : (b == nb / 2 ? 2 : (b == nb - 1 ? 3 : -1)));
+        if (dbg != nullptr && p.ksplit == 1 && slot >= 0 && (threadIdx.x & 63) == 0) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) dbg[(slot * 16 + (int)(threadIdx.x >> 6)) * 16 + i] = st_[i];
+        }
+    };
+#endif
     constexpr bool BF = std::is_same_v<T, bf16>;
     constexpr bool ACT = XM == 1, PEER = XM == 3;          // 3: plain staging + the tensor-parallel epilogue (gemv_tiled_peer.hip)
     // XM = 4 (PAIR, round 5): a [gate | up] layer with the SILU_MUL epilogue (the reference's fused MLP: auto_gptq/nn_modules/fused_llama_mlp.py:131-306).  A
@@ -106,7 +137,15 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
     const int s = (sidx >= be0) + (sidx >= be1) + (sidx >= be2);                  // scalar compares on entry-loaded words
     const TiledSeg sg = p.seg[s];                                                 // one dependent kernarg load
     const int strip = sidx - (s == 0 ? 0 : (s == 1 ? be0 : (s == 2 ? be1 : be2)));
-    const int N = sg.N;
+    // what the tail needs of the layer stays in SGPRs from here on (pinned like the entry batch: left to itself the compiler fetches these words from the
+    // kernel-argument segment again BEHIND the K loop -- a dependent scalar-load round trip in front of the store)
+    int N = sg.N;
+    const void* biasp = sg.bias;
+    void* outp = sg.out;
+    asm volatile("" : "+s"(N), "+s"(biasp), "+s"(outp));
+    typedef __attribute__((address_space(1))) T gT;                               // (behind the asm the compiler no longer knows that these are global pointers)
+    const gT* const biasg = (const gT*)biasp;
+    gT* const outg = (gT*)outp;
     const int Wh = NSTR == 4 ? (W >> 2) : (NSTR == 2 ? (W >> 1) : W);             // waves per strip
     const int sel = NSTR == 1 ? 0 : ((wave >= Wh ? 1 : 0) + (NSTR == 4 ? (wave >= 2 * Wh ? 1 : 0) + (wave >= 3 * Wh ? 1 : 0) : 0));      // which of the workgroup's strips (wave-uniform); PAIR: 0 = gate, 1 = up
     const int wv = NSTR == 1 ? wave : wave - sel * Wh;
@@ -300,6 +339,11 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
             return __builtin_bit_cast(unsigned, hv);
         }
     };
+    // the output this thread writes behind an unsplit launch's cross-wave sum (entry = tid: strip of the workgroup, row, column) and its bias, requested in the
+    // first pass -- in flight under the whole K loop, not a global round trip behind the last chunk
+    constexpr int E = MT * 16, NE = (MULTI ? NSTR : 1) * E;
+    const int n_t = (MULTI ? strip * NSTR + tid / E : strip) * 16 + (tid & 15);
+    float bv0 = 0.f, bv1 = 0.f;
     bool staged = false;
     for (int cbase = cb; cbase < ce; cbase += Wh * U) {
         const int c0 = cbase + wv * U;
@@ -307,6 +351,7 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
 #pragma unroll
         for (int j = 0; j < U; ++j) q[j] = __builtin_nontemporal_load((const qvec*)(tb + ((unsigned)min(c0 + j, ce - 1) * (unsigned)CHB + t_lane)));
         if (!staged) {                                                            // first pass only (uniform): the staging DMAs are OLDER than the U loads just issued
+            TILED_STAMP(1);
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(U) : "memory");
             if constexpr (ACT) {
                 __syncthreads();                                                  // the raw rows (every wave's DMAs) are in the LDS
@@ -315,8 +360,16 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
             __syncthreads();
             if constexpr (XC) x_to_f16();
             if constexpr (XS) x_sums();
+            if (biasp != nullptr && tid < NE && n_t < (PAIR ? N >> 1 : N)) {
+                bv0 = DType<T>::to_f32(biasg[n_t]);
+                if constexpr (PAIR) bv1 = DType<T>::to_f32(biasg[n_t + (N >> 1)]);
+            }
+            TILED_STAMP(2);
             staged = true;
         }
+#ifdef GPTQ_TILED_STAMPS
+        if (cbase + Wh * U >= ce) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); TILED_STAMP(3); }      // the last pass's chunks have landed
+#endif
 #pragma unroll
         for (int j = 0; j < U; ++j) {
             const int cc = min(c0 + j, ce - 1);
@@ -440,38 +493,64 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
             }
         }
     }
-    // ---- k-slots (two shuffles: a lane owns one column), waves (LDS), then write / publish ---------------------------------------------------
+    TILED_STAMP(4);
+    // ---- k-slots (two register swaps: a lane owns one column), waves (LDS), then write / publish ---------------------------------------------
 #pragma unroll
-    for (int m = 0; m < MT; ++m) {
-        float v = acc[m];
-        v += __shfl_xor(v, 16, 64);
-        v += __shfl_xor(v, 32, 64);
-        acc[m] = v;
-    }
+    for (int m = 0; m < MT; ++m) acc[m] = kslot_sum_swap(acc[m]);
     if (!staged) __syncthreads();                                                 // (an empty slice never took the staging barrier; the planner makes none)
     if (lane < 16) {
 #pragma unroll
         for (int m = 0; m < MT; ++m) red[wave * ES + m * 16 + lane] = acc[m];
     }
     __syncthreads();
+    TILED_STAMP(5);
+    // Behind this barrier an unsplit launch is straight-line code: the threads that own an output read its W partials in one LDS round trip (wave count known
+    // at compile time in each arm: tree_sum / seq_sum, the association of the loops they replace), add the bias that has been in a register since the first
+    // pass, and store through pointers held in SGPRs since entry -- no kernel-argument load, no shuffle, no second barrier.  Other wave counts (a forced
+    // geometry, a very short K) keep the run-time loops.
     if constexpr (PAIR) {
         // entry e = (row m, column c): gate = the sum over the first half of the waves, up = over the second half (fixed order), SiLU on the fp32 sum --
         // the arithmetic of the fused GEMV epilogue of rounds 1-3 (gemv.hip) and, up to the one rounding it saves, of silu_mul_kernel (utils.hip)
         const int NH = N >> 1;
-        if (tid < MT * 16) {
-            const int m = tid >> 4, c = tid & 15, n = strip * 16 + c;
+        if (tid < E) {
+            const int m = tid >> 4;
+            const float* const r = red + tid;
             float s0 = 0.f, s1 = 0.f;
-            for (int w = 0; w < Wh; ++w) { s0 += red[w * ES + tid]; s1 += red[(Wh + w) * ES + tid]; }
-            if (m < Mrows && n < NH) {
-                if (sg.bias) { s0 += DType<T>::to_f32(((const T*)sg.bias)[n]); s1 += DType<T>::to_f32(((const T*)sg.bias)[n + NH]); }
+            if (Wh == 4) { s0 = seq_sum<4, ES>(r); s1 = seq_sum<4, ES>(r + 4 * ES); }
+            else if (MAXW == 16 && Wh == 8) { s0 = seq_sum<8, ES>(r); s1 = seq_sum<8, ES>(r + 8 * ES); }
+            else if (Wh == 2) { s0 = seq_sum<2, ES>(r); s1 = seq_sum<2, ES>(r + 2 * ES); }
+            else for (int w = 0; w < Wh; ++w) { s0 += r[w * ES]; s1 += r[(Wh + w) * ES]; }
+            if (m < Mrows && n_t < NH) {
+                if (biasp != nullptr) { s0 += bv0; s1 += bv1; }
                 const float g = s0 / (1.f + __expf(-s0));
-                ((T*)sg.out)[(size_t)m * NH + n] = DType<T>::from_f32(g * s1);
+                outg[(size_t)m * NH + n_t] = DType<T>::from_f32(g * s1);
             }
         }
+        TILED_STAMP(6);
+        TILED_STAMPS_OUT();
         return;
     }
     if constexpr (MULTI) {
         // per strip: the sum over its group of waves (fixed order), bias, one rounding
+        const bool lean = (NE <= W * 64) & ((((MAXW == 16 ? 0x114u : 0x14u) >> (Wh & 31)) & 1u) != 0u);      // 2, 4 or 8 waves per strip, a thread per output
+        if (__builtin_expect(lean, 1)) {
+            if (tid < NE) {
+                const int s4 = tid / E, r = tid & (E - 1), m = r >> 4;
+                float t;
+                constexpr int WHOT = (XM == 6 && MT <= 2) ? 2 : 4;                // the planner's: 4 waves x 2 strips at 1 - 2 rows (K <= 7168), else 4 waves per strip
+                if (__builtin_expect(Wh == WHOT, 1)) t = seq_sum<WHOT, ES>(red + s4 * WHOT * ES + r);
+                else if (Wh == 6 - WHOT) t = seq_sum<6 - WHOT, ES>(red + s4 * (6 - WHOT) * ES + r);
+                else if constexpr (MAXW == 16) t = seq_sum<8, ES>(red + s4 * 8 * ES + r);
+                else t = 0.f;                                                     // (not reached)
+                if (m < Mrows && n_t < N) {
+                    if (biasp != nullptr) t += bv0;
+                    outg[(size_t)m * N + n_t] = DType<T>::from_f32(t);
+                }
+            }
+            TILED_STAMP(6);
+            TILED_STAMPS_OUT();
+            TILED_HOT_END();
+        }
         for (int e = tid; e < NSTR * MT * 16; e += W * 64) {
             const int s4 = e / (MT * 16), r = e - s4 * (MT * 16), m = r >> 4, c = r & 15, n = (strip * NSTR + s4) * 16 + c;
             float t = 0.f;
@@ -482,6 +561,29 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
             }
         }
         return;
+    }
+    if constexpr (!PEER) {
+        // launches without K slices (every launch of the Llama decode step): the hot tail ends here; K slices (granules, epochs, bounded polling) and the other
+        // wave counts are the cold block behind it -- one uniform branch on words loaded at entry
+        const bool lean = (ksplit == 1) & ((((MAXW == 16 ? 0x10110u : 0x110u) >> (W & 31)) & 1u) != 0u);      // 4, 8 or 16 waves: one scalar test
+        if (__builtin_expect(lean, 1)) {
+            if (tid < E) {
+                const int m = tid >> 4;
+                const float* const r = red + tid;
+                float t;
+                constexpr int WHOT = MAXW == 16 ? 16 : 4;                         // the planner's usual geometry of this compilation first: 16 waves x 2 chunks (up to 256
+                if (__builtin_expect(W == WHOT, 1)) t = tree_sum<WHOT, ES>(r);    // workgroups), 4 waves x 4 chunks (more than 512)
+                else if (MAXW == 8 || W == 8) t = tree_sum<8, ES>(r);
+                else t = tree_sum<4, ES>(r);
+                if (m < Mrows && n_t < N) {
+                    if (biasp != nullptr) t += bv0;
+                    outg[(size_t)m * N + n_t] = DType<T>::from_f32(t);
+                }
+            }
+            TILED_STAMP(6);
+            TILED_STAMPS_OUT();
+            TILED_HOT_END();                                            // the hot s_endpgm: not a jump over the cold block to a shared return
+        }
     }
     T* const stage = PEER ? (T*)xs : nullptr;                                      // the staged x is dead behind the barrier above
     stream_finish<16, MT, T, TiledParams, TiledSeg>(p, sg, strip, sidx, ks, N, red, stage);

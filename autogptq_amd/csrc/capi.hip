@@ -301,6 +301,7 @@ int gptq_init(void) {
     if (e == hipSuccess) e = init_gemm_wide_sk_device();
     if (e == hipSuccess) e = init_gemm_rows_device();
     if (e == hipSuccess) e = init_gemm_panel_device();
+    if (e == hipSuccess) e = init_moe_decode_device();
     if (e != hipSuccess) return hip_fail(e, "gptq_init (hipFuncSetAttribute)");
     return GPTQ_OK;
 }
@@ -880,6 +881,109 @@ int gptq_describe_moe_plan(const gptq_moe_t* m, int T, int topk, char* out, size
     const gptq_layer_t* G = m->gate[0];
     const MoePlan pl = plan_moe(m->E, T, topk, G->K, G->N, G->dtype);
     snprintf(out, out_bytes, "path=grouped bm=%d bn=%d tiles=%d ksplit=%d launches=%d", pl.bm, pl.bn, pl.tiles, pl.ksplit, T > 0 ? 4 : 0);
+    return GPTQ_OK;
+}
+
+// ---- the same layers at 1..4 tokens on the experts' decode copy (moe_decode.hip) ----
+static int moe_decode_check_proj(const gptq_layer_t* const* Ls, int E, int K, int N, const gptq_layer_t* A, const char* name) {
+    if (!Ls) return fail(GPTQ_ERR_NULL, "moe->%s is NULL", name);
+    for (int e = 0; e < E; ++e) {
+        const gptq_layer_t* L = Ls[e];
+        if (int rc = check_layer(L)) return rc;
+        if (L->K != K || L->N != N)
+            return fail(GPTQ_ERR_SHAPE, "expert %d %s is [%d -> %d], expected [%d -> %d]", e, name, L->K, L->N, K, N);
+        if (L->bits != A->bits || L->group_size != Ls[0]->group_size || L->dtype != A->dtype || L->zero_mode != Ls[0]->zero_mode)
+            return fail(GPTQ_ERR_UNSUPPORTED, "the %s layers of all experts must share bits, group_size, dtype and zero_mode (expert %d differs)", name, e);
+        if (L->bias || L->epilogue != GPTQ_EPI_NONE)
+            return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s: the decode path takes no bias and no epilogue", e, name);
+        if (!L->qweight_tiled || !L->qconst_tiled)
+            return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s carries no decode copy (QuantMoEExperts.post_init(decode_copy=True) builds it)", e, name);
+        if (!tiled_layer_ok(*L))
+            return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s: group_size %d (or raw act-order) is not taken by the decode copy", e, name, L->group_size);
+    }
+    return GPTQ_OK;
+}
+
+static int moe_decode_check(const gptq_moe_t* m, int T, int topk) {
+    if (!m) return fail(GPTQ_ERR_NULL, "moe is NULL");
+    if (m->E < 1 || m->E > 256) return fail(GPTQ_ERR_UNSUPPORTED, "E = %d experts: the decode path takes 1..256", m->E);
+    if (topk < 1 || topk > 8) return fail(GPTQ_ERR_UNSUPPORTED, "topk = %d: the decode path takes 1..8", topk);
+    if (T < 0) return fail(GPTQ_ERR_SHAPE, "T must be >= 0, got %d", T);
+    if (T > 4) return fail(GPTQ_ERR_UNSUPPORTED, "T = %d tokens: the decode path takes 1..4 (the grouped path serves more)", T);
+    if (!m->gate || !m->up || !m->down || !m->gate[0]) return fail(GPTQ_ERR_NULL, "moe->gate / up / down must be non-NULL");
+    const gptq_layer_t* G = m->gate[0];
+    if (int rc = check_layer(G)) return rc;
+    if (G->dtype != GPTQ_F16 && G->dtype != GPTQ_BF16) return fail(GPTQ_ERR_UNSUPPORTED, "fp32 experts: the decode path takes fp16 / bf16");
+    if (G->bits != 4 && G->bits != 8) return fail(GPTQ_ERR_UNSUPPORTED, "%d-bit experts: the decode path takes 4 or 8 bits", G->bits);
+    const int H = G->K, I = G->N;
+    if (H % 64 || I % 64) return fail(GPTQ_ERR_UNSUPPORTED, "hidden (%d) and intermediate (%d) sizes must be multiples of 64", H, I);
+    if (int rc = moe_decode_check_proj(m->gate, m->E, H, I, G, "gate")) return rc;
+    if (int rc = moe_decode_check_proj(m->up, m->E, H, I, G, "up")) return rc;
+    const gptq_layer_t* U = m->up[0];
+    if (U->group_size != G->group_size || U->zero_mode != G->zero_mode)
+        return fail(GPTQ_ERR_UNSUPPORTED, "gate and up layers must share bits, group_size and zero_mode");
+    if (int rc = moe_decode_check_proj(m->down, m->E, I, H, G, "down")) return rc;
+    const MoeDecodePlan pl = plan_moe_decode(*m, T, topk);
+    if (!pl.ok) return fail(GPTQ_ERR_UNSUPPORTED, "hidden (%d) / intermediate (%d) sizes: the staged row and constants (%d / %d bytes) do not fit the LDS", H, I, pl.lds_pair, pl.lds_down);
+    return GPTQ_OK;
+}
+
+size_t gptq_moe_decode_table_bytes(int E) { return E > 0 ? 3 * (size_t)E * moe_decode_table_entry_bytes() : 0; }
+
+int gptq_moe_build_decode_table(const gptq_moe_t* m, void* table, void* stream) {
+    if (int rc = moe_decode_check(m, 0, 1)) return rc;
+    if (!table) return fail(GPTQ_ERR_NULL, "table is NULL");
+    const size_t eb = moe_decode_table_entry_bytes(), E = (size_t)m->E;
+    std::vector<char> host(gptq_moe_decode_table_bytes(m->E));
+    for (size_t e = 0; e < E; ++e) {
+        moe_decode_table_entry(*m->gate[e], host.data() + e * eb);
+        moe_decode_table_entry(*m->up[e], host.data() + (E + e) * eb);
+        moe_decode_table_entry(*m->down[e], host.data() + (2 * E + e) * eb);
+    }
+    hipError_t e = hipMemcpyAsync(table, host.data(), host.size(), hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);      // the host copy dies with this call
+    if (e != hipSuccess) return hip_fail(e, "gptq_moe_build_decode_table copy");
+    return GPTQ_OK;
+}
+
+size_t gptq_moe_decode_workspace_bytes(const gptq_moe_t* m, int T, int topk) {
+    if (moe_decode_check(m, T, topk)) return 0;
+    return plan_moe_decode(*m, T, topk).bytes;
+}
+
+int gptq_moe_decode_forward(const gptq_moe_t* m, const void* table, const void* x, const int64_t* idx, const float* w, int T, int topk, void* out, void* h_out,
+                            void* ws, size_t ws_bytes, void* stream) {
+    if (int rc = moe_decode_check(m, T, topk)) return rc;
+    if (T == 0) return GPTQ_OK;
+    if (!table || !x || !idx || !w || !out) return fail(GPTQ_ERR_NULL, "table / x / topk_idx / topk_w / out must be non-NULL");
+    if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)ws) & 15) return fail(GPTQ_ERR_UNSUPPORTED, "x / out / workspace must be 16-byte aligned");
+    const MoeDecodePlan pl = plan_moe_decode(*m, T, topk);
+    if (!ws || ws_bytes < pl.bytes) return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", pl.bytes, ws ? ws_bytes : (size_t)0);
+    hipError_t e = launch_moe_decode(*m, table, pl, x, idx, w, T, topk, out, (char*)ws, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "gptq_moe_decode_forward launch (was gptq_init() called on this device?)");
+    if (h_out) {
+        const gptq_layer_t* G = m->gate[0];
+        const size_t R = (size_t)T * topk, hb = R * G->N * dtype_size(G->dtype);
+        e = hipMemcpyAsync(h_out, (char*)ws + pl.off_h, hb, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+        if (e == hipSuccess) e = hipMemcpyAsync((char*)h_out + hb, (char*)ws + pl.off_pos, 4 * R, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+        if (e != hipSuccess) return hip_fail(e, "gptq_moe_decode_forward h_out copy");
+    }
+    return GPTQ_OK;
+}
+
+int gptq_describe_moe_decode_plan(const gptq_moe_t* m, int T, int topk, char* out, size_t out_bytes) {
+    if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out is NULL");
+    if (moe_decode_check(m, T, topk)) {
+        char reason[sizeof(g_err)];
+        snprintf(reason, sizeof(reason), "%s", g_err);
+        for (char* c = reason; *c; ++c)
+            if (*c == ' ' || *c == '=') *c = '_';
+        snprintf(out, out_bytes, "path=none reason=%s", reason);
+        return GPTQ_OK;
+    }
+    const MoeDecodePlan pl = plan_moe_decode(*m, T, topk);
+    snprintf(out, out_bytes, "path=decode launches=%d wg_pair=%d wg_down=%d waves_pair=%d waves_down=%d lds_pair=%d lds_down=%d", T > 0 ? 2 : 0, pl.wg_pair, pl.wg_down,
+             pl.waves_pair, pl.waves_down, pl.lds_pair, pl.lds_down);
     return GPTQ_OK;
 }
 

@@ -187,6 +187,18 @@ size_t moe_table_entry_bytes();
 void moe_table_entry(const gptq_layer_t& L, void* dst);
 hipError_t launch_moe(const gptq_moe_t& m, const void* table, const MoePlan& pl, const void* x, const int64_t* idx, const float* w, int T, int topk,
                       void* out, char* ws, hipStream_t st);
+// moe_decode.hip: the same layer at 1..4 tokens on the experts' decode copy (gptq_moe_decode_forward): gate|up + silu * mul, down + combine -- two launches
+struct MoeDecodePlan {
+    bool ok;                                        // the staged rows and constants fit the LDS
+    int wg_pair, wg_down, waves_pair, waves_down, lds_pair, lds_down;
+    size_t off_h, off_pos, bytes;                   // workspace layout (from GPTQ_WORKSPACE_HEADER_BYTES on)
+};
+MoeDecodePlan plan_moe_decode(const gptq_moe_t& m, int T, int topk);
+size_t moe_decode_table_entry_bytes();
+void moe_decode_table_entry(const gptq_layer_t& L, void* dst);
+hipError_t launch_moe_decode(const gptq_moe_t& m, const void* table, const MoeDecodePlan& pl, const void* x, const int64_t* idx, const float* w, int T, int topk,
+                             void* out, char* ws, hipStream_t st);
+hipError_t init_moe_decode_device();
 hipError_t launch_unpack_weights(const uint32_t* qweight, int K, int N, int bits, uint8_t* w_out, hipStream_t st);
 hipError_t launch_unpack_zeros(const uint32_t* qzeros, int G, int N, int bits, int zero_mode, int32_t* z_out, hipStream_t st);
 hipError_t launch_pack_weights(const void* W, const void* scale_in, const void* zero_in, const int32_t* g_idx,

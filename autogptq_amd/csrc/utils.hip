@@ -214,28 +214,27 @@ __global__ void __launch_bounds__(256) pack_zeros_kernel(const void* __restrict_
 
 // ---------------------------------------------------------------------------------------------
 // out row-stream position i holds the field of source k = perm[i] (masked fields, clean re-pack).
-template <int BITS>
+// (bits is a run-time, workgroup-uniform argument: a load-time integer kernel needs one instantiation, not one per packing)
 __global__ void __launch_bounds__(256) resequence_kernel(const unsigned* __restrict__ qweight, const int* __restrict__ perm,
-                                                         int units, int N, unsigned* __restrict__ out) {
-    constexpr int UW = Pack<BITS>::words, KPU = Pack<BITS>::vals;
+                                                         int units, int N, int bits, unsigned* __restrict__ out) {
+    const int UW = unit_words(bits), KPU = unit_vals(bits);
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     const int u = blockIdx.y;
     if (n >= N || u >= units) return;
     unsigned long long lo = 0ull;  // bits 0..63 of the unit stream
     unsigned hi = 0u;              // bits 64..95 (3-bit only)
-#pragma unroll
     for (int v = 0; v < KPU; ++v) {
-        const unsigned f = stream_field(qweight + n, (size_t)N, (unsigned)perm[u * KPU + v], BITS);
-        const int bit = BITS * v;
+        const unsigned f = stream_field(qweight + n, (size_t)N, (unsigned)perm[u * KPU + v], bits);
+        const int bit = bits * v;
         if (bit < 64) {
             lo |= (unsigned long long)f << bit;
-            if (bit + BITS > 64) hi |= f >> (64 - bit);
+            if (bit + bits > 64) hi |= f >> (64 - bit);
         } else {
             hi |= f << (bit - 64);
         }
     }
     out[(size_t)(u * UW) * N + n] = (unsigned)lo;
-    if constexpr (UW == 3) {
+    if (UW == 3) {
         out[(size_t)(u * UW + 1) * N + n] = (unsigned)(lo >> 32);
         out[(size_t)(u * UW + 2) * N + n] = hi;
     }
@@ -249,28 +248,27 @@ __global__ void __launch_bounds__(256) resequence_kernel(const unsigned* __restr
 //   8-bit  stored byte p of word w = k 4w + {0, 2, 1, 3}[p]: (q & 0x00ff00ff) = (k0, k1), the same on q >> 8 = (k2, k3)
 //   3-bit  word j of the lane's three: pair 5j + i (i = 0..4) = (k 2p, k 2p + 1) at bit 3i of the low / high 16 bits; bit 15 / 31 = bit j of k30 / k31
 //   2-bit  (round 6) a lane holds TWO words = 32 k: word w holds pair p (p = 0..7) = (k 16w + 2p, k 16w + 2p + 1) at bit 2p of its low / high 16 bits
-template <int BITS>
-__global__ void __launch_bounds__(256) prepack_decode_weights_kernel(const unsigned* __restrict__ q, int K, int N, int chunks, unsigned* __restrict__ out) {
-    constexpr int WPL = BITS == 3 ? 3 : (BITS == 2 ? 2 : 4), KPL = BITS == 8 ? 16 : 32, CKE = 4 * KPL;
+// (bits is a run-time, workgroup-uniform argument: one instantiation)
+__global__ void __launch_bounds__(256) prepack_decode_weights_kernel(const unsigned* __restrict__ q, int K, int N, int chunks, int bits, unsigned* __restrict__ out) {
+    const int WPL = bits == 3 ? 3 : (bits == 2 ? 2 : 4), KPL = bits == 8 ? 16 : 32, CKE = 4 * KPL;
+    const int UV = unit_vals(bits), UWD = unit_words(bits);
     const int c = blockIdx.x, s = blockIdx.y, t = threadIdx.x;
     const int col = t & 15, w = (t >> 4) % WPL, kb = (t >> 4) / WPL;              // reads of one k run over 16 adjacent columns
     if (kb >= 4) return;
     const int n = s * 16 + col, k0 = c * CKE + kb * KPL;
     auto val = [&](int k) -> unsigned {                                          // the checkpoint's value (k, n); rows past K read as 0
         if (k >= K) return 0u;
-        const int unit = k / Pack<BITS>::vals;
-        return stream_field(q + (size_t)unit * Pack<BITS>::words * N + n, (size_t)N, (unsigned)(k - unit * Pack<BITS>::vals), BITS);
+        const int unit = k / UV;
+        return stream_field(q + (size_t)unit * UWD * N + n, (size_t)N, (unsigned)(k - unit * UV), bits);
     };
     unsigned v = 0;
-    if constexpr (BITS == 4) {
-        constexpr int order[8] = {0, 2, 4, 6, 1, 3, 5, 7};
+    if (bits == 4) {
 #pragma unroll
-        for (int p = 0; p < 8; ++p) v |= val(k0 + 8 * w + order[p]) << (4 * p);
-    } else if constexpr (BITS == 8) {
-        constexpr int order[4] = {0, 2, 1, 3};
+        for (int p = 0; p < 8; ++p) v |= val(k0 + 8 * w + (p < 4 ? 2 * p : 2 * (p - 4) + 1)) << (4 * p);      // k order 0 2 4 6 1 3 5 7
+    } else if (bits == 8) {
 #pragma unroll
-        for (int p = 0; p < 4; ++p) v |= val(k0 + 4 * w + order[p]) << (8 * p);
-    } else if constexpr (BITS == 2) {
+        for (int p = 0; p < 4; ++p) v |= val(k0 + 4 * w + (p == 1 ? 2 : (p == 2 ? 1 : p))) << (8 * p);        // k order 0 2 1 3
+    } else if (bits == 2) {
 #pragma unroll
         for (int p = 0; p < 8; ++p) {
             v |= val(k0 + 16 * w + 2 * p) << (2 * p);
@@ -292,22 +290,22 @@ __global__ void __launch_bounds__(256) prepack_decode_weights_kernel(const unsig
 // the copy -- what lets a layer whose checkpoint rows have left the HBM (QuantLinear.post_init(release_checkpoint_layout=True)) still serve the kernels that
 // read rows, and what state_dict() / a re-save would be rebuilt from.  Reference behaviour it answers: the in-place re-layouts of exllama / exllamav2
 // (q4_matrix.cu:160, q_matrix.cu:149) keep ONE copy of the weights on the device.
-template <int BITS>
-__global__ void __launch_bounds__(256) unprepack_decode_weights_kernel(const unsigned* __restrict__ t, int K, int N, int chunks, unsigned* __restrict__ out) {
-    constexpr int WPL = BITS == 3 ? 3 : (BITS == 2 ? 2 : 4), KPL = BITS == 8 ? 16 : 32, CKE = 4 * KPL;
+// (bits is a run-time, workgroup-uniform argument: one instantiation)
+__global__ void __launch_bounds__(256) unprepack_decode_weights_kernel(const unsigned* __restrict__ t, int K, int N, int chunks, int bits, unsigned* __restrict__ out) {
+    const int WPL = bits == 3 ? 3 : (bits == 2 ? 2 : 4), KPL = bits == 8 ? 16 : 32, CKE = 4 * KPL;
     const int n = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;          // output word (row r, column n)
     if (n >= N) return;
     const int s = n >> 4, col = n & 15;
     auto val = [&](int k) -> unsigned {                                          // the copy's value (k, n)
         const int c = k / CKE, kb = (k - c * CKE) / KPL, j = k - c * CKE - kb * KPL;
         const unsigned* lw = t + ((size_t)s * chunks + c) * (64 * WPL) + (kb * 16 + col) * WPL;
-        if constexpr (BITS == 4) {
+        if (bits == 4) {
             const int i = j & 7, p = (i & 1) ? 4 + (i >> 1) : (i >> 1);          // stored nibble order k0 k2 k4 k6 k1 k3 k5 k7
             return (lw[j >> 3] >> (4 * p)) & 15u;
-        } else if constexpr (BITS == 8) {
+        } else if (bits == 8) {
             const int i = j & 3, p = i == 1 ? 2 : (i == 2 ? 1 : i);              // stored byte order k0 k2 k1 k3
             return (lw[j >> 2] >> (8 * p)) & 255u;
-        } else if constexpr (BITS == 2) {
+        } else if (bits == 2) {
             const int i = j & 15;                                                // pair i >> 1 at bit 2 (i >> 1) of the low (even k) / high (odd k) half
             return (lw[j >> 4] >> (2 * (i >> 1) + 16 * (i & 1))) & 3u;
         } else {
@@ -317,7 +315,7 @@ __global__ void __launch_bounds__(256) unprepack_decode_weights_kernel(const uns
         }
     };
     unsigned v = 0;
-    if constexpr (BITS == 3) {
+    if (bits == 3) {
         const int unit = r / 3, wi = r - unit * 3;                               // 32 values in 96 bits, little-endian bit stream (qlinear_cuda.py:144-162)
         for (int f = 0; f < 32; ++f) {
             const int bit = 3 * f - 32 * wi;                                     // position of field f in this word
@@ -326,9 +324,8 @@ __global__ void __launch_bounds__(256) unprepack_decode_weights_kernel(const uns
             v |= bit >= 0 ? (x << bit) : (x >> (-bit));
         }
     } else {
-        constexpr int P = 32 / BITS;
-#pragma unroll
-        for (int f = 0; f < P; ++f) v |= val(r * P + f) << (BITS * f);
+        const int P = 32 / bits;
+        for (int f = 0; f < P; ++f) v |= val(r * P + f) << (bits * f);
     }
     out[(size_t)r * N + n] = v;
 }
@@ -442,13 +439,8 @@ hipError_t launch_pack_zeros(const void* zero_in, int G, int N, int bits, int qp
 hipError_t launch_unprepack_decode(const uint32_t* tiled, int K, int N, int bits, uint32_t* qweight_out, hipStream_t st) {
     const int cke = bits == 8 ? 64 : 128, chunks = (K + cke - 1) / cke, rows = K / 32 * bits;
     const dim3 grid((N + 255) / 256, rows);
-    switch (bits) {
-        case 4: hipLaunchKernelGGL(unprepack_decode_weights_kernel<4>, grid, dim3(256), 0, st, tiled, K, N, chunks, qweight_out); break;
-        case 8: hipLaunchKernelGGL(unprepack_decode_weights_kernel<8>, grid, dim3(256), 0, st, tiled, K, N, chunks, qweight_out); break;
-        case 3: hipLaunchKernelGGL(unprepack_decode_weights_kernel<3>, grid, dim3(256), 0, st, tiled, K, N, chunks, qweight_out); break;
-        case 2: hipLaunchKernelGGL(unprepack_decode_weights_kernel<2>, grid, dim3(256), 0, st, tiled, K, N, chunks, qweight_out); break;
-        default: return hipErrorInvalidValue;
-    }
+    if (bits != 2 && bits != 3 && bits != 4 && bits != 8) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(unprepack_decode_weights_kernel, grid, dim3(256), 0, st, tiled, K, N, chunks, bits, qweight_out);
     return hipGetLastError();
 }
 
@@ -456,13 +448,9 @@ hipError_t launch_prepack_decode(const uint32_t* qweight, const uint32_t* qzeros
                                  uint32_t* tiled_out, void* const_out, hipStream_t st) {
     const int cke = bits == 8 ? 64 : 128, chunks = (K + cke - 1) / cke, G = (K + group_size - 1) / group_size;
     const dim3 grid(chunks, N / 16);
-    switch (bits) {
-        case 4: hipLaunchKernelGGL(prepack_decode_weights_kernel<4>, grid, dim3(256), 0, st, qweight, K, N, chunks, tiled_out); break;
-        case 8: hipLaunchKernelGGL(prepack_decode_weights_kernel<8>, grid, dim3(256), 0, st, qweight, K, N, chunks, tiled_out); break;
-        case 3: hipLaunchKernelGGL(prepack_decode_weights_kernel<3>, grid, dim3(192), 0, st, qweight, K, N, chunks, tiled_out); break;
-        case 2: hipLaunchKernelGGL(prepack_decode_weights_kernel<2>, grid, dim3(128), 0, st, qweight, K, N, chunks, tiled_out); break;
-        default: return hipErrorInvalidValue;
-    }
+    if (bits != 2 && bits != 3 && bits != 4 && bits != 8) return hipErrorInvalidValue;
+    const int threads = bits == 3 ? 192 : (bits == 2 ? 128 : 256);                // 4 k-slots x WPL words x 16 columns
+    hipLaunchKernelGGL(prepack_decode_weights_kernel, grid, dim3(threads), 0, st, qweight, K, N, chunks, bits, tiled_out);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(prepack_decode_consts_kernel, dim3((N + 255) / 256, G), dim3(256), 0, st, qzeros, (const unsigned short*)scales, G, N, bits, zero_mode,
@@ -473,7 +461,8 @@ hipError_t launch_prepack_decode(const uint32_t* qweight, const uint32_t* qzeros
 hipError_t launch_resequence(const uint32_t* qweight, const int32_t* perm, int K, int N, int bits, uint32_t* out, hipStream_t st) {
     const int units = K / unit_vals(bits);
     dim3 grid((N + 255) / 256, units), block(256);
-    GPTQ_BITS_SWITCH(bits, hipLaunchKernelGGL(resequence_kernel<B>, grid, block, 0, st, qweight, perm, units, N, out));
+    if (bits != 2 && bits != 3 && bits != 4 && bits != 8) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(resequence_kernel, grid, block, 0, st, qweight, perm, units, N, bits, out);
     return hipGetLastError();
 }
 

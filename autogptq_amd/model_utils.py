@@ -86,7 +86,8 @@ def pack_model(model: nn.Module, quantizers: dict, bits: int, group_size: int, d
 
 
 def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_length: Optional[int] = None,
-                       release_checkpoint_layout: Optional[bool] = None, decode_copy: Optional[bool] = None) -> nn.Module:
+                       release_checkpoint_layout: Optional[bool] = None, decode_copy: Optional[bool] = None,
+                       expert_decode_copy: bool = False) -> nn.Module:
     """post_init every mi355x layer and size the per-device scratch once (so forward never allocates; needed before hipGraph
     capture).  ``max_input_length`` bounds the rows M the scratch is sized for (default 2048, the reference's exllama default).
     Memory (the model-level switches for what post_init keeps next to the checkpoint tensors): ``decode_copy=False`` builds no decode copy (1x the packed
@@ -95,19 +96,23 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
     layouts on the device (2x; act-order layers 3x with their re-sequenced rows) -- 288 GB of HBM is what makes that the default.
     Mixture-of-experts layers (``QuantMoEExperts``) are post-initialised without a decode copy (1x the packed bytes, + the re-sequenced rows of act-order
     experts; ``release_checkpoint_layout`` does not apply to them), get their pointer table, and the scratch covers ``gptq_moe_workspace_bytes`` of
-    ``max_input_length`` tokens at the module's ``top_k``."""
+    ``max_input_length`` tokens at the module's ``top_k``.  ``expert_decode_copy=True`` gives the expert layers a decode copy as well (2x the packed expert
+    bytes -- Mixtral-8x7B 4-bit: about 23 GB -> 46 GB of 288 GB; both layouts stay resident): calls of 1..4 tokens then run the two-launch decode kernels,
+    larger ones the grouped path as before."""
     from .moe import QuantMoEExperts
     rows = max_input_length or 2048
     need: Dict[torch.device, int] = {}
     in_experts = set()
+    expert_copy_bytes = 0
     for _, sub in model.named_modules():
         # mixture-of-experts layers: their QuantLinears are post-initialised by the module (no decode copy; a checkpoint-layout release does not apply)
         if isinstance(sub, QuantMoEExperts) and sub[0].layers()[0].qweight.device.type == "cuda":
             dev = sub[0].layers()[0].qweight.device
-            sub.post_init()
+            sub.post_init(decode_copy=expert_decode_copy)
             for e in range(sub.num_experts):
                 in_experts.update(id(l) for l in sub[e].layers())
-            need[dev] = max(need.get(dev, 0), sub.workspace_bytes(rows, sub.top_k))
+            expert_copy_bytes += sub.decode_copy_bytes
+            need[dev] = max([need.get(dev, 0)] + [sub.workspace_bytes(t, sub.top_k) for t in sorted({rows, *range(1, min(rows, 4) + 1)})])
     for _, sub in model.named_modules():
         if getattr(sub, "QUANT_TYPE", None) != QuantLinear.QUANT_TYPE or id(sub) in in_experts:
             continue
@@ -127,6 +132,9 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
         else:
             b = int(lib.gptq_workspace_bytes_max(ctypes.byref(sub._layer), rows))
         need[dev] = max(need.get(dev, 0), b)
+    if expert_copy_bytes:
+        logger.info("mixture-of-experts layers: the decode copy of the experts holds %.2f GB next to their packed checkpoint tensors (2x the packed expert "
+                    "bytes; 1..4 tokens run the decode kernels on it, more the grouped kernels on the checkpoint rows)", expert_copy_bytes / 1e9)
     for dev, b in need.items():
         reserve_workspace(dev, b)
     return model

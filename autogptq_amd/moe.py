@@ -5,7 +5,9 @@
                         ``forward(hidden_states, top_k_index, top_k_weights)``; its children are per-expert ``QuantLinear``s whose
                         state_dict keys are ``<path>.{e}.w1 / w3 / w2.{qweight, qzeros, scales, g_idx}``
 * ``moe_forward``       the grouped path (gptq_moe_forward: routing table, grouped W1 / W3 + silu * mul, grouped W2, combine -- four
-                        launches, no host round trip, capturable), or the per-expert composition of differentiable ``QuantLinear`` calls
+                        launches, no host round trip, capturable), the decode path for 1..4 tokens when the experts carry a decode copy
+                        (gptq_moe_decode_forward: two launches on streaming kernels, the expert chosen on the device, capturable), or the
+                        per-expert composition of differentiable ``QuantLinear`` calls
 * ``pack_moe_experts``  pack the dense 3-D expert parameters of a model (``quantizers`` keyed ``...mlp.experts.{e}.w1`` as ``pack_model`` takes)
 
 The per-expert composition serves what the grouped kernels do not take (2- / 3-bit or fp32 experts, odd group sizes, raw act-order), CPU tensors (which
@@ -16,6 +18,7 @@ from __future__ import annotations
 
 import ctypes
 import types
+from logging import getLogger
 
 import torch
 import torch.nn as nn
@@ -23,6 +26,8 @@ import torch.nn.functional as F
 
 from . import _lib
 from .qlinear_mi355x import QuantLinear, _raw_stream, exchange_tick, forward_multi, reserve_workspace
+
+logger = getLogger(__name__)
 
 DEFAULT_NAMES = ("w1", "w3", "w2")          # gate, up, down (AutoGPTQ's Mixtral names)
 
@@ -42,8 +47,8 @@ class _Expert(nn.Module):
 
 class QuantMoEExperts(nn.Module):
     """E quantised experts behind the forward of transformers' ``MixtralExperts``: ``out[t] = sum_j w[t, j] * down(silu(gate(x_t)) * up(x_t))`` over the
-    experts ``top_k_index[t, j]`` (indices outside [0, E) are dropped).  ``post_init`` (or ``autogptq_post_init``) prepares the experts' layers without a
-    decode copy and builds the device table of per-expert pointers the grouped kernels read."""
+    experts ``top_k_index[t, j]`` (indices outside [0, E) are dropped).  ``post_init`` (or ``autogptq_post_init``) prepares the experts' layers (without a
+    decode copy unless ``decode_copy=True``) and builds the device table of per-expert pointers the grouped kernels read (and the decode kernels' own)."""
 
     QUANT_TYPE = "mi355x_moe"
 
@@ -58,6 +63,7 @@ class QuantMoEExperts(nn.Module):
         self.top_k = top_k
         self.bits = bits
         self.names = tuple(names)
+        self._decode_copy = False
         for e in range(num_experts):
             self.add_module(str(e), _Expert(self.names, bits, group_size, hidden_dim, intermediate_dim, weight_dtype, zero_mode))
         self._invalidate()
@@ -70,6 +76,8 @@ class QuantMoEExperts(nn.Module):
 
     def _invalidate(self):
         self._moe = None
+        self._decode_table = None
+        self.decode_copy_bytes = 0
         self._keep = ()
         self._plans = {}
         self.last_plan = None
@@ -89,15 +97,27 @@ class QuantMoEExperts(nn.Module):
         return [l[0] for l in ls], [l[1] for l in ls], [l[2] for l in ls]
 
     # ------------------------------------------------------------------ post_init
-    def post_init(self):
-        """post_init every expert layer WITHOUT a decode copy (1x the packed bytes; act-order layers add their re-sequenced rows) and build the pointer
-        table.  The decode copy is not read by the grouped kernels, and a checkpoint-layout release does not apply to expert layers."""
+    def post_init(self, decode_copy: bool = False):
+        """post_init every expert layer and build the pointer table.  Default: WITHOUT a decode copy (1x the packed bytes; act-order layers add their
+        re-sequenced rows) -- calls of any row count run the grouped kernels.  ``decode_copy=True``: the layers also get their decode copy (2x the packed
+        bytes; both layouts stay resident: the grouped path still serves more than 4 tokens), the decode table is built, and calls of 1..4 tokens run the
+        decode kernels (``plan(T)["path"] == "decode"``).  ``decode_copy_bytes`` reports what the copies hold.  A checkpoint-layout release does not apply
+        to expert layers."""
         dev = self[0].layers()[0].qweight.device
         if dev.type != "cuda":
             raise RuntimeError(f"mi355x QuantMoEExperts.post_init needs the module on a ROCm GPU device (got {dev}); there is no CPU path.")
+        self._decode_copy = bool(decode_copy)
+        if self._decode_copy:
+            why = self._decode_copy_declined()
+            if why:                                          # known from the metadata: no copy is built for a set the decode plan would decline
+                logger.warning("QuantMoEExperts.post_init(decode_copy=True) has no effect for these experts (%s): no decode copy is built", why)
+                self._decode_copy = False
+        extra = 0
         for e in range(self.num_experts):
             for l in self[e].layers():
-                l.post_init(tiled=False, release_checkpoint_layout=False)
+                l.post_init(tiled=self._decode_copy, release_checkpoint_layout=False)
+                if l._qweight_tiled is not None:
+                    extra += l._qweight_tiled.numel() + l._qconst_tiled.numel()
         lib = _lib.load()
         gate, up, down = self.projections()
         arrs = [(ctypes.POINTER(_lib.GptqLayer) * self.num_experts)(*[ctypes.pointer(l._layer) for l in ls]) for ls in (gate, up, down)]
@@ -107,29 +127,71 @@ class QuantMoEExperts(nn.Module):
         table = torch.zeros(max(1, int(lib.gptq_moe_table_bytes(self.num_experts))), dtype=torch.uint8, device=dev)
         self._moe, self._keep, self._plans = m, (arrs, table, gate, up, down), {}
         self._table = table
+        self._decode_table = None
+        self.decode_copy_bytes = extra
         self._dev = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
         self._w_dtype = gate[0].scales.dtype
         if self.plan(1, self.top_k)["path"] == "grouped":          # (a declined layer set has no valid table: it runs per expert)
             with torch.cuda.device(self._dev):
                 _lib.check(lib.gptq_moe_build_table(ctypes.byref(m), table.data_ptr(), _lib.current_stream_handle(self._dev)))
+        if self._decode_copy:
+            dplan = _lib.describe_moe_decode_plan(m, 1, self.top_k)
+            if dplan["path"] != "decode":
+                # declined (2- / 3-bit, fp32, a group size the copy does not take, ...): nothing would read the copies -- say so and give their memory back
+                logger.warning("QuantMoEExperts.post_init(decode_copy=True) has no effect for these experts (%s): no decode copy is kept",
+                               str(dplan.get("reason", "")).replace("_", " "))
+                return self.post_init(decode_copy=False)
+            dtable = torch.zeros(max(1, int(lib.gptq_moe_decode_table_bytes(self.num_experts))), dtype=torch.uint8, device=dev)
+            with torch.cuda.device(self._dev):
+                _lib.check(lib.gptq_moe_build_decode_table(ctypes.byref(m), dtable.data_ptr(), _lib.current_stream_handle(self._dev)))
+            self._decode_table = dtable
+            self._plans = {}
         return self
 
+    def _decode_copy_declined(self) -> str:
+        """Why the decode plan would decline these experts, as far as the layer metadata says (empty: build the copies and ask the plan)."""
+        gate, _, down = self[0].layers()
+        if self.bits not in (4, 8):
+            return f"{self.bits}-bit experts: the decode path takes 4 or 8 bits"
+        if gate.scales.dtype not in (torch.float16, torch.bfloat16):
+            return "fp32 experts: the decode path takes fp16 / bf16"
+        if self.hidden_dim % 64 or self.intermediate_dim % 64:
+            return "hidden and intermediate sizes must be multiples of 64"
+        if not 1 <= self.num_experts <= 256 or not 1 <= self.top_k <= 8:
+            return "the decode path takes up to 256 experts and topk up to 8"
+        kpl = 16 if self.bits == 8 else 32
+        for l in (gate, down):
+            gs, K = l.group_size, l.infeatures
+            gu = gs // kpl
+            if gs < K and (gs % kpl or gu & (gu - 1)):
+                return f"group_size {gs}: the decode copy takes {kpl} times a power of two, or one group"
+        return ""
+
     def workspace_bytes(self, T: int, top_k: "int | None" = None) -> int:
+        """Scratch of one call with T tokens on the path ``plan(T)`` names."""
         if self._moe is None:
-            self.post_init()
+            self.post_init(self._decode_copy)
+        if self.plan(T, top_k)["path"] == "decode":
+            return int(_lib.load().gptq_moe_decode_workspace_bytes(ctypes.byref(self._moe), T, top_k or self.top_k))
         return int(_lib.load().gptq_moe_workspace_bytes(ctypes.byref(self._moe), T, top_k or self.top_k))
 
     def plan(self, T: int, top_k: "int | None" = None) -> dict:
-        """{"path": "grouped" | "per_expert", "reason": ...} (+ the tile geometry) for T tokens: what moe_forward runs without grad."""
+        """{"path": "decode" | "grouped" | "per_expert", "reason": ...} (+ the launch / tile geometry) for T tokens: what moe_forward runs without grad.
+        "decode" only when the experts carry a decode copy (``post_init(decode_copy=True)``) and the decode plan accepts (1..4 tokens)."""
         top_k = top_k or self.top_k
         if self[0].layers()[0].qweight.device.type != "cuda":
             return {"path": "per_expert", "reason": "cpu tensors"}
         if self._moe is None:
-            self.post_init()
+            self.post_init(self._decode_copy)
         key = (T, top_k)
         d = self._plans.get(key)
         if d is None:
-            d = _lib.describe_moe_plan(self._moe, T, top_k)
+            if self._decode_table is not None and 0 < T <= 4:
+                d = _lib.describe_moe_decode_plan(self._moe, T, top_k)
+                if d["path"] != "decode":
+                    d = None
+            if d is None:
+                d = _lib.describe_moe_plan(self._moe, T, top_k)
             d.setdefault("reason", "")
             if isinstance(d["reason"], str):
                 d["reason"] = d["reason"].replace("_", " ")
@@ -142,8 +204,10 @@ class QuantMoEExperts(nn.Module):
 
 def moe_forward(experts: QuantMoEExperts, x: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor, return_intermediate: bool = False):
     """``experts(x, top_k_index, top_k_weights)``: x [T, H] (or [..., H]), top_k_index [T, topk] (int64 as torch.topk returns it), top_k_weights [T, topk].
-    The grouped path: one gptq_moe_forward call (workspace from the per-stream scratch, nothing allocated but the output).  ``return_intermediate``:
-    also (H_sorted [T topk, I], pos [T, topk] int32) -- the kernel's silu * mul rows grouped by expert and the row of each assignment (-1: dropped)."""
+    The grouped path: one gptq_moe_forward call (workspace from the per-stream scratch, nothing allocated but the output); the decode path (1..4 tokens
+    on experts with a decode copy): one gptq_moe_decode_forward call, same conventions.  ``return_intermediate``: also (H [T topk, I], pos [T, topk] int32)
+    -- the kernel's silu * mul rows and the row of each assignment (-1: dropped); rows grouped by expert on the grouped path, in assignment order on the
+    decode path: ``H[pos[t, j]]`` reads the same way on both."""
     H = experts.hidden_dim
     lead = x.shape[:-1]
     x2 = x.reshape(-1, H)
@@ -156,9 +220,10 @@ def moe_forward(experts: QuantMoEExperts, x: torch.Tensor, top_k_index: torch.Te
         experts.last_plan = {"path": "per_expert", "reason": "grad enabled and hidden_states / top_k_weights require grad"}
     else:
         experts.last_plan = experts.plan(T, topk)
-    if experts.last_plan["path"] != "grouped":
+    decode = experts.last_plan["path"] == "decode"
+    if experts.last_plan["path"] != "grouped" and not decode:
         if return_intermediate:
-            raise RuntimeError(f"moe_forward: return_intermediate needs the grouped path ({experts.last_plan['reason']})")
+            raise RuntimeError(f"moe_forward: return_intermediate needs the grouped or the decode path ({experts.last_plan['reason']})")
         return _per_expert(experts, x2, top_k_index.reshape(T, topk), top_k_weights.reshape(T, topk)).reshape(lead + (H,))
     dev, w_dtype = experts._dev, experts._w_dtype
     if x.device != dev:
@@ -188,8 +253,10 @@ def moe_forward(experts: QuantMoEExperts, x: torch.Tensor, top_k_index: torch.Te
         exchange_tick(dev)
         idx_dev = experts._dev.index
         with torch.cuda.device(idx_dev):
-            rc = _lib.load().gptq_moe_forward(ctypes.byref(experts._moe), experts._table.data_ptr(), xw.data_ptr(), idx.data_ptr(), w.data_ptr(), T, topk,
-                                              out.data_ptr(), _lib.ptr(h_out), buf.data_ptr(), buf.numel(), _raw_stream(idx_dev))
+            lib = _lib.load()
+            fn, table = (lib.gptq_moe_decode_forward, experts._decode_table) if decode else (lib.gptq_moe_forward, experts._table)
+            rc = fn(ctypes.byref(experts._moe), table.data_ptr(), xw.data_ptr(), idx.data_ptr(), w.data_ptr(), T, topk,
+                    out.data_ptr(), _lib.ptr(h_out), buf.data_ptr(), buf.numel(), _raw_stream(idx_dev))
         if rc:
             _lib.check(rc)
     res = out.to(x.dtype) if x.dtype != w_dtype else out

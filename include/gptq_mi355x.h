@@ -17,6 +17,8 @@
  *       <- the `reconstruct` step of exllama / exllamav2              exllama/cuda_func/q4_matrix.cu:171-225, exllamav2/cuda/q_matrix.cu:158-279,452-500
  *   gptq_moe_forward
  *       <- the expert loop of the reference's Mixtral (per-expert QuantLinears, auto_gptq/modeling/mixtral.py) as one routed, grouped call
+ *   gptq_moe_decode_forward
+ *       <- the same expert loop at the row counts of token generation (1..4 tokens), on the experts' decode copy
  *   gptq_grad_input
  *       <- the backward of the reference's training route: dequantise + torch.matmul under autograd
  *                                                                     qlinear_cuda_old.py:291-355, qlinear_cuda.py:253-317
@@ -75,7 +77,7 @@
 extern "C" {
 #endif
 
-#define GPTQ_MI355X_ABI_VERSION 7
+#define GPTQ_MI355X_ABI_VERSION 8
 #define GPTQ_WORKSPACE_HEADER_BYTES 65536
 
 typedef enum gptq_status_t {
@@ -282,6 +284,33 @@ int gptq_moe_forward(const gptq_moe_t *moe, const void *table, const void *x, co
 /* Host-only: "path=grouped bm=16 bn=64 tiles=2 ksplit=4 launches=4" or "path=per_expert reason=...", for (moe, T, topk).  GPTQ_OK either way
  * (GPTQ_ERR_NULL for a NULL out). */
 int gptq_describe_moe_plan(const gptq_moe_t *moe, int T, int topk, char *out, size_t out_bytes);
+
+/* The same layer at DECODE row counts, T <= 4, on the experts' decode copy (ABI 8): every expert layer carries qweight_tiled / qconst_tiled
+ * (gptq_prepack_decode; act-order experts: built from qweight_seq, with perm), and the call runs on streaming kernels of the dense decode kernel's kind.
+ *   ARITHMETIC: that of the dense decode-copy kernel, NOT "every W bit-exact to gptq_dequant" as on the grouped path: w - z exact in the layer dtype,
+ *   products x (w - z) exact in fp32, fp32 sums over the 32 (8 bits: 16) consecutive k a lane holds, the group's scale applied to that fp32 sum; W is never
+ *   rounded to the layer dtype.  silu and the product on the fp32 sums, h rounded once; out[t] = T(sum_j topk_w[t, j] (h_(t,j) . W2_e)) in fp32, ascending j,
+ *   0 for a token with no valid expert.  Bit-reproducible; the row of token t does not depend on the other tokens of the call.
+ *   TWO launches (gate|up + silu * mul; down + combine), no routing launch: every workgroup reads its expert from topk_idx and that expert's entry from the
+ *   device table, so a captured graph replays with new routing.
+ * Takes 4- and 8-bit fp16 / bf16 experts, every group size the decode copy takes, plain and act-order (gate and up may have different activation orders:
+ * each is gathered through its own perm; equal perm pointers -> one gather), T <= 4, topk <= 8, E <= 256, H and I multiples of 64, no bias.  Anything
+ * else: GPTQ_ERR_UNSUPPORTED with the reason, and the caller keeps gptq_moe_forward / the per-expert composition.
+ * Table: [3 projections][E] entries of 32 bytes {qweight_tiled, qconst_tiled, perm or NULL, 0}; gptq_moe_build_decode_table fills
+ * gptq_moe_decode_table_bytes(E) = 3 E 32 caller-owned device bytes, synchronises `stream` (not capturable); rebuild it whenever a layer's buffers move. */
+size_t gptq_moe_decode_table_bytes(int E);
+int gptq_moe_build_decode_table(const gptq_moe_t *moe, void *table, void *stream);
+/* GPTQ_WORKSPACE_HEADER_BYTES (left untouched) + a256(T topk I sizeof(T)) + a256(4 T topk): the h rows and pos.  0 when the call is declined. */
+size_t gptq_moe_decode_workspace_bytes(const gptq_moe_t *moe, int T, int topk);
+/* Arguments as gptq_moe_forward.  h_out (optional, for tests): H [T topk, I] in ASSIGNMENT order (row t topk + j; rows of dropped assignments are not
+ * written) followed by pos [T, topk] int32 = that row, or -1 for a dropped assignment -- H[pos[t, j]] reads as with the grouped path.
+ * Caller's stream, no allocation, no synchronisation, legal inside hipGraph capture (gptq_init() first: long act-order rows need its LDS grant);
+ * T = 0 launches nothing. */
+int gptq_moe_decode_forward(const gptq_moe_t *moe, const void *table, const void *x, const int64_t *topk_idx, const float *topk_w, int T, int topk, void *out,
+                            void *h_out, void *workspace, size_t workspace_bytes, void *stream);
+/* Host-only: "path=decode launches=2 wg_pair=1792 wg_down=256 waves_pair=8 waves_down=16 lds_pair=... lds_down=..." (workgroups, waves per workgroup and
+ * dynamic LDS bytes of the two launches) or "path=none reason=..." (experts without a decode copy, T > 4, 2- / 3-bit, fp32, topk > 8, ...).  GPTQ_OK either way. */
+int gptq_describe_moe_decode_plan(const gptq_moe_t *moe, int T, int topk, char *out, size_t out_bytes);
 
 /* Integer unpack (bit-exact targets). w_out uint8 [K,N]; z_out int32 [G,N] (zero-point as used). */
 int gptq_unpack_weights(const uint32_t *qweight, int K, int N, int bits, uint8_t *w_out, void *stream);

@@ -35,6 +35,7 @@ EXPORTS = (
     "gptq_mlp_forward", "gptq_mlp_forward_ex", "gptq_workspace_bytes_mlp", "gptq_workspace_bytes_mlp_ex", "gptq_describe_mlp_plan",
     "gptq_moe_table_bytes", "gptq_moe_build_table", "gptq_moe_workspace_bytes", "gptq_moe_forward", "gptq_describe_moe_plan",
     "gptq_moe_decode_table_bytes", "gptq_moe_build_decode_table", "gptq_moe_decode_workspace_bytes", "gptq_moe_decode_forward", "gptq_describe_moe_decode_plan",
+    "gptq_moe_batch_workspace_bytes", "gptq_moe_batch_forward", "gptq_describe_moe_batch_plan",
 )
 WS_HEADER_BYTES = 65536
 STRIP_COLS = 16          # GPTQ_STRIP_COLS: columns per strip of the decode copy (gptq_prepack_decode)
@@ -171,6 +172,10 @@ def load() -> ctypes.CDLL:
     lib.gptq_moe_decode_workspace_bytes.argtypes = [MP, c_int, c_int]
     lib.gptq_moe_decode_forward.argtypes = lib.gptq_moe_forward.argtypes
     lib.gptq_describe_moe_decode_plan.argtypes = [MP, c_int, c_int, c_char_p, c_size_t]
+    lib.gptq_moe_batch_workspace_bytes.restype = c_size_t
+    lib.gptq_moe_batch_workspace_bytes.argtypes = [MP, c_int, c_int]
+    lib.gptq_moe_batch_forward.argtypes = lib.gptq_moe_forward.argtypes
+    lib.gptq_describe_moe_batch_plan.argtypes = [MP, c_int, c_int, c_char_p, c_size_t]
     lib.gptq_peer_scatter.argtypes = [POINTER(GptqPeerGroup), c_void_p, c_int, c_int, c_int, c_void_p]
     lib.gptq_peer_collect.argtypes = [POINTER(GptqPeerGroup), c_void_p, c_int, c_int, ctypes.c_uint32, c_void_p]
     lib.gptq_peer_gather.argtypes = [POINTER(GptqPeerGroup), c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_uint32, c_void_p]
@@ -181,7 +186,7 @@ def load() -> ctypes.CDLL:
         if name not in ("gptq_last_error", "gptq_status_string", "gptq_workspace_bytes", "gptq_workspace_bytes_ex",
                         "gptq_workspace_bytes_max", "gptq_workspace_bytes_multi", "gptq_workspace_bytes_multi_ex",
                         "gptq_workspace_bytes_mlp", "gptq_workspace_bytes_mlp_ex", "gptq_moe_table_bytes", "gptq_moe_workspace_bytes",
-                        "gptq_moe_decode_table_bytes", "gptq_moe_decode_workspace_bytes"):
+                        "gptq_moe_decode_table_bytes", "gptq_moe_decode_workspace_bytes", "gptq_moe_batch_workspace_bytes"):
             getattr(lib, name).restype = c_int
     got = lib.gptq_abi_version()
     if got != ABI_VERSION:
@@ -284,6 +289,18 @@ def describe_moe_decode_plan(moe: "GptqMoe", T: int, topk: int) -> dict:
     lib = load()
     buf = ctypes.create_string_buffer(512)
     check(lib.gptq_describe_moe_decode_plan(ctypes.byref(moe), T, topk, buf, len(buf)))
+    out = {}
+    for kv in buf.value.decode().split():
+        k, v = kv.split("=", 1)
+        out[k] = int(v) if v.lstrip("-").isdigit() else v
+    return out
+
+
+def describe_moe_batch_plan(moe: "GptqMoe", T: int, topk: int) -> dict:
+    """What gptq_moe_batch_forward would run for (moe, T, topk): path=batch with its tile geometry, or path=none with the reason (host-only query)."""
+    lib = load()
+    buf = ctypes.create_string_buffer(512)
+    check(lib.gptq_describe_moe_batch_plan(ctypes.byref(moe), T, topk, buf, len(buf)))
     out = {}
     for kv in buf.value.decode().split():
         k, v = kv.split("=", 1)

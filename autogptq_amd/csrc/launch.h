@@ -187,6 +187,11 @@ size_t moe_table_entry_bytes();
 void moe_table_entry(const gptq_layer_t& L, void* dst);
 hipError_t launch_moe(const gptq_moe_t& m, const void* table, const MoePlan& pl, const void* x, const int64_t* idx, const float* w, int T, int topk,
                       void* out, char* ws, hipStream_t st);
+// host-side launches of moe_route_kernel / moe_combine_kernel (tiles: int4 (expert, first row, rows, 0) per tile)
+hipError_t launch_moe_route(const int64_t* idx, int T, int topk, int E, int bm, int* offsets, int* tile_count, void* tiles, int* pos, int* row_assign,
+                            hipStream_t st);
+hipError_t launch_moe_combine(const int* pos, const float* w, const float* y, void* out, int T, int topk, int H, int ksplit, int rstride, int dtype,
+                              hipStream_t st);
 // moe_decode.hip: the same layer at 1..4 tokens on the experts' decode copy (gptq_moe_decode_forward): gate|up + silu * mul, down + combine -- two launches
 struct MoeDecodePlan {
     bool ok;                                        // the staged rows and constants fit the LDS
@@ -199,6 +204,19 @@ void moe_decode_table_entry(const gptq_layer_t& L, void* dst);
 hipError_t launch_moe_decode(const gptq_moe_t& m, const void* table, const MoeDecodePlan& pl, const void* x, const int64_t* idx, const float* w, int T, int topk,
                              void* out, char* ws, hipStream_t st);
 hipError_t init_moe_decode_device();
+// moe_rows.hip: the same layer at 5..64 tokens on the experts' decode copy (gptq_moe_batch_forward): route, gate|up + silu * mul, down, combine -- four
+// launches (act-order experts: + one row gather through perm in front of either GEMM)
+struct MoeBatchPlan {
+    bool act_pair, act_down;                        // some gate / up (down) expert is act-order: the gather pre-pass runs
+    int bm, s, tiles, launches;                     // tile height, strip-chunks per wave and chunk, tile bound
+    int waves_pair, waves_down, cpw_pair, cpw_down, lds_pair, lds_down;
+    size_t off_offsets, off_tile_count, off_tiles, off_pos, off_rows, off_h, off_y, off_xg, off_hg, bytes;   // workspace layout (from GPTQ_WORKSPACE_HEADER_BYTES on)
+};
+bool moe_batch_group_ok(const gptq_layer_t& L);    // a group size the rows family takes
+MoeBatchPlan plan_moe_batch(const gptq_moe_t& m, int T, int topk);
+hipError_t launch_moe_batch(const gptq_moe_t& m, const void* table, const MoeBatchPlan& pl, const void* x, const int64_t* idx, const float* w, int T, int topk,
+                            void* out, char* ws, hipStream_t st);
+hipError_t init_moe_batch_device();
 hipError_t launch_unpack_weights(const uint32_t* qweight, int K, int N, int bits, uint8_t* w_out, hipStream_t st);
 hipError_t launch_unpack_zeros(const uint32_t* qzeros, int G, int N, int bits, int zero_mode, int32_t* z_out, hipStream_t st);
 hipError_t launch_pack_weights(const void* W, const void* scale_in, const void* zero_in, const int32_t* g_idx,

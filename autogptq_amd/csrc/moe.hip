@@ -400,28 +400,48 @@ MoePlan plan_moe(int E, int T, int topk, int H, int I, int dtype) {
     return pl;
 }
 
+// host-side launch helpers of the routing and the combine kernel (moe_rows.hip launches them around its own GEMMs)
+hipError_t launch_moe_route(const int64_t* idx, int T, int topk, int E, int bm, int* offsets, int* tile_count, void* tiles, int* pos, int* row_assign,
+                            hipStream_t st) {
+    moe::RouteArgs ra;
+    ra.idx = (const long long*)idx;
+    ra.T = T; ra.topk = topk; ra.E = E; ra.bm = bm;
+    ra.offsets = offsets;
+    ra.tile_count = tile_count;
+    ra.tiles = (int4*)tiles;
+    ra.pos = pos;
+    ra.row_assign = row_assign;
+    hipLaunchKernelGGL(moe::moe_route_kernel, dim3(1), dim3(moe::ROUTE_THREADS), 0, st, ra);
+    return hipGetLastError();
+}
+
+hipError_t launch_moe_combine(const int* pos, const float* w, const float* y, void* out, int T, int topk, int H, int ksplit, int rstride, int dtype,
+                              hipStream_t st) {
+    moe::CombineArgs c;
+    c.pos = pos; c.w = w; c.y = y; c.out = out;
+    c.T = T; c.topk = topk; c.H = H; c.ksplit = ksplit; c.rstride = rstride; c.dtype = dtype;
+    const long items = (long)T * (H / 4);
+    hipLaunchKernelGGL(moe::moe_combine_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, c);
+    return hipGetLastError();
+}
+
 hipError_t launch_moe(const gptq_moe_t& m, const void* table, const MoePlan& pl, const void* x, const int64_t* idx, const float* w, int T, int topk,
                       void* out, char* ws, hipStream_t st) {
     const gptq_layer_t& G = *m.gate[0];
     const gptq_layer_t& D = *m.down[0];
     const int E = m.E, H = G.K, I = G.N;
     const int R = T * topk;
-    moe::RouteArgs ra;
-    ra.idx = (const long long*)idx;
-    ra.T = T; ra.topk = topk; ra.E = E; ra.bm = pl.bm;
-    ra.offsets = (int*)(ws + pl.off_offsets);
-    ra.tile_count = (int*)(ws + pl.off_tile_count);
-    ra.tiles = (int4*)(ws + pl.off_tiles);
-    ra.pos = (int*)(ws + pl.off_pos);
-    ra.row_assign = (int*)(ws + pl.off_rows);
-    hipLaunchKernelGGL(moe::moe_route_kernel, dim3(1), dim3(moe::ROUTE_THREADS), 0, st, ra);
-    hipError_t e = hipGetLastError();
+    int* const tile_count = (int*)(ws + pl.off_tile_count);
+    int4* const tiles = (int4*)(ws + pl.off_tiles);
+    int* const pos = (int*)(ws + pl.off_pos);
+    int* const row_assign = (int*)(ws + pl.off_rows);
+    hipError_t e = launch_moe_route(idx, T, topk, E, pl.bm, (int*)(ws + pl.off_offsets), tile_count, tiles, pos, row_assign, st);
     if (e != hipSuccess) return e;
 
     moe::GemmArgs g;
     g.table = (const moe::ExpertPtrs*)table;
-    g.E = E; g.pair = 1; g.a = x; g.row_assign = ra.row_assign; g.topk = topk;
-    g.tile_count = ra.tile_count; g.tiles = ra.tiles;
+    g.E = E; g.pair = 1; g.a = x; g.row_assign = row_assign; g.topk = topk;
+    g.tile_count = tile_count; g.tiles = tiles;
     g.K = H; g.N = I; g.bits = G.bits; g.group_size = G.group_size; g.zero_mode = G.zero_mode;
     g.nblk = I / moe::BN; g.ksplit = 1; g.steps_per_split = H / 32;
     g.out = ws + pl.off_h; g.rstride = R;
@@ -442,12 +462,7 @@ hipError_t launch_moe(const gptq_moe_t& m, const void* table, const MoePlan& pl,
     d.out = ws + pl.off_y;
     if ((e = gemm(d, (long)pl.tiles * d.nblk * d.ksplit)) != hipSuccess) return e;
 
-    moe::CombineArgs c;
-    c.pos = ra.pos; c.w = w; c.y = (const float*)(ws + pl.off_y); c.out = out;
-    c.T = T; c.topk = topk; c.H = H; c.ksplit = pl.ksplit; c.rstride = R; c.dtype = G.dtype;
-    const long items = (long)T * (H / 4);
-    hipLaunchKernelGGL(moe::moe_combine_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, c);
-    return hipGetLastError();
+    return launch_moe_combine(pos, w, (const float*)(ws + pl.off_y), out, T, topk, H, pl.ksplit, R, G.dtype, st);
 }
 
 size_t moe_table_entry_bytes() { return sizeof(moe::ExpertPtrs); }

@@ -1,0 +1,460 @@
+// moe_rows.hip -- routed mixture-of-experts layers at batched-decode row counts (gptq_moe_batch_forward): 5..64 tokens on the experts' DECODE COPY.
+//
+// What one call computes: the formulas and the ARITHMETIC CONTRACT of the grouped path (moe.hip): every W bit-exact to gptq_dequant, products and sums in fp32
+// on the matrix core, h rounded once, out[t] = T(sum_j w[t, j] * y_(t, j)) in ascending j with one rounding; assignments outside [0, E) are dropped.
+// Four launches, no host round trip (capturable):
+//   1. moe_route_kernel (moe.hip) with bm = 16: sorted rows, pos, row_assign and the tile table (expert, first row, rows <= 16) with its count.
+//   2. moe_rows_kernel<T, BITS>, pair form: a workgroup = one tile x 2 adjacent 16-column strips of W1_e AND the same 2 strips of W3_e x the whole K;
+//      silu * mul on the fp32 sums -> H_sorted [R][I] in T.
+//   3. moe_rows_kernel<T, BITS>, down form: a workgroup = one tile x 4 adjacent strips of W2_e x the whole K -> Y [R][H] fp32.
+//   4. moe_combine_kernel (moe.hip), one slice.
+// The grid is the bound tiles <= floor(T topk / 16) + min(E, T topk) times the strip groups; workgroups past the tile count the routing kernel wrote return
+// at once (the strip group is the fast index: they are the end of the grid).
+//
+// moe_rows_kernel is the dense rows kernel (gemm_rows_kernel.cuh, RB = 1) with the expert, the rows and the strips looked up per workgroup.  The waves split
+// the 128-deep chunks of K into contiguous ranges and meet once in LDS, in wave order.  Per chunk a wave
+//   * loads NS = 4 strip-chunks of the copy (1 KiB each at 4 bits, two 64-deep halves at 8; lane = 32 consecutive k of one column) and their constants
+//     (qconst_tiled records) from the expert's entries of the decode table: inline-asm loads behind hand-counted s_waitcnt vmcnt, a ring of DW chunks in flight;
+//   * stages its 16 rows x 128 k of the A operand by LDS DMA into wave-private double buffers (no barrier in the K loop).  The DMA's per-lane global address
+//     gathers the rows: row r of the tile is x[row_assign[first + r] / topk] (pair form) or H_sorted[first + r] (down form); the XOR swizzle against the
+//     256-byte row pitch is applied on the global side, as in the rows kernel.  Rows past the tile's count repeat its last row and are not stored;
+//   * dequantises with rowsk::Deq1 / Deq1_8 (bit-exact W, one rounding) and runs v_mfma_f32_16x16x32_{f16,bf16} (rowsk::Mma16).
+// No K slices, no atomics: every output is one fixed-order sum -- bit-reproducible, and a token's row depends only on that token's x, indices and weights
+// (the fp32 sum of a row does not depend on which other rows share its tile: the MFMA rows are independent).
+// The pair / down form, the group mode and the number of staged planes are run-time uniform: T x BITS = four instantiations.
+//
+// ACT-ORDER experts (the copy is made of the re-sequenced rows): one small untyped 2-byte gather pre-pass, moe_gather_rows_kernel,
+// rows_out[r][i] = rows_in[src(r)][perm_e(r)[i]], runs before the pair stage (x through W1_e's perm into plane 0 and through W3_e's perm into plane 1 -- gate
+// and up of an expert may have different activation orders; the pair form then stages BOTH planes, W1's strips multiply plane 0 and W3's plane 1) and again
+// between the stages (H_sorted through W2_e's perm): six launches.  Plain experts do not pay for it.  Built instead of an LDS -> LDS gather inside the K loop
+// because a chunk's 128 positions of perm point anywhere in the row: the wave would have to stage whole rows (16 x K x 2 bytes: 448 KiB at K = 14336), not
+// chunks, which is what the decode kernel does for ONE row and does not scale to 16.
+//
+// GEOMETRY (cost model in the style of plan_rows).  Per chunk and strip a workgroup pulls 1 KiB of weights (HBM) and, per chunk, 4 KiB of rows (L2); with NS
+// strips behind one staged chunk the row traffic is 4 / NS KiB per KiB of weights.  NS = 4: a workgroup pulls 2x its weight bytes in all; at the measured
+// 105 - 125 GB/s per CU the 256 CUs pull ~14 TB/s of weights, above the 8 TB/s HBM gives, so the row pulls hide.  NS = 2 would halve the headroom below HBM
+// speed; NS = 8 needs 8 x 4 (x 2 at 8 bits) registers per ring slot x DW slots plus 8 accumulators: past 128 VGPRs, and half the workgroups.
+// Dequant issue: 13 VALU per 8 weights = 208 per lane and chunk at NS = 4 against 16 MFMAs (8 passes each): ~340 cycles per chunk and wave, 4 KiB per
+// 340 cycles and wave; a CU needs 16 waves (2 workgroups of 8) for 105 GB/s at 2.4 GHz -- 8 waves x 8 KiB of x buffers = 64 KiB of LDS, two workgroups
+// per CU (act-order pair form: two planes, 128 KiB, one workgroup).  Waves: min(8, chunks / 2) so that every wave runs at least two chunks behind its ring.
+// Pair form: both projections in every wave (2 + 2 strips behind the same staged chunk) rather than half the waves each: the halves would stage the same
+// rows twice.  Rounds: +~2 us per round of 256 workgroups x 2; Mixtral at T = 16 (<= 10 tiles): pair 10 x 448 = 4480 workgroups of 128 KiB, down 10 x 64 =
+// 640 of 448 KiB.
+#include <string.h>
+
+#include <algorithm>
+
+#include "common.cuh"
+#include "launch.h"
+#include "gemm_rows_kernel.cuh"      // rowsk::Deq1<T> / Deq1_8<T>, rowsk::Mma16<T>
+
+namespace gptq {
+namespace moerows {
+
+constexpr int NS = 4;                           // strip-chunks per wave and chunk (pair: 2 of W1 + 2 of W3; down: 4 of W2)
+constexpr int MAX_WAVES = 8;
+constexpr int BM = 16;
+constexpr int XB = 4096;                        // 16 rows x 128 k x 2 bytes
+constexpr int MAX_LDS = 160 * 1024;
+
+struct Entry {                                  // one (projection, expert) of the decode table (moe_decode.hip fills it): [3 projections][E], 32 bytes
+    const unsigned* tq;                         // qweight_tiled
+    const void* cst;                            // qconst_tiled
+    const int* perm;                            // NULL: sequential groups
+    const void* reserved;
+};
+
+struct Args {
+    const Entry* table;                         // entries of the first projection (pair: W1; W3 is table + E)
+    int E, pair;
+    const void* a;                              // rows of the A operand [.][K]; planes > 1: plane q at a + q * plane_bytes
+    size_t plane_bytes;
+    const int* row_assign;                      // non-NULL: row r of the tile is a[row_assign[first + r] / topk]; NULL: a[first + r]
+    int topk, planes;
+    const int* tile_count;
+    const int4* tiles;
+    int K, N, chunks, groups, gshift, gm, cpw, nsg;
+    void* out;                                  // pair: H_sorted [R][N] (T); down: Y [R][N] fp32
+};
+
+typedef unsigned u32x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ Entry load_entry(const Entry* p) {      // every lane loads the same 32 bytes; readfirstlane makes the pointers scalars
+    const u32x8 v = *(const u32x8*)p;
+    u32x8 o;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) o[i] = __builtin_amdgcn_readfirstlane(v[i]);
+    return __builtin_bit_cast(Entry, o);
+}
+
+// 4 bits: compiled for 128 registers (two 8-wave workgroups per CU); 8 bits: a ring slot is twice as large -- 256 registers, one workgroup per CU
+template <typename T, int BITS>
+__global__ void __launch_bounds__(BITS == 8 ? 512 : 1024) moe_rows_kernel(Args p) {
+    constexpr int NH = BITS == 8 ? 2 : 1;                      // chunks of the copy per 128-deep chunk of the rows
+    constexpr unsigned REC = BITS == 8 ? 64u : 48u, WCH = 1024u;
+    constexpr int NDMA = 4, NW = 3 * NH * NS;                  // DMA instructions of one plane of a chunk; a chunk's weight + constant loads
+    constexpr int DW = 2;                                      // ring of chunks in flight per wave (4 bits: 48 registers, 8 bits: 96)
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = blockDim.x >> 6;
+    const int sgi = blockIdx.x % p.nsg, tile = blockIdx.x / p.nsg;
+    if (tile >= *p.tile_count) return;
+    const int4 tl = p.tiles[tile];
+    const int e = __builtin_amdgcn_readfirstlane(tl.x), row0 = __builtin_amdgcn_readfirstlane(tl.y), rows = __builtin_amdgcn_readfirstlane(tl.z);
+    const int S = p.pair ? NS / 2 : NS, s0 = sgi * S;
+    const int planes = p.planes;
+    const int r = lane & 15, g = lane >> 4;
+
+    const Entry e0 = load_entry(p.table + e);
+    const Entry e1 = p.pair ? load_entry(p.table + p.E + e) : e0;
+    const char* wb[NS];
+    const char* cb[NS];
+#pragma unroll
+    for (int v = 0; v < NS; ++v) {
+        const bool up = p.pair && v >= NS / 2;
+        const int strip = s0 + (up ? v - NS / 2 : v);
+        wb[v] = (const char*)(up ? e1.tq : e0.tq) + (size_t)strip * (size_t)(p.chunks * NH) * WCH;
+        cb[v] = (const char*)(up ? e1.cst : e0.cst) + (size_t)strip * (size_t)p.groups * REC;
+    }
+
+    char* const xbuf = smem + (size_t)wave * 2 * planes * XB;      // buffer b, plane q: xbuf + (b planes + q) XB
+    const unsigned xbuf_lds = lds_addr_of(xbuf);
+    // DMA i of a plane (4 rows x 256 bytes): lane (rr = lane >> 4, slot = lane & 15) fetches piece slot ^ (row & 15) of row 4 i + rr, so that LDS slot s of row R
+    // holds piece s ^ (R & 15) (gemm_rows_kernel.cuh); the row itself is looked up here
+    unsigned xoff[NDMA];
+#pragma unroll
+    for (int i = 0; i < NDMA; ++i) {
+        const int row = 4 * i + g;
+        const int sr = row0 + min(row, rows - 1);              // rows past the tile repeat its last one (their outputs are not stored)
+        const int m = p.row_assign ? p.row_assign[sr] / p.topk : sr;
+        xoff[i] = (unsigned)m * (unsigned)p.K * 2u + (unsigned)((r ^ (row & 15)) * 16);
+    }
+    unsigned aoff[4];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const int piece = BITS == 8 ? 8 * (w >> 1) + 2 * g + (w & 1) : 4 * g + w;
+        aoff[w] = (unsigned)(r * 256 + ((piece ^ r) * 16));
+    }
+    const unsigned a3off = planes > 1 ? (unsigned)XB : 0u;     // W3's strips read plane 1 when there is one
+    const unsigned wlane = (unsigned)lane * 16u;
+    const int gm = p.gm;
+    const unsigned glane = BITS == 8 ? (gm == 2 ? (unsigned)(g >> 1) * REC : 0u) : (gm == 2 ? (unsigned)g * REC : (gm == 1 ? (unsigned)(g >> 1) * REC : 0u));
+    const unsigned slane = glane + (unsigned)r * 2u, zlane = glane + 32u + (unsigned)r * (BITS == 8 ? 2u : 1u);
+    const int c0 = wave * p.cpw, c1 = min(c0 + p.cpw, p.chunks);
+
+    struct Buf { u32x4 wq[NS][NH]; unsigned cs[NS][NH], cz[NS][NH]; };
+    Buf q[DW];
+    // every register of the ring starts as its own opaque definition: the compiler cannot share one between two loads' destinations and split them with a
+    // copy behind the first load
+#pragma unroll
+    for (int j = 0; j < DW; ++j)
+#pragma unroll
+        for (int v = 0; v < NS; ++v)
+#pragma unroll
+            for (int h = 0; h < NH; ++h) {
+                asm volatile("; ring slot" : "=v"(q[j].wq[v][h]));
+                asm volatile("v_mov_b32 %0, 0" : "=v"(q[j].cs[v][h]));
+                asm volatile("v_mov_b32 %0, 0" : "=v"(q[j].cz[v][h]));
+            }
+    auto issue_w = [&](int c, Buf& B) __attribute__((always_inline)) {
+#pragma unroll
+        for (int v = 0; v < NS; ++v) {
+            const char* const wv = wb[v];
+            const char* const cv = cb[v];
+#pragma unroll
+            for (int h = 0; h < NH; ++h) {
+                const char* wsrc = wv + (size_t)(c * NH + h) * WCH;
+                const int grp = gm == 0 ? min(c >> p.gshift, p.groups - 1) : (BITS == 8 ? (gm == 1 ? 2 * c + h : 4 * c + 2 * h) : (gm == 1 ? 2 * c : 4 * c));
+                const char* csrc = cv + (size_t)grp * REC;
+                asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(B.wq[v][h]) : "v"(wlane), "s"(wsrc) : "memory");
+                asm volatile("global_load_ushort %0, %1, %2" : "=v"(B.cs[v][h]) : "v"(slane), "s"(csrc) : "memory");
+                if constexpr (BITS == 8) asm volatile("global_load_ushort %0, %1, %2" : "=v"(B.cz[v][h]) : "v"(zlane), "s"(csrc) : "memory");
+                else asm volatile("global_load_ubyte %0, %1, %2" : "=v"(B.cz[v][h]) : "v"(zlane), "s"(csrc) : "memory");
+            }
+        }
+    };
+    // DMAs [i0, i1) of chunk c's rows (every plane) into buffer b
+    auto issue_x = [&](int c, int b, int i0, int i1) __attribute__((always_inline)) {
+        const char* xsrc = (const char*)p.a + (size_t)c * 256;
+        const unsigned l0 = __builtin_amdgcn_readfirstlane(xbuf_lds + (unsigned)(b * planes * XB));
+#pragma unroll
+        for (int i = i0; i < i1; ++i) {
+            const unsigned xo = xoff[i];
+            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(l0 + (unsigned)(i * 1024)), "v"(xo), "s"(xsrc) : "memory");
+            if (planes > 1) {
+                const char* xsrc1 = xsrc + p.plane_bytes;
+                asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(l0 + (unsigned)(XB + i * 1024)), "v"(xo), "s"(xsrc1) : "memory");
+            }
+        }
+    };
+    // the registers pass through a statement behind the wait so that no use of them is scheduled in front of it
+    auto claim = [&](Buf& B) __attribute__((always_inline)) {
+#pragma unroll
+        for (int v = 0; v < NS; ++v)
+#pragma unroll
+            for (int h = 0; h < NH; ++h) asm volatile("" : "+v"(B.wq[v][h]), "+v"(B.cs[v][h]), "+v"(B.cz[v][h])::"memory");
+    };
+
+    f32x4 acc[NS];
+#pragma unroll
+    for (int v = 0; v < NS; ++v) acc[v] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    // chunk in buffer b; the NEXT chunk's DMAs (cn, into the other buffer) are issued a quarter at a time behind the MFMAs of each step (gemm_rows_kernel.cuh)
+    auto compute = [&](const Buf& B, int b, int cn, bool has_x) __attribute__((always_inline)) {
+        typename rowsk::DeqSel<T, BITS>::type dq[NS][NH];
+#pragma unroll
+        for (int v = 0; v < NS; ++v)
+#pragma unroll
+            for (int h = 0; h < NH; ++h) dq[v][h].setup(B.cs[v][h], B.cz[v][h]);
+        const char* xb = xbuf + b * planes * XB;
+        u32x4 a1[4], a3[4];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            a1[w] = *(const u32x4*)(xb + aoff[w]);
+            a3[w] = *(const u32x4*)(xb + a3off + aoff[w]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+#pragma unroll
+            for (int v = 0; v < NS; ++v) {
+                u32x4 bq;
+                if constexpr (BITS == 4) bq = dq[v][0].frag(B.wq[v][0][w]);
+                else bq = dq[v][w >> 1].frag(B.wq[v][w >> 1][2 * (w & 1)], B.wq[v][w >> 1][2 * (w & 1) + 1]);
+                acc[v] = rowsk::Mma16<T>::run(v < NS / 2 ? a1[w] : a3[w], bq, acc[v]);
+            }
+            if (has_x) issue_x(cn, b ^ 1, w, w + 1);
+        }
+    };
+
+    if (c0 < c1) {
+#pragma unroll
+        for (int j = 0; j < DW; ++j)
+            if (c0 + j < c1) issue_w(c0 + j, q[j]);
+        issue_x(c0, 0, 0, NDMA);
+        for (int cbase = c0; cbase < c1; cbase += DW) {
+#pragma unroll
+            for (int j = 0; j < DW; ++j) {
+                const int c = cbase + j;
+                if (c >= c1) break;
+                // VMEM queue, oldest first: W(c0 .. c0 + DW - 1), x(c0) | x(c0 + 1) under the MFMAs of c0, W(c0 + DW) | x(c0 + 2), W(c0 + DW + 1) | ...
+                // chunk c needs x(c) and everything older (W(c) is); behind x(c) there is only W(c + DW - 1), issued at the end of the previous iteration
+                const bool has_w = c > c0 && c + DW - 1 < c1;
+                if (has_w) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NW) : "memory");
+                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                claim(q[j]);
+                compute(q[j], j & 1, c + 1, c + 1 < c1);
+                if (c + DW < c1) issue_w(c + DW, q[j]);
+            }
+        }
+    }
+    // every destination register of the ring passes through a statement behind a full wait: nothing is in flight into a register the epilogue reuses
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int j = 0; j < DW; ++j) claim(q[j]);
+
+    // ---- the waves' sums meet in LDS (wave order), epilogue, store ------------------------------------------------------------------------------
+    __syncthreads();                                           // every wave is done with its x buffers
+    float* const red = (float*)smem;                           // [wave][v][lane] float4
+#pragma unroll
+    for (int v = 0; v < NS; ++v) *(f32x4*)(red + ((size_t)(wave * NS + v) * 64 + lane) * 4) = acc[v];
+    __syncthreads();
+    auto wsum = [&](int v, int l) -> f32x4 {
+        f32x4 s = *(const f32x4*)(red + ((size_t)v * 64 + l) * 4);
+        for (int w = 1; w < nw; ++w) s += *(const f32x4*)(red + ((size_t)(w * NS + v) * 64 + l) * 4);
+        return s;
+    };
+    const int N = p.N;
+    for (int item = tid; item < S * 64; item += (int)blockDim.x) {
+        const int l = item & 63, v = item >> 6;
+        const int n = (s0 + v) * 16 + (l & 15);
+        const f32x4 sg = wsum(v, l);
+        if (p.pair) {
+            const f32x4 su = wsum(v + NS / 2, l);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {                      // C/D layout of the 16x16 MFMA: row = 4 (lane >> 4) + i, column = lane & 15
+                const int row = 4 * (l >> 4) + i;
+                const float gv = sg[i];
+                if (row < rows) ((T*)p.out)[(size_t)(row0 + row) * N + n] = DType<T>::from_f32(gv / (1.f + __expf(-gv)) * su[i]);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int row = 4 * (l >> 4) + i;
+                if (row < rows) ((float*)p.out)[(size_t)(row0 + row) * N + n] = sg[i];
+            }
+        }
+    }
+}
+
+// act-order pre-pass, untyped 2-byte elements: out[plane][r][i] = in[src(r)][perm[i]], perm = that of expert e(r)'s entry of projection (first + plane);
+// src(r) = row_assign[r] / topk (topk > 0: the token's row of x) or r (topk = 0: H_sorted).  A thread = one 16-byte piece.  Entries without a perm: a copy.
+struct GatherArgs {
+    const Entry* table;
+    const long long* idx;
+    const int* row_assign;
+    const int* offsets;                         // [E + 1]: offsets[E] = sorted rows in use
+    const unsigned short* in;
+    unsigned short* out;                        // [planes][R][K]
+    int E, topk, K, R;
+};
+
+__global__ void __launch_bounds__(256) moe_gather_rows_kernel(GatherArgs p) {
+    const int r = blockIdx.y, plane = blockIdx.z;
+    if (r >= p.offsets[p.E]) return;
+    const int piece = blockIdx.x * 256 + threadIdx.x;
+    if (piece >= (p.K >> 3)) return;
+    const int a = p.row_assign[r];
+    const int e = (int)p.idx[a];                               // a sorted row in use belongs to a valid expert
+    const int* __restrict__ perm = p.table[(size_t)plane * p.E + e].perm;
+    const unsigned short* __restrict__ src = p.in + (size_t)(p.topk ? a / p.topk : r) * p.K;
+    u32x4 o;
+    if (perm) {
+        const int4 pa = *(const int4*)(perm + piece * 8), pb = *(const int4*)(perm + piece * 8 + 4);
+        o[0] = (unsigned)src[pa.x] | ((unsigned)src[pa.y] << 16);
+        o[1] = (unsigned)src[pa.z] | ((unsigned)src[pa.w] << 16);
+        o[2] = (unsigned)src[pb.x] | ((unsigned)src[pb.y] << 16);
+        o[3] = (unsigned)src[pb.z] | ((unsigned)src[pb.w] << 16);
+    } else {
+        o = *(const u32x4*)(src + piece * 8);
+    }
+    *(u32x4*)(p.out + ((size_t)plane * p.R + r) * p.K + piece * 8) = o;
+}
+
+template <typename T, int BITS>
+static hipError_t launch_one(const Args& a, long blocks, int waves, int lds, hipStream_t st) {
+    hipLaunchKernelGGL((moe_rows_kernel<T, BITS>), dim3((unsigned)blocks), dim3(waves * 64), lds, st, a);
+    return hipGetLastError();
+}
+static hipError_t launch_any(int dtype, int bits, const Args& a, long blocks, int waves, int lds, hipStream_t st) {
+    if (blocks <= 0) return hipSuccess;
+    if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
+    if (dtype == GPTQ_F16) return bits == 4 ? launch_one<f16, 4>(a, blocks, waves, lds, st) : launch_one<f16, 8>(a, blocks, waves, lds, st);
+    return bits == 4 ? launch_one<bf16, 4>(a, blocks, waves, lds, st) : launch_one<bf16, 8>(a, blocks, waves, lds, st);
+}
+
+static int group_mode(const gptq_layer_t& L) {                  // what the rows family takes: 0 = 128 2^n or one group, 1 = 64, 2 = 32
+    if (L.group_size >= 128) {
+        if (L.group_size >= L.K) return 0;
+        const int q = L.group_size / 128;
+        return (L.group_size % 128 == 0 && (q & (q - 1)) == 0) ? 0 : -1;
+    }
+    return L.group_size == 64 ? 1 : (L.group_size == 32 ? 2 : -1);
+}
+
+}  // namespace moerows
+
+static size_t b256(size_t b) { return (b + 255) & ~(size_t)255; }
+static bool any_perm_of(const gptq_layer_t* const* Ls, int E) {
+    for (int e = 0; e < E; ++e)
+        if (Ls[e]->perm) return true;
+    return false;
+}
+
+bool moe_batch_group_ok(const gptq_layer_t& L) { return moerows::group_mode(L) >= 0; }
+
+MoeBatchPlan plan_moe_batch(const gptq_moe_t& m, int T, int topk) {
+    MoeBatchPlan pl{};
+    const gptq_layer_t& G = *m.gate[0];
+    const int E = m.E, H = G.K, I = G.N;
+    const long R = (long)T * topk;
+    pl.bm = moerows::BM;
+    pl.s = moerows::NS;
+    pl.tiles = (int)(R / moerows::BM + std::min<long>(E, R));
+    pl.act_pair = any_perm_of(m.gate, E) || any_perm_of(m.up, E);
+    pl.act_down = any_perm_of(m.down, E);
+    auto waves_for = [](int K) { return std::max(1, std::min(moerows::MAX_WAVES, K / 128 / 2)); };
+    pl.waves_pair = waves_for(H);
+    pl.waves_down = waves_for(I);
+    pl.cpw_pair = (H / 128 + pl.waves_pair - 1) / pl.waves_pair;
+    pl.cpw_down = (I / 128 + pl.waves_down - 1) / pl.waves_down;
+    pl.waves_pair = (H / 128 + pl.cpw_pair - 1) / pl.cpw_pair;      // no wave without a chunk
+    pl.waves_down = (I / 128 + pl.cpw_down - 1) / pl.cpw_down;
+    pl.lds_pair = pl.waves_pair * 2 * (pl.act_pair ? 2 : 1) * moerows::XB;      // >= the waves' sums (waves x NS x 1 KiB)
+    pl.lds_down = pl.waves_down * 2 * moerows::XB;
+    pl.launches = T > 0 ? 4 + (pl.act_pair ? 1 : 0) + (pl.act_down ? 1 : 0) : 0;
+    const size_t es = dtype_size(G.dtype);
+    size_t o = GPTQ_WORKSPACE_HEADER_BYTES;                      // the header of a shared workspace belongs to the other entry points: left as it is
+    pl.off_offsets = o; o += b256(4 * (size_t)(E + 1));
+    pl.off_tile_count = o; o += 256;
+    pl.off_tiles = o; o += b256(16 * (size_t)pl.tiles);
+    pl.off_pos = o; o += b256(4 * (size_t)R);
+    pl.off_rows = o; o += b256(4 * (size_t)R);
+    pl.off_h = o; o += b256((size_t)R * I * es);
+    pl.off_y = o; o += b256((size_t)R * H * 4);
+    pl.off_xg = o; o += b256(2 * (size_t)R * H * es);            // act-order: x through W1's / W3's perm (two planes)
+    pl.off_hg = o; o += b256((size_t)R * I * es);                // act-order: H_sorted through W2's perm
+    pl.bytes = o;
+    return pl;
+}
+
+hipError_t launch_moe_batch(const gptq_moe_t& m, const void* table, const MoeBatchPlan& pl, const void* x, const int64_t* idx, const float* w, int T, int topk,
+                            void* out, char* ws, hipStream_t st) {
+    const gptq_layer_t& G = *m.gate[0];
+    const gptq_layer_t& D = *m.down[0];
+    const int E = m.E, H = G.K, I = G.N;
+    const int R = T * topk;
+    int* const offsets = (int*)(ws + pl.off_offsets);
+    int* const tile_count = (int*)(ws + pl.off_tile_count);
+    int* const pos = (int*)(ws + pl.off_pos);
+    int* const row_assign = (int*)(ws + pl.off_rows);
+    hipError_t e = launch_moe_route(idx, T, topk, E, pl.bm, offsets, tile_count, ws + pl.off_tiles, pos, row_assign, st);
+    if (e != hipSuccess) return e;
+
+    const moerows::Entry* const tab = (const moerows::Entry*)table;
+    auto gather = [&](const moerows::Entry* t, int planes, int tk, const void* in, void* o, int K) -> hipError_t {
+        moerows::GatherArgs ga;
+        ga.table = t; ga.idx = (const long long*)idx; ga.row_assign = row_assign; ga.offsets = offsets;
+        ga.in = (const unsigned short*)in; ga.out = (unsigned short*)o;
+        ga.E = E; ga.topk = tk; ga.K = K; ga.R = R;
+        hipLaunchKernelGGL(moerows::moe_gather_rows_kernel, dim3((K / 8 + 255) / 256, R, planes), dim3(256), 0, st, ga);
+        return hipGetLastError();
+    };
+    auto fill = [&](moerows::Args& a, const gptq_layer_t& L, int cpw, int s) {
+        a.E = E; a.topk = topk;
+        a.tile_count = tile_count; a.tiles = (const int4*)(ws + pl.off_tiles);
+        a.K = L.K; a.N = L.N; a.chunks = L.K / 128;
+        a.groups = (L.K + L.group_size - 1) / L.group_size;
+        a.gshift = 31;
+        if (L.group_size >= 128 && L.group_size < L.K) a.gshift = __builtin_ctz((unsigned)(L.group_size / 128));
+        a.gm = moerows::group_mode(L);
+        a.cpw = cpw; a.nsg = L.N / 16 / s;
+    };
+
+    moerows::Args g{};
+    g.table = tab; g.pair = 1;
+    if (pl.act_pair) {
+        if ((e = gather(tab, 2, topk, x, ws + pl.off_xg, H)) != hipSuccess) return e;
+        g.a = ws + pl.off_xg; g.plane_bytes = (size_t)R * H * 2; g.row_assign = nullptr; g.planes = 2;
+    } else {
+        g.a = x; g.plane_bytes = 0; g.row_assign = row_assign; g.planes = 1;
+    }
+    g.out = ws + pl.off_h;
+    fill(g, G, pl.cpw_pair, moerows::NS / 2);
+    if ((e = moerows::launch_any(G.dtype, G.bits, g, (long)pl.tiles * g.nsg, pl.waves_pair, pl.lds_pair, st)) != hipSuccess) return e;
+
+    moerows::Args d{};
+    d.table = tab + 2 * (size_t)E; d.pair = 0;
+    if (pl.act_down) {
+        if ((e = gather(tab + 2 * (size_t)E, 1, 0, ws + pl.off_h, ws + pl.off_hg, I)) != hipSuccess) return e;
+        d.a = ws + pl.off_hg;
+    } else {
+        d.a = ws + pl.off_h;
+    }
+    d.plane_bytes = 0; d.row_assign = nullptr; d.planes = 1;
+    d.out = ws + pl.off_y;
+    fill(d, D, pl.cpw_down, moerows::NS);
+    if ((e = moerows::launch_any(D.dtype, D.bits, d, (long)pl.tiles * d.nsg, pl.waves_down, pl.lds_down, st)) != hipSuccess) return e;
+
+    return launch_moe_combine(pos, w, (const float*)(ws + pl.off_y), out, T, topk, H, 1, R, G.dtype, st);
+}
+
+// grants > 64 KiB of dynamic LDS (act-order pair form: two planes of x buffers)
+hipError_t init_moe_batch_device() {
+    hipError_t e = hipSuccess;
+    auto grant = [&](auto kern) { hipError_t r = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, moerows::MAX_LDS); if (e == hipSuccess) e = r; };
+    grant(moerows::moe_rows_kernel<f16, 4>); grant(moerows::moe_rows_kernel<f16, 8>);
+    grant(moerows::moe_rows_kernel<bf16, 4>); grant(moerows::moe_rows_kernel<bf16, 8>);
+    return e;
+}
+
+}  // namespace gptq

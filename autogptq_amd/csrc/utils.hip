@@ -14,30 +14,38 @@
 namespace gptq {
 
 // ---------------------------------------------------------------------------------------------
-template <int BITS>
-__global__ void __launch_bounds__(256) unpack_weights_kernel(const unsigned* __restrict__ qweight, int units, int N,
+// (bits is a run-time, workgroup-uniform argument: a load-time integer kernel needs one instantiation, not one per packing)
+__global__ void __launch_bounds__(256) unpack_weights_kernel(const unsigned* __restrict__ qweight, int units, int N, int bits,
                                                              uint8_t* __restrict__ out) {
-    constexpr int UW = Pack<BITS>::words, KPU = Pack<BITS>::vals;
+    const int UW = unit_words(bits), KPU = unit_vals(bits);
     const int n0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
     const int u = blockIdx.y;
     if (n0 >= N || u >= units) return;
-    u32x4 q[UW];
+    // the unit's little-endian bit stream of each of the 4 columns: bits 0..63 and (3-bit only) 64..95
+    const u32x4 q0 = *(const u32x4*)(qweight + (size_t)(u * UW) * N + n0);
+    u32x4 q1 = u32x4{0u, 0u, 0u, 0u}, q2 = q1;
+    if (UW == 3) {
+        q1 = *(const u32x4*)(qweight + (size_t)(u * UW + 1) * N + n0);
+        q2 = *(const u32x4*)(qweight + (size_t)(u * UW + 2) * N + n0);
+    }
+    const unsigned maxq = (1u << bits) - 1u;
+    for (int v = 0; v < KPU; ++v) {
+        const int bit = bits * v;
+        unsigned o = 0;
 #pragma unroll
-    for (int w = 0; w < UW; ++w) q[w] = *(const u32x4*)(qweight + (size_t)(u * UW + w) * N + n0);
-    [&]<int... V>(std::integer_sequence<int, V...>) {
-        (([&] {
-             unsigned o = 0;
-#pragma unroll
-             for (int c = 0; c < 4; ++c) {
-                 unsigned w[UW];
-#pragma unroll
-                 for (int i = 0; i < UW; ++i) w[i] = q[i][c];
-                 o |= unit_field<BITS, V>(w) << (8 * c);
-             }
-             *(unsigned*)(out + (size_t)(u * KPU + V) * N + n0) = o;
-         }()),
-         ...);
-    }(std::make_integer_sequence<int, KPU>{});
+        for (int c = 0; c < 4; ++c) {
+            const unsigned long long lo = (unsigned long long)q0[c] | ((unsigned long long)q1[c] << 32);
+            unsigned f;
+            if (bit < 64) {
+                f = (unsigned)(lo >> bit);
+                if (bit + bits > 64) f |= q2[c] << (64 - bit);
+            } else {
+                f = q2[c] >> (bit - 64);
+            }
+            o |= (f & maxq) << (8 * c);
+        }
+        *(unsigned*)(out + (size_t)(u * KPU + v) * N + n0) = o;
+    }
 }
 
 __global__ void __launch_bounds__(256) unpack_zeros_kernel(const unsigned* __restrict__ qzeros, int G, int N, int bits,
@@ -177,39 +185,36 @@ __global__ void __launch_bounds__(256) pack_weights_kernel(const void* __restric
     }
 }
 
-template <int BITS>
-__global__ void __launch_bounds__(256) pack_zeros_kernel(const void* __restrict__ zero_in, int G, int N, int q_dt,
+// (bits is a run-time, workgroup-uniform argument: one instantiation)
+__global__ void __launch_bounds__(256) pack_zeros_kernel(const void* __restrict__ zero_in, int G, int N, int bits, int q_dt,
                                                          unsigned* __restrict__ qzeros) {
-    constexpr int UW = Pack<BITS>::words, KPU = Pack<BITS>::vals;
+    const int UW = unit_words(bits), KPU = unit_vals(bits);
     const int cu = blockIdx.x * blockDim.x + threadIdx.x;   // column unit
     const int g = blockIdx.y;
     if (cu >= N / KPU || g >= G) return;
-    unsigned vals[KPU];
-#pragma unroll
-    for (int v = 0; v < KPU; ++v) {
+    auto val = [&](int v) -> unsigned {
         const float z = round_to(load_as_f32(zero_in, (size_t)g * N + cu * KPU + v, q_dt) - 1.0f, q_dt);  // zeros -= 1
-        vals[v] = (unsigned)(long long)z;                    // numpy .astype(uint32): -1.0 -> 0xFFFFFFFF
-    }
-    unsigned w[UW];
-#pragma unroll
-    for (int i = 0; i < UW; ++i) w[i] = 0u;
-    if constexpr (BITS != 3) {
-#pragma unroll
-        for (int v = 0; v < KPU; ++v) w[0] |= vals[v] << (BITS * v);
+        return (unsigned)(long long)z;                       // numpy .astype(uint32): -1.0 -> 0xFFFFFFFF
+    };
+    unsigned w0 = 0u, w1 = 0u, w2 = 0u;
+    if (bits != 3) {
+        for (int v = 0; v < KPU; ++v) w0 |= val(v) << (bits * v);              // unmasked OR, like the reference
     } else {
-#pragma unroll
-        for (int j = 0; j < 10; ++j) w[0] |= vals[j] << (3 * j);
-        w[0] |= vals[10] << 30;
-        w[1] |= (vals[10] >> 2) & 1u;
-#pragma unroll
-        for (int j = 0; j < 10; ++j) w[1] |= vals[11 + j] << (3 * j + 1);
-        w[1] |= vals[21] << 31;
-        w[2] |= (vals[21] >> 1) & 3u;
-#pragma unroll
-        for (int j = 0; j < 10; ++j) w[2] |= vals[22 + j] << (3 * j + 2);
+        for (int j = 0; j < 10; ++j) w0 |= val(j) << (3 * j);
+        const unsigned v10 = val(10), v21 = val(21);
+        w0 |= v10 << 30;
+        w1 |= (v10 >> 2) & 1u;
+        for (int j = 0; j < 10; ++j) w1 |= val(11 + j) << (3 * j + 1);
+        w1 |= v21 << 31;
+        w2 |= (v21 >> 1) & 3u;
+        for (int j = 0; j < 10; ++j) w2 |= val(22 + j) << (3 * j + 2);
     }
-#pragma unroll
-    for (int i = 0; i < UW; ++i) qzeros[(size_t)g * (N / 32 * BITS) + cu * UW + i] = w[i];
+    unsigned* const dst = qzeros + (size_t)g * (N / 32 * bits) + cu * UW;
+    dst[0] = w0;
+    if (UW == 3) {
+        dst[1] = w1;
+        dst[2] = w2;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -393,7 +398,7 @@ hipError_t launch_silu_mul(const void* y, void* out, int M, int N, int dtype, hi
 hipError_t launch_unpack_weights(const uint32_t* qweight, int K, int N, int bits, uint8_t* w_out, hipStream_t st) {
     const int units = K / unit_vals(bits);
     dim3 grid((N / 4 + 255) / 256, units), block(256);
-    GPTQ_BITS_SWITCH(bits, hipLaunchKernelGGL(unpack_weights_kernel<B>, grid, block, 0, st, qweight, units, N, w_out));
+    hipLaunchKernelGGL(unpack_weights_kernel, grid, block, 0, st, qweight, units, N, bits, w_out);
     return hipGetLastError();
 }
 
@@ -432,7 +437,7 @@ hipError_t launch_pack_weights(const void* W, const void* scale_in, const void* 
 
 hipError_t launch_pack_zeros(const void* zero_in, int G, int N, int bits, int qparam_dtype, uint32_t* qzeros_out, hipStream_t st) {
     dim3 grid((N / unit_vals(bits) + 255) / 256, G), block(256);
-    GPTQ_BITS_SWITCH(bits, hipLaunchKernelGGL(pack_zeros_kernel<B>, grid, block, 0, st, zero_in, G, N, qparam_dtype, qzeros_out));
+    hipLaunchKernelGGL(pack_zeros_kernel, grid, block, 0, st, zero_in, G, N, bits, qparam_dtype, qzeros_out);
     return hipGetLastError();
 }
 

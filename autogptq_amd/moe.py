@@ -6,8 +6,9 @@
                         state_dict keys are ``<path>.{e}.w1 / w3 / w2.{qweight, qzeros, scales, g_idx}``
 * ``moe_forward``       the grouped path (gptq_moe_forward: routing table, grouped W1 / W3 + silu * mul, grouped W2, combine -- four
                         launches, no host round trip, capturable), the decode path for 1..4 tokens when the experts carry a decode copy
-                        (gptq_moe_decode_forward: two launches on streaming kernels, the expert chosen on the device, capturable), or the
-                        per-expert composition of differentiable ``QuantLinear`` calls
+                        (gptq_moe_decode_forward: two launches on streaming kernels, the expert chosen on the device, capturable), the batch
+                        path for 5..64 tokens when opted in (gptq_moe_batch_forward: the grouped formulas on the decode copy, 16-row tiles of
+                        one expert over the whole K, capturable), or the per-expert composition of differentiable ``QuantLinear`` calls
 * ``pack_moe_experts``  pack the dense 3-D expert parameters of a model (``quantizers`` keyed ``...mlp.experts.{e}.w1`` as ``pack_model`` takes)
 
 The per-expert composition serves what the grouped kernels do not take (2- / 3-bit or fp32 experts, odd group sizes, raw act-order), CPU tensors (which
@@ -64,6 +65,8 @@ class QuantMoEExperts(nn.Module):
         self.bits = bits
         self.names = tuple(names)
         self._decode_copy = False
+        self._batch = False
+        self.batch_max_tokens = 64
         for e in range(num_experts):
             self.add_module(str(e), _Expert(self.names, bits, group_size, hidden_dim, intermediate_dim, weight_dtype, zero_mode))
         self._invalidate()
@@ -77,6 +80,7 @@ class QuantMoEExperts(nn.Module):
     def _invalidate(self):
         self._moe = None
         self._decode_table = None
+        self._batch_ok = False
         self.decode_copy_bytes = 0
         self._keep = ()
         self._plans = {}
@@ -97,21 +101,29 @@ class QuantMoEExperts(nn.Module):
         return [l[0] for l in ls], [l[1] for l in ls], [l[2] for l in ls]
 
     # ------------------------------------------------------------------ post_init
-    def post_init(self, decode_copy: bool = False):
+    def post_init(self, decode_copy: bool = False, batch: bool = False):
         """post_init every expert layer and build the pointer table.  Default: WITHOUT a decode copy (1x the packed bytes; act-order layers add their
         re-sequenced rows) -- calls of any row count run the grouped kernels.  ``decode_copy=True``: the layers also get their decode copy (2x the packed
         bytes; both layouts stay resident: the grouped path still serves more than 4 tokens), the decode table is built, and calls of 1..4 tokens run the
-        decode kernels (``plan(T)["path"] == "decode"``).  ``decode_copy_bytes`` reports what the copies hold.  A checkpoint-layout release does not apply
-        to expert layers."""
+        decode kernels (``plan(T)["path"] == "decode"``).  ``batch=True`` (opt-in as well; builds the decode copy and its table if not asked for already):
+        calls of 5..``batch_max_tokens`` (64) tokens run the batch kernels on the copy (``plan(T)["path"] == "batch"``); experts the batch plan declines
+        log the reason once and behave as without the flag.  ``decode_copy_bytes`` reports what the copies hold.  A checkpoint-layout release does not
+        apply to expert layers."""
         dev = self[0].layers()[0].qweight.device
         if dev.type != "cuda":
             raise RuntimeError(f"mi355x QuantMoEExperts.post_init needs the module on a ROCm GPU device (got {dev}); there is no CPU path.")
-        self._decode_copy = bool(decode_copy)
+        want_decode, self._batch = bool(decode_copy), bool(batch)
+        if self._batch:
+            why = self._batch_declined()
+            if why:
+                logger.warning("QuantMoEExperts.post_init(batch=True) has no effect for these experts (%s)", why)
+                self._batch = False
+        self._decode_copy = want_decode or self._batch
         if self._decode_copy:
             why = self._decode_copy_declined()
             if why:                                          # known from the metadata: no copy is built for a set the decode plan would decline
                 logger.warning("QuantMoEExperts.post_init(decode_copy=True) has no effect for these experts (%s): no decode copy is built", why)
-                self._decode_copy = False
+                self._decode_copy = self._batch = False
         extra = 0
         for e in range(self.num_experts):
             for l in self[e].layers():
@@ -128,6 +140,7 @@ class QuantMoEExperts(nn.Module):
         self._moe, self._keep, self._plans = m, (arrs, table, gate, up, down), {}
         self._table = table
         self._decode_table = None
+        self._batch_ok = False
         self.decode_copy_bytes = extra
         self._dev = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
         self._w_dtype = gate[0].scales.dtype
@@ -141,12 +154,29 @@ class QuantMoEExperts(nn.Module):
                 logger.warning("QuantMoEExperts.post_init(decode_copy=True) has no effect for these experts (%s): no decode copy is kept",
                                str(dplan.get("reason", "")).replace("_", " "))
                 return self.post_init(decode_copy=False)
+            bplan = _lib.describe_moe_batch_plan(m, 5, self.top_k) if self._batch else None
+            if bplan is not None and bplan["path"] != "batch":
+                logger.warning("QuantMoEExperts.post_init(batch=True) has no effect for these experts (%s)", str(bplan.get("reason", "")).replace("_", " "))
+                return self.post_init(decode_copy=want_decode)
             dtable = torch.zeros(max(1, int(lib.gptq_moe_decode_table_bytes(self.num_experts))), dtype=torch.uint8, device=dev)
             with torch.cuda.device(self._dev):
                 _lib.check(lib.gptq_moe_build_decode_table(ctypes.byref(m), dtable.data_ptr(), _lib.current_stream_handle(self._dev)))
             self._decode_table = dtable
+            self._batch_ok = self._batch
             self._plans = {}
         return self
+
+    def _batch_declined(self) -> str:
+        """Why the batch plan would decline these experts, as far as the layer metadata says (empty: build the copies and ask the plan)."""
+        gate, _, down = self[0].layers()
+        if self.hidden_dim % 128 or self.intermediate_dim % 128:
+            return "hidden and intermediate sizes must be multiples of 128"
+        for l in (gate, down):
+            gs, K = l.group_size, l.infeatures
+            q = gs // 128
+            if not (gs in (32, 64) or gs >= K or (gs % 128 == 0 and q & (q - 1) == 0)):
+                return f"group_size {gs}: the batch path takes 32, 64, 128 times a power of two, or one group"
+        return self._decode_copy_declined().replace("the decode path", "the batch path")
 
     def _decode_copy_declined(self) -> str:
         """Why the decode plan would decline these experts, as far as the layer metadata says (empty: build the copies and ask the plan)."""
@@ -170,25 +200,33 @@ class QuantMoEExperts(nn.Module):
     def workspace_bytes(self, T: int, top_k: "int | None" = None) -> int:
         """Scratch of one call with T tokens on the path ``plan(T)`` names."""
         if self._moe is None:
-            self.post_init(self._decode_copy)
-        if self.plan(T, top_k)["path"] == "decode":
+            self.post_init(self._decode_copy, self._batch)
+        path = self.plan(T, top_k)["path"]
+        if path == "decode":
             return int(_lib.load().gptq_moe_decode_workspace_bytes(ctypes.byref(self._moe), T, top_k or self.top_k))
+        if path == "batch":
+            return int(_lib.load().gptq_moe_batch_workspace_bytes(ctypes.byref(self._moe), T, top_k or self.top_k))
         return int(_lib.load().gptq_moe_workspace_bytes(ctypes.byref(self._moe), T, top_k or self.top_k))
 
     def plan(self, T: int, top_k: "int | None" = None) -> dict:
-        """{"path": "decode" | "grouped" | "per_expert", "reason": ...} (+ the launch / tile geometry) for T tokens: what moe_forward runs without grad.
-        "decode" only when the experts carry a decode copy (``post_init(decode_copy=True)``) and the decode plan accepts (1..4 tokens)."""
+        """{"path": "decode" | "batch" | "grouped" | "per_expert", "reason": ...} (+ the launch / tile geometry) for T tokens: what moe_forward runs
+        without grad.  "decode" only when the experts carry a decode copy (``post_init(decode_copy=True)``) and the decode plan accepts (1..4 tokens);
+        "batch" only after ``post_init(batch=True)``, for 5..``batch_max_tokens`` tokens; else the grouped path (or the composition)."""
         top_k = top_k or self.top_k
         if self[0].layers()[0].qweight.device.type != "cuda":
             return {"path": "per_expert", "reason": "cpu tensors"}
         if self._moe is None:
-            self.post_init(self._decode_copy)
-        key = (T, top_k)
+            self.post_init(self._decode_copy, self._batch)
+        key = (T, top_k, self.batch_max_tokens)
         d = self._plans.get(key)
         if d is None:
             if self._decode_table is not None and 0 < T <= 4:
                 d = _lib.describe_moe_decode_plan(self._moe, T, top_k)
                 if d["path"] != "decode":
+                    d = None
+            if d is None and self._batch_ok and self._decode_table is not None and 4 < T <= min(64, self.batch_max_tokens):
+                d = _lib.describe_moe_batch_plan(self._moe, T, top_k)
+                if d["path"] != "batch":
                     d = None
             if d is None:
                 d = _lib.describe_moe_plan(self._moe, T, top_k)
@@ -205,7 +243,8 @@ class QuantMoEExperts(nn.Module):
 def moe_forward(experts: QuantMoEExperts, x: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor, return_intermediate: bool = False):
     """``experts(x, top_k_index, top_k_weights)``: x [T, H] (or [..., H]), top_k_index [T, topk] (int64 as torch.topk returns it), top_k_weights [T, topk].
     The grouped path: one gptq_moe_forward call (workspace from the per-stream scratch, nothing allocated but the output); the decode path (1..4 tokens
-    on experts with a decode copy): one gptq_moe_decode_forward call, same conventions.  ``return_intermediate``: also (H [T topk, I], pos [T, topk] int32)
+    on experts with a decode copy): one gptq_moe_decode_forward call, same conventions; the batch path (5..64 tokens, opted in): one
+    gptq_moe_batch_forward call, same conventions, rows grouped by expert as on the grouped path.  ``return_intermediate``: also (H [T topk, I], pos [T, topk] int32)
     -- the kernel's silu * mul rows and the row of each assignment (-1: dropped); rows grouped by expert on the grouped path, in assignment order on the
     decode path: ``H[pos[t, j]]`` reads the same way on both."""
     H = experts.hidden_dim
@@ -220,10 +259,10 @@ def moe_forward(experts: QuantMoEExperts, x: torch.Tensor, top_k_index: torch.Te
         experts.last_plan = {"path": "per_expert", "reason": "grad enabled and hidden_states / top_k_weights require grad"}
     else:
         experts.last_plan = experts.plan(T, topk)
-    decode = experts.last_plan["path"] == "decode"
-    if experts.last_plan["path"] != "grouped" and not decode:
+    path = experts.last_plan["path"]
+    if path not in ("grouped", "decode", "batch"):
         if return_intermediate:
-            raise RuntimeError(f"moe_forward: return_intermediate needs the grouped or the decode path ({experts.last_plan['reason']})")
+            raise RuntimeError(f"moe_forward: return_intermediate needs the grouped, the batch or the decode path ({experts.last_plan['reason']})")
         return _per_expert(experts, x2, top_k_index.reshape(T, topk), top_k_weights.reshape(T, topk)).reshape(lead + (H,))
     dev, w_dtype = experts._dev, experts._w_dtype
     if x.device != dev:
@@ -246,15 +285,20 @@ def moe_forward(experts: QuantMoEExperts, x: torch.Tensor, top_k_index: torch.Te
         es = torch.tensor([], dtype=w_dtype).element_size()
         h_out = torch.empty(R * I * es + 4 * R, dtype=torch.uint8, device=dev)
     if T:
-        need = experts._plans.get(("ws", T, topk))
+        need = experts._plans.get(("ws", T, topk, path))
         if need is None:
-            need = experts._plans[("ws", T, topk)] = experts.workspace_bytes(T, topk)
+            need = experts._plans[("ws", T, topk, path)] = experts.workspace_bytes(T, topk)
         buf = reserve_workspace(dev, need)
         exchange_tick(dev)
         idx_dev = experts._dev.index
         with torch.cuda.device(idx_dev):
             lib = _lib.load()
-            fn, table = (lib.gptq_moe_decode_forward, experts._decode_table) if decode else (lib.gptq_moe_forward, experts._table)
+            if path == "decode":
+                fn, table = lib.gptq_moe_decode_forward, experts._decode_table
+            elif path == "batch":
+                fn, table = lib.gptq_moe_batch_forward, experts._decode_table
+            else:
+                fn, table = lib.gptq_moe_forward, experts._table
             rc = fn(ctypes.byref(experts._moe), table.data_ptr(), xw.data_ptr(), idx.data_ptr(), w.data_ptr(), T, topk,
                     out.data_ptr(), _lib.ptr(h_out), buf.data_ptr(), buf.numel(), _raw_stream(idx_dev))
         if rc:

@@ -17,8 +17,8 @@
  *       <- the `reconstruct` step of exllama / exllamav2              exllama/cuda_func/q4_matrix.cu:171-225, exllamav2/cuda/q_matrix.cu:158-279,452-500
  *   gptq_moe_forward
  *       <- the expert loop of the reference's Mixtral (per-expert QuantLinears, auto_gptq/modeling/mixtral.py) as one routed, grouped call
- *   gptq_moe_decode_forward
- *       <- the same expert loop at the row counts of token generation (1..4 tokens), on the experts' decode copy
+ *   gptq_moe_decode_forward, gptq_moe_batch_forward
+ *       <- the same expert loop at the row counts of token generation (1..4 tokens) and of batched generation (5..64), on the experts' decode copy
  *   gptq_grad_input
  *       <- the backward of the reference's training route: dequantise + torch.matmul under autograd
  *                                                                     qlinear_cuda_old.py:291-355, qlinear_cuda.py:253-317
@@ -311,6 +311,29 @@ int gptq_moe_decode_forward(const gptq_moe_t *moe, const void *table, const void
 /* Host-only: "path=decode launches=2 wg_pair=1792 wg_down=256 waves_pair=8 waves_down=16 lds_pair=... lds_down=..." (workgroups, waves per workgroup and
  * dynamic LDS bytes of the two launches) or "path=none reason=..." (experts without a decode copy, T > 4, 2- / 3-bit, fp32, topk > 8, ...).  GPTQ_OK either way. */
 int gptq_describe_moe_decode_plan(const gptq_moe_t *moe, int T, int topk, char *out, size_t out_bytes);
+
+/* The same layer at BATCHED-DECODE row counts, 1 <= T <= 64 (additive in ABI 8), on the experts' decode copy: the arithmetic of gptq_moe_forward (every W
+ * bit-exact to gptq_dequant, fp32 products and sums on the matrix core, h rounded once, out[t] = T(sum_j topk_w[t, j] y_(t, j)) in ascending j), on kernels
+ * of the dense batched-decode kind: a workgroup = one tile of up to 16 rows of one expert x 4 strip-chunks x the whole K, no K slices, no atomics --
+ * bit-reproducible, and the row of token t does not depend on the other tokens of the call.
+ *   Launches: routing (bm = 16), gate|up + silu * mul, down, combine: FOUR; sets with act-order experts add one row gather through perm in front of either
+ *   GEMM (five or six).  No host round trip; the grid is a bound from (T, topk, E), so a captured graph replays with new routing.
+ * Takes 4- and 8-bit fp16 / bf16 experts, plain or act-order (gate and up may have different activation orders), group_size 32, 64, 128 2^n or one group,
+ * H and I multiples of 128, E <= 256, topk <= 8, no bias, every expert with its decode copy.  Anything else: GPTQ_ERR_UNSUPPORTED with the reason.
+ * `table` is the DECODE table (gptq_moe_build_decode_table): there is no table of its own.
+ * Workspace of one call:  GPTQ_WORKSPACE_HEADER_BYTES (left untouched)
+ *   + a256(4 (E + 1)) + 256 + a256(16 tiles) + 2 a256(4 T topk) + a256(T topk I sizeof(T)) + a256(4 T topk H) + a256(2 T topk H sizeof(T)) + a256(T topk I sizeof(T)),
+ * a256 = round up to 256, tiles = floor(T topk / 16) + min(E, T topk): offsets, tile count, tiles, pos, sorted rows, H_sorted, Y, and the two gathered
+ * operands of act-order sets (reserved for every set: the size depends on (T, topk, E, H, I) alone).  0 when the call is declined. */
+size_t gptq_moe_batch_workspace_bytes(const gptq_moe_t *moe, int T, int topk);
+/* Arguments as gptq_moe_forward, except that `table` is the decode table.  h_out (optional, for tests): H_sorted [T topk, I] (rows grouped by expert, as on
+ * the grouped path) followed by pos [T, topk] int32.  Caller's stream, no allocation, no synchronisation, legal inside hipGraph capture (gptq_init() first:
+ * act-order sets need its LDS grant); T = 0 launches nothing. */
+int gptq_moe_batch_forward(const gptq_moe_t *moe, const void *table, const void *x, const int64_t *topk_idx, const float *topk_w, int T, int topk, void *out,
+                           void *h_out, void *workspace, size_t workspace_bytes, void *stream);
+/* Host-only: "path=batch bm=16 s=4 tiles=10 launches=4 waves_pair=8 waves_down=8 lds_pair=... lds_down=..." (s: strip-chunks per wave and chunk -- the pair
+ * form runs 2 strips of W1 and of W3, the down form 4 of W2) or "path=none reason=..." (no decode copy, T > 64, 2- / 3-bit, fp32, ...).  GPTQ_OK either way. */
+int gptq_describe_moe_batch_plan(const gptq_moe_t *moe, int T, int topk, char *out, size_t out_bytes);
 
 /* Integer unpack (bit-exact targets). w_out uint8 [K,N]; z_out int32 [G,N] (zero-point as used). */
 int gptq_unpack_weights(const uint32_t *qweight, int K, int N, int bits, uint8_t *w_out, void *stream);

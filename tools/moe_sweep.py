@@ -13,6 +13,14 @@ each as CALL time (one event pair around --reps back-to-back eager calls) and, f
 Writes profiles/moe_decode_sweep.log.  --trace-only T: only run a few decode calls at T tokens on the Mixtral block (for a rocprofv3 --kernel-trace run).
 
     python tools/moe_sweep.py --decode [--reps 20] [--repeats 5] [--out profiles/moe_decode_sweep.log]
+
+--batch: the batch path (gptq_moe_batch_forward, experts post-initialised with batch=True) against the grouped path and the per-expert composition on experts
+WITHOUT a copy, T = 5, 8, 16, 32, 64 on both shapes, in the protocol of --decode (one process, the paths timed in turn per repeat, eager CALL time and
+graph-replayed time, median of --repeats repeats [min .. max]).  Routing: rotated -- eight routings whose expert indices advance by ceil(E / 8) from call to
+call, so all E experts are walked.  frac_bw = bytes of the hit experts / graph time / 8 TB/s.  Writes profiles/moe_batch_sweep.log.
+--trace-only T --batch: a few batch calls at T tokens on the Mixtral block (for a rocprofv3 --kernel-trace run).
+
+    python tools/moe_sweep.py --batch [--reps 20] [--repeats 5] [--out profiles/moe_batch_sweep.log]
 """
 import argparse
 import os
@@ -128,10 +136,64 @@ def decode_sweep(args):
         f.write("\n".join(lines) + "\n")
 
 
-def trace_only(T):
+def _make_batch(E, H, I, topk, batch):
+    from test_gpu_moe import _fill
+    from autogptq_amd.moe import QuantMoEExperts
+    gen = torch.Generator().manual_seed(1)
+    q = QuantMoEExperts(E, H, I, 4, 128, top_k=topk, weight_dtype=torch.float16)
+    for e in range(E):
+        for l in q[e].layers():
+            _fill(l, gen, False)
+    q = q.cuda()
+    q.post_init(batch=batch)
+    return q
+
+
+def batch_sweep(args):
+    lines = [f"# tools/moe_sweep.py --batch: 4-bit g128 fp16 experts; per repeat the paths are timed in turn (batch, batch_graph, grouped, grouped_graph, per_expert); "
+             f"*_us = CALL time: one event pair around {args.reps} back-to-back eager calls / {args.reps}; *_graph_us = the same call captured in a hipGraph per routing and "
+             f"replayed (kernel-side time); value = median over {args.repeats} repeats [min .. max]; batch = experts post-initialised with batch=True, grouped / per_expert = "
+             "experts post-initialised without a copy; routing rotated over all E experts (8 routings, indices advanced by ceil(E / 8)); bytes = packed weights + "
+             "scales / zeros of the hit experts; frac_bw = bytes / graph time / 8 TB/s"]
+    for name, (E, topk, H, I) in SHAPES.items():
+        qb = _make_batch(E, H, I, topk, True)
+        qp = _make_batch(E, H, I, topk, False)
+        per_expert_bytes = 3 * (H * I // 2 + (H // 128) * I * 2 + (H // 128) * I // 2)
+        step = (E + 7) // 8
+        for T in (5, 8, 16, 32, 64):
+            x = (torch.rand((T, H), generator=torch.Generator().manual_seed(T)) - 0.5).half().cuda()
+            idx, w = _routing(T, E, topk, T)
+            hit = int(torch.unique(idx).numel())
+            assert qb.plan(T, topk)["path"] == "batch" and qp.plan(T, topk)["path"] == "grouped"
+            routings = [((idx + k * step) % E, w) for k in range(8)]
+            fb, fg = (lambda i, ww: moe_forward(qb, x, i, ww)), (lambda i, ww: moe_forward(qp, x, i, ww))
+            fns = {"batch": lambda: _time_rot(fb, routings, args.reps), "batch_graph": lambda: _time_graph(fb, routings, args.reps),
+                   "grouped": lambda: _time_rot(fg, routings, args.reps), "grouped_graph": lambda: _time_graph(fg, routings, args.reps),
+                   "per_expert": lambda: _time_rot(lambda i, ww: _per_expert(qp, x, i, ww), routings, max(5, args.reps // 2))}
+            got = {k: [] for k in fns}
+            with torch.no_grad():
+                for _ in range(args.repeats):
+                    for k, fn in fns.items():
+                        got[k].append(fn())
+            med = {k: sorted(v)[len(v) // 2] for k, v in got.items()}
+            byt = hit * per_expert_bytes
+            wins = max(got["batch"]) < min(got["grouped"]) and max(got["batch"]) < min(got["per_expert"]) and max(got["batch_graph"]) < min(got["grouped_graph"])
+            lines.append(f"{name} T={T} hit={hit} " + " ".join(f"{k}_us={med[k]:.1f}[{min(got[k]):.1f}..{max(got[k]):.1f}]" for k in fns)
+                         + f" batch_frac_bw={byt / (med['batch_graph'] * 1e-6) / 8e12:.3f} grouped_frac_bw={byt / (med['grouped_graph'] * 1e-6) / 8e12:.3f}"
+                         + f" call_speedup_vs_grouped={med['grouped'] / med['batch']:.2f} call_speedup_vs_per_expert={med['per_expert'] / med['batch']:.2f}"
+                         + f" graph_speedup_vs_grouped={med['grouped_graph'] / med['batch_graph']:.2f} wins_beyond_spread={'yes' if wins else 'NO'}")
+            print(lines[-1], flush=True)
+        del qb, qp
+        torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+def trace_only(T, batch=False):
     from test_gpu_moe_decode import make_experts as make_dc
     E, topk, H, I = SHAPES["mixtral8x7b"]
-    qd = make_dc(E, H, I, 4, 128, False, torch.float16, seed=1, top_k=topk, decode_copy=True)
+    qd = _make_batch(E, H, I, topk, True) if batch else make_dc(E, H, I, 4, 128, False, torch.float16, seed=1, top_k=topk, decode_copy=True)
     x = (torch.rand((T, H), generator=torch.Generator().manual_seed(T)) - 0.5).half().cuda()
     idx, w = _routing(T, E, topk, T)
     with torch.no_grad():
@@ -146,13 +208,16 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--per-expert-max-t", type=int, default=2048)
     ap.add_argument("--decode", action="store_true")
+    ap.add_argument("--batch", action="store_true")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--trace-only", type=int, default=0)
     args = ap.parse_args()
     if args.trace_only:
-        return trace_only(args.trace_only)
+        return trace_only(args.trace_only, args.batch)
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "moe_decode_sweep.log" if args.decode else "moe_sweep.log")
+        args.out = os.path.join(ROOT, "profiles", "moe_batch_sweep.log" if args.batch else ("moe_decode_sweep.log" if args.decode else "moe_sweep.log"))
+    if args.batch:
+        return batch_sweep(args)
     if args.decode:
         return decode_sweep(args)
     lines = [f"# tools/moe_sweep.py: 4-bit g128 fp16 experts, median of {args.reps} hipEvent-timed calls; bytes = packed weights + scales / zeros of the hit "

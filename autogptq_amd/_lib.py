@@ -36,6 +36,7 @@ EXPORTS = (
     "gptq_moe_table_bytes", "gptq_moe_build_table", "gptq_moe_workspace_bytes", "gptq_moe_forward", "gptq_describe_moe_plan",
     "gptq_moe_decode_table_bytes", "gptq_moe_build_decode_table", "gptq_moe_decode_workspace_bytes", "gptq_moe_decode_forward", "gptq_describe_moe_decode_plan",
     "gptq_moe_batch_workspace_bytes", "gptq_moe_batch_forward", "gptq_describe_moe_batch_plan",
+    "gptq_lora_down", "gptq_lora_up", "gptq_lora_apply", "gptq_describe_lora_plan",
 )
 WS_HEADER_BYTES = 65536
 STRIP_COLS = 16          # GPTQ_STRIP_COLS: columns per strip of the decode copy (gptq_prepack_decode)
@@ -60,6 +61,15 @@ class GptqTuning(Structure):
 class GptqMoe(Structure):
     """gptq_moe_t: E experts, each a gate / up / down layer (arrays of E layer pointers)."""
     _fields_ = [("E", c_int32), ("reserved", c_int32), ("gate", c_void_p), ("up", c_void_p), ("down", c_void_p)]
+
+
+LORA_MAX = 4             # GPTQ_LORA_MAX: adapters of one gptq_lora_* call
+
+
+class GptqLora(Structure):
+    """gptq_lora_t: one adapter -- lora_A.weight [r, K] and lora_B.weight [N, r] in the layer dtype, scale = lora_alpha / r."""
+    _fields_ = [("A", c_void_p), ("B", c_void_p), ("K", c_int32), ("N", c_int32), ("r", c_int32), ("dtype", c_int32),
+                ("scale", ctypes.c_float), ("reserved", c_int32)]
 
 
 PEER_MAX = 8
@@ -176,6 +186,11 @@ def load() -> ctypes.CDLL:
     lib.gptq_moe_batch_workspace_bytes.argtypes = [MP, c_int, c_int]
     lib.gptq_moe_batch_forward.argtypes = lib.gptq_moe_forward.argtypes
     lib.gptq_describe_moe_batch_plan.argtypes = [MP, c_int, c_int, c_char_p, c_size_t]
+    RP = POINTER(POINTER(GptqLora))
+    lib.gptq_lora_down.argtypes = [RP, c_int, c_void_p, POINTER(c_void_p), c_int, c_void_p]
+    lib.gptq_lora_up.argtypes = [RP, c_int, POINTER(c_void_p), POINTER(c_void_p), c_int, c_void_p]
+    lib.gptq_lora_apply.argtypes = [RP, c_int, c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_int, c_void_p]
+    lib.gptq_describe_lora_plan.argtypes = [RP, c_int, c_int, c_char_p, c_size_t]
     lib.gptq_peer_scatter.argtypes = [POINTER(GptqPeerGroup), c_void_p, c_int, c_int, c_int, c_void_p]
     lib.gptq_peer_collect.argtypes = [POINTER(GptqPeerGroup), c_void_p, c_int, c_int, ctypes.c_uint32, c_void_p]
     lib.gptq_peer_gather.argtypes = [POINTER(GptqPeerGroup), c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_uint32, c_void_p]
@@ -301,6 +316,21 @@ def describe_moe_batch_plan(moe: "GptqMoe", T: int, topk: int) -> dict:
     lib = load()
     buf = ctypes.create_string_buffer(512)
     check(lib.gptq_describe_moe_batch_plan(ctypes.byref(moe), T, topk, buf, len(buf)))
+    out = {}
+    for kv in buf.value.decode().split():
+        k, v = kv.split("=", 1)
+        out[k] = int(v) if v.lstrip("-").isdigit() else v
+    return out
+
+
+def describe_lora_plan(loras, M: int) -> dict:
+    """What gptq_lora_apply would run for these adapters (a sequence of GptqLora) at M rows: path=lora with its row regime and grid sizes, or path=none
+    with the reason (host-only query)."""
+    lib = load()
+    n = len(loras)
+    arr = (POINTER(GptqLora) * max(1, n))(*[ctypes.pointer(l) for l in loras])
+    buf = ctypes.create_string_buffer(512)
+    check(lib.gptq_describe_lora_plan(arr, n, M, buf, len(buf)))
     out = {}
     for kv in buf.value.decode().split():
         k, v = kv.split("=", 1)

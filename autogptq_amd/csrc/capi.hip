@@ -782,6 +782,84 @@ int gptq_grad_input(const gptq_layer_t* L, const void* dy, void* dx, int M, int 
     return GPTQ_OK;
 }
 
+// ---- LoRA adapters (lora.hip) ----
+static int lora_check(const gptq_lora_t* const* Ls, int n) {
+    if (!Ls) return fail(GPTQ_ERR_NULL, "loras is NULL");
+    if (n < 1 || n > GPTQ_LORA_MAX) return fail(GPTQ_ERR_UNSUPPORTED, "n = %d adapters: one call takes 1..%d", n, GPTQ_LORA_MAX);
+    for (int i = 0; i < n; ++i) {
+        const gptq_lora_t* L = Ls[i];
+        if (!L) return fail(GPTQ_ERR_NULL, "loras[%d] is NULL", i);
+        if (!L->A || !L->B) return fail(GPTQ_ERR_NULL, "loras[%d]: A/B must be non-NULL", i);
+        if (L->dtype == GPTQ_F32) return fail(GPTQ_ERR_UNSUPPORTED, "loras[%d]: fp32 layer: the adapter kernels take fp16 / bf16", i);
+        if (L->dtype != GPTQ_F16 && L->dtype != GPTQ_BF16) return fail(GPTQ_ERR_UNSUPPORTED, "loras[%d]: unknown dtype enum %d", i, L->dtype);
+        if (L->r < 8 || L->r > 64 || L->r % 8) return fail(GPTQ_ERR_UNSUPPORTED, "loras[%d]: r = %d: the adapter kernels take r in 8, 16, .., 64", i, L->r);
+        if (L->K <= 0 || L->K % 32) return fail(GPTQ_ERR_UNSUPPORTED, "loras[%d]: K = %d must be a positive multiple of 32", i, L->K);
+        if (L->N <= 0 || L->N % 16) return fail(GPTQ_ERR_UNSUPPORTED, "loras[%d]: N = %d must be a positive multiple of 16", i, L->N);
+        if (((uintptr_t)L->A | (uintptr_t)L->B) & 15) return fail(GPTQ_ERR_UNSUPPORTED, "loras[%d]: A / B must be 16-byte aligned", i);
+        if (L->K != Ls[0]->K || L->dtype != Ls[0]->dtype) return fail(GPTQ_ERR_UNSUPPORTED, "the adapters of one call share K and dtype (adapter %d differs)", i);
+    }
+    return GPTQ_OK;
+}
+
+static int lora_check_ptrs(const void* const* ps, int n, const char* name) {
+    if (!ps) return fail(GPTQ_ERR_NULL, "%s is NULL", name);
+    for (int i = 0; i < n; ++i) {
+        if (!ps[i]) return fail(GPTQ_ERR_NULL, "%s[%d] is NULL", name, i);
+        if ((uintptr_t)ps[i] & 15) return fail(GPTQ_ERR_UNSUPPORTED, "%s[%d] must be 16-byte aligned", name, i);
+    }
+    return GPTQ_OK;
+}
+
+int gptq_lora_down(const gptq_lora_t* const* Ls, int n, const void* x, void* const* u, int M, void* stream) {
+    if (int rc = lora_check(Ls, n)) return rc;
+    if (!x) return fail(GPTQ_ERR_NULL, "x must be non-NULL");
+    if ((uintptr_t)x & 15) return fail(GPTQ_ERR_UNSUPPORTED, "x must be 16-byte aligned");
+    if (int rc = lora_check_ptrs((const void* const*)u, n, "u")) return rc;
+    if (M < 0) return fail(GPTQ_ERR_SHAPE, "M must be >= 0, got %d", M);
+    if (M == 0) return GPTQ_OK;
+    hipError_t e = launch_lora_down(Ls, n, x, u, M, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "gptq_lora_down launch");
+    return GPTQ_OK;
+}
+
+int gptq_lora_up(const gptq_lora_t* const* Ls, int n, const void* const* u, void* const* outs, int M, void* stream) {
+    if (int rc = lora_check(Ls, n)) return rc;
+    if (int rc = lora_check_ptrs(u, n, "u")) return rc;
+    if (int rc = lora_check_ptrs((const void* const*)outs, n, "outs")) return rc;
+    if (M < 0) return fail(GPTQ_ERR_SHAPE, "M must be >= 0, got %d", M);
+    if (M == 0) return GPTQ_OK;
+    hipError_t e = launch_lora_up(Ls, n, u, outs, M, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "gptq_lora_up launch");
+    return GPTQ_OK;
+}
+
+int gptq_lora_apply(const gptq_lora_t* const* Ls, int n, const void* x, void* const* u, void* const* outs, int M, void* stream) {
+    if (int rc = lora_check(Ls, n)) return rc;                 // everything is validated before the first launch
+    if (!x) return fail(GPTQ_ERR_NULL, "x must be non-NULL");
+    if ((uintptr_t)x & 15) return fail(GPTQ_ERR_UNSUPPORTED, "x must be 16-byte aligned");
+    if (int rc = lora_check_ptrs((const void* const*)u, n, "u")) return rc;
+    if (int rc = lora_check_ptrs((const void* const*)outs, n, "outs")) return rc;
+    if (int rc = gptq_lora_down(Ls, n, x, u, M, stream)) return rc;
+    return gptq_lora_up(Ls, n, (const void* const*)u, outs, M, stream);
+}
+
+int gptq_describe_lora_plan(const gptq_lora_t* const* Ls, int n, int M, char* out, size_t out_bytes) {
+    if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out is NULL");
+    int rc = lora_check(Ls, n);
+    if (!rc && M < 0) rc = fail(GPTQ_ERR_SHAPE, "M must be >= 0, got %d", M);
+    if (rc) {
+        char reason[sizeof(g_err)];
+        snprintf(reason, sizeof(reason), "%s", g_err);
+        for (char* c = reason; *c; ++c)
+            if (*c == ' ' || *c == '=') *c = '_';
+        snprintf(out, out_bytes, "path=none reason=%s", reason);
+        return GPTQ_OK;
+    }
+    const LoraPlan pl = plan_lora(Ls, n, M);
+    snprintf(out, out_bytes, "path=lora rows=%s wg_down=%ld wg_up=%ld launches=2", pl.gemv ? "gemv" : "mfma", M ? pl.wg_down : 0L, M ? pl.wg_up : 0L);
+    return GPTQ_OK;
+}
+
 // ---- routed mixture-of-experts layers (moe.hip) ----
 static int moe_check_proj(const gptq_layer_t* const* Ls, int E, int K, int N, int dtype, const char* name) {
     if (!Ls) return fail(GPTQ_ERR_NULL, "moe->%s is NULL", name);

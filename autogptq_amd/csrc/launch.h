@@ -217,6 +217,15 @@ MoeBatchPlan plan_moe_batch(const gptq_moe_t& m, int T, int topk);
 hipError_t launch_moe_batch(const gptq_moe_t& m, const void* table, const MoeBatchPlan& pl, const void* x, const int64_t* idx, const float* w, int T, int topk,
                             void* out, char* ws, hipStream_t st);
 hipError_t init_moe_batch_device();
+// lora.hip: the adapter branch out += scale * (x . A^T) . B^T for up to GPTQ_LORA_MAX adapters that share x: one down launch, one up launch
+constexpr int GPTQ_LORA_GEMV_ROWS = 8;              // up to here the VALU forms, above the matrix-core forms
+struct LoraPlan {
+    bool gemv;
+    long mtiles, units_down, units_up, wg_down, wg_up;
+};
+LoraPlan plan_lora(const gptq_lora_t* const* Ls, int n, int M);
+hipError_t launch_lora_down(const gptq_lora_t* const* Ls, int n, const void* x, void* const* u, int M, hipStream_t st);
+hipError_t launch_lora_up(const gptq_lora_t* const* Ls, int n, const void* const* u, void* const* outs, int M, hipStream_t st);
 hipError_t launch_unpack_weights(const uint32_t* qweight, int K, int N, int bits, uint8_t* w_out, hipStream_t st);
 hipError_t launch_unpack_zeros(const uint32_t* qzeros, int G, int N, int bits, int zero_mode, int32_t* z_out, hipStream_t st);
 hipError_t launch_pack_weights(const void* W, const void* scale_in, const void* zero_in, const int32_t* g_idx,

@@ -115,12 +115,14 @@ __host__ __device__ inline int promote(int a, int b) { return (a == b) ? a : GPT
 // (512 contiguous bytes per W row for fp16), then every thread quantises and packs whole units for consecutive columns n --
 // so both the W reads and the qweight / scales accesses are coalesced (the first version read W[n, k] with lanes along n,
 // one 16-64 byte piece per lane at stride K).
-template <int BITS>
+// (bits is a run-time, workgroup-uniform argument: one instantiation.  A unit's words are three named registers and its values are placed as they are
+// computed -- a value array indexed by a run-time bound would live in scratch.)
 __global__ void __launch_bounds__(256) pack_weights_kernel(const void* __restrict__ W, const void* __restrict__ scale_in,
                                                            const void* __restrict__ zero_in, const int* __restrict__ g_idx,
-                                                           int K, int N, int group_size, int w_dt, int q_dt,
+                                                           int K, int N, int bits, int group_size, int w_dt, int q_dt,
                                                            unsigned* __restrict__ qweight, void* __restrict__ scales_out) {
-    constexpr int UW = Pack<BITS>::words, KPU = Pack<BITS>::vals, TN = 32, TK = 256;
+    constexpr int TN = 32, TK = 256;
+    const int UW = unit_words(bits), KPU = unit_vals(bits);
     __shared__ float tile[TN][TK + 1];
     const int n0 = blockIdx.x * TN, k0 = blockIdx.y * TK;
     const int tid = threadIdx.x;
@@ -134,8 +136,7 @@ __global__ void __launch_bounds__(256) pack_weights_kernel(const void* __restric
         const int ul = idx / TN, nl = idx - ul * TN;
         const int n = n0 + nl, u = k0 / KPU + ul;
         if (n >= N || u >= K / KPU) continue;
-        unsigned vals[KPU];
-#pragma unroll
+        unsigned w0 = 0u, w1 = 0u, w2 = 0u;
         for (int v = 0; v < KPU; ++v) {
             const int k = u * KPU + v;
             const int g = g_idx ? g_idx[k] : k / group_size;
@@ -146,28 +147,21 @@ __global__ void __launch_bounds__(256) pack_weights_kernel(const void* __restric
             const float w = tile[nl][ul * KPU + v];
             const float sum = round_to(w + sz, p_dt);
             const float quo = round_to(sum / s_cast, p_dt);
-            vals[v] = (unsigned)(int)rintf(quo);                               // torch.round = half-to-even
+            const unsigned val = (unsigned)(int)rintf(quo);                    // torch.round = half-to-even
+            // little-endian bit stream; unmasked OR into the word the field starts in, like the reference; the two 3-bit straddlers (values 10 and
+            // 21) put their upper bits, masked, into the next word (qlinear_cuda.py:144-162)
+            const int bit = bits * v, wi = bit >> 5, sh = bit & 31;
+            const unsigned lo = val << sh;
+            const unsigned hi = sh + bits > 32 ? (val >> (32 - sh)) & ((1u << (sh + bits - 32)) - 1u) : 0u;
+            if (wi == 0) { w0 |= lo; w1 |= hi; }
+            else if (wi == 1) { w1 |= lo; w2 |= hi; }
+            else w2 |= lo;
         }
-        unsigned w[UW];
-#pragma unroll
-        for (int i = 0; i < UW; ++i) w[i] = 0u;
-        if constexpr (BITS != 3) {
-#pragma unroll
-            for (int v = 0; v < KPU; ++v) w[0] |= vals[v] << (BITS * v);        // unmasked OR, like the reference
-        } else {
-#pragma unroll
-            for (int j = 0; j < 10; ++j) w[0] |= vals[j] << (3 * j);
-            w[0] |= vals[10] << 30;
-            w[1] |= (vals[10] >> 2) & 1u;
-#pragma unroll
-            for (int j = 0; j < 10; ++j) w[1] |= vals[11 + j] << (3 * j + 1);
-            w[1] |= vals[21] << 31;
-            w[2] |= (vals[21] >> 1) & 3u;
-#pragma unroll
-            for (int j = 0; j < 10; ++j) w[2] |= vals[22 + j] << (3 * j + 2);
+        qweight[(size_t)(u * UW) * N + n] = w0;
+        if (UW == 3) {
+            qweight[(size_t)(u * UW + 1) * N + n] = w1;
+            qweight[(size_t)(u * UW + 2) * N + n] = w2;
         }
-#pragma unroll
-        for (int i = 0; i < UW; ++i) qweight[(size_t)(u * UW + i) * N + n] = w[i];
     }
     // scales_out = scales.to(layer dtype): the workgroups of the first K tile write their 32 columns of every group row
     if (scales_out && blockIdx.y == 0) {
@@ -430,8 +424,8 @@ hipError_t launch_pack_weights(const void* W, const void* scale_in, const void* 
                                int K, int N, int bits, int group_size, int w_dtype, int qparam_dtype,
                                uint32_t* qweight_out, void* scales_out, hipStream_t st) {
     dim3 grid((N + 31) / 32, (K + 255) / 256), block(256);       // 32-column x 256-k tiles
-    GPTQ_BITS_SWITCH(bits, hipLaunchKernelGGL(pack_weights_kernel<B>, grid, block, 0, st, W, scale_in, zero_in, g_idx, K, N,
-                                              group_size, w_dtype, qparam_dtype, qweight_out, scales_out));
+    hipLaunchKernelGGL(pack_weights_kernel, grid, block, 0, st, W, scale_in, zero_in, g_idx, K, N, bits, group_size, w_dtype, qparam_dtype, qweight_out,
+                       scales_out);
     return hipGetLastError();
 }
 

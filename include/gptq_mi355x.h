@@ -23,6 +23,8 @@
  *       <- the backward of the reference's training route: dequantise + torch.matmul under autograd
  *                                                                     qlinear_cuda_old.py:291-355, qlinear_cuda.py:253-317
  *          and the triton backend's QuantLinearFunction.backward      auto_gptq/nn_modules/triton_utils/kernels.py:408-426
+ *   gptq_lora_down, gptq_lora_up, gptq_lora_apply
+ *       <- GPTQLoraLinear.forward's adapter branch (torch matmuls on the base output)   auto_gptq/utils/peft_utils.py:100-123
  *   gptq_make_sequential + gptq_resequence_qweight + gptq_permute_columns
  *       <- exllama_kernels.make_q4 (Q4Matrix::make_sequential)        exllama/exllama_ext.cpp:134-171, cuda_func/q4_matrix.cu:63-169
  *          exllamav2_kernels.make_q_matrix                            exllamav2/ext.cpp:26-93, cuda/q_matrix.cu:502-627
@@ -251,6 +253,31 @@ int gptq_dequant(const gptq_layer_t *layer, void *W_out, void *stream);
  * Caller's stream, no allocation, no workspace, capturable in a graph.  GPTQ_ERR_NULL / _SHAPE / _UNSUPPORTED as for gptq_forward
  * (dy and dx must also be 16-byte aligned).  Products and sums in fp32, one rounding at the store (accumulate: dX + the sum in fp32, one rounding). */
 int gptq_grad_input(const gptq_layer_t *layer, const void *dy, void *dx, int M, int accumulate, void *stream);
+
+/* LoRA adapters beside a quantized layer (the reference's GPTQLoraLinear, auto_gptq/utils/peft_utils.py:58-123, whose merge() must refuse: W is int4 on a
+ * fixed grid, so W + s B A has no packed form and every call pays the adapter branch at run time).  For each adapter i of a call:
+ *   down:  u_i[m, j]   = T(sum_k x[m, k] * A_i[j, k])                                      fp32 products and sums, one rounding
+ *   up:    out_i[m, n] = T(float(out_i[m, n]) + scale_i * sum_j float(u_i[m, j]) * float(B_i[n, j]))   in place on the base layer's output, one rounding
+ * A is peft's lora_A.weight [r, K], B its lora_B.weight [N, r], both in the layer dtype T (fp16 / bf16), row-major.  n = 1..GPTQ_LORA_MAX adapters of one
+ * call share x, K and dtype (q|k|v, gate|up) and run as ONE launch per direction; adapter i's result is bit-identical to a call of its own.  u_i is a
+ * caller tensor [M, r_i] (no workspace); x, u_i, out_i dense row-major and 16-byte aligned.  Caller's stream, no allocation, no atomics, fixed summation
+ * order (bit-reproducible), legal inside hipGraph capture; M = 0 launches nothing.  Declined with GPTQ_ERR_UNSUPPORTED and the reason in
+ * gptq_last_error() (the caller composes the branch itself): fp32, r outside {8, 16, .., 64}, K % 32, N % 16, misaligned pointers, n > GPTQ_LORA_MAX,
+ * adapters of one call that differ in K or dtype. */
+#define GPTQ_LORA_MAX 4
+typedef struct gptq_lora_t {
+    const void *A;          /* [r, K] dtype, row-major, 16-byte aligned */
+    const void *B;          /* [N, r] dtype, row-major, 16-byte aligned */
+    int32_t K, N, r, dtype; /* r % 8 == 0, 8 <= r <= 64; K % 32 == 0; N % 16 == 0; GPTQ_F16 / GPTQ_BF16 */
+    float   scale;          /* lora_alpha / r */
+    int32_t reserved;       /* 0 */
+} gptq_lora_t;
+int gptq_lora_down (const gptq_lora_t *const *loras, int n, const void *x, void *const *u, int M, void *stream);
+int gptq_lora_up   (const gptq_lora_t *const *loras, int n, const void *const *u, void *const *outs, int M, void *stream);
+int gptq_lora_apply(const gptq_lora_t *const *loras, int n, const void *x, void *const *u, void *const *outs, int M, void *stream); /* down + up */
+/* Host-only: "path=lora rows=gemv|mfma wg_down=... wg_up=... launches=2" (rows: the VALU forms up to 8 rows, the matrix-core forms above) or
+ * "path=none reason=...".  GPTQ_OK either way (GPTQ_ERR_NULL for a NULL out). */
+int gptq_describe_lora_plan(const gptq_lora_t *const *loras, int n, int M, char *out, size_t out_bytes);
 
 /* Routed mixture-of-experts layer (the experts of a Mixtral block: auto_gptq/modeling/mixtral.py, block_sparse_moe.experts.{e}.w1 / w3 / w2).  E experts,
  * each three plain layers: gate (w1) and up (w3) [H -> I], down (w2) [I -> H].  For token t and its topk assignments (t, j) to experts

@@ -6,7 +6,7 @@
  * reach under hipGraph replay.  This module does the per-call part -- checks on x, the output allocation (at::empty on x's options), the current HIP
  * stream, the C-ABI call -- behind ONE METH_FASTCALL entry per kind of call; everything that depends only on the layer is resolved once by post_init.
  * It calls the SAME gptq_forward_ex / gptq_forward_multi_ex of the SAME loaded libgptq_mi355x.so (addresses handed over by _lib.py), and answers None
- * whenever a call is not the plain case (other device, dtype cast, non-contiguous x, a tuning struct): the Python path then does what it always did.
+ * whenever a call is not the plain case (other device, dtype cast, non-contiguous or misaligned x, a tuning struct): the Python path then does what it always did.
  * Optional: without it (not built, or a torch it was not built for) the Python path is the only path.                                                        */
 #define PY_SSIZE_T_CLEAN
 #include <Python.h>
@@ -45,6 +45,7 @@ static inline bool plain_x(const at::Tensor& x, long K, long dtype_code, long de
     if (x.requires_grad() && at::GradMode::is_enabled()) return false;
     if (!x.is_cuda() || (long)x.scalar_type() != dtype_code || x.dim() < 1 || x.size(-1) != K || !x.is_contiguous()) return false;
     if (x.get_device() != dev_index || c10::hip::current_device() != dev_index) return false;
+    if ((uintptr_t)x.data_ptr() & 15) return false;      /* a view at an odd element offset: the C ABI takes 16-byte aligned x, the Python path copies it */
     *M = K ? x.numel() / K : 0;
     return *M > 0 && *M <= 2147483647;
 }

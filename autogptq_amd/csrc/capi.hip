@@ -64,6 +64,13 @@ int check_io(const void* x, const void* out, int M) {
     return GPTQ_OK;
 }
 
+// x / out / outs[i] / workspace of the dense entry points: the kernels load x by LDS DMA and 16-byte vectors and lay the workspace out in 16-byte
+// granules -- anything else is refused before a launch (the wrappers copy a misaligned x first).  NULL passes: the NULL checks name those.
+int check_align(const void* x, const void* out, const void* ws) {
+    if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)ws) & 15) return fail(GPTQ_ERR_UNSUPPORTED, "x / out / workspace must be 16-byte aligned");
+    return GPTQ_OK;
+}
+
 bool want_gemm(const gptq_layer_t* L, int M, const gptq_tuning_t* t) {
     if (t && t->path == 3) return true;
     if (t && (t->path == 1 || t->path == 2 || t->path == 4 || t->path == 5)) return false;
@@ -346,6 +353,7 @@ static int gemv_core(const gptq_layer_t* L, const void* x, void* out, int M, con
 }
 int gptq_gemv(const gptq_layer_t* L, const void* x, void* out, int M, void* ws, size_t ws_bytes, void* stream,
               const gptq_tuning_t* tune) {
+    if (int rc = check_align(x, out, ws)) return rc;
     return gemv_core(L, x, out, M, split_ws(ws, ws_bytes), stream, tune);
 }
 
@@ -371,6 +379,7 @@ static int gemm_core(const gptq_layer_t* L, const void* x, void* out, int M, con
 }
 int gptq_gemm(const gptq_layer_t* L, const void* x, void* out, int M, void* ws, size_t ws_bytes, void* stream,
               const gptq_tuning_t* tune) {
+    if (int rc = check_align(x, out, ws)) return rc;
     return gemm_core(L, x, out, M, split_ws(ws, ws_bytes), stream, tune);
 }
 
@@ -469,6 +478,7 @@ static int forward_impl(const gptq_layer_t* L, const void* x, void* out, int M, 
 
 int gptq_forward_ex(const gptq_layer_t* L, const void* x, void* out, int M, void* ws, size_t ws_bytes, void* stream,
                     const gptq_tuning_t* tune) {
+    if (int rc = check_align(x, out, ws)) return rc;
     return forward_impl(L, x, out, M, split_ws(ws, ws_bytes), stream, tune);
 }
 
@@ -653,6 +663,9 @@ static int forward_multi_core(const gptq_layer_t* const* layers, int n_layers, c
 
 int gptq_forward_multi_ex(const gptq_layer_t* const* layers, int n_layers, const void* x, void* const* outs, int M, void* ws,
                           size_t ws_bytes, void* stream, const gptq_tuning_t* tune) {
+    if (int rc = check_align(x, nullptr, ws)) return rc;
+    for (int i = 0; outs && i < n_layers; ++i)
+        if ((uintptr_t)outs[i] & 15) return fail(GPTQ_ERR_UNSUPPORTED, "outs[%d] must be 16-byte aligned", i);
     return forward_multi_core(layers, n_layers, x, outs, M, split_ws(ws, ws_bytes), stream, tune);
 }
 
@@ -710,6 +723,7 @@ int gptq_mlp_forward_ex(const gptq_layer_t* gate, const gptq_layer_t* up, const 
     int rc = check_mlp(gate, up, down);
     if (rc) return rc;
     if ((rc = check_io(x, out, M))) return rc;
+    if ((rc = check_align(x, out, ws))) return rc;
     const WsView wv = split_ws(ws, ws_bytes);
     const size_t have = wv.header ? WS_HEADER_BYTES + wv.body_bytes : (size_t)0;
     if (tune && tune->path != 0)
@@ -1406,6 +1420,7 @@ int gptq_forward_scatter(const gptq_layer_t* L, const void* x, int M, const gptq
     int rc = check_layer(L);
     if (rc) return rc;
     if (!x) return fail(GPTQ_ERR_NULL, "x must be non-NULL");
+    if ((rc = check_align(x, nullptr, ws))) return rc;
     if ((rc = check_peer_group(pg, M, L->dtype))) return rc;
     if (L->N != pg->N / pg->world) return fail(GPTQ_ERR_SHAPE, "the layer's out_features (%d) must be the rank's shard N / world = %d", L->N, pg->N / pg->world);
     const gptq_layer_t* one[1] = {L};
@@ -1426,6 +1441,7 @@ int gptq_forward_gather(const gptq_layer_t* L, const void* x, void* out, int M, 
                         void* stream) {
     if (!out) return fail(GPTQ_ERR_NULL, "out must be non-NULL");
     if (max_spins == 0) return fail(GPTQ_ERR_SHAPE, "max_spins must be > 0 (the wait is bounded by design)");
+    if (int rc = check_align(x, out, ws)) return rc;
     if (int rc = gptq_forward_scatter(L, x, M, pg, ws, ws_bytes, stream)) return rc;
     return gptq_peer_collect(pg, out, M, L->dtype, max_spins, stream);
 }

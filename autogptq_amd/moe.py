@@ -270,6 +270,8 @@ def moe_forward(experts: QuantMoEExperts, x: torch.Tensor, top_k_index: torch.Te
     xw = x2.to(w_dtype) if x2.dtype != w_dtype else x2
     if not xw.is_contiguous():
         xw = xw.contiguous()
+    if xw.data_ptr() & 15:                # a contiguous view at an odd element offset: the C ABI takes 16-byte aligned x
+        xw = xw.clone()
     idx = top_k_index.reshape(T, topk)
     if idx.dtype != torch.int64:
         idx = idx.to(torch.int64)

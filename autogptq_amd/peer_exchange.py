@@ -257,6 +257,8 @@ class PeerExchange:
 
         if qlinear._layer is None:
             qlinear.post_init()
+        if not x2.is_contiguous() or x2.data_ptr() & 15:          # the C ABI takes a dense, 16-byte aligned x
+            x2 = x2.clone(memory_format=torch.contiguous_format)
         M = x2.shape[0]
         if out is None:
             out = torch.empty((M, self.N), dtype=self.dtype, device=self.device)

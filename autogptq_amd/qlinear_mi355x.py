@@ -433,6 +433,8 @@ class QuantLinear(nn.Module):
             x2 = x2.reshape(-1, K)
         if not x2.is_contiguous():
             x2 = x2.contiguous()
+        if x2.data_ptr() & 15:            # a contiguous view at an odd element offset: the C ABI takes 16-byte aligned x (gptq_mi355x.h)
+            x2 = x2.clone()
         M = x2.shape[0]
         n_out = self._n_out
         out = torch.empty((M, n_out), dtype=w_dtype, device=dev)
@@ -504,6 +506,8 @@ class QuantLinear(nn.Module):
             self._rebuild_rows_now()
         L.qweight = self._layer.qweight
         x2 = x.reshape(-1, K).contiguous()
+        if x2.data_ptr() & 15:
+            x2 = x2.clone()
         M = x2.shape[0]
         out = torch.empty((M, N), dtype=self._w_dtype, device=self._dev)
         if M:
@@ -793,6 +797,8 @@ def forward_multi(layers, x: torch.Tensor, tuning: "_lib.GptqTuning | None" = No
         x2 = x2.reshape(-1, K)
     if not x2.is_contiguous():
         x2 = x2.contiguous()
+    if x2.data_ptr() & 15:                # a contiguous view at an odd element offset: the C ABI takes 16-byte aligned x
+        x2 = x2.clone()
     M = x2.shape[0]
     if M == 1:      # one decode row: ONE allocation, the outputs are its column slices (contiguous for a single row) -- torch.empty is 1.9 us of a ~10 us call
         outs = list(torch.empty((1, ent[11]), dtype=w_dtype, device=dev).split(n_outs, dim=1))
@@ -871,6 +877,8 @@ def mlp_forward(gate: QuantLinear, up: QuantLinear, down: QuantLinear, x: torch.
         x2 = x2.reshape(-1, K)
     if not x2.is_contiguous():
         x2 = x2.contiguous()
+    if x2.data_ptr() & 15:
+        x2 = x2.clone()
     M = x2.shape[0]
     out = torch.empty((M, down.outfeatures), dtype=w_dtype, device=dev)
     if M:

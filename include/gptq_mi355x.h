@@ -68,6 +68,10 @@
  *     A bounded wait inside a launch that gives up (another process held the CUs) sets word [2] of the header's last 64 bytes and never hangs the queue:
  *     that launch's result is wrong and the word stays set -- poll it (autogptq_amd.qlinear_mi355x.exchange_error) where CUs are shared.
  *   - results are run-to-run deterministic (no floating-point atomics, fixed summation orders): every entry point is bit-reproducible.
+ *   - alignment: `x`, `out`, every `outs[i]` and `workspace` of the dense forward entry points -- gptq_forward[_ex], gptq_gemv, gptq_gemm,
+ *     gptq_forward_multi[_ex], gptq_mlp_forward[_ex], gptq_forward_scatter / _gather -- are 16-byte aligned (the kernels load x by LDS DMA and 16-byte
+ *     vectors); anything else is refused with GPTQ_ERR_UNSUPPORTED before a launch.  A contiguous view at an odd element offset (a slice of a flat
+ *     arena) is copied by the caller first -- the Python wrappers do.  gptq_grad_input, the gptq_lora_* and the gptq_moe_* entries state the same rule.
  */
 #ifndef GPTQ_MI355X_H
 #define GPTQ_MI355X_H

@@ -36,6 +36,7 @@ EXPORTS = (
     "gptq_moe_table_bytes", "gptq_moe_build_table", "gptq_moe_workspace_bytes", "gptq_moe_forward", "gptq_describe_moe_plan",
     "gptq_moe_decode_table_bytes", "gptq_moe_build_decode_table", "gptq_moe_decode_workspace_bytes", "gptq_moe_decode_forward", "gptq_describe_moe_decode_plan",
     "gptq_moe_batch_workspace_bytes", "gptq_moe_batch_forward", "gptq_describe_moe_batch_plan",
+    "gptq_moe_grad_table_bytes", "gptq_moe_build_grad_table", "gptq_moe_backward_workspace_bytes", "gptq_moe_backward", "gptq_describe_moe_backward_plan",
     "gptq_lora_down", "gptq_lora_up", "gptq_lora_apply", "gptq_describe_lora_plan",
 )
 WS_HEADER_BYTES = 65536
@@ -186,6 +187,14 @@ def load() -> ctypes.CDLL:
     lib.gptq_moe_batch_workspace_bytes.argtypes = [MP, c_int, c_int]
     lib.gptq_moe_batch_forward.argtypes = lib.gptq_moe_forward.argtypes
     lib.gptq_describe_moe_batch_plan.argtypes = [MP, c_int, c_int, c_char_p, c_size_t]
+    lib.gptq_moe_grad_table_bytes.restype = c_size_t
+    lib.gptq_moe_grad_table_bytes.argtypes = [c_int]
+    lib.gptq_moe_build_grad_table.argtypes = [MP, c_void_p, c_void_p]
+    lib.gptq_moe_backward_workspace_bytes.restype = c_size_t
+    lib.gptq_moe_backward_workspace_bytes.argtypes = [MP, c_int, c_int]
+    lib.gptq_moe_backward.argtypes = [MP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_size_t, c_void_p]
+    lib.gptq_describe_moe_backward_plan.argtypes = [MP, c_int, c_int, c_char_p, c_size_t]
     RP = POINTER(POINTER(GptqLora))
     lib.gptq_lora_down.argtypes = [RP, c_int, c_void_p, POINTER(c_void_p), c_int, c_void_p]
     lib.gptq_lora_up.argtypes = [RP, c_int, POINTER(c_void_p), POINTER(c_void_p), c_int, c_void_p]
@@ -201,7 +210,8 @@ def load() -> ctypes.CDLL:
         if name not in ("gptq_last_error", "gptq_status_string", "gptq_workspace_bytes", "gptq_workspace_bytes_ex",
                         "gptq_workspace_bytes_max", "gptq_workspace_bytes_multi", "gptq_workspace_bytes_multi_ex",
                         "gptq_workspace_bytes_mlp", "gptq_workspace_bytes_mlp_ex", "gptq_moe_table_bytes", "gptq_moe_workspace_bytes",
-                        "gptq_moe_decode_table_bytes", "gptq_moe_decode_workspace_bytes", "gptq_moe_batch_workspace_bytes"):
+                        "gptq_moe_decode_table_bytes", "gptq_moe_decode_workspace_bytes", "gptq_moe_batch_workspace_bytes",
+                        "gptq_moe_grad_table_bytes", "gptq_moe_backward_workspace_bytes"):
             getattr(lib, name).restype = c_int
     got = lib.gptq_abi_version()
     if got != ABI_VERSION:
@@ -292,6 +302,18 @@ def describe_moe_plan(moe: "GptqMoe", T: int, topk: int) -> dict:
     lib = load()
     buf = ctypes.create_string_buffer(512)
     check(lib.gptq_describe_moe_plan(ctypes.byref(moe), T, topk, buf, len(buf)))
+    out = {}
+    for kv in buf.value.decode().split():
+        k, v = kv.split("=", 1)
+        out[k] = int(v) if v.lstrip("-").isdigit() else v
+    return out
+
+
+def describe_moe_backward_plan(moe: "GptqMoe", T: int, topk: int) -> dict:
+    """What gptq_moe_backward would run for (moe, T, topk): path=grouped_backward with its grids, or path=per_expert with the reason (host-only query)."""
+    lib = load()
+    buf = ctypes.create_string_buffer(512)
+    check(lib.gptq_describe_moe_backward_plan(ctypes.byref(moe), T, topk, buf, len(buf)))
     out = {}
     for kv in buf.value.decode().split():
         k, v = kv.split("=", 1)

@@ -977,6 +977,72 @@ int gptq_describe_moe_plan(const gptq_moe_t* m, int T, int topk, char* out, size
     return GPTQ_OK;
 }
 
+// ---- the backward of the grouped path (moe_grad.hip) ----
+size_t gptq_moe_grad_table_bytes(int E) { return E > 0 ? 3 * (size_t)E * moe_grad_table_entry_bytes() : 0; }
+
+int gptq_moe_build_grad_table(const gptq_moe_t* m, void* table, void* stream) {
+    if (int rc = moe_check(m, 0, 1)) return rc;
+    if (!table) return fail(GPTQ_ERR_NULL, "table is NULL");
+    const size_t eb = moe_grad_table_entry_bytes(), E = (size_t)m->E;
+    std::vector<char> host(gptq_moe_grad_table_bytes(m->E));
+    for (size_t e = 0; e < E; ++e) {
+        moe_grad_table_entry(*m->gate[e], host.data() + e * eb);
+        moe_grad_table_entry(*m->up[e], host.data() + (E + e) * eb);
+        moe_grad_table_entry(*m->down[e], host.data() + (2 * E + e) * eb);
+    }
+    hipError_t e = hipMemcpyAsync(table, host.data(), host.size(), hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);      // the host copy dies with this call
+    if (e != hipSuccess) return hip_fail(e, "gptq_moe_build_grad_table copy");
+    return GPTQ_OK;
+}
+
+size_t gptq_moe_backward_workspace_bytes(const gptq_moe_t* m, int T, int topk) {
+    if (moe_check(m, T, topk)) return 0;
+    const gptq_layer_t* G = m->gate[0];
+    return plan_moe_grad(m->E, T, topk, G->K, G->N, G->dtype).bytes;
+}
+
+int gptq_moe_backward(const gptq_moe_t* m, const void* table, const void* grad_table, const void* x, const int64_t* idx, const float* w, const void* dout,
+                      int T, int topk, void* dx, float* dw, void* dgu_out, void* ws, size_t ws_bytes, void* stream) {
+    if (int rc = moe_check(m, T, topk)) return rc;
+    if (T == 0) return GPTQ_OK;
+    if (!dx && !dw) return fail(GPTQ_ERR_NULL, "dx and dw are both NULL: nothing to compute");
+    if (!table || !grad_table || !x || !idx || !w || !dout)
+        return fail(GPTQ_ERR_NULL, "table / grad_table / x / topk_idx / topk_w / dout must be non-NULL");
+    if (((uintptr_t)x | (uintptr_t)dout | (uintptr_t)dx | (uintptr_t)ws) & 15)
+        return fail(GPTQ_ERR_UNSUPPORTED, "x / dout / dx / workspace must be 16-byte aligned");
+    const gptq_layer_t* G = m->gate[0];
+    const MoeGradPlan pl = plan_moe_grad(m->E, T, topk, G->K, G->N, G->dtype);
+    if (!ws || ws_bytes < pl.bytes) return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", pl.bytes, ws ? ws_bytes : (size_t)0);
+    hipError_t e = launch_moe_grad(*m, table, grad_table, pl, x, idx, w, dout, T, topk, dx, dw, (char*)ws, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "gptq_moe_backward launch");
+    if (dgu_out) {
+        const size_t R = (size_t)T * topk, gb = R * G->N * dtype_size(G->dtype);
+        e = hipMemcpyAsync(dgu_out, (char*)ws + pl.off_g, gb, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+        if (e == hipSuccess) e = hipMemcpyAsync((char*)dgu_out + gb, (char*)ws + pl.off_u, gb, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+        if (e == hipSuccess) e = hipMemcpyAsync((char*)dgu_out + 2 * gb, (char*)ws + pl.off_pos, 4 * R, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+        if (e != hipSuccess) return hip_fail(e, "gptq_moe_backward dgu_out copy");
+    }
+    return GPTQ_OK;
+}
+
+int gptq_describe_moe_backward_plan(const gptq_moe_t* m, int T, int topk, char* out, size_t out_bytes) {
+    if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out is NULL");
+    if (moe_check(m, T, topk)) {
+        char reason[sizeof(g_err)];
+        snprintf(reason, sizeof(reason), "%s", g_err);
+        for (char* c = reason; *c; ++c)
+            if (*c == ' ' || *c == '=') *c = '_';
+        snprintf(out, out_bytes, "path=per_expert reason=%s", reason);
+        return GPTQ_OK;
+    }
+    const gptq_layer_t* G = m->gate[0];
+    const MoeGradPlan pl = plan_moe_grad(m->E, T, topk, G->K, G->N, G->dtype);
+    snprintf(out, out_bytes, "path=grouped_backward tiles=%d launches=%d wg_recompute=%ld wg_down=%ld wg_up=%ld", pl.tiles, T > 0 ? 5 : 0,
+             (long)pl.tiles * (G->N / 64), (long)pl.tiles * pl.nblk_i, (long)pl.tiles * pl.nblk_h);
+    return GPTQ_OK;
+}
+
 // ---- the same layers at 1..4 tokens on the experts' decode copy (moe_decode.hip) ----
 static int moe_decode_check_proj(const gptq_layer_t* const* Ls, int E, int K, int N, const gptq_layer_t* A, const char* name) {
     if (!Ls) return fail(GPTQ_ERR_NULL, "moe->%s is NULL", name);

@@ -192,6 +192,19 @@ hipError_t launch_moe_route(const int64_t* idx, int T, int topk, int E, int bm, 
                             hipStream_t st);
 hipError_t launch_moe_combine(const int* pos, const float* w, const float* y, void* out, int T, int topk, int H, int ksplit, int rstride, int dtype,
                               hipStream_t st);
+// ... and of the pair-mode grouped GEMM with the recompute epilogue (g -> G_sorted, u -> U_sorted [R][I] in T, no silu * mul): moe_grad.hip's second launch
+hipError_t launch_moe_recompute(const gptq_moe_t& m, const void* table, const void* x, const int* row_assign, const int* tile_count, const void* tiles,
+                                int tiles_bound, int T, int topk, void* g_out, void* u_out, hipStream_t st);
+// moe_grad.hip: the backward of the routed layer (gptq_moe_backward): route, recompute g / u, down stage, up stage, combine -- five launches
+struct MoeGradPlan {
+    int tiles, nblk_i, nblk_h;                      // tile bound (64-row tiles), 128-column blocks of I and of H
+    size_t off_offsets, off_tile_count, off_tiles, off_pos, off_rows, off_g, off_u, off_dwp, off_dxr, bytes;   // workspace layout (from GPTQ_WORKSPACE_HEADER_BYTES on)
+};
+MoeGradPlan plan_moe_grad(int E, int T, int topk, int H, int I, int dtype);
+size_t moe_grad_table_entry_bytes();
+void moe_grad_table_entry(const gptq_layer_t& L, void* dst);
+hipError_t launch_moe_grad(const gptq_moe_t& m, const void* table, const void* grad_table, const MoeGradPlan& pl, const void* x, const int64_t* idx,
+                           const float* w, const void* dout, int T, int topk, void* dx, float* dw, char* ws, hipStream_t st);
 // moe_decode.hip: the same layer at 1..4 tokens on the experts' decode copy (gptq_moe_decode_forward): gate|up + silu * mul, down + combine -- two launches
 struct MoeDecodePlan {
     bool ok;                                        // the staged rows and constants fit the LDS

@@ -135,7 +135,7 @@ __global__ void __launch_bounds__(ROUTE_THREADS) moe_route_kernel(RouteArgs p) {
 struct GemmArgs {
     const ExpertPtrs* table;                    // entries of the first projection (pair mode: W1; W3 is table + E)
     int E;
-    int pair;                                   // 1: W1 / W3 + silu * mul -> H (T); 0: one projection -> Y (fp32)
+    int pair;                                   // 1: W1 / W3 + silu * mul -> H (T); 0: one projection -> Y (fp32); 2: W1 / W3 -> G, U (T): the backward's recompute
     const void* a;                              // pair: x [T][K]; down: H_sorted [R][K]
     const int* row_assign;
     int topk;
@@ -143,8 +143,9 @@ struct GemmArgs {
     const int4* tiles;
     int K, N, bits, group_size, zero_mode;
     int nblk, ksplit, steps_per_split;          // column blocks; K slices and 32-deep steps per slice
-    void* out;                                  // pair: H_sorted [R][N] (T); down: Y [ksplit][rstride][N] fp32
+    void* out;                                  // pair: H_sorted [R][N] (T); down: Y [ksplit][rstride][N] fp32; pair == 2: G_sorted [R][N] (T)
     int rstride;
+    void* out2;                                 // pair == 2: U_sorted [R][N] (T)
 };
 
 // A fragment of one lane: 8 consecutive k of one row, put in the order the dequantised B fragment has
@@ -329,6 +330,15 @@ __global__ void __launch_bounds__(THREADS) moe_gemm_kernel(GemmArgs p) {
         u += *(const f32x4*)&red[2][row][c4];
         u += *(const f32x4*)&red[3][row][c4];
         unsigned short o[4];
+        if (p.pair == 2) {                      // the sums themselves, rounded once each
+#pragma unroll
+            for (int c = 0; c < 4; ++c) o[c] = __builtin_bit_cast(unsigned short, DType<T>::from_f32(u[c]));
+            *(u32x2*)((T*)p.out2 + (size_t)(row0 + row) * p.N + n0 + c4) = u32x2{o[0] | ((unsigned)o[1] << 16), o[2] | ((unsigned)o[3] << 16)};
+#pragma unroll
+            for (int c = 0; c < 4; ++c) o[c] = __builtin_bit_cast(unsigned short, DType<T>::from_f32(sg[m][c]));
+            *(u32x2*)(h + (size_t)(row0 + row) * p.N + n0 + c4) = u32x2{o[0] | ((unsigned)o[1] << 16), o[2] | ((unsigned)o[3] << 16)};
+            continue;
+        }
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const float gv = sg[m][c];
@@ -444,7 +454,7 @@ hipError_t launch_moe(const gptq_moe_t& m, const void* table, const MoePlan& pl,
     g.tile_count = tile_count; g.tiles = tiles;
     g.K = H; g.N = I; g.bits = G.bits; g.group_size = G.group_size; g.zero_mode = G.zero_mode;
     g.nblk = I / moe::BN; g.ksplit = 1; g.steps_per_split = H / 32;
-    g.out = ws + pl.off_h; g.rstride = R;
+    g.out = ws + pl.off_h; g.rstride = R; g.out2 = nullptr;
     auto gemm = [&](const moe::GemmArgs& a, long blocks) -> hipError_t {
         if (blocks <= 0) return hipSuccess;
         if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
@@ -463,6 +473,24 @@ hipError_t launch_moe(const gptq_moe_t& m, const void* table, const MoePlan& pl,
     if ((e = gemm(d, (long)pl.tiles * d.nblk * d.ksplit)) != hipSuccess) return e;
 
     return launch_moe_combine(pos, w, (const float*)(ws + pl.off_y), out, T, topk, H, pl.ksplit, R, G.dtype, st);
+}
+
+hipError_t launch_moe_recompute(const gptq_moe_t& m, const void* table, const void* x, const int* row_assign, const int* tile_count, const void* tiles,
+                                int tiles_bound, int T, int topk, void* g_out, void* u_out, hipStream_t st) {
+    const gptq_layer_t& G = *m.gate[0];
+    moe::GemmArgs g;
+    g.table = (const moe::ExpertPtrs*)table;
+    g.E = m.E; g.pair = 2; g.a = x; g.row_assign = row_assign; g.topk = topk;
+    g.tile_count = tile_count; g.tiles = (const int4*)tiles;
+    g.K = G.K; g.N = G.N; g.bits = G.bits; g.group_size = G.group_size; g.zero_mode = G.zero_mode;
+    g.nblk = G.N / moe::BN; g.ksplit = 1; g.steps_per_split = G.K / 32;
+    g.out = g_out; g.rstride = T * topk; g.out2 = u_out;
+    const long blocks = (long)tiles_bound * g.nblk;
+    if (blocks <= 0) return hipSuccess;
+    if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
+    if (G.dtype == GPTQ_F16) hipLaunchKernelGGL(moe::moe_gemm_kernel<f16>, dim3((unsigned)blocks), dim3(moe::THREADS), 0, st, g);
+    else hipLaunchKernelGGL(moe::moe_gemm_kernel<bf16>, dim3((unsigned)blocks), dim3(moe::THREADS), 0, st, g);
+    return hipGetLastError();
 }
 
 size_t moe_table_entry_bytes() { return sizeof(moe::ExpertPtrs); }

@@ -62,10 +62,10 @@ __global__ void __launch_bounds__(256) unpack_zeros_kernel(const unsigned* __res
 // W[k,n] = T( float(scale[g,n]) * float(w - z) ): the fp32 product is exact for 16-bit scales, so
 // this is the correctly rounded product = what torch computes for scales * (weight - zeros).
 template <int BITS, typename T>
-__global__ void __launch_bounds__(256) dequant_kernel(const unsigned* __restrict__ qweight, const unsigned* __restrict__ qzeros,
-                                                      const T* __restrict__ scales, const int* __restrict__ g_idx,
-                                                      int units, int N, int group_size, int zero_mode,
-                                                      T* __restrict__ out) {
+__device__ __forceinline__ void dequant_body(const unsigned* __restrict__ qweight, const unsigned* __restrict__ qzeros,
+                                             const T* __restrict__ scales, const int* __restrict__ g_idx,
+                                             int units, int N, int group_size, int zero_mode,
+                                             T* __restrict__ out) {
     constexpr int UW = Pack<BITS>::words, KPU = Pack<BITS>::vals;
     const int n0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
     const int u = blockIdx.y;
@@ -91,6 +91,20 @@ __global__ void __launch_bounds__(256) dequant_kernel(const unsigned* __restrict
          }()),
          ...);
     }(std::make_integer_sequence<int, KPU>{});
+}
+
+// bits is a run-time, workgroup-uniform argument: one instantiation per dtype, the four packings behind one switch
+template <typename T>
+__global__ void __launch_bounds__(256) dequant_kernel(const unsigned* __restrict__ qweight, const unsigned* __restrict__ qzeros,
+                                                      const T* __restrict__ scales, const int* __restrict__ g_idx,
+                                                      int units, int N, int group_size, int zero_mode, int bits,
+                                                      T* __restrict__ out) {
+    switch (bits) {
+        case 2: dequant_body<2, T>(qweight, qzeros, scales, g_idx, units, N, group_size, zero_mode, out); break;
+        case 3: dequant_body<3, T>(qweight, qzeros, scales, g_idx, units, N, group_size, zero_mode, out); break;
+        case 4: dequant_body<4, T>(qweight, qzeros, scales, g_idx, units, N, group_size, zero_mode, out); break;
+        default: dequant_body<8, T>(qweight, qzeros, scales, g_idx, units, N, group_size, zero_mode, out); break;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -380,15 +394,6 @@ hipError_t launch_silu_mul(const void* y, void* out, int M, int N, int dtype, hi
 }
 
 // ---------------------------------------------------------------------------------------------
-#define GPTQ_BITS_SWITCH(bits, EXPR)                      \
-    switch (bits) {                                       \
-        case 2: { constexpr int B = 2; EXPR; } break;     \
-        case 3: { constexpr int B = 3; EXPR; } break;     \
-        case 4: { constexpr int B = 4; EXPR; } break;     \
-        case 8: { constexpr int B = 8; EXPR; } break;     \
-        default: return hipErrorInvalidValue;             \
-    }
-
 hipError_t launch_unpack_weights(const uint32_t* qweight, int K, int N, int bits, uint8_t* w_out, hipStream_t st) {
     const int units = K / unit_vals(bits);
     dim3 grid((N / 4 + 255) / 256, units), block(256);
@@ -406,8 +411,9 @@ template <typename T>
 static hipError_t launch_dequant_t(const gptq_layer_t& L, void* W_out, hipStream_t st) {
     const int units = L.K / unit_vals(L.bits);
     dim3 grid((L.N / 4 + 255) / 256, units), block(256);
-    GPTQ_BITS_SWITCH(L.bits, hipLaunchKernelGGL((dequant_kernel<B, T>), grid, block, 0, st, L.qweight, L.qzeros,
-                                                (const T*)L.scales, L.g_idx, units, L.N, L.group_size, L.zero_mode, (T*)W_out));
+    if (L.bits != 2 && L.bits != 3 && L.bits != 4 && L.bits != 8) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(dequant_kernel<T>, grid, block, 0, st, L.qweight, L.qzeros, (const T*)L.scales, L.g_idx, units, L.N, L.group_size, L.zero_mode,
+                       L.bits, (T*)W_out);
     return hipGetLastError();
 }
 

@@ -87,7 +87,7 @@ def pack_model(model: nn.Module, quantizers: dict, bits: int, group_size: int, d
 
 def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_length: Optional[int] = None,
                        release_checkpoint_layout: Optional[bool] = None, decode_copy: Optional[bool] = None,
-                       expert_decode_copy: bool = False, expert_batched_decode: bool = False) -> nn.Module:
+                       expert_decode_copy: bool = False, expert_batched_decode: bool = False, expert_backward: bool = False) -> nn.Module:
     """post_init every mi355x layer and size the per-device scratch once (so forward never allocates; needed before hipGraph
     capture).  ``max_input_length`` bounds the rows M the scratch is sized for (default 2048, the reference's exllama default).
     Memory (the model-level switches for what post_init keeps next to the checkpoint tensors): ``decode_copy=False`` builds no decode copy (1x the packed
@@ -99,7 +99,10 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
     ``max_input_length`` tokens at the module's ``top_k``.  ``expert_decode_copy=True`` gives the expert layers a decode copy as well (2x the packed expert
     bytes -- Mixtral-8x7B 4-bit: about 23 GB -> 46 GB of 288 GB; both layouts stay resident): calls of 1..4 tokens then run the two-launch decode kernels,
     larger ones the grouped path as before.  ``expert_batched_decode=True`` (implies the expert decode copy) also routes calls of 5..64 tokens to the batch
-    kernels on that copy (``QuantMoEExperts.post_init(batch=True)``); the scratch covers the largest need of the paths up to ``max_input_length``."""
+    kernels on that copy (``QuantMoEExperts.post_init(batch=True)``); the scratch covers the largest need of the paths up to ``max_input_length``.
+    ``expert_backward=True`` (``QuantMoEExperts.post_init(backward=True)``): calls under grad run the grouped backward (one autograd node, one
+    gptq_moe_backward call) instead of the per-expert composition; the scratch also covers ``gptq_moe_backward_workspace_bytes`` of ``max_input_length``
+    tokens."""
     from .moe import QuantMoEExperts
     rows = max_input_length or 2048
     need: Dict[torch.device, int] = {}
@@ -109,7 +112,7 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
         # mixture-of-experts layers: their QuantLinears are post-initialised by the module (no decode copy; a checkpoint-layout release does not apply)
         if isinstance(sub, QuantMoEExperts) and sub[0].layers()[0].qweight.device.type == "cuda":
             dev = sub[0].layers()[0].qweight.device
-            sub.post_init(decode_copy=expert_decode_copy, batch=expert_batched_decode)
+            sub.post_init(decode_copy=expert_decode_copy, batch=expert_batched_decode, backward=expert_backward)
             for e in range(sub.num_experts):
                 in_experts.update(id(l) for l in sub[e].layers())
             expert_copy_bytes += sub.decode_copy_bytes
@@ -117,6 +120,8 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
             if expert_batched_decode:
                 ts.add(min(rows, sub.batch_max_tokens))          # the batch path's need grows with T: its largest T
             need[dev] = max([need.get(dev, 0)] + [sub.workspace_bytes(t, sub.top_k) for t in sorted(ts)])
+            if sub._grad_table is not None:
+                need[dev] = max(need[dev], sub.backward_workspace_bytes(rows, sub.top_k))
     for _, sub in model.named_modules():
         if getattr(sub, "QUANT_TYPE", None) != QuantLinear.QUANT_TYPE or id(sub) in in_experts:
             continue

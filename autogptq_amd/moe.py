@@ -12,8 +12,10 @@
 * ``pack_moe_experts``  pack the dense 3-D expert parameters of a model (``quantizers`` keyed ``...mlp.experts.{e}.w1`` as ``pack_model`` takes)
 
 The per-expert composition serves what the grouped kernels do not take (2- / 3-bit or fp32 experts, odd group sizes, raw act-order), CPU tensors (which
-``QuantLinear`` refuses), and calls under grad where ``hidden_states`` or ``top_k_weights`` require grad: training through the experts gets dX and the
-router-weight gradient from the existing backward of ``QuantLinear``.
+``QuantLinear`` refuses), and -- by default -- calls under grad where ``hidden_states`` or ``top_k_weights`` require grad: training through the experts gets
+dX and the router-weight gradient from the existing backward of ``QuantLinear``.  After ``post_init(backward=True)`` such a call is ONE autograd node
+instead: the forward runs the ordinary no-grad path, the backward is one gptq_moe_backward call (route, recompute of gate / up, two grouped transposed
+dequant-GEMM stages on the checkpoint rows, combine -- five launches, nothing saved but the inputs).
 """
 from __future__ import annotations
 
@@ -66,6 +68,7 @@ class QuantMoEExperts(nn.Module):
         self.names = tuple(names)
         self._decode_copy = False
         self._batch = False
+        self._backward = False
         self.batch_max_tokens = 64
         for e in range(num_experts):
             self.add_module(str(e), _Expert(self.names, bits, group_size, hidden_dim, intermediate_dim, weight_dtype, zero_mode))
@@ -80,6 +83,7 @@ class QuantMoEExperts(nn.Module):
     def _invalidate(self):
         self._moe = None
         self._decode_table = None
+        self._grad_table = None
         self._batch_ok = False
         self.decode_copy_bytes = 0
         self._keep = ()
@@ -101,18 +105,20 @@ class QuantMoEExperts(nn.Module):
         return [l[0] for l in ls], [l[1] for l in ls], [l[2] for l in ls]
 
     # ------------------------------------------------------------------ post_init
-    def post_init(self, decode_copy: bool = False, batch: bool = False):
+    def post_init(self, decode_copy: bool = False, batch: bool = False, backward: bool = False):
         """post_init every expert layer and build the pointer table.  Default: WITHOUT a decode copy (1x the packed bytes; act-order layers add their
         re-sequenced rows) -- calls of any row count run the grouped kernels.  ``decode_copy=True``: the layers also get their decode copy (2x the packed
         bytes; both layouts stay resident: the grouped path still serves more than 4 tokens), the decode table is built, and calls of 1..4 tokens run the
         decode kernels (``plan(T)["path"] == "decode"``).  ``batch=True`` (opt-in as well; builds the decode copy and its table if not asked for already):
         calls of 5..``batch_max_tokens`` (64) tokens run the batch kernels on the copy (``plan(T)["path"] == "batch"``); experts the batch plan declines
-        log the reason once and behave as without the flag.  ``decode_copy_bytes`` reports what the copies hold.  A checkpoint-layout release does not
-        apply to expert layers."""
+        log the reason once and behave as without the flag.  ``backward=True`` (opt-in as well): calls under grad whose ``hidden_states`` or
+        ``top_k_weights`` require grad run the grouped backward (``last_plan["backward"] == "grouped"``: one autograd node, one gptq_moe_backward call
+        on a pointer table of its own) instead of the per-expert composition; experts the backward plan declines log the reason once and keep the
+        composition.  ``decode_copy_bytes`` reports what the copies hold.  A checkpoint-layout release does not apply to expert layers."""
         dev = self[0].layers()[0].qweight.device
         if dev.type != "cuda":
             raise RuntimeError(f"mi355x QuantMoEExperts.post_init needs the module on a ROCm GPU device (got {dev}); there is no CPU path.")
-        want_decode, self._batch = bool(decode_copy), bool(batch)
+        want_decode, self._batch, self._backward = bool(decode_copy), bool(batch), bool(backward)
         if self._batch:
             why = self._batch_declined()
             if why:
@@ -140,6 +146,7 @@ class QuantMoEExperts(nn.Module):
         self._moe, self._keep, self._plans = m, (arrs, table, gate, up, down), {}
         self._table = table
         self._decode_table = None
+        self._grad_table = None
         self._batch_ok = False
         self.decode_copy_bytes = extra
         self._dev = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
@@ -147,17 +154,27 @@ class QuantMoEExperts(nn.Module):
         if self.plan(1, self.top_k)["path"] == "grouped":          # (a declined layer set has no valid table: it runs per expert)
             with torch.cuda.device(self._dev):
                 _lib.check(lib.gptq_moe_build_table(ctypes.byref(m), table.data_ptr(), _lib.current_stream_handle(self._dev)))
+        if self._backward:
+            gplan = _lib.describe_moe_backward_plan(m, 1, self.top_k)
+            if gplan["path"] != "grouped_backward":
+                logger.warning("QuantMoEExperts.post_init(backward=True) has no effect for these experts (%s): calls under grad keep the per-expert "
+                               "composition", str(gplan.get("reason", "")).replace("_", " "))
+            else:
+                gtable = torch.zeros(max(1, int(lib.gptq_moe_grad_table_bytes(self.num_experts))), dtype=torch.uint8, device=dev)
+                with torch.cuda.device(self._dev):
+                    _lib.check(lib.gptq_moe_build_grad_table(ctypes.byref(m), gtable.data_ptr(), _lib.current_stream_handle(self._dev)))
+                self._grad_table = gtable
         if self._decode_copy:
             dplan = _lib.describe_moe_decode_plan(m, 1, self.top_k)
             if dplan["path"] != "decode":
                 # declined (2- / 3-bit, fp32, a group size the copy does not take, ...): nothing would read the copies -- say so and give their memory back
                 logger.warning("QuantMoEExperts.post_init(decode_copy=True) has no effect for these experts (%s): no decode copy is kept",
                                str(dplan.get("reason", "")).replace("_", " "))
-                return self.post_init(decode_copy=False)
+                return self.post_init(decode_copy=False, backward=self._backward)
             bplan = _lib.describe_moe_batch_plan(m, 5, self.top_k) if self._batch else None
             if bplan is not None and bplan["path"] != "batch":
                 logger.warning("QuantMoEExperts.post_init(batch=True) has no effect for these experts (%s)", str(bplan.get("reason", "")).replace("_", " "))
-                return self.post_init(decode_copy=want_decode)
+                return self.post_init(decode_copy=want_decode, backward=self._backward)
             dtable = torch.zeros(max(1, int(lib.gptq_moe_decode_table_bytes(self.num_experts))), dtype=torch.uint8, device=dev)
             with torch.cuda.device(self._dev):
                 _lib.check(lib.gptq_moe_build_decode_table(ctypes.byref(m), dtable.data_ptr(), _lib.current_stream_handle(self._dev)))
@@ -200,13 +217,21 @@ class QuantMoEExperts(nn.Module):
     def workspace_bytes(self, T: int, top_k: "int | None" = None) -> int:
         """Scratch of one call with T tokens on the path ``plan(T)`` names."""
         if self._moe is None:
-            self.post_init(self._decode_copy, self._batch)
+            self.post_init(self._decode_copy, self._batch, self._backward)
         path = self.plan(T, top_k)["path"]
         if path == "decode":
             return int(_lib.load().gptq_moe_decode_workspace_bytes(ctypes.byref(self._moe), T, top_k or self.top_k))
         if path == "batch":
             return int(_lib.load().gptq_moe_batch_workspace_bytes(ctypes.byref(self._moe), T, top_k or self.top_k))
         return int(_lib.load().gptq_moe_workspace_bytes(ctypes.byref(self._moe), T, top_k or self.top_k))
+
+    def backward_workspace_bytes(self, T: int, top_k: "int | None" = None) -> int:
+        """Scratch of one gptq_moe_backward call with T tokens (0 when the experts have no grouped backward)."""
+        if self._moe is None:
+            self.post_init(self._decode_copy, self._batch, self._backward)
+        if self._grad_table is None:
+            return 0
+        return int(_lib.load().gptq_moe_backward_workspace_bytes(ctypes.byref(self._moe), T, top_k or self.top_k))
 
     def plan(self, T: int, top_k: "int | None" = None) -> dict:
         """{"path": "decode" | "batch" | "grouped" | "per_expert", "reason": ...} (+ the launch / tile geometry) for T tokens: what moe_forward runs
@@ -216,7 +241,7 @@ class QuantMoEExperts(nn.Module):
         if self[0].layers()[0].qweight.device.type != "cuda":
             return {"path": "per_expert", "reason": "cpu tensors"}
         if self._moe is None:
-            self.post_init(self._decode_copy, self._batch)
+            self.post_init(self._decode_copy, self._batch, self._backward)
         key = (T, top_k, self.batch_max_tokens)
         d = self._plans.get(key)
         if d is None:
@@ -255,6 +280,10 @@ def moe_forward(experts: QuantMoEExperts, x: torch.Tensor, top_k_index: torch.Te
     grad = torch.is_grad_enabled() and (x.requires_grad or top_k_weights.requires_grad)
     if x.device.type != "cuda":
         experts.last_plan = {"path": "per_expert", "reason": "cpu tensors"}
+    elif grad and experts._backward and _grouped_backward_ready(experts):
+        if return_intermediate:
+            raise RuntimeError("moe_forward: return_intermediate is not available under grad")
+        return _MoEBackward.apply(experts, x, top_k_index, top_k_weights)
     elif grad:
         experts.last_plan = {"path": "per_expert", "reason": "grad enabled and hidden_states / top_k_weights require grad"}
     else:
@@ -314,6 +343,72 @@ def moe_forward(experts: QuantMoEExperts, x: torch.Tensor, top_k_index: torch.Te
     hs = h_out[:R * I * es].view(w_dtype).view(R, I)
     pos = h_out[R * I * es:].view(torch.int32).view(T, topk)
     return res, hs, pos
+
+
+def _grouped_backward_ready(experts: QuantMoEExperts) -> bool:
+    """The experts were post-initialised with backward=True and the backward plan took them (post_init runs here when the tables were invalidated)."""
+    if experts._moe is None:
+        experts.post_init(experts._decode_copy, experts._batch, experts._backward)
+    return experts._grad_table is not None
+
+
+def _aligned(t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """t as a contiguous, 16-byte aligned tensor of ``dtype`` (the C ABI's rule for x / dout)."""
+    if t.dtype != dtype:
+        t = t.to(dtype)
+    if not t.is_contiguous():
+        t = t.contiguous()
+    if t.data_ptr() & 15:
+        t = t.clone()
+    return t
+
+
+class _MoEBackward(torch.autograd.Function):
+    """``moe_forward`` under grad as one node: forward = the no-grad path ``plan(T)`` names (bit-identical values), backward = one gptq_moe_backward call
+    that recomputes gate / up from x.  Saves x, top_k_index and top_k_weights only; no double backward."""
+
+    @staticmethod
+    def forward(ctx, experts, x, top_k_index, top_k_weights):
+        with torch.no_grad():
+            out = moe_forward(experts, x.detach(), top_k_index, top_k_weights.detach())
+        experts.last_plan = dict(experts.last_plan, backward="grouped")
+        ctx.experts = experts
+        ctx.save_for_backward(x, top_k_index, top_k_weights)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        experts = ctx.experts
+        x, top_k_index, top_k_weights = ctx.saved_tensors
+        if not _grouped_backward_ready(experts):
+            raise RuntimeError("mi355x moe backward: the experts lost their grouped backward between forward and backward")
+        want_x, want_w = ctx.needs_input_grad[1], ctx.needs_input_grad[3]
+        H = experts.hidden_dim
+        dev, w_dtype = experts._dev, experts._w_dtype
+        x2 = _aligned(x.reshape(-1, H), w_dtype)
+        T = x2.shape[0]
+        topk = top_k_index.shape[-1] if top_k_index.dim() else 1
+        dout = _aligned(grad_out.reshape(-1, H), w_dtype)
+        idx = top_k_index.reshape(T, topk).to(torch.int64).contiguous()
+        w = top_k_weights.reshape(T, topk).to(torch.float32).contiguous()
+        dx = torch.empty((T, H), dtype=w_dtype, device=dev) if want_x else None
+        dw = torch.empty((T, topk), dtype=torch.float32, device=dev) if want_w else None
+        if T and (want_x or want_w):
+            need = experts._plans.get(("bws", T, topk))
+            if need is None:
+                need = experts._plans[("bws", T, topk)] = experts.backward_workspace_bytes(T, topk)
+            buf = reserve_workspace(dev, need)
+            exchange_tick(dev)
+            with torch.cuda.device(dev.index):
+                rc = _lib.load().gptq_moe_backward(ctypes.byref(experts._moe), experts._table.data_ptr(), experts._grad_table.data_ptr(), x2.data_ptr(),
+                                                   idx.data_ptr(), w.data_ptr(), dout.data_ptr(), T, topk, _lib.ptr(dx), _lib.ptr(dw), None,
+                                                   buf.data_ptr(), buf.numel(), _raw_stream(dev.index))
+            if rc:
+                _lib.check(rc)
+        gx = dx.to(x.dtype).reshape(x.shape) if want_x else None
+        gw = dw.to(top_k_weights.dtype).reshape(top_k_weights.shape) if want_w else None
+        return None, gx, None, gw
 
 
 def _per_expert(experts: QuantMoEExperts, x: torch.Tensor, idx: torch.Tensor, w: torch.Tensor) -> torch.Tensor:

@@ -19,6 +19,8 @@
  *       <- the expert loop of the reference's Mixtral (per-expert QuantLinears, auto_gptq/modeling/mixtral.py) as one routed, grouped call
  *   gptq_moe_decode_forward, gptq_moe_batch_forward
  *       <- the same expert loop at the row counts of token generation (1..4 tokens) and of batched generation (5..64), on the experts' decode copy
+ *   gptq_moe_backward
+ *       <- autograd through the same expert loop (dequantise + torch.matmul per expert), as one routed, grouped call
  *   gptq_grad_input
  *       <- the backward of the reference's training route: dequantise + torch.matmul under autograd
  *                                                                     qlinear_cuda_old.py:291-355, qlinear_cuda.py:253-317
@@ -365,6 +367,39 @@ int gptq_moe_batch_forward(const gptq_moe_t *moe, const void *table, const void 
 /* Host-only: "path=batch bm=16 s=4 tiles=10 launches=4 waves_pair=8 waves_down=8 lds_pair=... lds_down=..." (s: strip-chunks per wave and chunk -- the pair
  * form runs 2 strips of W1 and of W3, the down form 4 of W2) or "path=none reason=..." (no decode copy, T > 64, 2- / 3-bit, fp32, ...).  GPTQ_OK either way. */
 int gptq_describe_moe_batch_plan(const gptq_moe_t *moe, int T, int topk, char *out, size_t out_bytes);
+
+/* BACKWARD of the routed layer (additive in ABI 8): the gradients of gptq_moe_forward's formulas with respect to x and topk_w, from the packed weights.
+ * Given dout [T, H] in the experts' dtype T, for every valid assignment r = (t, j) with expert e:
+ *   d_r     = dout[t] . W2_e^T                          fp32 sums over H, every W bit-exact to gptq_dequant
+ *   dw[t,j] = sum_i d_r[i] h_r[i]                       fp32, fixed order; h_r = T(silu(g_r) u_r)
+ *   dg_r    = T(w[t,j] d_r u_r silu'(g_r))              silu'(g) = s (1 + g (1 - s)), s = 1 / (1 + exp(-g)), on fp32, one rounding
+ *   du_r    = T(w[t,j] d_r silu(g_r))
+ *   dx[t]   = T(sum_j (dg_r . W1_e^T + du_r . W3_e^T))  fp32, ascending j, one rounding
+ * Nothing is saved by the forward: g_r = T(x_t . W1_e), u_r = T(x_t . W3_e) are recomputed (the grouped GEMM's fp32 sums, rounded once).  Dropped
+ * assignments give dw = 0 and contribute nothing; a token without a valid expert gets a zero dx row.  No atomics, fixed summation orders: bit-reproducible
+ * and independent of the tiling.  Takes exactly what gptq_moe_forward takes; anything else is GPTQ_ERR_UNSUPPORTED with the reason.
+ *   Launches: routing (64-row tiles), recompute of g / u (the forward's grouped GEMM, reading `table`), down stage (d, dg, du, dw partials), up stage
+ *   (fp32 rows of dx per assignment), combine: FIVE (four when dx is NULL).  The down and up stages read the CHECKPOINT rows (qweight with g_idx, as
+ *   gptq_grad_input does) through a table of their own: [3 projections][E] entries of 32 bytes {qweight, qzeros, scales, g_idx or NULL};
+ *   gptq_moe_build_grad_table fills gptq_moe_grad_table_bytes(E) = 3 E 32 caller-owned device bytes, synchronises `stream` (not capturable); rebuild it
+ *   whenever a layer's buffers move. */
+size_t gptq_moe_grad_table_bytes(int E);
+int gptq_moe_build_grad_table(const gptq_moe_t *moe, void *table, void *stream);
+/* Workspace of one call:  GPTQ_WORKSPACE_HEADER_BYTES (left untouched)
+ *   + a256(4 (E + 1)) + 256 + a256(16 tiles) + 2 a256(4 T topk) + 2 a256(T topk I sizeof(T)) + a256(4 T topk ceil(I / 128)) + a256(4 T topk H),
+ * a256 = round up to 256, tiles = floor(T topk / 64) + min(E, T topk): offsets, tile count, tiles, pos, sorted rows, G and U (overwritten by dg and du),
+ * the dw partials, and the fp32 dx rows per assignment.  0 when the call is declined. */
+size_t gptq_moe_backward_workspace_bytes(const gptq_moe_t *moe, int T, int topk);
+/* dx [T, H] (layer dtype) or NULL, dw [T, topk] fp32 or NULL (both NULL: GPTQ_ERR_NULL).  x, topk_idx, topk_w as gptq_moe_forward took them, dout [T, H]
+ * layer dtype; x, dout, dx and the workspace 16-byte aligned.  `table` is the forward table (gptq_moe_build_table), `grad_table` the one above.
+ * dgu_out (optional, for tests): the kernel's dg rows [T topk, I], then its du rows [T topk, I] (layer dtype, rows grouped by expert as H_sorted), then
+ * pos [T, topk] int32, copied in stream order.  Caller's stream, no allocation, no synchronisation, legal inside hipGraph capture; the grids are bounds
+ * from (T, topk, E) alone, so a captured graph replays with new routing.  T = 0 launches nothing. */
+int gptq_moe_backward(const gptq_moe_t *moe, const void *table, const void *grad_table, const void *x, const int64_t *topk_idx, const float *topk_w,
+                      const void *dout, int T, int topk, void *dx, float *dw, void *dgu_out, void *workspace, size_t workspace_bytes, void *stream);
+/* Host-only: "path=grouped_backward tiles=3 launches=5 wg_recompute=... wg_down=... wg_up=..." or "path=per_expert reason=...", for (moe, T, topk).
+ * GPTQ_OK either way (GPTQ_ERR_NULL for a NULL out). */
+int gptq_describe_moe_backward_plan(const gptq_moe_t *moe, int T, int topk, char *out, size_t out_bytes);
 
 /* Integer unpack (bit-exact targets). w_out uint8 [K,N]; z_out int32 [G,N] (zero-point as used). */
 int gptq_unpack_weights(const uint32_t *qweight, int K, int N, int bits, uint8_t *w_out, void *stream);

@@ -102,6 +102,46 @@ __device__ __forceinline__ void dma16_nt(const void* gsrc, unsigned lds_dst) {
                  : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
 }
 
+// The same DMA from a 64-bit SCALAR base plus a 32-bit lane offset (global_load_lds with saddr), for a burst whose lanes keep one offset register: M0 is set
+// per DMA and NOT saved -- nothing else in these kernels reads it (gfx9 LDS instructions do not; the compiler emits no other M0 user here), and the save /
+// restore pair was two of five instructions.  sbase must come from scalar arithmetic on kernel arguments (no VALU-written SGPR: the VMEM read of it would
+// need wait states the compiler cannot see inside the string); s_nop 0: the M0 write -> LDS-DMA hazard.
+template <bool NT> __device__ __forceinline__ void dma16_sv(__attribute__((address_space(1))) const char* sbase, unsigned voff, unsigned lds_dst) {
+    if constexpr (NT) asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 nt" : : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
+    else asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
+}
+// Stage ROWS rows of `pieces` 16-byte pieces, global -> LDS, by all waves of a workgroup: piece i of row r goes from base[r] + 16 i to LDS byte lds[r] + 16 i.
+// Round t moves pieces [t step, (t + 1) step) (step = threads of the workgroup), thread tid its piece tid + t step: the lane offset 16 (tid + t step) is the
+// DMAs' only vector operand, the row's base stays scalar.  Straight-line for what the planner's geometries produce -- a wave with no piece skips everything
+// on ONE scalar compare (w64 = 64 * wave), one round, two rounds -- and a loop from the third round on (long K).  Only a ragged last wave runs with lanes
+// masked off.
+template <int ROWS, bool NT>
+__device__ __forceinline__ void stage_rows(__attribute__((address_space(1))) const char* const (&base)[ROWS], const unsigned (&lds)[ROWS], int tid, int w64, int step, int pieces) {
+    if (w64 >= pieces) return;
+    if (tid < pieces) {
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) dma16_sv<NT>(base[r], (unsigned)tid * 16u, lds[r] + (unsigned)w64 * 16u);
+    }
+    if (w64 + step >= pieces) return;
+    if (tid + step < pieces) {
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) dma16_sv<NT>(base[r], (unsigned)(tid + step) * 16u, lds[r] + (unsigned)(w64 + step) * 16u);
+    }
+    if (__builtin_expect(w64 + 2 * step >= pieces, 1)) return;
+    for (int a = 2 * step; w64 + a < pieces; a += step) {                         // wave-uniform trip count
+        if (tid + a < pieces) {
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) dma16_sv<NT>(base[r], (unsigned)(tid + a) * 16u, lds[r] + (unsigned)(w64 + a) * 16u);
+        }
+    }
+}
+// (a >= b) as 1 / 0 on the scalar unit: written in C++, a wave-uniform compare with several users becomes a lane mask and a v_cndmask_b32
+__device__ __forceinline__ int scalar_ge(int a, int b) {
+    int r;
+    asm("s_cmp_ge_i32 %1, %2\n\ts_cselect_b32 %0, 1, 0" : "=s"(r) : "s"(a), "s"(b) : "scc");
+    return r;
+}
+
 struct GemvSeg {
     const unsigned* qweight;
     const unsigned* qzeros;

@@ -229,7 +229,10 @@ hipError_t launch_tiled(const gptq_layer_t* const* Ls, const TiledPlan& pl, cons
         const gptq_layer_t& L = *Ls[i];
         blk += L.N / GPTQ_STRIP_COLS / (pl.pair ? 2 : pl.nstr);
         p.blk_end[i] = blk;
-        p.seg[i] = TiledSeg{L.qweight_tiled, L.qconst_tiled, L.bias, outs[i], L.N, col, L.g_idx ? L.perm : nullptr};
+        p.tq[i] = L.qweight_tiled;
+        p.cst[i] = L.qconst_tiled;
+        p.perm[i] = L.g_idx ? L.perm : nullptr;
+        p.seg[i] = TiledSeg{L.bias, outs[i], L.N, col};
         col += L.N;
     }
     p.blk_end[3] = 0x7fffffff;                                                    // the selector adds three compares: a fourth layer is reached by the first three
@@ -253,6 +256,7 @@ hipError_t launch_tiled(const gptq_layer_t* const* Ls, const TiledPlan& pl, cons
     p.xstride = pl.xstride;
     p.waves = pl.waves;
     p.xraw_off = pl.xraw_off;
+    p.pair_strips = pl.pair ? A.N / (2 * GPTQ_STRIP_COLS) : 0;
     if (pg) {                                                                     // plain layers, 2 or 4 chunks per wave in flight (the compiled forms)
         if (A.g_idx || A.bits == 2 || (pl.u != 2 && pl.u != 4)) return hipErrorInvalidValue;
         return launch_tiled_peer(pl, p, A.dtype, st);                             // gemv_tiled_peer.hip

@@ -3,20 +3,22 @@
 // ([gate | up] layers with the fused SiLU * mul epilogue, XM = 4) -- separate only for build time, and so that the plain kernels carry nothing of the
 // other forms.  Description: gemv_tiled.hip.
 #pragma once
+#include <cstddef>
+
 #include "gemv_shared.cuh"
 
 namespace gptq {
 
-// Kernel arguments, laid out for a short prologue: everything a workgroup needs to find its layer sits in the first bytes (loaded with the other scalars
-// at kernel entry), the layer's pointers are ONE dependent scalar load.  (The first version walked GemvStreamParams::seg[] with a dependent kernarg load per
-// step and divided by ksplit: ~230 instructions and five scalar-load round trips before the first weight load, ~1 us per launch against the lab kernel.)
+// Kernel arguments, laid out for a short head: everything a workgroup needs to form its first weight address and to issue its x and constant DMAs
+// -- the layer boundaries, the geometry, and the weight / constant pointers of ALL four layers -- sits in the first 128 bytes and is loaded in ONE batch of scalar
+// loads at entry; the layer is then chosen by scalar compares and selects, no load is indexed by it in front of the first weight load.  What only the tail
+// and the bias request need of the layer (TiledSeg) is one dependent load issued BEHIND the first weight burst; the K-slice words and the tensor-parallel
+// epilogue lie behind that.  (Before: the layer's pointers were a second, dependent scalar-load round trip in front of the weight loads; the first version
+// walked GemvStreamParams::seg[] with a dependent kernarg load per step and divided by ksplit: five round trips, ~1 us per launch against the lab kernel.)
 struct TiledSeg {
-    const unsigned* tq;      // qweight_tiled
-    const void* cst;         // qconst_tiled
     const void* bias;
     void* out;
     int N, col0;             // columns of this layer; its first column in the concatenated partial slab
-    const int* perm;         // act-order layers (ACT kernels): x position i of the copy = x[perm[i]]; else unused
 };
 // Tensor-parallel epilogue (gptq_forward_scatter; protocol: peer.hip): the owner workgroup of a strip stores its [M][16] outputs at the rank's column
 // offset of EVERY rank's exchange buffer of this call's parity; the rank's arrival flag is raised by the collect launch behind this kernel.
@@ -28,17 +30,27 @@ struct PeerEpi {
     unsigned row_bytes, col_off_bytes, owners, pad_;
 };
 struct TiledParams {
-    int blk_end[4];          // cumulative strip count up to and including layer i (unused entries: INT_MAX)
+    // ---- bytes 0 .. 127: the entry batch
+    int blk_end[4];          // cumulative strip count up to and including layer i (unused entries, and [3]: INT_MAX)
     const void* x;
+    int M, K;
+    int chunks, chunks_per_split, ksplit, gu_shift, groups, xstride, waves;
+    int pair_strips;         // PAIR kernels: strips of one half of the [gate | up] layer (N / 32)
+    const unsigned* tq[4];   // qweight_tiled of layer i
+    const void* cst[4];      // qconst_tiled
+    // ---- act-order kernels: part of their entry batch
+    const int* perm[4];      // x position i of the copy = x[perm[i]]
+    int xraw_off;            // byte offset of the raw x rows (whole K, row stride 2 K + 16) in the dynamic LDS
+    // ---- behind the first weight burst / cold
+    int nseg, nsum;
+    unsigned max_spins;
+    TiledSeg seg[4];
     unsigned long long* gran;   // K-split exchange granules (stream_finish)
     unsigned* epochs;
     unsigned* err;
-    int nseg, M, K, chunks, chunks_per_split, ksplit, gu_shift, nsum, groups, xstride, waves;
-    int xraw_off;            // ACT kernels: byte offset of the raw x rows (whole K, row stride 2 K + 16) in the dynamic LDS
-    unsigned max_spins;
-    TiledSeg seg[4];
     PeerEpi peer;            // XM = 3 kernels only: read by the owner workgroups behind their K loop
 };
+static_assert(offsetof(TiledParams, perm) == 128, "the entry batch of the decode-copy kernel is the first two cache lines of its arguments");
 
 // Per packing: what a lane of one chunk load holds.  The chunk is always 4 k-slots x 16 columns; a lane (k-slot, column) holds WPL consecutive words =
 // KPL consecutive k of ONE column, re-encoded at load time (gptq_prepack_decode) so that the packed fp16 magic-number extraction yields the k pairs in
@@ -126,71 +138,119 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);                    // scalar: the staging loops below are scalar loops
     const int col = lane & 15, kb = lane >> 4;                                    // lane = kb * 16 + col: lane-linear inside the chunk
-    // every scalar argument in ONE batch of kernarg loads (the empty asm pins them here: left to itself the compiler loads them one dependent step at a time)
-    int ksplit = p.ksplit, be0 = p.blk_end[0], be1 = p.blk_end[1], be2 = p.blk_end[2], nchunks = p.chunks, cps = p.chunks_per_split, K = p.K, Mrows = p.M,
-        G = p.groups, xstride = p.xstride, gshift = p.gu_shift, W = p.waves;
-    const char* xg = (const char*)p.x;
-    asm volatile("" : "+s"(ksplit), "+s"(be0), "+s"(be1), "+s"(be2), "+s"(nchunks), "+s"(cps), "+s"(K), "+s"(Mrows), "+s"(G), "+s"(xstride), "+s"(gshift), "+s"(W), "+s"(xg));
-    // workgroup -> (strip over all layers, K slice); no XCD remap: strips share nothing but x, which every L2 holds
-    int sidx = blockIdx.x, ks = 0;
-    if (ksplit != 1) { sidx = (int)blockIdx.x / ksplit; ks = (int)blockIdx.x - sidx * ksplit; }      // uniform branch: the division only where slices exist
-    const int s = (sidx >= be0) + (sidx >= be1) + (sidx >= be2);                  // scalar compares on entry-loaded words
-    const TiledSeg sg = p.seg[s];                                                 // one dependent kernarg load
-    const int strip = sidx - (s == 0 ? 0 : (s == 1 ? be0 : (s == 2 ? be1 : be2)));
-    // what the tail needs of the layer stays in SGPRs from here on (pinned like the entry batch: left to itself the compiler fetches these words from the
-    // kernel-argument segment again BEHIND the K loop -- a dependent scalar-load round trip in front of the store)
-    int N = sg.N;
-    const void* biasp = sg.bias;
-    void* outp = sg.out;
-    asm volatile("" : "+s"(N), "+s"(biasp), "+s"(outp));
-    typedef __attribute__((address_space(1))) T gT;                               // (behind the asm the compiler no longer knows that these are global pointers)
-    const gT* const biasg = (const gT*)biasp;
-    gT* const outg = (gT*)outp;
+    // Everything the head needs: the first 128 bytes of the kernel arguments, in ONE batch of two scalar loads and ONE wait -- issued by hand, so that the words
+    // are used where the loads put them.  (Left to itself the compiler loads kernel arguments one dependent step at a time; pinned by an empty asm, as here
+    // before, the batch held, and ~25 s_mov copied its words out of the load tuples.)  The words the K loop and the tail need stay in these SGPRs.
+    typedef unsigned u32x16 __attribute__((ext_vector_type(16)));
+    typedef unsigned long long u64x8 __attribute__((ext_vector_type(8)));
+    typedef unsigned long long u64x4 __attribute__((ext_vector_type(4)));
+    static_assert(offsetof(TiledParams, x) == 16 && offsetof(TiledParams, M) == 24 && offsetof(TiledParams, chunks) == 32 && offsetof(TiledParams, pair_strips) == 60 &&
+                  offsetof(TiledParams, tq) == 64 && offsetof(TiledParams, cst) == 96 && offsetof(TiledParams, perm) == 128 && offsetof(TiledParams, xraw_off) == 160, "the entry batch");
+    u32x16 ha;                                                                    // blk_end[4], x, M, K, chunks, chunks_per_split, ksplit, gu_shift, groups, xstride, waves, pair_strips
+    u64x8 hb;                                                                     // tq[4], cst[4]
+    [[maybe_unused]] u64x4 hp = {};                                               // ACT: perm[4]
+    [[maybe_unused]] int xraw_off = 0;
+    {
+        const auto kargs = __builtin_amdgcn_kernarg_segment_ptr();      // (p is the kernel's only parameter: offset 0)
+        if constexpr (ACT)
+            asm volatile("s_load_dwordx16 %0, %4, 0x0\n\ts_load_dwordx16 %1, %4, 0x40\n\ts_load_dwordx8 %2, %4, 0x80\n\ts_load_dword %3, %4, 0xa0\n\ts_waitcnt lgkmcnt(0)"
+                         : "=&s"(ha), "=&s"(hb), "=&s"(hp), "=&s"(xraw_off) : "s"(kargs));
+        else
+            asm volatile("s_load_dwordx16 %0, %2, 0x0\n\ts_load_dwordx16 %1, %2, 0x40\n\ts_waitcnt lgkmcnt(0)" : "=&s"(ha), "=&s"(hb) : "s"(kargs));
+    }
+    const int be0 = (int)ha[0], be1 = (int)ha[1], be2 = (int)ha[2], Mrows = (int)ha[6], K = (int)ha[7], nchunks = (int)ha[8], cps = (int)ha[9], ksplit = (int)ha[10],
+              gshift = (int)ha[11], G = (int)ha[12], xstride = (int)ha[13], W = (int)ha[14];
+    [[maybe_unused]] const int hstrips = (int)ha[15];                             // PAIR: strips of one half
+    typedef __attribute__((address_space(1))) const char gchar;                   // (behind the asm the compiler no longer knows that these are global pointers)
+    gchar* const xg = (gchar*)(((unsigned long long)ha[5] << 32) | ha[4]);
+    // workgroup -> (strip over all layers, K slice); no XCD remap: strips share nothing but x, which every L2 holds.  A launch without K slices (every launch of
+    // the Llama decode step) pays one compare: the division and the slice's chunk / k range are a cold block
+    int sidx = blockIdx.x, ks = 0, cb = 0, ce = nchunks, kbeg = 0, kend = K;      // (no slices: chunks_per_split = chunks)
+    if (__builtin_expect(ksplit != 1, 0)) {
+        sidx = (int)blockIdx.x / ksplit; ks = (int)blockIdx.x - sidx * ksplit;
+        cb = ks * cps; ce = min(cb + cps, nchunks);                               // this slice's chunks
+        kbeg = cb * CKE; kend = min(ce * CKE, K);                                 // ... and its k range: what is staged of x
+    }
+    // the layer: scalar compares on entry-loaded words, everything of it the head needs chosen by s_cselect (blk_end is cumulative, unused entries INT_MAX: the
+    // compares are nested, and a workgroup of the first layer -- every workgroup of a one-layer launch -- leaves behind the first).  In asm on purpose: written
+    // as C++ selects, the compiler keeps each compare as a lane mask with several users and selects on the VECTOR unit (v_cndmask_b32 + v_readfirstlane_b32
+    // -- or fails with "illegal VGPR to SGPR copy" where the result feeds an "s" operand).
+    unsigned long long tqs_ = hb[0], csts_ = hb[4];
+    [[maybe_unused]] unsigned long long perm_ = hp[0];
+    int sbase = 0, s = 0;
+    if constexpr (ACT)
+        asm("s_cmp_ge_i32 %[i], %[e0]\n\ts_cbranch_scc0 1f\n\t"
+            "s_mov_b64 %[tq], %[tq1]\n\ts_mov_b64 %[cs], %[cs1]\n\ts_mov_b64 %[pm], %[pm1]\n\ts_mov_b32 %[sb], %[e0]\n\ts_mov_b32 %[s], 1\n\t"
+            "s_cmp_ge_i32 %[i], %[e1]\n\ts_cselect_b64 %[tq], %[tq2], %[tq]\n\ts_cselect_b64 %[cs], %[cs2], %[cs]\n\ts_cselect_b64 %[pm], %[pm2], %[pm]\n\ts_cselect_b32 %[sb], %[e1], %[sb]\n\ts_cselect_b32 %[s], 2, %[s]\n\t"
+            "s_cmp_ge_i32 %[i], %[e2]\n\ts_cselect_b64 %[tq], %[tq3], %[tq]\n\ts_cselect_b64 %[cs], %[cs3], %[cs]\n\ts_cselect_b64 %[pm], %[pm3], %[pm]\n\ts_cselect_b32 %[sb], %[e2], %[sb]\n\ts_cselect_b32 %[s], 3, %[s]\n"
+            "1:"
+            : [tq] "+&s"(tqs_), [cs] "+&s"(csts_), [pm] "+&s"(perm_), [sb] "+&s"(sbase), [s] "+&s"(s)
+            : [i] "s"(sidx), [e0] "s"(be0), [e1] "s"(be1), [e2] "s"(be2), [tq1] "s"(hb[1]), [tq2] "s"(hb[2]), [tq3] "s"(hb[3]), [cs1] "s"(hb[5]), [cs2] "s"(hb[6]), [cs3] "s"(hb[7]),
+              [pm1] "s"(hp[1]), [pm2] "s"(hp[2]), [pm3] "s"(hp[3])
+            : "scc");
+    else
+        asm("s_cmp_ge_i32 %[i], %[e0]\n\ts_cbranch_scc0 1f\n\t"
+            "s_mov_b64 %[tq], %[tq1]\n\ts_mov_b64 %[cs], %[cs1]\n\ts_mov_b32 %[sb], %[e0]\n\ts_mov_b32 %[s], 1\n\t"
+            "s_cmp_ge_i32 %[i], %[e1]\n\ts_cselect_b64 %[tq], %[tq2], %[tq]\n\ts_cselect_b64 %[cs], %[cs2], %[cs]\n\ts_cselect_b32 %[sb], %[e1], %[sb]\n\ts_cselect_b32 %[s], 2, %[s]\n\t"
+            "s_cmp_ge_i32 %[i], %[e2]\n\ts_cselect_b64 %[tq], %[tq3], %[tq]\n\ts_cselect_b64 %[cs], %[cs3], %[cs]\n\ts_cselect_b32 %[sb], %[e2], %[sb]\n\ts_cselect_b32 %[s], 3, %[s]\n"
+            "1:"
+            : [tq] "+&s"(tqs_), [cs] "+&s"(csts_), [sb] "+&s"(sbase), [s] "+&s"(s)
+            : [i] "s"(sidx), [e0] "s"(be0), [e1] "s"(be1), [e2] "s"(be2), [tq1] "s"(hb[1]), [tq2] "s"(hb[2]), [tq3] "s"(hb[3]), [cs1] "s"(hb[5]), [cs2] "s"(hb[6]), [cs3] "s"(hb[7])
+            : "scc");
+    gchar* const tqs = (gchar*)tqs_;
+    gchar* const csts = (gchar*)csts_;
+    [[maybe_unused]] const int* const permp = (const int*)perm_;                  // ACT: the layer's perm, its words requested in front of the weight loads
+    const int strip = sidx - sbase;
     const int Wh = NSTR == 4 ? (W >> 2) : (NSTR == 2 ? (W >> 1) : W);             // waves per strip
-    const int sel = NSTR == 1 ? 0 : ((wave >= Wh ? 1 : 0) + (NSTR == 4 ? (wave >= 2 * Wh ? 1 : 0) + (wave >= 3 * Wh ? 1 : 0) : 0));      // which of the workgroup's strips (wave-uniform); PAIR: 0 = gate, 1 = up
+    const int sel = NSTR == 1 ? 0 : (scalar_ge(wave, Wh) + (NSTR == 4 ? scalar_ge(wave, 2 * Wh) + scalar_ge(wave, 3 * Wh) : 0));      // which of the workgroup's strips (wave-uniform); PAIR: 0 = gate, 1 = up
     const int wv = NSTR == 1 ? wave : wave - sel * Wh;
-    const int strip_w = PAIR ? strip + sel * (N >> 5) : (MULTI ? strip * NSTR + sel : strip);      // the strip this WAVE streams
-    const int cb = ks * cps, ce = min(cb + cps, nchunks);                         // this slice's chunks
-    const int kbeg = cb * CKE, kend = min(ce * CKE, K);                           // ... and its k range: what is staged of x
+    const int strip_w = PAIR ? strip + sel * hstrips : (MULTI ? strip * NSTR + sel : strip);      // the strip this WAVE streams
     // LDS: [x: MT rows of (kend - kbeg) values, row stride + 16 B][constants: G x REC bytes][cross-wave sums]
     char* const xs = smem;                                                        // row stride xstride = chunks_per_split * CKE * 2 + 16 bytes: the 4 rows of a 4-lane group hit different banks
     char* const cs = smem + (size_t)MT * xstride;
-    const size_t cpad = ((size_t)G * REC + 15) & ~(size_t)15;
+    const unsigned crec = (unsigned)G * (unsigned)REC;                            // bytes of one strip's constants
+    const size_t cpad = ((size_t)crec + 15) & ~(size_t)15;
     float* const red = (float*)(cs + NSTR * cpad);
-    const char* const cg = (const char*)sg.cst + (size_t)(MULTI ? strip * NSTR : strip) * G * REC;      // this strip's (MULTI: these strips') constants: one contiguous run
-    const char* const tb = (const char*)sg.tq + (size_t)strip_w * nchunks * CHB;  // this wave's strip of weights: one contiguous run
+    gchar* const tb = tqs + (size_t)(unsigned)strip_w * ((unsigned)nchunks * (unsigned)CHB);      // this wave's strip of weights: one contiguous run
+    gchar* const cg = csts + (size_t)(unsigned)(MULTI ? strip * NSTR : strip) * crec;             // this strip's (MULTI: these strips') constants: one contiguous run
     const unsigned t_lane = (unsigned)lane * (WPL * 4u);
-    // ---- stage x and the constants by LDS DMA: no VGPRs, issued FIRST (loads return in issue order), waited for behind the first weight burst
-    {
+    // ---- stage x and the constants by LDS DMA: no VGPRs, issued FIRST (loads return in issue order), waited for behind the first weight burst.  Every DMA of a
+    // thread takes a scalar base and a 32-bit lane offset; a wave without a piece skips a block on one scalar compare (stage_rows)
+    auto stage_all = [&]() __attribute__((always_inline)) {
         const unsigned xs_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)xs, cs_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)cs;
-        const int pieces = (kend - kbeg) >> 3;                                    // 16-byte pieces per x row
+        const int w64 = wave * 64, step = W * 64;
+        gchar* xrow[MT];
+        unsigned xdst[MT];
         if constexpr (XM == 0 || XM == 3 || XM == 4 || MULTI) {
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
-                const char* xr = xg + ((size_t)min(m, Mrows - 1) * K + kbeg) * 2;
-                for (int pc0 = wave * 64; pc0 < pieces; pc0 += W * 64)            // wave-uniform trip count
-                    if (pc0 + lane < pieces) lds_dma16(xr + (size_t)(pc0 + lane) * 16, xs_lds + m * xstride + pc0 * 16);      // default cache policy: every workgroup reads x
+                xrow[m] = xg + (unsigned)((m == 0 ? 0 : min(m, Mrows - 1)) * K + kbeg) * 2u;
+                xdst[m] = xs_lds + m * xstride;
             }
+            stage_rows<MT, false>(xrow, xdst, tid, w64, step, (kend - kbeg) >> 3);      // default cache policy: every workgroup reads x
         } else if constexpr (ACT) {
             // act-order: the RAW rows, whole K (a slice's positions map to any original k), by the same DMA; the gather through perm is LDS -> LDS
-            const int rpieces = K >> 3;
-            const unsigned xr_lds = xs_lds + (unsigned)p.xraw_off;
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
-                const char* xr = xg + (size_t)min(m, Mrows - 1) * K * 2;
-                for (int pc0 = wave * 64; pc0 < rpieces; pc0 += W * 64)
-                    if (pc0 + lane < rpieces) lds_dma16(xr + (size_t)(pc0 + lane) * 16, xr_lds + m * (K * 2 + 16) + pc0 * 16);
+                xrow[m] = xg + (unsigned)((m == 0 ? 0 : min(m, Mrows - 1)) * K) * 2u;
+                xdst[m] = xs_lds + (unsigned)xraw_off + m * (K * 2 + 16);
             }
+            stage_rows<MT, false>(xrow, xdst, tid, w64, step, K >> 3);
         }
-        const int cpieces = ((G * REC) >> 4) * (MULTI ? NSTR : 1);                // REC is a multiple of 16 (MULTI: adjacent strips' records are adjacent, cpad = G * REC)
-        for (int pc0 = wave * 64; pc0 < cpieces; pc0 += W * 64)
-            if (pc0 + lane < cpieces) dma16_nt(cg + (size_t)(pc0 + lane) * 16, __builtin_amdgcn_readfirstlane(cs_lds + pc0 * 16));
+        const int cpieces = (int)(crec >> 4) * (MULTI ? NSTR : 1);                // REC is a multiple of 16 (MULTI: adjacent strips' records are adjacent, cpad = G * REC)
         if constexpr (PAIR) {                                                     // the up strip's constants behind the gate strip's
-            const char* const cg2 = cg + (size_t)(N >> 5) * G * REC;
-            for (int pc0 = wave * 64; pc0 < cpieces; pc0 += W * 64)
-                if (pc0 + lane < cpieces) dma16_nt(cg2 + (size_t)(pc0 + lane) * 16, __builtin_amdgcn_readfirstlane(cs_lds + (unsigned)cpad + pc0 * 16));
+            gchar* const crow[2] = {cg, cg + (size_t)(unsigned)hstrips * crec};
+            const unsigned cdst[2] = {cs_lds, cs_lds + (unsigned)cpad};
+            stage_rows<2, true>(crow, cdst, tid, w64, step, cpieces);
+        } else {
+            gchar* const crow[1] = {cg};
+            const unsigned cdst[1] = {cs_lds};
+            stage_rows<1, true>(crow, cdst, tid, w64, step, cpieces);
         }
-    }
+    };
+#ifndef GPTQ_TILED_WEIGHTS_FIRST
+    stage_all();
+#endif
     // ACT: one thread = one 16-byte piece of the staged rows: 8 consecutive positions -> 32 contiguous bytes of perm (global, requested HERE, in front of the
     // weight loads), then 8 two-byte LDS reads per row from the raw x the DMA above delivers.  (Gathering x from global instead -- 8 scattered 2-byte
     // loads per piece, by every workgroup -- cost 1.2 - 3 us per launch: profiles/r04_tiled_sweep_act_global_gather.log.)
@@ -198,13 +258,13 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
     i32x4 pa[2][2] = {};
     const int apieces = ACT ? (kend - kbeg) >> 3 : 0;
     if constexpr (ACT) {
-        const int* const pg = sg.perm + kbeg;
+        const int* const pg = permp + kbeg;
         if (tid < apieces) { pa[0][0] = *(const i32x4*)(pg + tid * 8); pa[0][1] = *(const i32x4*)(pg + tid * 8 + 4); }
         if (tid + W * 64 < apieces) { pa[1][0] = *(const i32x4*)(pg + (tid + W * 64) * 8); pa[1][1] = *(const i32x4*)(pg + (tid + W * 64) * 8 + 4); }
     }
     auto x_gather = [&]() {                                                       // behind the barrier that makes the raw rows visible
-        const int* const pg = sg.perm + kbeg;
-        const char* const xraw = smem + p.xraw_off;
+        const int* const pg = permp + kbeg;
+        const char* const xraw = smem + xraw_off;
         for (int pc0 = tid; pc0 < apieces; pc0 += 2 * W * 64) {
             const int pcb = pc0 + W * 64;
             const bool two = pcb < apieces;
@@ -344,15 +404,35 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
     constexpr int E = MT * 16, NE = (MULTI ? NSTR : 1) * E;
     const int n_t = (MULTI ? strip * NSTR + tid / E : strip) * 16 + (tid & 15);
     float bv0 = 0.f, bv1 = 0.f;
+    // what the tail and the bias request need of the layer: ONE scalar load indexed by the layer, issued behind the first weight burst (the empty asm in front of
+    // it: a memory barrier for the compiler that also makes the index opaque, so the load cannot rise above the weight loads), waited for behind the staging
+    // barrier.  From there the words stay in SGPRs (pinned like the entry batch: left to itself the compiler fetches them from the kernel-argument segment
+    // again BEHIND the K loop -- a dependent scalar-load round trip in front of the store)
+    typedef __attribute__((address_space(1))) T gT;
+    int N = 0;
+    const void* biasp = nullptr;
+    void* outp = nullptr;
+    auto seg_request = [&]() __attribute__((always_inline)) {
+        int sl = s;
+        asm volatile("" : "+s"(sl) : : "memory");
+        N = p.seg[sl].N; biasp = p.seg[sl].bias; outp = p.seg[sl].out;
+    };
+    auto seg_pin = [&]() __attribute__((always_inline)) { asm volatile("" : "+s"(N), "+s"(biasp), "+s"(outp)); };
     bool staged = false;
     for (int cbase = cb; cbase < ce; cbase += Wh * U) {
         const int c0 = cbase + wv * U;
         qvec q[U];
 #pragma unroll
-        for (int j = 0; j < U; ++j) q[j] = __builtin_nontemporal_load((const qvec*)(tb + ((unsigned)min(c0 + j, ce - 1) * (unsigned)CHB + t_lane)));
+        for (int j = 0; j < U; ++j) q[j] = __builtin_nontemporal_load((const __attribute__((address_space(1))) qvec*)(tb + ((unsigned)min(c0 + j, ce - 1) * (unsigned)CHB + t_lane)));
         if (!staged) {                                                            // first pass only (uniform): the staging DMAs are OLDER than the U loads just issued
             TILED_STAMP(1);
+            seg_request();
+#ifdef GPTQ_TILED_WEIGHTS_FIRST                                                    // lab: the DMAs BEHIND the first weight burst -- the staging barrier then waits for the first chunks too
+            stage_all();
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#else
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(U) : "memory");
+#endif
             if constexpr (ACT) {
                 __syncthreads();                                                  // the raw rows (every wave's DMAs) are in the LDS
                 x_gather();
@@ -360,9 +440,10 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
             __syncthreads();
             if constexpr (XC) x_to_f16();
             if constexpr (XS) x_sums();
+            seg_pin();
             if (biasp != nullptr && tid < NE && n_t < (PAIR ? N >> 1 : N)) {
-                bv0 = DType<T>::to_f32(biasg[n_t]);
-                if constexpr (PAIR) bv1 = DType<T>::to_f32(biasg[n_t + (N >> 1)]);
+                bv0 = DType<T>::to_f32(((const gT*)biasp)[n_t]);
+                if constexpr (PAIR) bv1 = DType<T>::to_f32(((const gT*)biasp)[n_t + (N >> 1)]);
             }
             TILED_STAMP(2);
             staged = true;
@@ -497,7 +578,12 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
     // ---- k-slots (two register swaps: a lane owns one column), waves (LDS), then write / publish ---------------------------------------------
 #pragma unroll
     for (int m = 0; m < MT; ++m) acc[m] = kslot_sum_swap(acc[m]);
-    if (!staged) __syncthreads();                                                 // (an empty slice never took the staging barrier; the planner makes none)
+    if (__builtin_expect(!staged, 0)) {                                           // (an empty slice never took the staging barrier; the planner makes none)
+        seg_request();
+        seg_pin();
+        __syncthreads();
+    }
+    gT* const outg = (gT*)outp;
     if (lane < 16) {
 #pragma unroll
         for (int m = 0; m < MT; ++m) red[wave * ES + m * 16 + lane] = acc[m];
@@ -556,8 +642,8 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
             float t = 0.f;
             for (int w = 0; w < Wh; ++w) t += red[(s4 * Wh + w) * ES + r];
             if (m < Mrows && n < N) {
-                if (sg.bias) t += DType<T>::to_f32(((const T*)sg.bias)[n]);
-                ((T*)sg.out)[(size_t)m * N + n] = DType<T>::from_f32(t);
+                if (biasp) t += DType<T>::to_f32(((const T*)biasp)[n]);
+                ((T*)outp)[(size_t)m * N + n] = DType<T>::from_f32(t);
             }
         }
         return;
@@ -586,6 +672,7 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
         }
     }
     T* const stage = PEER ? (T*)xs : nullptr;                                      // the staged x is dead behind the barrier above
+    const TiledSeg sg{biasp, outp, N, ksplit != 1 ? p.seg[s].col0 : 0};              // (col0: K slices only -- a kernel-argument load in the cold block)
     stream_finish<16, MT, T, TiledParams, TiledSeg>(p, sg, strip, sidx, ks, N, red, stage);
     if constexpr (PEER) if (ks == 0) {                                            // uniform: the strip's owner
         const int pworld = p.peer.world;

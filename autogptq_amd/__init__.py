@@ -4,7 +4,7 @@ Only what the path needs: the HIP kernels + C ABI (``csrc/`` -> ``libgptq_mi355x
 loader (``_lib``), the ``QuantLinear`` backend class (``qlinear_mi355x``), the backend selector
 mirror (``import_utils``), the callers either side of the path (``model_utils``, ``fused``), the
 checkpoint formats that feed it (``awq``, ``marlin``), the tensor-parallel wrappers (``tensor_parallel``) and LoRA adapters on the
-quantized layers (``lora``).
+quantized layers (``lora``; ``adapter_bank``: banks of adapters selected per row).
 """
 from .import_utils import MI355X_KERNELS_AVAILABLE, dynamically_import_QuantLinear  # noqa: F401
 from .qlinear_mi355x import QuantLinear, reserve_workspace  # noqa: F401
@@ -12,5 +12,7 @@ from .fused import fuse_gate_up, fuse_qkv, fuse_quant_linears  # noqa: F401
 from .model_utils import autogptq_post_init, load_packed_layers, make_quant, pack_model  # noqa: F401
 from .lora import (LoraQuantLinear, inject_lora, load_lora_adapter, lora_forward_multi, lora_state_dict,  # noqa: F401
                    mark_only_lora_trainable, refresh_lora)
+from .adapter_bank import (AdapterRouting, LoraBankQuantLinear, attach_routing, inject_lora_bank, load_adapter_slot,  # noqa: F401
+                           lora_bank_forward_multi)
 
 __version__ = "0.1.0"

@@ -38,6 +38,7 @@ EXPORTS = (
     "gptq_moe_batch_workspace_bytes", "gptq_moe_batch_forward", "gptq_describe_moe_batch_plan",
     "gptq_moe_grad_table_bytes", "gptq_moe_build_grad_table", "gptq_moe_backward_workspace_bytes", "gptq_moe_backward", "gptq_describe_moe_backward_plan",
     "gptq_lora_down", "gptq_lora_up", "gptq_lora_apply", "gptq_describe_lora_plan",
+    "gptq_adapter_route_bytes", "gptq_adapter_route", "gptq_adapter_rows_apply", "gptq_describe_adapter_rows_plan",
 )
 WS_HEADER_BYTES = 65536
 STRIP_COLS = 16          # GPTQ_STRIP_COLS: columns per strip of the decode copy (gptq_prepack_decode)
@@ -71,6 +72,15 @@ class GptqLora(Structure):
     """gptq_lora_t: one adapter -- lora_A.weight [r, K] and lora_B.weight [N, r] in the layer dtype, scale = lora_alpha / r."""
     _fields_ = [("A", c_void_p), ("B", c_void_p), ("K", c_int32), ("N", c_int32), ("r", c_int32), ("dtype", c_int32),
                 ("scale", ctypes.c_float), ("reserved", c_int32)]
+
+
+ADAPTER_MAX_SLOTS = 256  # slots of one adapter bank (the routing kernel's tables)
+
+
+class GptqAdapterBank(Structure):
+    """gptq_adapter_bank_t: `slots` adapters of one layer -- A [slots, r, K], B [slots, N, r] in the layer dtype, scales [slots] fp32 (device memory)."""
+    _fields_ = [("A", c_void_p), ("B", c_void_p), ("scales", c_void_p), ("K", c_int32), ("N", c_int32), ("r", c_int32), ("slots", c_int32),
+                ("dtype", c_int32), ("reserved", c_int32)]
 
 
 PEER_MAX = 8
@@ -200,6 +210,12 @@ def load() -> ctypes.CDLL:
     lib.gptq_lora_up.argtypes = [RP, c_int, POINTER(c_void_p), POINTER(c_void_p), c_int, c_void_p]
     lib.gptq_lora_apply.argtypes = [RP, c_int, c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_int, c_void_p]
     lib.gptq_describe_lora_plan.argtypes = [RP, c_int, c_int, c_char_p, c_size_t]
+    BP = POINTER(POINTER(GptqAdapterBank))
+    lib.gptq_adapter_route_bytes.restype = c_size_t
+    lib.gptq_adapter_route_bytes.argtypes = [c_int, c_int]
+    lib.gptq_adapter_route.argtypes = [c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]
+    lib.gptq_adapter_rows_apply.argtypes = [BP, c_int, c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_int, c_void_p]
+    lib.gptq_describe_adapter_rows_plan.argtypes = [BP, c_int, c_int, c_char_p, c_size_t]
     lib.gptq_peer_scatter.argtypes = [POINTER(GptqPeerGroup), c_void_p, c_int, c_int, c_int, c_void_p]
     lib.gptq_peer_collect.argtypes = [POINTER(GptqPeerGroup), c_void_p, c_int, c_int, ctypes.c_uint32, c_void_p]
     lib.gptq_peer_gather.argtypes = [POINTER(GptqPeerGroup), c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_uint32, c_void_p]
@@ -353,6 +369,21 @@ def describe_lora_plan(loras, M: int) -> dict:
     arr = (POINTER(GptqLora) * max(1, n))(*[ctypes.pointer(l) for l in loras])
     buf = ctypes.create_string_buffer(512)
     check(lib.gptq_describe_lora_plan(arr, n, M, buf, len(buf)))
+    out = {}
+    for kv in buf.value.decode().split():
+        k, v = kv.split("=", 1)
+        out[k] = int(v) if v.lstrip("-").isdigit() else v
+    return out
+
+
+def describe_adapter_rows_plan(banks, M: int) -> dict:
+    """What gptq_adapter_rows_apply would run for these banks (a sequence of GptqAdapterBank) at M rows: path=adapter_rows with its tile bound and grid
+    sizes, or path=none with the reason (host-only query)."""
+    lib = load()
+    n = len(banks)
+    arr = (POINTER(GptqAdapterBank) * max(1, n))(*[ctypes.pointer(b) for b in banks])
+    buf = ctypes.create_string_buffer(512)
+    check(lib.gptq_describe_adapter_rows_plan(arr, n, M, buf, len(buf)))
     out = {}
     for kv in buf.value.decode().split():
         k, v = kv.split("=", 1)

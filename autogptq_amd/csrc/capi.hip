@@ -874,6 +874,86 @@ int gptq_describe_lora_plan(const gptq_lora_t* const* Ls, int n, int M, char* ou
     return GPTQ_OK;
 }
 
+// ---- per-row adapter banks (adapter_rows.hip) ----
+static int adapter_check_slots(int slots) {
+    if (slots < 1 || slots > GPTQ_ADAPTER_MAX_SLOTS)
+        return fail(GPTQ_ERR_UNSUPPORTED, "slots = %d: a bank holds 1..%d adapters (the routing kernel's tables)", slots, GPTQ_ADAPTER_MAX_SLOTS);
+    return GPTQ_OK;
+}
+
+static int adapter_check(const gptq_adapter_bank_t* const* Bs, int n) {
+    if (!Bs) return fail(GPTQ_ERR_NULL, "banks is NULL");
+    if (n < 1 || n > GPTQ_LORA_MAX) return fail(GPTQ_ERR_UNSUPPORTED, "n = %d banks: one call takes 1..%d", n, GPTQ_LORA_MAX);
+    for (int i = 0; i < n; ++i) {
+        const gptq_adapter_bank_t* L = Bs[i];
+        if (!L) return fail(GPTQ_ERR_NULL, "banks[%d] is NULL", i);
+        if (!L->A || !L->B || !L->scales) return fail(GPTQ_ERR_NULL, "banks[%d]: A / B / scales must be non-NULL", i);
+        if (L->dtype == GPTQ_F32) return fail(GPTQ_ERR_UNSUPPORTED, "banks[%d]: fp32 layer: the adapter kernels take fp16 / bf16", i);
+        if (L->dtype != GPTQ_F16 && L->dtype != GPTQ_BF16) return fail(GPTQ_ERR_UNSUPPORTED, "banks[%d]: unknown dtype enum %d", i, L->dtype);
+        if (L->r < 8 || L->r > 64 || L->r % 8) return fail(GPTQ_ERR_UNSUPPORTED, "banks[%d]: r = %d: the adapter kernels take r in 8, 16, .., 64", i, L->r);
+        if (L->K <= 0 || L->K % 32) return fail(GPTQ_ERR_UNSUPPORTED, "banks[%d]: K = %d must be a positive multiple of 32", i, L->K);
+        if (L->N <= 0 || L->N % 16) return fail(GPTQ_ERR_UNSUPPORTED, "banks[%d]: N = %d must be a positive multiple of 16", i, L->N);
+        if (int rc = adapter_check_slots(L->slots)) return rc;
+        if (((uintptr_t)L->A | (uintptr_t)L->B) & 15) return fail(GPTQ_ERR_UNSUPPORTED, "banks[%d]: A / B must be 16-byte aligned", i);
+        if ((uintptr_t)L->scales & 3) return fail(GPTQ_ERR_UNSUPPORTED, "banks[%d]: scales must be 4-byte aligned", i);
+        if (L->K != Bs[0]->K || L->dtype != Bs[0]->dtype || L->slots != Bs[0]->slots)
+            return fail(GPTQ_ERR_UNSUPPORTED, "the banks of one call share K, dtype and slots (bank %d differs)", i);
+    }
+    return GPTQ_OK;
+}
+
+size_t gptq_adapter_route_bytes(int M, int slots) {
+    if (M < 0 || slots < 1 || slots > GPTQ_ADAPTER_MAX_SLOTS) return 0;
+    return plan_adapter_route(M, slots).bytes;
+}
+
+int gptq_adapter_route(const int64_t* ids, int M, int slots, void* route, size_t route_bytes, void* stream) {
+    if (int rc = adapter_check_slots(slots)) return rc;
+    if (M < 0) return fail(GPTQ_ERR_SHAPE, "M must be >= 0, got %d", M);
+    if (M == 0) return GPTQ_OK;
+    if (!ids || !route) return fail(GPTQ_ERR_NULL, "ids / route must be non-NULL");
+    if ((uintptr_t)ids & 7) return fail(GPTQ_ERR_UNSUPPORTED, "ids must be 8-byte aligned");
+    if ((uintptr_t)route & 15) return fail(GPTQ_ERR_UNSUPPORTED, "route must be 16-byte aligned");
+    const size_t need = plan_adapter_route(M, slots).bytes;
+    if (route_bytes < need)
+        return fail(GPTQ_ERR_UNSUPPORTED, "route_bytes = %zu is too small: M = %d rows over %d slots need %zu", route_bytes, M, slots, need);
+    hipError_t e = launch_adapter_route(ids, M, slots, (char*)route, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "gptq_adapter_route launch");
+    return GPTQ_OK;
+}
+
+int gptq_adapter_rows_apply(const gptq_adapter_bank_t* const* Bs, int n, const void* x, void* const* u, void* const* outs, const void* route, int M,
+                            void* stream) {
+    if (int rc = adapter_check(Bs, n)) return rc;                // everything is validated before the first launch
+    if (M < 0) return fail(GPTQ_ERR_SHAPE, "M must be >= 0, got %d", M);
+    if (M == 0) return GPTQ_OK;
+    if (!x || !route) return fail(GPTQ_ERR_NULL, "x / route must be non-NULL");
+    if ((uintptr_t)x & 15) return fail(GPTQ_ERR_UNSUPPORTED, "x must be 16-byte aligned");
+    if ((uintptr_t)route & 15) return fail(GPTQ_ERR_UNSUPPORTED, "route must be 16-byte aligned");
+    if (int rc = lora_check_ptrs((const void* const*)u, n, "u")) return rc;
+    if (int rc = lora_check_ptrs((const void* const*)outs, n, "outs")) return rc;
+    hipError_t e = launch_adapter_rows(Bs, n, x, u, outs, route, M, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "gptq_adapter_rows_apply launch");
+    return GPTQ_OK;
+}
+
+int gptq_describe_adapter_rows_plan(const gptq_adapter_bank_t* const* Bs, int n, int M, char* out, size_t out_bytes) {
+    if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out is NULL");
+    int rc = adapter_check(Bs, n);
+    if (!rc && M < 0) rc = fail(GPTQ_ERR_SHAPE, "M must be >= 0, got %d", M);
+    if (rc) {
+        char reason[sizeof(g_err)];
+        snprintf(reason, sizeof(reason), "%s", g_err);
+        for (char* c = reason; *c; ++c)
+            if (*c == ' ' || *c == '=') *c = '_';
+        snprintf(out, out_bytes, "path=none reason=%s", reason);
+        return GPTQ_OK;
+    }
+    const AdapterRowsPlan pl = plan_adapter_rows(Bs, n, M);
+    snprintf(out, out_bytes, "path=adapter_rows tiles=%ld wg_down=%ld wg_up=%ld launches=2", pl.tiles, pl.wg_down, pl.wg_up);
+    return GPTQ_OK;
+}
+
 // ---- routed mixture-of-experts layers (moe.hip) ----
 static int moe_check_proj(const gptq_layer_t* const* Ls, int E, int K, int N, int dtype, const char* name) {
     if (!Ls) return fail(GPTQ_ERR_NULL, "moe->%s is NULL", name);

@@ -239,6 +239,21 @@ struct LoraPlan {
 LoraPlan plan_lora(const gptq_lora_t* const* Ls, int n, int M);
 hipError_t launch_lora_down(const gptq_lora_t* const* Ls, int n, const void* x, void* const* u, int M, hipStream_t st);
 hipError_t launch_lora_up(const gptq_lora_t* const* Ls, int n, const void* const* u, void* const* outs, int M, hipStream_t st);
+// adapter_rows.hip: per-row adapter banks (gptq_adapter_route, gptq_adapter_rows_apply): moe_route_kernel with 16-row tiles, one down launch, one up launch
+constexpr int GPTQ_ADAPTER_TILE_ROWS = 16;
+constexpr int GPTQ_ADAPTER_MAX_SLOTS = 256;         // the routing kernel's LDS arrays
+struct AdapterRoutePlan {
+    long tiles;                                     // tile bound: M / 16 + min(slots, M)
+    size_t off_offsets, off_tile_count, off_tiles, off_pos, off_rows, bytes;   // layout of the route buffer
+};
+struct AdapterRowsPlan {
+    long tiles, units_down, units_up, wg_down, wg_up;
+};
+AdapterRoutePlan plan_adapter_route(int M, int slots);
+AdapterRowsPlan plan_adapter_rows(const gptq_adapter_bank_t* const* Bs, int n, int M);
+hipError_t launch_adapter_route(const int64_t* ids, int M, int slots, char* route, hipStream_t st);
+hipError_t launch_adapter_rows(const gptq_adapter_bank_t* const* Bs, int n, const void* x, void* const* u, void* const* outs, const void* route, int M,
+                               hipStream_t st);
 hipError_t launch_unpack_weights(const uint32_t* qweight, int K, int N, int bits, uint8_t* w_out, hipStream_t st);
 hipError_t launch_unpack_zeros(const uint32_t* qzeros, int G, int N, int bits, int zero_mode, int32_t* z_out, hipStream_t st);
 hipError_t launch_pack_weights(const void* W, const void* scale_in, const void* zero_in, const int32_t* g_idx,

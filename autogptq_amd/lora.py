@@ -301,6 +301,18 @@ def lora_state_dict(model: nn.Module) -> dict:
     return sd
 
 
+def parse_adapter_key(key: str, who: str = "parse_adapter_key"):
+    """(module name, "lora_A" | "lora_B") of one key of a peft adapter state dict: ``base_model.model.<name>.lora_A.weight``, the prefix optional and the
+    ``.default`` infix of peft's in-memory form accepted.  Any other key raises KeyError."""
+    k = key[len("base_model.model."):] if key.startswith("base_model.model.") else key
+    k = k.replace(".lora_A.default.", ".lora_A.").replace(".lora_B.default.", ".lora_B.")
+    for which in ("lora_A", "lora_B"):
+        suffix = f".{which}.weight"
+        if k.endswith(suffix):
+            return k[:-len(suffix)], which
+    raise KeyError(f"{who}: unexpected key {key}")
+
+
 def load_lora_adapter(model: nn.Module, state_dict: dict, config: dict) -> dict:
     """Inject the adapters ``config`` describes (``r``, ``lora_alpha``, ``target_modules``, ``lora_dropout``: peft's adapter_config.json as a dict) where
     the model does not carry them yet and load ``state_dict`` (peft's keys; the ``.default`` infix is accepted).  Returns {name: LoraQuantLinear}."""
@@ -310,23 +322,15 @@ def load_lora_adapter(model: nn.Module, state_dict: dict, config: dict) -> dict:
         layers = lora_layers(model)
     seen = set()
     for key, value in state_dict.items():
-        k = key[len("base_model.model."):] if key.startswith("base_model.model.") else key
-        k = k.replace(".lora_A.default.", ".lora_A.").replace(".lora_B.default.", ".lora_B.")
-        for which in ("lora_A", "lora_B"):
-            suffix = f".{which}.weight"
-            if k.endswith(suffix):
-                name = k[:-len(suffix)]
-                if name not in layers:
-                    raise KeyError(f"load_lora_adapter: {key} names no adapted layer of the model")
-                p = getattr(layers[name], which).weight
-                if tuple(p.shape) != tuple(value.shape):
-                    raise ValueError(f"load_lora_adapter: {key} is {tuple(value.shape)}, the layer expects {tuple(p.shape)}")
-                with torch.no_grad():
-                    p.copy_(value)
-                seen.add((name, which))
-                break
-        else:
-            raise KeyError(f"load_lora_adapter: unexpected key {key}")
+        name, which = parse_adapter_key(key, "load_lora_adapter")
+        if name not in layers:
+            raise KeyError(f"load_lora_adapter: {key} names no adapted layer of the model")
+        p = getattr(layers[name], which).weight
+        if tuple(p.shape) != tuple(value.shape):
+            raise ValueError(f"load_lora_adapter: {key} is {tuple(value.shape)}, the layer expects {tuple(p.shape)}")
+        with torch.no_grad():
+            p.copy_(value)
+        seen.add((name, which))
     missing = [f"{n}.{w}" for n in layers for w in ("lora_A", "lora_B") if (n, w) not in seen]
     if missing:
         raise KeyError(f"load_lora_adapter: the state dict lacks {missing[:4]}{' ...' if len(missing) > 4 else ''}")
@@ -347,5 +351,5 @@ def refresh_lora(model: nn.Module) -> None:
             m.refresh_adapter()
 
 
-__all__ = ["LoraQuantLinear", "lora_forward_multi", "inject_lora", "lora_state_dict", "load_lora_adapter", "mark_only_lora_trainable", "refresh_lora",
+__all__ = ["LoraQuantLinear", "parse_adapter_key", "lora_forward_multi", "inject_lora", "lora_state_dict", "load_lora_adapter", "mark_only_lora_trainable", "refresh_lora",
            "lora_layers"]

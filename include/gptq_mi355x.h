@@ -285,6 +285,38 @@ int gptq_lora_apply(const gptq_lora_t *const *loras, int n, const void *x, void 
  * "path=none reason=...".  GPTQ_OK either way (GPTQ_ERR_NULL for a NULL out). */
 int gptq_describe_lora_plan(const gptq_lora_t *const *loras, int n, int M, char *out, size_t out_bytes);
 
+/* Per-row adapter banks: a batch whose rows belong to different fine-tunes of one GPTQ base.  Row m carries a slot ids[m] (int64, device memory); a bank
+ * holds `slots` adapters of ONE layer: A [slots][r][K] and B [slots][N][r] in the layer dtype T (fp16 / bf16), scales [slots] fp32, all device memory.
+ *   row m with a = ids[m] in [0, slots):
+ *     u_m[j]    = T(sum_k x[m, k] * A[a][j, k])                                              fp32 products and sums, one rounding
+ *     out[m, n] = T(float(out[m, n]) + scales[a] * sum_j float(u_m[j]) * float(B[a][n, j]))   in place on the base layer's output, one rounding
+ *   any other id (-1 is the documented "no adapter") leaves out[m] untouched, bit for bit.
+ * The bits of row m depend on x[m], its slot and the bank alone: not on the other rows, their ids, or where row m sits in the batch.  No atomics, no
+ * workgroup waits on another, fixed summation order.  ids is read on the device only: all three launches (routing, down, up) are legal inside hipGraph
+ * capture and a replay follows the ids then in memory.
+ *   routing: rows sorted by slot into tiles of up to 16 rows of one slot, written to `route` (a caller buffer of the size the _bytes query names for
+ *            (M, slots), 16-byte aligned; the library owns its layout).  One routing serves every layer of a model step -- the ids are the same for all.
+ *   apply:   n = 1..GPTQ_LORA_MAX banks that share x, K, dtype, slots and the routing (q|k|v, gate|up) run as ONE down and ONE up launch; bank i's
+ *            result is bit-identical to a call of its own.  u[i] is a caller tensor [M, r_i] (no workspace): the routed rows' u in SORTED-row order
+ *            (routed rows ordered by slot, the rows of one slot by ascending m), the rest is not written.  The caller passes the M the route was built with, and banks of the slots it was
+ *            built with: the apply call cannot verify either.
+ * M = 0 returns GPTQ_OK, launches nothing and dereferences nothing.  Declined with GPTQ_ERR_UNSUPPORTED and the reason in the last-error string, before
+ * any launch: fp32, r outside {8, 16, .., 64}, K % 32, N % 16, slots outside 1..256, n > GPTQ_LORA_MAX, banks of one call that differ in K, dtype or
+ * slots, any of x, A, B, u[i], outs[i], route not 16-byte aligned, a route_bytes that is too small. */
+typedef struct gptq_adapter_bank_t {
+    const void  *A;         /* [slots, r, K] dtype, row-major, 16-byte aligned */
+    const void  *B;         /* [slots, N, r] dtype, row-major, 16-byte aligned */
+    const float *scales;    /* [slots] fp32: lora_alpha / rank of each slot */
+    int32_t K, N, r, slots, dtype, reserved; /* r % 8 == 0, 8 <= r <= 64; K % 32 == 0; N % 16 == 0; 1 <= slots <= 256; GPTQ_F16 / GPTQ_BF16; 0 */
+} gptq_adapter_bank_t;
+size_t gptq_adapter_route_bytes(int M, int slots);  /* 0 for M < 0 or slots outside 1..256 */
+int gptq_adapter_route(const int64_t *ids, int M, int slots, void *route, size_t route_bytes, void *stream);
+int gptq_adapter_rows_apply(const gptq_adapter_bank_t *const *banks, int n, const void *x, void *const *u, void *const *outs,
+                            const void *route, int M, void *stream);
+/* Host-only: "path=adapter_rows tiles=... wg_down=... wg_up=... launches=2" (tiles: the grid's bound M / 16 + min(slots, M); workgroups past the routed
+ * count return at once) or "path=none reason=...".  GPTQ_OK either way (GPTQ_ERR_NULL for a NULL out). */
+int gptq_describe_adapter_rows_plan(const gptq_adapter_bank_t *const *banks, int n, int M, char *out, size_t out_bytes);
+
 /* Routed mixture-of-experts layer (the experts of a Mixtral block: auto_gptq/modeling/mixtral.py, block_sparse_moe.experts.{e}.w1 / w3 / w2).  E experts,
  * each three plain layers: gate (w1) and up (w3) [H -> I], down (w2) [I -> H].  For token t and its topk assignments (t, j) to experts
  * e = topk_idx[t, j] (int64, the dtype of torch.topk; values outside [0, E) are dropped):

@@ -11,7 +11,7 @@ from .qlinear_mi355x import QuantLinear, reserve_workspace  # noqa: F401
 from .fused import fuse_gate_up, fuse_qkv, fuse_quant_linears  # noqa: F401
 from .model_utils import autogptq_post_init, load_packed_layers, make_quant, pack_model  # noqa: F401
 from .lora import (LoraQuantLinear, inject_lora, load_lora_adapter, lora_forward_multi, lora_state_dict,  # noqa: F401
-                   mark_only_lora_trainable, refresh_lora)
+                   mark_only_lora_trainable, refresh_lora, set_lora_fused_backward)
 from .adapter_bank import (AdapterRouting, LoraBankQuantLinear, attach_routing, inject_lora_bank, load_adapter_slot,  # noqa: F401
                            lora_bank_forward_multi)
 

@@ -38,6 +38,7 @@ EXPORTS = (
     "gptq_moe_batch_workspace_bytes", "gptq_moe_batch_forward", "gptq_describe_moe_batch_plan",
     "gptq_moe_grad_table_bytes", "gptq_moe_build_grad_table", "gptq_moe_backward_workspace_bytes", "gptq_moe_backward", "gptq_describe_moe_backward_plan",
     "gptq_lora_down", "gptq_lora_up", "gptq_lora_apply", "gptq_describe_lora_plan",
+    "gptq_lora_backward_workspace_bytes", "gptq_lora_backward", "gptq_describe_lora_backward_plan",
     "gptq_adapter_route_bytes", "gptq_adapter_route", "gptq_adapter_rows_apply", "gptq_describe_adapter_rows_plan",
 )
 WS_HEADER_BYTES = 65536
@@ -72,6 +73,12 @@ class GptqLora(Structure):
     """gptq_lora_t: one adapter -- lora_A.weight [r, K] and lora_B.weight [N, r] in the layer dtype, scale = lora_alpha / r."""
     _fields_ = [("A", c_void_p), ("B", c_void_p), ("K", c_int32), ("N", c_int32), ("r", c_int32), ("dtype", c_int32),
                 ("scale", ctypes.c_float), ("reserved", c_int32)]
+
+
+class GptqLoraGrad(Structure):
+    """gptq_lora_grad_t: one adapter's operands and outputs of gptq_lora_backward -- At [K, r], Bt [r, N], the forward's u [M, r], dY [M, N] in the layer
+    dtype; du [M, r] written; dA [r, K] / dB [N, r] fp32, NULL to skip."""
+    _fields_ = [("At", c_void_p), ("Bt", c_void_p), ("u", c_void_p), ("dY", c_void_p), ("du", c_void_p), ("dA", c_void_p), ("dB", c_void_p)]
 
 
 ADAPTER_MAX_SLOTS = 256  # slots of one adapter bank (the routing kernel's tables)
@@ -210,6 +217,10 @@ def load() -> ctypes.CDLL:
     lib.gptq_lora_up.argtypes = [RP, c_int, POINTER(c_void_p), POINTER(c_void_p), c_int, c_void_p]
     lib.gptq_lora_apply.argtypes = [RP, c_int, c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_int, c_void_p]
     lib.gptq_describe_lora_plan.argtypes = [RP, c_int, c_int, c_char_p, c_size_t]
+    lib.gptq_lora_backward_workspace_bytes.restype = c_size_t
+    lib.gptq_lora_backward_workspace_bytes.argtypes = [RP, c_int, c_int]
+    lib.gptq_lora_backward.argtypes = [RP, POINTER(POINTER(GptqLoraGrad)), c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]
+    lib.gptq_describe_lora_backward_plan.argtypes = [RP, c_int, c_int, c_char_p, c_size_t]
     BP = POINTER(POINTER(GptqAdapterBank))
     lib.gptq_adapter_route_bytes.restype = c_size_t
     lib.gptq_adapter_route_bytes.argtypes = [c_int, c_int]
@@ -227,7 +238,7 @@ def load() -> ctypes.CDLL:
                         "gptq_workspace_bytes_max", "gptq_workspace_bytes_multi", "gptq_workspace_bytes_multi_ex",
                         "gptq_workspace_bytes_mlp", "gptq_workspace_bytes_mlp_ex", "gptq_moe_table_bytes", "gptq_moe_workspace_bytes",
                         "gptq_moe_decode_table_bytes", "gptq_moe_decode_workspace_bytes", "gptq_moe_batch_workspace_bytes",
-                        "gptq_moe_grad_table_bytes", "gptq_moe_backward_workspace_bytes"):
+                        "gptq_moe_grad_table_bytes", "gptq_moe_backward_workspace_bytes", "gptq_lora_backward_workspace_bytes"):
             getattr(lib, name).restype = c_int
     got = lib.gptq_abi_version()
     if got != ABI_VERSION:
@@ -373,6 +384,25 @@ def describe_lora_plan(loras, M: int) -> dict:
     for kv in buf.value.decode().split():
         k, v = kv.split("=", 1)
         out[k] = int(v) if v.lstrip("-").isdigit() else v
+    return out
+
+
+def describe_lora_backward_plan(loras, M: int) -> dict:
+    """What gptq_lora_backward would run for these adapters (a sequence of GptqLora; A / B are not looked at) at M rows, every output asked for:
+    path=lora_backward with the slice counts S_dA / S_dB (lists, one entry per adapter), the grids, the workspace and the launches, or path=none with the
+    reason (host-only query)."""
+    lib = load()
+    n = len(loras)
+    arr = (POINTER(GptqLora) * max(1, n))(*[ctypes.pointer(l) for l in loras])
+    buf = ctypes.create_string_buffer(512)
+    check(lib.gptq_describe_lora_backward_plan(arr, n, M, buf, len(buf)))
+    out = {}
+    for kv in buf.value.decode().split():
+        k, v = kv.split("=", 1)
+        if k in ("S_dA", "S_dB"):
+            out[k] = [int(t) for t in v.split(",")]
+        else:
+            out[k] = int(v) if v.lstrip("-").isdigit() else v
     return out
 
 

@@ -874,6 +874,115 @@ int gptq_describe_lora_plan(const gptq_lora_t* const* Ls, int n, int M, char* ou
     return GPTQ_OK;
 }
 
+// ---- the adapters' backward (lora.hip's kernels on the transposed copies + adapter_grad.hip) ----
+static int lora_grad_check(const gptq_lora_t* const* Ls, int n) {     // as lora_check, but A / B are not read and N is a summed length
+    if (!Ls) return fail(GPTQ_ERR_NULL, "loras is NULL");
+    if (n < 1 || n > GPTQ_LORA_MAX) return fail(GPTQ_ERR_UNSUPPORTED, "n = %d adapters: one call takes 1..%d", n, GPTQ_LORA_MAX);
+    for (int i = 0; i < n; ++i) {
+        const gptq_lora_t* L = Ls[i];
+        if (!L) return fail(GPTQ_ERR_NULL, "loras[%d] is NULL", i);
+        if (L->dtype == GPTQ_F32) return fail(GPTQ_ERR_UNSUPPORTED, "loras[%d]: fp32 layer: the adapter kernels take fp16 / bf16", i);
+        if (L->dtype != GPTQ_F16 && L->dtype != GPTQ_BF16) return fail(GPTQ_ERR_UNSUPPORTED, "loras[%d]: unknown dtype enum %d", i, L->dtype);
+        if (L->r < 8 || L->r > 64 || L->r % 8) return fail(GPTQ_ERR_UNSUPPORTED, "loras[%d]: r = %d: the adapter kernels take r in 8, 16, .., 64", i, L->r);
+        if (L->K <= 0 || L->K % 32) return fail(GPTQ_ERR_UNSUPPORTED, "loras[%d]: K = %d must be a positive multiple of 32", i, L->K);
+        if (L->N <= 0 || L->N % 32) return fail(GPTQ_ERR_UNSUPPORTED, "loras[%d]: N = %d must be a positive multiple of 32 (the backward sums over N)", i, L->N);
+        if (L->K != Ls[0]->K || L->dtype != Ls[0]->dtype) return fail(GPTQ_ERR_UNSUPPORTED, "the adapters of one call share K and dtype (adapter %d differs)", i);
+    }
+    return GPTQ_OK;
+}
+
+// the reused kernels' view of adapter L: down with A := Bt [r][N], K := N; up with B := At [K][r], N := K
+static gptq_lora_t lora_grad_down_view(const gptq_lora_t& L, const void* Bt) {
+    gptq_lora_t d = L;
+    d.A = d.B = Bt;
+    d.K = L.N;
+    return d;
+}
+static gptq_lora_t lora_grad_up_view(const gptq_lora_t& L, const void* At) {
+    gptq_lora_t d = L;
+    d.A = d.B = At;
+    d.N = L.K;
+    return d;
+}
+
+size_t gptq_lora_backward_workspace_bytes(const gptq_lora_t* const* Ls, int n, int M) {
+    if (lora_grad_check(Ls, n) || M < 0) return 0;
+    return plan_wgrad(Ls, nullptr, n, M).bytes;
+}
+
+int gptq_lora_backward(const gptq_lora_t* const* Ls, const gptq_lora_grad_t* const* Gs, int n, const void* x, void* dX, int M, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    if (int rc = lora_grad_check(Ls, n)) return rc;              // everything is validated before the first launch
+    if (!Gs) return fail(GPTQ_ERR_NULL, "grads is NULL");
+    if (!x) return fail(GPTQ_ERR_NULL, "x must be non-NULL");
+    uintptr_t bits = (uintptr_t)x | (uintptr_t)dX | (uintptr_t)workspace;
+    for (int i = 0; i < n; ++i) {
+        const gptq_lora_grad_t* G = Gs[i];
+        if (!G) return fail(GPTQ_ERR_NULL, "grads[%d] is NULL", i);
+        if (!G->At || !G->Bt || !G->u || !G->dY || !G->du) return fail(GPTQ_ERR_NULL, "grads[%d]: At / Bt / u / dY / du must be non-NULL", i);
+        bits |= (uintptr_t)G->At | (uintptr_t)G->Bt | (uintptr_t)G->u | (uintptr_t)G->dY | (uintptr_t)G->du | (uintptr_t)G->dA | (uintptr_t)G->dB;
+    }
+    if (bits & 15) return fail(GPTQ_ERR_UNSUPPORTED, "x, dX, the workspace and every pointer of grads[] must be 16-byte aligned");
+    if (M < 0) return fail(GPTQ_ERR_SHAPE, "M must be >= 0, got %d", M);
+    if (M == 0) return GPTQ_OK;
+    const WgradPlan pl = plan_wgrad(Ls, Gs, n, M);
+    if (pl.bytes && (!workspace || workspace_bytes < pl.bytes))
+        return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", pl.bytes, workspace ? workspace_bytes : (size_t)0);
+    hipStream_t st = (hipStream_t)stream;
+    for (int i = 0; i < n; ++i) {                                   // 1. du_i: each adapter has its own dY, so a launch each
+        const gptq_lora_t d = lora_grad_down_view(*Ls[i], Gs[i]->Bt);
+        const gptq_lora_t* dp = &d;
+        void* du = Gs[i]->du;
+        hipError_t e = launch_lora_down(&dp, 1, Gs[i]->dY, &du, M, st);
+        if (e != hipSuccess) return hip_fail(e, "gptq_lora_backward du launch");
+    }
+    hipError_t e = launch_wgrad(Ls, Gs, n, x, M, pl, (char*)workspace, st);   // 2. + 3.
+    if (e != hipSuccess) return hip_fail(e, "gptq_lora_backward wgrad launch");
+    if (dX) {
+        for (int i = 0; i < n; ++i) {                               // 4. one shared dX: read-modify-write, so in index order
+            const gptq_lora_t d = lora_grad_up_view(*Ls[i], Gs[i]->At);
+            const gptq_lora_t* dp = &d;
+            const void* du = Gs[i]->du;
+            e = launch_lora_up(&dp, 1, &du, &dX, M, st);
+            if (e != hipSuccess) return hip_fail(e, "gptq_lora_backward dX launch");
+        }
+    }
+    return GPTQ_OK;
+}
+
+int gptq_describe_lora_backward_plan(const gptq_lora_t* const* Ls, int n, int M, char* out, size_t out_bytes) {
+    if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out is NULL");
+    int rc = lora_grad_check(Ls, n);
+    if (!rc && M < 0) rc = fail(GPTQ_ERR_SHAPE, "M must be >= 0, got %d", M);
+    if (rc) {
+        char reason[sizeof(g_err)];
+        snprintf(reason, sizeof(reason), "%s", g_err);
+        for (char* c = reason; *c; ++c)
+            if (*c == ' ' || *c == '=') *c = '_';
+        snprintf(out, out_bytes, "path=none reason=%s", reason);
+        return GPTQ_OK;
+    }
+    const WgradPlan pl = plan_wgrad(Ls, nullptr, n, M);
+    long wg_down = 0, wg_up = 0;
+    char sa[64] = "", sb[64] = "";
+    bool sliced = false;
+    for (int i = 0; i < n; ++i) {
+        const gptq_lora_t d = lora_grad_down_view(*Ls[i], nullptr), u = lora_grad_up_view(*Ls[i], nullptr);
+        const gptq_lora_t *dp = &d, *up = &u;
+        if (M) {
+            wg_down += plan_lora(&dp, 1, M).wg_down;
+            wg_up += plan_lora(&up, 1, M).wg_up;
+        }
+        const int a = wgrad_slices(M, Ls[i]->r, Ls[i]->K).S, b = wgrad_slices(M, Ls[i]->N, Ls[i]->r).S;
+        sliced = sliced || a > 1 || b > 1;
+        snprintf(sa + strlen(sa), sizeof(sa) - strlen(sa), "%s%d", i ? "," : "", a);
+        snprintf(sb + strlen(sb), sizeof(sb) - strlen(sb), "%s%d", i ? "," : "", b);
+    }
+    snprintf(out, out_bytes, "path=lora_backward S_dA=%s S_dB=%s wg_down=%ld wg_wgrad=%ld wg_sum=%ld wg_up=%ld workspace=%zu launches=%d", sa, sb, wg_down,
+             pl.wg_wgrad, pl.wg_sum, wg_up, pl.bytes, M ? 2 * n + 1 + (sliced ? 1 : 0) : 0);
+    return GPTQ_OK;
+}
+
 // ---- per-row adapter banks (adapter_rows.hip) ----
 static int adapter_check_slots(int slots) {
     if (slots < 1 || slots > GPTQ_ADAPTER_MAX_SLOTS)

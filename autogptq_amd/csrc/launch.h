@@ -239,6 +239,23 @@ struct LoraPlan {
 LoraPlan plan_lora(const gptq_lora_t* const* Ls, int n, int M);
 hipError_t launch_lora_down(const gptq_lora_t* const* Ls, int n, const void* x, void* const* u, int M, hipStream_t st);
 hipError_t launch_lora_up(const gptq_lora_t* const* Ls, int n, const void* const* u, void* const* outs, int M, hipStream_t st);
+// adapter_grad.hip: the adapters' weight gradients dA = s du^T x and dB = s dY^T u (gptq_lora_backward): one launch over all jobs, one more to add the
+// M-slices where a job has more than one.  A job is one output [P][Q] with one of P, Q = r; slices are a function of (M, P, Q) alone.
+constexpr int GPTQ_WGRAD_JOBS = 2 * GPTQ_LORA_MAX;
+struct WgradSlices {
+    int S, steps_per_slice;                         // steps are 32 rows
+};
+struct WgradPlan {
+    int jobs;                                       // outputs asked for
+    WgradSlices sl[GPTQ_WGRAD_JOBS];                // [2 i] dA of adapter i, [2 i + 1] its dB (S = 0: not asked for)
+    size_t off[GPTQ_WGRAD_JOBS];                    // workspace offset of the job's partials (S > 1)
+    long wg_wgrad, wg_sum;
+    size_t bytes;                                   // of all adapters' two outputs, asked for or not
+};
+WgradSlices wgrad_slices(int M, int P, int Q);
+WgradPlan plan_wgrad(const gptq_lora_t* const* Ls, const gptq_lora_grad_t* const* Gs, int n, int M);   // Gs NULL: every output
+hipError_t launch_wgrad(const gptq_lora_t* const* Ls, const gptq_lora_grad_t* const* Gs, int n, const void* x, int M, const WgradPlan& pl, char* ws,
+                        hipStream_t st);
 // adapter_rows.hip: per-row adapter banks (gptq_adapter_route, gptq_adapter_rows_apply): moe_route_kernel with 16-row tiles, one down launch, one up launch
 constexpr int GPTQ_ADAPTER_TILE_ROWS = 16;
 constexpr int GPTQ_ADAPTER_MAX_SLOTS = 256;         // the routing kernel's LDS arrays

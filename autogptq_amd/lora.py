@@ -10,7 +10,9 @@ The capability of the reference's ``get_gptq_peft_model`` / ``GPTQLoraLinear`` (
 * parameters carry peft's names and shapes (``lora_A.weight [r, K]``, ``lora_B.weight [N, r]``), so ``lora_state_dict`` / ``load_lora_adapter`` speak
   peft's adapter format (``base_model.model.<name>.lora_A.weight``), dicts in and dicts out;
 * gradients: the base term goes through the existing ``_GradInput`` node (gptq_grad_input), the adapter term through one autograd Function whose
-  backward runs on torch matmuls (r/N-sized corrections beside the base gradient).
+  backward runs on torch matmuls in fp32 -- or, with ``fused_backward=True`` (opt-in), as ONE ``gptq_lora_backward`` (csrc/adapter_grad.hip and the
+  forward's kernels on transposed copies: no activation-sized fp32 temporary).  With the flag on, ``lora_forward_multi`` under
+  grad is one autograd node per group: one fused apply forward, one ``gptq_lora_backward`` with a shared dX backward.
 
 What the kernels decline (fp32 layers, r outside 8, 16, .., 64, odd shapes) falls back to the torch composition with one warning.
 """
@@ -46,7 +48,8 @@ class LoraQuantLinear(nn.Module):
     ``refresh_adapter()`` (or ``refresh_lora(model)``) before the next replay -- no re-capture.  Under grad they are a fresh ``.to(dtype)`` of the
     masters inside the autograd Function, whose backward hands the masters their gradient in their own dtype."""
 
-    def __init__(self, base: QuantLinear, r: int, lora_alpha: float, lora_dropout: float = 0.0, adapter_dtype=torch.float32):
+    def __init__(self, base: QuantLinear, r: int, lora_alpha: float, lora_dropout: float = 0.0, adapter_dtype=torch.float32,
+                 fused_backward: bool = False):
         super().__init__()
         if not isinstance(base, QuantLinear):
             raise TypeError(f"LoraQuantLinear wraps an mi355x QuantLinear, got {type(base).__name__}")
@@ -68,6 +71,8 @@ class LoraQuantLinear(nn.Module):
         self._copies = None           # (A16, B16, version of A, version of B)
         self._struct = None           # (GptqLora, its pointer array, u / out pointer arrays, the tensors it points to)
         self._fused = None            # None: not asked yet; True / False: gptq_lora_apply takes this adapter
+        self.fused_backward = bool(fused_backward)   # opt-in: the adapter's backward as one gptq_lora_backward instead of torch matmuls
+        self._fused_bwd = None        # None: not asked yet; True / False: gptq_lora_backward takes this adapter
 
     # ------------------------------------------------------------------ reference surface
     def merge(self):
@@ -108,7 +113,7 @@ class LoraQuantLinear(nn.Module):
             self._kernel_weights(self._layer_dtype())
 
     def _apply(self, fn, *args, **kwargs):
-        self._copies = self._struct = self._fused = None
+        self._copies = self._struct = self._fused = self._fused_bwd = None
         return super()._apply(fn, *args, **kwargs)
 
     # ------------------------------------------------------------------ the fused call
@@ -136,6 +141,18 @@ class LoraQuantLinear(nn.Module):
             if not self._fused:
                 _warn_once(f"LoraQuantLinear: the adapter kernels decline this layer ({plan.get('reason')}); composing the adapter branch in torch")
         return self._fused
+
+    def fused_backward_ok(self, dtype=None) -> bool:
+        """Whether gptq_lora_backward takes this adapter (host-only query, asked once): as fused_ok, and N % 32 == 0 (N is a summed length there)."""
+        if self._fused_bwd is None:
+            L = _lib.GptqLora()
+            L.K, L.N, L.r = self.in_features, self.out_features, self.r
+            L.dtype = _lib.DTYPE_ENUM.get(dtype or self._layer_dtype(), -1)
+            plan = _lib.describe_lora_backward_plan([L], 1)
+            self._fused_bwd = plan["path"] == "lora_backward"
+            if not self._fused_bwd:
+                _warn_once(f"LoraQuantLinear: gptq_lora_backward declines this layer ({plan.get('reason')}); the adapter's backward runs on torch matmuls")
+        return self._fused_bwd
 
     def _adapter_(self, y: torch.Tensor, xl: torch.Tensor, A16: torch.Tensor, B16: torch.Tensor) -> torch.Tensor:
         """y += scaling * (xl @ A16^T) @ B16^T, in place where the kernels run; returns (y, u)."""
@@ -189,7 +206,9 @@ class _LoraApply(torch.autograd.Function):
     """out = y + scaling * (x_lora @ A^T) @ B^T through gptq_lora_apply (the same launches and values as the no_grad call, on a copy of y).  Takes the
     master weights and casts them to the layer dtype itself; saves x_lora, u and the 16-bit A / B.  Backward, with du = scaling * (dY @ B):
     dA = du^T @ x_lora,  dB = scaling * dY^T @ u,  dX_lora = du @ A,  dY passes through to the base output.  Torch matmuls in fp32 (r/N-sized corrections
-    beside gptq_grad_input); dA / dB are handed to the masters in the masters' dtype, never rounded to 16 bits on the way.  No double backward."""
+    beside gptq_grad_input); dA / dB are handed to the masters in the masters' dtype, never rounded to 16 bits on the way.  No double backward.
+    A layer with ``fused_backward`` that gptq_lora_backward accepts runs the same four products as ONE C call (du unscaled and rounded once to the layer
+    dtype; dA / dB in fp32, so fp32 masters get them with no 16-bit hop) and honours needs_input_grad: a frozen master or an x without grad is not computed."""
 
     @staticmethod
     def forward(ctx, y, xl, a, b, layer):
@@ -202,6 +221,7 @@ class _LoraApply(torch.autograd.Function):
         ctx.save_for_backward(xl, u, A16, B16)
         ctx.scaling = float(layer.scaling)
         ctx.master_dtypes = (a.dtype, b.dtype)
+        ctx.fused = bool(layer.fused_backward) and out.is_cuda and layer.fused_backward_ok(T)
         return out
 
     @staticmethod
@@ -210,6 +230,12 @@ class _LoraApply(torch.autograd.Function):
         xl, u, A16, B16 = ctx.saved_tensors
         need_y, need_x, need_a, need_b = ctx.needs_input_grad[:4]
         N, K = B16.shape[0], A16.shape[1]
+        if ctx.fused and (need_x or need_a or need_b):
+            res = _fused_backward(xl.reshape(-1, K), [(A16, B16, u, dy, ctx.scaling, need_a, need_b)], need_x)
+            if res is not None:
+                dx2, ((da, db),) = res
+                return ((dy if need_y else None), (dx2.reshape(xl.shape) if need_x else None),
+                        (da.to(ctx.master_dtypes[0]) if need_a else None), (db.to(ctx.master_dtypes[1]) if need_b else None), None)
         dy2 = dy.reshape(-1, N).float()
         dx = da = db = None
         if need_x or need_a:
@@ -223,10 +249,140 @@ class _LoraApply(torch.autograd.Function):
         return (dy if need_y else None), dx, da, db, None
 
 
+def _fused_backward(x2: torch.Tensor, items, need_x: bool, dx: torch.Tensor = None):
+    """ONE gptq_lora_backward for up to LORA_MAX adapters that share x2 [M, K] (layer dtype).  items: (A16 [r, K], B16 [N, r], u [M, r], dY [.., N], scale,
+    need_a, need_b) per adapter.  Returns (dX [M, K] or None, [(dA fp32 [r, K] or None, dB fp32 [N, r] or None)]); dx: a dX to go on adding to (the next
+    group of one input).  None when the library declines the call (the caller composes the backward in torch)."""
+    T, dev = x2.dtype, x2.device
+    M, K = x2.shape
+    n = len(items)
+    if need_x and dx is None:
+        dx = torch.zeros((M, K), dtype=T, device=dev)
+    if M == 0:
+        return (dx if need_x else None), [(torch.zeros((a.shape[0], K), dtype=torch.float32, device=dev) if na else None,
+                                           torch.zeros(tuple(b.shape), dtype=torch.float32, device=dev) if nb else None) for a, b, _, _, _, na, nb in items]
+    if not x2.is_contiguous() or x2.data_ptr() % 16:
+        x2 = x2.clone(memory_format=torch.contiguous_format)
+    lib = _lib.load()
+    loras, grads, keep, outs = [], [], [], []
+    for A16, B16, u, dy, scale, need_a, need_b in items:
+        N, r = B16.shape
+        dy2 = dy.reshape(-1, N)
+        if dy2.dtype != T or not dy2.is_contiguous() or dy2.data_ptr() % 16:
+            dy2 = dy2.to(T).clone(memory_format=torch.contiguous_format)
+        if not u.is_contiguous() or u.data_ptr() % 16:
+            u = u.clone(memory_format=torch.contiguous_format)
+        At, Bt = A16.t().contiguous(), B16.t().contiguous()        # r-sized copies: the reused kernels' operands as they want them
+        du = torch.empty((M, r), dtype=T, device=dev)
+        da = torch.empty((r, K), dtype=torch.float32, device=dev) if need_a else None
+        db = torch.empty((N, r), dtype=torch.float32, device=dev) if need_b else None
+        L = _lib.GptqLora()
+        L.K, L.N, L.r, L.dtype, L.scale = K, N, r, _lib.DTYPE_ENUM.get(T, -1), float(scale)
+        G = _lib.GptqLoraGrad()
+        G.At, G.Bt, G.u, G.dY, G.du = At.data_ptr(), Bt.data_ptr(), u.data_ptr(), dy2.data_ptr(), du.data_ptr()
+        G.dA, G.dB = (da.data_ptr() if need_a else None), (db.data_ptr() if need_b else None)
+        loras.append(L)
+        grads.append(G)
+        keep.append((At, Bt, u, dy2, du))
+        outs.append((da, db))
+    la = (ctypes.POINTER(_lib.GptqLora) * n)(*[ctypes.pointer(L) for L in loras])
+    ga = (ctypes.POINTER(_lib.GptqLoraGrad) * n)(*[ctypes.pointer(G) for G in grads])
+    idx = dev.index
+    with torch.cuda.device(idx):
+        nbytes = lib.gptq_lora_backward_workspace_bytes(la, n, M)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        rc = lib.gptq_lora_backward(la, ga, n, x2.data_ptr(), dx.data_ptr() if need_x else None, M, ws.data_ptr() if nbytes else None, nbytes,
+                                    _raw_stream(idx))
+    if rc == 3:                                                     # GPTQ_ERR_UNSUPPORTED: nothing was launched
+        _warn_once(f"LoraQuantLinear: gptq_lora_backward declined a call ({lib.gptq_last_error().decode()}); the adapter's backward runs on torch matmuls")
+        return None
+    _lib.check(rc)
+    return (dx if need_x else None), outs
+
+
+class _LoraGroupApply(torch.autograd.Function):
+    """The adapter branches of up to LORA_MAX layers that read one input, as ONE autograd node: forward is one gptq_lora_apply on copies of the base
+    outputs (the values of the per-layer calls, bit for bit), backward one gptq_lora_backward with one shared dX -- x's adapter gradient is produced once
+    instead of once per layer.  Arguments: (layers, x, y_0 .., a_0 .., b_0 ..); the masters are cast to the layer dtype here, as _LoraApply does."""
+
+    @staticmethod
+    def forward(ctx, layers, xw, *rest):
+        n = len(layers)
+        ys, As, Bs = rest[:n], rest[n:2 * n], rest[2 * n:]
+        T = ys[0].dtype
+        K = layers[0].in_features
+        x2 = xw.reshape(-1, K)
+        if not x2.is_contiguous() or x2.data_ptr() % 16:
+            x2 = x2.clone(memory_format=torch.contiguous_format)
+        M = x2.shape[0]
+        A16 = [a.detach().to(T).contiguous() for a in As]
+        B16 = [b.detach().to(T).contiguous() for b in Bs]
+        outs = [y.clone(memory_format=torch.contiguous_format) for y in ys]
+        us = [torch.empty((M, l.r), dtype=T, device=x2.device) for l in layers]
+        structs = []
+        for l, a16, b16 in zip(layers, A16, B16):
+            L = _lib.GptqLora()
+            L.A, L.B = a16.data_ptr(), b16.data_ptr()
+            L.K, L.N, L.r, L.dtype, L.scale = K, l.out_features, l.r, _lib.DTYPE_ENUM.get(T, -1), float(l.scaling)
+            structs.append(L)
+        arr = (ctypes.POINTER(_lib.GptqLora) * n)(*[ctypes.pointer(s) for s in structs])
+        uptr = (ctypes.c_void_p * n)(*[u.data_ptr() for u in us])
+        optr = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
+        idx = x2.device.index
+        with torch.cuda.device(idx):
+            _lib.check(_lib.load().gptq_lora_apply(arr, n, x2.data_ptr(), uptr, optr, M, _raw_stream(idx)))
+        ctx.save_for_backward(x2, *us, *A16, *B16)
+        ctx.n = n
+        ctx.x_shape = xw.shape
+        ctx.scalings = [float(l.scaling) for l in layers]
+        ctx.master_dtypes = [(a.dtype, b.dtype) for a, b in zip(As, Bs)]
+        return tuple(outs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *dys):
+        n = ctx.n
+        saved = ctx.saved_tensors
+        x2, us, A16, B16 = saved[0], saved[1:1 + n], saved[1 + n:1 + 2 * n], saved[1 + 2 * n:]
+        need = ctx.needs_input_grad
+        need_x, need_y, need_a, need_b = need[1], need[2:2 + n], need[2 + n:2 + 2 * n], need[2 + 2 * n:]
+        dx, das, dbs = None, [None] * n, [None] * n
+        if need_x or any(need_a) or any(need_b):
+            items = [(A16[i], B16[i], us[i], dys[i], ctx.scalings[i], need_a[i], need_b[i]) for i in range(n)]
+            res = _fused_backward(x2, items, need_x)
+            if res is None:                                         # declined at call time: the same products in torch, per adapter
+                res = _torch_backward(x2, items, need_x)
+            dx, outs = res
+            for i, (da, db) in enumerate(outs):
+                das[i] = da.to(ctx.master_dtypes[i][0]) if need_a[i] else None
+                dbs[i] = db.to(ctx.master_dtypes[i][1]) if need_b[i] else None
+        return (None, (dx.reshape(ctx.x_shape) if need_x else None), *[(dys[i] if need_y[i] else None) for i in range(n)], *das, *dbs)
+
+
+def _torch_backward(x2, items, need_x):
+    """_fused_backward's contract on torch matmuls in fp32 (_LoraApply.backward's formulas)."""
+    dx = torch.zeros(x2.shape, dtype=torch.float32, device=x2.device) if need_x else None
+    outs = []
+    for A16, B16, u, dy, scale, need_a, need_b in items:
+        dy2 = dy.reshape(-1, B16.shape[0]).float()
+        da = db = None
+        if need_x or need_a:
+            du = (dy2 @ B16.float()) * scale
+            if need_a:
+                da = du.t() @ x2.float()
+            if need_x:
+                dx += du @ A16.float()
+        if need_b:
+            db = (dy2.t() @ u.float()) * scale
+        outs.append((da, db))
+    return (dx.to(x2.dtype) if need_x else None), outs
+
+
 def lora_forward_multi(layers, x: torch.Tensor):
     """``[l(x) for l in layers]`` for LoraQuantLinears that read one input (q|k|v, gate|up): ``forward_multi`` on the bases, then ONE down launch and ONE
     up launch for all adapters (groups of up to 4).  Values are bit-identical to the per-layer calls.  Dropout in training mode, a call that records
-    gradients, bases that are not single layers, or adapters the kernels decline: per-layer calls."""
+    gradients, bases that are not single layers, or adapters the kernels decline: per-layer calls.  A call that records gradients whose layers all have
+    ``fused_backward`` on (and are accepted by gptq_lora_backward) stays grouped: one autograd node per group of up to 4 (_LoraGroupApply)."""
     layers = list(layers)
     plain = all(isinstance(l, LoraQuantLinear) and getattr(l.base, "_parts", None) is None for l in layers)
     if not plain or any(l.training and l.lora_dropout > 0.0 for l in layers):
@@ -243,7 +399,13 @@ def lora_forward_multi(layers, x: torch.Tensor):
     x2 = xw.reshape(-1, K)
     M = x2.shape[0]
     fused = not grad and M > 0 and all(l.fused_ok(T) for l in layers) and all(y.is_contiguous() and y.data_ptr() % 16 == 0 for y in ys)
-    if not fused:
+    group = (grad and M > 0 and x2.is_cuda and all(l.fused_backward and l.fused_ok(T) and l.fused_backward_ok(T) for l in layers))
+    if group:
+        outs = []
+        for i in range(0, len(layers), _lib.LORA_MAX):
+            grp = tuple(layers[i:i + _lib.LORA_MAX])
+            outs += list(_LoraGroupApply.apply(grp, xw, *ys[i:i + _lib.LORA_MAX], *[l.lora_A.weight for l in grp], *[l.lora_B.weight for l in grp]))
+    elif not fused:
         outs = [l._after_base(y, xw) for l, y in zip(layers, ys)]
     else:
         if not x2.is_contiguous() or x2.data_ptr() % 16:
@@ -271,9 +433,10 @@ def _matches(name: str, target_modules) -> bool:
     return any(name == t or name.endswith("." + t) for t in target_modules)
 
 
-def inject_lora(model: nn.Module, target_modules, r: int, lora_alpha: float, lora_dropout: float = 0.0, adapter_dtype=torch.float32) -> dict:
+def inject_lora(model: nn.Module, target_modules, r: int, lora_alpha: float, lora_dropout: float = 0.0, adapter_dtype=torch.float32,
+                fused_backward: bool = False) -> dict:
     """Wrap every mi355x QuantLinear of ``model`` whose name is, or ends in, one of ``target_modules`` (peft's rule; get_gptq_peft_model,
-    peft_utils.py:126-176) in a LoraQuantLinear.  Returns {module name: LoraQuantLinear}."""
+    peft_utils.py:126-176) in a LoraQuantLinear.  Returns {module name: LoraQuantLinear}.  ``fused_backward``: the layers' opt-in switch (LoraQuantLinear)."""
     found = {n: m for n, m in model.named_modules() if isinstance(m, QuantLinear) and _matches(n, target_modules)}
     out = {}
     for name, base in found.items():
@@ -281,11 +444,17 @@ def inject_lora(model: nn.Module, target_modules, r: int, lora_alpha: float, lor
         parent = model.get_submodule(parent_name) if parent_name else model
         if isinstance(parent, LoraQuantLinear):                     # already wrapped
             continue
-        wrapped = LoraQuantLinear(base, r, lora_alpha, lora_dropout, adapter_dtype)
+        wrapped = LoraQuantLinear(base, r, lora_alpha, lora_dropout, adapter_dtype, fused_backward)
         wrapped.train(model.training)
         setattr(parent, attr, wrapped)
         out[name] = wrapped
     return out
+
+
+def set_lora_fused_backward(model: nn.Module, on: bool = True) -> None:
+    """Switch every adapted layer's backward between one gptq_lora_backward (on) and the torch matmuls (off, the default)."""
+    for m in lora_layers(model).values():
+        m.fused_backward = bool(on)
 
 
 def lora_layers(model: nn.Module) -> dict:
@@ -352,4 +521,4 @@ def refresh_lora(model: nn.Module) -> None:
 
 
 __all__ = ["LoraQuantLinear", "parse_adapter_key", "lora_forward_multi", "inject_lora", "lora_state_dict", "load_lora_adapter", "mark_only_lora_trainable", "refresh_lora",
-           "lora_layers"]
+           "lora_layers", "set_lora_fused_backward"]

@@ -27,6 +27,8 @@
  *          and the triton backend's QuantLinearFunction.backward      auto_gptq/nn_modules/triton_utils/kernels.py:408-426
  *   gptq_lora_down, gptq_lora_up, gptq_lora_apply
  *       <- GPTQLoraLinear.forward's adapter branch (torch matmuls on the base output)   auto_gptq/utils/peft_utils.py:100-123
+ *   gptq_lora_backward
+ *       <- autograd through that branch (torch matmuls; get_gptq_peft_model's training use)   auto_gptq/utils/peft_utils.py:126-176
  *   gptq_make_sequential + gptq_resequence_qweight + gptq_permute_columns
  *       <- exllama_kernels.make_q4 (Q4Matrix::make_sequential)        exllama/exllama_ext.cpp:134-171, cuda_func/q4_matrix.cu:63-169
  *          exllamav2_kernels.make_q_matrix                            exllamav2/ext.cpp:26-93, cuda/q_matrix.cu:502-627
@@ -284,6 +286,41 @@ int gptq_lora_apply(const gptq_lora_t *const *loras, int n, const void *x, void 
 /* Host-only: "path=lora rows=gemv|mfma wg_down=... wg_up=... launches=2" (rows: the VALU forms up to 8 rows, the matrix-core forms above) or
  * "path=none reason=...".  GPTQ_OK either way (GPTQ_ERR_NULL for a NULL out). */
 int gptq_describe_lora_plan(const gptq_lora_t *const *loras, int n, int M, char *out, size_t out_bytes);
+
+/* The adapters' backward.  For each adapter i of a call (T the layer dtype, s = loras[i]->scale, K / N / r of loras[i]; loras[i]->A and ->B are NOT read):
+ *   1. du_i[m, j] = T(sum_n dY_i[m, n] * Bt_i[j, n])                      gptq_lora_down with A := Bt [r, N], K := N: bit-identical to that call
+ *   2. dA_i[j, k] = s * sum_m float(du_i[m, j]) * float(x[m, k])          fp32 [r, K], overwritten
+ *   3. dB_i[n, j] = s * sum_m float(dY_i[m, n]) * float(u_i[m, j])        fp32 [N, r], overwritten; u_i is the forward's u
+ *   4. dX[m, k]   = T(float(dX[m, k]) + s * sum_j du_i[m, j] * At_i[k, j])  gptq_lora_up with B := At [K, r], N := K, in place on ONE dX shared by all
+ *                                                                          adapters, i = 0 .. n-1 in that order (one launch each); the caller passes
+ *                                                                          zeros or a gradient to add to
+ * At = A^T [K, r] and Bt = B^T [r, N] are copies in T the caller makes.  dA or dB NULL skips that output; dX NULL skips step 4.  Steps 2 and 3 of all
+ * adapters are ONE launch (csrc/adapter_grad.hip): a unit is one 64-wide block of K (or N) x all of r x one slice of M, the row index is the summed one.
+ * The slice count of one output [P, Q] ({r, K} or {N, r}) is a function of (M, P, Q) alone, the same on every device:
+ *     steps = ceil(M / 32), blocks = ceil(max(P, Q) / 64), S0 = min(64, max(1, steps / 4), ceil(512 / blocks)),
+ *     steps_per_slice = ceil(steps / S0), S = ceil(steps / steps_per_slice)          (a slice is 32 steps_per_slice rows, the last may be short)
+ * S = 1 writes s * sum straight to the output; S > 1 writes fp32 partials [S, P, Q] to the workspace and a second launch adds them in ascending slice order
+ * and applies s.  No atomics, fixed orders: bit-reproducible, and adapter i's results in a call of n are bit-identical to a call of its own.
+ * Workspace: sum over the adapters and their two outputs of (S > 1 ? a256(4 S P Q) : 0), a256 = round up to 256; it does not depend on which outputs are
+ * NULL, and may be NULL when that is 0.  Caller's stream, no allocation, no sync, legal inside hipGraph capture; M = 0 launches nothing.
+ * Declined with GPTQ_ERR_UNSUPPORTED and the reason in gptq_last_error(), before any launch: fp32, r outside {8, 16, .., 64}, K % 32, N % 32 (stricter than
+ * the forward: N is a summed length of step 1), n > GPTQ_LORA_MAX, adapters that differ in K or dtype, any pointer not 16-byte aligned.
+ * GPTQ_ERR_WORKSPACE for a workspace that is too small, GPTQ_ERR_NULL for a NULL At / Bt / u / dY / du / x. */
+typedef struct gptq_lora_grad_t {
+    const void *At;         /* [K, r] dtype: lora_A.weight^T */
+    const void *Bt;         /* [r, N] dtype: lora_B.weight^T */
+    const void *u;          /* [M, r] dtype: the forward's u */
+    const void *dY;         /* [M, N] dtype */
+    void       *du;         /* [M, r] dtype, written */
+    float      *dA;         /* [r, K] fp32, overwritten; NULL: skipped */
+    float      *dB;         /* [N, r] fp32, overwritten; NULL: skipped */
+} gptq_lora_grad_t;
+size_t gptq_lora_backward_workspace_bytes(const gptq_lora_t *const *loras, int n, int M);  /* 0 when the call is declined */
+int gptq_lora_backward(const gptq_lora_t *const *loras, const gptq_lora_grad_t *const *grads, int n, const void *x, void *dX, int M,
+                       void *workspace, size_t workspace_bytes, void *stream);
+/* Host-only: "path=lora_backward S_dA=a,b,.. S_dB=a,b,.. wg_down=... wg_wgrad=... wg_sum=... wg_up=... workspace=... launches=..." for a call that asks
+ * for every output (per-adapter slice counts; launches = n + 1 + (any S > 1) + n) or "path=none reason=...".  GPTQ_OK either way. */
+int gptq_describe_lora_backward_plan(const gptq_lora_t *const *loras, int n, int M, char *out, size_t out_bytes);
 
 /* Per-row adapter banks: a batch whose rows belong to different fine-tunes of one GPTQ base.  Row m carries a slot ids[m] (int64, device memory); a bank
  * holds `slots` adapters of ONE layer: A [slots][r][K] and B [slots][N][r] in the layer dtype T (fp16 / bf16), scales [slots] fp32, all device memory.

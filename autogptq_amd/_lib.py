@@ -62,8 +62,11 @@ class GptqTuning(Structure):
 
 
 class GptqMoe(Structure):
-    """gptq_moe_t: E experts, each a gate / up / down layer (arrays of E layer pointers)."""
-    _fields_ = [("E", c_int32), ("reserved", c_int32), ("gate", c_void_p), ("up", c_void_p), ("down", c_void_p)]
+    """gptq_moe_t: E experts, each a gate / up / down layer (arrays of E layer pointers); flags: 0 (the default) or MOE_LOW_BIT."""
+    _fields_ = [("E", c_int32), ("flags", c_int32), ("gate", c_void_p), ("up", c_void_p), ("down", c_void_p)]
+
+
+MOE_LOW_BIT = 1          # GPTQ_MOE_LOW_BIT: the grouped path (forward and backward) also takes 2- and 3-bit experts
 
 
 LORA_MAX = 4             # GPTQ_LORA_MAX: adapters of one gptq_lora_* call

@@ -1064,7 +1064,7 @@ int gptq_describe_adapter_rows_plan(const gptq_adapter_bank_t* const* Bs, int n,
 }
 
 // ---- routed mixture-of-experts layers (moe.hip) ----
-static int moe_check_proj(const gptq_layer_t* const* Ls, int E, int K, int N, int dtype, const char* name) {
+static int moe_check_proj(const gptq_layer_t* const* Ls, int E, int K, int N, int dtype, int flags, const char* name) {
     if (!Ls) return fail(GPTQ_ERR_NULL, "moe->%s is NULL", name);
     for (int e = 0; e < E; ++e) {
         const gptq_layer_t* L = Ls[e];
@@ -1080,7 +1080,10 @@ static int moe_check_proj(const gptq_layer_t* const* Ls, int E, int K, int N, in
             return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s: raw act-order (no re-sequenced rows) is not taken by the grouped path", e, name);
     }
     const gptq_layer_t* A = Ls[0];
-    if (A->bits != 4 && A->bits != 8) return fail(GPTQ_ERR_UNSUPPORTED, "%d-bit experts: the grouped path takes 4 or 8 bits", A->bits);
+    if (A->bits != 4 && A->bits != 8) {
+        if (!(flags & GPTQ_MOE_LOW_BIT)) return fail(GPTQ_ERR_UNSUPPORTED, "%d-bit experts: the grouped path takes 4 or 8 bits", A->bits);
+        if (A->bits != 2 && A->bits != 3) return fail(GPTQ_ERR_UNSUPPORTED, "%d-bit experts: the grouped path takes 2, 3, 4 or 8 bits", A->bits);
+    }
     if (A->group_size % 32 && A->group_size < K)
         return fail(GPTQ_ERR_UNSUPPORTED, "group_size %d: the grouped path takes multiples of 32 (or one group)", A->group_size);
     return GPTQ_OK;
@@ -1088,6 +1091,7 @@ static int moe_check_proj(const gptq_layer_t* const* Ls, int E, int K, int N, in
 
 static int moe_check(const gptq_moe_t* m, int T, int topk) {
     if (!m) return fail(GPTQ_ERR_NULL, "moe is NULL");
+    if (m->flags & ~GPTQ_MOE_LOW_BIT) return fail(GPTQ_ERR_UNSUPPORTED, "moe->flags = 0x%x: unknown flag bits (GPTQ_MOE_LOW_BIT is the only one)", (unsigned)m->flags);
     if (m->E < 1 || m->E > 256) return fail(GPTQ_ERR_UNSUPPORTED, "E = %d experts: the grouped path takes 1..256", m->E);
     if (topk < 1 || topk > 8) return fail(GPTQ_ERR_UNSUPPORTED, "topk = %d: the grouped path takes 1..8", topk);
     if (T < 0) return fail(GPTQ_ERR_SHAPE, "T must be >= 0, got %d", T);
@@ -1098,12 +1102,12 @@ static int moe_check(const gptq_moe_t* m, int T, int topk) {
     const int H = G->K, I = G->N;
     if (H % 64 || I % 64) return fail(GPTQ_ERR_UNSUPPORTED, "hidden (%d) and intermediate (%d) sizes must be multiples of 64", H, I);
     if ((long)T * topk > 0x3fffffffL / 4) return fail(GPTQ_ERR_SHAPE, "T = %d is too large", T);
-    if (int rc = moe_check_proj(m->gate, m->E, H, I, G->dtype, "gate")) return rc;
-    if (int rc = moe_check_proj(m->up, m->E, H, I, G->dtype, "up")) return rc;
+    if (int rc = moe_check_proj(m->gate, m->E, H, I, G->dtype, m->flags, "gate")) return rc;
+    if (int rc = moe_check_proj(m->up, m->E, H, I, G->dtype, m->flags, "up")) return rc;
     const gptq_layer_t* U = m->up[0];
     if (U->bits != G->bits || U->group_size != G->group_size || U->zero_mode != G->zero_mode)
         return fail(GPTQ_ERR_UNSUPPORTED, "gate and up layers must share bits, group_size and zero_mode");
-    return moe_check_proj(m->down, m->E, I, H, G->dtype, "down");
+    return moe_check_proj(m->down, m->E, I, H, G->dtype, m->flags, "down");
 }
 
 size_t gptq_moe_table_bytes(int E) { return E > 0 ? 3 * (size_t)E * moe_table_entry_bytes() : 0; }

@@ -138,6 +138,35 @@ template <typename T> struct Deq1_8 {
         return u32x4{sc.mul(h0, 0), sc.mul(h1, 0), sc.mul(h2, 0), sc.mul(h3, 0)};
     }
 };
+// 2 bits: fields i = 0..3 at bit 2 i of both halves of w (pairs (i, 4 + i)), read in place like the 3-bit ones: OR-ing the exponent of 1024 over field i
+// gives 1024 + 4^i f, and one fma with 4^-i and -(1024 / 4^i + z) leaves f - z exactly
+template <typename T> struct Deq1_2 {
+    wide::Scale4<T> sc;                                            // (column 0 of it)
+    f16x2 c0, c1, c2, c3;
+    __device__ __forceinline__ void setup(unsigned sraw, unsigned z) {
+        sc.setup(u32x2{sraw & 0xffffu, 0u});
+        c0 = as_f16x2(z * 0x00010001u + 0xE400E400u);                 // -(1024 + z)
+        c1 = as_f16x2(z * 0x00040004u + 0xDC00DC00u);                 // -(256 + z)
+        c2 = as_f16x2(z * 0x00100010u + 0xD400D400u);                 // -(64 + z)
+        c3 = as_f16x2(z * 0x00400040u + 0xCC00CC00u);                 // -(16 + z)
+    }
+    __device__ __forceinline__ f16x2 p0(unsigned q) const { return as_f16x2(wide::and_or(q, 0x00030003u, 0x64006400u)) + c0; }
+    __device__ __forceinline__ f16x2 p1(unsigned q) const {
+        const f16x2 rr = {(f16)0.25f, (f16)0.25f};
+        return as_f16x2(wide::and_or(q, 0x000c000cu, 0x64006400u)) * rr + c1;
+    }
+    __device__ __forceinline__ f16x2 p2(unsigned q) const {
+        const f16x2 rr = {(f16)0.0625f, (f16)0.0625f};
+        return as_f16x2(wide::and_or(q, 0x00300030u, 0x64006400u)) * rr + c2;
+    }
+    __device__ __forceinline__ f16x2 p3(unsigned q) const {
+        const f16x2 rr = {(f16)0.015625f, (f16)0.015625f};
+        return as_f16x2(wide::and_or(q, 0x00c000c0u, 0x64006400u)) * rr + c3;
+    }
+    __device__ __forceinline__ u32x4 frag(unsigned w) const {         // k order (0,4,1,5,2,6,3,7)
+        return u32x4{sc.mul(p0(w), 0), sc.mul(p1(w), 0), sc.mul(p2(w), 0), sc.mul(p3(w), 0)};
+    }
+};
 template <typename T, int BITS> struct DeqSel { typedef Deq1<T> type; };
 template <typename T> struct DeqSel<T, 3> { typedef Deq1_3<T> type; };
 template <typename T> struct DeqSel<T, 8> { typedef Deq1_8<T> type; };

@@ -23,19 +23,25 @@
 //   * dequantises them with the magic-number form of the panel / rows kernels (rowsk::Deq1, Deq1_8: w - z exact in packed fp16, times the scale with one
 //     rounding: bit-exact W).  On checkpoint words that form yields the k of a fragment in the order (0,4,1,5,2,6,3,7) (8 bits: (0,2,1,3,4,6,5,7)), so
 //     the A fragment is permuted the same way (4 v_perm_b32) -- the MFMA pairs A and B element by element;
+//     2 and 3 bits (GPTQ_MOE_LOW_BIT): the lane cuts its 8 fields out of the step's rows -- 3 bits: bits 24 ks .. 24 ks + 23 of the column's 96 (rows
+//     3 st + lo and 3 st + min(lo + 1, 2), lo = 24 ks >> 5: two 16-byte loads and one v_alignbit_b32 per column), 2 bits: half ks & 1 of row
+//     2 st + (ks >> 1) -- moves fields 0..3 | 4..7 to the two halves of a register and reads them in place (rowsk::Deq1_3's readers, Deq1_2): the
+//     4-bit k order, so order_a is the 4-bit one;
 //   * reads its A fragment (row lane & 15 of each 16-row block of the tile, 8 consecutive k) straight from global memory: x gathered through the sorted row's
 //     token (pair mode) or the H_sorted row (down mode); act-order experts gather the 8 columns through the expert's perm (W3 through its own when it has
 //     another order than W1; a checkpoint's gate / up share one).  Rows past the tile repeat its
 //     last row (results discarded), so the loop has no branches on the row count.
 // Groups: group_size is a multiple of 32 (or covers K), so a 32-deep step lies in one group: group = k0 / group_size, uniform over the wave (for act-order
 // experts k0 is the position in the re-sequenced rows).  bits, the group mode, the rows of the tile and the epilogue are runtime-uniform: two instantiations.
+// The four zero points of a lane are 4 fields at bit bits * n of the group's qzeros row: one word, except the 3-bit quads with n % 32 in {8, 20}, which
+// straddle two (the second word is read only then: the last quad of a row never straddles, N being a multiple of 64).
 #include <string.h>
 
 #include <algorithm>
 
 #include "common.cuh"
 #include "launch.h"
-#include "gemm_rows_kernel.cuh"      // rowsk::Deq1<T> / Deq1_8<T>: the magic-number dequantisation
+#include "gemm_rows_kernel.cuh"      // rowsk::Deq1<T> / Deq1_8<T> / Deq1_3<T> / Deq1_2<T>: the magic-number dequantisation
 
 namespace gptq {
 namespace moe {
@@ -150,7 +156,7 @@ struct GemmArgs {
 
 // A fragment of one lane: 8 consecutive k of one row, put in the order the dequantised B fragment has
 __device__ __forceinline__ u32x4 order_a(u32x4 v, int bits) {
-    if (bits == 4)      // (0,4,1,5,2,6,3,7)
+    if (bits != 8)      // 2, 3, 4 bits: (0,4,1,5,2,6,3,7)
         return u32x4{__builtin_amdgcn_perm(v.z, v.x, 0x05040100u), __builtin_amdgcn_perm(v.z, v.x, 0x07060302u),
                      __builtin_amdgcn_perm(v.w, v.y, 0x05040100u), __builtin_amdgcn_perm(v.w, v.y, 0x07060302u)};
     return u32x4{__builtin_amdgcn_perm(v.y, v.x, 0x05040100u), __builtin_amdgcn_perm(v.y, v.x, 0x07060302u),   // 8 bits: (0,2,1,3,4,6,5,7)
@@ -163,37 +169,85 @@ struct Proj {                                   // one projection's weights for 
     const unsigned* qz;
     const T* sc;
     int gcur;
-    typename rowsk::Deq1<T> d4[4];
-    typename rowsk::Deq1_8<T> d8[4];
+    wide::Scale4<T> s4;                         // the 4 columns' scales
+    f16x2 k[4][4];                              // column c's constants -(2^m + z), shared by the widths: 4 bits k[c][0..1] (Deq1's c1, c2), 8 bits k[c][0],
+                                                // 3 bits k[c][0..2] (Deq1_3's c0..c2), 2 bits k[c][0..3] (Deq1_2's c0..c3); the rest is never read
 
     __device__ __forceinline__ void group(const GemmArgs& p, int g, int n) {
         if (g == gcur) return;
         gcur = g;
-        const u32x2 s = *(const u32x2*)(sc + (size_t)g * p.N + n);           // 4 scales (8 bytes)
+        s4.setup(*(const u32x2*)(sc + (size_t)g * p.N + n));                  // 4 scales (8 bytes)
         const int zrow = p.N / 32 * p.bits;
-        const unsigned bit = (unsigned)(p.bits * n);
-        const unsigned zw = qz[(size_t)g * zrow + (bit >> 5)] >> (bit & 31);  // 4 fields inside one word (n % 4 == 0; 4 or 8 bits)
+        const unsigned bit = (unsigned)(p.bits * n), wi = bit >> 5, sh = bit & 31u;
+        const unsigned* __restrict__ zr = qz + (size_t)g * zrow;
+        unsigned zw = zr[wi] >> sh;                                           // 4 fields (n % 4 == 0): inside one word at 2, 4 and 8 bits
+        if (sh + 4u * (unsigned)p.bits > 32u) zw |= zr[wi + 1] << (32u - sh); // 3 bits, n % 32 in {8, 20}: they straddle (never the last quad of a row: N % 64 == 0)
         const unsigned maxq = (1u << p.bits) - 1u;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            int z = (int)((zw >> (p.bits * c)) & maxq) + 1;
-            if (p.zero_mode == GPTQ_ZERO_WRAP) z &= (int)maxq;
-            const unsigned sraw = (c & 1) ? (s[c >> 1] >> 16) : (s[c >> 1] & 0xffffu);
-            if (p.bits == 4) d4[c].setup(sraw, (unsigned)z);
-            else d8[c].setup(sraw, (unsigned)z);
+            int zi = (int)((zw >> (p.bits * c)) & maxq) + 1;
+            if (p.zero_mode == GPTQ_ZERO_WRAP) zi &= (int)maxq;
+            const unsigned z = (unsigned)zi;
+            k[c][0] = as_f16x2(z * 0x00010001u + 0xE400E400u);                // -(1024 + z): every width
+            if (p.bits == 4) {
+                const f16x2 k960 = {(f16)960.f, (f16)960.f};
+                k[c][1] = k[c][0] + k960;                                     // -(64 + z)
+            } else if (p.bits == 3) {
+                k[c][1] = as_f16x2(z * 0x00080008u + 0xD800D800u);            // -(128 + z)
+                k[c][2] = as_f16x2(z * 0x00400040u + 0xCC00CC00u);            // -(16 + z)
+            } else if (p.bits == 2) {
+                k[c][1] = as_f16x2(z * 0x00040004u + 0xDC00DC00u);            // -(256 + z)
+                k[c][2] = as_f16x2(z * 0x00100010u + 0xD400D400u);            // -(64 + z)
+                k[c][3] = as_f16x2(z * 0x00400040u + 0xCC00CC00u);            // -(16 + z)
+            }
         }
     }
+    // the lane's fields of one step: 4 bits one row of words (8 k each); 8 bits rows k0 / 4 + 2 ks, + 1; 3 bits the step's rows 3 st + lo, + hi that hold
+    // bits 24 ks .. 24 ks + 23 of the columns' 96 (hi is clamped: k-slot 3 must not read the next step's row); 2 bits row 2 st + (ks >> 1)
     __device__ __forceinline__ void load(const GemmArgs& p, int k0, int ks, int n, u32x4& q0, u32x4& q1) const {
         if (p.bits == 4) {
             q0 = *(const u32x4*)(qw + (size_t)(k0 / 8 + ks) * p.N + n);
-        } else {
+        } else if (p.bits == 8) {
             const size_t r = (size_t)(k0 / 4 + 2 * ks);
             q0 = *(const u32x4*)(qw + r * p.N + n);
             q1 = *(const u32x4*)(qw + (r + 1) * p.N + n);
+        } else if (p.bits == 3) {
+            const int lo = (24 * ks) >> 5, hi = min(lo + 1, 2);
+            const size_t r = (size_t)(k0 / 32) * 3;
+            q0 = *(const u32x4*)(qw + (r + lo) * p.N + n);
+            q1 = *(const u32x4*)(qw + (r + hi) * p.N + n);
+        } else {
+            q0 = *(const u32x4*)(qw + (size_t)(k0 / 16 + (ks >> 1)) * p.N + n);
         }
     }
-    __device__ __forceinline__ u32x4 frag(const GemmArgs& p, int c, const u32x4& q0, const u32x4& q1) const {
-        return p.bits == 4 ? d4[c].frag(q0[c]) : d8[c].frag(q0[c], q1[c]);
+    __device__ __forceinline__ u32x4 frag(const GemmArgs& p, int c, int ks, const u32x4& q0, const u32x4& q1) const {
+        f16x2 h0, h1, h2, h3;
+        if (p.bits == 4) {                      // rowsk::Deq1: (0,4) (1,5) (2,6) (3,7)
+            const unsigned q = q0[c], q8 = q >> 8;
+            const f16x2 r16 = {(f16)0.0625f, (f16)0.0625f};
+            h0 = as_f16x2(wide::and_or(q, 0x000f000fu, 0x64006400u)) + k[c][0];
+            h1 = as_f16x2(wide::and_or(q, 0x00f000f0u, 0x64006400u)) * r16 + k[c][1];
+            h2 = as_f16x2(wide::and_or(q8, 0x000f000fu, 0x64006400u)) + k[c][0];
+            h3 = as_f16x2(wide::and_or(q8, 0x00f000f0u, 0x64006400u)) * r16 + k[c][1];
+        } else if (p.bits == 8) {               // rowsk::Deq1_8: (0,2) (1,3) (4,6) (5,7)
+            h0 = as_f16x2(wide::and_or(q0[c], 0x00ff00ffu, 0x64006400u)) + k[c][0];
+            h1 = as_f16x2(wide::and_or(q0[c] >> 8, 0x00ff00ffu, 0x64006400u)) + k[c][0];
+            h2 = as_f16x2(wide::and_or(q1[c], 0x00ff00ffu, 0x64006400u)) + k[c][0];
+            h3 = as_f16x2(wide::and_or(q1[c] >> 8, 0x00ff00ffu, 0x64006400u)) + k[c][0];
+        } else if (p.bits == 3) {               // the 24-bit window, fields 0..3 | 4..7 moved to bit 0 / 3 / 6 / 9 of the halves: Deq1_3's in-place readers
+            const unsigned v = __builtin_amdgcn_alignbit(q1[c], q0[c], (unsigned)(24 * ks) & 31u) & 0xffffffu;
+            const unsigned w = (v & 0xfffu) | ((v >> 12) << 16);
+            rowsk::Deq1_3<T> d;
+            d.c0 = k[c][0]; d.c1 = k[c][1]; d.c2 = k[c][2];
+            h0 = d.p0(w); h1 = d.p1(w); h2 = d.p2(w); h3 = d.p1(w >> 6);
+        } else {                                // half ks & 1 of the word, its bytes moved to the halves: Deq1_2's readers
+            const unsigned v = q0[c] >> (16 * (ks & 1));
+            const unsigned w = (v & 0xffu) | ((v & 0xff00u) << 8);
+            rowsk::Deq1_2<T> d;
+            d.c0 = k[c][0]; d.c1 = k[c][1]; d.c2 = k[c][2]; d.c3 = k[c][3];
+            h0 = d.p0(w); h1 = d.p1(w); h2 = d.p2(w); h3 = d.p3(w);
+        }
+        return u32x4{s4.mul(h0, c), s4.mul(h1, c), s4.mul(h2, c), s4.mul(h3, c)};
     }
 };
 
@@ -267,12 +321,12 @@ __global__ void __launch_bounds__(THREADS) moe_gemm_kernel(GemmArgs p) {
         if (p.pair) pu.group(p, g, n);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            const u32x4 bg = pg.frag(p, c, qg0, qg1);
+            const u32x4 bg = pg.frag(p, c, ks, qg0, qg1);
 #pragma unroll
             for (int i = 0; i < 4; ++i)
                 if (i < rb) ag[i][c] = rowsk::Mma16<T>::run(a[i], bg, ag[i][c]);
             if (p.pair) {
-                const u32x4 bu = pu.frag(p, c, qu0, qu1);
+                const u32x4 bu = pu.frag(p, c, ks, qu0, qu1);
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
                     if (i < rb) au[i][c] = rowsk::Mma16<T>::run(sep ? a3[i] : a[i], bu, au[i][c]);

@@ -87,7 +87,7 @@ def pack_model(model: nn.Module, quantizers: dict, bits: int, group_size: int, d
 
 def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_length: Optional[int] = None,
                        release_checkpoint_layout: Optional[bool] = None, decode_copy: Optional[bool] = None,
-                       expert_decode_copy: bool = False, expert_batched_decode: bool = False, expert_backward: bool = False) -> nn.Module:
+                       expert_decode_copy: bool = False, expert_batched_decode: bool = False, expert_backward: bool = False, expert_low_bit: bool = False) -> nn.Module:
     """post_init every mi355x layer and size the per-device scratch once (so forward never allocates; needed before hipGraph
     capture).  ``max_input_length`` bounds the rows M the scratch is sized for (default 2048, the reference's exllama default).
     Memory (the model-level switches for what post_init keeps next to the checkpoint tensors): ``decode_copy=False`` builds no decode copy (1x the packed
@@ -102,7 +102,9 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
     kernels on that copy (``QuantMoEExperts.post_init(batch=True)``); the scratch covers the largest need of the paths up to ``max_input_length``.
     ``expert_backward=True`` (``QuantMoEExperts.post_init(backward=True)``): calls under grad run the grouped backward (one autograd node, one
     gptq_moe_backward call) instead of the per-expert composition; the scratch also covers ``gptq_moe_backward_workspace_bytes`` of ``max_input_length``
-    tokens."""
+    tokens.  ``expert_low_bit=True`` (``QuantMoEExperts.post_init(low_bit=True)``): 2- and 3-bit experts run the grouped kernels (forward, and the backward
+    with ``expert_backward=True``) instead of the per-expert composition, so ``capture_decode_step`` takes such a model; nothing changes for 4- and 8-bit
+    experts, and the expert decode copy keeps declining 2 / 3 bits."""
     from .moe import QuantMoEExperts
     rows = max_input_length or 2048
     need: Dict[torch.device, int] = {}
@@ -112,7 +114,7 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
         # mixture-of-experts layers: their QuantLinears are post-initialised by the module (no decode copy; a checkpoint-layout release does not apply)
         if isinstance(sub, QuantMoEExperts) and sub[0].layers()[0].qweight.device.type == "cuda":
             dev = sub[0].layers()[0].qweight.device
-            sub.post_init(decode_copy=expert_decode_copy, batch=expert_batched_decode, backward=expert_backward)
+            sub.post_init(decode_copy=expert_decode_copy, batch=expert_batched_decode, backward=expert_backward, low_bit=expert_low_bit)
             for e in range(sub.num_experts):
                 in_experts.update(id(l) for l in sub[e].layers())
             expert_copy_bytes += sub.decode_copy_bytes

@@ -11,8 +11,8 @@
                         one expert over the whole K, capturable), or the per-expert composition of differentiable ``QuantLinear`` calls
 * ``pack_moe_experts``  pack the dense 3-D expert parameters of a model (``quantizers`` keyed ``...mlp.experts.{e}.w1`` as ``pack_model`` takes)
 
-The per-expert composition serves what the grouped kernels do not take (2- / 3-bit or fp32 experts, odd group sizes, raw act-order), CPU tensors (which
-``QuantLinear`` refuses), and -- by default -- calls under grad where ``hidden_states`` or ``top_k_weights`` require grad: training through the experts gets
+The per-expert composition serves what the grouped kernels do not take (2- / 3-bit experts unless ``post_init(low_bit=True)``, fp32 experts, odd group
+sizes, raw act-order), CPU tensors (which ``QuantLinear`` refuses), and -- by default -- calls under grad where ``hidden_states`` or ``top_k_weights`` require grad: training through the experts gets
 dX and the router-weight gradient from the existing backward of ``QuantLinear``.  After ``post_init(backward=True)`` such a call is ONE autograd node
 instead: the forward runs the ordinary no-grad path, the backward is one gptq_moe_backward call (route, recompute of gate / up, two grouped transposed
 dequant-GEMM stages on the checkpoint rows, combine -- five launches, nothing saved but the inputs).
@@ -69,6 +69,7 @@ class QuantMoEExperts(nn.Module):
         self._decode_copy = False
         self._batch = False
         self._backward = False
+        self._low_bit = False
         self.batch_max_tokens = 64
         for e in range(num_experts):
             self.add_module(str(e), _Expert(self.names, bits, group_size, hidden_dim, intermediate_dim, weight_dtype, zero_mode))
@@ -105,7 +106,7 @@ class QuantMoEExperts(nn.Module):
         return [l[0] for l in ls], [l[1] for l in ls], [l[2] for l in ls]
 
     # ------------------------------------------------------------------ post_init
-    def post_init(self, decode_copy: bool = False, batch: bool = False, backward: bool = False):
+    def post_init(self, decode_copy: bool = False, batch: bool = False, backward: bool = False, low_bit: bool = False):
         """post_init every expert layer and build the pointer table.  Default: WITHOUT a decode copy (1x the packed bytes; act-order layers add their
         re-sequenced rows) -- calls of any row count run the grouped kernels.  ``decode_copy=True``: the layers also get their decode copy (2x the packed
         bytes; both layouts stay resident: the grouped path still serves more than 4 tokens), the decode table is built, and calls of 1..4 tokens run the
@@ -114,11 +115,14 @@ class QuantMoEExperts(nn.Module):
         log the reason once and behave as without the flag.  ``backward=True`` (opt-in as well): calls under grad whose ``hidden_states`` or
         ``top_k_weights`` require grad run the grouped backward (``last_plan["backward"] == "grouped"``: one autograd node, one gptq_moe_backward call
         on a pointer table of its own) instead of the per-expert composition; experts the backward plan declines log the reason once and keep the
-        composition.  ``decode_copy_bytes`` reports what the copies hold.  A checkpoint-layout release does not apply to expert layers."""
+        composition.  ``low_bit=True`` (opt-in as well): 2- and 3-bit experts run the grouped kernels too (``plan(T)["path"] == "grouped"`` at every T, and
+        ``backward=True`` yields their grouped backward) instead of the per-expert composition; it changes nothing for 4- and 8-bit experts, and the
+        decode and batch paths keep declining 2 / 3 bits.  ``decode_copy_bytes`` reports what the copies hold.  A checkpoint-layout release does not apply
+        to expert layers."""
         dev = self[0].layers()[0].qweight.device
         if dev.type != "cuda":
             raise RuntimeError(f"mi355x QuantMoEExperts.post_init needs the module on a ROCm GPU device (got {dev}); there is no CPU path.")
-        want_decode, self._batch, self._backward = bool(decode_copy), bool(batch), bool(backward)
+        want_decode, self._batch, self._backward, self._low_bit = bool(decode_copy), bool(batch), bool(backward), bool(low_bit)
         if self._batch:
             why = self._batch_declined()
             if why:
@@ -141,6 +145,7 @@ class QuantMoEExperts(nn.Module):
         arrs = [(ctypes.POINTER(_lib.GptqLayer) * self.num_experts)(*[ctypes.pointer(l._layer) for l in ls]) for ls in (gate, up, down)]
         m = _lib.GptqMoe()
         m.E = self.num_experts
+        m.flags = _lib.MOE_LOW_BIT if self._low_bit else 0
         m.gate, m.up, m.down = (ctypes.addressof(a) for a in arrs)
         table = torch.zeros(max(1, int(lib.gptq_moe_table_bytes(self.num_experts))), dtype=torch.uint8, device=dev)
         self._moe, self._keep, self._plans = m, (arrs, table, gate, up, down), {}
@@ -170,11 +175,11 @@ class QuantMoEExperts(nn.Module):
                 # declined (2- / 3-bit, fp32, a group size the copy does not take, ...): nothing would read the copies -- say so and give their memory back
                 logger.warning("QuantMoEExperts.post_init(decode_copy=True) has no effect for these experts (%s): no decode copy is kept",
                                str(dplan.get("reason", "")).replace("_", " "))
-                return self.post_init(decode_copy=False, backward=self._backward)
+                return self.post_init(decode_copy=False, backward=self._backward, low_bit=self._low_bit)
             bplan = _lib.describe_moe_batch_plan(m, 5, self.top_k) if self._batch else None
             if bplan is not None and bplan["path"] != "batch":
                 logger.warning("QuantMoEExperts.post_init(batch=True) has no effect for these experts (%s)", str(bplan.get("reason", "")).replace("_", " "))
-                return self.post_init(decode_copy=want_decode, backward=self._backward)
+                return self.post_init(decode_copy=want_decode, backward=self._backward, low_bit=self._low_bit)
             dtable = torch.zeros(max(1, int(lib.gptq_moe_decode_table_bytes(self.num_experts))), dtype=torch.uint8, device=dev)
             with torch.cuda.device(self._dev):
                 _lib.check(lib.gptq_moe_build_decode_table(ctypes.byref(m), dtable.data_ptr(), _lib.current_stream_handle(self._dev)))
@@ -217,7 +222,7 @@ class QuantMoEExperts(nn.Module):
     def workspace_bytes(self, T: int, top_k: "int | None" = None) -> int:
         """Scratch of one call with T tokens on the path ``plan(T)`` names."""
         if self._moe is None:
-            self.post_init(self._decode_copy, self._batch, self._backward)
+            self.post_init(self._decode_copy, self._batch, self._backward, self._low_bit)
         path = self.plan(T, top_k)["path"]
         if path == "decode":
             return int(_lib.load().gptq_moe_decode_workspace_bytes(ctypes.byref(self._moe), T, top_k or self.top_k))
@@ -228,7 +233,7 @@ class QuantMoEExperts(nn.Module):
     def backward_workspace_bytes(self, T: int, top_k: "int | None" = None) -> int:
         """Scratch of one gptq_moe_backward call with T tokens (0 when the experts have no grouped backward)."""
         if self._moe is None:
-            self.post_init(self._decode_copy, self._batch, self._backward)
+            self.post_init(self._decode_copy, self._batch, self._backward, self._low_bit)
         if self._grad_table is None:
             return 0
         return int(_lib.load().gptq_moe_backward_workspace_bytes(ctypes.byref(self._moe), T, top_k or self.top_k))
@@ -241,7 +246,7 @@ class QuantMoEExperts(nn.Module):
         if self[0].layers()[0].qweight.device.type != "cuda":
             return {"path": "per_expert", "reason": "cpu tensors"}
         if self._moe is None:
-            self.post_init(self._decode_copy, self._batch, self._backward)
+            self.post_init(self._decode_copy, self._batch, self._backward, self._low_bit)
         key = (T, top_k, self.batch_max_tokens)
         d = self._plans.get(key)
         if d is None:
@@ -348,7 +353,7 @@ def moe_forward(experts: QuantMoEExperts, x: torch.Tensor, top_k_index: torch.Te
 def _grouped_backward_ready(experts: QuantMoEExperts) -> bool:
     """The experts were post-initialised with backward=True and the backward plan took them (post_init runs here when the tables were invalidated)."""
     if experts._moe is None:
-        experts.post_init(experts._decode_copy, experts._batch, experts._backward)
+        experts.post_init(experts._decode_copy, experts._batch, experts._backward, experts._low_bit)
     return experts._grad_table is not None
 
 

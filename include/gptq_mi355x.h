@@ -361,10 +361,15 @@ int gptq_describe_adapter_rows_plan(const gptq_adapter_bank_t *const *banks, int
  * (a token with no valid expert gets 0).  Every W is gptq_dequant of its layer, bit for bit.  Grouped path: 4- or 8-bit fp16 / bf16 experts, group_size a
  * multiple of 32 (or >= K), plain or act-order with qweight_seq / perm (re-sequenced rows), H and I multiples of 64, no bias, no epilogue, E <= 256,
  * topk <= 8; all experts of one projection share K, N, bits, group_size, dtype and zero_mode, and gate / up share them too.  Anything else:
- * GPTQ_ERR_UNSUPPORTED with the reason (the caller composes the layer from per-expert gptq_forward calls instead). */
+ * GPTQ_ERR_UNSUPPORTED with the reason (the caller composes the layer from per-expert gptq_forward calls instead).
+ * flags: 0, or GPTQ_MOE_LOW_BIT: the grouped path (gptq_moe_build_table / gptq_moe_forward, gptq_moe_build_grad_table / gptq_moe_backward and their
+ * describe / workspace twins) also takes 2- and 3-bit experts -- same contract, same workspace; gate and up still share their width, down may have
+ * another (3-bit gate | up with 4-bit down is legal).  The decode and the batch path decline 2 / 3 bits whatever the flag says.  Unknown flag bits:
+ * GPTQ_ERR_UNSUPPORTED. */
+#define GPTQ_MOE_LOW_BIT 1
 typedef struct gptq_moe_t {
     int32_t E;
-    int32_t reserved;                  /* 0 */
+    int32_t flags;                     /* 0 | GPTQ_MOE_LOW_BIT (the field was `reserved`, 0, before: a zeroed struct means what it meant) */
     const gptq_layer_t *const *gate;   /* [E] */
     const gptq_layer_t *const *up;     /* [E] */
     const gptq_layer_t *const *down;   /* [E] */

@@ -40,6 +40,7 @@ EXPORTS = (
     "gptq_lora_down", "gptq_lora_up", "gptq_lora_apply", "gptq_describe_lora_plan",
     "gptq_lora_backward_workspace_bytes", "gptq_lora_backward", "gptq_describe_lora_backward_plan",
     "gptq_adapter_route_bytes", "gptq_adapter_route", "gptq_adapter_rows_apply", "gptq_describe_adapter_rows_plan",
+    "gptq_moe_router", "gptq_describe_moe_router_plan",
 )
 WS_HEADER_BYTES = 65536
 STRIP_COLS = 16          # GPTQ_STRIP_COLS: columns per strip of the decode copy (gptq_prepack_decode)
@@ -67,6 +68,7 @@ class GptqMoe(Structure):
 
 
 MOE_LOW_BIT = 1          # GPTQ_MOE_LOW_BIT: the grouped path (forward and backward) also takes 2- and 3-bit experts
+ROUTER_RENORM = 1        # GPTQ_ROUTER_RENORM: gptq_moe_router divides the selected probabilities by their sum
 
 
 LORA_MAX = 4             # GPTQ_LORA_MAX: adapters of one gptq_lora_* call
@@ -215,6 +217,8 @@ def load() -> ctypes.CDLL:
     lib.gptq_moe_backward.argtypes = [MP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_size_t, c_void_p]
     lib.gptq_describe_moe_backward_plan.argtypes = [MP, c_int, c_int, c_char_p, c_size_t]
+    lib.gptq_moe_router.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.gptq_describe_moe_router_plan.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int, c_char_p, c_size_t]
     RP = POINTER(POINTER(GptqLora))
     lib.gptq_lora_down.argtypes = [RP, c_int, c_void_p, POINTER(c_void_p), c_int, c_void_p]
     lib.gptq_lora_up.argtypes = [RP, c_int, POINTER(c_void_p), POINTER(c_void_p), c_int, c_void_p]
@@ -368,6 +372,19 @@ def describe_moe_batch_plan(moe: "GptqMoe", T: int, topk: int) -> dict:
     lib = load()
     buf = ctypes.create_string_buffer(512)
     check(lib.gptq_describe_moe_batch_plan(ctypes.byref(moe), T, topk, buf, len(buf)))
+    out = {}
+    for kv in buf.value.decode().split():
+        k, v = kv.split("=", 1)
+        out[k] = int(v) if v.lstrip("-").isdigit() else v
+    return out
+
+
+def describe_moe_router_plan(T: int, H: int, E: int, topk: int, dtype: int, flags: int = 0) -> dict:
+    """What gptq_moe_router would run for T tokens of width H over E experts (dtype: GPTQ_F16 / GPTQ_BF16 / GPTQ_F32): path=router with its row regime
+    (form=rows: one token per workgroup, form=tiles: 16 tokens per workgroup), grid and LDS bytes, or path=none with the reason (host-only query)."""
+    lib = load()
+    buf = ctypes.create_string_buffer(512)
+    check(lib.gptq_describe_moe_router_plan(T, H, E, topk, dtype, flags, buf, len(buf)))
     out = {}
     for kv in buf.value.decode().split():
         k, v = kv.split("=", 1)

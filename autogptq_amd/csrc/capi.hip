@@ -796,6 +796,47 @@ int gptq_grad_input(const gptq_layer_t* L, const void* dy, void* dx, int M, int 
     return GPTQ_OK;
 }
 
+// ---- the router of a routed layer (moe_router.hip) ----
+static int router_check(int T, int H, int E, int topk, int dtype, int flags) {
+    if (dtype == GPTQ_F32) return fail(GPTQ_ERR_UNSUPPORTED, "fp32 router: the router kernel takes fp16 / bf16");
+    if (dtype != GPTQ_F16 && dtype != GPTQ_BF16) return fail(GPTQ_ERR_UNSUPPORTED, "unknown dtype enum %d", dtype);
+    if (flags & ~GPTQ_ROUTER_RENORM) return fail(GPTQ_ERR_UNSUPPORTED, "unknown router flags 0x%x", flags);
+    if (E < 1 || E > 256) return fail(GPTQ_ERR_UNSUPPORTED, "E = %d experts: the router kernel takes 1..256", E);
+    if (topk < 1 || topk > 8 || topk > E) return fail(GPTQ_ERR_UNSUPPORTED, "topk = %d: the router kernel takes 1..min(E, 8) (E = %d)", topk, E);
+    if (H <= 0 || H % 64) return fail(GPTQ_ERR_UNSUPPORTED, "H = %d must be a positive multiple of 64", H);
+    if (T < 0) return fail(GPTQ_ERR_SHAPE, "T must be >= 0, got %d", T);
+    const RouterPlan pl = plan_moe_router(T, H, E, topk, dtype);
+    if (pl.lds_bytes > GPTQ_ROUTER_MAX_LDS) return fail(GPTQ_ERR_UNSUPPORTED, "H = %d: the staged row of x needs %zu bytes of LDS, more than %zu", H, pl.lds_bytes, GPTQ_ROUTER_MAX_LDS);
+    return GPTQ_OK;
+}
+
+int gptq_moe_router(const void* x, const void* w, int T, int H, int E, int topk, int dtype, int flags, void* logits_out, int64_t* topk_idx, float* topk_w,
+                    void* stream) {
+    if (!x || !w || !topk_idx || !topk_w) return fail(GPTQ_ERR_NULL, "x / w / topk_idx / topk_w must be non-NULL");
+    if (int rc = router_check(T, H, E, topk, dtype, flags)) return rc;
+    if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)logits_out | (uintptr_t)topk_idx | (uintptr_t)topk_w) & 15)
+        return fail(GPTQ_ERR_UNSUPPORTED, "x / w / logits_out / topk_idx / topk_w must be 16-byte aligned");
+    if (T == 0) return GPTQ_OK;
+    hipError_t e = launch_moe_router(x, w, T, H, E, topk, dtype, flags & GPTQ_ROUTER_RENORM, logits_out, topk_idx, topk_w, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "gptq_moe_router launch");
+    return GPTQ_OK;
+}
+
+int gptq_describe_moe_router_plan(int T, int H, int E, int topk, int dtype, int flags, char* out, size_t out_bytes) {
+    if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out is NULL");
+    if (router_check(T, H, E, topk, dtype, flags)) {
+        char reason[sizeof(g_err)];
+        snprintf(reason, sizeof(reason), "%s", g_err);
+        for (char* c = reason; *c; ++c)
+            if (*c == ' ' || *c == '=') *c = '_';
+        snprintf(out, out_bytes, "path=none reason=%s", reason);
+        return GPTQ_OK;
+    }
+    const RouterPlan pl = plan_moe_router(T, H, E, topk, dtype);
+    snprintf(out, out_bytes, "path=router form=%s wg=%ld waves=8 lds=%zu launches=1", pl.rows ? "rows" : "tiles", pl.wg, pl.lds_bytes);
+    return GPTQ_OK;
+}
+
 // ---- LoRA adapters (lora.hip) ----
 static int lora_check(const gptq_lora_t* const* Ls, int n) {
     if (!Ls) return fail(GPTQ_ERR_NULL, "loras is NULL");

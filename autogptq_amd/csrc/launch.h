@@ -239,6 +239,17 @@ struct LoraPlan {
 LoraPlan plan_lora(const gptq_lora_t* const* Ls, int n, int M);
 hipError_t launch_lora_down(const gptq_lora_t* const* Ls, int n, const void* x, void* const* u, int M, hipStream_t st);
 hipError_t launch_lora_up(const gptq_lora_t* const* Ls, int n, const void* const* u, void* const* outs, int M, hipStream_t st);
+// moe_router.hip: the router of a routed layer (gptq_moe_router): logits, softmax and top-k in one launch, no workspace
+constexpr int GPTQ_ROUTER_ROWS = 8;                 // up to here one token per workgroup (VALU), above 16 tokens per workgroup (matrix core)
+constexpr size_t GPTQ_ROUTER_MAX_LDS = 65536;       // dynamic LDS the kernel may ask for without a grant
+struct RouterPlan {
+    bool rows;
+    long wg;
+    size_t lds_bytes;
+};
+RouterPlan plan_moe_router(int T, int H, int E, int topk, int dtype);
+hipError_t launch_moe_router(const void* x, const void* w, int T, int H, int E, int topk, int dtype, int renorm, void* logits, int64_t* idx, float* wts,
+                             hipStream_t st);
 // adapter_grad.hip: the adapters' weight gradients dA = s du^T x and dB = s dY^T u (gptq_lora_backward): one launch over all jobs, one more to add the
 // M-slices where a job has more than one.  A job is one output [P][Q] with one of P, Q = r; slices are a function of (M, P, Q) alone.
 constexpr int GPTQ_WGRAD_JOBS = 2 * GPTQ_LORA_MAX;

@@ -9,6 +9,10 @@
                         (gptq_moe_decode_forward: two launches on streaming kernels, the expert chosen on the device, capturable), the batch
                         path for 5..64 tokens when opted in (gptq_moe_batch_forward: the grouped formulas on the decode copy, 16-row tiles of
                         one expert over the whole K, capturable), or the per-expert composition of differentiable ``QuantLinear`` calls
+* ``moe_route``         the router in front of the experts as ONE launch (gptq_moe_router: logits, softmax, top-k with a written tie rule and the
+                        optional renormalisation; dense fp16 / bf16 weight, no workspace, capturable); the torch composition for what it declines
+* ``inject_fused_router`` / ``remove_fused_router``   bind ``moe_route`` as the forward of a model's softmax-top-k routers (Mixtral, Qwen2-MoE, Qwen3-MoE), on
+                        the instances: classes, parameters, state-dict keys, hooks and transformers' output recorders stay as they are.  Opt-in.
 * ``pack_moe_experts``  pack the dense 3-D expert parameters of a model (``quantizers`` keyed ``...mlp.experts.{e}.w1`` as ``pack_model`` takes)
 
 The per-expert composition serves what the grouped kernels do not take (2- / 3-bit experts unless ``post_init(low_bit=True)``, fp32 experts, odd group
@@ -432,6 +436,126 @@ def _per_expert(experts: QuantMoEExperts, x: torch.Tensor, idx: torch.Tensor, w:
     return out.to(x.dtype)
 
 
+# ---------------------------------------------------------------------------------------------------------------- the router
+_ROUTER_PLANS: dict = {}
+ROUTER_CLASSES = {"MixtralTopKRouter": "mixtral", "Qwen2MoeTopKRouter": "qwen", "Qwen3MoeTopKRouter": "qwen"}      # matched by class name
+
+
+def router_plan(T: int, H: int, E: int, top_k: int, dtype: torch.dtype, renorm: bool = True) -> dict:
+    """{"path": "router" | "none", "form": "rows" | "tiles", "reason": ...} for one ``moe_route`` call on GPU tensors (host-only, cached)."""
+    key = (T, H, E, top_k, dtype, bool(renorm))
+    d = _ROUTER_PLANS.get(key)
+    if d is None:
+        enum = _lib.DTYPE_ENUM.get(dtype)
+        if enum is None:
+            d = {"path": "none", "reason": f"dtype {dtype}: the router kernel takes fp16 / bf16"}
+        else:
+            d = _lib.describe_moe_router_plan(T, H, E, top_k, enum, _lib.ROUTER_RENORM if renorm else 0)
+            d.setdefault("reason", "")
+            d["reason"] = str(d["reason"]).replace("_", " ")
+        _ROUTER_PLANS[key] = d
+    return dict(d)
+
+
+def _route_composition(x2, weight, top_k, renorm, return_logits):
+    """The routers of transformers, operation for operation (MixtralTopKRouter.forward; the Qwen routers up to their final cast)."""
+    logits = F.linear(x2, weight)
+    probs = F.softmax(logits, dim=-1, dtype=torch.float)
+    val, idx = torch.topk(probs, top_k, dim=-1)
+    if renorm:
+        val = val / val.sum(dim=-1, keepdim=True)
+    return (logits if return_logits else None), val, idx
+
+
+def moe_route(x: torch.Tensor, weight: torch.Tensor, top_k: int, renorm: bool = True, return_logits: bool = True):
+    """Router of a softmax-then-top-k mixture-of-experts layer: x [T, H] (or [..., H]), weight [E, H] -> (logits [T, E] in x's dtype or None, weights fp32
+    [T, top_k], indices int64 [T, top_k]).  On the GPU, without grad, for what the plan takes (fp16 / bf16, E <= 256, top_k <= min(E, 8), H % 64 == 0): ONE
+    gptq_moe_router call on the current stream -- the selection rule is written (descending logit, equal logits to the lower index), nothing is allocated
+    but the outputs, nothing synchronises, and a captured graph replays it.  Everything else runs the torch composition (``last_route_plan`` says why):
+    CPU tensors, what the plan declines, and calls under grad where ``x`` or ``weight`` require grad -- router training keeps autograd."""
+    global last_route_plan
+    E, H = weight.shape
+    x2 = x.reshape(-1, H)
+    T = x2.shape[0]
+    if x2.device.type != "cuda" or weight.device != x2.device:
+        plan = {"path": "none", "reason": "cpu tensors"}
+    elif torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad):
+        plan = {"path": "none", "reason": "grad enabled and x / weight require grad"}
+    elif x2.dtype != weight.dtype:
+        plan = {"path": "none", "reason": f"x is {x2.dtype}, weight {weight.dtype}"}
+    elif not weight.is_contiguous() or weight.data_ptr() & 15:
+        plan = {"path": "none", "reason": "weight must be contiguous and 16-byte aligned"}
+    else:
+        plan = router_plan(T, H, E, top_k, x2.dtype, renorm)
+    last_route_plan = plan
+    if plan["path"] != "router":
+        return _route_composition(x2, weight, top_k, renorm, return_logits)
+    dev = x2.device
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    if x2.data_ptr() & 15:                # a contiguous view at an odd element offset: the C ABI takes 16-byte aligned x
+        x2 = x2.clone()
+    logits = torch.empty((T, E), dtype=x2.dtype, device=dev) if return_logits else None
+    idx = torch.empty((T, top_k), dtype=torch.int64, device=dev)
+    w = torch.empty((T, top_k), dtype=torch.float32, device=dev)
+    if T:
+        with torch.cuda.device(dev.index):
+            rc = _lib.load().gptq_moe_router(x2.data_ptr(), weight.data_ptr(), T, H, E, top_k, _lib.DTYPE_ENUM[x2.dtype],
+                                             _lib.ROUTER_RENORM if renorm else 0, _lib.ptr(logits), idx.data_ptr(), w.data_ptr(), _raw_stream(dev.index))
+        if rc:
+            _lib.check(rc)
+    return logits, w, idx
+
+
+last_route_plan: dict = {}
+
+
+def _fused_router_forward(self, hidden_states):
+    """Bound on a router instance by inject_fused_router: the class's own triple (router_logits, router_scores, router_indices)."""
+    qwen = self._fused_router_kind == "qwen"
+    renorm = bool(getattr(self, "norm_topk_prob", True)) if qwen else True
+    logits, scores, idx = moe_route(hidden_states.reshape(-1, self.weight.shape[1]), self.weight, self.top_k, renorm=renorm, return_logits=True)
+    if qwen:
+        scores = scores.to(logits.dtype)
+    return logits, scores, idx
+
+
+def _router_kind(m: nn.Module):
+    kind = ROUTER_CLASSES.get(type(m).__name__)
+    w = getattr(m, "weight", None)
+    if kind is None or not torch.is_tensor(w) or w.dim() != 2 or not hasattr(m, "top_k") or getattr(m, "num_experts", None) != w.shape[0]:
+        return None
+    return kind
+
+
+def inject_fused_router(model: nn.Module) -> int:
+    """Give every MixtralTopKRouter / Qwen2MoeTopKRouter / Qwen3MoeTopKRouter of ``model`` (matched by class name, with ``weight [E, H]``, ``top_k`` and
+    ``num_experts``) a forward bound on the INSTANCE that calls ``moe_route``.  The module keeps its object, class and parameters, so state-dict keys,
+    hooks and transformers' ``OutputRecorder(<RouterClass>, index=0)`` (``output_router_logits=True``) keep working.  Mixtral: renormalised fp32 scores;
+    Qwen 2 / 3: renormalised iff ``norm_topk_prob``, scores cast to the logits dtype.  Routers of any other class (sigmoid, grouped) are left alone.
+    Returns the number of routers bound.  Nothing is injected by default."""
+    n = 0
+    for m in model.modules():
+        kind = _router_kind(m)
+        if kind is None:
+            continue
+        m.__dict__["_fused_router_kind"] = kind
+        m.__dict__["forward"] = types.MethodType(_fused_router_forward, m)
+        n += 1
+    return n
+
+
+def remove_fused_router(model: nn.Module) -> int:
+    """Undo inject_fused_router: the class forward is back on every router it bound.  Returns their number."""
+    n = 0
+    for m in model.modules():
+        if "_fused_router_kind" in m.__dict__:
+            m.__dict__.pop("forward", None)
+            del m.__dict__["_fused_router_kind"]
+            n += 1
+    return n
+
+
 def _is_dense_experts(m: nn.Module) -> bool:
     gu, dn = getattr(m, "gate_up_proj", None), getattr(m, "down_proj", None)
     return torch.is_tensor(gu) and torch.is_tensor(dn) and gu.dim() == 3 and dn.dim() == 3 and hasattr(m, "num_experts")
@@ -474,4 +598,5 @@ def pack_moe_experts(model: nn.Module, quantizers: dict, bits: int, group_size: 
         q._invalidate()
 
 
-__all__ = ["QuantMoEExperts", "moe_forward", "pack_moe_experts", "dense_expert_modules", "make_quant_experts"]
+__all__ = ["QuantMoEExperts", "moe_forward", "pack_moe_experts", "dense_expert_modules", "make_quant_experts", "moe_route", "router_plan",
+           "inject_fused_router", "remove_fused_router"]

@@ -19,6 +19,8 @@
  *       <- the expert loop of the reference's Mixtral (per-expert QuantLinears, auto_gptq/modeling/mixtral.py) as one routed, grouped call
  *   gptq_moe_decode_forward, gptq_moe_batch_forward
  *       <- the same expert loop at the row counts of token generation (1..4 tokens) and of batched generation (5..64), on the experts' decode copy
+ *   gptq_moe_router
+ *       <- the router in front of that loop (transformers' MixtralTopKRouter: F.linear, softmax, topk, renormalise) as one launch
  *   gptq_moe_backward
  *       <- autograd through the same expert loop (dequantise + torch.matmul per expert), as one routed, grouped call
  *   gptq_grad_input
@@ -474,6 +476,31 @@ int gptq_moe_backward(const gptq_moe_t *moe, const void *table, const void *grad
 /* Host-only: "path=grouped_backward tiles=3 launches=5 wg_recompute=... wg_down=... wg_up=..." or "path=per_expert reason=...", for (moe, T, topk).
  * GPTQ_OK either way (GPTQ_ERR_NULL for a NULL out). */
 int gptq_describe_moe_backward_plan(const gptq_moe_t *moe, int T, int topk, char *out, size_t out_bytes);
+
+/* The ROUTER in front of the routed layer (additive in ABI 8): logits, softmax and top-k of a softmax-then-top-k router (Mixtral, Qwen2-MoE, Qwen3-MoE) in
+ * ONE launch.  The router weight is not quantized (auto_gptq/modeling/mixtral.py lists only w1 / w2 / w3 and the attention projections): a dense kernel.
+ * For x [T, H] and w [E, H] in the layer dtype D (fp16 or bf16):
+ *   Logits.     l[t, e] = D(sum_k x[t, k] w[e, k]): fp32 products and sums in a fixed order, one rounding to D -- F.linear in D up to summation order.
+ *               Everything below is a function of these rounded logits alone.
+ *   Selection.  topk times, take the largest remaining logit; equal logits go to the LOWER expert index.  topk_idx [T, topk] (int64) is in that order:
+ *               descending logit, then ascending index (sorted=True).  -0 equals +0 and a NaN ranks above every number, as in torch.sort.  Indices are
+ *               always distinct and inside [0, E), whatever the input holds (NaN or Inf rows included).  These are the experts torch.topk on the fp32
+ *               probabilities picks, except where that call's own tie order is undefined (equal logits, or probabilities that round to the same fp32).
+ *   Weights.    p_e = exp(l_e - max_e l) / sum_e exp(l_e - max_e l) in fp32, fixed summation order; topk_w[t, j] = p_sel(j).  With GPTQ_ROUTER_RENORM,
+ *               topk_w[t, j] = p_sel(j) / sum_j p_sel(j), summed in ascending j.  fp32 [T, topk]: the layout gptq_moe_*forward takes.
+ *   logits_out  [T, E] in D, the rounded logits (the auxiliary loss and output_router_logits need them), or NULL.
+ * No workspace, no atomics, no exchange between workgroups: bit-reproducible and legal inside hipGraph capture.  A workgroup owns its tokens' whole rows
+ * of logits; softmax and selection run in its epilogue.  Two launch-uniform row regimes: 9+ tokens, 16 tokens x all experts per workgroup on
+ * v_mfma_f32_16x16x32 (8 waves split the k-steps and meet in LDS in wave order); 1..8 tokens, one token per workgroup (x staged in LDS, waves take experts
+ * round robin).  Within a regime a token's bits depend on nothing but its own row; the regimes sum in different orders.
+ * Takes D in {fp16, bf16} (the same for x and w), 1 <= E <= 256, 1 <= topk <= min(E, 8), H % 64 == 0 (and a staged row within 64 KiB of LDS), all pointers
+ * 16-byte aligned and contiguous.  Anything else: GPTQ_ERR_UNSUPPORTED with the reason, nothing launched.  Unknown flag bits: GPTQ_ERR_UNSUPPORTED.
+ * GPTQ_ERR_NULL for a NULL x / w / topk_idx / topk_w.  T = 0 launches nothing. */
+#define GPTQ_ROUTER_RENORM 1
+int gptq_moe_router(const void *x, const void *w, int T, int H, int E, int topk, int dtype, int flags, void *logits_out, int64_t *topk_idx, float *topk_w,
+                    void *stream);
+/* Host-only: "path=router form=rows|tiles wg=... waves=8 lds=... launches=1" or "path=none reason=...".  GPTQ_OK either way (GPTQ_ERR_NULL for a NULL out). */
+int gptq_describe_moe_router_plan(int T, int H, int E, int topk, int dtype, int flags, char *out, size_t out_bytes);
 
 /* Integer unpack (bit-exact targets). w_out uint8 [K,N]; z_out int32 [G,N] (zero-point as used). */
 int gptq_unpack_weights(const uint32_t *qweight, int K, int N, int bits, uint8_t *w_out, void *stream);

@@ -36,6 +36,7 @@ EXPORTS = (
     "gptq_moe_table_bytes", "gptq_moe_build_table", "gptq_moe_workspace_bytes", "gptq_moe_forward", "gptq_describe_moe_plan",
     "gptq_moe_decode_table_bytes", "gptq_moe_build_decode_table", "gptq_moe_decode_workspace_bytes", "gptq_moe_decode_forward", "gptq_describe_moe_decode_plan",
     "gptq_moe_batch_workspace_bytes", "gptq_moe_batch_forward", "gptq_describe_moe_batch_plan",
+    "gptq_moe_prefill_workspace_bytes", "gptq_moe_prefill_forward", "gptq_describe_moe_prefill_plan",
     "gptq_moe_grad_table_bytes", "gptq_moe_build_grad_table", "gptq_moe_backward_workspace_bytes", "gptq_moe_backward", "gptq_describe_moe_backward_plan",
     "gptq_lora_down", "gptq_lora_up", "gptq_lora_apply", "gptq_describe_lora_plan",
     "gptq_lora_backward_workspace_bytes", "gptq_lora_backward", "gptq_describe_lora_backward_plan",
@@ -209,6 +210,10 @@ def load() -> ctypes.CDLL:
     lib.gptq_moe_batch_workspace_bytes.argtypes = [MP, c_int, c_int]
     lib.gptq_moe_batch_forward.argtypes = lib.gptq_moe_forward.argtypes
     lib.gptq_describe_moe_batch_plan.argtypes = [MP, c_int, c_int, c_char_p, c_size_t]
+    lib.gptq_moe_prefill_workspace_bytes.restype = c_size_t
+    lib.gptq_moe_prefill_workspace_bytes.argtypes = [MP, c_int, c_int]
+    lib.gptq_moe_prefill_forward.argtypes = lib.gptq_moe_forward.argtypes
+    lib.gptq_describe_moe_prefill_plan.argtypes = [MP, c_int, c_int, c_char_p, c_size_t]
     lib.gptq_moe_grad_table_bytes.restype = c_size_t
     lib.gptq_moe_grad_table_bytes.argtypes = [c_int]
     lib.gptq_moe_build_grad_table.argtypes = [MP, c_void_p, c_void_p]
@@ -245,6 +250,7 @@ def load() -> ctypes.CDLL:
                         "gptq_workspace_bytes_max", "gptq_workspace_bytes_multi", "gptq_workspace_bytes_multi_ex",
                         "gptq_workspace_bytes_mlp", "gptq_workspace_bytes_mlp_ex", "gptq_moe_table_bytes", "gptq_moe_workspace_bytes",
                         "gptq_moe_decode_table_bytes", "gptq_moe_decode_workspace_bytes", "gptq_moe_batch_workspace_bytes",
+                        "gptq_moe_prefill_workspace_bytes",
                         "gptq_moe_grad_table_bytes", "gptq_moe_backward_workspace_bytes", "gptq_lora_backward_workspace_bytes"):
             getattr(lib, name).restype = c_int
     got = lib.gptq_abi_version()
@@ -372,6 +378,18 @@ def describe_moe_batch_plan(moe: "GptqMoe", T: int, topk: int) -> dict:
     lib = load()
     buf = ctypes.create_string_buffer(512)
     check(lib.gptq_describe_moe_batch_plan(ctypes.byref(moe), T, topk, buf, len(buf)))
+    out = {}
+    for kv in buf.value.decode().split():
+        k, v = kv.split("=", 1)
+        out[k] = int(v) if v.lstrip("-").isdigit() else v
+    return out
+
+
+def describe_moe_prefill_plan(moe: "GptqMoe", T: int, topk: int) -> dict:
+    """What gptq_moe_prefill_forward would run for (moe, T, topk): path=prefill with its tile geometry, or path=none with the reason (host-only query)."""
+    lib = load()
+    buf = ctypes.create_string_buffer(512)
+    check(lib.gptq_describe_moe_prefill_plan(ctypes.byref(moe), T, topk, buf, len(buf)))
     out = {}
     for kv in buf.value.decode().split():
         k, v = kv.split("=", 1)

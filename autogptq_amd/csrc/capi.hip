@@ -310,6 +310,7 @@ int gptq_init(void) {
     if (e == hipSuccess) e = init_gemm_panel_device();
     if (e == hipSuccess) e = init_moe_decode_device();
     if (e == hipSuccess) e = init_moe_batch_device();
+    if (e == hipSuccess) e = init_moe_prefill_device();
     if (e != hipSuccess) return hip_fail(e, "gptq_init (hipFuncSetAttribute)");
     return GPTQ_OK;
 }
@@ -1461,6 +1462,93 @@ int gptq_describe_moe_batch_plan(const gptq_moe_t* m, int T, int topk, char* out
     const MoeBatchPlan pl = plan_moe_batch(*m, T, topk);
     snprintf(out, out_bytes, "path=batch bm=%d s=%d tiles=%d launches=%d waves_pair=%d waves_down=%d lds_pair=%d lds_down=%d", pl.bm, pl.s, pl.tiles, pl.launches,
              pl.waves_pair, pl.waves_down, pl.lds_pair, pl.lds_down);
+    return GPTQ_OK;
+}
+
+// ---- the same layers at prompt row counts on the experts' decode copy (moe_panel.hip) ----
+static int moe_prefill_check_proj(const gptq_layer_t* const* Ls, int E, int K, int N, const gptq_layer_t* A, const char* name) {
+    if (!Ls) return fail(GPTQ_ERR_NULL, "moe->%s is NULL", name);
+    for (int e = 0; e < E; ++e) {
+        const gptq_layer_t* L = Ls[e];
+        if (int rc = check_layer(L)) return rc;
+        if (L->K != K || L->N != N)
+            return fail(GPTQ_ERR_SHAPE, "expert %d %s is [%d -> %d], expected [%d -> %d]", e, name, L->K, L->N, K, N);
+        if (L->bits != A->bits || L->group_size != Ls[0]->group_size || L->dtype != A->dtype || L->zero_mode != Ls[0]->zero_mode)
+            return fail(GPTQ_ERR_UNSUPPORTED, "the %s layers of all experts must share bits, group_size, dtype and zero_mode (expert %d differs)", name, e);
+        if (L->bias || L->epilogue != GPTQ_EPI_NONE)
+            return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s: the prefill path takes no bias and no epilogue", e, name);
+        if (!moe_prefill_group_ok(*L))
+            return fail(GPTQ_ERR_UNSUPPORTED, "group_size %d: the prefill path takes 64 times a power of two, or one group", L->group_size);
+        if (!L->qweight_tiled || !L->qconst_tiled)
+            return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s carries no decode copy (QuantMoEExperts.post_init(prefill=True) builds it)", e, name);
+        if (!tiled_layer_ok(*L))
+            return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s: raw act-order (no re-sequenced rows) is not taken by the decode copy", e, name);
+        if (((uintptr_t)L->qweight_tiled | (uintptr_t)L->qconst_tiled) & 15)
+            return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s: the decode copy must be 16-byte aligned", e, name);
+    }
+    return GPTQ_OK;
+}
+
+static int moe_prefill_check(const gptq_moe_t* m, int T, int topk) {
+    if (!m) return fail(GPTQ_ERR_NULL, "moe is NULL");
+    if (m->E < 1 || m->E > 256) return fail(GPTQ_ERR_UNSUPPORTED, "E = %d experts: the prefill path takes 1..256", m->E);
+    if (topk < 1 || topk > 8) return fail(GPTQ_ERR_UNSUPPORTED, "topk = %d: the prefill path takes 1..8", topk);
+    if (T < 0) return fail(GPTQ_ERR_SHAPE, "T must be >= 0, got %d", T);
+    if ((long)T * topk > GPTQ_MOE_PREFILL_MAX_ROWS)
+        return fail(GPTQ_ERR_UNSUPPORTED, "T topk = %ld rows: the prefill path takes up to %d (the grouped path serves more)", (long)T * topk, GPTQ_MOE_PREFILL_MAX_ROWS);
+    if (!m->gate || !m->up || !m->down || !m->gate[0]) return fail(GPTQ_ERR_NULL, "moe->gate / up / down must be non-NULL");
+    const gptq_layer_t* G = m->gate[0];
+    if (int rc = check_layer(G)) return rc;
+    if (G->dtype != GPTQ_F16 && G->dtype != GPTQ_BF16) return fail(GPTQ_ERR_UNSUPPORTED, "fp32 experts: the prefill path takes fp16 / bf16");
+    if (G->bits != 4 && G->bits != 8) return fail(GPTQ_ERR_UNSUPPORTED, "%d-bit experts: the prefill path takes 4 or 8 bits", G->bits);
+    const int H = G->K, I = G->N;
+    if (H % 128 || I % 128) return fail(GPTQ_ERR_UNSUPPORTED, "hidden (%d) and intermediate (%d) sizes must be multiples of 128", H, I);
+    if (int rc = moe_prefill_check_proj(m->gate, m->E, H, I, G, "gate")) return rc;
+    if (int rc = moe_prefill_check_proj(m->up, m->E, H, I, G, "up")) return rc;
+    const gptq_layer_t* U = m->up[0];
+    if (U->group_size != G->group_size || U->zero_mode != G->zero_mode)
+        return fail(GPTQ_ERR_UNSUPPORTED, "gate and up layers must share bits, group_size and zero_mode");
+    return moe_prefill_check_proj(m->down, m->E, I, H, G, "down");
+}
+
+size_t gptq_moe_prefill_workspace_bytes(const gptq_moe_t* m, int T, int topk) {
+    if (moe_prefill_check(m, T, topk)) return 0;
+    return plan_moe_prefill(*m, T, topk).bytes;
+}
+
+int gptq_moe_prefill_forward(const gptq_moe_t* m, const void* table, const void* x, const int64_t* idx, const float* w, int T, int topk, void* out, void* h_out,
+                             void* ws, size_t ws_bytes, void* stream) {
+    if (int rc = moe_prefill_check(m, T, topk)) return rc;
+    if (T == 0) return GPTQ_OK;
+    if (!table || !x || !idx || !w || !out) return fail(GPTQ_ERR_NULL, "table / x / topk_idx / topk_w / out must be non-NULL");
+    if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)ws) & 15) return fail(GPTQ_ERR_UNSUPPORTED, "x / out / workspace must be 16-byte aligned");
+    const MoePrefillPlan pl = plan_moe_prefill(*m, T, topk);
+    if (!ws || ws_bytes < pl.bytes) return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", pl.bytes, ws ? ws_bytes : (size_t)0);
+    hipError_t e = launch_moe_prefill(*m, table, pl, x, idx, w, T, topk, out, (char*)ws, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "gptq_moe_prefill_forward launch (was gptq_init() called on this device?)");
+    if (h_out) {
+        const gptq_layer_t* G = m->gate[0];
+        const size_t R = (size_t)T * topk, hb = R * G->N * dtype_size(G->dtype);
+        e = hipMemcpyAsync(h_out, (char*)ws + pl.off_h, hb, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+        if (e == hipSuccess) e = hipMemcpyAsync((char*)h_out + hb, (char*)ws + pl.off_pos, 4 * R, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+        if (e != hipSuccess) return hip_fail(e, "gptq_moe_prefill_forward h_out copy");
+    }
+    return GPTQ_OK;
+}
+
+int gptq_describe_moe_prefill_plan(const gptq_moe_t* m, int T, int topk, char* out, size_t out_bytes) {
+    if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out is NULL");
+    if (moe_prefill_check(m, T, topk)) {
+        char reason[sizeof(g_err)];
+        snprintf(reason, sizeof(reason), "%s", g_err);
+        for (char* c = reason; *c; ++c)
+            if (*c == ' ' || *c == '=') *c = '_';
+        snprintf(out, out_bytes, "path=none reason=%s", reason);
+        return GPTQ_OK;
+    }
+    const MoePrefillPlan pl = plan_moe_prefill(*m, T, topk);
+    snprintf(out, out_bytes, "path=prefill bm=%d launches=%d tiles=%d nt_pair=%d nt_down=%d waves=%d waves_pair=%d spw_pair=%d spw_down=%d lds=%d", pl.bm, pl.launches,
+             pl.tiles, pl.nt_pair, pl.nt_down, pl.waves_down, pl.waves_pair, pl.spw_pair, pl.spw_down, pl.lds_down);
     return GPTQ_OK;
 }
 

@@ -963,8 +963,7 @@ __global__ void __launch_bounds__(MT == 8 ? 512 : 1024, MT == 8 ? 2 : 4) gemv_mf
 
 // ---- second pass for ksplit > 1: out = sum_s partial[s] (+bias), fixed order ----------------
 template <typename T>
-__global__ void __launch_bounds__(256) gemv_reduce_kernel(const float* __restrict__ partial, const T* __restrict__ bias,
-                                                          T* __restrict__ out, int S, int M, int N) {
+__device__ __forceinline__ void gemv_reduce_body(const float* __restrict__ partial, const T* __restrict__ bias, T* __restrict__ out, int S, int M, int N) {
     const size_t total = (size_t)M * N;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         float s = 0.f;
@@ -972,6 +971,13 @@ __global__ void __launch_bounds__(256) gemv_reduce_kernel(const float* __restric
         if (bias) s += DType<T>::to_f32(bias[i % N]);
         out[i] = DType<T>::from_f32(s);
     }
+}
+// one code object for the three dtypes (a launch-uniform branch): the library keeps to its kernel count
+__global__ void __launch_bounds__(256) gemv_reduce_kernel(const float* __restrict__ partial, const void* __restrict__ bias, void* __restrict__ out, int S, int M, int N,
+                                                          int dtype) {
+    if (dtype == GPTQ_F16) gemv_reduce_body<f16>(partial, (const f16*)bias, (f16*)out, S, M, N);
+    else if (dtype == GPTQ_BF16) gemv_reduce_body<bf16>(partial, (const bf16*)bias, (bf16*)out, S, M, N);
+    else gemv_reduce_body<float>(partial, (const float*)bias, (float*)out, S, M, N);
 }
 
 // ---- host side: shape heuristic + dispatch ---------------------------------------------------
@@ -1633,16 +1639,7 @@ hipError_t launch_gemv(const gptq_layer_t& L, const GemvPlan& pl, const void* x,
         const size_t total = (size_t)M * L.N;
         int blocks = (int)((total + 255) / 256);
         if (blocks > 2048) blocks = 2048;
-        switch (L.dtype) {
-            case GPTQ_F16:
-                hipLaunchKernelGGL(gemv_reduce_kernel<f16>, dim3(blocks), dim3(256), 0, st, p.partial, (const f16*)L.bias, (f16*)out, pl.ksplit, M, L.N);
-                break;
-            case GPTQ_BF16:
-                hipLaunchKernelGGL(gemv_reduce_kernel<bf16>, dim3(blocks), dim3(256), 0, st, p.partial, (const bf16*)L.bias, (bf16*)out, pl.ksplit, M, L.N);
-                break;
-            default:
-                hipLaunchKernelGGL(gemv_reduce_kernel<float>, dim3(blocks), dim3(256), 0, st, p.partial, (const float*)L.bias, (float*)out, pl.ksplit, M, L.N);
-        }
+        hipLaunchKernelGGL(gemv_reduce_kernel, dim3(blocks), dim3(256), 0, st, (const float*)p.partial, (const void*)L.bias, out, pl.ksplit, M, L.N, (int)L.dtype);
         e = hipGetLastError();
     }
     return e;

@@ -230,6 +230,25 @@ MoeBatchPlan plan_moe_batch(const gptq_moe_t& m, int T, int topk);
 hipError_t launch_moe_batch(const gptq_moe_t& m, const void* table, const MoeBatchPlan& pl, const void* x, const int64_t* idx, const float* w, int T, int topk,
                             void* out, char* ws, hipStream_t st);
 hipError_t init_moe_batch_device();
+// ... and its row gather (moe_gather_rows_kernel) for the prefill path: out[plane][r] = in[src(r)] through the perm of expert e(r)'s entry of projection
+// `plane` of `table` (entries without a perm: a copy); src(r) = row_assign[r] / topk (topk > 0) or r (topk = 0).  R <= 65535 (a grid dimension).
+hipError_t launch_moe_gather_rows(const void* table, int planes, int topk, const int64_t* idx, const int* row_assign, const int* offsets, const void* in,
+                                  void* out, int E, int K, int R, hipStream_t st);
+// moe_panel.hip: the same layer at any token count on the experts' decode copy (gptq_moe_prefill_forward; Python: 65 tokens and more): route with 64-row
+// tiles, x into sorted order, gate|up + silu * mul, down, combine -- five launches (act-order down projections: + the gather of H_sorted through perm)
+constexpr int GPTQ_MOE_PREFILL_MAX_ROWS = 65535;    // T topk: the gather's grid
+struct MoePrefillPlan {
+    bool act_pair, act_down;                        // some gate / up (down) expert is act-order: two planes of x_sorted / the gather of H_sorted
+    int bm, tiles, launches;                        // tile height, tile bound
+    int nt_pair, nt_down;                           // 32-column blocks of I (of both W1 and W3) / of H per workgroup
+    int waves_pair, waves_down, spw_pair, spw_down, lds_pair, lds_down;
+    size_t off_offsets, off_tile_count, off_tiles, off_pos, off_rows, off_xs, off_h, off_y, off_hg, bytes;   // workspace layout (from GPTQ_WORKSPACE_HEADER_BYTES on)
+};
+bool moe_prefill_group_ok(const gptq_layer_t& L);  // 64 times a power of two, or one group
+MoePrefillPlan plan_moe_prefill(const gptq_moe_t& m, int T, int topk);
+hipError_t launch_moe_prefill(const gptq_moe_t& m, const void* table, const MoePrefillPlan& pl, const void* x, const int64_t* idx, const float* w, int T, int topk,
+                              void* out, char* ws, hipStream_t st);
+hipError_t init_moe_prefill_device();
 // lora.hip: the adapter branch out += scale * (x . A^T) . B^T for up to GPTQ_LORA_MAX adapters that share x: one down launch, one up launch
 constexpr int GPTQ_LORA_GEMV_ROWS = 8;              // up to here the VALU forms, above the matrix-core forms
 struct LoraPlan {

@@ -10,11 +10,17 @@ namespace gptq {
 namespace mlpk {
 
 template <typename T>
-__global__ void __launch_bounds__(256) silu_mul2_kernel(const T* __restrict__ g, const T* __restrict__ u, T* __restrict__ out, size_t total) {
+__device__ __forceinline__ void silu_mul2_body(const T* __restrict__ g, const T* __restrict__ u, T* __restrict__ out, size_t total) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const float a = DType<T>::to_f32(g[i]), b = DType<T>::to_f32(u[i]);
         out[i] = DType<T>::from_f32(a / (1.f + __expf(-a)) * b);
     }
+}
+// one code object for the three dtypes (a launch-uniform branch): the library keeps to its kernel count
+__global__ void __launch_bounds__(256) silu_mul2_kernel(const void* __restrict__ g, const void* __restrict__ u, void* __restrict__ out, size_t total, int dtype) {
+    if (dtype == GPTQ_F16) silu_mul2_body<f16>((const f16*)g, (const f16*)u, (f16*)out, total);
+    else if (dtype == GPTQ_BF16) silu_mul2_body<bf16>((const bf16*)g, (const bf16*)u, (bf16*)out, total);
+    else silu_mul2_body<float>((const float*)g, (const float*)u, (float*)out, total);
 }
 
 // SiLU * mul AND the x permute of an act-order `down` in ONE pass (round 6): out[m][i] = silu(g[m][perm[i]]) * u[m][perm[i]].  gptq_mlp_forward used to run the
@@ -88,11 +94,7 @@ hipError_t launch_silu_mul2(const void* g, const void* u, void* out, size_t tota
     int blocks = (int)((total + 255) / 256);
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
-    switch (dtype) {
-        case GPTQ_F16: hipLaunchKernelGGL(silu_mul2_kernel<f16>, dim3(blocks), dim3(256), 0, st, (const f16*)g, (const f16*)u, (f16*)out, total); break;
-        case GPTQ_BF16: hipLaunchKernelGGL(silu_mul2_kernel<bf16>, dim3(blocks), dim3(256), 0, st, (const bf16*)g, (const bf16*)u, (bf16*)out, total); break;
-        default: hipLaunchKernelGGL(silu_mul2_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)g, (const float*)u, (float*)out, total);
-    }
+    hipLaunchKernelGGL(silu_mul2_kernel, dim3(blocks), dim3(256), 0, st, g, u, out, total, dtype);
     return hipGetLastError();
 }
 

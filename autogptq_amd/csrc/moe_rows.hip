@@ -47,6 +47,7 @@
 #include "common.cuh"
 #include "launch.h"
 #include "gemm_rows_kernel.cuh"      // rowsk::Deq1<T> / Deq1_8<T>, rowsk::Mma16<T>
+#include "moe_entry.cuh"             // moerows::Entry, load_entry
 
 namespace gptq {
 namespace moerows {
@@ -56,13 +57,6 @@ constexpr int MAX_WAVES = 8;
 constexpr int BM = 16;
 constexpr int XB = 4096;                        // 16 rows x 128 k x 2 bytes
 constexpr int MAX_LDS = 160 * 1024;
-
-struct Entry {                                  // one (projection, expert) of the decode table (moe_decode.hip fills it): [3 projections][E], 32 bytes
-    const unsigned* tq;                         // qweight_tiled
-    const void* cst;                            // qconst_tiled
-    const int* perm;                            // NULL: sequential groups
-    const void* reserved;
-};
 
 struct Args {
     const Entry* table;                         // entries of the first projection (pair: W1; W3 is table + E)
@@ -76,15 +70,6 @@ struct Args {
     int K, N, chunks, groups, gshift, gm, cpw, nsg;
     void* out;                                  // pair: H_sorted [R][N] (T); down: Y [R][N] fp32
 };
-
-typedef unsigned u32x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ Entry load_entry(const Entry* p) {      // every lane loads the same 32 bytes; readfirstlane makes the pointers scalars
-    const u32x8 v = *(const u32x8*)p;
-    u32x8 o;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] = __builtin_amdgcn_readfirstlane(v[i]);
-    return __builtin_bit_cast(Entry, o);
-}
 
 // 4 bits: compiled for 128 registers (two 8-wave workgroups per CU); 8 bits: a ring slot is twice as large -- 256 registers, one workgroup per CU
 template <typename T, int BITS>
@@ -387,6 +372,16 @@ MoeBatchPlan plan_moe_batch(const gptq_moe_t& m, int T, int topk) {
     return pl;
 }
 
+hipError_t launch_moe_gather_rows(const void* table, int planes, int topk, const int64_t* idx, const int* row_assign, const int* offsets, const void* in,
+                                  void* out, int E, int K, int R, hipStream_t st) {
+    moerows::GatherArgs ga;
+    ga.table = (const moerows::Entry*)table; ga.idx = (const long long*)idx; ga.row_assign = row_assign; ga.offsets = offsets;
+    ga.in = (const unsigned short*)in; ga.out = (unsigned short*)out;
+    ga.E = E; ga.topk = topk; ga.K = K; ga.R = R;
+    hipLaunchKernelGGL(moerows::moe_gather_rows_kernel, dim3((K / 8 + 255) / 256, R, planes), dim3(256), 0, st, ga);
+    return hipGetLastError();
+}
+
 hipError_t launch_moe_batch(const gptq_moe_t& m, const void* table, const MoeBatchPlan& pl, const void* x, const int64_t* idx, const float* w, int T, int topk,
                             void* out, char* ws, hipStream_t st) {
     const gptq_layer_t& G = *m.gate[0];
@@ -402,12 +397,7 @@ hipError_t launch_moe_batch(const gptq_moe_t& m, const void* table, const MoeBat
 
     const moerows::Entry* const tab = (const moerows::Entry*)table;
     auto gather = [&](const moerows::Entry* t, int planes, int tk, const void* in, void* o, int K) -> hipError_t {
-        moerows::GatherArgs ga;
-        ga.table = t; ga.idx = (const long long*)idx; ga.row_assign = row_assign; ga.offsets = offsets;
-        ga.in = (const unsigned short*)in; ga.out = (unsigned short*)o;
-        ga.E = E; ga.topk = tk; ga.K = K; ga.R = R;
-        hipLaunchKernelGGL(moerows::moe_gather_rows_kernel, dim3((K / 8 + 255) / 256, R, planes), dim3(256), 0, st, ga);
-        return hipGetLastError();
+        return launch_moe_gather_rows(t, planes, tk, idx, row_assign, offsets, in, o, E, K, R, st);
     };
     auto fill = [&](moerows::Args& a, const gptq_layer_t& L, int cpw, int s) {
         a.E = E; a.topk = topk;

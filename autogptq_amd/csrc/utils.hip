@@ -358,13 +358,17 @@ __global__ void __launch_bounds__(256) prepack_decode_consts_kernel(const unsign
     else rec[32 + col] = (unsigned char)z;
 }
 
-template <typename T>
-__global__ void __launch_bounds__(256) permute_columns_kernel(const T* __restrict__ x, const int* __restrict__ perm, int M, int K,
-                                                              T* __restrict__ out) {
+// untyped: es = bytes per element (2 or 4, launch-uniform) -- one code object for the three dtypes
+__global__ void __launch_bounds__(256) permute_columns_kernel(const void* __restrict__ x, const int* __restrict__ perm, int M, int K, int es,
+                                                              void* __restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= K) return;
     const int src = perm[i];
-    for (int m = blockIdx.y; m < M; m += gridDim.y) out[(size_t)m * K + i] = x[(size_t)m * K + src];
+    if (es == 4) {
+        for (int m = blockIdx.y; m < M; m += gridDim.y) ((unsigned*)out)[(size_t)m * K + i] = ((const unsigned*)x)[(size_t)m * K + src];
+    } else {
+        for (int m = blockIdx.y; m < M; m += gridDim.y) ((unsigned short*)out)[(size_t)m * K + i] = ((const unsigned short*)x)[(size_t)m * K + src];
+    }
 }
 
 // out[m, n] = T( silu(y[m, n]) * y[m, n + N/2] ): the unfused form of the SILU_MUL epilogue (used after the GEMM paths
@@ -569,11 +573,7 @@ hipError_t launch_permute_columns(const void* x, const int32_t* perm, int M, int
     // one-thread-per-element gather below has K/256 x M workgroups instead (K = 28672, M = 1: ~7 us against ~2.5)
     if (dtype != GPTQ_F32 && K % 8 == 0 && (size_t)K * 2 <= 64 * 1024 && (M >= 64 || K <= 4096)) return launch_permute_rows16(x, perm, M, K, x_out, st);
     dim3 grid((K + 255) / 256, M < 1024 ? M : 1024), block(256);
-    if (dtype == GPTQ_F32)
-        hipLaunchKernelGGL(permute_columns_kernel<float>, grid, block, 0, st, (const float*)x, perm, M, K, (float*)x_out);
-    else
-        hipLaunchKernelGGL(permute_columns_kernel<unsigned short>, grid, block, 0, st, (const unsigned short*)x, perm, M, K,
-                           (unsigned short*)x_out);
+    hipLaunchKernelGGL(permute_columns_kernel, grid, block, 0, st, x, perm, M, K, dtype == GPTQ_F32 ? 4 : 2, x_out);
     return hipGetLastError();
 }
 

@@ -87,7 +87,8 @@ def pack_model(model: nn.Module, quantizers: dict, bits: int, group_size: int, d
 
 def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_length: Optional[int] = None,
                        release_checkpoint_layout: Optional[bool] = None, decode_copy: Optional[bool] = None,
-                       expert_decode_copy: bool = False, expert_batched_decode: bool = False, expert_backward: bool = False, expert_low_bit: bool = False) -> nn.Module:
+                       expert_decode_copy: bool = False, expert_batched_decode: bool = False, expert_backward: bool = False, expert_low_bit: bool = False,
+                       expert_prefill: bool = False) -> nn.Module:
     """post_init every mi355x layer and size the per-device scratch once (so forward never allocates; needed before hipGraph
     capture).  ``max_input_length`` bounds the rows M the scratch is sized for (default 2048, the reference's exllama default).
     Memory (the model-level switches for what post_init keeps next to the checkpoint tensors): ``decode_copy=False`` builds no decode copy (1x the packed
@@ -104,7 +105,9 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
     gptq_moe_backward call) instead of the per-expert composition; the scratch also covers ``gptq_moe_backward_workspace_bytes`` of ``max_input_length``
     tokens.  ``expert_low_bit=True`` (``QuantMoEExperts.post_init(low_bit=True)``): 2- and 3-bit experts run the grouped kernels (forward, and the backward
     with ``expert_backward=True``) instead of the per-expert composition, so ``capture_decode_step`` takes such a model; nothing changes for 4- and 8-bit
-    experts, and the expert decode copy keeps declining 2 / 3 bits."""
+    experts, and the expert decode copy keeps declining 2 / 3 bits.  ``expert_prefill=True`` (implies the expert decode copy;
+    ``QuantMoEExperts.post_init(prefill=True)``): calls of 65 tokens and more run the prefill kernels on that copy (64-row panels, one
+    gptq_moe_prefill_forward call) instead of the grouped path; the scratch covers ``gptq_moe_prefill_workspace_bytes`` of ``max_input_length`` tokens."""
     from .moe import QuantMoEExperts
     rows = max_input_length or 2048
     need: Dict[torch.device, int] = {}
@@ -114,13 +117,16 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
         # mixture-of-experts layers: their QuantLinears are post-initialised by the module (no decode copy; a checkpoint-layout release does not apply)
         if isinstance(sub, QuantMoEExperts) and sub[0].layers()[0].qweight.device.type == "cuda":
             dev = sub[0].layers()[0].qweight.device
-            sub.post_init(decode_copy=expert_decode_copy, batch=expert_batched_decode, backward=expert_backward, low_bit=expert_low_bit)
+            sub.post_init(decode_copy=expert_decode_copy, batch=expert_batched_decode, backward=expert_backward, low_bit=expert_low_bit,
+                          prefill=expert_prefill)
             for e in range(sub.num_experts):
                 in_experts.update(id(l) for l in sub[e].layers())
             expert_copy_bytes += sub.decode_copy_bytes
             ts = {rows, *range(1, min(rows, 4) + 1)}
             if expert_batched_decode:
                 ts.add(min(rows, sub.batch_max_tokens))          # the batch path's need grows with T: its largest T
+            if expert_prefill:
+                ts.add(min(rows, 64))                            # the prefill path starts at 65 tokens (its need grows with T: `rows`); below, the other paths' largest T
             need[dev] = max([need.get(dev, 0)] + [sub.workspace_bytes(t, sub.top_k) for t in sorted(ts)])
             if sub._grad_table is not None:
                 need[dev] = max(need[dev], sub.backward_workspace_bytes(rows, sub.top_k))

@@ -8,7 +8,9 @@
                         launches, no host round trip, capturable), the decode path for 1..4 tokens when the experts carry a decode copy
                         (gptq_moe_decode_forward: two launches on streaming kernels, the expert chosen on the device, capturable), the batch
                         path for 5..64 tokens when opted in (gptq_moe_batch_forward: the grouped formulas on the decode copy, 16-row tiles of
-                        one expert over the whole K, capturable), or the per-expert composition of differentiable ``QuantLinear`` calls
+                        one expert over the whole K, capturable), the prefill path for 65 tokens and more when opted in
+                        (gptq_moe_prefill_forward: the same formulas on the decode copy, 64-row panels of one expert over the whole K,
+                        capturable), or the per-expert composition of differentiable ``QuantLinear`` calls
 * ``moe_route``         the router in front of the experts as ONE launch (gptq_moe_router: logits, softmax, top-k with a written tie rule and the
                         optional renormalisation; dense fp16 / bf16 weight, no workspace, capturable); the torch composition for what it declines
 * ``inject_fused_router`` / ``remove_fused_router``   bind ``moe_route`` as the forward of a model's softmax-top-k routers (Mixtral, Qwen2-MoE, Qwen3-MoE), on
@@ -74,6 +76,7 @@ class QuantMoEExperts(nn.Module):
         self._batch = False
         self._backward = False
         self._low_bit = False
+        self._prefill = False
         self.batch_max_tokens = 64
         for e in range(num_experts):
             self.add_module(str(e), _Expert(self.names, bits, group_size, hidden_dim, intermediate_dim, weight_dtype, zero_mode))
@@ -90,6 +93,7 @@ class QuantMoEExperts(nn.Module):
         self._decode_table = None
         self._grad_table = None
         self._batch_ok = False
+        self._prefill_ok = False
         self.decode_copy_bytes = 0
         self._keep = ()
         self._plans = {}
@@ -110,7 +114,7 @@ class QuantMoEExperts(nn.Module):
         return [l[0] for l in ls], [l[1] for l in ls], [l[2] for l in ls]
 
     # ------------------------------------------------------------------ post_init
-    def post_init(self, decode_copy: bool = False, batch: bool = False, backward: bool = False, low_bit: bool = False):
+    def post_init(self, decode_copy: bool = False, batch: bool = False, backward: bool = False, low_bit: bool = False, prefill: bool = False):
         """post_init every expert layer and build the pointer table.  Default: WITHOUT a decode copy (1x the packed bytes; act-order layers add their
         re-sequenced rows) -- calls of any row count run the grouped kernels.  ``decode_copy=True``: the layers also get their decode copy (2x the packed
         bytes; both layouts stay resident: the grouped path still serves more than 4 tokens), the decode table is built, and calls of 1..4 tokens run the
@@ -121,23 +125,31 @@ class QuantMoEExperts(nn.Module):
         on a pointer table of its own) instead of the per-expert composition; experts the backward plan declines log the reason once and keep the
         composition.  ``low_bit=True`` (opt-in as well): 2- and 3-bit experts run the grouped kernels too (``plan(T)["path"] == "grouped"`` at every T, and
         ``backward=True`` yields their grouped backward) instead of the per-expert composition; it changes nothing for 4- and 8-bit experts, and the
-        decode and batch paths keep declining 2 / 3 bits.  ``decode_copy_bytes`` reports what the copies hold.  A checkpoint-layout release does not apply
-        to expert layers."""
+        decode and batch paths keep declining 2 / 3 bits.  ``prefill=True`` (opt-in as well; builds the decode copy and its table if not asked for already): calls of 65
+        tokens and more run the prefill kernels on the copy (``plan(T)["path"] == "prefill"``: 64-row panels of the routed rows, one
+        gptq_moe_prefill_forward call) instead of the grouped path; experts the prefill plan declines log the reason once and behave as without the
+        flag.  ``decode_copy_bytes`` reports what the copies hold.  A checkpoint-layout release does not apply to expert layers."""
         dev = self[0].layers()[0].qweight.device
         if dev.type != "cuda":
             raise RuntimeError(f"mi355x QuantMoEExperts.post_init needs the module on a ROCm GPU device (got {dev}); there is no CPU path.")
         want_decode, self._batch, self._backward, self._low_bit = bool(decode_copy), bool(batch), bool(backward), bool(low_bit)
+        self._prefill = bool(prefill)
+        if self._prefill:
+            why = self._prefill_declined()
+            if why:
+                logger.warning("QuantMoEExperts.post_init(prefill=True) has no effect for these experts (%s)", why)
+                self._prefill = False
         if self._batch:
             why = self._batch_declined()
             if why:
                 logger.warning("QuantMoEExperts.post_init(batch=True) has no effect for these experts (%s)", why)
                 self._batch = False
-        self._decode_copy = want_decode or self._batch
+        self._decode_copy = want_decode or self._batch or self._prefill
         if self._decode_copy:
             why = self._decode_copy_declined()
             if why:                                          # known from the metadata: no copy is built for a set the decode plan would decline
                 logger.warning("QuantMoEExperts.post_init(decode_copy=True) has no effect for these experts (%s): no decode copy is built", why)
-                self._decode_copy = self._batch = False
+                self._decode_copy = self._batch = self._prefill = False
         extra = 0
         for e in range(self.num_experts):
             for l in self[e].layers():
@@ -157,6 +169,7 @@ class QuantMoEExperts(nn.Module):
         self._decode_table = None
         self._grad_table = None
         self._batch_ok = False
+        self._prefill_ok = False
         self.decode_copy_bytes = extra
         self._dev = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
         self._w_dtype = gate[0].scales.dtype
@@ -179,16 +192,21 @@ class QuantMoEExperts(nn.Module):
                 # declined (2- / 3-bit, fp32, a group size the copy does not take, ...): nothing would read the copies -- say so and give their memory back
                 logger.warning("QuantMoEExperts.post_init(decode_copy=True) has no effect for these experts (%s): no decode copy is kept",
                                str(dplan.get("reason", "")).replace("_", " "))
-                return self.post_init(decode_copy=False, backward=self._backward, low_bit=self._low_bit)
+                return self.post_init(decode_copy=False, backward=self._backward, low_bit=self._low_bit)      # (batch and prefill need the copy: declined with it)
             bplan = _lib.describe_moe_batch_plan(m, 5, self.top_k) if self._batch else None
             if bplan is not None and bplan["path"] != "batch":
                 logger.warning("QuantMoEExperts.post_init(batch=True) has no effect for these experts (%s)", str(bplan.get("reason", "")).replace("_", " "))
-                return self.post_init(decode_copy=want_decode, backward=self._backward, low_bit=self._low_bit)
+                return self.post_init(decode_copy=want_decode, backward=self._backward, low_bit=self._low_bit, prefill=self._prefill)
+            pplan = _lib.describe_moe_prefill_plan(m, 65, self.top_k) if self._prefill else None
+            if pplan is not None and pplan["path"] != "prefill":
+                logger.warning("QuantMoEExperts.post_init(prefill=True) has no effect for these experts (%s)", str(pplan.get("reason", "")).replace("_", " "))
+                return self.post_init(decode_copy=want_decode, batch=self._batch, backward=self._backward, low_bit=self._low_bit)
             dtable = torch.zeros(max(1, int(lib.gptq_moe_decode_table_bytes(self.num_experts))), dtype=torch.uint8, device=dev)
             with torch.cuda.device(self._dev):
                 _lib.check(lib.gptq_moe_build_decode_table(ctypes.byref(m), dtable.data_ptr(), _lib.current_stream_handle(self._dev)))
             self._decode_table = dtable
             self._batch_ok = self._batch
+            self._prefill_ok = self._prefill
             self._plans = {}
         return self
 
@@ -203,6 +221,18 @@ class QuantMoEExperts(nn.Module):
             if not (gs in (32, 64) or gs >= K or (gs % 128 == 0 and q & (q - 1) == 0)):
                 return f"group_size {gs}: the batch path takes 32, 64, 128 times a power of two, or one group"
         return self._decode_copy_declined().replace("the decode path", "the batch path")
+
+    def _prefill_declined(self) -> str:
+        """Why the prefill plan would decline these experts, as far as the layer metadata says (empty: build the copies and ask the plan)."""
+        gate, _, down = self[0].layers()
+        if self.hidden_dim % 128 or self.intermediate_dim % 128:
+            return "hidden and intermediate sizes must be multiples of 128"
+        for l in (gate, down):
+            gs, K = l.group_size, l.infeatures
+            q = gs // 64
+            if not (gs >= K or (gs % 64 == 0 and q & (q - 1) == 0)):
+                return f"group_size {gs}: the prefill path takes 64 times a power of two, or one group"
+        return self._decode_copy_declined().replace("the decode path", "the prefill path")
 
     def _decode_copy_declined(self) -> str:
         """Why the decode plan would decline these experts, as far as the layer metadata says (empty: build the copies and ask the plan)."""
@@ -226,31 +256,34 @@ class QuantMoEExperts(nn.Module):
     def workspace_bytes(self, T: int, top_k: "int | None" = None) -> int:
         """Scratch of one call with T tokens on the path ``plan(T)`` names."""
         if self._moe is None:
-            self.post_init(self._decode_copy, self._batch, self._backward, self._low_bit)
+            self.post_init(self._decode_copy, self._batch, self._backward, self._low_bit, self._prefill)
         path = self.plan(T, top_k)["path"]
         if path == "decode":
             return int(_lib.load().gptq_moe_decode_workspace_bytes(ctypes.byref(self._moe), T, top_k or self.top_k))
         if path == "batch":
             return int(_lib.load().gptq_moe_batch_workspace_bytes(ctypes.byref(self._moe), T, top_k or self.top_k))
+        if path == "prefill":
+            return int(_lib.load().gptq_moe_prefill_workspace_bytes(ctypes.byref(self._moe), T, top_k or self.top_k))
         return int(_lib.load().gptq_moe_workspace_bytes(ctypes.byref(self._moe), T, top_k or self.top_k))
 
     def backward_workspace_bytes(self, T: int, top_k: "int | None" = None) -> int:
         """Scratch of one gptq_moe_backward call with T tokens (0 when the experts have no grouped backward)."""
         if self._moe is None:
-            self.post_init(self._decode_copy, self._batch, self._backward, self._low_bit)
+            self.post_init(self._decode_copy, self._batch, self._backward, self._low_bit, self._prefill)
         if self._grad_table is None:
             return 0
         return int(_lib.load().gptq_moe_backward_workspace_bytes(ctypes.byref(self._moe), T, top_k or self.top_k))
 
     def plan(self, T: int, top_k: "int | None" = None) -> dict:
-        """{"path": "decode" | "batch" | "grouped" | "per_expert", "reason": ...} (+ the launch / tile geometry) for T tokens: what moe_forward runs
+        """{"path": "decode" | "batch" | "prefill" | "grouped" | "per_expert", "reason": ...} (+ the launch / tile geometry) for T tokens: what moe_forward runs
         without grad.  "decode" only when the experts carry a decode copy (``post_init(decode_copy=True)``) and the decode plan accepts (1..4 tokens);
-        "batch" only after ``post_init(batch=True)``, for 5..``batch_max_tokens`` tokens; else the grouped path (or the composition)."""
+        "batch" only after ``post_init(batch=True)``, for 5..``batch_max_tokens`` tokens; "prefill" only after ``post_init(prefill=True)``, for 65 tokens
+        and more; else the grouped path (or the composition)."""
         top_k = top_k or self.top_k
         if self[0].layers()[0].qweight.device.type != "cuda":
             return {"path": "per_expert", "reason": "cpu tensors"}
         if self._moe is None:
-            self.post_init(self._decode_copy, self._batch, self._backward, self._low_bit)
+            self.post_init(self._decode_copy, self._batch, self._backward, self._low_bit, self._prefill)
         key = (T, top_k, self.batch_max_tokens)
         d = self._plans.get(key)
         if d is None:
@@ -261,6 +294,10 @@ class QuantMoEExperts(nn.Module):
             if d is None and self._batch_ok and self._decode_table is not None and 4 < T <= min(64, self.batch_max_tokens):
                 d = _lib.describe_moe_batch_plan(self._moe, T, top_k)
                 if d["path"] != "batch":
+                    d = None
+            if d is None and self._prefill_ok and self._decode_table is not None and T > 64:
+                d = _lib.describe_moe_prefill_plan(self._moe, T, top_k)
+                if d["path"] != "prefill":                       # (more than 65535 routed rows: the grouped path)
                     d = None
             if d is None:
                 d = _lib.describe_moe_plan(self._moe, T, top_k)
@@ -278,7 +315,8 @@ def moe_forward(experts: QuantMoEExperts, x: torch.Tensor, top_k_index: torch.Te
     """``experts(x, top_k_index, top_k_weights)``: x [T, H] (or [..., H]), top_k_index [T, topk] (int64 as torch.topk returns it), top_k_weights [T, topk].
     The grouped path: one gptq_moe_forward call (workspace from the per-stream scratch, nothing allocated but the output); the decode path (1..4 tokens
     on experts with a decode copy): one gptq_moe_decode_forward call, same conventions; the batch path (5..64 tokens, opted in): one
-    gptq_moe_batch_forward call, same conventions, rows grouped by expert as on the grouped path.  ``return_intermediate``: also (H [T topk, I], pos [T, topk] int32)
+    gptq_moe_batch_forward call, same conventions, rows grouped by expert as on the grouped path; the prefill path (65 tokens and more, opted in): one
+    gptq_moe_prefill_forward call, the same again.  ``return_intermediate``: also (H [T topk, I], pos [T, topk] int32)
     -- the kernel's silu * mul rows and the row of each assignment (-1: dropped); rows grouped by expert on the grouped path, in assignment order on the
     decode path: ``H[pos[t, j]]`` reads the same way on both."""
     H = experts.hidden_dim
@@ -298,9 +336,9 @@ def moe_forward(experts: QuantMoEExperts, x: torch.Tensor, top_k_index: torch.Te
     else:
         experts.last_plan = experts.plan(T, topk)
     path = experts.last_plan["path"]
-    if path not in ("grouped", "decode", "batch"):
+    if path not in ("grouped", "decode", "batch", "prefill"):
         if return_intermediate:
-            raise RuntimeError(f"moe_forward: return_intermediate needs the grouped, the batch or the decode path ({experts.last_plan['reason']})")
+            raise RuntimeError(f"moe_forward: return_intermediate needs the grouped, the batch, the prefill or the decode path ({experts.last_plan['reason']})")
         return _per_expert(experts, x2, top_k_index.reshape(T, topk), top_k_weights.reshape(T, topk)).reshape(lead + (H,))
     dev, w_dtype = experts._dev, experts._w_dtype
     if x.device != dev:
@@ -337,6 +375,8 @@ def moe_forward(experts: QuantMoEExperts, x: torch.Tensor, top_k_index: torch.Te
                 fn, table = lib.gptq_moe_decode_forward, experts._decode_table
             elif path == "batch":
                 fn, table = lib.gptq_moe_batch_forward, experts._decode_table
+            elif path == "prefill":
+                fn, table = lib.gptq_moe_prefill_forward, experts._decode_table
             else:
                 fn, table = lib.gptq_moe_forward, experts._table
             rc = fn(ctypes.byref(experts._moe), table.data_ptr(), xw.data_ptr(), idx.data_ptr(), w.data_ptr(), T, topk,
@@ -357,7 +397,7 @@ def moe_forward(experts: QuantMoEExperts, x: torch.Tensor, top_k_index: torch.Te
 def _grouped_backward_ready(experts: QuantMoEExperts) -> bool:
     """The experts were post-initialised with backward=True and the backward plan took them (post_init runs here when the tables were invalidated)."""
     if experts._moe is None:
-        experts.post_init(experts._decode_copy, experts._batch, experts._backward, experts._low_bit)
+        experts.post_init(experts._decode_copy, experts._batch, experts._backward, experts._low_bit, experts._prefill)
     return experts._grad_table is not None
 
 

@@ -17,7 +17,7 @@
  *       <- the `reconstruct` step of exllama / exllamav2              exllama/cuda_func/q4_matrix.cu:171-225, exllamav2/cuda/q_matrix.cu:158-279,452-500
  *   gptq_moe_forward
  *       <- the expert loop of the reference's Mixtral (per-expert QuantLinears, auto_gptq/modeling/mixtral.py) as one routed, grouped call
- *   gptq_moe_decode_forward, gptq_moe_batch_forward
+ *   gptq_moe_decode_forward, gptq_moe_batch_forward, gptq_moe_prefill_forward
  *       <- the same expert loop at the row counts of token generation (1..4 tokens) and of batched generation (5..64), on the experts' decode copy
  *   gptq_moe_router
  *       <- the router in front of that loop (transformers' MixtralTopKRouter: F.linear, softmax, topk, renormalise) as one launch
@@ -443,6 +443,32 @@ int gptq_moe_batch_forward(const gptq_moe_t *moe, const void *table, const void 
 /* Host-only: "path=batch bm=16 s=4 tiles=10 launches=4 waves_pair=8 waves_down=8 lds_pair=... lds_down=..." (s: strip-chunks per wave and chunk -- the pair
  * form runs 2 strips of W1 and of W3, the down form 4 of W2) or "path=none reason=..." (no decode copy, T > 64, 2- / 3-bit, fp32, ...).  GPTQ_OK either way. */
 int gptq_describe_moe_batch_plan(const gptq_moe_t *moe, int T, int topk, char *out, size_t out_bytes);
+
+/* PREFILL path of the routed layer (additive in ABI 8): the same formulas and arithmetic contract on the experts' DECODE COPY at ANY token count (the Python
+ * layer uses it from 65 tokens on), on kernels of the dense panel kind: a workgroup = one tile of up to 64 rows of one expert x a column tile x the whole K;
+ * its waves are K parts that meet once in LDS in wave order; no K slices, no atomics, nothing exchanged between workgroups -- bit-reproducible, and the row
+ * of token t does not depend on the other tokens of the call (the K split is a function of the layers alone).
+ *   Launches: routing (bm = 64), x into sorted order (act-order sets: through W1's and W3's perm, two planes), gate|up + silu * mul, down, combine: FIVE;
+ *   sets with act-order down projections add the gather of H_sorted through W2's perm (six).  No host round trip; the grid is a bound from (T, topk, E),
+ *   so a captured graph replays with new routing.
+ * Takes 4- and 8-bit fp16 / bf16 experts, plain or act-order, group_size 64 2^n or one group, H and I multiples of 128, E <= 256, topk <= 8,
+ * T topk <= 65535, no bias, every expert with its 16-byte aligned decode copy.  Anything else: GPTQ_ERR_UNSUPPORTED with the reason.
+ * `table` is the DECODE table (gptq_moe_build_decode_table).
+ * Workspace of one call:  GPTQ_WORKSPACE_HEADER_BYTES (left untouched)
+ *   + a256(4 (E + 1)) + 256 + a256(16 tiles) + 2 a256(4 T topk) + a256(planes T topk H sizeof(T)) + a256(T topk I sizeof(T)) + a256(4 T topk H)
+ *   [+ a256(T topk I sizeof(T)) for act-order down projections],
+ * a256 = round up to 256, tiles = floor(T topk / 64) + min(E, T topk), planes = 2 for act-order gate / up layers, else 1: offsets, tile count, tiles, pos,
+ * sorted rows, x_sorted, H_sorted, Y, gathered H.  0 when the call is declined. */
+size_t gptq_moe_prefill_workspace_bytes(const gptq_moe_t *moe, int T, int topk);
+/* Arguments and status codes as gptq_moe_batch_forward.  h_out (optional, for tests): H_sorted [T topk, I] (rows grouped by expert) followed by pos
+ * [T, topk] int32.  Caller's stream, no allocation, no synchronisation, legal inside hipGraph capture (gptq_init() first: the kernels need its LDS grant);
+ * T = 0 launches nothing. */
+int gptq_moe_prefill_forward(const gptq_moe_t *moe, const void *table, const void *x, const int64_t *topk_idx, const float *topk_w, int T, int topk, void *out,
+                             void *h_out, void *workspace, size_t workspace_bytes, void *stream);
+/* Host-only: "path=prefill bm=64 launches=5 tiles=72 nt_pair=2 nt_down=4 waves=8 waves_pair=8 spw_pair=8 spw_down=28 lds=131072" (nt: 32-column blocks per
+ * workgroup -- the pair form runs nt_pair blocks of W1 and of W3, the down form nt_down of W2; waves_pair = 4 for act-order gate / up layers; spw: 64-deep
+ * steps per wave) or "path=none reason=..." (no decode copy, 2- / 3-bit, fp32, 32-wide groups, ...).  GPTQ_OK either way. */
+int gptq_describe_moe_prefill_plan(const gptq_moe_t *moe, int T, int topk, char *out, size_t out_bytes);
 
 /* BACKWARD of the routed layer (additive in ABI 8): the gradients of gptq_moe_forward's formulas with respect to x and topk_w, from the packed weights.
  * Given dout [T, H] in the experts' dtype T, for every valid assignment r = (t, j) with expert e:

@@ -419,161 +419,202 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
     };
     auto seg_pin = [&]() __attribute__((always_inline)) { asm volatile("" : "+s"(N), "+s"(biasp), "+s"(outp)); };
     bool staged = false;
+    auto wload = [&](int c) __attribute__((always_inline)) -> qvec {              // chunk c of this wave's strip, clamped into the slice: [cb, ce)
+        return __builtin_nontemporal_load((const __attribute__((address_space(1))) qvec*)(tb + ((unsigned)min(c, ce - 1) * (unsigned)CHB + t_lane)));
+    };
+    auto first_pass = [&]() __attribute__((always_inline)) {                      // (uniform): the staging DMAs are OLDER than the U loads just issued
+        TILED_STAMP(1);
+        seg_request();
+#ifdef GPTQ_TILED_WEIGHTS_FIRST                                                    // lab (DESIGN.md 12): the DMAs BEHIND the first weight burst -- the staging barrier then waits for the first chunks too
+        stage_all();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#else
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(U) : "memory");
+#endif
+        if constexpr (ACT) {
+            __syncthreads();                                                  // the raw rows (every wave's DMAs) are in the LDS
+            x_gather();
+        }
+        __syncthreads();
+        if constexpr (XC) x_to_f16();
+        if constexpr (XS) x_sums();
+        seg_pin();
+        if (biasp != nullptr && tid < NE && n_t < (PAIR ? N >> 1 : N)) {
+            bv0 = DType<T>::to_f32(((const gT*)biasp)[n_t]);
+            if constexpr (PAIR) bv1 = DType<T>::to_f32(((const gT*)biasp)[n_t + (N >> 1)]);
+        }
+        TILED_STAMP(2);
+        staged = true;
+    };
+    auto chunk = [&](const int cj, const qvec qv) __attribute__((always_inline)) {      // decode chunk cj (dead: >= ce) from its words into acc[]
+        const int cc = min(cj, ce - 1);
+        const int k0 = cc * CKE + kb * KPL;                                   // first k of this lane's words
+        const bool live = (cj < ce) && (k0 < K);                          // a ragged last chunk: whole k-slots are missing
+        const int g = min(k0 >> LKPL >> gshift, G - 1);
+        const char* cp = cs + (NSTR > 1 ? (size_t)sel * cpad : (size_t)0) + g * REC;
+        const unsigned short sraw = *(const unsigned short*)(cp + col * 2);
+        unsigned z;
+        if constexpr (F::ZB == 1) z = *(const unsigned char*)(cp + 32 + col);
+        else z = *(const unsigned short*)(cp + 32 + col * 2);
+        u32x4 xa[NX];
+#pragma unroll
+        for (int w = 0; w < NX; ++w) xa[w] = *(const u32x4*)(xl + ((unsigned)(cc - cb) * (unsigned)(CKE * 2) + w * 16u));
+        u32x4 xb[MT > 4 ? NX : 1];
+        if constexpr (MT > 4) {
+#pragma unroll
+            for (int w = 0; w < NX; ++w) xb[w] = *(const u32x4*)(xl2 + ((unsigned)(cc - cb) * (unsigned)(CKE * 2) + w * 16u));
+        }
+        const f16x2 c1 = as_f16x2(z * 0x00010001u + 0xE400E400u);            // -(1024 + z)
+        f32x4 accg = {0.f, 0.f, 0.f, 0.f}, accg2 = {0.f, 0.f, 0.f, 0.f};
+        auto mm = [&](int pc, int hf, unsigned b0, unsigned b1) __attribute__((always_inline)) {      // 4 k of the lane's column against x piece pc, half hf: rows 0..3 (and 4..7)
+            accg = Mma4<MM>::run(u32x2{xa[pc][hf * 2], xa[pc][hf * 2 + 1]}, u32x2{b0, b1}, accg);
+            if constexpr (MT > 4) accg2 = Mma4<MM>::run(u32x2{xb[pc][hf * 2], xb[pc][hf * 2 + 1]}, u32x2{b0, b1}, accg2);
+        };
+        if constexpr (BITS == 4 && ZM) {
+            unsigned mgz;
+            asm("v_mov_b32 %0, %1" : "=v"(mgz) : "n"(BF ? 0x43004300 : 0x64006400));     // bias twice: bf16 128 / fp16 1024 (ulp 1 in either)
+            const unsigned nz = z * 0x00010001u + (BF ? 0xC300C300u : 0xE400E400u);     // -(bias + z) twice (z <= 16: exact)
+            f32x4 accz = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const unsigned qw = qv[w];
+                mm(w, 0, (qw & m_lo) | mgz, ((qw >> 4) & m_lo) | mgz);                  // (k0, k1) (k2, k3): stored nibbles 0 | 4, 1 | 5
+                mm(w, 1, ((qw >> 8) & m_lo) | mgz, ((qw >> 12) & m_lo) | mgz);          // (k4, k5) (k6, k7)
+                accz = Mma4<MM>::run(u32x2{xa[w][0], xa[w][1]}, u32x2{nz, nz}, accz);
+                accz = Mma4<MM>::run(u32x2{xa[w][2], xa[w][3]}, u32x2{nz, nz}, accz);
+            }
+            accg += accz;
+        } else if constexpr (BITS == 4 && XS) {
+            unsigned magicb;
+            asm("v_mov_b32 %0, 0x43004300" : "=v"(magicb));                   // bf16 128.0 twice: its 7 mantissa bits take a 4-bit field with an ulp of 1
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const unsigned qw = qv[w];
+                mm(w, 0, (qw & m_lo) | magicb, ((qw >> 4) & m_lo) | magicb);            // (k0, k1) (k2, k3): stored nibbles 0 | 4, 1 | 5
+                mm(w, 1, ((qw >> 8) & m_lo) | magicb, ((qw >> 12) & m_lo) | magicb);    // (k4, k5) (k6, k7)
+            }
+        } else if constexpr (BITS == 4) {
+            const f16x2 c2 = c1 + k960;                                       // -(64 + z)
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const unsigned qw = qv[w], q8 = qw >> 8;
+                const f16x2 h0 = as_f16x2((qw & m_lo) | magic) + c1;          // k0,k1  (stored nibbles 0 and 4)
+                const f16x2 h1 = as_f16x2((qw & m_hi) | magic) * r16 + c2;    // k2,k3  (1 and 5)
+                const f16x2 h2 = as_f16x2((q8 & m_lo) | magic) + c1;          // k4,k5  (2 and 6)
+                const f16x2 h3 = as_f16x2((q8 & m_hi) | magic) * r16 + c2;    // k6,k7  (3 and 7)
+                mm(w, 0, bits_of(h0), bits_of(h1));
+                mm(w, 1, bits_of(h2), bits_of(h3));
+            }
+        } else if constexpr (BITS == 2) {
+            // 16 fields per word: the fp16 mantissa takes the five pairs at bits 0..9 in place (1024 + 4^p w, times 4^-p, minus (1024 / 4^p + z): exact), the
+            // three at bits 10..15 come down by a shift first -- 17 VALU per 16 k
+            const f16x2 c4 = c1 + k768, c16 = c1 + k960, c64 = c1 + k1008, c256 = c1 + k1020;     // -(256 + z), -(64 + z), -(16 + z), -(4 + z)
+#pragma unroll
+            for (int w = 0; w < 2; ++w) {
+                const unsigned t = qv[w], t10 = t >> 10;
+                const unsigned p0 = bits_of(as_f16x2((t & m2a) | magic) + c1);
+                const unsigned p1 = bits_of(as_f16x2((t & m2b) | magic) * r4 + c4);
+                const unsigned p2 = bits_of(as_f16x2((t & m2c) | magic) * r16 + c16);
+                const unsigned p3 = bits_of(as_f16x2((t & m2d) | magic) * r64 + c64);
+                const unsigned p4 = bits_of(as_f16x2((t & m2e) | magic) * r256 + c256);
+                const unsigned p5 = bits_of(as_f16x2((t10 & m2a) | magic) + c1);
+                const unsigned p6 = bits_of(as_f16x2((t10 & m2b) | magic) * r4 + c4);
+                const unsigned p7 = bits_of(as_f16x2((t10 & m2c) | magic) * r16 + c16);
+                mm(2 * w, 0, p0, p1);
+                mm(2 * w, 1, p2, p3);
+                mm(2 * w + 1, 0, p4, p5);
+                mm(2 * w + 1, 1, p6, p7);
+            }
+        } else if constexpr (BITS == 8) {
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {                                     // one word = 4 k = one matrix-core step
+                const unsigned qw = qv[w], q8 = qw >> 8;
+                const f16x2 h0 = as_f16x2((qw & m_b) | magic) + c1;           // k0,k1  (stored bytes 0 and 2)
+                const f16x2 h1 = as_f16x2((q8 & m_b) | magic) + c1;           // k2,k3  (1 and 3)
+                mm(w >> 1, w & 1, bits_of(h0), bits_of(h1));
+            }
+        } else {
+            const f16x2 c3 = c1 + k896;                                       // -(128 + z): fields at bit 3, times 1/8
+            const f16x2 c6 = c1 + k1008;                                      // -(16 + z): fields at bit 6, times 1/64
+            unsigned pr[16];                                                  // the 16 k pairs of the unit, in k order
+#pragma unroll
+            for (int w = 0; w < 3; ++w) {
+                const unsigned t = qv[w], t6 = t >> 6;
+                pr[5 * w + 0] = bits_of(as_f16x2((t & m3a) | magic) + c1);
+                pr[5 * w + 1] = bits_of(as_f16x2((t & m3b) | magic) * r8 + c3);
+                pr[5 * w + 2] = bits_of(as_f16x2((t & m3c) | magic) * r64 + c6);
+                pr[5 * w + 3] = bits_of(as_f16x2((t6 & m3b) | magic) * r8 + c3);
+                pr[5 * w + 4] = bits_of(as_f16x2((t6 & m3c) | magic) * r64 + c6);
+            }
+            const unsigned e = ((qv[0] >> 15) & 0x00010001u) | ((qv[1] >> 14) & 0x00020002u) | ((qv[2] >> 13) & 0x00040004u);   // (k30 | k31 << 16): bits 15 / 31 of the three words
+            pr[15] = bits_of(as_f16x2(e | magic) + c1);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) mm(i >> 1, i & 1, pr[2 * i], pr[2 * i + 1]);
+        }
+        // the scale is pinned in front of the select on live (an empty asm: the value is read by every lane here).  Left to the compiler, the LDS read of a
+        // dead slot's scale is sunk under a branch on live -- s_and_saveexec, ds_read_u16, s_waitcnt lgkmcnt(0), one v_fma_mix -- behind the last matrix-core
+        // step of EVERY chunk: an exposed LDS round trip per chunk, and a block boundary the scheduler cannot move the next chunk's reads across
+        unsigned sr_ = sraw;
+        asm volatile("" : "+v"(sr_));
+        const float sc = DType<T>::to_f32(__builtin_bit_cast(T, (unsigned short)sr_));
+        if constexpr (XS) {
+            const float* const xv = xe + ((cc - cb) * 4 + kb) * 4;           // the run's sums of x, one per row
+            const float zc = (float)(128u + z);
+#pragma unroll
+            for (int m = 0; m < MT; ++m) acc[m] = live ? fmaf(sc, fmaf(-zc, xv[m], accg[m]), acc[m]) : acc[m];
+        } else if constexpr (XC) {
+            const float* const xi = xe + ((cc - cb) * 4 + kb) * 4;           // the run's inverse block factors, one per row
+#pragma unroll
+            for (int m = 0; m < MT; ++m) acc[m] = live ? fmaf(sc * xi[m], accg[m], acc[m]) : acc[m];
+        } else {
+#pragma unroll
+            for (int m = 0; m < MT; ++m) acc[m] = live ? fmaf(sc, m < 4 ? accg[m] : accg2[m - 4], acc[m]) : acc[m];   // a select, not a product by 0: a dead slot's x is whatever the LDS holds
+        }
+    };
+    // The K loop: a ROLLING refill.  The wave's first U chunks are requested in front of the staging barrier as before; from then on the load of
+    // chunk c0 + j + Wh U goes into q[j] as soon as q[j] has been decoded -- the same registers, no copy -- so U - 1 loads are in flight under every decode
+    // (the wait in front of chunk j is vmcnt(U - 1)) and the stream drains only in the wave's LAST pass, which is peeled: it requests nothing.  A wave leaves
+    // the loop on its own chunk count (wave-uniform; nothing behind the staging barrier synchronises the waves before the reduction).  Every address is
+    // min(c, ce - 1) of the wave's own strip: [cb, ce) as before.  The sched_barriers keep each refill where it is written: free to move, the loads gather at
+    // the top of the block, the registers are renamed (copies of registers whose load is in flight: a vmcnt(0) at loop entry) and the counted waits collapse.
+    // Same chunks, same sequence, same acc[]: bit-identical to the pass-at-a-time loop (lab: -DGPTQ_TILED_NO_ROLL, tools/ab_tiled.sh).
+#ifdef GPTQ_TILED_NO_ROLL
     for (int cbase = cb; cbase < ce; cbase += Wh * U) {
         const int c0 = cbase + wv * U;
         qvec q[U];
 #pragma unroll
-        for (int j = 0; j < U; ++j) q[j] = __builtin_nontemporal_load((const __attribute__((address_space(1))) qvec*)(tb + ((unsigned)min(c0 + j, ce - 1) * (unsigned)CHB + t_lane)));
-        if (!staged) {                                                            // first pass only (uniform): the staging DMAs are OLDER than the U loads just issued
-            TILED_STAMP(1);
-            seg_request();
-#ifdef GPTQ_TILED_WEIGHTS_FIRST                                                    // lab (DESIGN.md 12): the DMAs BEHIND the first weight burst -- the staging barrier then waits for the first chunks too
-            stage_all();
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(U) : "memory");
-#endif
-            if constexpr (ACT) {
-                __syncthreads();                                                  // the raw rows (every wave's DMAs) are in the LDS
-                x_gather();
-            }
-            __syncthreads();
-            if constexpr (XC) x_to_f16();
-            if constexpr (XS) x_sums();
-            seg_pin();
-            if (biasp != nullptr && tid < NE && n_t < (PAIR ? N >> 1 : N)) {
-                bv0 = DType<T>::to_f32(((const gT*)biasp)[n_t]);
-                if constexpr (PAIR) bv1 = DType<T>::to_f32(((const gT*)biasp)[n_t + (N >> 1)]);
-            }
-            TILED_STAMP(2);
-            staged = true;
-        }
+        for (int j = 0; j < U; ++j) q[j] = wload(c0 + j);
+        if (!staged) first_pass();
 #ifdef GPTQ_TILED_STAMPS
         if (cbase + Wh * U >= ce) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); TILED_STAMP(3); }      // the last pass's chunks have landed
 #endif
 #pragma unroll
-        for (int j = 0; j < U; ++j) {
-            const int cc = min(c0 + j, ce - 1);
-            const int k0 = cc * CKE + kb * KPL;                                   // first k of this lane's words
-            const bool live = (c0 + j < ce) && (k0 < K);                          // a ragged last chunk: whole k-slots are missing
-            const int g = min(k0 >> LKPL >> gshift, G - 1);
-            const char* cp = cs + (NSTR > 1 ? (size_t)sel * cpad : (size_t)0) + g * REC;
-            const unsigned short sraw = *(const unsigned short*)(cp + col * 2);
-            unsigned z;
-            if constexpr (F::ZB == 1) z = *(const unsigned char*)(cp + 32 + col);
-            else z = *(const unsigned short*)(cp + 32 + col * 2);
-            u32x4 xa[NX];
-#pragma unroll
-            for (int w = 0; w < NX; ++w) xa[w] = *(const u32x4*)(xl + ((unsigned)(cc - cb) * (unsigned)(CKE * 2) + w * 16u));
-            u32x4 xb[MT > 4 ? NX : 1];
-            if constexpr (MT > 4) {
-#pragma unroll
-                for (int w = 0; w < NX; ++w) xb[w] = *(const u32x4*)(xl2 + ((unsigned)(cc - cb) * (unsigned)(CKE * 2) + w * 16u));
-            }
-            const f16x2 c1 = as_f16x2(z * 0x00010001u + 0xE400E400u);            // -(1024 + z)
-            const qvec qv = q[j];
-            f32x4 accg = {0.f, 0.f, 0.f, 0.f}, accg2 = {0.f, 0.f, 0.f, 0.f};
-            auto mm = [&](int pc, int hf, unsigned b0, unsigned b1) __attribute__((always_inline)) {      // 4 k of the lane's column against x piece pc, half hf: rows 0..3 (and 4..7)
-                accg = Mma4<MM>::run(u32x2{xa[pc][hf * 2], xa[pc][hf * 2 + 1]}, u32x2{b0, b1}, accg);
-                if constexpr (MT > 4) accg2 = Mma4<MM>::run(u32x2{xb[pc][hf * 2], xb[pc][hf * 2 + 1]}, u32x2{b0, b1}, accg2);
-            };
-            if constexpr (BITS == 4 && ZM) {
-                unsigned mgz;
-                asm("v_mov_b32 %0, %1" : "=v"(mgz) : "n"(BF ? 0x43004300 : 0x64006400));     // bias twice: bf16 128 / fp16 1024 (ulp 1 in either)
-                const unsigned nz = z * 0x00010001u + (BF ? 0xC300C300u : 0xE400E400u);     // -(bias + z) twice (z <= 16: exact)
-                f32x4 accz = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    const unsigned qw = qv[w];
-                    mm(w, 0, (qw & m_lo) | mgz, ((qw >> 4) & m_lo) | mgz);                  // (k0, k1) (k2, k3): stored nibbles 0 | 4, 1 | 5
-                    mm(w, 1, ((qw >> 8) & m_lo) | mgz, ((qw >> 12) & m_lo) | mgz);          // (k4, k5) (k6, k7)
-                    accz = Mma4<MM>::run(u32x2{xa[w][0], xa[w][1]}, u32x2{nz, nz}, accz);
-                    accz = Mma4<MM>::run(u32x2{xa[w][2], xa[w][3]}, u32x2{nz, nz}, accz);
-                }
-                accg += accz;
-            } else if constexpr (BITS == 4 && XS) {
-                unsigned magicb;
-                asm("v_mov_b32 %0, 0x43004300" : "=v"(magicb));                   // bf16 128.0 twice: its 7 mantissa bits take a 4-bit field with an ulp of 1
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    const unsigned qw = qv[w];
-                    mm(w, 0, (qw & m_lo) | magicb, ((qw >> 4) & m_lo) | magicb);            // (k0, k1) (k2, k3): stored nibbles 0 | 4, 1 | 5
-                    mm(w, 1, ((qw >> 8) & m_lo) | magicb, ((qw >> 12) & m_lo) | magicb);    // (k4, k5) (k6, k7)
-                }
-            } else if constexpr (BITS == 4) {
-                const f16x2 c2 = c1 + k960;                                       // -(64 + z)
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    const unsigned qw = qv[w], q8 = qw >> 8;
-                    const f16x2 h0 = as_f16x2((qw & m_lo) | magic) + c1;          // k0,k1  (stored nibbles 0 and 4)
-                    const f16x2 h1 = as_f16x2((qw & m_hi) | magic) * r16 + c2;    // k2,k3  (1 and 5)
-                    const f16x2 h2 = as_f16x2((q8 & m_lo) | magic) + c1;          // k4,k5  (2 and 6)
-                    const f16x2 h3 = as_f16x2((q8 & m_hi) | magic) * r16 + c2;    // k6,k7  (3 and 7)
-                    mm(w, 0, bits_of(h0), bits_of(h1));
-                    mm(w, 1, bits_of(h2), bits_of(h3));
-                }
-            } else if constexpr (BITS == 2) {
-                // 16 fields per word: the fp16 mantissa takes the five pairs at bits 0..9 in place (1024 + 4^p w, times 4^-p, minus (1024 / 4^p + z): exact), the
-                // three at bits 10..15 come down by a shift first -- 17 VALU per 16 k
-                const f16x2 c4 = c1 + k768, c16 = c1 + k960, c64 = c1 + k1008, c256 = c1 + k1020;     // -(256 + z), -(64 + z), -(16 + z), -(4 + z)
-#pragma unroll
-                for (int w = 0; w < 2; ++w) {
-                    const unsigned t = qv[w], t10 = t >> 10;
-                    const unsigned p0 = bits_of(as_f16x2((t & m2a) | magic) + c1);
-                    const unsigned p1 = bits_of(as_f16x2((t & m2b) | magic) * r4 + c4);
-                    const unsigned p2 = bits_of(as_f16x2((t & m2c) | magic) * r16 + c16);
-                    const unsigned p3 = bits_of(as_f16x2((t & m2d) | magic) * r64 + c64);
-                    const unsigned p4 = bits_of(as_f16x2((t & m2e) | magic) * r256 + c256);
-                    const unsigned p5 = bits_of(as_f16x2((t10 & m2a) | magic) + c1);
-                    const unsigned p6 = bits_of(as_f16x2((t10 & m2b) | magic) * r4 + c4);
-                    const unsigned p7 = bits_of(as_f16x2((t10 & m2c) | magic) * r16 + c16);
-                    mm(2 * w, 0, p0, p1);
-                    mm(2 * w, 1, p2, p3);
-                    mm(2 * w + 1, 0, p4, p5);
-                    mm(2 * w + 1, 1, p6, p7);
-                }
-            } else if constexpr (BITS == 8) {
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {                                     // one word = 4 k = one matrix-core step
-                    const unsigned qw = qv[w], q8 = qw >> 8;
-                    const f16x2 h0 = as_f16x2((qw & m_b) | magic) + c1;           // k0,k1  (stored bytes 0 and 2)
-                    const f16x2 h1 = as_f16x2((q8 & m_b) | magic) + c1;           // k2,k3  (1 and 3)
-                    mm(w >> 1, w & 1, bits_of(h0), bits_of(h1));
-                }
-            } else {
-                const f16x2 c3 = c1 + k896;                                       // -(128 + z): fields at bit 3, times 1/8
-                const f16x2 c6 = c1 + k1008;                                      // -(16 + z): fields at bit 6, times 1/64
-                unsigned pr[16];                                                  // the 16 k pairs of the unit, in k order
-#pragma unroll
-                for (int w = 0; w < 3; ++w) {
-                    const unsigned t = qv[w], t6 = t >> 6;
-                    pr[5 * w + 0] = bits_of(as_f16x2((t & m3a) | magic) + c1);
-                    pr[5 * w + 1] = bits_of(as_f16x2((t & m3b) | magic) * r8 + c3);
-                    pr[5 * w + 2] = bits_of(as_f16x2((t & m3c) | magic) * r64 + c6);
-                    pr[5 * w + 3] = bits_of(as_f16x2((t6 & m3b) | magic) * r8 + c3);
-                    pr[5 * w + 4] = bits_of(as_f16x2((t6 & m3c) | magic) * r64 + c6);
-                }
-                const unsigned e = ((qv[0] >> 15) & 0x00010001u) | ((qv[1] >> 14) & 0x00020002u) | ((qv[2] >> 13) & 0x00040004u);   // (k30 | k31 << 16): bits 15 / 31 of the three words
-                pr[15] = bits_of(as_f16x2(e | magic) + c1);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) mm(i >> 1, i & 1, pr[2 * i], pr[2 * i + 1]);
-            }
-            const float sc = DType<T>::to_f32(__builtin_bit_cast(T, sraw));
-            if constexpr (XS) {
-                const float* const xv = xe + ((cc - cb) * 4 + kb) * 4;           // the run's sums of x, one per row
-                const float zc = (float)(128u + z);
-#pragma unroll
-                for (int m = 0; m < MT; ++m) acc[m] = live ? fmaf(sc, fmaf(-zc, xv[m], accg[m]), acc[m]) : acc[m];
-            } else if constexpr (XC) {
-                const float* const xi = xe + ((cc - cb) * 4 + kb) * 4;           // the run's inverse block factors, one per row
-#pragma unroll
-                for (int m = 0; m < MT; ++m) acc[m] = live ? fmaf(sc * xi[m], accg[m], acc[m]) : acc[m];
-            } else {
-#pragma unroll
-                for (int m = 0; m < MT; ++m) acc[m] = live ? fmaf(sc, m < 4 ? accg[m] : accg2[m - 4], acc[m]) : acc[m];   // a select, not a product by 0: a dead slot's x is whatever the LDS holds
-            }
-        }
+        for (int j = 0; j < U; ++j) chunk(c0 + j, q[j]);
     }
+#else
+    if (cb < ce) {                                                                // (an empty slice takes no staging barrier; the planner makes none)
+        int c0 = cb + wv * U;
+        qvec q[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) q[j] = wload(c0 + j);
+        first_pass();
+        for (int cn = c0 + Wh * U; cn < ce; cn += Wh * U) {                       // this wave has a live chunk in the next pass
+#pragma unroll
+            for (int j = 0; j < U; ++j) {
+                chunk(c0 + j, q[j]);
+                __builtin_amdgcn_sched_barrier(0);
+                q[j] = wload(cn + j);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            c0 = cn;
+        }
+#ifdef GPTQ_TILED_STAMPS
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); TILED_STAMP(3);          // the last pass's chunks have landed
+#endif
+#pragma unroll
+        for (int j = 0; j < U; ++j) chunk(c0 + j, q[j]);
+    }
+#endif
     TILED_STAMP(4);
     // ---- k-slots (two register swaps: a lane owns one column), waves (LDS), then write / publish ---------------------------------------------
 #pragma unroll

@@ -42,6 +42,7 @@ EXPORTS = (
     "gptq_lora_backward_workspace_bytes", "gptq_lora_backward", "gptq_describe_lora_backward_plan",
     "gptq_adapter_route_bytes", "gptq_adapter_route", "gptq_adapter_rows_apply", "gptq_describe_adapter_rows_plan",
     "gptq_moe_router", "gptq_describe_moe_router_plan",
+    "gptq_moe_shared_decode_workspace_bytes", "gptq_moe_shared_decode_forward", "gptq_describe_moe_shared_decode_plan", "gptq_moe_shared_combine",
 )
 WS_HEADER_BYTES = 65536
 STRIP_COLS = 16          # GPTQ_STRIP_COLS: columns per strip of the decode copy (gptq_prepack_decode)
@@ -66,6 +67,11 @@ class GptqTuning(Structure):
 class GptqMoe(Structure):
     """gptq_moe_t: E experts, each a gate / up / down layer (arrays of E layer pointers); flags: 0 (the default) or MOE_LOW_BIT."""
     _fields_ = [("E", c_int32), ("flags", c_int32), ("gate", c_void_p), ("up", c_void_p), ("down", c_void_p)]
+
+
+class GptqMoeShared(Structure):
+    """gptq_moe_shared_t: the shared expert of a Qwen-MoE block -- its gate / up / down layers (with decode copies) and the dense gate vector [H] (or NULL)."""
+    _fields_ = [("gate", c_void_p), ("up", c_void_p), ("down", c_void_p), ("gate_w", c_void_p), ("flags", c_int32), ("reserved", c_int32)]
 
 
 MOE_LOW_BIT = 1          # GPTQ_MOE_LOW_BIT: the grouped path (forward and backward) also takes 2- and 3-bit experts
@@ -224,6 +230,12 @@ def load() -> ctypes.CDLL:
     lib.gptq_describe_moe_backward_plan.argtypes = [MP, c_int, c_int, c_char_p, c_size_t]
     lib.gptq_moe_router.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.gptq_describe_moe_router_plan.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int, c_char_p, c_size_t]
+    SP = POINTER(GptqMoeShared)
+    lib.gptq_moe_shared_decode_workspace_bytes.restype = c_size_t
+    lib.gptq_moe_shared_decode_workspace_bytes.argtypes = [MP, SP, c_int, c_int]
+    lib.gptq_moe_shared_decode_forward.argtypes = [MP, SP, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.gptq_describe_moe_shared_decode_plan.argtypes = [MP, SP, c_int, c_int, c_char_p, c_size_t]
+    lib.gptq_moe_shared_combine.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]
     RP = POINTER(POINTER(GptqLora))
     lib.gptq_lora_down.argtypes = [RP, c_int, c_void_p, POINTER(c_void_p), c_int, c_void_p]
     lib.gptq_lora_up.argtypes = [RP, c_int, POINTER(c_void_p), POINTER(c_void_p), c_int, c_void_p]
@@ -251,7 +263,8 @@ def load() -> ctypes.CDLL:
                         "gptq_workspace_bytes_mlp", "gptq_workspace_bytes_mlp_ex", "gptq_moe_table_bytes", "gptq_moe_workspace_bytes",
                         "gptq_moe_decode_table_bytes", "gptq_moe_decode_workspace_bytes", "gptq_moe_batch_workspace_bytes",
                         "gptq_moe_prefill_workspace_bytes",
-                        "gptq_moe_grad_table_bytes", "gptq_moe_backward_workspace_bytes", "gptq_lora_backward_workspace_bytes"):
+                        "gptq_moe_grad_table_bytes", "gptq_moe_backward_workspace_bytes", "gptq_lora_backward_workspace_bytes",
+                        "gptq_moe_shared_decode_workspace_bytes"):
             getattr(lib, name).restype = c_int
     got = lib.gptq_abi_version()
     if got != ABI_VERSION:
@@ -366,6 +379,19 @@ def describe_moe_decode_plan(moe: "GptqMoe", T: int, topk: int) -> dict:
     lib = load()
     buf = ctypes.create_string_buffer(512)
     check(lib.gptq_describe_moe_decode_plan(ctypes.byref(moe), T, topk, buf, len(buf)))
+    out = {}
+    for kv in buf.value.decode().split():
+        k, v = kv.split("=", 1)
+        out[k] = int(v) if v.lstrip("-").isdigit() else v
+    return out
+
+
+def describe_moe_shared_decode_plan(moe: "GptqMoe", shared: "GptqMoeShared", T: int, topk: int) -> dict:
+    """What gptq_moe_shared_decode_forward would run for (moe, shared, T, topk): path=decode_shared with its launch geometry, or path=none with the reason
+    (host-only query)."""
+    lib = load()
+    buf = ctypes.create_string_buffer(512)
+    check(lib.gptq_describe_moe_shared_decode_plan(ctypes.byref(moe), ctypes.byref(shared), T, topk, buf, len(buf)))
     out = {}
     for kv in buf.value.decode().split():
         k, v = kv.split("=", 1)

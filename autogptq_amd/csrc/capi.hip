@@ -309,6 +309,7 @@ int gptq_init(void) {
     if (e == hipSuccess) e = init_gemm_rows_device();
     if (e == hipSuccess) e = init_gemm_panel_device();
     if (e == hipSuccess) e = init_moe_decode_device();
+    if (e == hipSuccess) e = init_moe_shared_device();
     if (e == hipSuccess) e = init_moe_batch_device();
     if (e == hipSuccess) e = init_moe_prefill_device();
     if (e != hipSuccess) return hip_fail(e, "gptq_init (hipFuncSetAttribute)");
@@ -1378,6 +1379,99 @@ int gptq_describe_moe_decode_plan(const gptq_moe_t* m, int T, int topk, char* ou
     const MoeDecodePlan pl = plan_moe_decode(*m, T, topk);
     snprintf(out, out_bytes, "path=decode launches=%d wg_pair=%d wg_down=%d waves_pair=%d waves_down=%d lds_pair=%d lds_down=%d", T > 0 ? 2 : 0, pl.wg_pair, pl.wg_down,
              pl.waves_pair, pl.waves_down, pl.lds_pair, pl.lds_down);
+    return GPTQ_OK;
+}
+
+// ---- the shared expert of a Qwen-MoE block next to the routed experts (moe_shared.hip) ----
+static int moe_shared_check_layer(const gptq_layer_t* L, int K, int N, const gptq_layer_t* R, const char* name, const char* routed) {
+    if (!L) return fail(GPTQ_ERR_NULL, "shared->%s is NULL", name);
+    if (int rc = check_layer(L)) return rc;
+    if (L->K != K || L->N != N) return fail(GPTQ_ERR_SHAPE, "shared %s is [%d -> %d], expected [%d -> %d]", name, L->K, L->N, K, N);
+    if (L->bits != R->bits)
+        return fail(GPTQ_ERR_UNSUPPORTED, "shared %s has %d bits, the routed %s layers %d: the shared decode form takes equal bits", name, L->bits, routed, R->bits);
+    if (L->dtype != R->dtype)
+        return fail(GPTQ_ERR_UNSUPPORTED, "shared %s has dtype %d, the routed %s layers dtype %d: the shared decode form takes equal dtypes", name, L->dtype, routed, R->dtype);
+    if (L->bias || L->epilogue != GPTQ_EPI_NONE) return fail(GPTQ_ERR_UNSUPPORTED, "shared %s: the decode path takes no bias and no epilogue", name);
+    if (!L->qweight_tiled || !L->qconst_tiled)
+        return fail(GPTQ_ERR_UNSUPPORTED, "shared %s carries no decode copy (QuantLinear.post_init builds it)", name);
+    if (!tiled_layer_ok(*L))
+        return fail(GPTQ_ERR_UNSUPPORTED, "shared %s: group_size %d (or raw act-order) is not taken by the decode copy", name, L->group_size);
+    return GPTQ_OK;
+}
+
+static int moe_shared_check(const gptq_moe_t* m, const gptq_moe_shared_t* sh, int T, int topk) {
+    if (int rc = moe_decode_check(m, T, topk)) return rc;
+    if (!sh) return fail(GPTQ_ERR_NULL, "shared is NULL");
+    if (sh->flags || sh->reserved) return fail(GPTQ_ERR_UNSUPPORTED, "shared->flags / reserved must be 0");
+    if (!sh->gate || !sh->up || !sh->down) return fail(GPTQ_ERR_NULL, "shared->gate / up / down must be non-NULL");
+    const gptq_layer_t* G = m->gate[0];
+    const gptq_layer_t* D = m->down[0];
+    const int H = G->K, Is = sh->gate->N;
+    if (Is <= 0 || Is % 64) return fail(GPTQ_ERR_UNSUPPORTED, "shared intermediate size %d: I_s %% 64 must be 0", Is);
+    if (int rc = moe_shared_check_layer(sh->gate, H, Is, G, "gate", "gate")) return rc;
+    if (int rc = moe_shared_check_layer(sh->up, H, Is, G, "up", "up")) return rc;
+    if (int rc = moe_shared_check_layer(sh->down, Is, H, D, "down", "down")) return rc;
+    if (sh->up->group_size != sh->gate->group_size) return fail(GPTQ_ERR_UNSUPPORTED, "shared gate and up must share their group_size");
+    if ((uintptr_t)sh->gate_w & 15) return fail(GPTQ_ERR_UNSUPPORTED, "shared->gate_w must be 16-byte aligned");
+    const MoeSharedPlan pl = plan_moe_shared_decode(*m, *sh, T, topk);
+    if (!pl.ok) return fail(GPTQ_ERR_UNSUPPORTED, "shared intermediate size %d: the staged rows and constants (%d / %d bytes) do not fit the LDS", Is, pl.lds_pair, pl.lds_down);
+    return GPTQ_OK;
+}
+
+size_t gptq_moe_shared_decode_workspace_bytes(const gptq_moe_t* m, const gptq_moe_shared_t* sh, int T, int topk) {
+    if (moe_shared_check(m, sh, T, topk)) return 0;
+    return plan_moe_shared_decode(*m, *sh, T, topk).bytes;
+}
+
+int gptq_moe_shared_decode_forward(const gptq_moe_t* m, const gptq_moe_shared_t* sh, const void* table, const void* x, const int64_t* idx, const float* w, int T,
+                                   int topk, void* out, void* h_out, void* ws, size_t ws_bytes, void* stream) {
+    if (int rc = moe_shared_check(m, sh, T, topk)) return rc;
+    if (T == 0) return GPTQ_OK;
+    if (!table || !x || !idx || !w || !out) return fail(GPTQ_ERR_NULL, "decode_table / x / topk_idx / topk_w / out must be non-NULL");
+    if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)ws) & 15) return fail(GPTQ_ERR_UNSUPPORTED, "x / out / workspace must be 16-byte aligned");
+    const MoeSharedPlan pl = plan_moe_shared_decode(*m, *sh, T, topk);
+    if (!ws || ws_bytes < pl.bytes) return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", pl.bytes, ws ? ws_bytes : (size_t)0);
+    hipError_t e = launch_moe_shared_decode(*m, *sh, table, pl, x, idx, w, T, topk, out, (char*)ws, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "gptq_moe_shared_decode_forward launch (was gptq_init() called on this device?)");
+    if (h_out) {
+        const gptq_layer_t* G = m->gate[0];
+        const size_t R = (size_t)T * topk, es = dtype_size(G->dtype), hb = R * G->N * es, sb = (size_t)T * sh->gate->N * es;
+        hipStream_t st = (hipStream_t)stream;
+        e = hipMemcpyAsync(h_out, (char*)ws + pl.off_h, hb, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync((char*)h_out + hb, (char*)ws + pl.off_pos, 4 * R, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync((char*)h_out + hb + 4 * R, (char*)ws + pl.off_hs, sb, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync((char*)h_out + hb + 4 * R + sb, (char*)ws + pl.off_s, 4 * (size_t)T, hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) return hip_fail(e, "gptq_moe_shared_decode_forward h_out copy");
+    }
+    return GPTQ_OK;
+}
+
+int gptq_describe_moe_shared_decode_plan(const gptq_moe_t* m, const gptq_moe_shared_t* sh, int T, int topk, char* out, size_t out_bytes) {
+    if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out is NULL");
+    if (moe_shared_check(m, sh, T, topk)) {
+        char reason[sizeof(g_err)];
+        snprintf(reason, sizeof(reason), "%s", g_err);
+        for (char* c = reason; *c; ++c)
+            if (*c == ' ' || *c == '=') *c = '_';
+        snprintf(out, out_bytes, "path=none reason=%s", reason);
+        return GPTQ_OK;
+    }
+    const MoeSharedPlan pl = plan_moe_shared_decode(*m, *sh, T, topk);
+    snprintf(out, out_bytes, "path=decode_shared launches=%d wg_pair=%d wg_down=%d waves_pair=%d waves_down=%d lds_pair=%d lds_down=%d", T > 0 ? 2 : 0, pl.wg_pair,
+             pl.wg_down, pl.waves_pair, pl.waves_down, pl.lds_pair, pl.lds_down);
+    return GPTQ_OK;
+}
+
+int gptq_moe_shared_combine(const void* x, const void* gate_w, const void* ys, void* out, int T, int H, int dtype, void* stream) {
+    if (dtype == GPTQ_F32) return fail(GPTQ_ERR_UNSUPPORTED, "fp32: the shared combine kernel takes fp16 / bf16");
+    if (dtype != GPTQ_F16 && dtype != GPTQ_BF16) return fail(GPTQ_ERR_UNSUPPORTED, "unknown dtype enum %d", dtype);
+    if (H <= 0 || H % 8) return fail(GPTQ_ERR_UNSUPPORTED, "H = %d must be a positive multiple of 8", H);
+    if (T < 0) return fail(GPTQ_ERR_SHAPE, "T must be >= 0, got %d", T);
+    if (T == 0) return GPTQ_OK;
+    if (!ys || !out || (gate_w && !x)) return fail(GPTQ_ERR_NULL, "x / ys / out must be non-NULL");
+    if (((uintptr_t)x | (uintptr_t)gate_w | (uintptr_t)ys | (uintptr_t)out) & 15) return fail(GPTQ_ERR_UNSUPPORTED, "x / gate_w / ys / out must be 16-byte aligned");
+    hipError_t e = launch_moe_shared_combine(x, gate_w, ys, out, T, H, dtype, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "gptq_moe_shared_combine launch");
     return GPTQ_OK;
 }
 

@@ -217,6 +217,20 @@ void moe_decode_table_entry(const gptq_layer_t& L, void* dst);
 hipError_t launch_moe_decode(const gptq_moe_t& m, const void* table, const MoeDecodePlan& pl, const void* x, const int64_t* idx, const float* w, int T, int topk,
                              void* out, char* ws, hipStream_t st);
 hipError_t init_moe_decode_device();
+// moe_shared.hip: the shared expert of a Qwen-MoE block -- the two decode launches in their shared form (gptq_moe_shared_decode_forward, 1..4 tokens), and
+// the any-T tail out += sigmoid(x . w_g) * ys in one launch (gptq_moe_shared_combine)
+struct MoeSharedPlan {
+    bool ok;                                        // both launches' staged rows and constants fit the LDS
+    bool act_pair_r, act_down_r, act_pair_s, act_down_s;      // act-order among the routed / the shared layers of either launch
+    int wg_pair, wg_down, waves_pair, waves_down, lds_pair, lds_down;      // workgroups that do work, waves per workgroup, dynamic LDS
+    int waves_down_r, waves_down_s, per_tok;        // the wave counts the routed / the shared down segment distributes its chunks over; grid rows per token for I_s
+    size_t off_h, off_pos, off_hs, off_s, bytes;    // workspace layout (from GPTQ_WORKSPACE_HEADER_BYTES on): the decode path's, then hs [T, I_s] and s [T] fp32
+};
+MoeSharedPlan plan_moe_shared_decode(const gptq_moe_t& m, const gptq_moe_shared_t& sh, int T, int topk);
+hipError_t launch_moe_shared_decode(const gptq_moe_t& m, const gptq_moe_shared_t& sh, const void* table, const MoeSharedPlan& pl, const void* x,
+                                    const int64_t* idx, const float* w, int T, int topk, void* out, char* ws, hipStream_t st);
+hipError_t launch_moe_shared_combine(const void* x, const void* gate_w, const void* ys, void* out, int T, int H, int dtype, hipStream_t st);
+hipError_t init_moe_shared_device();
 // moe_rows.hip: the same layer at 5..64 tokens on the experts' decode copy (gptq_moe_batch_forward): route, gate|up + silu * mul, down, combine -- four
 // launches (act-order experts: + one row gather through perm in front of either GEMM)
 struct MoeBatchPlan {

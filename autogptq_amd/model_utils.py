@@ -107,7 +107,8 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
     with ``expert_backward=True``) instead of the per-expert composition, so ``capture_decode_step`` takes such a model; nothing changes for 4- and 8-bit
     experts, and the expert decode copy keeps declining 2 / 3 bits.  ``expert_prefill=True`` (implies the expert decode copy;
     ``QuantMoEExperts.post_init(prefill=True)``): calls of 65 tokens and more run the prefill kernels on that copy (64-row panels, one
-    gptq_moe_prefill_forward call) instead of the grouped path; the scratch covers ``gptq_moe_prefill_workspace_bytes`` of ``max_input_length`` tokens."""
+    gptq_moe_prefill_forward call) instead of the grouped path; the scratch covers ``gptq_moe_prefill_workspace_bytes`` of ``max_input_length`` tokens.
+    Blocks bound by ``inject_shared_expert`` before this call: the scratch also covers ``gptq_moe_shared_decode_workspace_bytes`` of 1..4 tokens."""
     from .moe import QuantMoEExperts
     rows = max_input_length or 2048
     need: Dict[torch.device, int] = {}
@@ -149,6 +150,12 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
         else:
             b = int(lib.gptq_workspace_bytes_max(ctypes.byref(sub._layer), rows))
         need[dev] = max(need.get(dev, 0), b)
+    # blocks bound by inject_shared_expert BEFORE this call: the fused call's scratch (the decode path's, plus the shared expert's rows and gate scalars)
+    from .moe import injected_shared_blocks, shared_workspace_bytes
+    for experts, layers in injected_shared_blocks(model):
+        dev = layers[0].qweight.device
+        if dev.type == "cuda" and experts._moe is not None:
+            need[dev] = max([need.get(dev, 0)] + [shared_workspace_bytes(experts, layers, t, experts.top_k) for t in range(1, min(rows, 4) + 1)])
     if expert_copy_bytes:
         logger.info("mixture-of-experts layers: the decode copy of the experts holds %.2f GB next to their packed checkpoint tensors (2x the packed expert "
                     "bytes; 1..4 tokens run the decode kernels on it, more the grouped kernels on the checkpoint rows)", expert_copy_bytes / 1e9)

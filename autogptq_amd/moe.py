@@ -15,6 +15,10 @@
                         optional renormalisation; dense fp16 / bf16 weight, no workspace, capturable); the torch composition for what it declines
 * ``inject_fused_router`` / ``remove_fused_router``   bind ``moe_route`` as the forward of a model's softmax-top-k routers (Mixtral, Qwen2-MoE, Qwen3-MoE), on
                         the instances: classes, parameters, state-dict keys, hooks and transformers' output recorders stay as they are.  Opt-in.
+* ``moe_shared_forward``  a Qwen-MoE block's ``experts(x, idx, w) + sigmoid(shared_expert_gate(x)) * shared_expert(x)``: at 1..2 tokens (up to 4 on request) on experts with a decode
+                        copy ONE gptq_moe_shared_decode_forward call (the two decode launches in their shared form), else the experts on the path they
+                        plan, the shared MLP through ``mlp_forward`` and ONE gptq_moe_shared_combine launch for the linear / sigmoid / mul / add tail
+* ``inject_shared_expert`` / ``remove_shared_expert``   bind that as the forward of a model's ``Qwen2MoeSparseMoeBlock``s, on the instances.  Opt-in.
 * ``pack_moe_experts``  pack the dense 3-D expert parameters of a model (``quantizers`` keyed ``...mlp.experts.{e}.w1`` as ``pack_model`` takes)
 
 The per-expert composition serves what the grouped kernels do not take (2- / 3-bit experts unless ``post_init(low_bit=True)``, fp32 experts, odd group
@@ -34,7 +38,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .qlinear_mi355x import QuantLinear, _raw_stream, exchange_tick, forward_multi, reserve_workspace
+from .qlinear_mi355x import QuantLinear, _raw_stream, exchange_tick, forward_multi, mlp_forward, reserve_workspace
 
 logger = getLogger(__name__)
 
@@ -596,6 +600,224 @@ def remove_fused_router(model: nn.Module) -> int:
     return n
 
 
+# ---------------------------------------------------------------------------------------------------------------- the shared expert
+SHARED_BLOCK_CLASSES = ("Qwen2MoeSparseMoeBlock",)      # matched by class name
+# Up to this many tokens moe_shared_forward runs the fused call where the plan accepts; above, experts + mlp_forward + the combine launch.  The kernels take
+# 1..4; the default is where the fused call was measured the fastest form on A2.7B's block (profiles/moe_shared_ab.log: at 3 and 4 tokens launch 2's
+# workgroups walk the routed segments and the long shared one in sequence, and the combine form wins).  Per experts module:
+# ``experts.shared_decode_max_tokens = n``.
+SHARED_DECODE_MAX_TOKENS = 2
+
+
+def _shared_state(experts: QuantMoEExperts, shared_layers):
+    """(GptqMoeShared, key) for these experts and shared layers: the struct holds the layers' current gptq_layer_t (gate_w is set per call); cached on the
+    experts, so it dies with their tables, and keyed by the layer structs, so a shared layer that was re-initialised gets a new one."""
+    for l in shared_layers:
+        if l._layer is None:
+            l.post_init()
+    key = ("shared",) + tuple(id(l._layer) for l in shared_layers)
+    ent = experts._plans.get(key)
+    if ent is None:
+        sh = _lib.GptqMoeShared()
+        sh.gate, sh.up, sh.down = (ctypes.addressof(l._layer) for l in shared_layers)
+        ent = experts._plans[key] = (sh, tuple(l._layer for l in shared_layers))      # (the structs stay alive with the entry: their ids are not reused)
+    return ent[0], key
+
+
+def shared_plan(experts: QuantMoEExperts, shared_layers, T: int, top_k: "int | None" = None) -> dict:
+    """{"path": "decode_shared" | "none", "reason": ...} (+ the launch geometry): what the fused call of ``moe_shared_forward`` would run for T tokens
+    (host-only; "none" also when the experts themselves do not plan the decode path at T)."""
+    top_k = top_k or experts.top_k
+    if experts.plan(T, top_k)["path"] != "decode":
+        return {"path": "none", "reason": "the routed experts do not run the decode path at this token count"}
+    sh, key = _shared_state(experts, shared_layers)
+    d = experts._plans.get(key + (T, top_k))
+    if d is None:
+        sh.gate_w = None
+        d = _lib.describe_moe_shared_decode_plan(experts._moe, sh, T, top_k)
+        d.setdefault("reason", "")
+        d["reason"] = str(d["reason"]).replace("_", " ")
+        experts._plans[key + (T, top_k)] = d
+    return dict(d)
+
+
+def shared_workspace_bytes(experts: QuantMoEExperts, shared_layers, T: int, top_k: "int | None" = None) -> int:
+    """Scratch of one fused call with T tokens (0 when ``shared_plan`` declines)."""
+    top_k = top_k or experts.top_k
+    if shared_plan(experts, shared_layers, T, top_k)["path"] != "decode_shared":
+        return 0
+    sh, _ = _shared_state(experts, shared_layers)
+    sh.gate_w = None
+    return int(_lib.load().gptq_moe_shared_decode_workspace_bytes(ctypes.byref(experts._moe), ctypes.byref(sh), T, top_k))
+
+
+def moe_shared_forward(experts: QuantMoEExperts, shared_layers, gate_weight: torch.Tensor, x: torch.Tensor, top_k_index: torch.Tensor,
+                       top_k_weights: torch.Tensor, return_intermediate: bool = False):
+    """A Qwen-MoE block behind its router: ``experts(x, idx, w) + sigmoid(x @ gate_weight.T) * down(silu(gate(x)) * up(x))`` with
+    ``shared_layers = (gate, up, down)`` QuantLinears [H -> I_s], [H -> I_s], [I_s -> H] and ``gate_weight`` the dense [1, H] (or [H]) weight of
+    ``shared_expert_gate``, read in place.  ``experts.last_plan["shared"]`` says what ran:
+
+    * ``"decode"``   without grad, on the GPU, when ``experts.plan(T)["path"] == "decode"`` (experts with a decode copy), ``shared_plan`` accepts and
+                     T <= ``experts.shared_decode_max_tokens`` (default SHARED_DECODE_MAX_TOKENS = 2; the kernels take up to 4): ONE
+                     gptq_moe_shared_decode_forward call -- two launches for the whole block behind the router
+    * ``"combine"``  every other call without grad on the GPU: ``experts`` on the path it plans, the shared MLP through ``mlp_forward``, then ONE
+                     gptq_moe_shared_combine launch (gate dot product, sigmoid, mul and add, in place on the routed output)
+    * ``"torch"``    calls under grad where x, the routing weights or ``gate_weight`` require grad, CPU tensors, and a ``gate_weight`` the kernels do not
+                     take (another dtype than the experts', not contiguous, not 16-byte aligned): the plain torch formula of the block
+
+    ``return_intermediate`` (the fused call only): also (H [T topk, I], pos [T, topk] int32, Hs [T, I_s], s [T] fp32) -- the kernel's silu * mul rows of the
+    routed and the shared expert and the gate scalars.  Workspace comes from the per-stream scratch, as ``moe_forward`` takes it."""
+    gate, up, down = shared_layers
+    H = experts.hidden_dim
+    lead = x.shape[:-1]
+    x2 = x.reshape(-1, H)
+    T = x2.shape[0]
+    topk = top_k_index.shape[-1] if top_k_index.dim() else 1
+    why = ""
+    if x.device.type != "cuda":
+        why = "cpu tensors"
+    elif torch.is_grad_enabled() and (x.requires_grad or top_k_weights.requires_grad or gate_weight.requires_grad):
+        why = "grad enabled and hidden_states / top_k_weights / gate_weight require grad"
+    else:
+        w_dtype = gate.scales.dtype
+        if gate_weight.dtype != w_dtype or gate_weight.device != x.device:
+            why = f"gate_weight is {gate_weight.dtype} on {gate_weight.device}, the shared layers {w_dtype} on {x.device}"
+        elif w_dtype not in (torch.float16, torch.bfloat16) or H % 8:
+            why = "the shared combine kernel takes fp16 / bf16 and H % 8 == 0"
+        elif gate_weight.numel() != H or not gate_weight.is_contiguous() or gate_weight.data_ptr() & 15:
+            why = "gate_weight must be [1, H], contiguous and 16-byte aligned"
+    if why:
+        if return_intermediate:
+            raise RuntimeError(f"moe_shared_forward: return_intermediate needs the fused decode call ({why})")
+        routed = experts(x2, top_k_index.reshape(T, topk), top_k_weights.reshape(T, topk))
+        shared = down(F.silu(gate(x2)) * up(x2))
+        out = routed + torch.sigmoid(F.linear(x2, gate_weight.reshape(1, H))) * shared
+        experts.last_plan = dict(experts.last_plan or {}, shared="torch", shared_reason=why)
+        return out.reshape(lead + (H,))
+    xw = _aligned(x2, w_dtype)
+    fused = 0 < T <= min(4, experts.__dict__.get("shared_decode_max_tokens", SHARED_DECODE_MAX_TOKENS)) and \
+        shared_plan(experts, shared_layers, T, topk)["path"] == "decode_shared"
+    if not fused:
+        if return_intermediate:
+            raise RuntimeError("moe_shared_forward: return_intermediate needs the fused decode call "
+                               f"({shared_plan(experts, shared_layers, T, topk).get('reason', '') if T else 'no tokens'})")
+        out = moe_forward(experts, xw, top_k_index, top_k_weights)
+        out = out.reshape(T, H)
+        if out.dtype != w_dtype or not out.is_contiguous() or out.data_ptr() & 15 or out.data_ptr() == xw.data_ptr():
+            out = out.to(w_dtype).clone()
+        if T:
+            ys = _aligned(mlp_forward(gate, up, down, xw), w_dtype)
+            with torch.cuda.device(xw.device.index):
+                rc = _lib.load().gptq_moe_shared_combine(xw.data_ptr(), gate_weight.data_ptr(), ys.data_ptr(), out.data_ptr(), T, H, _lib.DTYPE_ENUM[w_dtype],
+                                                         _raw_stream(xw.device.index))
+            if rc:
+                _lib.check(rc)
+        experts.last_plan = dict(experts.last_plan or {}, shared="combine")
+        res = out.to(x.dtype) if x.dtype != w_dtype else out
+        return res.reshape(lead + (H,))
+    dev = experts._dev
+    if x.device != dev:
+        raise RuntimeError(f"mi355x moe_shared_forward: input is on {x.device}, the experts on {dev}")
+    idx = top_k_index.reshape(T, topk)
+    if idx.dtype != torch.int64:
+        idx = idx.to(torch.int64)
+    idx = idx.contiguous()
+    w = top_k_weights.reshape(T, topk)
+    if w.dtype != torch.float32:
+        w = w.to(torch.float32)
+    w = w.contiguous()
+    sh, key = _shared_state(experts, shared_layers)
+    out = torch.empty((T, H), dtype=w_dtype, device=dev)
+    R, I, Is = T * topk, experts.intermediate_dim, gate.outfeatures
+    es = out.element_size()
+    h_out = torch.empty(R * I * es + 4 * R + T * Is * es + 4 * T, dtype=torch.uint8, device=dev) if return_intermediate else None
+    need = experts._plans.get(key + ("ws", T, topk))
+    if need is None:
+        need = experts._plans[key + ("ws", T, topk)] = shared_workspace_bytes(experts, shared_layers, T, topk)
+    buf = reserve_workspace(dev, need)
+    exchange_tick(dev)
+    sh.gate_w = gate_weight.data_ptr()
+    with torch.cuda.device(dev.index):
+        rc = _lib.load().gptq_moe_shared_decode_forward(ctypes.byref(experts._moe), ctypes.byref(sh), experts._decode_table.data_ptr(), xw.data_ptr(),
+                                                        idx.data_ptr(), w.data_ptr(), T, topk, out.data_ptr(), _lib.ptr(h_out), buf.data_ptr(), buf.numel(),
+                                                        _raw_stream(dev.index))
+    if rc:
+        _lib.check(rc)
+    experts.last_plan = dict(experts.plan(T, topk), shared="decode")
+    res = out.to(x.dtype) if x.dtype != w_dtype else out
+    res = res.reshape(lead + (H,))
+    if not return_intermediate:
+        return res
+    o1, o2, o3 = R * I * es, R * I * es + 4 * R, R * I * es + 4 * R + T * Is * es
+    return (res, h_out[:o1].view(w_dtype).view(R, I), h_out[o1:o2].view(torch.int32).view(T, topk), h_out[o2:o3].view(w_dtype).view(T, Is),
+            h_out[o3:].view(torch.float32))
+
+
+def _shared_block_forward(self, hidden_states):
+    """Bound on a block instance by inject_shared_expert: the class's own result (the router is called as before, so a fused router composes)."""
+    shape = hidden_states.shape
+    x = hidden_states.reshape(-1, shape[-1])
+    _, routing_weights, selected_experts = self.gate(x)
+    se = self.shared_expert
+    out = moe_shared_forward(self.experts, (se.gate_proj, se.up_proj, se.down_proj), self.shared_expert_gate.weight, x, selected_experts, routing_weights)
+    return out.reshape(shape)
+
+
+def _shared_block_parts(m: nn.Module):
+    """(experts, (gate, up, down)) of a block inject_shared_expert takes, or None."""
+    if type(m).__name__ not in SHARED_BLOCK_CLASSES:
+        return None
+    experts, se, sg = getattr(m, "experts", None), getattr(m, "shared_expert", None), getattr(m, "shared_expert_gate", None)
+    if not isinstance(experts, QuantMoEExperts) or se is None or not hasattr(m, "gate"):
+        return None
+    layers = tuple(getattr(se, nm, None) for nm in ("gate_proj", "up_proj", "down_proj"))
+    if not all(isinstance(l, QuantLinear) for l in layers):
+        return None
+    if not isinstance(sg, nn.Linear) or sg.bias is not None or sg.out_features != 1 or sg.in_features != experts.hidden_dim:
+        return None
+    return experts, layers
+
+
+def inject_shared_expert(model: nn.Module) -> int:
+    """Give every ``Qwen2MoeSparseMoeBlock`` of ``model`` (matched by class name; ``experts`` a QuantMoEExperts, ``shared_expert.{gate_proj, up_proj,
+    down_proj}`` QuantLinears, ``shared_expert_gate`` a bias-free Linear(H, 1)) a forward bound on the INSTANCE that calls ``moe_shared_forward``.  The block
+    keeps its object, class, parameters, state-dict keys and hooks; it calls ``self.gate(...)`` as before, so ``inject_fused_router`` composes;
+    ``shared_expert_gate.weight`` is read in place at every call, so a later ``.to()`` is seen.  (Forward hooks on the children: ``shared_expert`` and
+    ``shared_expert_gate`` are never called as modules; ``experts`` and the three shared QuantLinears only on the ``"torch"`` path.)  Order: inject, then
+    ``autogptq_post_init(model, expert_decode_copy=True)`` -- its scratch then covers the fused call -- then ``capture_decode_step``.  Returns the number of
+    blocks bound.  Nothing is injected by default."""
+    n = 0
+    for m in model.modules():
+        if _shared_block_parts(m) is None:
+            continue
+        m.__dict__["_shared_expert_injected"] = True
+        m.__dict__["forward"] = types.MethodType(_shared_block_forward, m)
+        n += 1
+    return n
+
+
+def remove_shared_expert(model: nn.Module) -> int:
+    """Undo inject_shared_expert: the class forward is back on every block it bound.  Returns their number."""
+    n = 0
+    for m in model.modules():
+        if "_shared_expert_injected" in m.__dict__:
+            m.__dict__.pop("forward", None)
+            del m.__dict__["_shared_expert_injected"]
+            n += 1
+    return n
+
+
+def injected_shared_blocks(model: nn.Module):
+    """[(experts, (gate, up, down))] of the blocks inject_shared_expert has bound (autogptq_post_init sizes the scratch of their fused call)."""
+    out = []
+    for m in model.modules():
+        if "_shared_expert_injected" in m.__dict__:
+            parts = _shared_block_parts(m)
+            if parts is not None:
+                out.append(parts)
+    return out
+
+
 def _is_dense_experts(m: nn.Module) -> bool:
     gu, dn = getattr(m, "gate_up_proj", None), getattr(m, "down_proj", None)
     return torch.is_tensor(gu) and torch.is_tensor(dn) and gu.dim() == 3 and dn.dim() == 3 and hasattr(m, "num_experts")
@@ -639,4 +861,5 @@ def pack_moe_experts(model: nn.Module, quantizers: dict, bits: int, group_size: 
 
 
 __all__ = ["QuantMoEExperts", "moe_forward", "pack_moe_experts", "dense_expert_modules", "make_quant_experts", "moe_route", "router_plan",
-           "inject_fused_router", "remove_fused_router"]
+           "inject_fused_router", "remove_fused_router", "moe_shared_forward", "shared_plan", "shared_workspace_bytes", "inject_shared_expert",
+           "remove_shared_expert"]

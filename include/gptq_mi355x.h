@@ -21,6 +21,9 @@
  *       <- the same expert loop at the row counts of token generation (1..4 tokens) and of batched generation (5..64), on the experts' decode copy
  *   gptq_moe_router
  *       <- the router in front of that loop (transformers' MixtralTopKRouter: F.linear, softmax, topk, renormalise) as one launch
+ *   gptq_moe_shared_decode_forward, gptq_moe_shared_combine
+ *       <- the shared expert next to that loop (transformers' Qwen2MoeSparseMoeBlock: + sigmoid(shared_expert_gate(x)) * shared_expert(x)), inside the two
+ *          decode launches at 1..4 tokens, and its linear / sigmoid / mul / add tail as one launch at any token count
  *   gptq_moe_backward
  *       <- autograd through the same expert loop (dequantise + torch.matmul per expert), as one routed, grouped call
  *   gptq_grad_input
@@ -420,6 +423,47 @@ int gptq_moe_decode_forward(const gptq_moe_t *moe, const void *table, const void
 /* Host-only: "path=decode launches=2 wg_pair=1792 wg_down=256 waves_pair=8 waves_down=16 lds_pair=... lds_down=..." (workgroups, waves per workgroup and
  * dynamic LDS bytes of the two launches) or "path=none reason=..." (experts without a decode copy, T > 4, 2- / 3-bit, fp32, topk > 8, ...).  GPTQ_OK either way. */
 int gptq_describe_moe_decode_plan(const gptq_moe_t *moe, int T, int topk, char *out, size_t out_bytes);
+
+/* The SHARED EXPERT of a Qwen-MoE block next to its routed experts (additive in ABI 8; transformers' Qwen2MoeSparseMoeBlock.forward):
+ *   out[t] = T( sum_j topk_w[t, j] (h_(t,j) . W2_e)  +  s_t (hs_t . W2_s) ),   hs_t = T(silu(x_t . W1_s) * (x_t . W3_s)),   s_t = sigmoid(l_t),
+ *   l_t = T(sum_k x_t[k] w_g[k]): fp32 products and sums in an order that depends on H alone (the router kernel's: lane l of one wave takes the 16-byte
+ *   pieces l, l + 64, .. in ascending order, then a butterfly), rounded ONCE to the layer dtype as gptq_moe_router rounds its logits; the sigmoid is
+ *   1 / (1 + exp(-l_t)) in fp32.  gate_w == NULL: s_t = 1 (the DeepSeek form of a shared expert).
+ * gate / up are [H -> I_s], down is [I_s -> H]; every token takes them.
+ *
+ * gptq_moe_shared_decode_forward, T <= 4: the TWO launches of gptq_moe_decode_forward in their shared form, with that call's arithmetic contract (w - z
+ * exact, products exact in fp32, per-run fp32 sums on the matrix core, the scale applied to the sum, W never rounded; no atomics, no K slices;
+ * bit-reproducible, row t independent of the other tokens, capturable).
+ *   launch 1  the routed grid plus, per token, ceil(I_s / I) grid rows of I / 16 workgroups: row q, column c serves strip q (I / 16) + c of I_s (strips
+ *             past I_s / 16 leave at once); the shared workgroup of strip 0 also writes s_t from the row of x it has staged.
+ *   launch 2  grid (H / 16, T) as before; behind the token's topk routed assignments (ascending j) the workgroup adds s_t (hs_t . W2_s) to the same fp32
+ *             register and rounds once.  The routed terms are summed exactly as gptq_moe_decode_forward sums them.  A token with no valid routed
+ *             expert gets T(s_t (hs_t . W2_s)).
+ * Takes what gptq_moe_decode_forward takes for `moe`, and shared layers with a decode copy, 4 or 8 bits, fp16 / bf16, plain or act-order.  Declined with
+ * GPTQ_ERR_UNSUPPORTED and the reason: shared gate / up (down) that differ from the routed gate / up (down) in bits or dtype, I_s % 64 != 0, a bias or an
+ * epilogue on a shared layer, a shared layer without a decode copy or with a group size the copy does not take, shared gate and up of different group
+ * sizes, either launch's LDS layout above 160 KiB, gate_w not 16-byte aligned, flags or reserved != 0. */
+typedef struct gptq_moe_shared_t {
+    const gptq_layer_t *gate, *up, *down;   /* [H -> I_s], [H -> I_s], [I_s -> H], with decode copies */
+    const void *gate_w;                     /* [H] layer dtype, 16-byte aligned, or NULL (s = 1) */
+    int32_t flags, reserved;                /* 0 */
+} gptq_moe_shared_t;
+/* gptq_moe_decode_workspace_bytes(moe, T, topk) + a256(T I_s sizeof(T)) + a256(4 T): the decode path's h rows and pos, then hs [T, I_s] and s [T] fp32.
+ * The GPTQ_WORKSPACE_HEADER_BYTES in front are left untouched.  0 when the call is declined. */
+size_t gptq_moe_shared_decode_workspace_bytes(const gptq_moe_t *moe, const gptq_moe_shared_t *shared, int T, int topk);
+/* Arguments as gptq_moe_decode_forward (decode_table: gptq_moe_build_decode_table of `moe`; the shared layers need no table).  h_out (optional, for
+ * tests), at byte offsets  0: H [T topk, I] in assignment order;  T topk I sizeof(T): pos [T, topk] int32;  + 4 T topk: Hs [T, I_s];
+ * + T I_s sizeof(T): s [T] fp32 -- copied in stream order.  Caller's stream, no allocation, no synchronisation, legal inside hipGraph capture
+ * (gptq_init() first); T = 0 launches nothing. */
+int gptq_moe_shared_decode_forward(const gptq_moe_t *moe, const gptq_moe_shared_t *shared, const void *decode_table, const void *x, const int64_t *topk_idx,
+                                   const float *topk_w, int T, int topk, void *out, void *h_out, void *workspace, size_t workspace_bytes, void *stream);
+/* Host-only: "path=decode_shared launches=2 wg_pair=... wg_down=... waves_pair=... waves_down=... lds_pair=... lds_down=..." (wg_pair =
+ * T topk (I / 16) + T (I_s / 16): the workgroups that do work) or "path=none reason=...".  GPTQ_OK either way (GPTQ_ERR_NULL for a NULL out). */
+int gptq_describe_moe_shared_decode_plan(const gptq_moe_t *moe, const gptq_moe_shared_t *shared, int T, int topk, char *out, size_t out_bytes);
+/* The same tail at ANY token count, in place on the routed output: out[t, :] = T(float(out[t, :]) + s_t float(ys[t, :])), s_t as above from x [T, H] and
+ * gate_w [H] (NULL: s_t = 1, x is not read), ys [T, H] the shared expert's output; all in `dtype` (GPTQ_F16 / GPTQ_BF16), contiguous, 16-byte aligned.
+ * ONE launch, one workgroup per token, H % 8 == 0, no workspace, no atomics, bit-reproducible, legal inside hipGraph capture; T = 0 launches nothing. */
+int gptq_moe_shared_combine(const void *x, const void *gate_w, const void *ys, void *out, int T, int H, int dtype, void *stream);
 
 /* The same layer at BATCHED-DECODE row counts, 1 <= T <= 64 (additive in ABI 8), on the experts' decode copy: the arithmetic of gptq_moe_forward (every W
  * bit-exact to gptq_dequant, fp32 products and sums on the matrix core, h rounded once, out[t] = T(sum_j topk_w[t, j] y_(t, j)) in ascending j), on kernels

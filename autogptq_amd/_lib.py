@@ -41,7 +41,7 @@ EXPORTS = (
     "gptq_lora_down", "gptq_lora_up", "gptq_lora_apply", "gptq_describe_lora_plan",
     "gptq_lora_backward_workspace_bytes", "gptq_lora_backward", "gptq_describe_lora_backward_plan",
     "gptq_adapter_route_bytes", "gptq_adapter_route", "gptq_adapter_rows_apply", "gptq_describe_adapter_rows_plan",
-    "gptq_moe_router", "gptq_describe_moe_router_plan",
+    "gptq_moe_router", "gptq_describe_moe_router_plan", "gptq_moe_router_grouped", "gptq_describe_moe_router_grouped_plan",
     "gptq_moe_shared_decode_workspace_bytes", "gptq_moe_shared_decode_forward", "gptq_describe_moe_shared_decode_plan", "gptq_moe_shared_combine",
 )
 WS_HEADER_BYTES = 65536
@@ -230,6 +230,9 @@ def load() -> ctypes.CDLL:
     lib.gptq_describe_moe_backward_plan.argtypes = [MP, c_int, c_int, c_char_p, c_size_t]
     lib.gptq_moe_router.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.gptq_describe_moe_router_plan.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int, c_char_p, c_size_t]
+    lib.gptq_moe_router_grouped.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_float, c_int, c_int,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.gptq_describe_moe_router_grouped_plan.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_char_p, c_size_t]
     SP = POINTER(GptqMoeShared)
     lib.gptq_moe_shared_decode_workspace_bytes.restype = c_size_t
     lib.gptq_moe_shared_decode_workspace_bytes.argtypes = [MP, SP, c_int, c_int]
@@ -429,6 +432,19 @@ def describe_moe_router_plan(T: int, H: int, E: int, topk: int, dtype: int, flag
     lib = load()
     buf = ctypes.create_string_buffer(512)
     check(lib.gptq_describe_moe_router_plan(T, H, E, topk, dtype, flags, buf, len(buf)))
+    out = {}
+    for kv in buf.value.decode().split():
+        k, v = kv.split("=", 1)
+        out[k] = int(v) if v.lstrip("-").isdigit() else v
+    return out
+
+
+def describe_moe_router_grouped_plan(T: int, H: int, E: int, topk: int, n_group: int, topk_group: int, dtype: int, flags: int = 0) -> dict:
+    """What gptq_moe_router_grouped would run: path=router_grouped with its row regime, grid, LDS bytes and groups, or path=none with the reason
+    (host-only query)."""
+    lib = load()
+    buf = ctypes.create_string_buffer(512)
+    check(lib.gptq_describe_moe_router_grouped_plan(T, H, E, topk, n_group, topk_group, dtype, flags, buf, len(buf)))
     out = {}
     for kv in buf.value.decode().split():
         k, v = kv.split("=", 1)

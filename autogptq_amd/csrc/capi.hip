@@ -839,6 +839,55 @@ int gptq_describe_moe_router_plan(int T, int H, int E, int topk, int dtype, int 
     return GPTQ_OK;
 }
 
+// ---- the grouped-sigmoid form of the router (DeepSeek-V3 / GLM-4 MoE) ----
+static int router_grouped_check(int T, int H, int E, int topk, int n_group, int topk_group, float scale, int dtype, int flags) {
+    if (dtype == GPTQ_F32) return fail(GPTQ_ERR_UNSUPPORTED, "fp32 router: the router kernel takes fp16 / bf16");
+    if (dtype != GPTQ_F16 && dtype != GPTQ_BF16) return fail(GPTQ_ERR_UNSUPPORTED, "unknown dtype enum %d", dtype);
+    if (flags & ~GPTQ_ROUTER_RENORM) return fail(GPTQ_ERR_UNSUPPORTED, "unknown router flags 0x%x", flags);
+    if (E < 1 || E > 256) return fail(GPTQ_ERR_UNSUPPORTED, "E = %d experts: the router kernel takes 1..256", E);
+    if (topk < 1 || topk > 8) return fail(GPTQ_ERR_UNSUPPORTED, "topk = %d: the router kernel takes 1..8", topk);
+    if (n_group < 1 || n_group > 32) return fail(GPTQ_ERR_UNSUPPORTED, "n_group = %d: the grouped router takes 1..32 groups", n_group);
+    if (topk_group < 1 || topk_group > n_group) return fail(GPTQ_ERR_UNSUPPORTED, "topk_group = %d: the grouped router takes 1..n_group (n_group = %d)", topk_group, n_group);
+    if (E % n_group) return fail(GPTQ_ERR_UNSUPPORTED, "E = %d is not a multiple of n_group = %d", E, n_group);
+    if (n_group > 1 && E / n_group < 2) return fail(GPTQ_ERR_UNSUPPORTED, "E / n_group = %d: a group's score is the sum of its two largest, so groups hold 2 experts or more", E / n_group);
+    if (topk > topk_group * (E / n_group)) return fail(GPTQ_ERR_UNSUPPORTED, "topk = %d is more than the %d experts of the %d groups that stay", topk, topk_group * (E / n_group), topk_group);
+    if (!(scale - scale == 0.f)) return fail(GPTQ_ERR_UNSUPPORTED, "scale must be finite");
+    if (H <= 0 || H % 64) return fail(GPTQ_ERR_UNSUPPORTED, "H = %d must be a positive multiple of 64", H);
+    if (T < 0) return fail(GPTQ_ERR_SHAPE, "T must be >= 0, got %d", T);
+    const RouterPlan pl = plan_moe_router(T, H, E, topk, dtype);
+    if (pl.lds_bytes > GPTQ_ROUTER_MAX_LDS) return fail(GPTQ_ERR_UNSUPPORTED, "H = %d: the staged row of x needs %zu bytes of LDS, more than %zu", H, pl.lds_bytes, GPTQ_ROUTER_MAX_LDS);
+    return GPTQ_OK;
+}
+
+int gptq_moe_router_grouped(const void* x, const void* w, const float* bias, int T, int H, int E, int topk, int n_group, int topk_group, float scale, int dtype,
+                            int flags, float* logits_out, float* scores_out, int64_t* topk_idx, float* topk_w, void* stream) {
+    if (!x || !w || !topk_idx || !topk_w) return fail(GPTQ_ERR_NULL, "x / w / topk_idx / topk_w must be non-NULL");
+    if (int rc = router_grouped_check(T, H, E, topk, n_group, topk_group, scale, dtype, flags)) return rc;
+    if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)logits_out | (uintptr_t)scores_out | (uintptr_t)topk_idx | (uintptr_t)topk_w) & 15)
+        return fail(GPTQ_ERR_UNSUPPORTED, "x / w / logits_out / scores_out / topk_idx / topk_w must be 16-byte aligned");
+    if ((uintptr_t)bias & 3) return fail(GPTQ_ERR_UNSUPPORTED, "bias must be 4-byte aligned");
+    if (T == 0) return GPTQ_OK;
+    hipError_t e = launch_moe_router_grouped(x, w, bias, T, H, E, topk, n_group, topk_group, scale, dtype, flags & GPTQ_ROUTER_RENORM, logits_out, scores_out,
+                                             topk_idx, topk_w, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "gptq_moe_router_grouped launch");
+    return GPTQ_OK;
+}
+
+int gptq_describe_moe_router_grouped_plan(int T, int H, int E, int topk, int n_group, int topk_group, int dtype, int flags, char* out, size_t out_bytes) {
+    if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out is NULL");
+    if (router_grouped_check(T, H, E, topk, n_group, topk_group, 1.f, dtype, flags)) {
+        char reason[sizeof(g_err)];
+        snprintf(reason, sizeof(reason), "%s", g_err);
+        for (char* c = reason; *c; ++c)
+            if (*c == ' ' || *c == '=') *c = '_';
+        snprintf(out, out_bytes, "path=none reason=%s", reason);
+        return GPTQ_OK;
+    }
+    const RouterPlan pl = plan_moe_router(T, H, E, topk, dtype);
+    snprintf(out, out_bytes, "path=router_grouped form=%s wg=%ld waves=8 lds=%zu groups=%d launches=1", pl.rows ? "rows" : "tiles", pl.wg, pl.lds_bytes, n_group);
+    return GPTQ_OK;
+}
+
 // ---- LoRA adapters (lora.hip) ----
 static int lora_check(const gptq_lora_t* const* Ls, int n) {
     if (!Ls) return fail(GPTQ_ERR_NULL, "loras is NULL");

@@ -283,6 +283,9 @@ struct RouterPlan {
 RouterPlan plan_moe_router(int T, int H, int E, int topk, int dtype);
 hipError_t launch_moe_router(const void* x, const void* w, int T, int H, int E, int topk, int dtype, int renorm, void* logits, int64_t* idx, float* wts,
                              hipStream_t st);
+// the grouped-sigmoid form of the same kernels (gptq_moe_router_grouped): fp32 logits, sigmoid scores, group-limited top-k; plan_moe_router's grid and LDS
+hipError_t launch_moe_router_grouped(const void* x, const void* w, const float* bias, int T, int H, int E, int topk, int n_group, int topk_group, float scale,
+                                     int dtype, int renorm, float* logits, float* scores, int64_t* idx, float* wts, hipStream_t st);
 // adapter_grad.hip: the adapters' weight gradients dA = s du^T x and dB = s dY^T u (gptq_lora_backward): one launch over all jobs, one more to add the
 // M-slices where a job has more than one.  A job is one output [P][Q] with one of P, Q = r; slices are a function of (M, P, Q) alone.
 constexpr int GPTQ_WGRAD_JOBS = 2 * GPTQ_LORA_MAX;

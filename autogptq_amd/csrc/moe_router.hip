@@ -18,6 +18,17 @@
 //   1-8 tokens: a workgroup is one token; its x row is staged once in LDS, waves take experts round robin (four rows in flight per wave), lanes stride k
 //               in 16-byte loads, butterfly across the wave.  Wave 0 runs the epilogue.
 // The regime is a launch-uniform branch: one instantiation per dtype.  Within a regime a token's bits depend on nothing but its own row.
+//
+// The GROUPED-SIGMOID form (gptq_moe_router_grouped: DeepSeek-V3 / GLM-4 MoE) is a launch-uniform mode of the same two instantiations: the same two regimes
+// and the same sums, but the logits stay fp32 (the reference casts x and w to fp32), and the epilogue is route_token_grouped:
+//   scores     s_e = 1 / (1 + expf(-l_e)), c_e = s_e + bias_e (one fp32 add; no bias: c_e = s_e)
+//   groups     (G > 1) group g = experts [g Eg, (g + 1) Eg); its score is the largest c plus the second largest (one add); the kg groups with the largest
+//              score stay, equal scores to the LOWER group
+//   selection  topk times the largest remaining c among the experts of the groups that stay, equal c to the LOWER expert; order_key's total order
+//   weights    topk_w[t, j] = s_sel(j) (WITHOUT the bias), with GPTQ_ROUTER_RENORM divided by (sum_j s_sel(j) in ascending j) + 1e-20, then times scale
+// Epilogue layout: the wave writes c over the token's logits in LDS; P = 64 / G' lanes per group (G' = G rounded up to a power of two) scan the group's Eg
+// values P apart and keep a (largest, second) pair of keys, log2 P shuffle steps merge the pairs; a group's rank is counted over G lane reads of the
+// group scores (no butterfly), one ballot marks the groups that stay, and the wave-wide arg-max rounds run on keys cleared outside them.
 #include "common.cuh"
 #include "launch.h"
 
@@ -37,6 +48,11 @@ struct Args {
     int64_t* idx;
     float* wts;
     int T, H, E, topk, renorm, rows;
+    // the grouped-sigmoid form (mode = 1); logits is then fp32 [T, E]
+    int mode, G, kg, Eg, P;                 // P = 64 / (G rounded up to a power of two): lanes per group
+    float scale;
+    const float* bias;                      // [E] or NULL
+    float* scores;                          // fp32 [T, E] or NULL
 };
 
 template <typename T> struct Mma;
@@ -68,6 +84,41 @@ __device__ __forceinline__ unsigned order_key(float v) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// topk rounds of a wave-wide arg-max on (value, index) keys (0: no candidate): lane j keeps the j-th choice and val of it
+__device__ __forceinline__ void select_topk(const unsigned long long (&key)[4], const float (&val)[4], int topk, int lane, unsigned& my_idx, float& my_p) {
+    unsigned taken = 0;
+    my_idx = 0;
+    my_p = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        if (j < topk) {
+            unsigned long long best = 0ull;
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                if (!((taken >> s) & 1u) && key[s] > best) best = key[s];
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) {
+                const unsigned long long o = __shfl_xor(best, off);
+                best = o > best ? o : best;
+            }
+            const unsigned e = 0xffffffffu - (unsigned)best;      // a candidate is left in every round (the plan's bound on topk), so e < E
+            float pv = 0.f;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                if (e == (unsigned)(lane + 64 * s)) {
+                    taken |= 1u << s;
+                    pv = val[s];
+                }
+            }
+            pv = __shfl(pv, (int)(e & 63u));
+            if (lane == j) {
+                my_idx = e;
+                my_p = pv;
+            }
+        }
+    }
+}
+
 // softmax and selection of one token by one wave; lg: the token's E rounded logits in LDS (as fp32)
 template <typename T>
 __device__ __forceinline__ void route_token(const float* lg, const Args& p, size_t t, int lane) {
@@ -96,37 +147,9 @@ __device__ __forceinline__ void route_token(const float* lg, const Args& p, size
 #pragma unroll
     for (int s = 0; s < 4; ++s) pr[s] = pr[s] / sum;
 
-    // topk rounds of a wave-wide arg-max on (logit, index): lane j keeps the j-th choice
-    unsigned taken = 0, my_idx = 0;
-    float my_p = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        if (j < topk) {
-            unsigned long long best = 0ull;
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-                if (!((taken >> s) & 1u) && key[s] > best) best = key[s];
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) {
-                const unsigned long long o = __shfl_xor(best, off);
-                best = o > best ? o : best;
-            }
-            const unsigned e = 0xffffffffu - (unsigned)best;      // topk <= E: a candidate is left in every round, so e < E
-            float pv = 0.f;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                if (e == (unsigned)(lane + 64 * s)) {
-                    taken |= 1u << s;
-                    pv = pr[s];
-                }
-            }
-            pv = __shfl(pv, (int)(e & 63u));
-            if (lane == j) {
-                my_idx = e;
-                my_p = pv;
-            }
-        }
-    }
+    unsigned my_idx;
+    float my_p;
+    select_topk(key, pr, topk, lane, my_idx, my_p);
     if (p.renorm) {
         float s = 0.f;
 #pragma unroll
@@ -147,6 +170,84 @@ __device__ __forceinline__ void route_token(const float* lg, const Args& p, size
             const int e = lane + 64 * s;
             if (e < E) lo[e] = DType<T>::from_f32(lg[e]);      // exact: lg holds rounded values
         }
+    }
+}
+
+// the value behind a key of order_key (a NaN for the NaN key)
+__device__ __forceinline__ float key_value(unsigned k) { return as_f32((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+// (k1 >= k2) the two largest keys seen: take one more
+__device__ __forceinline__ void top2_push(unsigned& k1, unsigned& k2, unsigned k) {
+    const unsigned lo = k > k1 ? k1 : k;
+    k1 = k > k1 ? k : k1;
+    k2 = lo > k2 ? lo : k2;
+}
+
+// the grouped-sigmoid form: scores, group choice and selection of one token by one wave; lg: the token's E fp32 logits in LDS, overwritten with c
+__device__ __forceinline__ void route_token_grouped(float* lg, const Args& p, size_t t, int lane) {
+    const int E = p.E, topk = p.topk;
+    float sc[4], c[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const int e = lane + 64 * s;
+        sc[s] = c[s] = 0.f;
+        if (e < E) {
+            const float l = lg[e];
+            sc[s] = 1.f / (1.f + expf(-l));
+            c[s] = p.bias ? sc[s] + p.bias[e] : sc[s];
+            if (p.logits) ((float*)p.logits)[t * E + e] = l;
+            if (p.scores) p.scores[t * E + e] = sc[s];
+        }
+    }
+    unsigned long long kept = ~0ull;                            // bit g P: group g stays
+    if (p.G > 1) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+            if (lane + 64 * s < E) lg[lane + 64 * s] = c[s];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const int P = p.P, Eg = p.Eg, g = lane / P, r = lane - g * P;
+        unsigned k1 = 0, k2 = 0;                                // Eg >= 2: both are set after the merge
+        if (g < p.G)
+            for (int j = r; j < Eg; j += P) top2_push(k1, k2, order_key(lg[g * Eg + j]));
+        for (int off = 1; off < P; off <<= 1) {
+            const unsigned o1 = __shfl_xor(k1, off), o2 = __shfl_xor(k2, off);
+            const unsigned hi = k1 > o1 ? k1 : o1, lo = k1 > o1 ? o1 : k1, nx = k2 > o2 ? k2 : o2;
+            k1 = hi;
+            k2 = lo > nx ? lo : nx;
+        }
+        const unsigned gk = order_key(key_value(k1) + key_value(k2));
+        int rank = 0;                                           // groups ahead of mine: a larger score, or an equal one at a lower index
+        for (int h = 0; h < p.G; ++h) {
+            const unsigned o = (unsigned)__builtin_amdgcn_readlane((int)gk, h * P);
+            rank += (o > gk || (o == gk && h < g)) ? 1 : 0;
+        }
+        kept = __ballot(g < p.G && rank < p.kg);
+    }
+    unsigned long long key[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const int e = lane + 64 * s;
+        const bool ok = e < E && ((kept >> (p.G > 1 ? (e / p.Eg) * p.P : 0)) & 1ull);
+        key[s] = ok ? ((unsigned long long)order_key(c[s]) << 32) | (0xffffffffu - (unsigned)e) : 0ull;
+    }
+    unsigned my_idx;
+    float my_p;
+    select_topk(key, sc, topk, lane, my_idx, my_p);
+    if (p.renorm) {
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float pj = __shfl(my_p, j);
+            if (j < topk) s += pj;
+        }
+        my_p = my_p / (s + 1e-20f);
+    }
+    my_p *= p.scale;
+    if (lane < topk) {
+        p.idx[t * topk + lane] = (int64_t)my_idx;
+        p.wts[t * topk + lane] = my_p;
     }
 }
 
@@ -227,11 +328,14 @@ __global__ void __launch_bounds__(THREADS) moe_router_kernel(Args p) {
 #pragma unroll
                 for (int off = 32; off >= 1; off >>= 1) a[i] += __shfl_xor(a[i], off);
                 const int e = e0 + i * WAVES;
-                if (lane == 0 && e < E) lg[e] = round_to<T>(a[i]);
+                if (lane == 0 && e < E) lg[e] = p.mode ? a[i] : round_to<T>(a[i]);
             }
         }
         __syncthreads();
-        if (wave == 0) route_token<T>(lg, p, t, lane);
+        if (wave == 0) {
+            if (p.mode) route_token_grouped(lg, p, t, lane);
+            else route_token<T>(lg, p, t, lane);
+        }
         return;
     }
 
@@ -273,7 +377,7 @@ __global__ void __launch_bounds__(THREADS) moe_router_kernel(Args p) {
                     float s = 0.f;
 #pragma unroll
                     for (int wv = 0; wv < WAVES; ++wv) s += red[(wv * CHUNK + i) * 256 + (v & 255)];
-                    lg[((v >> 4) & 15) * EP + n * 16 + (v & 15)] = round_to<T>(s);
+                    lg[((v >> 4) & 15) * EP + n * 16 + (v & 15)] = p.mode ? s : round_to<T>(s);
                 }
             }
         }
@@ -282,7 +386,10 @@ __global__ void __launch_bounds__(THREADS) moe_router_kernel(Args p) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         const int m = 2 * wave + h;
-        if (m0 + m < (size_t)p.T) route_token<T>(lg + m * EP, p, m0 + m, lane);
+        if (m0 + m < (size_t)p.T) {
+            if (p.mode) route_token_grouped(lg + m * EP, p, m0 + m, lane);
+            else route_token<T>(lg + m * EP, p, m0 + m, lane);
+        }
     }
 }
 
@@ -299,11 +406,20 @@ RouterPlan plan_moe_router(int T, int H, int E, int topk, int dtype) {
     return pl;
 }
 
+static hipError_t launch_router(router::Args p, int dtype, hipStream_t st) {
+    const RouterPlan pl = plan_moe_router(p.T, p.H, p.E, p.topk, dtype);
+    if (pl.wg < 1 || pl.wg > 0x7fffffffL || pl.lds_bytes > GPTQ_ROUTER_MAX_LDS) return hipErrorInvalidValue;
+    p.rows = pl.rows ? 1 : 0;
+    const dim3 grid((unsigned)pl.wg), block(router::THREADS);
+    if (dtype == GPTQ_F16) hipLaunchKernelGGL(router::moe_router_kernel<f16>, grid, block, pl.lds_bytes, st, p);
+    else if (dtype == GPTQ_BF16) hipLaunchKernelGGL(router::moe_router_kernel<bf16>, grid, block, pl.lds_bytes, st, p);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
 hipError_t launch_moe_router(const void* x, const void* w, int T, int H, int E, int topk, int dtype, int renorm, void* logits, int64_t* idx, float* wts,
                              hipStream_t st) {
-    const RouterPlan pl = plan_moe_router(T, H, E, topk, dtype);
-    if (pl.wg < 1 || pl.wg > 0x7fffffffL || pl.lds_bytes > GPTQ_ROUTER_MAX_LDS) return hipErrorInvalidValue;
-    router::Args p;
+    router::Args p = {};
     p.x = x;
     p.w = w;
     p.logits = logits;
@@ -314,12 +430,35 @@ hipError_t launch_moe_router(const void* x, const void* w, int T, int H, int E, 
     p.E = E;
     p.topk = topk;
     p.renorm = renorm;
-    p.rows = pl.rows ? 1 : 0;
-    const dim3 grid((unsigned)pl.wg), block(router::THREADS);
-    if (dtype == GPTQ_F16) hipLaunchKernelGGL(router::moe_router_kernel<f16>, grid, block, pl.lds_bytes, st, p);
-    else if (dtype == GPTQ_BF16) hipLaunchKernelGGL(router::moe_router_kernel<bf16>, grid, block, pl.lds_bytes, st, p);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return launch_router(p, dtype, st);
+}
+
+// the grouped-sigmoid form: the same plan (grid, LDS) as the softmax form
+hipError_t launch_moe_router_grouped(const void* x, const void* w, const float* bias, int T, int H, int E, int topk, int n_group, int topk_group, float scale,
+                                     int dtype, int renorm, float* logits, float* scores, int64_t* idx, float* wts, hipStream_t st) {
+    if (n_group < 1 || n_group > 32 || E % n_group) return hipErrorInvalidValue;
+    int gp = 1;
+    while (gp < n_group) gp <<= 1;
+    router::Args p = {};
+    p.x = x;
+    p.w = w;
+    p.logits = logits;
+    p.idx = idx;
+    p.wts = wts;
+    p.T = T;
+    p.H = H;
+    p.E = E;
+    p.topk = topk;
+    p.renorm = renorm;
+    p.mode = 1;
+    p.G = n_group;
+    p.kg = topk_group;
+    p.Eg = E / n_group;
+    p.P = 64 / gp;
+    p.scale = scale;
+    p.bias = bias;
+    p.scores = scores;
+    return launch_router(p, dtype, st);
 }
 
 }  // namespace gptq

@@ -13,12 +13,17 @@
                         capturable), or the per-expert composition of differentiable ``QuantLinear`` calls
 * ``moe_route``         the router in front of the experts as ONE launch (gptq_moe_router: logits, softmax, top-k with a written tie rule and the
                         optional renormalisation; dense fp16 / bf16 weight, no workspace, capturable); the torch composition for what it declines
-* ``inject_fused_router`` / ``remove_fused_router``   bind ``moe_route`` as the forward of a model's softmax-top-k routers (Mixtral, Qwen2-MoE, Qwen3-MoE), on
-                        the instances: classes, parameters, state-dict keys, hooks and transformers' output recorders stay as they are.  Opt-in.
+* ``moe_route_grouped`` the sigmoid / group-limited router of DeepSeek-V3 and GLM-4 MoE blocks as ONE launch (gptq_moe_router_grouped: fp32 logits, sigmoid,
+                        correction bias, group choice, top-k, renormalisation and scaling); the transformers composition for what it declines
+* ``inject_fused_router`` / ``remove_fused_router``   bind ``moe_route`` as the forward of a model's softmax-top-k routers (Mixtral, Qwen2-MoE, Qwen3-MoE) and
+                        ``moe_route_grouped`` as that of its grouped-sigmoid routers (DeepSeek-V3, GLM-4 MoE), on the instances: classes, parameters,
+                        state-dict keys, hooks and transformers' output recorders stay as they are.  Opt-in.
 * ``moe_shared_forward``  a Qwen-MoE block's ``experts(x, idx, w) + sigmoid(shared_expert_gate(x)) * shared_expert(x)``: at 1..2 tokens (up to 4 on request) on experts with a decode
                         copy ONE gptq_moe_shared_decode_forward call (the two decode launches in their shared form), else the experts on the path they
                         plan, the shared MLP through ``mlp_forward`` and ONE gptq_moe_shared_combine launch for the linear / sigmoid / mul / add tail
-* ``inject_shared_expert`` / ``remove_shared_expert``   bind that as the forward of a model's ``Qwen2MoeSparseMoeBlock``s, on the instances.  Opt-in.
+                        ``gate_weight=None``: the ungated form ``experts(x, idx, w) + shared_experts(x)`` of DeepSeek-V3 / GLM-4 MoE blocks, same paths
+* ``inject_shared_expert`` / ``remove_shared_expert``   bind that as the forward of a model's ``Qwen2MoeSparseMoeBlock``s, ``DeepseekV3MoE``s and
+                        ``Glm4MoeMoE``s, on the instances.  Opt-in.
 * ``pack_moe_experts``  pack the dense 3-D expert parameters of a model (``quantizers`` keyed ``...mlp.experts.{e}.w1`` as ``pack_model`` takes)
 
 The per-expert composition serves what the grouped kernels do not take (2- / 3-bit experts unless ``post_init(low_bit=True)``, fp32 experts, odd group
@@ -482,7 +487,9 @@ def _per_expert(experts: QuantMoEExperts, x: torch.Tensor, idx: torch.Tensor, w:
 
 # ---------------------------------------------------------------------------------------------------------------- the router
 _ROUTER_PLANS: dict = {}
-ROUTER_CLASSES = {"MixtralTopKRouter": "mixtral", "Qwen2MoeTopKRouter": "qwen", "Qwen3MoeTopKRouter": "qwen"}      # matched by class name
+ROUTER_CLASSES = {"MixtralTopKRouter": "mixtral", "Qwen2MoeTopKRouter": "qwen", "Qwen3MoeTopKRouter": "qwen",      # matched by class name
+                  "DeepseekV3TopkRouter": "grouped", "Glm4MoeTopkRouter": "grouped"}
+_GROUPED_ATTRS = ("topk_group", "norm_topk_prob", "routed_scaling_factor", "e_score_correction_bias")      # (+ num_group or n_group)
 
 
 def router_plan(T: int, H: int, E: int, top_k: int, dtype: torch.dtype, renorm: bool = True) -> dict:
@@ -551,11 +558,127 @@ def moe_route(x: torch.Tensor, weight: torch.Tensor, top_k: int, renorm: bool = 
     return logits, w, idx
 
 
+# ---------------------------------------------------------------------------------------------------------------- the grouped-sigmoid router
+_BIAS_F32: dict = {}
+# (E * H at and above which, token count up to which) moe_route_grouped leaves the 16-token (tiles) form to the composition: measured slower there
+# (profiles/moe_router_grouped_ab.log: DeepSeek-V3's router, E 256 x H 7168, at 16 and 64 tokens -- one to four workgroups pull all of the weight with one
+# k-step in flight per wave; faster again at 512 tokens, and at every token count on the 128 x 4096 router).  None: no region is declined for speed.
+GROUPED_SLOW_TILES = (256 * 7168, 64)
+
+
+def router_grouped_plan(T: int, H: int, E: int, top_k: int, n_group: int, topk_group: int, dtype: torch.dtype, renorm: bool = True) -> dict:
+    """{"path": "router_grouped" | "none", "form": "rows" | "tiles", "reason": ...} for one ``moe_route_grouped`` call on GPU tensors (host-only, cached)."""
+    key = ("grouped", T, H, E, top_k, n_group, topk_group, dtype, bool(renorm), GROUPED_SLOW_TILES)
+    d = _ROUTER_PLANS.get(key)
+    if d is None:
+        enum = _lib.DTYPE_ENUM.get(dtype)
+        if enum is None:
+            d = {"path": "none", "reason": f"dtype {dtype}: the router kernel takes fp16 / bf16"}
+        else:
+            d = _lib.describe_moe_router_grouped_plan(T, H, E, top_k, n_group, topk_group, enum, _lib.ROUTER_RENORM if renorm else 0)
+            d.setdefault("reason", "")
+            d["reason"] = str(d["reason"]).replace("_", " ")
+            slow = GROUPED_SLOW_TILES
+            if slow is not None and d["path"] == "router_grouped" and d["form"] == "tiles" and E * H >= slow[0] and T <= slow[1]:
+                d = {"path": "none", "reason": f"the tiles form was measured slower than the composition at 9..{slow[1]} tokens with E * H >= {slow[0]}"}
+        _ROUTER_PLANS[key] = d
+    return dict(d)
+
+
+def _route_grouped_composition(x2, weight, bias, top_k, n_group, topk_group, renorm, scale, return_logits):
+    """The router of transformers' DeepSeek-V3 / GLM-4 MoE, operation for operation (DeepseekV3TopkRouter.forward)."""
+    E = weight.shape[0]
+    router_logits = F.linear(x2.type(torch.float32), weight.type(torch.float32))
+    scores = router_logits.sigmoid()
+    scores_for_choice = scores + bias if bias is not None else scores
+    group_scores = scores_for_choice.view(-1, n_group, E // n_group).topk(2, dim=-1)[0].sum(dim=-1)
+    group_idx = torch.topk(group_scores, k=topk_group, dim=-1, sorted=False)[1]
+    group_mask = torch.zeros_like(group_scores)
+    group_mask.scatter_(1, group_idx, 1)
+    score_mask = group_mask.unsqueeze(-1).expand(-1, n_group, E // n_group).reshape(-1, E)
+    scores_for_choice = scores_for_choice.masked_fill(~score_mask.bool(), float("-inf"))
+    topk_indices = torch.topk(scores_for_choice, k=top_k, dim=-1, sorted=False)[1]
+    topk_weights = scores.gather(1, topk_indices)
+    if renorm:
+        denominator = topk_weights.sum(dim=-1, keepdim=True) + 1e-20
+        topk_weights = topk_weights / denominator
+    topk_weights = topk_weights * scale
+    return (router_logits if return_logits else None), topk_weights, topk_indices
+
+
+def _bias_f32(bias: torch.Tensor) -> torch.Tensor:
+    """``bias`` as a contiguous fp32 tensor: itself, or a copy cached on (data_ptr, _version, device) -- ``model.half()`` casts the correction-bias buffer
+    too, and a cast per call would be a launch of its own in a captured step."""
+    if bias.dtype == torch.float32 and bias.is_contiguous() and not bias.data_ptr() & 3:
+        return bias
+    key = (bias.data_ptr(), bias._version, bias.device, bias.dtype, tuple(bias.shape), tuple(bias.stride()))
+    ent = _BIAS_F32.get(key)
+    if ent is None:
+        if len(_BIAS_F32) >= 4096:      # (buffers that were freed or updated in place leave stale entries behind)
+            _BIAS_F32.clear()
+        ent = _BIAS_F32[key] = bias.detach().to(torch.float32).contiguous()
+    return ent
+
+
+def moe_route_grouped(x: torch.Tensor, weight: torch.Tensor, bias: "torch.Tensor | None", top_k: int, n_group: int, topk_group: int, renorm: bool = True,
+                      scale: float = 1.0, return_logits: bool = True):
+    """Router of a DeepSeek-V3 / GLM-4 MoE layer: x [T, H] (or [..., H]), weight [E, H], bias [E] (``e_score_correction_bias``) or None -> (logits fp32
+    [T, E] or None, weights fp32 [T, top_k], indices int64 [T, top_k]): fp32 logits, sigmoid scores, group-limited top-k on the biased scores, weights from
+    the unbiased ones, renormalised when ``renorm`` and multiplied by ``scale`` (``routed_scaling_factor``).  On the GPU, without grad, for what the plan
+    takes (``router_grouped_plan``): ONE gptq_moe_router_grouped call on the current stream -- written tie rules (equal scores to the lower group / expert
+    index), nothing allocated but the outputs, nothing synchronises, a captured graph replays it.  Everything else runs the transformers composition
+    (``last_route_plan`` says why): CPU tensors, what the plan declines (for its shape, or for speed: ``GROUPED_SLOW_TILES``), x and weight of different
+    dtypes, a weight that is not contiguous, and calls under grad where ``x`` or ``weight`` require grad.  A bias that is not contiguous fp32 is read through a cached fp32 copy."""
+    global last_route_plan
+    E, H = weight.shape
+    x2 = x.reshape(-1, H)
+    T = x2.shape[0]
+    scale = float(scale)
+    if x2.device.type != "cuda" or weight.device != x2.device or (bias is not None and bias.device != x2.device):
+        plan = {"path": "none", "reason": "cpu tensors"}
+    elif torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad):
+        plan = {"path": "none", "reason": "grad enabled and x / weight require grad"}
+    elif x2.dtype != weight.dtype:
+        plan = {"path": "none", "reason": f"x is {x2.dtype}, weight {weight.dtype}"}
+    elif not weight.is_contiguous() or weight.data_ptr() & 15:
+        plan = {"path": "none", "reason": "weight must be contiguous and 16-byte aligned"}
+    elif bias is not None and tuple(bias.shape) != (E,):
+        plan = {"path": "none", "reason": f"bias must be [{E}]"}
+    elif scale - scale != 0.0:
+        plan = {"path": "none", "reason": "scale must be finite"}
+    else:
+        plan = router_grouped_plan(T, H, E, top_k, n_group, topk_group, x2.dtype, renorm)
+    last_route_plan = plan
+    if plan["path"] != "router_grouped":
+        return _route_grouped_composition(x2, weight, bias, top_k, n_group, topk_group, renorm, scale, return_logits)
+    dev = x2.device
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    if x2.data_ptr() & 15:
+        x2 = x2.clone()
+    b = _bias_f32(bias) if bias is not None else None
+    logits = torch.empty((T, E), dtype=torch.float32, device=dev) if return_logits else None
+    idx = torch.empty((T, top_k), dtype=torch.int64, device=dev)
+    w = torch.empty((T, top_k), dtype=torch.float32, device=dev)
+    if T:
+        with torch.cuda.device(dev.index):
+            rc = _lib.load().gptq_moe_router_grouped(x2.data_ptr(), weight.data_ptr(), _lib.ptr(b), T, H, E, top_k, n_group, topk_group, scale,
+                                                     _lib.DTYPE_ENUM[x2.dtype], _lib.ROUTER_RENORM if renorm else 0, _lib.ptr(logits), None, idx.data_ptr(),
+                                                     w.data_ptr(), _raw_stream(dev.index))
+        if rc:
+            _lib.check(rc)
+    return logits, w, idx
+
+
 last_route_plan: dict = {}
 
 
 def _fused_router_forward(self, hidden_states):
     """Bound on a router instance by inject_fused_router: the class's own triple (router_logits, router_scores, router_indices)."""
+    if self._fused_router_kind == "grouped":
+        n_group = self.num_group if hasattr(self, "num_group") else self.n_group
+        return moe_route_grouped(hidden_states.reshape(-1, self.weight.shape[1]), self.weight, self.e_score_correction_bias, self.top_k, n_group,
+                                 self.topk_group, renorm=bool(self.norm_topk_prob), scale=self.routed_scaling_factor, return_logits=True)
     qwen = self._fused_router_kind == "qwen"
     renorm = bool(getattr(self, "norm_topk_prob", True)) if qwen else True
     logits, scores, idx = moe_route(hidden_states.reshape(-1, self.weight.shape[1]), self.weight, self.top_k, renorm=renorm, return_logits=True)
@@ -569,6 +692,8 @@ def _router_kind(m: nn.Module):
     w = getattr(m, "weight", None)
     if kind is None or not torch.is_tensor(w) or w.dim() != 2 or not hasattr(m, "top_k") or getattr(m, "num_experts", None) != w.shape[0]:
         return None
+    if kind == "grouped" and not (all(hasattr(m, a) for a in _GROUPED_ATTRS) and (hasattr(m, "num_group") or hasattr(m, "n_group"))):
+        return None
     return kind
 
 
@@ -576,7 +701,9 @@ def inject_fused_router(model: nn.Module) -> int:
     """Give every MixtralTopKRouter / Qwen2MoeTopKRouter / Qwen3MoeTopKRouter of ``model`` (matched by class name, with ``weight [E, H]``, ``top_k`` and
     ``num_experts``) a forward bound on the INSTANCE that calls ``moe_route``.  The module keeps its object, class and parameters, so state-dict keys,
     hooks and transformers' ``OutputRecorder(<RouterClass>, index=0)`` (``output_router_logits=True``) keep working.  Mixtral: renormalised fp32 scores;
-    Qwen 2 / 3: renormalised iff ``norm_topk_prob``, scores cast to the logits dtype.  Routers of any other class (sigmoid, grouped) are left alone.
+    Qwen 2 / 3: renormalised iff ``norm_topk_prob``, scores cast to the logits dtype.  DeepseekV3TopkRouter / Glm4MoeTopkRouter (which must also carry
+    ``num_group`` or ``n_group``, ``topk_group``, ``norm_topk_prob``, ``routed_scaling_factor`` and ``e_score_correction_bias``): ``moe_route_grouped`` --
+    fp32 logits, fp32 weights.  Routers of any other class are left alone.
     Returns the number of routers bound.  Nothing is injected by default."""
     n = 0
     for m in model.modules():
@@ -601,7 +728,7 @@ def remove_fused_router(model: nn.Module) -> int:
 
 
 # ---------------------------------------------------------------------------------------------------------------- the shared expert
-SHARED_BLOCK_CLASSES = ("Qwen2MoeSparseMoeBlock",)      # matched by class name
+SHARED_BLOCK_CLASSES = ("Qwen2MoeSparseMoeBlock", "DeepseekV3MoE", "Glm4MoeMoE")      # matched by class name
 # Up to this many tokens moe_shared_forward runs the fused call where the plan accepts; above, experts + mlp_forward + the combine launch.  The kernels take
 # 1..4; the default is where the fused call was measured the fastest form on A2.7B's block (profiles/moe_shared_ab.log: at 3 and 4 tokens launch 2's
 # workgroups walk the routed segments and the long shared one in sequence, and the combine form wins).  Per experts module:
@@ -651,11 +778,12 @@ def shared_workspace_bytes(experts: QuantMoEExperts, shared_layers, T: int, top_
     return int(_lib.load().gptq_moe_shared_decode_workspace_bytes(ctypes.byref(experts._moe), ctypes.byref(sh), T, top_k))
 
 
-def moe_shared_forward(experts: QuantMoEExperts, shared_layers, gate_weight: torch.Tensor, x: torch.Tensor, top_k_index: torch.Tensor,
+def moe_shared_forward(experts: QuantMoEExperts, shared_layers, gate_weight: "torch.Tensor | None", x: torch.Tensor, top_k_index: torch.Tensor,
                        top_k_weights: torch.Tensor, return_intermediate: bool = False):
     """A Qwen-MoE block behind its router: ``experts(x, idx, w) + sigmoid(x @ gate_weight.T) * down(silu(gate(x)) * up(x))`` with
     ``shared_layers = (gate, up, down)`` QuantLinears [H -> I_s], [H -> I_s], [I_s -> H] and ``gate_weight`` the dense [1, H] (or [H]) weight of
-    ``shared_expert_gate``, read in place.  ``experts.last_plan["shared"]`` says what ran:
+    ``shared_expert_gate``, read in place.  ``gate_weight=None`` is the ungated block of DeepSeek-V3 / GLM-4 MoE, ``experts(x, idx, w) + shared_experts(x)``:
+    the same three paths with the gate scalar 1 (the kernels take a NULL gate weight).  ``experts.last_plan["shared"]`` says what ran:
 
     * ``"decode"``   without grad, on the GPU, when ``experts.plan(T)["path"] == "decode"`` (experts with a decode copy), ``shared_plan`` accepts and
                      T <= ``experts.shared_decode_max_tokens`` (default SHARED_DECODE_MAX_TOKENS = 2; the kernels take up to 4): ONE
@@ -676,22 +804,22 @@ def moe_shared_forward(experts: QuantMoEExperts, shared_layers, gate_weight: tor
     why = ""
     if x.device.type != "cuda":
         why = "cpu tensors"
-    elif torch.is_grad_enabled() and (x.requires_grad or top_k_weights.requires_grad or gate_weight.requires_grad):
+    elif torch.is_grad_enabled() and (x.requires_grad or top_k_weights.requires_grad or (gate_weight is not None and gate_weight.requires_grad)):
         why = "grad enabled and hidden_states / top_k_weights / gate_weight require grad"
     else:
         w_dtype = gate.scales.dtype
-        if gate_weight.dtype != w_dtype or gate_weight.device != x.device:
+        if gate_weight is not None and (gate_weight.dtype != w_dtype or gate_weight.device != x.device):
             why = f"gate_weight is {gate_weight.dtype} on {gate_weight.device}, the shared layers {w_dtype} on {x.device}"
         elif w_dtype not in (torch.float16, torch.bfloat16) or H % 8:
             why = "the shared combine kernel takes fp16 / bf16 and H % 8 == 0"
-        elif gate_weight.numel() != H or not gate_weight.is_contiguous() or gate_weight.data_ptr() & 15:
+        elif gate_weight is not None and (gate_weight.numel() != H or not gate_weight.is_contiguous() or gate_weight.data_ptr() & 15):
             why = "gate_weight must be [1, H], contiguous and 16-byte aligned"
     if why:
         if return_intermediate:
             raise RuntimeError(f"moe_shared_forward: return_intermediate needs the fused decode call ({why})")
         routed = experts(x2, top_k_index.reshape(T, topk), top_k_weights.reshape(T, topk))
         shared = down(F.silu(gate(x2)) * up(x2))
-        out = routed + torch.sigmoid(F.linear(x2, gate_weight.reshape(1, H))) * shared
+        out = routed + shared if gate_weight is None else routed + torch.sigmoid(F.linear(x2, gate_weight.reshape(1, H))) * shared
         experts.last_plan = dict(experts.last_plan or {}, shared="torch", shared_reason=why)
         return out.reshape(lead + (H,))
     xw = _aligned(x2, w_dtype)
@@ -708,7 +836,7 @@ def moe_shared_forward(experts: QuantMoEExperts, shared_layers, gate_weight: tor
         if T:
             ys = _aligned(mlp_forward(gate, up, down, xw), w_dtype)
             with torch.cuda.device(xw.device.index):
-                rc = _lib.load().gptq_moe_shared_combine(xw.data_ptr(), gate_weight.data_ptr(), ys.data_ptr(), out.data_ptr(), T, H, _lib.DTYPE_ENUM[w_dtype],
+                rc = _lib.load().gptq_moe_shared_combine(xw.data_ptr(), _lib.ptr(gate_weight), ys.data_ptr(), out.data_ptr(), T, H, _lib.DTYPE_ENUM[w_dtype],
                                                          _raw_stream(xw.device.index))
             if rc:
                 _lib.check(rc)
@@ -736,7 +864,7 @@ def moe_shared_forward(experts: QuantMoEExperts, shared_layers, gate_weight: tor
         need = experts._plans[key + ("ws", T, topk)] = shared_workspace_bytes(experts, shared_layers, T, topk)
     buf = reserve_workspace(dev, need)
     exchange_tick(dev)
-    sh.gate_w = gate_weight.data_ptr()
+    sh.gate_w = _lib.ptr(gate_weight)
     with torch.cuda.device(dev.index):
         rc = _lib.load().gptq_moe_shared_decode_forward(ctypes.byref(experts._moe), ctypes.byref(sh), experts._decode_table.data_ptr(), xw.data_ptr(),
                                                         idx.data_ptr(), w.data_ptr(), T, topk, out.data_ptr(), _lib.ptr(h_out), buf.data_ptr(), buf.numel(),
@@ -758,8 +886,11 @@ def _shared_block_forward(self, hidden_states):
     shape = hidden_states.shape
     x = hidden_states.reshape(-1, shape[-1])
     _, routing_weights, selected_experts = self.gate(x)
-    se = self.shared_expert
-    out = moe_shared_forward(self.experts, (se.gate_proj, se.up_proj, se.down_proj), self.shared_expert_gate.weight, x, selected_experts, routing_weights)
+    if hasattr(self, "shared_expert_gate"):                       # the Qwen form
+        se, gate_weight = self.shared_expert, self.shared_expert_gate.weight
+    else:                                                         # the DeepSeek-V3 / GLM-4 MoE form: always on, no gate
+        se, gate_weight = self.shared_experts, None
+    out = moe_shared_forward(self.experts, (se.gate_proj, se.up_proj, se.down_proj), gate_weight, x, selected_experts, routing_weights)
     return out.reshape(shape)
 
 
@@ -767,20 +898,26 @@ def _shared_block_parts(m: nn.Module):
     """(experts, (gate, up, down)) of a block inject_shared_expert takes, or None."""
     if type(m).__name__ not in SHARED_BLOCK_CLASSES:
         return None
-    experts, se, sg = getattr(m, "experts", None), getattr(m, "shared_expert", None), getattr(m, "shared_expert_gate", None)
+    experts, sg = getattr(m, "experts", None), getattr(m, "shared_expert_gate", None)
+    gated = hasattr(m, "shared_expert_gate")                      # Qwen: shared_expert + shared_expert_gate; DeepSeek-V3 / GLM-4 MoE: shared_experts, no gate
+    se = getattr(m, "shared_expert" if gated else "shared_experts", None)
     if not isinstance(experts, QuantMoEExperts) or se is None or not hasattr(m, "gate"):
         return None
     layers = tuple(getattr(se, nm, None) for nm in ("gate_proj", "up_proj", "down_proj"))
     if not all(isinstance(l, QuantLinear) for l in layers):
         return None
-    if not isinstance(sg, nn.Linear) or sg.bias is not None or sg.out_features != 1 or sg.in_features != experts.hidden_dim:
+    H, Is = experts.hidden_dim, layers[0].outfeatures
+    if [(l.infeatures, l.outfeatures) for l in layers] != [(H, Is), (H, Is), (Is, H)]:
+        return None
+    if gated and (not isinstance(sg, nn.Linear) or sg.bias is not None or sg.out_features != 1 or sg.in_features != H):
         return None
     return experts, layers
 
 
 def inject_shared_expert(model: nn.Module) -> int:
     """Give every ``Qwen2MoeSparseMoeBlock`` of ``model`` (matched by class name; ``experts`` a QuantMoEExperts, ``shared_expert.{gate_proj, up_proj,
-    down_proj}`` QuantLinears, ``shared_expert_gate`` a bias-free Linear(H, 1)) a forward bound on the INSTANCE that calls ``moe_shared_forward``.  The block
+    down_proj}`` QuantLinears, ``shared_expert_gate`` a bias-free Linear(H, 1)) and every ``DeepseekV3MoE`` / ``Glm4MoeMoE`` (``shared_experts.{gate_proj,
+    up_proj, down_proj}`` QuantLinears and no ``shared_expert_gate``) a forward bound on the INSTANCE that calls ``moe_shared_forward``.  The block
     keeps its object, class, parameters, state-dict keys and hooks; it calls ``self.gate(...)`` as before, so ``inject_fused_router`` composes;
     ``shared_expert_gate.weight`` is read in place at every call, so a later ``.to()`` is seen.  (Forward hooks on the children: ``shared_expert`` and
     ``shared_expert_gate`` are never called as modules; ``experts`` and the three shared QuantLinears only on the ``"torch"`` path.)  Order: inject, then
@@ -862,4 +999,4 @@ def pack_moe_experts(model: nn.Module, quantizers: dict, bits: int, group_size: 
 
 __all__ = ["QuantMoEExperts", "moe_forward", "pack_moe_experts", "dense_expert_modules", "make_quant_experts", "moe_route", "router_plan",
            "inject_fused_router", "remove_fused_router", "moe_shared_forward", "shared_plan", "shared_workspace_bytes", "inject_shared_expert",
-           "remove_shared_expert"]
+           "remove_shared_expert", "moe_route_grouped", "router_grouped_plan"]

@@ -21,6 +21,8 @@
  *       <- the same expert loop at the row counts of token generation (1..4 tokens) and of batched generation (5..64), on the experts' decode copy
  *   gptq_moe_router
  *       <- the router in front of that loop (transformers' MixtralTopKRouter: F.linear, softmax, topk, renormalise) as one launch
+ *   gptq_moe_router_grouped
+ *       <- the sigmoid / group-limited router of DeepSeek-V3 and GLM-4 MoE blocks (transformers' DeepseekV3TopkRouter) as one launch
  *   gptq_moe_shared_decode_forward, gptq_moe_shared_combine
  *       <- the shared expert next to that loop (transformers' Qwen2MoeSparseMoeBlock: + sigmoid(shared_expert_gate(x)) * shared_expert(x)), inside the two
  *          decode launches at 1..4 tokens, and its linear / sigmoid / mul / add tail as one launch at any token count
@@ -571,6 +573,33 @@ int gptq_moe_router(const void *x, const void *w, int T, int H, int E, int topk,
                     void *stream);
 /* Host-only: "path=router form=rows|tiles wg=... waves=8 lds=... launches=1" or "path=none reason=...".  GPTQ_OK either way (GPTQ_ERR_NULL for a NULL out). */
 int gptq_describe_moe_router_plan(int T, int H, int E, int topk, int dtype, int flags, char *out, size_t out_bytes);
+
+/* The GROUPED-SIGMOID form of the router (additive in ABI 8): the router of DeepSeek-V3 / R1 and GLM-4.5 / 4.6 MoE blocks (transformers'
+ * DeepseekV3TopkRouter / Glm4MoeTopkRouter: fp32 linear, sigmoid, correction bias, group-limited top-k, gather, renormalise, scale) in ONE launch of the
+ * same kernels.  For x [T, H] and w [E, H] in D (fp16 or bf16), bias [E] fp32 or NULL, G = n_group, kg = topk_group, Eg = E / G:
+ *   Logits.     l[t, e] = sum_k x[t, k] w[e, k]: fp32 products and sums in the fixed orders of the two row regimes, NOT rounded to D (the reference
+ *               casts x and w to fp32 first).
+ *   Scores.     s_e = 1 / (1 + expf(-l_e)) in fp32; c_e = s_e + bias_e, one fp32 add (NULL bias: c_e = s_e).
+ *   Groups.     Only when G > 1: group g holds the experts [g Eg, (g + 1) Eg); its score is the fp32 sum of its two largest c (one add: largest plus
+ *               second largest).  The kg groups with the largest score stay; equal scores go to the LOWER group index.
+ *   Selection.  Among the experts of the groups that stay, topk times the largest remaining c; equal c goes to the LOWER expert index.  topk_idx [T, topk]
+ *               (int64) is in that order: descending c, then ascending index.  -0 equals +0 and a NaN ranks above every number, for c and for the group
+ *               scores alike.  Indices are always distinct, inside [0, E) and inside the groups that stay, whatever the input holds.
+ *   Weights.    topk_w[t, j] = s_sel(j): the score WITHOUT the bias, as in the reference.  With GPTQ_ROUTER_RENORM divided by
+ *               (sum_j s_sel(j), in ascending j) + 1e-20.  Then multiplied by scale, the routed scaling factor (1.0 for none).  fp32 [T, topk].
+ *   logits_out  fp32 [T, E], the logits, or NULL.      scores_out  fp32 [T, E], s, or NULL.
+ * Given s, everything after the sigmoid is single fp32 adds and comparisons: a host can reproduce the selection bit for bit.
+ * As gptq_moe_router: no workspace, no atomics, no exchange between workgroups; bit-reproducible, legal inside hipGraph capture; the same two row regimes
+ * (1..8 tokens: one token per workgroup; 9+: 16 tokens x all experts on v_mfma_f32_16x16x32), within which a token's bits depend on its own row only.
+ * Takes D in {fp16, bf16}, H % 64 == 0 (and a staged row within 64 KiB of LDS), 1 <= E <= 256, 1 <= topk <= 8, 1 <= kg <= G <= 32, E % G == 0, Eg >= 2
+ * when G > 1, topk <= kg Eg, flags within {0, GPTQ_ROUTER_RENORM}, a finite scale; x, w and the outputs 16-byte aligned and contiguous, bias 4-byte
+ * aligned.  Anything else: GPTQ_ERR_UNSUPPORTED with the reason, nothing launched.  GPTQ_ERR_NULL for a NULL x / w / topk_idx / topk_w; T < 0 is
+ * GPTQ_ERR_SHAPE; T = 0 validates and launches nothing. */
+int gptq_moe_router_grouped(const void *x, const void *w, const float *bias, int T, int H, int E, int topk, int n_group, int topk_group, float scale,
+                            int dtype, int flags, float *logits_out, float *scores_out, int64_t *topk_idx, float *topk_w, void *stream);
+/* Host-only: "path=router_grouped form=rows|tiles wg=... waves=8 lds=... groups=... launches=1" or "path=none reason=...".  GPTQ_OK either way
+ * (GPTQ_ERR_NULL for a NULL out). */
+int gptq_describe_moe_router_grouped_plan(int T, int H, int E, int topk, int n_group, int topk_group, int dtype, int flags, char *out, size_t out_bytes);
 
 /* Integer unpack (bit-exact targets). w_out uint8 [K,N]; z_out int32 [G,N] (zero-point as used). */
 int gptq_unpack_weights(const uint32_t *qweight, int K, int N, int bits, uint8_t *w_out, void *stream);

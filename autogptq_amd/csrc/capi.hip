@@ -1835,8 +1835,8 @@ int gptq_describe_plan(const gptq_layer_t* L, int M, const gptq_tuning_t* tune, 
     if (tiled_pair_call(L, M, tune)) {
         const gptq_layer_t* one[1] = {L};
         const TiledPlan tp = plan_tiled(one, 1, M, tune);
-        snprintf(out, out_bytes, "path=gemv kernel=strips ln=4 waves=%d u=%d ksplit=%d mt=%d strips=%d pair=1 perm=0 epilogue=fused", tp.waves, tp.u, tp.ksplit, tp.mt,
-                 tp.strips_total);
+        snprintf(out, out_bytes, "path=gemv kernel=strips ln=4 waves=%d u=%d ksplit=%d mt=%d strips=%d pair=1 perm=0 epilogue=fused aligned=%d", tp.waves, tp.u, tp.ksplit, tp.mt,
+                 tp.strips_total, tp.aligned ? 1 : 0);
         return GPTQ_OK;
     }
     const bool unfused_epilogue = L->epilogue != GPTQ_EPI_NONE && !fused_epilogue_ok(L, M, tune);
@@ -1850,8 +1850,8 @@ int gptq_describe_plan(const gptq_layer_t* L, int M, const gptq_tuning_t* tune, 
     const gptq_layer_t* one_t[1] = {&Lc};
     if (!unfused_epilogue && Lc.epilogue == GPTQ_EPI_NONE && want_tiled(one_t, 1, M, tune)) {
         const TiledPlan tp = plan_tiled(one_t, 1, M, tune);
-        snprintf(out, out_bytes, "path=gemv kernel=strips ln=4 waves=%d u=%d ksplit=%d mt=%d strips=%d pair=0 perm=0 epilogue=none", tp.waves, tp.u, tp.ksplit, tp.mt,
-                 tp.strips_total);
+        snprintf(out, out_bytes, "path=gemv kernel=strips ln=4 waves=%d u=%d ksplit=%d mt=%d strips=%d pair=0 perm=0 epilogue=none aligned=%d", tp.waves, tp.u, tp.ksplit, tp.mt,
+                 tp.strips_total, tp.aligned ? 1 : 0);
     } else if (!unfused_epilogue && want_stream_seq(L, M, tune, &Pseq)) {
         const gptq_layer_t* one[1] = {&Pseq};
         const StreamPlan sp = plan_stream(one, 1, M, nullptr);

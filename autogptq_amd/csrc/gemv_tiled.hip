@@ -30,6 +30,7 @@
 //     gemv_tiled_kernel.cuh), K slices through {fp32, tag} granules in a cold block (stream_finish, gemv_shared.cuh);
 //   * up to four layers that share x in one launch (gptq_forward_multi).
 #include "gemv_tiled_kernel.cuh"
+#include "../../include/gptq_mi355x_lab.h"
 
 namespace gptq {
 
@@ -44,6 +45,7 @@ hipError_t init_gemv_tiled_multi_device();
 
 // ---- plan + launch ---------------------------------------------------------------------------------------------------------------------
 int tiled_max_waves(int u, int nstr) { return (u == 2 || nstr == 4) ? 16 : 8; }       // = tiled_maxw<U, XM>() of gemv_tiled_kernel.cuh: the launch bound each depth is compiled for
+bool tiled_has_aligned(int bits, int mt, int u, int nstr) { return bits == 4 && ((nstr == 1 && mt == 1) || (nstr == 2 && mt <= 2 && u == 4)); }      // = tiled_aligned_form<BITS, MT, U, XM>()
 static int tiled_kpl(int bits) { return bits == 8 ? 16 : 32; }          // k per lane and chunk
 static int tiled_chunk_bytes(int bits) { return bits == 3 ? 768 : (bits == 2 ? 512 : 1024); }
 static int tiled_rec_bytes(int bits) { return bits == 8 ? 64 : 48; }
@@ -193,9 +195,14 @@ TiledPlan plan_tiled(const gptq_layer_t* const* Ls, int n, int M, const gptq_tun
     if (nstr > 1 && waves % nstr != 0) return pl;
     if (waves < 1 || waves > 16 || (u != 2 && u != 4)) return pl;                // 2 or 4 chunks per wave in flight (the 1- / 8-chunk forms were lab-only: retired in round 6)
     if (waves > tiled_max_waves(u, nstr)) return pl;                              // 4 chunks in flight: workgroups of at most 8 waves (one compilation per depth; only a forced geometry gets here)
+    if (nstr == 4 && u == 2 && A.bits != 4) return pl;                            // the four-strip form with 2 chunks in flight is compiled for 4-bit layers only (a doubly forced geometry)
     pl.waves = waves;
     pl.u = u;
     pl.zm2 = A.bits == 4 && A.dtype == GPTQ_BF16 && pl.mt == 2 && (long)strips * pl.ksplit < 1024;      // profiles/r06_zm_ab.log
+    // The aligned form of the K loop: no ragged chunk, no missing k-slot (K a whole number of chunks; a lane's k lie in one group by tiled_layer_ok),
+    // plain layers (no act-order, no pair epilogue), where the form is compiled.  tuning.reserved[GPTQ_LAB_GEMM_VARIANT] = GPTQ_LAB_VARIANT_TILED_GENERAL keeps the general form.
+    pl.aligned = A.K % cke == 0 && !A.g_idx && !pair && tiled_has_aligned(A.bits, pl.mt, u, nstr) &&
+                 !(tune && tune->reserved[GPTQ_LAB_GEMM_VARIANT] == GPTQ_LAB_VARIANT_TILED_GENERAL);
     pl.xstride = cps * cke * 2 + 16;
     pl.lds_bytes = lds_need(pl.ksplit, waves);
     pl.xraw_off = A.g_idx ? (int)((pl.lds_bytes - ((size_t)pl.mt * ((size_t)A.K * 2 + 16) + 16) + 15) & ~(size_t)15) : 0;
@@ -259,7 +266,9 @@ hipError_t launch_tiled(const gptq_layer_t* const* Ls, const TiledPlan& pl, cons
     p.pair_strips = pl.pair ? A.N / (2 * GPTQ_STRIP_COLS) : 0;
     if (pg) {                                                                     // plain layers, 2 or 4 chunks per wave in flight (the compiled forms)
         if (A.g_idx || A.bits == 2 || (pl.u != 2 && pl.u != 4)) return hipErrorInvalidValue;
-        return launch_tiled_peer(pl, p, A.dtype, st);                             // gemv_tiled_peer.hip
+        TiledPlan plg = pl;
+        plg.aligned = false;                                                      // the tensor-parallel form has no aligned twin
+        return launch_tiled_peer(plg, p, A.dtype, st);                            // gemv_tiled_peer.hip
     }
     if (pl.pair) return (pl.u == 2 || pl.u == 4) ? launch_tiled_pair(pl, p, A.dtype, st) : hipErrorInvalidValue;   // gemv_tiled_pair.hip
     if (pl.nstr > 1) return (pl.u == 2 || pl.u == 4) ? launch_tiled_multi(pl, p, A.dtype, st) : hipErrorInvalidValue;  // gemv_tiled_multi.hip

@@ -85,8 +85,20 @@ template <int N_> struct WordsOf { typedef unsigned type __attribute__((ext_vect
 // x rows (whole K) into the LDS and gathers its slice through perm LDS -> LDS (one more barrier; + M (2 K + 16) bytes of LDS); the rest is the plain kernel.
 // (XM = 2 was a GATED form -- the down projection of an MLP forming silu(g) * u while staging its input: correct, and no faster than the elementwise launch it
 // removed (20.6 against 20.0 us per Llama-7B MLP: every workgroup repeats the activation); not kept.)
-template <int BITS, int MT, int U, typename T, int MAXW, int XM = 0, int ZM2 = 0>
+// FL (flags; the kernels' names keep seven arguments -- the ISA tests and the tools find them by their full names): bit 0 = ZM2 (below), bit 1 = AL, the ALIGNED
+// form of the K loop: K is a whole number of chunks, so no k-slot is missing, no group index needs a clamp, and every LDS address of a chunk is
+// a lane constant set up in front of the loop plus a scalar of the chunk (TiledPlan.aligned).
+template <int BITS, int MT, int U, typename T, int MAXW, int XM = 0, int FL = 0>
 __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kernel(TiledParams p) {
+    constexpr int ZM2 = FL & 1;
+    // Lab (tools/ab_tiled.sh ABLn -DGPTQ_TILED_ABL=n; timing only, the outputs are WRONG by design; never in the product library; fp16 4-bit forms): bit 1 = every
+    // kernel takes the aligned form's addressing, 2 = no decode (raw words to the matrix core), 4 = no x reads from the LDS, 8 = no matrix-core steps.
+#ifdef GPTQ_TILED_ABL
+    constexpr int ABL = GPTQ_TILED_ABL;
+#else
+    constexpr int ABL = 0;
+#endif
+    constexpr bool AL = (FL & 2) != 0 || (ABL & 1) != 0;
 #ifdef GPTQ_TILED_STAMPS
     unsigned long long st_[9] = {};
     unsigned vz_;
@@ -214,6 +226,7 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
     gchar* const tb = tqs + (size_t)(unsigned)strip_w * ((unsigned)nchunks * (unsigned)CHB);      // this wave's strip of weights: one contiguous run
     gchar* const cg = csts + (size_t)(unsigned)(MULTI ? strip * NSTR : strip) * crec;             // this strip's (MULTI: these strips') constants: one contiguous run
     const unsigned t_lane = (unsigned)lane * (WPL * 4u);
+    [[maybe_unused]] unsigned tlv = t_lane;                                       // AL: the same offset, as the weight loads' only vector operand (wload)
     // ---- stage x and the constants by LDS DMA: no VGPRs, issued FIRST (loads return in issue order), waited for behind the first weight burst.  Every DMA of a
     // thread takes a scalar base and a 32-bit lane offset; a wave without a piece skips a block on one scalar compare (stage_rows)
     auto stage_all = [&]() __attribute__((always_inline)) {
@@ -385,6 +398,17 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
     };
     const char* const xl = xs + (size_t)min(lane & 3, MT - 1) * xstride + kb * (KPL * 2);    // A operand: lane i of a 4-lane group carries x row i
     const char* const xl2 = xs + (size_t)min(4 + (lane & 3), MT - 1) * xstride + kb * (KPL * 2);   // MT = 8: rows 4..7, a second matrix-core step per decoded pair
+    // AL: 32-bit LDS addresses, lane constants.  The group of (chunk c, k-slot kb) is (4 c + kb) >> gu_shift = (4 c >> gu_shift) + (kb >> gu_shift) for every group
+    // size >= KPL (a shift <= 2 divides 4 c; a larger one leaves nothing of kb < 4): a scalar of the chunk plus a constant of the lane.
+    typedef __attribute__((address_space(3))) const char lchar;
+    [[maybe_unused]] lchar* const cl = (lchar*)cs + ((NSTR > 1 ? (unsigned)sel * (unsigned)cpad : 0u) + (unsigned)(kb >> gshift) * (unsigned)REC);
+    [[maybe_unused]] lchar* const sl = cl + col * 2;                              // the lane's scale of group 0
+    [[maybe_unused]] lchar* const zl = cl + 32 + col * F::ZB;                     // ... and its zero-point
+    [[maybe_unused]] lchar* const xll = (lchar*)xl;
+    [[maybe_unused]] lchar* const xll2 = (lchar*)xl2;
+    [[maybe_unused]] unsigned xpass = 0u;                                         // steady loop: LDS offset of the pass's first chunk of x (one VALU per PASS; the chunks are immediates)
+    [[maybe_unused]] unsigned abl_x = 0u;
+    if constexpr ((ABL & 4) != 0) asm("v_mov_b32 %0, 0x3c003c00" : "=v"(abl_x));
     float acc[MT];
 #pragma unroll
     for (int m = 0; m < MT; ++m) acc[m] = 0.f;
@@ -420,7 +444,15 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
     auto seg_pin = [&]() __attribute__((always_inline)) { asm volatile("" : "+s"(N), "+s"(biasp), "+s"(outp)); };
     bool staged = false;
     auto wload = [&](int c) __attribute__((always_inline)) -> qvec {              // chunk c of this wave's strip, clamped into the slice: [cb, ce)
-        return __builtin_nontemporal_load((const __attribute__((address_space(1))) qvec*)(tb + ((unsigned)min(c, ce - 1) * (unsigned)CHB + t_lane)));
+        if constexpr (AL) {                                                       // the chunk in the scalar base, the lane constant as the only vector operand: no VALU
+            // (the base's halves through readfirstlane: left visible, the sum is reassociated into (tb + lane offset) + chunk -- a 64-bit vector add per load)
+            const unsigned long long sb0 = (unsigned long long)tb + (unsigned long long)((unsigned)min(c, ce - 1) * (unsigned)CHB);
+            const unsigned long long sb = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(sb0 >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)sb0);      // (of a scalar: folded to nothing)
+            asm volatile("" : "+v"(tlv));                                         // (pinned per load, in place: hoisted out of the loop, its zero-extension hides the 32-bit offset from instruction selection)
+            return __builtin_nontemporal_load((const __attribute__((address_space(1))) qvec*)((gchar*)sb + tlv));
+        } else {
+            return __builtin_nontemporal_load((const __attribute__((address_space(1))) qvec*)(tb + ((unsigned)min(c, ce - 1) * (unsigned)CHB + t_lane)));
+        }
     };
     auto first_pass = [&]() __attribute__((always_inline)) {                      // (uniform): the staging DMAs are OLDER than the U loads just issued
         TILED_STAMP(1);
@@ -446,27 +478,54 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
         TILED_STAMP(2);
         staged = true;
     };
-    auto chunk = [&](const int cj, const qvec qv) __attribute__((always_inline)) {      // decode chunk cj (dead: >= ce) from its words into acc[]
-        const int cc = min(cj, ce - 1);
-        const int k0 = cc * CKE + kb * KPL;                                   // first k of this lane's words
-        const bool live = (cj < ce) && (k0 < K);                          // a ragged last chunk: whole k-slots are missing
-        const int g = min(k0 >> LKPL >> gshift, G - 1);
-        const char* cp = cs + (NSTR > 1 ? (size_t)sel * cpad : (size_t)0) + g * REC;
-        const unsigned short sraw = *(const unsigned short*)(cp + col * 2);
+    // steady (AL only): chunk j of a pass of the steady loop -- alive by the loop's own condition: no clamp, no select, x at an immediate offset from xpass
+    auto chunk = [&](auto steady_c, const int cj, [[maybe_unused]] const int j, const qvec qv) __attribute__((always_inline)) {      // decode chunk cj (dead: >= ce) from its words into acc[]
+        constexpr bool STEADY = AL && decltype(steady_c)::value;
+        const int cc = STEADY ? cj : min(cj, ce - 1);
+        bool live;
+        unsigned short sraw;
         unsigned z;
-        if constexpr (F::ZB == 1) z = *(const unsigned char*)(cp + 32 + col);
-        else z = *(const unsigned short*)(cp + 32 + col * 2);
         u32x4 xa[NX];
-#pragma unroll
-        for (int w = 0; w < NX; ++w) xa[w] = *(const u32x4*)(xl + ((unsigned)(cc - cb) * (unsigned)(CKE * 2) + w * 16u));
         u32x4 xb[MT > 4 ? NX : 1];
-        if constexpr (MT > 4) {
+        if constexpr (AL) {
+            live = cj < ce;                                                   // wave-uniform: whole chunks only
+            const unsigned go = (unsigned)((cc * 4) >> gshift) * (unsigned)REC;      // scalar
+            sraw = *(const __attribute__((address_space(3))) unsigned short*)(sl + go);
+            if constexpr (F::ZB == 1) z = *(const __attribute__((address_space(3))) unsigned char*)(zl + go);
+            else z = *(const __attribute__((address_space(3))) unsigned short*)(zl + go);
+            typedef __attribute__((address_space(3))) const u32x4 lx4;
+            const unsigned xo = STEADY ? xpass + (unsigned)j * (unsigned)(CKE * 2) : (unsigned)(cc - cb) * (unsigned)(CKE * 2);
+            lchar* const xp = STEADY ? (lchar*)(size_t)xo : xll + xo;
 #pragma unroll
-            for (int w = 0; w < NX; ++w) xb[w] = *(const u32x4*)(xl2 + ((unsigned)(cc - cb) * (unsigned)(CKE * 2) + w * 16u));
+            for (int w = 0; w < NX; ++w) xa[w] = *(lx4*)(xp + w * 16u);
+            if constexpr (MT > 4) {
+                lchar* const xp2 = xp + (xll2 - xll);
+#pragma unroll
+                for (int w = 0; w < NX; ++w) xb[w] = *(lx4*)(xp2 + w * 16u);
+            }
+        } else {
+            const int k0 = cc * CKE + kb * KPL;                               // first k of this lane's words
+            live = (cj < ce) && (k0 < K);                                     // a ragged last chunk: whole k-slots are missing
+            const int g = min(k0 >> LKPL >> gshift, G - 1);
+            const char* cp = cs + (NSTR > 1 ? (size_t)sel * cpad : (size_t)0) + g * REC;
+            sraw = *(const unsigned short*)(cp + col * 2);
+            if constexpr (F::ZB == 1) z = *(const unsigned char*)(cp + 32 + col);
+            else z = *(const unsigned short*)(cp + 32 + col * 2);
+#pragma unroll
+            for (int w = 0; w < NX; ++w) xa[w] = *(const u32x4*)(xl + ((unsigned)(cc - cb) * (unsigned)(CKE * 2) + w * 16u));
+            if constexpr (MT > 4) {
+#pragma unroll
+                for (int w = 0; w < NX; ++w) xb[w] = *(const u32x4*)(xl2 + ((unsigned)(cc - cb) * (unsigned)(CKE * 2) + w * 16u));
+            }
+        }
+        if constexpr ((ABL & 4) != 0) {
+#pragma unroll
+            for (int w = 0; w < NX; ++w) xa[w] = u32x4{abl_x, abl_x, abl_x, abl_x};
         }
         const f16x2 c1 = as_f16x2(z * 0x00010001u + 0xE400E400u);            // -(1024 + z)
         f32x4 accg = {0.f, 0.f, 0.f, 0.f}, accg2 = {0.f, 0.f, 0.f, 0.f};
         auto mm = [&](int pc, int hf, unsigned b0, unsigned b1) __attribute__((always_inline)) {      // 4 k of the lane's column against x piece pc, half hf: rows 0..3 (and 4..7)
+            if constexpr ((ABL & 8) != 0) { asm volatile("" ::"v"(b0), "v"(b1), "v"(xa[pc][hf * 2]), "v"(xa[pc][hf * 2 + 1])); return; }
             accg = Mma4<MM>::run(u32x2{xa[pc][hf * 2], xa[pc][hf * 2 + 1]}, u32x2{b0, b1}, accg);
             if constexpr (MT > 4) accg2 = Mma4<MM>::run(u32x2{xb[pc][hf * 2], xb[pc][hf * 2 + 1]}, u32x2{b0, b1}, accg2);
         };
@@ -498,6 +557,7 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
 #pragma unroll
             for (int w = 0; w < 4; ++w) {
                 const unsigned qw = qv[w], q8 = qw >> 8;
+                if constexpr ((ABL & 2) != 0) { mm(w, 0, qw, qw); mm(w, 1, qw, qw); continue; }
                 const f16x2 h0 = as_f16x2((qw & m_lo) | magic) + c1;          // k0,k1  (stored nibbles 0 and 4)
                 const f16x2 h1 = as_f16x2((qw & m_hi) | magic) * r16 + c2;    // k2,k3  (1 and 5)
                 const f16x2 h2 = as_f16x2((q8 & m_lo) | magic) + c1;          // k4,k5  (2 and 6)
@@ -561,14 +621,14 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
             const float* const xv = xe + ((cc - cb) * 4 + kb) * 4;           // the run's sums of x, one per row
             const float zc = (float)(128u + z);
 #pragma unroll
-            for (int m = 0; m < MT; ++m) acc[m] = live ? fmaf(sc, fmaf(-zc, xv[m], accg[m]), acc[m]) : acc[m];
+            for (int m = 0; m < MT; ++m) acc[m] = (STEADY || live) ? fmaf(sc, fmaf(-zc, xv[m], accg[m]), acc[m]) : acc[m];
         } else if constexpr (XC) {
             const float* const xi = xe + ((cc - cb) * 4 + kb) * 4;           // the run's inverse block factors, one per row
 #pragma unroll
-            for (int m = 0; m < MT; ++m) acc[m] = live ? fmaf(sc * xi[m], accg[m], acc[m]) : acc[m];
+            for (int m = 0; m < MT; ++m) acc[m] = (STEADY || live) ? fmaf(sc * xi[m], accg[m], acc[m]) : acc[m];
         } else {
 #pragma unroll
-            for (int m = 0; m < MT; ++m) acc[m] = live ? fmaf(sc, m < 4 ? accg[m] : accg2[m - 4], acc[m]) : acc[m];   // a select, not a product by 0: a dead slot's x is whatever the LDS holds
+            for (int m = 0; m < MT; ++m) acc[m] = (STEADY || live) ? fmaf(sc, m < 4 ? accg[m] : accg2[m - 4], acc[m]) : acc[m];   // a select, not a product by 0: a dead slot's x is whatever the LDS holds
         }
     };
     // The K loop: a ROLLING refill.  The wave's first U chunks are requested in front of the staging barrier as before; from then on the load of
@@ -589,7 +649,7 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
         if (cbase + Wh * U >= ce) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); TILED_STAMP(3); }      // the last pass's chunks have landed
 #endif
 #pragma unroll
-        for (int j = 0; j < U; ++j) chunk(c0 + j, q[j]);
+        for (int j = 0; j < U; ++j) chunk(std::false_type{}, c0 + j, j, q[j]);
     }
 #else
     if (cb < ce) {                                                                // (an empty slice takes no staging barrier; the planner makes none)
@@ -598,21 +658,23 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
 #pragma unroll
         for (int j = 0; j < U; ++j) q[j] = wload(c0 + j);
         first_pass();
+        if constexpr (AL) { xpass = (unsigned)(size_t)xll + (unsigned)(c0 - cb) * (unsigned)(CKE * 2); asm volatile("" : "+v"(xpass)); }
         for (int cn = c0 + Wh * U; cn < ce; cn += Wh * U) {                       // this wave has a live chunk in the next pass
 #pragma unroll
             for (int j = 0; j < U; ++j) {
-                chunk(c0 + j, q[j]);
+                chunk(std::true_type{}, c0 + j, j, q[j]);
                 __builtin_amdgcn_sched_barrier(0);
                 q[j] = wload(cn + j);
                 __builtin_amdgcn_sched_barrier(0);
             }
             c0 = cn;
+            if constexpr (AL) { xpass += (unsigned)(Wh * U) * (unsigned)(CKE * 2); asm volatile("" : "+v"(xpass)); }
         }
 #ifdef GPTQ_TILED_STAMPS
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); TILED_STAMP(3);          // the last pass's chunks have landed
 #endif
 #pragma unroll
-        for (int j = 0; j < U; ++j) chunk(c0 + j, q[j]);
+        for (int j = 0; j < U; ++j) chunk(std::false_type{}, c0 + j, j, q[j]);
     }
 #endif
     TILED_STAMP(4);
@@ -741,10 +803,22 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
 // outside its compilation is refused by plan_tiled.
 template <int U, int XM> constexpr int tiled_maxw() { return (U == 2 || XM == 5) ? 16 : 8; }
 int tiled_max_waves(int u, int nstr);                                             // the same rule for the planner (gemv_tiled.hip)
+// The forms that have an aligned twin (FL = 2): 4-bit layers at one row, plain and two-strip, and the two-strip form at two rows -- what the
+// library's kernel budget (tests/test_kernel_resources.py) leaves room for; tiled_has_aligned() is the same rule for the planner.
+template <int BITS, int MT, int U, int XM> constexpr bool tiled_aligned_form() { return BITS == 4 && ((XM == 0 && MT == 1) || (XM == 6 && MT <= 2 && U == 4)); }
+bool tiled_has_aligned(int bits, int mt, int u, int nstr);
 template <int BITS, int MT, int U, typename T, int XM>
 static hipError_t launch_tiled_one(const TiledPlan& pl, const TiledParams& p, hipStream_t st) {
     constexpr int MAXW = tiled_maxw<U, XM>();
     if (pl.waves > MAXW) return hipErrorInvalidValue;
+    if constexpr (tiled_aligned_form<BITS, MT, U, XM>()) {
+        if (pl.aligned) {
+            hipLaunchKernelGGL((gemv_tiled_kernel<BITS, MT, U, T, MAXW, XM, 2>), dim3(pl.strips_total * pl.ksplit), dim3(pl.waves * 64), pl.lds_bytes, st, p);
+            return hipGetLastError();
+        }
+    } else if (pl.aligned) {
+        return hipErrorInvalidValue;
+    }
     if constexpr (BITS == 4 && MT == 2 && std::is_same_v<T, bf16> && (XM == 0 || XM == 1)) {      // plain and act-order forms
         if (pl.zm2) {
             hipLaunchKernelGGL((gemv_tiled_kernel<BITS, MT, U, T, MAXW, XM, 1>), dim3(pl.strips_total * pl.ksplit), dim3(pl.waves * 64), pl.lds_bytes, st, p);
@@ -757,7 +831,8 @@ static hipError_t launch_tiled_one(const TiledPlan& pl, const TiledParams& p, hi
 template <int BITS, int MT, typename T, int XM>
 static hipError_t launch_tiled_u(const TiledPlan& pl, const TiledParams& p, hipStream_t st) {
     switch (pl.u) {
-        case 2: if constexpr (!(XM == 6 && MT <= 2)) return launch_tiled_one<BITS, MT, 2, T, XM>(pl, p, st); else return hipErrorInvalidValue;
+        // (the four-strip form with 2 chunks in flight: 4-bit layers only -- no plan but a doubly forced one asks for it, and the 3- / 8-bit ones paid for the aligned twins)
+        case 2: if constexpr (!(XM == 6 && MT <= 2) && !(XM == 5 && BITS != 4)) return launch_tiled_one<BITS, MT, 2, T, XM>(pl, p, st); else return hipErrorInvalidValue;
         case 4: return launch_tiled_one<BITS, MT, 4, T, XM>(pl, p, st);
         default: return hipErrorInvalidValue;
     }
@@ -801,7 +876,8 @@ static hipError_t grant_tiled_lds() {
         auto grant_u = [&](auto bu, auto uu) {
             constexpr int B = decltype(bu)::value, U = decltype(uu)::value;
             constexpr int MAXW = tiled_maxw<U, XM>();
-            grant(gemv_tiled_kernel<B, MT, U, f16, MAXW, XM>); grant(gemv_tiled_kernel<B, MT, U, bf16, MAXW, XM>);
+            if constexpr (!(XM == 5 && B != 4 && U == 2)) { grant(gemv_tiled_kernel<B, MT, U, f16, MAXW, XM>); grant(gemv_tiled_kernel<B, MT, U, bf16, MAXW, XM>); }      // (else: not compiled -- launch_tiled_u)
+            if constexpr (tiled_aligned_form<B, MT, U, XM>()) { grant(gemv_tiled_kernel<B, MT, U, f16, MAXW, XM, 2>); grant(gemv_tiled_kernel<B, MT, U, bf16, MAXW, XM, 2>); }
             if constexpr (B == 4 && MT == 2 && (XM == 0 || XM == 1)) grant(gemv_tiled_kernel<B, MT, U, bf16, MAXW, XM, 1>);
         };
         using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>; using I4 = std::integral_constant<int, 4>; using I8 = std::integral_constant<int, 8>;
@@ -813,6 +889,8 @@ static hipError_t grant_tiled_lds() {
     if constexpr (XM == 6) {                                                      // the 1 - 2-row two-strip form (4 bits, 8 waves x 4 chunks)
         grant(gemv_tiled_kernel<4, 1, 4, f16, 8, 6>); grant(gemv_tiled_kernel<4, 1, 4, bf16, 8, 6>);
         grant(gemv_tiled_kernel<4, 2, 4, f16, 8, 6>); grant(gemv_tiled_kernel<4, 2, 4, bf16, 8, 6>);
+        grant(gemv_tiled_kernel<4, 1, 4, f16, 8, 6, 2>); grant(gemv_tiled_kernel<4, 1, 4, bf16, 8, 6, 2>);      // their aligned twins
+        grant(gemv_tiled_kernel<4, 2, 4, f16, 8, 6, 2>); grant(gemv_tiled_kernel<4, 2, 4, bf16, 8, 6, 2>);
     }
     grant_mt(std::integral_constant<int, 4>{});
     if constexpr (XM != 3 && XM != 4) grant_mt(std::integral_constant<int, 8>{});

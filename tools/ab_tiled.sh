@@ -2,6 +2,8 @@
 # usage (build container): tools/ab_tiled.sh <NAME> [extra hipcc flags...]
 #   tools/ab_tiled.sh ZM1 -DGPTQ_TILED_ZM=1   -> tools/libgptq_ZM1.so = the current objects with the five translation units of the decode-copy kernel
 # (gemv_tiled*.hip include gemv_tiled_kernel.cuh) rebuilt with the flags; select the library with GPTQ_MI355X_LIB=tools/libgptq_ZM1.so
+#   tools/ab_tiled.sh ABL1 -DGPTQ_TILED_ABL=1  -> the K-loop ablations of DESIGN.md 14 (TIMING ONLY: the outputs are wrong by design).  Bits, or-ed: 1 = every kernel
+#   takes the aligned form's addressing, 2 = no decode (raw words to the matrix core), 4 = no x reads from the LDS, 8 = no matrix-core steps (fp16 4-bit forms).
 set -eu
 NAME=$1; shift
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

@@ -1183,7 +1183,8 @@ static int moe_check_proj(const gptq_layer_t* const* Ls, int E, int K, int N, in
 
 static int moe_check(const gptq_moe_t* m, int T, int topk) {
     if (!m) return fail(GPTQ_ERR_NULL, "moe is NULL");
-    if (m->flags & ~GPTQ_MOE_LOW_BIT) return fail(GPTQ_ERR_UNSUPPORTED, "moe->flags = 0x%x: unknown flag bits (GPTQ_MOE_LOW_BIT is the only one)", (unsigned)m->flags);
+    if (m->flags & ~(GPTQ_MOE_LOW_BIT | GPTQ_MOE_LOW_BIT_DECODE))      // (GPTQ_MOE_LOW_BIT_DECODE: a known bit of the decode path's, nothing here reads it)
+        return fail(GPTQ_ERR_UNSUPPORTED, "moe->flags = 0x%x: unknown flag bits (GPTQ_MOE_LOW_BIT and GPTQ_MOE_LOW_BIT_DECODE are the only ones)", (unsigned)m->flags);
     if (m->E < 1 || m->E > 256) return fail(GPTQ_ERR_UNSUPPORTED, "E = %d experts: the grouped path takes 1..256", m->E);
     if (topk < 1 || topk > 8) return fail(GPTQ_ERR_UNSUPPORTED, "topk = %d: the grouped path takes 1..8", topk);
     if (T < 0) return fail(GPTQ_ERR_SHAPE, "T must be >= 0, got %d", T);
@@ -1358,7 +1359,8 @@ static int moe_decode_check(const gptq_moe_t* m, int T, int topk) {
     const gptq_layer_t* G = m->gate[0];
     if (int rc = check_layer(G)) return rc;
     if (G->dtype != GPTQ_F16 && G->dtype != GPTQ_BF16) return fail(GPTQ_ERR_UNSUPPORTED, "fp32 experts: the decode path takes fp16 / bf16");
-    if (G->bits != 4 && G->bits != 8) return fail(GPTQ_ERR_UNSUPPORTED, "%d-bit experts: the decode path takes 4 or 8 bits", G->bits);
+    if (G->bits != 4 && G->bits != 8 && !(m->flags & GPTQ_MOE_LOW_BIT_DECODE))      // (check_layer: 2, 3, 4 or 8 -- with the flag the 2- / 3-bit forms of moe_shared.hip serve them)
+        return fail(GPTQ_ERR_UNSUPPORTED, "%d-bit experts: the decode path takes 4 or 8 bits", G->bits);
     const int H = G->K, I = G->N;
     if (H % 64 || I % 64) return fail(GPTQ_ERR_UNSUPPORTED, "hidden (%d) and intermediate (%d) sizes must be multiples of 64", H, I);
     if (int rc = moe_decode_check_proj(m->gate, m->E, H, I, G, "gate")) return rc;
@@ -1450,6 +1452,8 @@ static int moe_shared_check_layer(const gptq_layer_t* L, int K, int N, const gpt
 
 static int moe_shared_check(const gptq_moe_t* m, const gptq_moe_shared_t* sh, int T, int topk) {
     if (int rc = moe_decode_check(m, T, topk)) return rc;
+    if (m->gate[0]->bits == 2 || m->gate[0]->bits == 3)      // (in front of everything that reads the shared layers: no form of the fused launches decodes these widths)
+        return fail(GPTQ_ERR_UNSUPPORTED, "%d-bit routed experts: the shared decode form takes 4 or 8 bits (2- and 3-bit experts run gptq_moe_decode_forward and the combine tail)", m->gate[0]->bits);
     if (!sh) return fail(GPTQ_ERR_NULL, "shared is NULL");
     if (sh->flags || sh->reserved) return fail(GPTQ_ERR_UNSUPPORTED, "shared->flags / reserved must be 0");
     if (!sh->gate || !sh->up || !sh->down) return fail(GPTQ_ERR_NULL, "shared->gate / up / down must be non-NULL");

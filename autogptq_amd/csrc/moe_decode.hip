@@ -18,7 +18,8 @@
 //      thread c keeps total += w[t, j] * sum in a register; one rounding at the store.  (The alternative -- a workgroup per (assignment, strip) into fp32
 //      rows plus moe_combine_kernel, three launches -- computes the same bits; it is not built: DESIGN 4.8.)
 // The body of both launches lives in moe_decode_kernel.cuh (moe_decode_body<T, BITS, PAIR, SHARED>): these kernels are its SHARED = false form, and
-// moe_shared.hip compiles the SHARED = true form (the shared expert of a Qwen-MoE block in the same two launches) into a kernel of its own.
+// moe_shared.hip compiles the SHARED = true form (the shared expert of a Qwen-MoE block in the same two launches) into a kernel of its own.  2- and 3-bit
+// experts (GPTQ_MOE_LOW_BIT_DECODE): the same two launches with the same grids, arguments and LDS bytes, on the 2- / 3-bit forms of that kernel.
 // No K slices, no atomics: every output is one thread's sum in a fixed order, so results are bit-reproducible and the row of token t does not depend on the
 // other tokens of the call.
 // Layout read: gptq_layer_t.qweight_tiled / qconst_tiled (include/gptq_mi355x.h): a strip is one contiguous run, a chunk (4 k-slots x 16 columns) one wave
@@ -44,6 +45,7 @@ static hipError_t launch_one(const Args& a, dim3 grid, int lds, hipStream_t st) 
 }
 template <bool PAIR>
 static hipError_t launch_any(int dtype, int bits, const Args& a, dim3 grid, int lds, hipStream_t st) {
+    if (bits == 2 || bits == 3) return launch_low_bit_form(PAIR, dtype, bits, a, grid, lds, st);      // (GPTQ_MOE_LOW_BIT_DECODE) forms of moe_shared.hip's kernel, not kernels of this file
     if (dtype == GPTQ_F16) return bits == 4 ? launch_one<f16, 4, PAIR>(a, grid, lds, st) : launch_one<f16, 8, PAIR>(a, grid, lds, st);
     return bits == 4 ? launch_one<bf16, 4, PAIR>(a, grid, lds, st) : launch_one<bf16, 8, PAIR>(a, grid, lds, st);
 }

@@ -1,6 +1,7 @@
 // moe_decode_kernel.cuh -- the body of the two decode launches of a routed mixture-of-experts layer, moe_decode_body<T, BITS, PAIR, SHARED>:
 //   SHARED = false  moe_decode.hip's moe_decode_kernel<T, BITS, PAIR>, the routed experts alone (every `sh` below is a constant false: the code of the
-//                   kernels as they were before the shared form existed)
+//                   kernels as they were before the shared form existed); at BITS 3 and 2 (GPTQ_MOE_LOW_BIT_DECODE) the same compilation runs as
+//                   forms 10..17 of moe_shared.hip's kernel -- the library's kernel count is guarded, so those widths are forms, not kernels
 //   SHARED = true   moe_shared.hip: the always-on shared expert of a Qwen-MoE block served by the same two launches
 //
 // A SEGMENT is one streamed strip (pair: one strip of W1 next to the same strip of W3) against one staged activation row.  The routed kernels run one
@@ -99,6 +100,19 @@ __device__ __forceinline__ void moe_decode_body(const Args& p, const Shared& sp)
     asm("s_mov_b32 %0, 0x00f000f0" : "=s"(m_hi));
     asm("s_mov_b32 %0, 0x00ff00ff" : "=s"(m_b));
     asm("v_mov_b32 %0, 0x64006400" : "=v"(magic));
+    [[maybe_unused]] unsigned m2a, m2b, m2c, m2d, m2e, m3a, m3b, m3c;            // the 2- and 3-bit forms' field masks (unused ones leave no instruction)
+    if constexpr (BITS == 2) {
+        asm("s_mov_b32 %0, 0x00030003" : "=s"(m2a));
+        asm("s_mov_b32 %0, 0x000c000c" : "=s"(m2b));
+        asm("s_mov_b32 %0, 0x00300030" : "=s"(m2c));
+        asm("s_mov_b32 %0, 0x00c000c0" : "=s"(m2d));
+        asm("s_mov_b32 %0, 0x03000300" : "=s"(m2e));
+    }
+    if constexpr (BITS == 3) {
+        asm("s_mov_b32 %0, 0x00070007" : "=s"(m3a));
+        asm("s_mov_b32 %0, 0x00380038" : "=s"(m3b));
+        asm("s_mov_b32 %0, 0x01c001c0" : "=s"(m3c));
+    }
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -120,6 +134,8 @@ __device__ __forceinline__ void moe_decode_body(const Args& p, const Shared& sp)
     const unsigned t_lane = (unsigned)lane * (WPL * 4u);
     const f16x2 k960 = {(f16)960.f, (f16)960.f};
     const f16x2 r16 = {(f16)0.0625f, (f16)0.0625f};
+    [[maybe_unused]] const f16x2 k768 = {(f16)768.f, (f16)768.f}, k896 = {(f16)896.f, (f16)896.f}, k1008 = {(f16)1008.f, (f16)1008.f}, k1020 = {(f16)1020.f, (f16)1020.f};
+    [[maybe_unused]] const f16x2 r4 = {(f16)0.25f, (f16)0.25f}, r8 = {(f16)0.125f, (f16)0.125f}, r64 = {(f16)0.015625f, (f16)0.015625f}, r256 = {(f16)0.00390625f, (f16)0.00390625f};
     auto bits_of = [&](f16x2 hv) -> unsigned {                                    // the pair as the matrix core takes it (bf16: fp16 -> fp32 -> bf16, exact: small integers)
         if constexpr (BF) {
             const bf16x2 o = {(bf16)(float)hv[0], (bf16)(float)hv[1]};
@@ -267,13 +283,58 @@ __device__ __forceinline__ void moe_decode_body(const Args& p, const Shared& sp)
                         mm(w, 0, bits_of(h0), bits_of(h1));
                         mm(w, 1, bits_of(h2), bits_of(h3));
                     }
-                } else {
+                } else if constexpr (BITS == 8) {
 #pragma unroll
                     for (int w = 0; w < 4; ++w) {                                 // one word = 4 k = one matrix-core step
                         const unsigned qw = qv[w], q8 = qw >> 8;
                         const f16x2 h0 = as_f16x2((qw & m_b) | magic) + c1;       // k0,k1  (stored bytes 0 and 2)
                         const f16x2 h1 = as_f16x2((q8 & m_b) | magic) + c1;       // k2,k3  (1 and 3)
                         mm(w >> 1, w & 1, bits_of(h0), bits_of(h1));
+                    }
+                } else if constexpr (BITS == 2) {
+                    // the dense decode kernel's 2-bit branch (gemv_tiled_kernel.cuh): the five pairs at bits 0..9 in place (1024 + 4^p w, times 4^-p, minus
+                    // (1024 / 4^p + z): exact), the three at bits 10..15 behind a shift
+                    const f16x2 c4 = c1 + k768, c16 = c1 + k960, c64 = c1 + k1008, c256 = c1 + k1020;      // -(256 + z), -(64 + z), -(16 + z), -(4 + z)
+#pragma unroll
+                    for (int w = 0; w < 2; ++w) {
+                        const unsigned t = qv[w], t10 = t >> 10;
+                        const unsigned p0 = bits_of(as_f16x2((t & m2a) | magic) + c1);
+                        const unsigned p1 = bits_of(as_f16x2((t & m2b) | magic) * r4 + c4);
+                        const unsigned p2 = bits_of(as_f16x2((t & m2c) | magic) * r16 + c16);
+                        const unsigned p3 = bits_of(as_f16x2((t & m2d) | magic) * r64 + c64);
+                        const unsigned p4 = bits_of(as_f16x2((t & m2e) | magic) * r256 + c256);
+                        const unsigned p5 = bits_of(as_f16x2((t10 & m2a) | magic) + c1);
+                        const unsigned p6 = bits_of(as_f16x2((t10 & m2b) | magic) * r4 + c4);
+                        const unsigned p7 = bits_of(as_f16x2((t10 & m2c) | magic) * r16 + c16);
+                        mm(2 * w, 0, p0, p1);
+                        mm(2 * w, 1, p2, p3);
+                        mm(2 * w + 1, 0, p4, p5);
+                        mm(2 * w + 1, 1, p6, p7);
+                    }
+                } else {
+                    // 3 bits, the dense decode kernel's branch: word j holds the pairs 5 j + i at bit 3 i of its halves, no field straddles a word; the
+                    // pairs are consumed as they are produced (two at a time, in k order), pair 15 = bits 15 / 31 of the three words
+                    static_assert(BITS == 3, "moe_decode_body: 2, 3, 4 or 8 bits");
+                    const f16x2 c3 = c1 + k896;                                   // -(128 + z): fields at bit 3, times 1/8
+                    const f16x2 c6 = c1 + k1008;                                  // -(16 + z): fields at bit 6, times 1/64
+                    auto field = [&](int pi) __attribute__((always_inline)) -> unsigned {      // pair pi of the unit (compile-time pi)
+                        if (pi == 15) {
+                            const unsigned e15 = ((qv[0] >> 15) & 0x00010001u) | ((qv[1] >> 14) & 0x00020002u) | ((qv[2] >> 13) & 0x00040004u);
+                            return bits_of(as_f16x2(e15 | magic) + c1);
+                        }
+                        const unsigned t = qv[pi / 5], t6 = t >> 6;
+                        switch (pi % 5) {
+                            case 0: return bits_of(as_f16x2((t & m3a) | magic) + c1);
+                            case 1: return bits_of(as_f16x2((t & m3b) | magic) * r8 + c3);
+                            case 2: return bits_of(as_f16x2((t & m3c) | magic) * r64 + c6);
+                            case 3: return bits_of(as_f16x2((t6 & m3b) | magic) * r8 + c3);
+                            default: return bits_of(as_f16x2((t6 & m3c) | magic) * r64 + c6);
+                        }
+                    };
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        const unsigned b0 = field(2 * i), b1 = field(2 * i + 1);
+                        mm(i >> 1, i & 1, b0, b1);
                     }
                 }
                 const float sc = DType<T>::to_f32(__builtin_bit_cast(T, sraw));
@@ -349,6 +410,10 @@ static inline void fill_geometry(A& a, const gptq_layer_t& L, bool act, bool pai
     const Lds l = lds_layout(L.K, a.groups, L.bits, act, pair, waves);
     a.off_xs0 = l.off_xs0; a.off_xs1 = l.off_xs1; a.off_cs = l.off_cs; a.cpad = l.cpad;
 }
+
+// moe_shared.hip: one launch of the routed experts alone at 2 or 3 bits -- moe_decode_body<T, BITS, PAIR, false> as a form of moe_shared_kernel (the
+// library's kernel count is guarded: a form, not a kernel), on a.waves waves; grid, arguments and LDS bytes as moe_decode_kernel takes them
+hipError_t launch_low_bit_form(bool pair, int dtype, int bits, const Args& a, dim3 grid, int lds, hipStream_t st);
 
 static inline size_t a256(size_t b) { return (b + 255) & ~(size_t)255; }      // the workspace's rounding
 static inline bool any_perm(const gptq_layer_t* const* Ls, int E) {

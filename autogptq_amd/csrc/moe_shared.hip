@@ -56,9 +56,21 @@ __device__ __forceinline__ void combine_rows(const void* x, const void* gate_w, 
 // kernel's register count is the largest of theirs (the 4-bit down form's), which keeps 16-wave workgroups at 4 waves per SIMD.
 //   form 0..7  moe_decode_body<T, BITS, PAIR, true>: 4 (T = bf16) + 2 (BITS = 8) + 1 (PAIR)
 //   form 8, 9  the combine tail for fp16 / bf16: x = sp.a, gate_w = sp.gate_w, ys = p.a, out = p.out, H = sp.K
-constexpr int FORM_COMBINE = 8;
+//   form 10..17  the ROUTED experts alone at 3 and 2 bits (gptq_moe_decode_forward with GPTQ_MOE_LOW_BIT_DECODE): moe_decode_body<T, BITS, PAIR, false>,
+//              10 + 4 (T = bf16) + 2 (BITS = 2) + 1 (PAIR) -- the SHARED = false compilation reads nothing of sp but form and runs on p.waves.
+//              The kernel keeps its 63 VGPRs with them.  Their cases stand in front of the others: of the two orders measured, the one that left forms
+//              0..9 closer to their times before (profiles/moe_lowbit_decode_ab.log).
+constexpr int FORM_COMBINE = 8, FORM_LOW_BIT = 10;
 __global__ void __launch_bounds__(1024) moe_shared_kernel(Args p, Shared sp) {
     switch (sp.form) {
+        case FORM_LOW_BIT + 0: moe_decode_body<f16, 3, false, false>(p, sp); break;
+        case FORM_LOW_BIT + 1: moe_decode_body<f16, 3, true, false>(p, sp); break;
+        case FORM_LOW_BIT + 2: moe_decode_body<f16, 2, false, false>(p, sp); break;
+        case FORM_LOW_BIT + 3: moe_decode_body<f16, 2, true, false>(p, sp); break;
+        case FORM_LOW_BIT + 4: moe_decode_body<bf16, 3, false, false>(p, sp); break;
+        case FORM_LOW_BIT + 5: moe_decode_body<bf16, 3, true, false>(p, sp); break;
+        case FORM_LOW_BIT + 6: moe_decode_body<bf16, 2, false, false>(p, sp); break;
+        case FORM_LOW_BIT + 7: moe_decode_body<bf16, 2, true, false>(p, sp); break;
         case 0: moe_decode_body<f16, 4, false, true>(p, sp); break;
         case 1: moe_decode_body<f16, 4, true, true>(p, sp); break;
         case 2: moe_decode_body<f16, 8, false, true>(p, sp); break;
@@ -75,6 +87,14 @@ __global__ void __launch_bounds__(1024) moe_shared_kernel(Args p, Shared sp) {
 static hipError_t launch_form(bool pair, int dtype, int bits, const Args& a, Shared s, dim3 grid, int lds, hipStream_t st) {
     s.form = (dtype == GPTQ_BF16 ? 4 : 0) + (bits == 8 ? 2 : 0) + (pair ? 1 : 0);
     hipLaunchKernelGGL(moe_shared_kernel, grid, dim3(s.block_waves * 64), lds, st, a, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_low_bit_form(bool pair, int dtype, int bits, const Args& a, dim3 grid, int lds, hipStream_t st) {
+    if ((bits != 2 && bits != 3) || (dtype != GPTQ_F16 && dtype != GPTQ_BF16)) return hipErrorInvalidValue;
+    Shared s{};
+    s.form = FORM_LOW_BIT + (dtype == GPTQ_BF16 ? 4 : 0) + (bits == 2 ? 2 : 0) + (pair ? 1 : 0);
+    hipLaunchKernelGGL(moe_shared_kernel, grid, dim3(a.waves * 64), lds, st, a, s);
     return hipGetLastError();
 }
 

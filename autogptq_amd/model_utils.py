@@ -88,7 +88,7 @@ def pack_model(model: nn.Module, quantizers: dict, bits: int, group_size: int, d
 def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_length: Optional[int] = None,
                        release_checkpoint_layout: Optional[bool] = None, decode_copy: Optional[bool] = None,
                        expert_decode_copy: bool = False, expert_batched_decode: bool = False, expert_backward: bool = False, expert_low_bit: bool = False,
-                       expert_prefill: bool = False) -> nn.Module:
+                       expert_prefill: bool = False, expert_low_bit_decode: bool = False) -> nn.Module:
     """post_init every mi355x layer and size the per-device scratch once (so forward never allocates; needed before hipGraph
     capture).  ``max_input_length`` bounds the rows M the scratch is sized for (default 2048, the reference's exllama default).
     Memory (the model-level switches for what post_init keeps next to the checkpoint tensors): ``decode_copy=False`` builds no decode copy (1x the packed
@@ -108,6 +108,9 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
     experts, and the expert decode copy keeps declining 2 / 3 bits.  ``expert_prefill=True`` (implies the expert decode copy;
     ``QuantMoEExperts.post_init(prefill=True)``): calls of 65 tokens and more run the prefill kernels on that copy (64-row panels, one
     gptq_moe_prefill_forward call) instead of the grouped path; the scratch covers ``gptq_moe_prefill_workspace_bytes`` of ``max_input_length`` tokens.
+    ``expert_low_bit_decode=True`` (``QuantMoEExperts.post_init(low_bit_decode=True)``): 2- and 3-bit experts get a decode copy (counted with the other
+    expert copies) and calls of 1..4 tokens run the decode kernels on it; it stands next to ``expert_low_bit`` (which serves the larger calls) and
+    ``expert_decode_copy``, and changes nothing for 4- and 8-bit experts.
     Blocks bound by ``inject_shared_expert`` before this call: the scratch also covers ``gptq_moe_shared_decode_workspace_bytes`` of 1..4 tokens."""
     from .moe import QuantMoEExperts
     rows = max_input_length or 2048
@@ -119,7 +122,7 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
         if isinstance(sub, QuantMoEExperts) and sub[0].layers()[0].qweight.device.type == "cuda":
             dev = sub[0].layers()[0].qweight.device
             sub.post_init(decode_copy=expert_decode_copy, batch=expert_batched_decode, backward=expert_backward, low_bit=expert_low_bit,
-                          prefill=expert_prefill)
+                          prefill=expert_prefill, low_bit_decode=expert_low_bit_decode)
             for e in range(sub.num_experts):
                 in_experts.update(id(l) for l in sub[e].layers())
             expert_copy_bytes += sub.decode_copy_bytes

@@ -26,6 +26,7 @@
                         ``Glm4MoeMoE``s, on the instances.  Opt-in.
 * ``pack_moe_experts``  pack the dense 3-D expert parameters of a model (``quantizers`` keyed ``...mlp.experts.{e}.w1`` as ``pack_model`` takes)
 
+2- and 3-bit experts: ``post_init(low_bit=True)`` opens the grouped path to them, ``post_init(low_bit_decode=True)`` the decode path (1..4 tokens).
 The per-expert composition serves what the grouped kernels do not take (2- / 3-bit experts unless ``post_init(low_bit=True)``, fp32 experts, odd group
 sizes, raw act-order), CPU tensors (which ``QuantLinear`` refuses), and -- by default -- calls under grad where ``hidden_states`` or ``top_k_weights`` require grad: training through the experts gets
 dX and the router-weight gradient from the existing backward of ``QuantLinear``.  After ``post_init(backward=True)`` such a call is ONE autograd node
@@ -86,7 +87,9 @@ class QuantMoEExperts(nn.Module):
         self._backward = False
         self._low_bit = False
         self._prefill = False
+        self._low_bit_decode = False
         self.batch_max_tokens = 64
+        self.low_bit_decode_max_tokens = 4          # 2- / 3-bit experts with low_bit_decode=True: the decode path up to this many tokens (the kernels take 4)
         for e in range(num_experts):
             self.add_module(str(e), _Expert(self.names, bits, group_size, hidden_dim, intermediate_dim, weight_dtype, zero_mode))
         self._invalidate()
@@ -123,7 +126,8 @@ class QuantMoEExperts(nn.Module):
         return [l[0] for l in ls], [l[1] for l in ls], [l[2] for l in ls]
 
     # ------------------------------------------------------------------ post_init
-    def post_init(self, decode_copy: bool = False, batch: bool = False, backward: bool = False, low_bit: bool = False, prefill: bool = False):
+    def post_init(self, decode_copy: bool = False, batch: bool = False, backward: bool = False, low_bit: bool = False, prefill: bool = False,
+                  low_bit_decode: bool = False):
         """post_init every expert layer and build the pointer table.  Default: WITHOUT a decode copy (1x the packed bytes; act-order layers add their
         re-sequenced rows) -- calls of any row count run the grouped kernels.  ``decode_copy=True``: the layers also get their decode copy (2x the packed
         bytes; both layouts stay resident: the grouped path still serves more than 4 tokens), the decode table is built, and calls of 1..4 tokens run the
@@ -137,12 +141,17 @@ class QuantMoEExperts(nn.Module):
         decode and batch paths keep declining 2 / 3 bits.  ``prefill=True`` (opt-in as well; builds the decode copy and its table if not asked for already): calls of 65
         tokens and more run the prefill kernels on the copy (``plan(T)["path"] == "prefill"``: 64-row panels of the routed rows, one
         gptq_moe_prefill_forward call) instead of the grouped path; experts the prefill plan declines log the reason once and behave as without the
-        flag.  ``decode_copy_bytes`` reports what the copies hold.  A checkpoint-layout release does not apply to expert layers."""
+        flag.  ``low_bit_decode=True`` (opt-in as well; implies ``decode_copy=True`` for such experts): 2- and 3-bit experts get their decode copy and
+        calls of 1..``low_bit_decode_max_tokens`` (4) tokens run the decode kernels (``plan(T)["path"] == "decode"``); more tokens run the grouped
+        path with ``low_bit=True``, else the per-expert composition.  ``batch=True`` / ``prefill=True`` have no effect on such experts (logged, dropped);
+        the keyword changes nothing for 4- and 8-bit experts.  ``decode_copy_bytes`` reports what the copies hold.  A checkpoint-layout release does not apply to expert layers."""
         dev = self[0].layers()[0].qweight.device
         if dev.type != "cuda":
             raise RuntimeError(f"mi355x QuantMoEExperts.post_init needs the module on a ROCm GPU device (got {dev}); there is no CPU path.")
         want_decode, self._batch, self._backward, self._low_bit = bool(decode_copy), bool(batch), bool(backward), bool(low_bit)
-        self._prefill = bool(prefill)
+        self._prefill, self._low_bit_decode = bool(prefill), bool(low_bit_decode)
+        if self._low_bit_decode and self.bits in (2, 3):
+            want_decode = True
         if self._prefill:
             why = self._prefill_declined()
             if why:
@@ -170,7 +179,7 @@ class QuantMoEExperts(nn.Module):
         arrs = [(ctypes.POINTER(_lib.GptqLayer) * self.num_experts)(*[ctypes.pointer(l._layer) for l in ls]) for ls in (gate, up, down)]
         m = _lib.GptqMoe()
         m.E = self.num_experts
-        m.flags = _lib.MOE_LOW_BIT if self._low_bit else 0
+        m.flags = (_lib.MOE_LOW_BIT if self._low_bit else 0) | (_lib.MOE_LOW_BIT_DECODE if self._low_bit_decode else 0)
         m.gate, m.up, m.down = (ctypes.addressof(a) for a in arrs)
         table = torch.zeros(max(1, int(lib.gptq_moe_table_bytes(self.num_experts))), dtype=torch.uint8, device=dev)
         self._moe, self._keep, self._plans = m, (arrs, table, gate, up, down), {}
@@ -201,15 +210,17 @@ class QuantMoEExperts(nn.Module):
                 # declined (2- / 3-bit, fp32, a group size the copy does not take, ...): nothing would read the copies -- say so and give their memory back
                 logger.warning("QuantMoEExperts.post_init(decode_copy=True) has no effect for these experts (%s): no decode copy is kept",
                                str(dplan.get("reason", "")).replace("_", " "))
-                return self.post_init(decode_copy=False, backward=self._backward, low_bit=self._low_bit)      # (batch and prefill need the copy: declined with it)
+                return self.post_init(decode_copy=False, backward=self._backward, low_bit=self._low_bit)      # (batch, prefill and low_bit_decode need the copy: declined with it)
             bplan = _lib.describe_moe_batch_plan(m, 5, self.top_k) if self._batch else None
             if bplan is not None and bplan["path"] != "batch":
                 logger.warning("QuantMoEExperts.post_init(batch=True) has no effect for these experts (%s)", str(bplan.get("reason", "")).replace("_", " "))
-                return self.post_init(decode_copy=want_decode, backward=self._backward, low_bit=self._low_bit, prefill=self._prefill)
+                return self.post_init(decode_copy=want_decode, backward=self._backward, low_bit=self._low_bit, prefill=self._prefill,
+                                      low_bit_decode=self._low_bit_decode)
             pplan = _lib.describe_moe_prefill_plan(m, 65, self.top_k) if self._prefill else None
             if pplan is not None and pplan["path"] != "prefill":
                 logger.warning("QuantMoEExperts.post_init(prefill=True) has no effect for these experts (%s)", str(pplan.get("reason", "")).replace("_", " "))
-                return self.post_init(decode_copy=want_decode, batch=self._batch, backward=self._backward, low_bit=self._low_bit)
+                return self.post_init(decode_copy=want_decode, batch=self._batch, backward=self._backward, low_bit=self._low_bit,
+                                      low_bit_decode=self._low_bit_decode)
             dtable = torch.zeros(max(1, int(lib.gptq_moe_decode_table_bytes(self.num_experts))), dtype=torch.uint8, device=dev)
             with torch.cuda.device(self._dev):
                 _lib.check(lib.gptq_moe_build_decode_table(ctypes.byref(m), dtable.data_ptr(), _lib.current_stream_handle(self._dev)))
@@ -229,6 +240,8 @@ class QuantMoEExperts(nn.Module):
             q = gs // 128
             if not (gs in (32, 64) or gs >= K or (gs % 128 == 0 and q & (q - 1) == 0)):
                 return f"group_size {gs}: the batch path takes 32, 64, 128 times a power of two, or one group"
+        if self.bits in (2, 3):
+            return f"{self.bits}-bit experts: the batch path takes 4 or 8 bits"
         return self._decode_copy_declined().replace("the decode path", "the batch path")
 
     def _prefill_declined(self) -> str:
@@ -241,12 +254,14 @@ class QuantMoEExperts(nn.Module):
             q = gs // 64
             if not (gs >= K or (gs % 64 == 0 and q & (q - 1) == 0)):
                 return f"group_size {gs}: the prefill path takes 64 times a power of two, or one group"
+        if self.bits in (2, 3):
+            return f"{self.bits}-bit experts: the prefill path takes 4 or 8 bits"
         return self._decode_copy_declined().replace("the decode path", "the prefill path")
 
     def _decode_copy_declined(self) -> str:
         """Why the decode plan would decline these experts, as far as the layer metadata says (empty: build the copies and ask the plan)."""
         gate, _, down = self[0].layers()
-        if self.bits not in (4, 8):
+        if self.bits not in (4, 8) and not (self._low_bit_decode and self.bits in (2, 3)):
             return f"{self.bits}-bit experts: the decode path takes 4 or 8 bits"
         if gate.scales.dtype not in (torch.float16, torch.bfloat16):
             return "fp32 experts: the decode path takes fp16 / bf16"
@@ -265,7 +280,7 @@ class QuantMoEExperts(nn.Module):
     def workspace_bytes(self, T: int, top_k: "int | None" = None) -> int:
         """Scratch of one call with T tokens on the path ``plan(T)`` names."""
         if self._moe is None:
-            self.post_init(self._decode_copy, self._batch, self._backward, self._low_bit, self._prefill)
+            self.post_init(self._decode_copy, self._batch, self._backward, self._low_bit, self._prefill, self._low_bit_decode)
         path = self.plan(T, top_k)["path"]
         if path == "decode":
             return int(_lib.load().gptq_moe_decode_workspace_bytes(ctypes.byref(self._moe), T, top_k or self.top_k))
@@ -278,7 +293,7 @@ class QuantMoEExperts(nn.Module):
     def backward_workspace_bytes(self, T: int, top_k: "int | None" = None) -> int:
         """Scratch of one gptq_moe_backward call with T tokens (0 when the experts have no grouped backward)."""
         if self._moe is None:
-            self.post_init(self._decode_copy, self._batch, self._backward, self._low_bit, self._prefill)
+            self.post_init(self._decode_copy, self._batch, self._backward, self._low_bit, self._prefill, self._low_bit_decode)
         if self._grad_table is None:
             return 0
         return int(_lib.load().gptq_moe_backward_workspace_bytes(ctypes.byref(self._moe), T, top_k or self.top_k))
@@ -292,11 +307,12 @@ class QuantMoEExperts(nn.Module):
         if self[0].layers()[0].qweight.device.type != "cuda":
             return {"path": "per_expert", "reason": "cpu tensors"}
         if self._moe is None:
-            self.post_init(self._decode_copy, self._batch, self._backward, self._low_bit, self._prefill)
-        key = (T, top_k, self.batch_max_tokens)
+            self.post_init(self._decode_copy, self._batch, self._backward, self._low_bit, self._prefill, self._low_bit_decode)
+        dmax = min(4, int(self.low_bit_decode_max_tokens)) if self.bits in (2, 3) else 4
+        key = (T, top_k, self.batch_max_tokens, dmax)
         d = self._plans.get(key)
         if d is None:
-            if self._decode_table is not None and 0 < T <= 4:
+            if self._decode_table is not None and 0 < T <= dmax:
                 d = _lib.describe_moe_decode_plan(self._moe, T, top_k)
                 if d["path"] != "decode":
                     d = None
@@ -406,7 +422,7 @@ def moe_forward(experts: QuantMoEExperts, x: torch.Tensor, top_k_index: torch.Te
 def _grouped_backward_ready(experts: QuantMoEExperts) -> bool:
     """The experts were post-initialised with backward=True and the backward plan took them (post_init runs here when the tables were invalidated)."""
     if experts._moe is None:
-        experts.post_init(experts._decode_copy, experts._batch, experts._backward, experts._low_bit, experts._prefill)
+        experts.post_init(experts._decode_copy, experts._batch, experts._backward, experts._low_bit, experts._prefill, experts._low_bit_decode)
     return experts._grad_table is not None
 
 

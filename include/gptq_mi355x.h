@@ -371,12 +371,17 @@ int gptq_describe_adapter_rows_plan(const gptq_adapter_bank_t *const *banks, int
  * GPTQ_ERR_UNSUPPORTED with the reason (the caller composes the layer from per-expert gptq_forward calls instead).
  * flags: 0, or GPTQ_MOE_LOW_BIT: the grouped path (gptq_moe_build_table / gptq_moe_forward, gptq_moe_build_grad_table / gptq_moe_backward and their
  * describe / workspace twins) also takes 2- and 3-bit experts -- same contract, same workspace; gate and up still share their width, down may have
- * another (3-bit gate | up with 4-bit down is legal).  The decode and the batch path decline 2 / 3 bits whatever the flag says.  Unknown flag bits:
- * GPTQ_ERR_UNSUPPORTED. */
+ * another (3-bit gate | up with 4-bit down is legal).  The decode and the batch path decline 2 / 3 bits whatever this flag says.
+ * GPTQ_MOE_LOW_BIT_DECODE (independent of GPTQ_MOE_LOW_BIT; the two may be or-ed): the DECODE path (gptq_moe_build_decode_table /
+ * gptq_moe_decode_forward and their describe / workspace twins, T <= 4) also takes 2- and 3-bit experts with a decode copy -- same contract, same
+ * workspace, same plan keys; gate, up and down share one width there as at 4 / 8 bits.  The grouped and the backward entry points ignore it (flags 8 / 9
+ * behave as 0 / 1); the batch, the prefill and the fused shared-expert entry points decline 2 / 3 bits whatever the flags say.  Without the flag every
+ * entry point answers as it did.  Unknown flag bits (2 and 4 among them): GPTQ_ERR_UNSUPPORTED from the grouped and the backward entry points. */
 #define GPTQ_MOE_LOW_BIT 1
+#define GPTQ_MOE_LOW_BIT_DECODE 8
 typedef struct gptq_moe_t {
     int32_t E;
-    int32_t flags;                     /* 0 | GPTQ_MOE_LOW_BIT (the field was `reserved`, 0, before: a zeroed struct means what it meant) */
+    int32_t flags;                     /* 0 | GPTQ_MOE_LOW_BIT | GPTQ_MOE_LOW_BIT_DECODE (the field was `reserved`, 0, before: a zeroed struct means what it meant) */
     const gptq_layer_t *const *gate;   /* [E] */
     const gptq_layer_t *const *up;     /* [E] */
     const gptq_layer_t *const *down;   /* [E] */
@@ -407,7 +412,7 @@ int gptq_describe_moe_plan(const gptq_moe_t *moe, int T, int topk, char *out, si
  *   0 for a token with no valid expert.  Bit-reproducible; the row of token t does not depend on the other tokens of the call.
  *   TWO launches (gate|up + silu * mul; down + combine), no routing launch: every workgroup reads its expert from topk_idx and that expert's entry from the
  *   device table, so a captured graph replays with new routing.
- * Takes 4- and 8-bit fp16 / bf16 experts, every group size the decode copy takes, plain and act-order (gate and up may have different activation orders:
+ * Takes 4- and 8-bit fp16 / bf16 experts (2- and 3-bit ones with GPTQ_MOE_LOW_BIT_DECODE in moe->flags: same launches, workspace and plan), every group size the decode copy takes, plain and act-order (gate and up may have different activation orders:
  * each is gathered through its own perm; equal perm pointers -> one gather), T <= 4, topk <= 8, E <= 256, H and I multiples of 64, no bias.  Anything
  * else: GPTQ_ERR_UNSUPPORTED with the reason, and the caller keeps gptq_moe_forward / the per-expert composition.
  * Table: [3 projections][E] entries of 32 bytes {qweight_tiled, qconst_tiled, perm or NULL, 0}; gptq_moe_build_decode_table fills
@@ -423,7 +428,7 @@ size_t gptq_moe_decode_workspace_bytes(const gptq_moe_t *moe, int T, int topk);
 int gptq_moe_decode_forward(const gptq_moe_t *moe, const void *table, const void *x, const int64_t *topk_idx, const float *topk_w, int T, int topk, void *out,
                             void *h_out, void *workspace, size_t workspace_bytes, void *stream);
 /* Host-only: "path=decode launches=2 wg_pair=1792 wg_down=256 waves_pair=8 waves_down=16 lds_pair=... lds_down=..." (workgroups, waves per workgroup and
- * dynamic LDS bytes of the two launches) or "path=none reason=..." (experts without a decode copy, T > 4, 2- / 3-bit, fp32, topk > 8, ...).  GPTQ_OK either way. */
+ * dynamic LDS bytes of the two launches) or "path=none reason=..." (experts without a decode copy, T > 4, 2- / 3-bit without GPTQ_MOE_LOW_BIT_DECODE, fp32, topk > 8, ...).  GPTQ_OK either way. */
 int gptq_describe_moe_decode_plan(const gptq_moe_t *moe, int T, int topk, char *out, size_t out_bytes);
 
 /* The SHARED EXPERT of a Qwen-MoE block next to its routed experts (additive in ABI 8; transformers' Qwen2MoeSparseMoeBlock.forward):
@@ -441,7 +446,7 @@ int gptq_describe_moe_decode_plan(const gptq_moe_t *moe, int T, int topk, char *
  *   launch 2  grid (H / 16, T) as before; behind the token's topk routed assignments (ascending j) the workgroup adds s_t (hs_t . W2_s) to the same fp32
  *             register and rounds once.  The routed terms are summed exactly as gptq_moe_decode_forward sums them.  A token with no valid routed
  *             expert gets T(s_t (hs_t . W2_s)).
- * Takes what gptq_moe_decode_forward takes for `moe`, and shared layers with a decode copy, 4 or 8 bits, fp16 / bf16, plain or act-order.  Declined with
+ * Takes what gptq_moe_decode_forward takes for `moe` at 4 and 8 bits (2- / 3-bit routed experts are declined whatever moe->flags says), and shared layers with a decode copy, 4 or 8 bits, fp16 / bf16, plain or act-order.  Declined with
  * GPTQ_ERR_UNSUPPORTED and the reason: shared gate / up (down) that differ from the routed gate / up (down) in bits or dtype, I_s % 64 != 0, a bias or an
  * epilogue on a shared layer, a shared layer without a decode copy or with a group size the copy does not take, shared gate and up of different group
  * sizes, either launch's LDS layout above 160 KiB, gate_w not 16-byte aligned, flags or reserved != 0. */

@@ -329,177 +329,96 @@ def check(status: int) -> None:
         raise GptqError(status, f"gptq_mi355x: {kind}: {msg}")
 
 
-def describe_plan(layer: "GptqLayer", M: int, tuning: "GptqTuning | None" = None) -> dict:
-    """Kernel and launch geometry gptq_forward_ex would pick (host-only query, see gptq_describe_plan in the header)."""
-    lib = load()
+def _describe(fn: str, *args) -> dict:
+    """One host-only describe query: the C function's "key=value key=value ..." answer as a dict (whole numbers as int)."""
     buf = ctypes.create_string_buffer(512)
-    check(lib.gptq_describe_plan(ctypes.byref(layer), M, ctypes.byref(tuning) if tuning is not None else None, buf, len(buf)))
+    check(getattr(load(), fn)(*args, buf, len(buf)))
     out = {}
     for kv in buf.value.decode().split():
         k, v = kv.split("=", 1)
         out[k] = int(v) if v.lstrip("-").isdigit() else v
     return out
+
+
+def _pointer_array(ctype, items):
+    return (POINTER(ctype) * max(1, len(items)))(*[ctypes.pointer(i) for i in items])
+
+
+def describe_plan(layer: "GptqLayer", M: int, tuning: "GptqTuning | None" = None) -> dict:
+    """Kernel and launch geometry gptq_forward_ex would pick (host-only query, see gptq_describe_plan in the header)."""
+    return _describe("gptq_describe_plan", ctypes.byref(layer), M, ctypes.byref(tuning) if tuning is not None else None)
 
 
 def describe_mlp_plan(gate: "GptqLayer", up: "GptqLayer", down: "GptqLayer", M: int, tuning: "GptqTuning | None" = None) -> dict:
     """What gptq_mlp_forward[_ex] would run for these three layers (host-only query)."""
-    lib = load()
-    buf = ctypes.create_string_buffer(512)
-    check(lib.gptq_describe_mlp_plan(ctypes.byref(gate), ctypes.byref(up), ctypes.byref(down), M,
-                                     ctypes.byref(tuning) if tuning is not None else None, buf, len(buf)))
-    out = {}
-    for kv in buf.value.decode().split():
-        k, v = kv.split("=", 1)
-        out[k] = int(v) if v.lstrip("-").isdigit() else v
-    return out
+    return _describe("gptq_describe_mlp_plan", ctypes.byref(gate), ctypes.byref(up), ctypes.byref(down), M,
+                     ctypes.byref(tuning) if tuning is not None else None)
 
 
 def describe_moe_plan(moe: "GptqMoe", T: int, topk: int) -> dict:
     """What gptq_moe_forward would run for (moe, T, topk): path=grouped with its tile geometry, or path=per_expert with the reason (host-only query)."""
-    lib = load()
-    buf = ctypes.create_string_buffer(512)
-    check(lib.gptq_describe_moe_plan(ctypes.byref(moe), T, topk, buf, len(buf)))
-    out = {}
-    for kv in buf.value.decode().split():
-        k, v = kv.split("=", 1)
-        out[k] = int(v) if v.lstrip("-").isdigit() else v
-    return out
+    return _describe("gptq_describe_moe_plan", ctypes.byref(moe), T, topk)
 
 
 def describe_moe_backward_plan(moe: "GptqMoe", T: int, topk: int) -> dict:
     """What gptq_moe_backward would run for (moe, T, topk): path=grouped_backward with its grids, or path=per_expert with the reason (host-only query)."""
-    lib = load()
-    buf = ctypes.create_string_buffer(512)
-    check(lib.gptq_describe_moe_backward_plan(ctypes.byref(moe), T, topk, buf, len(buf)))
-    out = {}
-    for kv in buf.value.decode().split():
-        k, v = kv.split("=", 1)
-        out[k] = int(v) if v.lstrip("-").isdigit() else v
-    return out
+    return _describe("gptq_describe_moe_backward_plan", ctypes.byref(moe), T, topk)
 
 
 def describe_moe_decode_plan(moe: "GptqMoe", T: int, topk: int) -> dict:
     """What gptq_moe_decode_forward would run for (moe, T, topk): path=decode with its launch geometry, or path=none with the reason (host-only query)."""
-    lib = load()
-    buf = ctypes.create_string_buffer(512)
-    check(lib.gptq_describe_moe_decode_plan(ctypes.byref(moe), T, topk, buf, len(buf)))
-    out = {}
-    for kv in buf.value.decode().split():
-        k, v = kv.split("=", 1)
-        out[k] = int(v) if v.lstrip("-").isdigit() else v
-    return out
+    return _describe("gptq_describe_moe_decode_plan", ctypes.byref(moe), T, topk)
 
 
 def describe_moe_shared_decode_plan(moe: "GptqMoe", shared: "GptqMoeShared", T: int, topk: int) -> dict:
     """What gptq_moe_shared_decode_forward would run for (moe, shared, T, topk): path=decode_shared with its launch geometry, or path=none with the reason
     (host-only query)."""
-    lib = load()
-    buf = ctypes.create_string_buffer(512)
-    check(lib.gptq_describe_moe_shared_decode_plan(ctypes.byref(moe), ctypes.byref(shared), T, topk, buf, len(buf)))
-    out = {}
-    for kv in buf.value.decode().split():
-        k, v = kv.split("=", 1)
-        out[k] = int(v) if v.lstrip("-").isdigit() else v
-    return out
+    return _describe("gptq_describe_moe_shared_decode_plan", ctypes.byref(moe), ctypes.byref(shared), T, topk)
 
 
 def describe_moe_batch_plan(moe: "GptqMoe", T: int, topk: int) -> dict:
     """What gptq_moe_batch_forward would run for (moe, T, topk): path=batch with its tile geometry, or path=none with the reason (host-only query)."""
-    lib = load()
-    buf = ctypes.create_string_buffer(512)
-    check(lib.gptq_describe_moe_batch_plan(ctypes.byref(moe), T, topk, buf, len(buf)))
-    out = {}
-    for kv in buf.value.decode().split():
-        k, v = kv.split("=", 1)
-        out[k] = int(v) if v.lstrip("-").isdigit() else v
-    return out
+    return _describe("gptq_describe_moe_batch_plan", ctypes.byref(moe), T, topk)
 
 
 def describe_moe_prefill_plan(moe: "GptqMoe", T: int, topk: int) -> dict:
     """What gptq_moe_prefill_forward would run for (moe, T, topk): path=prefill with its tile geometry, or path=none with the reason (host-only query)."""
-    lib = load()
-    buf = ctypes.create_string_buffer(512)
-    check(lib.gptq_describe_moe_prefill_plan(ctypes.byref(moe), T, topk, buf, len(buf)))
-    out = {}
-    for kv in buf.value.decode().split():
-        k, v = kv.split("=", 1)
-        out[k] = int(v) if v.lstrip("-").isdigit() else v
-    return out
+    return _describe("gptq_describe_moe_prefill_plan", ctypes.byref(moe), T, topk)
 
 
 def describe_moe_router_plan(T: int, H: int, E: int, topk: int, dtype: int, flags: int = 0) -> dict:
     """What gptq_moe_router would run for T tokens of width H over E experts (dtype: GPTQ_F16 / GPTQ_BF16 / GPTQ_F32): path=router with its row regime
     (form=rows: one token per workgroup, form=tiles: 16 tokens per workgroup), grid and LDS bytes, or path=none with the reason (host-only query)."""
-    lib = load()
-    buf = ctypes.create_string_buffer(512)
-    check(lib.gptq_describe_moe_router_plan(T, H, E, topk, dtype, flags, buf, len(buf)))
-    out = {}
-    for kv in buf.value.decode().split():
-        k, v = kv.split("=", 1)
-        out[k] = int(v) if v.lstrip("-").isdigit() else v
-    return out
+    return _describe("gptq_describe_moe_router_plan", T, H, E, topk, dtype, flags)
 
 
 def describe_moe_router_grouped_plan(T: int, H: int, E: int, topk: int, n_group: int, topk_group: int, dtype: int, flags: int = 0) -> dict:
     """What gptq_moe_router_grouped would run: path=router_grouped with its row regime, grid, LDS bytes and groups, or path=none with the reason
     (host-only query)."""
-    lib = load()
-    buf = ctypes.create_string_buffer(512)
-    check(lib.gptq_describe_moe_router_grouped_plan(T, H, E, topk, n_group, topk_group, dtype, flags, buf, len(buf)))
-    out = {}
-    for kv in buf.value.decode().split():
-        k, v = kv.split("=", 1)
-        out[k] = int(v) if v.lstrip("-").isdigit() else v
-    return out
+    return _describe("gptq_describe_moe_router_grouped_plan", T, H, E, topk, n_group, topk_group, dtype, flags)
 
 
 def describe_lora_plan(loras, M: int) -> dict:
     """What gptq_lora_apply would run for these adapters (a sequence of GptqLora) at M rows: path=lora with its row regime and grid sizes, or path=none
     with the reason (host-only query)."""
-    lib = load()
-    n = len(loras)
-    arr = (POINTER(GptqLora) * max(1, n))(*[ctypes.pointer(l) for l in loras])
-    buf = ctypes.create_string_buffer(512)
-    check(lib.gptq_describe_lora_plan(arr, n, M, buf, len(buf)))
-    out = {}
-    for kv in buf.value.decode().split():
-        k, v = kv.split("=", 1)
-        out[k] = int(v) if v.lstrip("-").isdigit() else v
-    return out
+    return _describe("gptq_describe_lora_plan", _pointer_array(GptqLora, loras), len(loras), M)
 
 
 def describe_lora_backward_plan(loras, M: int) -> dict:
     """What gptq_lora_backward would run for these adapters (a sequence of GptqLora; A / B are not looked at) at M rows, every output asked for:
     path=lora_backward with the slice counts S_dA / S_dB (lists, one entry per adapter), the grids, the workspace and the launches, or path=none with the
     reason (host-only query)."""
-    lib = load()
-    n = len(loras)
-    arr = (POINTER(GptqLora) * max(1, n))(*[ctypes.pointer(l) for l in loras])
-    buf = ctypes.create_string_buffer(512)
-    check(lib.gptq_describe_lora_backward_plan(arr, n, M, buf, len(buf)))
-    out = {}
-    for kv in buf.value.decode().split():
-        k, v = kv.split("=", 1)
-        if k in ("S_dA", "S_dB"):
-            out[k] = [int(t) for t in v.split(",")]
-        else:
-            out[k] = int(v) if v.lstrip("-").isdigit() else v
+    out = _describe("gptq_describe_lora_backward_plan", _pointer_array(GptqLora, loras), len(loras), M)
+    for k in ("S_dA", "S_dB"):
+        if k in out:
+            out[k] = [int(t) for t in str(out[k]).split(",")]
     return out
 
 
 def describe_adapter_rows_plan(banks, M: int) -> dict:
     """What gptq_adapter_rows_apply would run for these banks (a sequence of GptqAdapterBank) at M rows: path=adapter_rows with its tile bound and grid
     sizes, or path=none with the reason (host-only query)."""
-    lib = load()
-    n = len(banks)
-    arr = (POINTER(GptqAdapterBank) * max(1, n))(*[ctypes.pointer(b) for b in banks])
-    buf = ctypes.create_string_buffer(512)
-    check(lib.gptq_describe_adapter_rows_plan(arr, n, M, buf, len(buf)))
-    out = {}
-    for kv in buf.value.decode().split():
-        k, v = kv.split("=", 1)
-        out[k] = int(v) if v.lstrip("-").isdigit() else v
-    return out
+    return _describe("gptq_describe_adapter_rows_plan", _pointer_array(GptqAdapterBank, banks), len(banks), M)
 
 
 _INITED = set()

@@ -164,8 +164,6 @@ __global__ void __launch_bounds__(SUM_THREADS) wgrad_sum_kernel(Args p) {
 
 }  // namespace adapters
 
-static size_t a256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 WgradSlices wgrad_slices(int M, int P, int Q) {
     WgradSlices s{1, 0};
     if (M <= 0) return s;
@@ -190,7 +188,7 @@ WgradPlan plan_wgrad(const gptq_lora_t* const* Ls, const gptq_lora_grad_t* const
             const WgradSlices s = wgrad_slices(M, w ? L.N : L.r, w ? L.r : L.K);
             const size_t pq = (size_t)big * L.r;
             pl.off[2 * i + w] = pl.bytes;
-            if (s.S > 1) pl.bytes += a256(4 * (size_t)s.S * pq);
+            if (s.S > 1) pl.bytes += align256(4 * (size_t)s.S * pq);
             const bool asked = !Gs || (w ? Gs[i]->dB : Gs[i]->dA) != nullptr;
             if (!asked || M <= 0) continue;
             pl.sl[2 * i + w] = s;

@@ -209,18 +209,10 @@ static Args make_args(const gptq_adapter_bank_t* const* Bs, int n, const void* x
 
 }  // namespace adapters
 
-static size_t adapter_align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 AdapterRoutePlan plan_adapter_route(int M, int slots) {
     AdapterRoutePlan rp;
     rp.tiles = (long)M / adapters::TILE_ROWS + std::min((long)slots, (long)M);
-    size_t o = 0;
-    rp.off_offsets = o; o += adapter_align256(4 * ((size_t)slots + 1));
-    rp.off_tile_count = o; o += 256;
-    rp.off_tiles = o; o += adapter_align256(16 * (size_t)rp.tiles);
-    rp.off_pos = o; o += adapter_align256(4 * (size_t)M);
-    rp.off_rows = o; o += adapter_align256(4 * (size_t)M);
-    rp.bytes = o;
+    rp.bytes = append_route_layout(rp, 0, slots, rp.tiles, M);
     return rp;
 }
 

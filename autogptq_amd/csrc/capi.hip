@@ -31,6 +31,16 @@ int hip_fail(hipError_t e, const char* what) {
     return fail(GPTQ_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
 }
 
+// What a describe function answers for a call its checker declined: the last error as one key=value token (blanks and '=' become '_').
+int describe_decline(char* out, size_t out_bytes, const char* path_word) {
+    char reason[sizeof(g_err)];
+    snprintf(reason, sizeof(reason), "%s", g_err);
+    for (char* c = reason; *c; ++c)
+        if (*c == ' ' || *c == '=') *c = '_';
+    snprintf(out, out_bytes, "path=%s reason=%s", path_word, reason);
+    return GPTQ_OK;
+}
+
 bool bits_ok(int b) { return b == 2 || b == 3 || b == 4 || b == 8; }
 bool dtype_ok(int d) { return d == GPTQ_F16 || d == GPTQ_BF16 || d == GPTQ_F32; }
 
@@ -826,14 +836,7 @@ int gptq_moe_router(const void* x, const void* w, int T, int H, int E, int topk,
 
 int gptq_describe_moe_router_plan(int T, int H, int E, int topk, int dtype, int flags, char* out, size_t out_bytes) {
     if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out is NULL");
-    if (router_check(T, H, E, topk, dtype, flags)) {
-        char reason[sizeof(g_err)];
-        snprintf(reason, sizeof(reason), "%s", g_err);
-        for (char* c = reason; *c; ++c)
-            if (*c == ' ' || *c == '=') *c = '_';
-        snprintf(out, out_bytes, "path=none reason=%s", reason);
-        return GPTQ_OK;
-    }
+    if (router_check(T, H, E, topk, dtype, flags)) return describe_decline(out, out_bytes, "none");
     const RouterPlan pl = plan_moe_router(T, H, E, topk, dtype);
     snprintf(out, out_bytes, "path=router form=%s wg=%ld waves=8 lds=%zu launches=1", pl.rows ? "rows" : "tiles", pl.wg, pl.lds_bytes);
     return GPTQ_OK;
@@ -875,14 +878,7 @@ int gptq_moe_router_grouped(const void* x, const void* w, const float* bias, int
 
 int gptq_describe_moe_router_grouped_plan(int T, int H, int E, int topk, int n_group, int topk_group, int dtype, int flags, char* out, size_t out_bytes) {
     if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out is NULL");
-    if (router_grouped_check(T, H, E, topk, n_group, topk_group, 1.f, dtype, flags)) {
-        char reason[sizeof(g_err)];
-        snprintf(reason, sizeof(reason), "%s", g_err);
-        for (char* c = reason; *c; ++c)
-            if (*c == ' ' || *c == '=') *c = '_';
-        snprintf(out, out_bytes, "path=none reason=%s", reason);
-        return GPTQ_OK;
-    }
+    if (router_grouped_check(T, H, E, topk, n_group, topk_group, 1.f, dtype, flags)) return describe_decline(out, out_bytes, "none");
     const RouterPlan pl = plan_moe_router(T, H, E, topk, dtype);
     snprintf(out, out_bytes, "path=router_grouped form=%s wg=%ld waves=8 lds=%zu groups=%d launches=1", pl.rows ? "rows" : "tiles", pl.wg, pl.lds_bytes, n_group);
     return GPTQ_OK;
@@ -953,14 +949,7 @@ int gptq_describe_lora_plan(const gptq_lora_t* const* Ls, int n, int M, char* ou
     if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out is NULL");
     int rc = lora_check(Ls, n);
     if (!rc && M < 0) rc = fail(GPTQ_ERR_SHAPE, "M must be >= 0, got %d", M);
-    if (rc) {
-        char reason[sizeof(g_err)];
-        snprintf(reason, sizeof(reason), "%s", g_err);
-        for (char* c = reason; *c; ++c)
-            if (*c == ' ' || *c == '=') *c = '_';
-        snprintf(out, out_bytes, "path=none reason=%s", reason);
-        return GPTQ_OK;
-    }
+    if (rc) return describe_decline(out, out_bytes, "none");
     const LoraPlan pl = plan_lora(Ls, n, M);
     snprintf(out, out_bytes, "path=lora rows=%s wg_down=%ld wg_up=%ld launches=2", pl.gemv ? "gemv" : "mfma", M ? pl.wg_down : 0L, M ? pl.wg_up : 0L);
     return GPTQ_OK;
@@ -1046,14 +1035,7 @@ int gptq_describe_lora_backward_plan(const gptq_lora_t* const* Ls, int n, int M,
     if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out is NULL");
     int rc = lora_grad_check(Ls, n);
     if (!rc && M < 0) rc = fail(GPTQ_ERR_SHAPE, "M must be >= 0, got %d", M);
-    if (rc) {
-        char reason[sizeof(g_err)];
-        snprintf(reason, sizeof(reason), "%s", g_err);
-        for (char* c = reason; *c; ++c)
-            if (*c == ' ' || *c == '=') *c = '_';
-        snprintf(out, out_bytes, "path=none reason=%s", reason);
-        return GPTQ_OK;
-    }
+    if (rc) return describe_decline(out, out_bytes, "none");
     const WgradPlan pl = plan_wgrad(Ls, nullptr, n, M);
     long wg_down = 0, wg_up = 0;
     char sa[64] = "", sb[64] = "";
@@ -1142,121 +1124,175 @@ int gptq_describe_adapter_rows_plan(const gptq_adapter_bank_t* const* Bs, int n,
     if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out is NULL");
     int rc = adapter_check(Bs, n);
     if (!rc && M < 0) rc = fail(GPTQ_ERR_SHAPE, "M must be >= 0, got %d", M);
-    if (rc) {
-        char reason[sizeof(g_err)];
-        snprintf(reason, sizeof(reason), "%s", g_err);
-        for (char* c = reason; *c; ++c)
-            if (*c == ' ' || *c == '=') *c = '_';
-        snprintf(out, out_bytes, "path=none reason=%s", reason);
-        return GPTQ_OK;
-    }
+    if (rc) return describe_decline(out, out_bytes, "none");
     const AdapterRowsPlan pl = plan_adapter_rows(Bs, n, M);
     snprintf(out, out_bytes, "path=adapter_rows tiles=%ld wg_down=%ld wg_up=%ld launches=2", pl.tiles, pl.wg_down, pl.wg_up);
     return GPTQ_OK;
 }
 
-// ---- routed mixture-of-experts layers (moe.hip) ----
-static int moe_check_proj(const gptq_layer_t* const* Ls, int E, int K, int N, int dtype, int flags, const char* name) {
+// ---- routed mixture-of-experts layers: the grouped path (moe.hip, moe_grad.hip) and the three paths on the experts' decode copy ----
+// What the paths' checks differ in.  The grouped path is the one without a decode copy (copy_hint NULL); where it orders or words a check differently,
+// moe_check and moe_check_proj branch on that.
+struct MoePathRules {
+    const char* word;                               // the path's name in messages
+    int max_T, max_rows;                            // the largest T / T topk the path takes (0: no such limit)
+    int multiple;                                   // of H and I
+    const char* copy_hint;                          // the post_init(...) argument that builds the decode copy the path needs (NULL: it needs none)
+    bool (*group_ok)(const gptq_layer_t&);          // the path's group-size rule (NULL: the decode copy's own, tiled_layer_ok) and what its message says
+    const char* group_text;
+    bool copy_aligned;                              // the decode copy is read by 16-byte vectors
+    int low_bit_flag;                               // the gptq_moe_t flag that opens 2- and 3-bit experts (0: 4 or 8 bits only)
+    bool lds_fit;                                   // plan_moe_decode has the last word
+};
+static const MoePathRules MOE_GROUPED = {"grouped", 0, 0, 64, nullptr, nullptr, nullptr, false, GPTQ_MOE_LOW_BIT, false};
+static const MoePathRules MOE_DECODE = {"decode", 4, 0, 64, "decode_copy=True", nullptr, nullptr, false, GPTQ_MOE_LOW_BIT_DECODE, true};
+static const MoePathRules MOE_BATCH = {"batch", 64, 0, 128, "batch=True", moe_batch_group_ok, "32, 64, 128 times a power of two, or one group", false, 0, false};
+static const MoePathRules MOE_PREFILL = {"prefill", 0, GPTQ_MOE_PREFILL_MAX_ROWS, 128, "prefill=True", moe_prefill_group_ok, "64 times a power of two, or one group",
+                                         true, 0, false};
+
+static int moe_check_bits(const MoePathRules& r, int bits, int flags) {
+    if (bits == 4 || bits == 8) return GPTQ_OK;
+    if (!(flags & r.low_bit_flag)) return fail(GPTQ_ERR_UNSUPPORTED, "%d-bit experts: the %s path takes 4 or 8 bits", bits, r.word);
+    if (bits != 2 && bits != 3) return fail(GPTQ_ERR_UNSUPPORTED, "%d-bit experts: the %s path takes 2, 3, 4 or 8 bits", bits, r.word);      // (check_layer: 2, 3, 4 or 8)
+    return GPTQ_OK;
+}
+
+// One projection's experts against the shape [K -> N] and gate[0] (G).
+static int moe_check_proj(const MoePathRules& r, const gptq_layer_t* const* Ls, int E, int K, int N, const gptq_layer_t* G, int flags, const char* name) {
     if (!Ls) return fail(GPTQ_ERR_NULL, "moe->%s is NULL", name);
+    const bool grouped = !r.copy_hint;
     for (int e = 0; e < E; ++e) {
         const gptq_layer_t* L = Ls[e];
         if (int rc = check_layer(L)) return rc;
-        const gptq_layer_t* A = Ls[0];
         if (L->K != K || L->N != N)
             return fail(GPTQ_ERR_SHAPE, "expert %d %s is [%d -> %d], expected [%d -> %d]", e, name, L->K, L->N, K, N);
-        if (L->bits != A->bits || L->group_size != A->group_size || L->dtype != dtype || L->zero_mode != A->zero_mode)
+        const gptq_layer_t* B = grouped ? Ls[0] : G;      // bits: the grouped path compares within the projection (gate against up: moe_check), the copy paths against gate[0]
+        if (L->bits != B->bits || L->group_size != Ls[0]->group_size || L->dtype != G->dtype || L->zero_mode != Ls[0]->zero_mode)
             return fail(GPTQ_ERR_UNSUPPORTED, "the %s layers of all experts must share bits, group_size, dtype and zero_mode (expert %d differs)", name, e);
         if (L->bias || L->epilogue != GPTQ_EPI_NONE)
-            return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s: the grouped path takes no bias and no epilogue", e, name);
-        if (L->g_idx && !L->qweight_seq)
-            return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s: raw act-order (no re-sequenced rows) is not taken by the grouped path", e, name);
+            return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s: the %s path takes no bias and no epilogue", e, name, r.word);
+        if (grouped) {
+            if (L->g_idx && !L->qweight_seq)
+                return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s: raw act-order (no re-sequenced rows) is not taken by the grouped path", e, name);
+            continue;
+        }
+        if (r.group_ok && !r.group_ok(*L)) return fail(GPTQ_ERR_UNSUPPORTED, "group_size %d: the %s path takes %s", L->group_size, r.word, r.group_text);
+        if (!L->qweight_tiled || !L->qconst_tiled)
+            return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s carries no decode copy (QuantMoEExperts.post_init(%s) builds it)", e, name, r.copy_hint);
+        if (!tiled_layer_ok(*L)) {
+            if (r.group_ok) return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s: raw act-order (no re-sequenced rows) is not taken by the decode copy", e, name);
+            return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s: group_size %d (or raw act-order) is not taken by the decode copy", e, name, L->group_size);
+        }
+        if (r.copy_aligned && (((uintptr_t)L->qweight_tiled | (uintptr_t)L->qconst_tiled) & 15))
+            return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s: the decode copy must be 16-byte aligned", e, name);
     }
+    if (!grouped) return GPTQ_OK;
     const gptq_layer_t* A = Ls[0];
-    if (A->bits != 4 && A->bits != 8) {
-        if (!(flags & GPTQ_MOE_LOW_BIT)) return fail(GPTQ_ERR_UNSUPPORTED, "%d-bit experts: the grouped path takes 4 or 8 bits", A->bits);
-        if (A->bits != 2 && A->bits != 3) return fail(GPTQ_ERR_UNSUPPORTED, "%d-bit experts: the grouped path takes 2, 3, 4 or 8 bits", A->bits);
-    }
+    if (int rc = moe_check_bits(r, A->bits, flags)) return rc;
     if (A->group_size % 32 && A->group_size < K)
         return fail(GPTQ_ERR_UNSUPPORTED, "group_size %d: the grouped path takes multiples of 32 (or one group)", A->group_size);
     return GPTQ_OK;
 }
 
-static int moe_check(const gptq_moe_t* m, int T, int topk) {
+static int moe_check(const MoePathRules& r, const gptq_moe_t* m, int T, int topk) {
+    const bool grouped = !r.copy_hint;
     if (!m) return fail(GPTQ_ERR_NULL, "moe is NULL");
-    if (m->flags & ~(GPTQ_MOE_LOW_BIT | GPTQ_MOE_LOW_BIT_DECODE))      // (GPTQ_MOE_LOW_BIT_DECODE: a known bit of the decode path's, nothing here reads it)
+    if (grouped && (m->flags & ~(GPTQ_MOE_LOW_BIT | GPTQ_MOE_LOW_BIT_DECODE)))      // (GPTQ_MOE_LOW_BIT_DECODE: a known bit of the decode path's, nothing here reads it)
         return fail(GPTQ_ERR_UNSUPPORTED, "moe->flags = 0x%x: unknown flag bits (GPTQ_MOE_LOW_BIT and GPTQ_MOE_LOW_BIT_DECODE are the only ones)", (unsigned)m->flags);
-    if (m->E < 1 || m->E > 256) return fail(GPTQ_ERR_UNSUPPORTED, "E = %d experts: the grouped path takes 1..256", m->E);
-    if (topk < 1 || topk > 8) return fail(GPTQ_ERR_UNSUPPORTED, "topk = %d: the grouped path takes 1..8", topk);
+    if (m->E < 1 || m->E > 256) return fail(GPTQ_ERR_UNSUPPORTED, "E = %d experts: the %s path takes 1..256", m->E, r.word);
+    if (topk < 1 || topk > 8) return fail(GPTQ_ERR_UNSUPPORTED, "topk = %d: the %s path takes 1..8", topk, r.word);
     if (T < 0) return fail(GPTQ_ERR_SHAPE, "T must be >= 0, got %d", T);
+    if (r.max_T && T > r.max_T) return fail(GPTQ_ERR_UNSUPPORTED, "T = %d tokens: the %s path takes 1..%d (the grouped path serves more)", T, r.word, r.max_T);
+    if (r.max_rows && (long)T * topk > r.max_rows)
+        return fail(GPTQ_ERR_UNSUPPORTED, "T topk = %ld rows: the %s path takes up to %d (the grouped path serves more)", (long)T * topk, r.word, r.max_rows);
     if (!m->gate || !m->up || !m->down || !m->gate[0]) return fail(GPTQ_ERR_NULL, "moe->gate / up / down must be non-NULL");
     const gptq_layer_t* G = m->gate[0];
     if (int rc = check_layer(G)) return rc;
-    if (G->dtype != GPTQ_F16 && G->dtype != GPTQ_BF16) return fail(GPTQ_ERR_UNSUPPORTED, "fp32 experts: the grouped path takes fp16 / bf16");
+    if (G->dtype != GPTQ_F16 && G->dtype != GPTQ_BF16) return fail(GPTQ_ERR_UNSUPPORTED, "fp32 experts: the %s path takes fp16 / bf16", r.word);
+    if (!grouped)      // (the grouped path judges each projection's own bits: moe_check_proj.  With the decode path's flag the 2- / 3-bit forms of moe_shared.hip serve them)
+        if (int rc = moe_check_bits(r, G->bits, m->flags)) return rc;
     const int H = G->K, I = G->N;
-    if (H % 64 || I % 64) return fail(GPTQ_ERR_UNSUPPORTED, "hidden (%d) and intermediate (%d) sizes must be multiples of 64", H, I);
-    if ((long)T * topk > 0x3fffffffL / 4) return fail(GPTQ_ERR_SHAPE, "T = %d is too large", T);
-    if (int rc = moe_check_proj(m->gate, m->E, H, I, G->dtype, m->flags, "gate")) return rc;
-    if (int rc = moe_check_proj(m->up, m->E, H, I, G->dtype, m->flags, "up")) return rc;
+    if (H % r.multiple || I % r.multiple)
+        return fail(GPTQ_ERR_UNSUPPORTED, "hidden (%d) and intermediate (%d) sizes must be multiples of %d", H, I, r.multiple);
+    if (grouped && (long)T * topk > 0x3fffffffL / 4) return fail(GPTQ_ERR_SHAPE, "T = %d is too large", T);
+    if (int rc = moe_check_proj(r, m->gate, m->E, H, I, G, m->flags, "gate")) return rc;
+    if (int rc = moe_check_proj(r, m->up, m->E, H, I, G, m->flags, "up")) return rc;
     const gptq_layer_t* U = m->up[0];
-    if (U->bits != G->bits || U->group_size != G->group_size || U->zero_mode != G->zero_mode)
+    if (U->bits != G->bits || U->group_size != G->group_size || U->zero_mode != G->zero_mode)      // (the copy paths: every expert's bits are gate[0]'s by now)
         return fail(GPTQ_ERR_UNSUPPORTED, "gate and up layers must share bits, group_size and zero_mode");
-    return moe_check_proj(m->down, m->E, I, H, G->dtype, m->flags, "down");
+    if (int rc = moe_check_proj(r, m->down, m->E, I, H, G, m->flags, "down")) return rc;
+    if (r.lds_fit) {
+        const MoeDecodePlan pl = plan_moe_decode(*m, T, topk);
+        if (!pl.ok) return fail(GPTQ_ERR_UNSUPPORTED, "hidden (%d) / intermediate (%d) sizes: the staged row and constants (%d / %d bytes) do not fit the LDS", H, I, pl.lds_pair, pl.lds_down);
+    }
+    return GPTQ_OK;
+}
+
+// The three tables: [gate | up | down][E] entries of the kernels' own pointer structs, built on the host and copied once.
+static int moe_build_table_impl(const MoePathRules& r, const gptq_moe_t* m, void* table, void* stream, size_t eb, void (*entry)(const gptq_layer_t&, void*),
+                                const char* what) {
+    if (int rc = moe_check(r, m, 0, 1)) return rc;
+    if (!table) return fail(GPTQ_ERR_NULL, "table is NULL");
+    const size_t E = (size_t)m->E;
+    std::vector<char> host(3 * E * eb);
+    for (size_t e = 0; e < E; ++e) {
+        entry(*m->gate[e], host.data() + e * eb);
+        entry(*m->up[e], host.data() + (E + e) * eb);
+        entry(*m->down[e], host.data() + (2 * E + e) * eb);
+    }
+    hipError_t e = hipMemcpyAsync(table, host.data(), host.size(), hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);      // the host copy dies with this call
+    if (e != hipSuccess) return hip_fail(e, what);
+    return GPTQ_OK;
+}
+
+// The front of the forward entry points behind their check and plan: the pointers, their alignment, the workspace.
+static int moe_forward_args(const char* table_word, const void* table, const void* x, const int64_t* idx, const float* w, const void* out, const void* ws,
+                            size_t ws_bytes, size_t need) {
+    if (!table || !x || !idx || !w || !out) return fail(GPTQ_ERR_NULL, "%s / x / topk_idx / topk_w / out must be non-NULL", table_word);
+    if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)ws) & 15) return fail(GPTQ_ERR_UNSUPPORTED, "x / out / workspace must be 16-byte aligned");
+    if (!ws || ws_bytes < need) return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", need, ws ? ws_bytes : (size_t)0);
+    return GPTQ_OK;
+}
+
+// ... and their tail: h_out = [H_sorted [R, I] | pos [R]] out of the workspace (h_out NULL: nothing)
+static int moe_copy_h_out(const gptq_moe_t* m, void* h_out, const void* ws, size_t off_h, size_t off_pos, int T, int topk, void* stream, const char* what) {
+    if (!h_out) return GPTQ_OK;
+    const gptq_layer_t* G = m->gate[0];
+    const size_t R = (size_t)T * topk, hb = R * G->N * dtype_size(G->dtype);
+    hipError_t e = hipMemcpyAsync(h_out, (const char*)ws + off_h, hb, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipMemcpyAsync((char*)h_out + hb, (const char*)ws + off_pos, 4 * R, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, what);
+    return GPTQ_OK;
 }
 
 size_t gptq_moe_table_bytes(int E) { return E > 0 ? 3 * (size_t)E * moe_table_entry_bytes() : 0; }
 
 int gptq_moe_build_table(const gptq_moe_t* m, void* table, void* stream) {
-    if (int rc = moe_check(m, 0, 1)) return rc;
-    if (!table) return fail(GPTQ_ERR_NULL, "table is NULL");
-    const size_t eb = moe_table_entry_bytes(), E = (size_t)m->E;
-    std::vector<char> host(gptq_moe_table_bytes(m->E));
-    for (size_t e = 0; e < E; ++e) {
-        moe_table_entry(*m->gate[e], host.data() + e * eb);
-        moe_table_entry(*m->up[e], host.data() + (E + e) * eb);
-        moe_table_entry(*m->down[e], host.data() + (2 * E + e) * eb);
-    }
-    hipError_t e = hipMemcpyAsync(table, host.data(), host.size(), hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);      // the host copy dies with this call
-    if (e != hipSuccess) return hip_fail(e, "gptq_moe_build_table copy");
-    return GPTQ_OK;
+    return moe_build_table_impl(MOE_GROUPED, m, table, stream, moe_table_entry_bytes(), moe_table_entry, "gptq_moe_build_table copy");
 }
 
 size_t gptq_moe_workspace_bytes(const gptq_moe_t* m, int T, int topk) {
-    if (moe_check(m, T, topk)) return 0;
+    if (moe_check(MOE_GROUPED, m, T, topk)) return 0;
     const gptq_layer_t* G = m->gate[0];
     return plan_moe(m->E, T, topk, G->K, G->N, G->dtype).bytes;
 }
 
 int gptq_moe_forward(const gptq_moe_t* m, const void* table, const void* x, const int64_t* idx, const float* w, int T, int topk, void* out, void* h_out,
                      void* ws, size_t ws_bytes, void* stream) {
-    if (int rc = moe_check(m, T, topk)) return rc;
+    if (int rc = moe_check(MOE_GROUPED, m, T, topk)) return rc;
     if (T == 0) return GPTQ_OK;
-    if (!table || !x || !idx || !w || !out) return fail(GPTQ_ERR_NULL, "table / x / topk_idx / topk_w / out must be non-NULL");
-    if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)ws) & 15) return fail(GPTQ_ERR_UNSUPPORTED, "x / out / workspace must be 16-byte aligned");
     const gptq_layer_t* G = m->gate[0];
     const MoePlan pl = plan_moe(m->E, T, topk, G->K, G->N, G->dtype);
-    if (!ws || ws_bytes < pl.bytes) return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", pl.bytes, ws ? ws_bytes : (size_t)0);
+    if (int rc = moe_forward_args("table", table, x, idx, w, out, ws, ws_bytes, pl.bytes)) return rc;
     hipError_t e = launch_moe(*m, table, pl, x, idx, w, T, topk, out, (char*)ws, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "gptq_moe_forward launch");
-    if (h_out) {
-        const size_t R = (size_t)T * topk, hb = R * G->N * dtype_size(G->dtype);
-        e = hipMemcpyAsync(h_out, (char*)ws + pl.off_h, hb, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-        if (e == hipSuccess) e = hipMemcpyAsync((char*)h_out + hb, (char*)ws + pl.off_pos, 4 * R, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-        if (e != hipSuccess) return hip_fail(e, "gptq_moe_forward h_out copy");
-    }
-    return GPTQ_OK;
+    return moe_copy_h_out(m, h_out, ws, pl.off_h, pl.off_pos, T, topk, stream, "gptq_moe_forward h_out copy");
 }
 
 int gptq_describe_moe_plan(const gptq_moe_t* m, int T, int topk, char* out, size_t out_bytes) {
     if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out is NULL");
-    if (moe_check(m, T, topk)) {
-        char reason[sizeof(g_err)];
-        snprintf(reason, sizeof(reason), "%s", g_err);
-        for (char* c = reason; *c; ++c)
-            if (*c == ' ' || *c == '=') *c = '_';
-        snprintf(out, out_bytes, "path=per_expert reason=%s", reason);
-        return GPTQ_OK;
-    }
+    if (moe_check(MOE_GROUPED, m, T, topk)) return describe_decline(out, out_bytes, "per_expert");
     const gptq_layer_t* G = m->gate[0];
     const MoePlan pl = plan_moe(m->E, T, topk, G->K, G->N, G->dtype);
     snprintf(out, out_bytes, "path=grouped bm=%d bn=%d tiles=%d ksplit=%d launches=%d", pl.bm, pl.bn, pl.tiles, pl.ksplit, T > 0 ? 4 : 0);
@@ -1267,30 +1303,18 @@ int gptq_describe_moe_plan(const gptq_moe_t* m, int T, int topk, char* out, size
 size_t gptq_moe_grad_table_bytes(int E) { return E > 0 ? 3 * (size_t)E * moe_grad_table_entry_bytes() : 0; }
 
 int gptq_moe_build_grad_table(const gptq_moe_t* m, void* table, void* stream) {
-    if (int rc = moe_check(m, 0, 1)) return rc;
-    if (!table) return fail(GPTQ_ERR_NULL, "table is NULL");
-    const size_t eb = moe_grad_table_entry_bytes(), E = (size_t)m->E;
-    std::vector<char> host(gptq_moe_grad_table_bytes(m->E));
-    for (size_t e = 0; e < E; ++e) {
-        moe_grad_table_entry(*m->gate[e], host.data() + e * eb);
-        moe_grad_table_entry(*m->up[e], host.data() + (E + e) * eb);
-        moe_grad_table_entry(*m->down[e], host.data() + (2 * E + e) * eb);
-    }
-    hipError_t e = hipMemcpyAsync(table, host.data(), host.size(), hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);      // the host copy dies with this call
-    if (e != hipSuccess) return hip_fail(e, "gptq_moe_build_grad_table copy");
-    return GPTQ_OK;
+    return moe_build_table_impl(MOE_GROUPED, m, table, stream, moe_grad_table_entry_bytes(), moe_grad_table_entry, "gptq_moe_build_grad_table copy");
 }
 
 size_t gptq_moe_backward_workspace_bytes(const gptq_moe_t* m, int T, int topk) {
-    if (moe_check(m, T, topk)) return 0;
+    if (moe_check(MOE_GROUPED, m, T, topk)) return 0;
     const gptq_layer_t* G = m->gate[0];
     return plan_moe_grad(m->E, T, topk, G->K, G->N, G->dtype).bytes;
 }
 
 int gptq_moe_backward(const gptq_moe_t* m, const void* table, const void* grad_table, const void* x, const int64_t* idx, const float* w, const void* dout,
                       int T, int topk, void* dx, float* dw, void* dgu_out, void* ws, size_t ws_bytes, void* stream) {
-    if (int rc = moe_check(m, T, topk)) return rc;
+    if (int rc = moe_check(MOE_GROUPED, m, T, topk)) return rc;
     if (T == 0) return GPTQ_OK;
     if (!dx && !dw) return fail(GPTQ_ERR_NULL, "dx and dw are both NULL: nothing to compute");
     if (!table || !grad_table || !x || !idx || !w || !dout)
@@ -1314,14 +1338,7 @@ int gptq_moe_backward(const gptq_moe_t* m, const void* table, const void* grad_t
 
 int gptq_describe_moe_backward_plan(const gptq_moe_t* m, int T, int topk, char* out, size_t out_bytes) {
     if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out is NULL");
-    if (moe_check(m, T, topk)) {
-        char reason[sizeof(g_err)];
-        snprintf(reason, sizeof(reason), "%s", g_err);
-        for (char* c = reason; *c; ++c)
-            if (*c == ' ' || *c == '=') *c = '_';
-        snprintf(out, out_bytes, "path=per_expert reason=%s", reason);
-        return GPTQ_OK;
-    }
+    if (moe_check(MOE_GROUPED, m, T, topk)) return describe_decline(out, out_bytes, "per_expert");
     const gptq_layer_t* G = m->gate[0];
     const MoeGradPlan pl = plan_moe_grad(m->E, T, topk, G->K, G->N, G->dtype);
     snprintf(out, out_bytes, "path=grouped_backward tiles=%d launches=%d wg_recompute=%ld wg_down=%ld wg_up=%ld", pl.tiles, T > 0 ? 5 : 0,
@@ -1330,103 +1347,31 @@ int gptq_describe_moe_backward_plan(const gptq_moe_t* m, int T, int topk, char* 
 }
 
 // ---- the same layers at 1..4 tokens on the experts' decode copy (moe_decode.hip) ----
-static int moe_decode_check_proj(const gptq_layer_t* const* Ls, int E, int K, int N, const gptq_layer_t* A, const char* name) {
-    if (!Ls) return fail(GPTQ_ERR_NULL, "moe->%s is NULL", name);
-    for (int e = 0; e < E; ++e) {
-        const gptq_layer_t* L = Ls[e];
-        if (int rc = check_layer(L)) return rc;
-        if (L->K != K || L->N != N)
-            return fail(GPTQ_ERR_SHAPE, "expert %d %s is [%d -> %d], expected [%d -> %d]", e, name, L->K, L->N, K, N);
-        if (L->bits != A->bits || L->group_size != Ls[0]->group_size || L->dtype != A->dtype || L->zero_mode != Ls[0]->zero_mode)
-            return fail(GPTQ_ERR_UNSUPPORTED, "the %s layers of all experts must share bits, group_size, dtype and zero_mode (expert %d differs)", name, e);
-        if (L->bias || L->epilogue != GPTQ_EPI_NONE)
-            return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s: the decode path takes no bias and no epilogue", e, name);
-        if (!L->qweight_tiled || !L->qconst_tiled)
-            return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s carries no decode copy (QuantMoEExperts.post_init(decode_copy=True) builds it)", e, name);
-        if (!tiled_layer_ok(*L))
-            return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s: group_size %d (or raw act-order) is not taken by the decode copy", e, name, L->group_size);
-    }
-    return GPTQ_OK;
-}
-
-static int moe_decode_check(const gptq_moe_t* m, int T, int topk) {
-    if (!m) return fail(GPTQ_ERR_NULL, "moe is NULL");
-    if (m->E < 1 || m->E > 256) return fail(GPTQ_ERR_UNSUPPORTED, "E = %d experts: the decode path takes 1..256", m->E);
-    if (topk < 1 || topk > 8) return fail(GPTQ_ERR_UNSUPPORTED, "topk = %d: the decode path takes 1..8", topk);
-    if (T < 0) return fail(GPTQ_ERR_SHAPE, "T must be >= 0, got %d", T);
-    if (T > 4) return fail(GPTQ_ERR_UNSUPPORTED, "T = %d tokens: the decode path takes 1..4 (the grouped path serves more)", T);
-    if (!m->gate || !m->up || !m->down || !m->gate[0]) return fail(GPTQ_ERR_NULL, "moe->gate / up / down must be non-NULL");
-    const gptq_layer_t* G = m->gate[0];
-    if (int rc = check_layer(G)) return rc;
-    if (G->dtype != GPTQ_F16 && G->dtype != GPTQ_BF16) return fail(GPTQ_ERR_UNSUPPORTED, "fp32 experts: the decode path takes fp16 / bf16");
-    if (G->bits != 4 && G->bits != 8 && !(m->flags & GPTQ_MOE_LOW_BIT_DECODE))      // (check_layer: 2, 3, 4 or 8 -- with the flag the 2- / 3-bit forms of moe_shared.hip serve them)
-        return fail(GPTQ_ERR_UNSUPPORTED, "%d-bit experts: the decode path takes 4 or 8 bits", G->bits);
-    const int H = G->K, I = G->N;
-    if (H % 64 || I % 64) return fail(GPTQ_ERR_UNSUPPORTED, "hidden (%d) and intermediate (%d) sizes must be multiples of 64", H, I);
-    if (int rc = moe_decode_check_proj(m->gate, m->E, H, I, G, "gate")) return rc;
-    if (int rc = moe_decode_check_proj(m->up, m->E, H, I, G, "up")) return rc;
-    const gptq_layer_t* U = m->up[0];
-    if (U->group_size != G->group_size || U->zero_mode != G->zero_mode)
-        return fail(GPTQ_ERR_UNSUPPORTED, "gate and up layers must share bits, group_size and zero_mode");
-    if (int rc = moe_decode_check_proj(m->down, m->E, I, H, G, "down")) return rc;
-    const MoeDecodePlan pl = plan_moe_decode(*m, T, topk);
-    if (!pl.ok) return fail(GPTQ_ERR_UNSUPPORTED, "hidden (%d) / intermediate (%d) sizes: the staged row and constants (%d / %d bytes) do not fit the LDS", H, I, pl.lds_pair, pl.lds_down);
-    return GPTQ_OK;
-}
-
 size_t gptq_moe_decode_table_bytes(int E) { return E > 0 ? 3 * (size_t)E * moe_decode_table_entry_bytes() : 0; }
 
 int gptq_moe_build_decode_table(const gptq_moe_t* m, void* table, void* stream) {
-    if (int rc = moe_decode_check(m, 0, 1)) return rc;
-    if (!table) return fail(GPTQ_ERR_NULL, "table is NULL");
-    const size_t eb = moe_decode_table_entry_bytes(), E = (size_t)m->E;
-    std::vector<char> host(gptq_moe_decode_table_bytes(m->E));
-    for (size_t e = 0; e < E; ++e) {
-        moe_decode_table_entry(*m->gate[e], host.data() + e * eb);
-        moe_decode_table_entry(*m->up[e], host.data() + (E + e) * eb);
-        moe_decode_table_entry(*m->down[e], host.data() + (2 * E + e) * eb);
-    }
-    hipError_t e = hipMemcpyAsync(table, host.data(), host.size(), hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);      // the host copy dies with this call
-    if (e != hipSuccess) return hip_fail(e, "gptq_moe_build_decode_table copy");
-    return GPTQ_OK;
+    return moe_build_table_impl(MOE_DECODE, m, table, stream, moe_decode_table_entry_bytes(), moe_decode_table_entry, "gptq_moe_build_decode_table copy");
 }
 
 size_t gptq_moe_decode_workspace_bytes(const gptq_moe_t* m, int T, int topk) {
-    if (moe_decode_check(m, T, topk)) return 0;
+    if (moe_check(MOE_DECODE, m, T, topk)) return 0;
     return plan_moe_decode(*m, T, topk).bytes;
 }
 
 int gptq_moe_decode_forward(const gptq_moe_t* m, const void* table, const void* x, const int64_t* idx, const float* w, int T, int topk, void* out, void* h_out,
                             void* ws, size_t ws_bytes, void* stream) {
-    if (int rc = moe_decode_check(m, T, topk)) return rc;
+    if (int rc = moe_check(MOE_DECODE, m, T, topk)) return rc;
     if (T == 0) return GPTQ_OK;
-    if (!table || !x || !idx || !w || !out) return fail(GPTQ_ERR_NULL, "table / x / topk_idx / topk_w / out must be non-NULL");
-    if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)ws) & 15) return fail(GPTQ_ERR_UNSUPPORTED, "x / out / workspace must be 16-byte aligned");
     const MoeDecodePlan pl = plan_moe_decode(*m, T, topk);
-    if (!ws || ws_bytes < pl.bytes) return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", pl.bytes, ws ? ws_bytes : (size_t)0);
+    if (int rc = moe_forward_args("table", table, x, idx, w, out, ws, ws_bytes, pl.bytes)) return rc;
     hipError_t e = launch_moe_decode(*m, table, pl, x, idx, w, T, topk, out, (char*)ws, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "gptq_moe_decode_forward launch (was gptq_init() called on this device?)");
-    if (h_out) {
-        const gptq_layer_t* G = m->gate[0];
-        const size_t R = (size_t)T * topk, hb = R * G->N * dtype_size(G->dtype);
-        e = hipMemcpyAsync(h_out, (char*)ws + pl.off_h, hb, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-        if (e == hipSuccess) e = hipMemcpyAsync((char*)h_out + hb, (char*)ws + pl.off_pos, 4 * R, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-        if (e != hipSuccess) return hip_fail(e, "gptq_moe_decode_forward h_out copy");
-    }
-    return GPTQ_OK;
+    return moe_copy_h_out(m, h_out, ws, pl.off_h, pl.off_pos, T, topk, stream, "gptq_moe_decode_forward h_out copy");
 }
 
 int gptq_describe_moe_decode_plan(const gptq_moe_t* m, int T, int topk, char* out, size_t out_bytes) {
     if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out is NULL");
-    if (moe_decode_check(m, T, topk)) {
-        char reason[sizeof(g_err)];
-        snprintf(reason, sizeof(reason), "%s", g_err);
-        for (char* c = reason; *c; ++c)
-            if (*c == ' ' || *c == '=') *c = '_';
-        snprintf(out, out_bytes, "path=none reason=%s", reason);
-        return GPTQ_OK;
-    }
+    if (moe_check(MOE_DECODE, m, T, topk)) return describe_decline(out, out_bytes, "none");
     const MoeDecodePlan pl = plan_moe_decode(*m, T, topk);
     snprintf(out, out_bytes, "path=decode launches=%d wg_pair=%d wg_down=%d waves_pair=%d waves_down=%d lds_pair=%d lds_down=%d", T > 0 ? 2 : 0, pl.wg_pair, pl.wg_down,
              pl.waves_pair, pl.waves_down, pl.lds_pair, pl.lds_down);
@@ -1451,7 +1396,7 @@ static int moe_shared_check_layer(const gptq_layer_t* L, int K, int N, const gpt
 }
 
 static int moe_shared_check(const gptq_moe_t* m, const gptq_moe_shared_t* sh, int T, int topk) {
-    if (int rc = moe_decode_check(m, T, topk)) return rc;
+    if (int rc = moe_check(MOE_DECODE, m, T, topk)) return rc;
     if (m->gate[0]->bits == 2 || m->gate[0]->bits == 3)      // (in front of everything that reads the shared layers: no form of the fused launches decodes these widths)
         return fail(GPTQ_ERR_UNSUPPORTED, "%d-bit routed experts: the shared decode form takes 4 or 8 bits (2- and 3-bit experts run gptq_moe_decode_forward and the combine tail)", m->gate[0]->bits);
     if (!sh) return fail(GPTQ_ERR_NULL, "shared is NULL");
@@ -1480,20 +1425,15 @@ int gptq_moe_shared_decode_forward(const gptq_moe_t* m, const gptq_moe_shared_t*
                                    int topk, void* out, void* h_out, void* ws, size_t ws_bytes, void* stream) {
     if (int rc = moe_shared_check(m, sh, T, topk)) return rc;
     if (T == 0) return GPTQ_OK;
-    if (!table || !x || !idx || !w || !out) return fail(GPTQ_ERR_NULL, "decode_table / x / topk_idx / topk_w / out must be non-NULL");
-    if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)ws) & 15) return fail(GPTQ_ERR_UNSUPPORTED, "x / out / workspace must be 16-byte aligned");
     const MoeSharedPlan pl = plan_moe_shared_decode(*m, *sh, T, topk);
-    if (!ws || ws_bytes < pl.bytes) return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", pl.bytes, ws ? ws_bytes : (size_t)0);
+    if (int rc = moe_forward_args("decode_table", table, x, idx, w, out, ws, ws_bytes, pl.bytes)) return rc;
     hipError_t e = launch_moe_shared_decode(*m, *sh, table, pl, x, idx, w, T, topk, out, (char*)ws, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "gptq_moe_shared_decode_forward launch (was gptq_init() called on this device?)");
-    if (h_out) {
-        const gptq_layer_t* G = m->gate[0];
-        const size_t R = (size_t)T * topk, es = dtype_size(G->dtype), hb = R * G->N * es, sb = (size_t)T * sh->gate->N * es;
-        hipStream_t st = (hipStream_t)stream;
-        e = hipMemcpyAsync(h_out, (char*)ws + pl.off_h, hb, hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync((char*)h_out + hb, (char*)ws + pl.off_pos, 4 * R, hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync((char*)h_out + hb + 4 * R, (char*)ws + pl.off_hs, sb, hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync((char*)h_out + hb + 4 * R + sb, (char*)ws + pl.off_s, 4 * (size_t)T, hipMemcpyDeviceToDevice, st);
+    if (int rc = moe_copy_h_out(m, h_out, ws, pl.off_h, pl.off_pos, T, topk, stream, "gptq_moe_shared_decode_forward h_out copy")) return rc;
+    if (h_out) {                                    // ... then hs [T, I_s] and s [T]
+        const size_t R = (size_t)T * topk, es = dtype_size(m->gate[0]->dtype), hb = R * m->gate[0]->N * es, sb = (size_t)T * sh->gate->N * es;
+        e = hipMemcpyAsync((char*)h_out + hb + 4 * R, (char*)ws + pl.off_hs, sb, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+        if (e == hipSuccess) e = hipMemcpyAsync((char*)h_out + hb + 4 * R + sb, (char*)ws + pl.off_s, 4 * (size_t)T, hipMemcpyDeviceToDevice, (hipStream_t)stream);
         if (e != hipSuccess) return hip_fail(e, "gptq_moe_shared_decode_forward h_out copy");
     }
     return GPTQ_OK;
@@ -1501,14 +1441,7 @@ int gptq_moe_shared_decode_forward(const gptq_moe_t* m, const gptq_moe_shared_t*
 
 int gptq_describe_moe_shared_decode_plan(const gptq_moe_t* m, const gptq_moe_shared_t* sh, int T, int topk, char* out, size_t out_bytes) {
     if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out is NULL");
-    if (moe_shared_check(m, sh, T, topk)) {
-        char reason[sizeof(g_err)];
-        snprintf(reason, sizeof(reason), "%s", g_err);
-        for (char* c = reason; *c; ++c)
-            if (*c == ' ' || *c == '=') *c = '_';
-        snprintf(out, out_bytes, "path=none reason=%s", reason);
-        return GPTQ_OK;
-    }
+    if (moe_shared_check(m, sh, T, topk)) return describe_decline(out, out_bytes, "none");
     const MoeSharedPlan pl = plan_moe_shared_decode(*m, *sh, T, topk);
     snprintf(out, out_bytes, "path=decode_shared launches=%d wg_pair=%d wg_down=%d waves_pair=%d waves_down=%d lds_pair=%d lds_down=%d", T > 0 ? 2 : 0, pl.wg_pair,
              pl.wg_down, pl.waves_pair, pl.waves_down, pl.lds_pair, pl.lds_down);
@@ -1529,83 +1462,25 @@ int gptq_moe_shared_combine(const void* x, const void* gate_w, const void* ys, v
 }
 
 // ---- the same layers at 5..64 tokens on the experts' decode copy (moe_rows.hip) ----
-static int moe_batch_check_proj(const gptq_layer_t* const* Ls, int E, int K, int N, const gptq_layer_t* A, const char* name) {
-    if (!Ls) return fail(GPTQ_ERR_NULL, "moe->%s is NULL", name);
-    for (int e = 0; e < E; ++e) {
-        const gptq_layer_t* L = Ls[e];
-        if (int rc = check_layer(L)) return rc;
-        if (L->K != K || L->N != N)
-            return fail(GPTQ_ERR_SHAPE, "expert %d %s is [%d -> %d], expected [%d -> %d]", e, name, L->K, L->N, K, N);
-        if (L->bits != A->bits || L->group_size != Ls[0]->group_size || L->dtype != A->dtype || L->zero_mode != Ls[0]->zero_mode)
-            return fail(GPTQ_ERR_UNSUPPORTED, "the %s layers of all experts must share bits, group_size, dtype and zero_mode (expert %d differs)", name, e);
-        if (L->bias || L->epilogue != GPTQ_EPI_NONE)
-            return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s: the batch path takes no bias and no epilogue", e, name);
-        if (!moe_batch_group_ok(*L))
-            return fail(GPTQ_ERR_UNSUPPORTED, "group_size %d: the batch path takes 32, 64, 128 times a power of two, or one group", L->group_size);
-        if (!L->qweight_tiled || !L->qconst_tiled)
-            return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s carries no decode copy (QuantMoEExperts.post_init(batch=True) builds it)", e, name);
-        if (!tiled_layer_ok(*L))
-            return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s: raw act-order (no re-sequenced rows) is not taken by the decode copy", e, name);
-    }
-    return GPTQ_OK;
-}
-
-static int moe_batch_check(const gptq_moe_t* m, int T, int topk) {
-    if (!m) return fail(GPTQ_ERR_NULL, "moe is NULL");
-    if (m->E < 1 || m->E > 256) return fail(GPTQ_ERR_UNSUPPORTED, "E = %d experts: the batch path takes 1..256", m->E);
-    if (topk < 1 || topk > 8) return fail(GPTQ_ERR_UNSUPPORTED, "topk = %d: the batch path takes 1..8", topk);
-    if (T < 0) return fail(GPTQ_ERR_SHAPE, "T must be >= 0, got %d", T);
-    if (T > 64) return fail(GPTQ_ERR_UNSUPPORTED, "T = %d tokens: the batch path takes 1..64 (the grouped path serves more)", T);
-    if (!m->gate || !m->up || !m->down || !m->gate[0]) return fail(GPTQ_ERR_NULL, "moe->gate / up / down must be non-NULL");
-    const gptq_layer_t* G = m->gate[0];
-    if (int rc = check_layer(G)) return rc;
-    if (G->dtype != GPTQ_F16 && G->dtype != GPTQ_BF16) return fail(GPTQ_ERR_UNSUPPORTED, "fp32 experts: the batch path takes fp16 / bf16");
-    if (G->bits != 4 && G->bits != 8) return fail(GPTQ_ERR_UNSUPPORTED, "%d-bit experts: the batch path takes 4 or 8 bits", G->bits);
-    const int H = G->K, I = G->N;
-    if (H % 128 || I % 128) return fail(GPTQ_ERR_UNSUPPORTED, "hidden (%d) and intermediate (%d) sizes must be multiples of 128", H, I);
-    if (int rc = moe_batch_check_proj(m->gate, m->E, H, I, G, "gate")) return rc;
-    if (int rc = moe_batch_check_proj(m->up, m->E, H, I, G, "up")) return rc;
-    const gptq_layer_t* U = m->up[0];
-    if (U->group_size != G->group_size || U->zero_mode != G->zero_mode)
-        return fail(GPTQ_ERR_UNSUPPORTED, "gate and up layers must share bits, group_size and zero_mode");
-    return moe_batch_check_proj(m->down, m->E, I, H, G, "down");
-}
-
 size_t gptq_moe_batch_workspace_bytes(const gptq_moe_t* m, int T, int topk) {
-    if (moe_batch_check(m, T, topk)) return 0;
+    if (moe_check(MOE_BATCH, m, T, topk)) return 0;
     return plan_moe_batch(*m, T, topk).bytes;
 }
 
 int gptq_moe_batch_forward(const gptq_moe_t* m, const void* table, const void* x, const int64_t* idx, const float* w, int T, int topk, void* out, void* h_out,
                            void* ws, size_t ws_bytes, void* stream) {
-    if (int rc = moe_batch_check(m, T, topk)) return rc;
+    if (int rc = moe_check(MOE_BATCH, m, T, topk)) return rc;
     if (T == 0) return GPTQ_OK;
-    if (!table || !x || !idx || !w || !out) return fail(GPTQ_ERR_NULL, "table / x / topk_idx / topk_w / out must be non-NULL");
-    if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)ws) & 15) return fail(GPTQ_ERR_UNSUPPORTED, "x / out / workspace must be 16-byte aligned");
     const MoeBatchPlan pl = plan_moe_batch(*m, T, topk);
-    if (!ws || ws_bytes < pl.bytes) return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", pl.bytes, ws ? ws_bytes : (size_t)0);
+    if (int rc = moe_forward_args("table", table, x, idx, w, out, ws, ws_bytes, pl.bytes)) return rc;
     hipError_t e = launch_moe_batch(*m, table, pl, x, idx, w, T, topk, out, (char*)ws, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "gptq_moe_batch_forward launch (was gptq_init() called on this device?)");
-    if (h_out) {
-        const gptq_layer_t* G = m->gate[0];
-        const size_t R = (size_t)T * topk, hb = R * G->N * dtype_size(G->dtype);
-        e = hipMemcpyAsync(h_out, (char*)ws + pl.off_h, hb, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-        if (e == hipSuccess) e = hipMemcpyAsync((char*)h_out + hb, (char*)ws + pl.off_pos, 4 * R, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-        if (e != hipSuccess) return hip_fail(e, "gptq_moe_batch_forward h_out copy");
-    }
-    return GPTQ_OK;
+    return moe_copy_h_out(m, h_out, ws, pl.off_h, pl.off_pos, T, topk, stream, "gptq_moe_batch_forward h_out copy");
 }
 
 int gptq_describe_moe_batch_plan(const gptq_moe_t* m, int T, int topk, char* out, size_t out_bytes) {
     if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out is NULL");
-    if (moe_batch_check(m, T, topk)) {
-        char reason[sizeof(g_err)];
-        snprintf(reason, sizeof(reason), "%s", g_err);
-        for (char* c = reason; *c; ++c)
-            if (*c == ' ' || *c == '=') *c = '_';
-        snprintf(out, out_bytes, "path=none reason=%s", reason);
-        return GPTQ_OK;
-    }
+    if (moe_check(MOE_BATCH, m, T, topk)) return describe_decline(out, out_bytes, "none");
     const MoeBatchPlan pl = plan_moe_batch(*m, T, topk);
     snprintf(out, out_bytes, "path=batch bm=%d s=%d tiles=%d launches=%d waves_pair=%d waves_down=%d lds_pair=%d lds_down=%d", pl.bm, pl.s, pl.tiles, pl.launches,
              pl.waves_pair, pl.waves_down, pl.lds_pair, pl.lds_down);
@@ -1613,86 +1488,25 @@ int gptq_describe_moe_batch_plan(const gptq_moe_t* m, int T, int topk, char* out
 }
 
 // ---- the same layers at prompt row counts on the experts' decode copy (moe_panel.hip) ----
-static int moe_prefill_check_proj(const gptq_layer_t* const* Ls, int E, int K, int N, const gptq_layer_t* A, const char* name) {
-    if (!Ls) return fail(GPTQ_ERR_NULL, "moe->%s is NULL", name);
-    for (int e = 0; e < E; ++e) {
-        const gptq_layer_t* L = Ls[e];
-        if (int rc = check_layer(L)) return rc;
-        if (L->K != K || L->N != N)
-            return fail(GPTQ_ERR_SHAPE, "expert %d %s is [%d -> %d], expected [%d -> %d]", e, name, L->K, L->N, K, N);
-        if (L->bits != A->bits || L->group_size != Ls[0]->group_size || L->dtype != A->dtype || L->zero_mode != Ls[0]->zero_mode)
-            return fail(GPTQ_ERR_UNSUPPORTED, "the %s layers of all experts must share bits, group_size, dtype and zero_mode (expert %d differs)", name, e);
-        if (L->bias || L->epilogue != GPTQ_EPI_NONE)
-            return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s: the prefill path takes no bias and no epilogue", e, name);
-        if (!moe_prefill_group_ok(*L))
-            return fail(GPTQ_ERR_UNSUPPORTED, "group_size %d: the prefill path takes 64 times a power of two, or one group", L->group_size);
-        if (!L->qweight_tiled || !L->qconst_tiled)
-            return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s carries no decode copy (QuantMoEExperts.post_init(prefill=True) builds it)", e, name);
-        if (!tiled_layer_ok(*L))
-            return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s: raw act-order (no re-sequenced rows) is not taken by the decode copy", e, name);
-        if (((uintptr_t)L->qweight_tiled | (uintptr_t)L->qconst_tiled) & 15)
-            return fail(GPTQ_ERR_UNSUPPORTED, "expert %d %s: the decode copy must be 16-byte aligned", e, name);
-    }
-    return GPTQ_OK;
-}
-
-static int moe_prefill_check(const gptq_moe_t* m, int T, int topk) {
-    if (!m) return fail(GPTQ_ERR_NULL, "moe is NULL");
-    if (m->E < 1 || m->E > 256) return fail(GPTQ_ERR_UNSUPPORTED, "E = %d experts: the prefill path takes 1..256", m->E);
-    if (topk < 1 || topk > 8) return fail(GPTQ_ERR_UNSUPPORTED, "topk = %d: the prefill path takes 1..8", topk);
-    if (T < 0) return fail(GPTQ_ERR_SHAPE, "T must be >= 0, got %d", T);
-    if ((long)T * topk > GPTQ_MOE_PREFILL_MAX_ROWS)
-        return fail(GPTQ_ERR_UNSUPPORTED, "T topk = %ld rows: the prefill path takes up to %d (the grouped path serves more)", (long)T * topk, GPTQ_MOE_PREFILL_MAX_ROWS);
-    if (!m->gate || !m->up || !m->down || !m->gate[0]) return fail(GPTQ_ERR_NULL, "moe->gate / up / down must be non-NULL");
-    const gptq_layer_t* G = m->gate[0];
-    if (int rc = check_layer(G)) return rc;
-    if (G->dtype != GPTQ_F16 && G->dtype != GPTQ_BF16) return fail(GPTQ_ERR_UNSUPPORTED, "fp32 experts: the prefill path takes fp16 / bf16");
-    if (G->bits != 4 && G->bits != 8) return fail(GPTQ_ERR_UNSUPPORTED, "%d-bit experts: the prefill path takes 4 or 8 bits", G->bits);
-    const int H = G->K, I = G->N;
-    if (H % 128 || I % 128) return fail(GPTQ_ERR_UNSUPPORTED, "hidden (%d) and intermediate (%d) sizes must be multiples of 128", H, I);
-    if (int rc = moe_prefill_check_proj(m->gate, m->E, H, I, G, "gate")) return rc;
-    if (int rc = moe_prefill_check_proj(m->up, m->E, H, I, G, "up")) return rc;
-    const gptq_layer_t* U = m->up[0];
-    if (U->group_size != G->group_size || U->zero_mode != G->zero_mode)
-        return fail(GPTQ_ERR_UNSUPPORTED, "gate and up layers must share bits, group_size and zero_mode");
-    return moe_prefill_check_proj(m->down, m->E, I, H, G, "down");
-}
-
 size_t gptq_moe_prefill_workspace_bytes(const gptq_moe_t* m, int T, int topk) {
-    if (moe_prefill_check(m, T, topk)) return 0;
+    if (moe_check(MOE_PREFILL, m, T, topk)) return 0;
     return plan_moe_prefill(*m, T, topk).bytes;
 }
 
 int gptq_moe_prefill_forward(const gptq_moe_t* m, const void* table, const void* x, const int64_t* idx, const float* w, int T, int topk, void* out, void* h_out,
                              void* ws, size_t ws_bytes, void* stream) {
-    if (int rc = moe_prefill_check(m, T, topk)) return rc;
+    if (int rc = moe_check(MOE_PREFILL, m, T, topk)) return rc;
     if (T == 0) return GPTQ_OK;
-    if (!table || !x || !idx || !w || !out) return fail(GPTQ_ERR_NULL, "table / x / topk_idx / topk_w / out must be non-NULL");
-    if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)ws) & 15) return fail(GPTQ_ERR_UNSUPPORTED, "x / out / workspace must be 16-byte aligned");
     const MoePrefillPlan pl = plan_moe_prefill(*m, T, topk);
-    if (!ws || ws_bytes < pl.bytes) return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", pl.bytes, ws ? ws_bytes : (size_t)0);
+    if (int rc = moe_forward_args("table", table, x, idx, w, out, ws, ws_bytes, pl.bytes)) return rc;
     hipError_t e = launch_moe_prefill(*m, table, pl, x, idx, w, T, topk, out, (char*)ws, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "gptq_moe_prefill_forward launch (was gptq_init() called on this device?)");
-    if (h_out) {
-        const gptq_layer_t* G = m->gate[0];
-        const size_t R = (size_t)T * topk, hb = R * G->N * dtype_size(G->dtype);
-        e = hipMemcpyAsync(h_out, (char*)ws + pl.off_h, hb, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-        if (e == hipSuccess) e = hipMemcpyAsync((char*)h_out + hb, (char*)ws + pl.off_pos, 4 * R, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-        if (e != hipSuccess) return hip_fail(e, "gptq_moe_prefill_forward h_out copy");
-    }
-    return GPTQ_OK;
+    return moe_copy_h_out(m, h_out, ws, pl.off_h, pl.off_pos, T, topk, stream, "gptq_moe_prefill_forward h_out copy");
 }
 
 int gptq_describe_moe_prefill_plan(const gptq_moe_t* m, int T, int topk, char* out, size_t out_bytes) {
     if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out is NULL");
-    if (moe_prefill_check(m, T, topk)) {
-        char reason[sizeof(g_err)];
-        snprintf(reason, sizeof(reason), "%s", g_err);
-        for (char* c = reason; *c; ++c)
-            if (*c == ' ' || *c == '=') *c = '_';
-        snprintf(out, out_bytes, "path=none reason=%s", reason);
-        return GPTQ_OK;
-    }
+    if (moe_check(MOE_PREFILL, m, T, topk)) return describe_decline(out, out_bytes, "none");
     const MoePrefillPlan pl = plan_moe_prefill(*m, T, topk);
     snprintf(out, out_bytes, "path=prefill bm=%d launches=%d tiles=%d nt_pair=%d nt_down=%d waves=%d waves_pair=%d spw_pair=%d spw_down=%d lds=%d", pl.bm, pl.launches,
              pl.tiles, pl.nt_pair, pl.nt_down, pl.waves_down, pl.waves_pair, pl.spw_pair, pl.spw_down, pl.lds_down);

@@ -178,10 +178,28 @@ hipError_t launch_dequant(const gptq_layer_t& L, void* W_out, hipStream_t st);
 int grad_input_bm(const gptq_layer_t& L, int M);
 hipError_t launch_grad_input(const gptq_layer_t& L, const void* dy, void* dx, int M, int accumulate, hipStream_t st);
 
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }      // the rounding of every workspace segment
+inline bool any_perm_of(const gptq_layer_t* const* Ls, int E) {
+    for (int e = 0; e < E; ++e)
+        if (Ls[e]->perm) return true;
+    return false;
+}
+// The routing block moe_route_kernel fills, as every plan that launches it lays it out: offsets [E + 1], the tile count, tiles (int4 each), pos [R], row_assign [R].
+struct RouteLayout {
+    size_t off_offsets, off_tile_count, off_tiles, off_pos, off_rows;
+};
+inline size_t append_route_layout(RouteLayout& rl, size_t o, size_t E, size_t tiles, size_t R) {      // returns the offset behind the block
+    rl.off_offsets = o; o += align256(4 * (E + 1));
+    rl.off_tile_count = o; o += 256;
+    rl.off_tiles = o; o += align256(16 * tiles);
+    rl.off_pos = o; o += align256(4 * R);
+    rl.off_rows = o; o += align256(4 * R);
+    return o;
+}
 // moe.hip: routed mixture-of-experts layers (gptq_moe_forward): routing table, grouped W1 / W3 + silu * mul, grouped W2, combine -- four launches
-struct MoePlan {
+struct MoePlan : RouteLayout {
     int bm, bn, tiles, ksplit, steps_per_split;     // tile height, column block, tile bound, K slices of the down projection and their 32-deep steps
-    size_t off_offsets, off_tile_count, off_tiles, off_pos, off_rows, off_h, off_y, bytes;   // workspace layout (from GPTQ_WORKSPACE_HEADER_BYTES on)
+    size_t off_h, off_y, bytes;                     // workspace layout behind the routing block (from GPTQ_WORKSPACE_HEADER_BYTES on)
 };
 MoePlan plan_moe(int E, int T, int topk, int H, int I, int dtype);
 size_t moe_table_entry_bytes();
@@ -197,9 +215,9 @@ hipError_t launch_moe_combine(const int* pos, const float* w, const float* y, vo
 hipError_t launch_moe_recompute(const gptq_moe_t& m, const void* table, const void* x, const int* row_assign, const int* tile_count, const void* tiles,
                                 int tiles_bound, int T, int topk, void* g_out, void* u_out, hipStream_t st);
 // moe_grad.hip: the backward of the routed layer (gptq_moe_backward): route, recompute g / u, down stage, up stage, combine -- five launches
-struct MoeGradPlan {
+struct MoeGradPlan : RouteLayout {
     int tiles, nblk_i, nblk_h;                      // tile bound (64-row tiles), 128-column blocks of I and of H
-    size_t off_offsets, off_tile_count, off_tiles, off_pos, off_rows, off_g, off_u, off_dwp, off_dxr, bytes;   // workspace layout (from GPTQ_WORKSPACE_HEADER_BYTES on)
+    size_t off_g, off_u, off_dwp, off_dxr, bytes;   // workspace layout behind the routing block (from GPTQ_WORKSPACE_HEADER_BYTES on)
 };
 MoeGradPlan plan_moe_grad(int E, int T, int topk, int H, int I, int dtype);
 size_t moe_grad_table_entry_bytes();
@@ -234,11 +252,11 @@ hipError_t launch_moe_shared_combine(const void* x, const void* gate_w, const vo
 hipError_t init_moe_shared_device();
 // moe_rows.hip: the same layer at 5..64 tokens on the experts' decode copy (gptq_moe_batch_forward): route, gate|up + silu * mul, down, combine -- four
 // launches (act-order experts: + one row gather through perm in front of either GEMM)
-struct MoeBatchPlan {
+struct MoeBatchPlan : RouteLayout {
     bool act_pair, act_down;                        // some gate / up (down) expert is act-order: the gather pre-pass runs
     int bm, s, tiles, launches;                     // tile height, strip-chunks per wave and chunk, tile bound
     int waves_pair, waves_down, cpw_pair, cpw_down, lds_pair, lds_down;
-    size_t off_offsets, off_tile_count, off_tiles, off_pos, off_rows, off_h, off_y, off_xg, off_hg, bytes;   // workspace layout (from GPTQ_WORKSPACE_HEADER_BYTES on)
+    size_t off_h, off_y, off_xg, off_hg, bytes;     // workspace layout behind the routing block (from GPTQ_WORKSPACE_HEADER_BYTES on)
 };
 bool moe_batch_group_ok(const gptq_layer_t& L);    // a group size the rows family takes
 MoeBatchPlan plan_moe_batch(const gptq_moe_t& m, int T, int topk);
@@ -252,12 +270,12 @@ hipError_t launch_moe_gather_rows(const void* table, int planes, int topk, const
 // moe_panel.hip: the same layer at any token count on the experts' decode copy (gptq_moe_prefill_forward; Python: 65 tokens and more): route with 64-row
 // tiles, x into sorted order, gate|up + silu * mul, down, combine -- five launches (act-order down projections: + the gather of H_sorted through perm)
 constexpr int GPTQ_MOE_PREFILL_MAX_ROWS = 65535;    // T topk: the gather's grid
-struct MoePrefillPlan {
+struct MoePrefillPlan : RouteLayout {
     bool act_pair, act_down;                        // some gate / up (down) expert is act-order: two planes of x_sorted / the gather of H_sorted
     int bm, tiles, launches;                        // tile height, tile bound
     int nt_pair, nt_down;                           // 32-column blocks of I (of both W1 and W3) / of H per workgroup
     int waves_pair, waves_down, spw_pair, spw_down, lds_pair, lds_down;
-    size_t off_offsets, off_tile_count, off_tiles, off_pos, off_rows, off_xs, off_h, off_y, off_hg, bytes;   // workspace layout (from GPTQ_WORKSPACE_HEADER_BYTES on)
+    size_t off_xs, off_h, off_y, off_hg, bytes;     // workspace layout behind the routing block (from GPTQ_WORKSPACE_HEADER_BYTES on)
 };
 bool moe_prefill_group_ok(const gptq_layer_t& L);  // 64 times a power of two, or one group
 MoePrefillPlan plan_moe_prefill(const gptq_moe_t& m, int T, int topk);
@@ -307,9 +325,9 @@ hipError_t launch_wgrad(const gptq_lora_t* const* Ls, const gptq_lora_grad_t* co
 // adapter_rows.hip: per-row adapter banks (gptq_adapter_route, gptq_adapter_rows_apply): moe_route_kernel with 16-row tiles, one down launch, one up launch
 constexpr int GPTQ_ADAPTER_TILE_ROWS = 16;
 constexpr int GPTQ_ADAPTER_MAX_SLOTS = 256;         // the routing kernel's LDS arrays
-struct AdapterRoutePlan {
+struct AdapterRoutePlan : RouteLayout {
     long tiles;                                     // tile bound: M / 16 + min(slots, M)
-    size_t off_offsets, off_tile_count, off_tiles, off_pos, off_rows, bytes;   // layout of the route buffer
+    size_t bytes;                                   // of the route buffer: the routing block from offset 0
 };
 struct AdapterRowsPlan {
     long tiles, units_down, units_up, wg_down, wg_up;

@@ -435,8 +435,6 @@ __global__ void __launch_bounds__(256) moe_combine_kernel(CombineArgs p) {
 
 }  // namespace moe
 
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 MoePlan plan_moe(int E, int T, int topk, int H, int I, int dtype) {
     MoePlan pl{};
     const long R = (long)T * topk;
@@ -452,12 +450,7 @@ MoePlan plan_moe(int E, int T, int topk, int H, int I, int dtype) {
     while (wg2 * pl.ksplit * 2 <= 512 && pl.ksplit < 8 && steps / (pl.ksplit * 2) >= 32) pl.ksplit *= 2;
     pl.steps_per_split = (steps + pl.ksplit - 1) / pl.ksplit;
     const size_t es = dtype_size(dtype);
-    size_t o = GPTQ_WORKSPACE_HEADER_BYTES;                      // the header of a shared workspace belongs to the other entry points: left as it is
-    pl.off_offsets = o; o += align256(4 * (size_t)(E + 1));
-    pl.off_tile_count = o; o += 256;
-    pl.off_tiles = o; o += align256(16 * (size_t)pl.tiles);
-    pl.off_pos = o; o += align256(4 * (size_t)R);
-    pl.off_rows = o; o += align256(4 * (size_t)R);
+    size_t o = append_route_layout(pl, GPTQ_WORKSPACE_HEADER_BYTES, E, pl.tiles, R);      // the header of a shared workspace belongs to the other entry points: left as it is
     pl.off_h = o; o += align256((size_t)R * I * es);
     pl.off_y = o; o += align256((size_t)pl.ksplit * R * H * 4);
     pl.bytes = o;

@@ -384,8 +384,6 @@ __global__ void __launch_bounds__(256) moe_grad_combine_kernel(CombineArgs p) {
 
 }  // namespace mgrad
 
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 MoeGradPlan plan_moe_grad(int E, int T, int topk, int H, int I, int dtype) {
     MoeGradPlan pl{};
     const long R = (long)T * topk;
@@ -393,12 +391,7 @@ MoeGradPlan plan_moe_grad(int E, int T, int topk, int H, int I, int dtype) {
     pl.nblk_i = (I + mgrad::BK - 1) / mgrad::BK;
     pl.nblk_h = (H + mgrad::BK - 1) / mgrad::BK;
     const size_t es = dtype_size(dtype);
-    size_t o = GPTQ_WORKSPACE_HEADER_BYTES;                      // the header of a shared workspace belongs to the other entry points: left as it is
-    pl.off_offsets = o; o += align256(4 * (size_t)(E + 1));
-    pl.off_tile_count = o; o += 256;
-    pl.off_tiles = o; o += align256(16 * (size_t)pl.tiles);
-    pl.off_pos = o; o += align256(4 * (size_t)R);
-    pl.off_rows = o; o += align256(4 * (size_t)R);
+    size_t o = append_route_layout(pl, GPTQ_WORKSPACE_HEADER_BYTES, E, pl.tiles, R);      // the header of a shared workspace belongs to the other entry points: left as it is
     pl.off_g = o; o += align256((size_t)R * I * es);
     pl.off_u = o; o += align256((size_t)R * I * es);
     pl.off_dwp = o; o += align256(4 * (size_t)R * pl.nblk_i);

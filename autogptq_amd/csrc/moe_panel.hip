@@ -324,13 +324,6 @@ static int group_shift(const gptq_layer_t& L) {                 // group of the 
     return __builtin_ctz((unsigned)q);
 }
 
-static bool any_perm_of(const gptq_layer_t* const* Ls, int E) {
-    for (int e = 0; e < E; ++e)
-        if (Ls[e]->perm) return true;
-    return false;
-}
-static size_t b256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace moepanel
 
 bool moe_prefill_group_ok(const gptq_layer_t& L) { return moepanel::group_shift(L) >= 0; }
@@ -354,16 +347,11 @@ MoePrefillPlan plan_moe_prefill(const gptq_moe_t& m, int T, int topk) {
     pl.lds_pair = pl.lds_down = LDS_BYTES;
     pl.launches = T > 0 ? 5 + (pl.act_down ? 1 : 0) : 0;
     const size_t es = dtype_size(G.dtype);
-    size_t o = GPTQ_WORKSPACE_HEADER_BYTES;                      // the header of a shared workspace belongs to the other entry points: left as it is
-    pl.off_offsets = o; o += b256(4 * (size_t)(E + 1));
-    pl.off_tile_count = o; o += 256;
-    pl.off_tiles = o; o += b256(16 * (size_t)pl.tiles);
-    pl.off_pos = o; o += b256(4 * (size_t)R);
-    pl.off_rows = o; o += b256(4 * (size_t)R);
-    pl.off_xs = o; o += b256((pl.act_pair ? 2 : 1) * (size_t)R * H * es);      // x in sorted order (act-order: through W1's / W3's perm, two planes)
-    pl.off_h = o; o += b256((size_t)R * I * es);
-    pl.off_y = o; o += b256((size_t)R * H * 4);
-    pl.off_hg = o; o += pl.act_down ? b256((size_t)R * I * es) : 0;            // act-order: H_sorted through W2's perm
+    size_t o = append_route_layout(pl, GPTQ_WORKSPACE_HEADER_BYTES, E, pl.tiles, R);      // the header of a shared workspace belongs to the other entry points: left as it is
+    pl.off_xs = o; o += align256((pl.act_pair ? 2 : 1) * (size_t)R * H * es);      // x in sorted order (act-order: through W1's / W3's perm, two planes)
+    pl.off_h = o; o += align256((size_t)R * I * es);
+    pl.off_y = o; o += align256((size_t)R * H * 4);
+    pl.off_hg = o; o += pl.act_down ? align256((size_t)R * I * es) : 0;            // act-order: H_sorted through W2's perm
     pl.bytes = o;
     return pl;
 }

@@ -328,13 +328,6 @@ static int group_mode(const gptq_layer_t& L) {                  // what the rows
 
 }  // namespace moerows
 
-static size_t b256(size_t b) { return (b + 255) & ~(size_t)255; }
-static bool any_perm_of(const gptq_layer_t* const* Ls, int E) {
-    for (int e = 0; e < E; ++e)
-        if (Ls[e]->perm) return true;
-    return false;
-}
-
 bool moe_batch_group_ok(const gptq_layer_t& L) { return moerows::group_mode(L) >= 0; }
 
 MoeBatchPlan plan_moe_batch(const gptq_moe_t& m, int T, int topk) {
@@ -358,16 +351,11 @@ MoeBatchPlan plan_moe_batch(const gptq_moe_t& m, int T, int topk) {
     pl.lds_down = pl.waves_down * 2 * moerows::XB;
     pl.launches = T > 0 ? 4 + (pl.act_pair ? 1 : 0) + (pl.act_down ? 1 : 0) : 0;
     const size_t es = dtype_size(G.dtype);
-    size_t o = GPTQ_WORKSPACE_HEADER_BYTES;                      // the header of a shared workspace belongs to the other entry points: left as it is
-    pl.off_offsets = o; o += b256(4 * (size_t)(E + 1));
-    pl.off_tile_count = o; o += 256;
-    pl.off_tiles = o; o += b256(16 * (size_t)pl.tiles);
-    pl.off_pos = o; o += b256(4 * (size_t)R);
-    pl.off_rows = o; o += b256(4 * (size_t)R);
-    pl.off_h = o; o += b256((size_t)R * I * es);
-    pl.off_y = o; o += b256((size_t)R * H * 4);
-    pl.off_xg = o; o += b256(2 * (size_t)R * H * es);            // act-order: x through W1's / W3's perm (two planes)
-    pl.off_hg = o; o += b256((size_t)R * I * es);                // act-order: H_sorted through W2's perm
+    size_t o = append_route_layout(pl, GPTQ_WORKSPACE_HEADER_BYTES, E, pl.tiles, R);      // the header of a shared workspace belongs to the other entry points: left as it is
+    pl.off_h = o; o += align256((size_t)R * I * es);
+    pl.off_y = o; o += align256((size_t)R * H * 4);
+    pl.off_xg = o; o += align256(2 * (size_t)R * H * es);            // act-order: x through W1's / W3's perm (two planes)
+    pl.off_hg = o; o += align256((size_t)R * I * es);                // act-order: H_sorted through W2's perm
     pl.bytes = o;
     return pl;
 }

@@ -37,6 +37,7 @@ from __future__ import annotations
 
 import ctypes
 import types
+from collections import namedtuple
 from logging import getLogger
 
 import torch
@@ -49,6 +50,24 @@ from .qlinear_mi355x import QuantLinear, _raw_stream, exchange_tick, forward_mul
 logger = getLogger(__name__)
 
 DEFAULT_NAMES = ("w1", "w3", "w2")          # gate, up, down (AutoGPTQ's Mixtral names)
+
+# The routed paths of the C ABI: the describe function, the workspace-bytes and the forward symbol, and the attribute that holds the table the forward reads.
+_Path = namedtuple("_Path", "describe workspace forward table")
+_PATHS = {
+    "decode": _Path(_lib.describe_moe_decode_plan, "gptq_moe_decode_workspace_bytes", "gptq_moe_decode_forward", "_decode_table"),
+    "batch": _Path(_lib.describe_moe_batch_plan, "gptq_moe_batch_workspace_bytes", "gptq_moe_batch_forward", "_decode_table"),
+    "prefill": _Path(_lib.describe_moe_prefill_plan, "gptq_moe_prefill_workspace_bytes", "gptq_moe_prefill_forward", "_decode_table"),
+    "grouped": _Path(_lib.describe_moe_plan, "gptq_moe_workspace_bytes", "gptq_moe_forward", "_table"),
+}
+# What the Python side knows of the batch / the prefill path's group-size rule: (base, other sizes taken, the message's wording); gs >= K is one group
+_BATCH_GROUPS = (128, (32, 64), "32, 64, 128 times a power of two, or one group")
+_PREFILL_GROUPS = (64, (), "64 times a power of two, or one group")
+
+
+def _clean_reason(d: dict) -> dict:
+    """A describe answer with its reason readable: always present, the C side's '_' back to blanks."""
+    d["reason"] = str(d.get("reason", "")).replace("_", " ")
+    return d
 
 
 class _Expert(nn.Module):
@@ -198,7 +217,7 @@ class QuantMoEExperts(nn.Module):
             gplan = _lib.describe_moe_backward_plan(m, 1, self.top_k)
             if gplan["path"] != "grouped_backward":
                 logger.warning("QuantMoEExperts.post_init(backward=True) has no effect for these experts (%s): calls under grad keep the per-expert "
-                               "composition", str(gplan.get("reason", "")).replace("_", " "))
+                               "composition", _clean_reason(gplan)["reason"])
             else:
                 gtable = torch.zeros(max(1, int(lib.gptq_moe_grad_table_bytes(self.num_experts))), dtype=torch.uint8, device=dev)
                 with torch.cuda.device(self._dev):
@@ -209,16 +228,16 @@ class QuantMoEExperts(nn.Module):
             if dplan["path"] != "decode":
                 # declined (2- / 3-bit, fp32, a group size the copy does not take, ...): nothing would read the copies -- say so and give their memory back
                 logger.warning("QuantMoEExperts.post_init(decode_copy=True) has no effect for these experts (%s): no decode copy is kept",
-                               str(dplan.get("reason", "")).replace("_", " "))
+                               _clean_reason(dplan)["reason"])
                 return self.post_init(decode_copy=False, backward=self._backward, low_bit=self._low_bit)      # (batch, prefill and low_bit_decode need the copy: declined with it)
             bplan = _lib.describe_moe_batch_plan(m, 5, self.top_k) if self._batch else None
             if bplan is not None and bplan["path"] != "batch":
-                logger.warning("QuantMoEExperts.post_init(batch=True) has no effect for these experts (%s)", str(bplan.get("reason", "")).replace("_", " "))
+                logger.warning("QuantMoEExperts.post_init(batch=True) has no effect for these experts (%s)", _clean_reason(bplan)["reason"])
                 return self.post_init(decode_copy=want_decode, backward=self._backward, low_bit=self._low_bit, prefill=self._prefill,
                                       low_bit_decode=self._low_bit_decode)
             pplan = _lib.describe_moe_prefill_plan(m, 65, self.top_k) if self._prefill else None
             if pplan is not None and pplan["path"] != "prefill":
-                logger.warning("QuantMoEExperts.post_init(prefill=True) has no effect for these experts (%s)", str(pplan.get("reason", "")).replace("_", " "))
+                logger.warning("QuantMoEExperts.post_init(prefill=True) has no effect for these experts (%s)", _clean_reason(pplan)["reason"])
                 return self.post_init(decode_copy=want_decode, batch=self._batch, backward=self._backward, low_bit=self._low_bit,
                                       low_bit_decode=self._low_bit_decode)
             dtable = torch.zeros(max(1, int(lib.gptq_moe_decode_table_bytes(self.num_experts))), dtype=torch.uint8, device=dev)
@@ -230,33 +249,32 @@ class QuantMoEExperts(nn.Module):
             self._plans = {}
         return self
 
-    def _batch_declined(self) -> str:
-        """Why the batch plan would decline these experts, as far as the layer metadata says (empty: build the copies and ask the plan)."""
+    def _ensure_init(self):
+        """post_init with the stored flags when the tables were invalidated (a move, a state-dict load, a repack)."""
+        if self._moe is None:
+            self.post_init(self._decode_copy, self._batch, self._backward, self._low_bit, self._prefill, self._low_bit_decode)
+
+    def _copy_path_declined(self, word: str, multiple: int, group_rule) -> str:
+        """Why the `word` plan would decline these experts, as far as the layer metadata says (empty: build the copies and ask the plan)."""
         gate, _, down = self[0].layers()
-        if self.hidden_dim % 128 or self.intermediate_dim % 128:
-            return "hidden and intermediate sizes must be multiples of 128"
+        if self.hidden_dim % multiple or self.intermediate_dim % multiple:
+            return f"hidden and intermediate sizes must be multiples of {multiple}"
+        base, others, text = group_rule
         for l in (gate, down):
-            gs, K = l.group_size, l.infeatures
-            q = gs // 128
-            if not (gs in (32, 64) or gs >= K or (gs % 128 == 0 and q & (q - 1) == 0)):
-                return f"group_size {gs}: the batch path takes 32, 64, 128 times a power of two, or one group"
+            gs, q = l.group_size, l.group_size // base
+            if not (gs in others or gs >= l.infeatures or (gs % base == 0 and q & (q - 1) == 0)):
+                return f"group_size {gs}: the {word} path takes {text}"
         if self.bits in (2, 3):
-            return f"{self.bits}-bit experts: the batch path takes 4 or 8 bits"
-        return self._decode_copy_declined().replace("the decode path", "the batch path")
+            return f"{self.bits}-bit experts: the {word} path takes 4 or 8 bits"
+        return self._decode_copy_declined().replace("the decode path", f"the {word} path")
+
+    def _batch_declined(self) -> str:
+        """Why the batch plan would decline these experts, as far as the layer metadata says."""
+        return self._copy_path_declined("batch", 128, _BATCH_GROUPS)
 
     def _prefill_declined(self) -> str:
-        """Why the prefill plan would decline these experts, as far as the layer metadata says (empty: build the copies and ask the plan)."""
-        gate, _, down = self[0].layers()
-        if self.hidden_dim % 128 or self.intermediate_dim % 128:
-            return "hidden and intermediate sizes must be multiples of 128"
-        for l in (gate, down):
-            gs, K = l.group_size, l.infeatures
-            q = gs // 64
-            if not (gs >= K or (gs % 64 == 0 and q & (q - 1) == 0)):
-                return f"group_size {gs}: the prefill path takes 64 times a power of two, or one group"
-        if self.bits in (2, 3):
-            return f"{self.bits}-bit experts: the prefill path takes 4 or 8 bits"
-        return self._decode_copy_declined().replace("the decode path", "the prefill path")
+        """Why the prefill plan would decline these experts, as far as the layer metadata says."""
+        return self._copy_path_declined("prefill", 128, _PREFILL_GROUPS)
 
     def _decode_copy_declined(self) -> str:
         """Why the decode plan would decline these experts, as far as the layer metadata says (empty: build the copies and ask the plan)."""
@@ -279,21 +297,13 @@ class QuantMoEExperts(nn.Module):
 
     def workspace_bytes(self, T: int, top_k: "int | None" = None) -> int:
         """Scratch of one call with T tokens on the path ``plan(T)`` names."""
-        if self._moe is None:
-            self.post_init(self._decode_copy, self._batch, self._backward, self._low_bit, self._prefill, self._low_bit_decode)
-        path = self.plan(T, top_k)["path"]
-        if path == "decode":
-            return int(_lib.load().gptq_moe_decode_workspace_bytes(ctypes.byref(self._moe), T, top_k or self.top_k))
-        if path == "batch":
-            return int(_lib.load().gptq_moe_batch_workspace_bytes(ctypes.byref(self._moe), T, top_k or self.top_k))
-        if path == "prefill":
-            return int(_lib.load().gptq_moe_prefill_workspace_bytes(ctypes.byref(self._moe), T, top_k or self.top_k))
-        return int(_lib.load().gptq_moe_workspace_bytes(ctypes.byref(self._moe), T, top_k or self.top_k))
+        self._ensure_init()
+        fn = _PATHS.get(self.plan(T, top_k)["path"], _PATHS["grouped"]).workspace          # (per_expert: the grouped entry point's answer, 0)
+        return int(getattr(_lib.load(), fn)(ctypes.byref(self._moe), T, top_k or self.top_k))
 
     def backward_workspace_bytes(self, T: int, top_k: "int | None" = None) -> int:
         """Scratch of one gptq_moe_backward call with T tokens (0 when the experts have no grouped backward)."""
-        if self._moe is None:
-            self.post_init(self._decode_copy, self._batch, self._backward, self._low_bit, self._prefill, self._low_bit_decode)
+        self._ensure_init()
         if self._grad_table is None:
             return 0
         return int(_lib.load().gptq_moe_backward_workspace_bytes(ctypes.byref(self._moe), T, top_k or self.top_k))
@@ -306,30 +316,22 @@ class QuantMoEExperts(nn.Module):
         top_k = top_k or self.top_k
         if self[0].layers()[0].qweight.device.type != "cuda":
             return {"path": "per_expert", "reason": "cpu tensors"}
-        if self._moe is None:
-            self.post_init(self._decode_copy, self._batch, self._backward, self._low_bit, self._prefill, self._low_bit_decode)
+        self._ensure_init()
         dmax = min(4, int(self.low_bit_decode_max_tokens)) if self.bits in (2, 3) else 4
         key = (T, top_k, self.batch_max_tokens, dmax)
         d = self._plans.get(key)
         if d is None:
-            if self._decode_table is not None and 0 < T <= dmax:
-                d = _lib.describe_moe_decode_plan(self._moe, T, top_k)
-                if d["path"] != "decode":
-                    d = None
-            if d is None and self._batch_ok and self._decode_table is not None and 4 < T <= min(64, self.batch_max_tokens):
-                d = _lib.describe_moe_batch_plan(self._moe, T, top_k)
-                if d["path"] != "batch":
-                    d = None
-            if d is None and self._prefill_ok and self._decode_table is not None and T > 64:
-                d = _lib.describe_moe_prefill_plan(self._moe, T, top_k)
-                if d["path"] != "prefill":                       # (more than 65535 routed rows: the grouped path)
-                    d = None
+            copy = self._decode_table is not None
+            for path, asked in (("decode", copy and 0 < T <= dmax),
+                                ("batch", copy and self._batch_ok and 4 < T <= min(64, self.batch_max_tokens)),
+                                ("prefill", copy and self._prefill_ok and T > 64)):      # (prefill declines more than 65535 routed rows: the grouped path)
+                if asked and d is None:
+                    d = _PATHS[path].describe(self._moe, T, top_k)
+                    if d["path"] != path:
+                        d = None
             if d is None:
-                d = _lib.describe_moe_plan(self._moe, T, top_k)
-            d.setdefault("reason", "")
-            if isinstance(d["reason"], str):
-                d["reason"] = d["reason"].replace("_", " ")
-            self._plans[key] = d
+                d = _PATHS["grouped"].describe(self._moe, T, top_k)
+            self._plans[key] = _clean_reason(d)
         return dict(d)
 
     def forward(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor) -> torch.Tensor:
@@ -361,26 +363,15 @@ def moe_forward(experts: QuantMoEExperts, x: torch.Tensor, top_k_index: torch.Te
     else:
         experts.last_plan = experts.plan(T, topk)
     path = experts.last_plan["path"]
-    if path not in ("grouped", "decode", "batch", "prefill"):
+    if path not in _PATHS:
         if return_intermediate:
             raise RuntimeError(f"moe_forward: return_intermediate needs the grouped, the batch, the prefill or the decode path ({experts.last_plan['reason']})")
         return _per_expert(experts, x2, top_k_index.reshape(T, topk), top_k_weights.reshape(T, topk)).reshape(lead + (H,))
     dev, w_dtype = experts._dev, experts._w_dtype
     if x.device != dev:
         raise RuntimeError(f"mi355x moe_forward: input is on {x.device}, the experts on {dev}")
-    xw = x2.to(w_dtype) if x2.dtype != w_dtype else x2
-    if not xw.is_contiguous():
-        xw = xw.contiguous()
-    if xw.data_ptr() & 15:                # a contiguous view at an odd element offset: the C ABI takes 16-byte aligned x
-        xw = xw.clone()
-    idx = top_k_index.reshape(T, topk)
-    if idx.dtype != torch.int64:
-        idx = idx.to(torch.int64)
-    idx = idx.contiguous()
-    w = top_k_weights.reshape(T, topk)
-    if w.dtype != torch.float32:
-        w = w.to(torch.float32)
-    w = w.contiguous()
+    xw = _aligned(x2, w_dtype)
+    idx, w = _routing(top_k_index, top_k_weights, T, topk)
     out = torch.empty((T, H), dtype=w_dtype, device=dev)
     h_out = None
     if return_intermediate:
@@ -395,17 +386,9 @@ def moe_forward(experts: QuantMoEExperts, x: torch.Tensor, top_k_index: torch.Te
         exchange_tick(dev)
         idx_dev = experts._dev.index
         with torch.cuda.device(idx_dev):
-            lib = _lib.load()
-            if path == "decode":
-                fn, table = lib.gptq_moe_decode_forward, experts._decode_table
-            elif path == "batch":
-                fn, table = lib.gptq_moe_batch_forward, experts._decode_table
-            elif path == "prefill":
-                fn, table = lib.gptq_moe_prefill_forward, experts._decode_table
-            else:
-                fn, table = lib.gptq_moe_forward, experts._table
-            rc = fn(ctypes.byref(experts._moe), table.data_ptr(), xw.data_ptr(), idx.data_ptr(), w.data_ptr(), T, topk,
-                    out.data_ptr(), _lib.ptr(h_out), buf.data_ptr(), buf.numel(), _raw_stream(idx_dev))
+            entry = _PATHS[path]
+            rc = getattr(_lib.load(), entry.forward)(ctypes.byref(experts._moe), getattr(experts, entry.table).data_ptr(), xw.data_ptr(), idx.data_ptr(),
+                                                     w.data_ptr(), T, topk, out.data_ptr(), _lib.ptr(h_out), buf.data_ptr(), buf.numel(), _raw_stream(idx_dev))
         if rc:
             _lib.check(rc)
     res = out.to(x.dtype) if x.dtype != w_dtype else out
@@ -421,8 +404,7 @@ def moe_forward(experts: QuantMoEExperts, x: torch.Tensor, top_k_index: torch.Te
 
 def _grouped_backward_ready(experts: QuantMoEExperts) -> bool:
     """The experts were post-initialised with backward=True and the backward plan took them (post_init runs here when the tables were invalidated)."""
-    if experts._moe is None:
-        experts.post_init(experts._decode_copy, experts._batch, experts._backward, experts._low_bit, experts._prefill, experts._low_bit_decode)
+    experts._ensure_init()
     return experts._grad_table is not None
 
 
@@ -432,9 +414,20 @@ def _aligned(t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
         t = t.to(dtype)
     if not t.is_contiguous():
         t = t.contiguous()
-    if t.data_ptr() & 15:
+    if t.data_ptr() & 15:                 # a contiguous view at an odd element offset
         t = t.clone()
     return t
+
+
+def _routing(top_k_index: torch.Tensor, top_k_weights: torch.Tensor, T: int, topk: int):
+    """(top_k_index, top_k_weights) as the contiguous int64 / fp32 [T, topk] pair the C ABI reads."""
+    idx = top_k_index.reshape(T, topk)
+    if idx.dtype != torch.int64:
+        idx = idx.to(torch.int64)
+    w = top_k_weights.reshape(T, topk)
+    if w.dtype != torch.float32:
+        w = w.to(torch.float32)
+    return idx.contiguous(), w.contiguous()
 
 
 class _MoEBackward(torch.autograd.Function):
@@ -464,8 +457,7 @@ class _MoEBackward(torch.autograd.Function):
         T = x2.shape[0]
         topk = top_k_index.shape[-1] if top_k_index.dim() else 1
         dout = _aligned(grad_out.reshape(-1, H), w_dtype)
-        idx = top_k_index.reshape(T, topk).to(torch.int64).contiguous()
-        w = top_k_weights.reshape(T, topk).to(torch.float32).contiguous()
+        idx, w = _routing(top_k_index, top_k_weights, T, topk)
         dx = torch.empty((T, H), dtype=w_dtype, device=dev) if want_x else None
         dw = torch.empty((T, topk), dtype=torch.float32, device=dev) if want_w else None
         if T and (want_x or want_w):
@@ -517,9 +509,7 @@ def router_plan(T: int, H: int, E: int, top_k: int, dtype: torch.dtype, renorm: 
         if enum is None:
             d = {"path": "none", "reason": f"dtype {dtype}: the router kernel takes fp16 / bf16"}
         else:
-            d = _lib.describe_moe_router_plan(T, H, E, top_k, enum, _lib.ROUTER_RENORM if renorm else 0)
-            d.setdefault("reason", "")
-            d["reason"] = str(d["reason"]).replace("_", " ")
+            d = _clean_reason(_lib.describe_moe_router_plan(T, H, E, top_k, enum, _lib.ROUTER_RENORM if renorm else 0))
         _ROUTER_PLANS[key] = d
     return dict(d)
 
@@ -591,9 +581,7 @@ def router_grouped_plan(T: int, H: int, E: int, top_k: int, n_group: int, topk_g
         if enum is None:
             d = {"path": "none", "reason": f"dtype {dtype}: the router kernel takes fp16 / bf16"}
         else:
-            d = _lib.describe_moe_router_grouped_plan(T, H, E, top_k, n_group, topk_group, enum, _lib.ROUTER_RENORM if renorm else 0)
-            d.setdefault("reason", "")
-            d["reason"] = str(d["reason"]).replace("_", " ")
+            d = _clean_reason(_lib.describe_moe_router_grouped_plan(T, H, E, top_k, n_group, topk_group, enum, _lib.ROUTER_RENORM if renorm else 0))
             slow = GROUPED_SLOW_TILES
             if slow is not None and d["path"] == "router_grouped" and d["form"] == "tiles" and E * H >= slow[0] and T <= slow[1]:
                 d = {"path": "none", "reason": f"the tiles form was measured slower than the composition at 9..{slow[1]} tokens with E * H >= {slow[0]}"}
@@ -777,10 +765,7 @@ def shared_plan(experts: QuantMoEExperts, shared_layers, T: int, top_k: "int | N
     d = experts._plans.get(key + (T, top_k))
     if d is None:
         sh.gate_w = None
-        d = _lib.describe_moe_shared_decode_plan(experts._moe, sh, T, top_k)
-        d.setdefault("reason", "")
-        d["reason"] = str(d["reason"]).replace("_", " ")
-        experts._plans[key + (T, top_k)] = d
+        d = experts._plans[key + (T, top_k)] = _clean_reason(_lib.describe_moe_shared_decode_plan(experts._moe, sh, T, top_k))
     return dict(d)
 
 
@@ -862,14 +847,7 @@ def moe_shared_forward(experts: QuantMoEExperts, shared_layers, gate_weight: "to
     dev = experts._dev
     if x.device != dev:
         raise RuntimeError(f"mi355x moe_shared_forward: input is on {x.device}, the experts on {dev}")
-    idx = top_k_index.reshape(T, topk)
-    if idx.dtype != torch.int64:
-        idx = idx.to(torch.int64)
-    idx = idx.contiguous()
-    w = top_k_weights.reshape(T, topk)
-    if w.dtype != torch.float32:
-        w = w.to(torch.float32)
-    w = w.contiguous()
+    idx, w = _routing(top_k_index, top_k_weights, T, topk)
     sh, key = _shared_state(experts, shared_layers)
     out = torch.empty((T, H), dtype=w_dtype, device=dev)
     R, I, Is = T * topk, experts.intermediate_dim, gate.outfeatures

@@ -1631,9 +1631,11 @@ __global__ void __launch_bounds__(256) gemm_reduce_kernel(const float* __restric
 // from global memory costs the texture path one address per cycle, so the rows are staged in LDS (coalesced 16-byte loads) and gathered there.
 // Round 4: R rows per workgroup share ONE read of perm[] (16 KiB for K = 4096 -- twice a row of x: with one row per workgroup the index loads were
 // two thirds of the request traffic; 11.7 us = 2.9 TB/s for the 33.5 MB of a 2048 x 4096 x) and the indices stay in registers across the R rows.
-template <bool SLOT, int R>
+// (slot is a run-time, launch-uniform argument: it only chooses which two of a piece's eight indices share an output word, so the indices are put in
+// output order once per piece -- eight selects on a scalar condition -- and one body serves both orders: R instantiations, not 2 R)
+template <int R>
 __global__ void __launch_bounds__(256) permute_rows_kernel(const unsigned short* __restrict__ x, const int* __restrict__ perm,
-                                                           int M, int K, unsigned short* __restrict__ out) {
+                                                           int M, int K, unsigned short* __restrict__ out, int slot) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     unsigned short* rows = (unsigned short*)smem;              // [R][K]
     const int m0 = blockIdx.x * R;
@@ -1645,22 +1647,16 @@ __global__ void __launch_bounds__(256) permute_rows_kernel(const unsigned short*
     __syncthreads();
     for (int i = threadIdx.x * 8; i < K; i += 256 * 8) {
         const u32x4 p0 = *(const u32x4*)(perm + i), p1 = *(const u32x4*)(perm + i + 4);
+        // output word w = (lo[w], hi[w]): slot order (k0, k4) (k1, k5) (k2, k6) (k3, k7), natural order (k0, k1) (k2, k3) (k4, k5) (k6, k7)
+        const u32x4 lo = slot ? p0 : u32x4{p0[0], p0[2], p1[0], p1[2]};
+        const u32x4 hi = slot ? p1 : u32x4{p0[1], p0[3], p1[1], p1[3]};
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             if (m0 + r >= M) break;
             const unsigned short* row = rows + (size_t)r * K;
             u32x4 o;
-            if constexpr (SLOT) {
-                o[0] = (unsigned)row[p0[0]] | ((unsigned)row[p1[0]] << 16);
-                o[1] = (unsigned)row[p0[1]] | ((unsigned)row[p1[1]] << 16);
-                o[2] = (unsigned)row[p0[2]] | ((unsigned)row[p1[2]] << 16);
-                o[3] = (unsigned)row[p0[3]] | ((unsigned)row[p1[3]] << 16);
-            } else {
-                o[0] = (unsigned)row[p0[0]] | ((unsigned)row[p0[1]] << 16);
-                o[1] = (unsigned)row[p0[2]] | ((unsigned)row[p0[3]] << 16);
-                o[2] = (unsigned)row[p1[0]] | ((unsigned)row[p1[1]] << 16);
-                o[3] = (unsigned)row[p1[2]] | ((unsigned)row[p1[3]] << 16);
-            }
+#pragma unroll
+            for (int w = 0; w < 4; ++w) o[w] = (unsigned)row[lo[w]] | ((unsigned)row[hi[w]] << 16);
             __builtin_nontemporal_store(o, (u32x4*)(out + (size_t)(m0 + r) * K + i));
         }
     }
@@ -1670,9 +1666,9 @@ __global__ void __launch_bounds__(256) permute_rows_kernel(const unsigned short*
 // value of all four rows -- 8 LDS reads + 16 v_perm per four 16-byte outputs where the row-major form above takes 32 ds_read_u16 + 32 address adds + 16
 // packs (tools/isa: ~88 -> ~32 instructions per four outputs; the kernel is bound by its instruction stream, not by the 33.5 MB it moves).  The load phase
 // transposes 4 rows x 8 k in registers (16 v_perm) and writes 64 contiguous bytes.  LDS: 8 K bytes (88 KiB at K = 11008: granted by init_gemm_device).
-template <bool SLOT>
+// (slot: a run-time, launch-uniform argument as in permute_rows_kernel -- the eight indices go into output order before the LDS reads: one instantiation)
 __global__ void __launch_bounds__(256) permute_rows4_kernel(const unsigned short* __restrict__ x, const int* __restrict__ perm, int M, int K,
-                                                            unsigned short* __restrict__ out) {
+                                                            unsigned short* __restrict__ out, int slot) {
     extern __shared__ __attribute__((aligned(16))) char smem[];                // [K][4] values
     const int m0 = blockIdx.x * 4;
     const unsigned short* xr[4];
@@ -1696,22 +1692,20 @@ __global__ void __launch_bounds__(256) permute_rows4_kernel(const unsigned short
     __syncthreads();
     for (int i = threadIdx.x * 8; i < K; i += 256 * 8) {
         const u32x4 p0 = *(const u32x4*)(perm + i), p1 = *(const u32x4*)(perm + i + 4);
-        u32x2 g[8];                                                             // g[j] = the four rows' values at source index j of this piece
+        // output word w = (lo[w], hi[w]): (k0, k4) (k1, k5) (k2, k6) (k3, k7), the slot order of the B fragments, or the natural (k0, k1) (k2, k3) ...
+        const u32x4 lo = slot ? p0 : u32x4{p0[0], p0[2], p1[0], p1[2]};
+        const u32x4 hi = slot ? p1 : u32x4{p0[1], p0[3], p1[1], p1[3]};
+        u32x2 gl[4], gh[4];                                                     // the four rows' values at the source indices of word w's halves
 #pragma unroll
-        for (int j = 0; j < 4; ++j) { g[j] = *(const u32x2*)(smem + (size_t)p0[j] * 8); g[4 + j] = *(const u32x2*)(smem + (size_t)p1[j] * 8); }
+        for (int w = 0; w < 4; ++w) { gl[w] = *(const u32x2*)(smem + (size_t)lo[w] * 8); gh[w] = *(const u32x2*)(smem + (size_t)hi[w] * 8); }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             if (m0 + r >= M) break;
             const unsigned sel = (r & 1) ? 0x07060302u : 0x05040100u;
             const int h = r >> 1;
             u32x4 o;
-            if constexpr (SLOT) {                                                // (k0, k4) (k1, k5) (k2, k6) (k3, k7): the slot order of the B fragments
 #pragma unroll
-                for (int w = 0; w < 4; ++w) o[w] = __builtin_amdgcn_perm(g[4 + w][h], g[w][h], sel);
-            } else {
-#pragma unroll
-                for (int w = 0; w < 4; ++w) o[w] = __builtin_amdgcn_perm(g[2 * w + 1][h], g[2 * w][h], sel);
-            }
+            for (int w = 0; w < 4; ++w) o[w] = __builtin_amdgcn_perm(gh[w][h], gl[w][h], sel);
             // plain stores: the GEMM behind this pass reads the permuted x at once -- written around the caches (nontemporal, round 4) the 45 MB of a K = 11008
             // call came back from HBM and cost the stream-K prefill kernel 7 us per layer call (profiles/r05_wide_sk_ab_v4.log); the pass itself is no slower
             *(u32x4*)(out + (size_t)(m0 + r) * K + i) = o;
@@ -1719,10 +1713,9 @@ __global__ void __launch_bounds__(256) permute_rows4_kernel(const unsigned short
     }
 }
 
-template <bool SLOT>
-static void launch_permute_rows_r(const unsigned short* x, const int* perm, int M, int K, unsigned short* out, hipStream_t st) {
+static void launch_permute_rows_r(const unsigned short* x, const int* perm, int M, int K, unsigned short* out, hipStream_t st, int slot) {
     if (M >= 1024 && (size_t)K * 8 <= 160 * 1024 && K % 8 == 0) {                // prefill rows: the interleaved four-row form
-        hipLaunchKernelGGL((permute_rows4_kernel<SLOT>), dim3((M + 3) / 4), dim3(256), (size_t)K * 8, st, x, perm, M, K, out);
+        hipLaunchKernelGGL(permute_rows4_kernel, dim3((M + 3) / 4), dim3(256), (size_t)K * 8, st, x, perm, M, K, out, slot);
         return;
     }
     // rows per workgroup: as many as keep >= 512 workgroups in the launch and <= 64 KiB of LDS (the default dynamic-LDS limit: no per-function grant needed)
@@ -1730,14 +1723,13 @@ static void launch_permute_rows_r(const unsigned short* x, const int* perm, int 
     while (r < 4 && (size_t)(2 * r) * K * 2 <= 64 * 1024 && M / (2 * r) >= 512) r *= 2;
     const int blocks = (M + r - 1) / r;
     const size_t lds = (size_t)r * K * 2;
-    if (r == 4) hipLaunchKernelGGL((permute_rows_kernel<SLOT, 4>), dim3(blocks), dim3(256), lds, st, x, perm, M, K, out);
-    else if (r == 2) hipLaunchKernelGGL((permute_rows_kernel<SLOT, 2>), dim3(blocks), dim3(256), lds, st, x, perm, M, K, out);
-    else hipLaunchKernelGGL((permute_rows_kernel<SLOT, 1>), dim3(blocks), dim3(256), lds, st, x, perm, M, K, out);
+    if (r == 4) hipLaunchKernelGGL((permute_rows_kernel<4>), dim3(blocks), dim3(256), lds, st, x, perm, M, K, out, slot);
+    else if (r == 2) hipLaunchKernelGGL((permute_rows_kernel<2>), dim3(blocks), dim3(256), lds, st, x, perm, M, K, out, slot);
+    else hipLaunchKernelGGL((permute_rows_kernel<1>), dim3(blocks), dim3(256), lds, st, x, perm, M, K, out, slot);
 }
 
 hipError_t launch_permute_rows16(const void* x, const int32_t* perm, int M, int K, void* x_out, hipStream_t st, bool slot_order) {
-    if (slot_order) launch_permute_rows_r<true>((const unsigned short*)x, perm, M, K, (unsigned short*)x_out, st);
-    else launch_permute_rows_r<false>((const unsigned short*)x, perm, M, K, (unsigned short*)x_out, st);
+    launch_permute_rows_r((const unsigned short*)x, perm, M, K, (unsigned short*)x_out, st, slot_order ? 1 : 0);
     return hipGetLastError();
 }
 
@@ -1769,8 +1761,7 @@ template <typename T> static hipError_t grant_stream64_t() {
 
 hipError_t init_gemm_device() {
     hipError_t e = grant_lds<4, f16, 4, 64, 1, true, true, 2>();
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)permute_rows4_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)permute_rows4_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)permute_rows4_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e == hipSuccess) e = grant_lds<4, f16, 4, 64, 1, false, false, 2>();
     if (e == hipSuccess) e = grant_lds<4, bf16, 4, 64, 1, false, false, 2>();
 #ifdef GPTQ_GEMM_ABLATIONS

@@ -23,6 +23,15 @@
 // (the fp32 sum of a row does not depend on which other rows share its tile: the MFMA rows are independent).
 // The pair / down form, the group mode and the number of staged planes are run-time uniform: T x BITS = four instantiations.
 //
+// 2- AND 3-BIT EXPERTS (opt-in: GPTQ_MOE_LOW_BIT_BATCH in gptq_moe_t.flags): moe_rows_lowbit_kernel<T, 2 | 3>, the same body (moe_rows_body.inc, included
+// into both kernel templates) with three template constants: the strip-chunk of the copy is 768 / 512 bytes instead of 1024, a lane's share 12 / 8 bytes
+// instead of 16, fetched by ONE global_load_dwordx3 / dwordx2 into a ring element of that size, and dequantised in place by rowsk::Deq1_3::frag(words, ks) /
+// rowsk::Deq1_2::frag(word[ks >> 1] >> 8 (ks & 1)) -- MFMA step ks gets the lane's k = 8 ks .. 8 ks + 7 in the order the A operand has them, as at 4 bits.
+// The constant record (48 bytes, one-byte zero-point), the group offsets, the x side, the ring depth, the loads per chunk (3 NS: the vmcnt counts) and the
+// reduction are the 4-bit form's.  Four more instantiations under a name of their own, so that "moe_rows_kernel" keeps meaning the 4- / 8-bit forms, whose
+// code objects are instruction for instruction what they were.  Registers (read off the code object): 124 (fp16) / 125 (bf16) VGPRs at both widths, no
+// scratch, no spill: the 4-bit form's 128-register compilation, two workgroups per CU.
+//
 // ACT-ORDER experts (the copy is made of the re-sequenced rows): one small untyped 2-byte gather pre-pass, moe_gather_rows_kernel,
 // rows_out[r][i] = rows_in[src(r)][perm_e(r)[i]], runs before the pair stage (x through W1_e's perm into plane 0 and through W3_e's perm into plane 1 -- gate
 // and up of an expert may have different activation orders; the pair form then stages BOTH planes, W1's strips multiply plane 0 and W3's plane 1) and again
@@ -71,204 +80,23 @@ struct Args {
     void* out;                                  // pair: H_sorted [R][N] (T); down: Y [R][N] fp32
 };
 
-// 4 bits: compiled for 128 registers (two 8-wave workgroups per CU); 8 bits: a ring slot is twice as large -- 256 registers, one workgroup per CU
+// 2 / 3 bits (opt-in: GPTQ_MOE_LOW_BIT_BATCH): the copy of utils.hip prepack_decode_weights_kernel read in place -- Deq1_3::frag(words, ks) as the dense rows
+// kernel does, Deq1_2::frag(word[ks >> 1] >> 8 (ks & 1)): pair p = (k 16 w + 2 p, + 1) sits at bit 2 p of the halves of word w, so fields 0..3 of the
+// (shifted) word are k = 8 ks .. 8 ks + 7 of the lane's 32 in the order the A operand has them
+template <typename T, int BITS> struct DeqOf { typedef typename rowsk::DeqSel<T, BITS>::type type; };
+template <typename T> struct DeqOf<T, 2> { typedef rowsk::Deq1_2<T> type; };
+
+// 2 / 3 / 4 bits: compiled for 128 registers (two 8-wave workgroups per CU); 8 bits: a ring slot is twice as large -- 256 registers, one workgroup per CU
 template <typename T, int BITS>
 __global__ void __launch_bounds__(BITS == 8 ? 512 : 1024) moe_rows_kernel(Args p) {
-    constexpr int NH = BITS == 8 ? 2 : 1;                      // chunks of the copy per 128-deep chunk of the rows
-    constexpr unsigned REC = BITS == 8 ? 64u : 48u, WCH = 1024u;
-    constexpr int NDMA = 4, NW = 3 * NH * NS;                  // DMA instructions of one plane of a chunk; a chunk's weight + constant loads
-    constexpr int DW = 2;                                      // ring of chunks in flight per wave (4 bits: 48 registers, 8 bits: 96)
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = blockDim.x >> 6;
-    const int sgi = blockIdx.x % p.nsg, tile = blockIdx.x / p.nsg;
-    if (tile >= *p.tile_count) return;
-    const int4 tl = p.tiles[tile];
-    const int e = __builtin_amdgcn_readfirstlane(tl.x), row0 = __builtin_amdgcn_readfirstlane(tl.y), rows = __builtin_amdgcn_readfirstlane(tl.z);
-    const int S = p.pair ? NS / 2 : NS, s0 = sgi * S;
-    const int planes = p.planes;
-    const int r = lane & 15, g = lane >> 4;
-
-    const Entry e0 = load_entry(p.table + e);
-    const Entry e1 = p.pair ? load_entry(p.table + p.E + e) : e0;
-    const char* wb[NS];
-    const char* cb[NS];
-#pragma unroll
-    for (int v = 0; v < NS; ++v) {
-        const bool up = p.pair && v >= NS / 2;
-        const int strip = s0 + (up ? v - NS / 2 : v);
-        wb[v] = (const char*)(up ? e1.tq : e0.tq) + (size_t)strip * (size_t)(p.chunks * NH) * WCH;
-        cb[v] = (const char*)(up ? e1.cst : e0.cst) + (size_t)strip * (size_t)p.groups * REC;
-    }
-
-    char* const xbuf = smem + (size_t)wave * 2 * planes * XB;      // buffer b, plane q: xbuf + (b planes + q) XB
-    const unsigned xbuf_lds = lds_addr_of(xbuf);
-    // DMA i of a plane (4 rows x 256 bytes): lane (rr = lane >> 4, slot = lane & 15) fetches piece slot ^ (row & 15) of row 4 i + rr, so that LDS slot s of row R
-    // holds piece s ^ (R & 15) (gemm_rows_kernel.cuh); the row itself is looked up here
-    unsigned xoff[NDMA];
-#pragma unroll
-    for (int i = 0; i < NDMA; ++i) {
-        const int row = 4 * i + g;
-        const int sr = row0 + min(row, rows - 1);              // rows past the tile repeat its last one (their outputs are not stored)
-        const int m = p.row_assign ? p.row_assign[sr] / p.topk : sr;
-        xoff[i] = (unsigned)m * (unsigned)p.K * 2u + (unsigned)((r ^ (row & 15)) * 16);
-    }
-    unsigned aoff[4];
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        const int piece = BITS == 8 ? 8 * (w >> 1) + 2 * g + (w & 1) : 4 * g + w;
-        aoff[w] = (unsigned)(r * 256 + ((piece ^ r) * 16));
-    }
-    const unsigned a3off = planes > 1 ? (unsigned)XB : 0u;     // W3's strips read plane 1 when there is one
-    const unsigned wlane = (unsigned)lane * 16u;
-    const int gm = p.gm;
-    const unsigned glane = BITS == 8 ? (gm == 2 ? (unsigned)(g >> 1) * REC : 0u) : (gm == 2 ? (unsigned)g * REC : (gm == 1 ? (unsigned)(g >> 1) * REC : 0u));
-    const unsigned slane = glane + (unsigned)r * 2u, zlane = glane + 32u + (unsigned)r * (BITS == 8 ? 2u : 1u);
-    const int c0 = wave * p.cpw, c1 = min(c0 + p.cpw, p.chunks);
-
-    struct Buf { u32x4 wq[NS][NH]; unsigned cs[NS][NH], cz[NS][NH]; };
-    Buf q[DW];
-    // every register of the ring starts as its own opaque definition: the compiler cannot share one between two loads' destinations and split them with a
-    // copy behind the first load
-#pragma unroll
-    for (int j = 0; j < DW; ++j)
-#pragma unroll
-        for (int v = 0; v < NS; ++v)
-#pragma unroll
-            for (int h = 0; h < NH; ++h) {
-                asm volatile("; ring slot" : "=v"(q[j].wq[v][h]));
-                asm volatile("v_mov_b32 %0, 0" : "=v"(q[j].cs[v][h]));
-                asm volatile("v_mov_b32 %0, 0" : "=v"(q[j].cz[v][h]));
-            }
-    auto issue_w = [&](int c, Buf& B) __attribute__((always_inline)) {
-#pragma unroll
-        for (int v = 0; v < NS; ++v) {
-            const char* const wv = wb[v];
-            const char* const cv = cb[v];
-#pragma unroll
-            for (int h = 0; h < NH; ++h) {
-                const char* wsrc = wv + (size_t)(c * NH + h) * WCH;
-                const int grp = gm == 0 ? min(c >> p.gshift, p.groups - 1) : (BITS == 8 ? (gm == 1 ? 2 * c + h : 4 * c + 2 * h) : (gm == 1 ? 2 * c : 4 * c));
-                const char* csrc = cv + (size_t)grp * REC;
-                asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(B.wq[v][h]) : "v"(wlane), "s"(wsrc) : "memory");
-                asm volatile("global_load_ushort %0, %1, %2" : "=v"(B.cs[v][h]) : "v"(slane), "s"(csrc) : "memory");
-                if constexpr (BITS == 8) asm volatile("global_load_ushort %0, %1, %2" : "=v"(B.cz[v][h]) : "v"(zlane), "s"(csrc) : "memory");
-                else asm volatile("global_load_ubyte %0, %1, %2" : "=v"(B.cz[v][h]) : "v"(zlane), "s"(csrc) : "memory");
-            }
-        }
-    };
-    // DMAs [i0, i1) of chunk c's rows (every plane) into buffer b
-    auto issue_x = [&](int c, int b, int i0, int i1) __attribute__((always_inline)) {
-        const char* xsrc = (const char*)p.a + (size_t)c * 256;
-        const unsigned l0 = __builtin_amdgcn_readfirstlane(xbuf_lds + (unsigned)(b * planes * XB));
-#pragma unroll
-        for (int i = i0; i < i1; ++i) {
-            const unsigned xo = xoff[i];
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(l0 + (unsigned)(i * 1024)), "v"(xo), "s"(xsrc) : "memory");
-            if (planes > 1) {
-                const char* xsrc1 = xsrc + p.plane_bytes;
-                asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(l0 + (unsigned)(XB + i * 1024)), "v"(xo), "s"(xsrc1) : "memory");
-            }
-        }
-    };
-    // the registers pass through a statement behind the wait so that no use of them is scheduled in front of it
-    auto claim = [&](Buf& B) __attribute__((always_inline)) {
-#pragma unroll
-        for (int v = 0; v < NS; ++v)
-#pragma unroll
-            for (int h = 0; h < NH; ++h) asm volatile("" : "+v"(B.wq[v][h]), "+v"(B.cs[v][h]), "+v"(B.cz[v][h])::"memory");
-    };
-
-    f32x4 acc[NS];
-#pragma unroll
-    for (int v = 0; v < NS; ++v) acc[v] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // chunk in buffer b; the NEXT chunk's DMAs (cn, into the other buffer) are issued a quarter at a time behind the MFMAs of each step (gemm_rows_kernel.cuh)
-    auto compute = [&](const Buf& B, int b, int cn, bool has_x) __attribute__((always_inline)) {
-        typename rowsk::DeqSel<T, BITS>::type dq[NS][NH];
-#pragma unroll
-        for (int v = 0; v < NS; ++v)
-#pragma unroll
-            for (int h = 0; h < NH; ++h) dq[v][h].setup(B.cs[v][h], B.cz[v][h]);
-        const char* xb = xbuf + b * planes * XB;
-        u32x4 a1[4], a3[4];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            a1[w] = *(const u32x4*)(xb + aoff[w]);
-            a3[w] = *(const u32x4*)(xb + a3off + aoff[w]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-#pragma unroll
-            for (int v = 0; v < NS; ++v) {
-                u32x4 bq;
-                if constexpr (BITS == 4) bq = dq[v][0].frag(B.wq[v][0][w]);
-                else bq = dq[v][w >> 1].frag(B.wq[v][w >> 1][2 * (w & 1)], B.wq[v][w >> 1][2 * (w & 1) + 1]);
-                acc[v] = rowsk::Mma16<T>::run(v < NS / 2 ? a1[w] : a3[w], bq, acc[v]);
-            }
-            if (has_x) issue_x(cn, b ^ 1, w, w + 1);
-        }
-    };
-
-    if (c0 < c1) {
-#pragma unroll
-        for (int j = 0; j < DW; ++j)
-            if (c0 + j < c1) issue_w(c0 + j, q[j]);
-        issue_x(c0, 0, 0, NDMA);
-        for (int cbase = c0; cbase < c1; cbase += DW) {
-#pragma unroll
-            for (int j = 0; j < DW; ++j) {
-                const int c = cbase + j;
-                if (c >= c1) break;
-                // VMEM queue, oldest first: W(c0 .. c0 + DW - 1), x(c0) | x(c0 + 1) under the MFMAs of c0, W(c0 + DW) | x(c0 + 2), W(c0 + DW + 1) | ...
-                // chunk c needs x(c) and everything older (W(c) is); behind x(c) there is only W(c + DW - 1), issued at the end of the previous iteration
-                const bool has_w = c > c0 && c + DW - 1 < c1;
-                if (has_w) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NW) : "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                claim(q[j]);
-                compute(q[j], j & 1, c + 1, c + 1 < c1);
-                if (c + DW < c1) issue_w(c + DW, q[j]);
-            }
-        }
-    }
-    // every destination register of the ring passes through a statement behind a full wait: nothing is in flight into a register the epilogue reuses
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int j = 0; j < DW; ++j) claim(q[j]);
-
-    // ---- the waves' sums meet in LDS (wave order), epilogue, store ------------------------------------------------------------------------------
-    __syncthreads();                                           // every wave is done with its x buffers
-    float* const red = (float*)smem;                           // [wave][v][lane] float4
-#pragma unroll
-    for (int v = 0; v < NS; ++v) *(f32x4*)(red + ((size_t)(wave * NS + v) * 64 + lane) * 4) = acc[v];
-    __syncthreads();
-    auto wsum = [&](int v, int l) -> f32x4 {
-        f32x4 s = *(const f32x4*)(red + ((size_t)v * 64 + l) * 4);
-        for (int w = 1; w < nw; ++w) s += *(const f32x4*)(red + ((size_t)(w * NS + v) * 64 + l) * 4);
-        return s;
-    };
-    const int N = p.N;
-    for (int item = tid; item < S * 64; item += (int)blockDim.x) {
-        const int l = item & 63, v = item >> 6;
-        const int n = (s0 + v) * 16 + (l & 15);
-        const f32x4 sg = wsum(v, l);
-        if (p.pair) {
-            const f32x4 su = wsum(v + NS / 2, l);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {                      // C/D layout of the 16x16 MFMA: row = 4 (lane >> 4) + i, column = lane & 15
-                const int row = 4 * (l >> 4) + i;
-                const float gv = sg[i];
-                if (row < rows) ((T*)p.out)[(size_t)(row0 + row) * N + n] = DType<T>::from_f32(gv / (1.f + __expf(-gv)) * su[i]);
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int row = 4 * (l >> 4) + i;
-                if (row < rows) ((float*)p.out)[(size_t)(row0 + row) * N + n] = sg[i];
-            }
-        }
-    }
+    static_assert(BITS == 4 || BITS == 8, "2 and 3 bits: moe_rows_lowbit_kernel");
+#include "moe_rows_body.inc"
+}
+// the opt-in widths under a name of their own: what counts or lints "moe_rows_kernel" keeps meaning the 4- and 8-bit forms
+template <typename T, int BITS>
+__global__ void __launch_bounds__(1024) moe_rows_lowbit_kernel(Args p) {
+    static_assert(BITS == 2 || BITS == 3, "4 and 8 bits: moe_rows_kernel");
+#include "moe_rows_body.inc"
 }
 
 // act-order pre-pass, untyped 2-byte elements: out[plane][r][i] = in[src(r)][perm[i]], perm = that of expert e(r)'s entry of projection (first + plane);
@@ -307,14 +135,22 @@ __global__ void __launch_bounds__(256) moe_gather_rows_kernel(GatherArgs p) {
 
 template <typename T, int BITS>
 static hipError_t launch_one(const Args& a, long blocks, int waves, int lds, hipStream_t st) {
-    hipLaunchKernelGGL((moe_rows_kernel<T, BITS>), dim3((unsigned)blocks), dim3(waves * 64), lds, st, a);
+    if constexpr (BITS == 2 || BITS == 3) hipLaunchKernelGGL((moe_rows_lowbit_kernel<T, BITS>), dim3((unsigned)blocks), dim3(waves * 64), lds, st, a);
+    else hipLaunchKernelGGL((moe_rows_kernel<T, BITS>), dim3((unsigned)blocks), dim3(waves * 64), lds, st, a);
     return hipGetLastError();
 }
 static hipError_t launch_any(int dtype, int bits, const Args& a, long blocks, int waves, int lds, hipStream_t st) {
     if (blocks <= 0) return hipSuccess;
     if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
-    if (dtype == GPTQ_F16) return bits == 4 ? launch_one<f16, 4>(a, blocks, waves, lds, st) : launch_one<f16, 8>(a, blocks, waves, lds, st);
-    return bits == 4 ? launch_one<bf16, 4>(a, blocks, waves, lds, st) : launch_one<bf16, 8>(a, blocks, waves, lds, st);
+    if (dtype != GPTQ_F16 && dtype != GPTQ_BF16) return hipErrorInvalidValue;
+    const bool h = dtype == GPTQ_F16;
+    switch (bits) {
+        case 2: return h ? launch_one<f16, 2>(a, blocks, waves, lds, st) : launch_one<bf16, 2>(a, blocks, waves, lds, st);
+        case 3: return h ? launch_one<f16, 3>(a, blocks, waves, lds, st) : launch_one<bf16, 3>(a, blocks, waves, lds, st);
+        case 4: return h ? launch_one<f16, 4>(a, blocks, waves, lds, st) : launch_one<bf16, 4>(a, blocks, waves, lds, st);
+        case 8: return h ? launch_one<f16, 8>(a, blocks, waves, lds, st) : launch_one<bf16, 8>(a, blocks, waves, lds, st);
+    }
+    return hipErrorInvalidValue;                                // (the entry point's check lets no other width through)
 }
 
 static int group_mode(const gptq_layer_t& L) {                  // what the rows family takes: 0 = 128 2^n or one group, 1 = 64, 2 = 32
@@ -432,6 +268,8 @@ hipError_t init_moe_batch_device() {
     auto grant = [&](auto kern) { hipError_t r = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, moerows::MAX_LDS); if (e == hipSuccess) e = r; };
     grant(moerows::moe_rows_kernel<f16, 4>); grant(moerows::moe_rows_kernel<f16, 8>);
     grant(moerows::moe_rows_kernel<bf16, 4>); grant(moerows::moe_rows_kernel<bf16, 8>);
+    grant(moerows::moe_rows_lowbit_kernel<f16, 3>); grant(moerows::moe_rows_lowbit_kernel<f16, 2>);
+    grant(moerows::moe_rows_lowbit_kernel<bf16, 3>); grant(moerows::moe_rows_lowbit_kernel<bf16, 2>);
     return e;
 }
 

@@ -26,7 +26,8 @@
                         ``Glm4MoeMoE``s, on the instances.  Opt-in.
 * ``pack_moe_experts``  pack the dense 3-D expert parameters of a model (``quantizers`` keyed ``...mlp.experts.{e}.w1`` as ``pack_model`` takes)
 
-2- and 3-bit experts: ``post_init(low_bit=True)`` opens the grouped path to them, ``post_init(low_bit_decode=True)`` the decode path (1..4 tokens).
+2- and 3-bit experts: ``post_init(low_bit=True)`` opens the grouped path to them, ``post_init(low_bit_decode=True)`` the decode path (1..4 tokens),
+the attribute ``low_bit_batch = True`` (set before ``post_init``) the batch path (5..64 tokens).
 The per-expert composition serves what the grouped kernels do not take (2- / 3-bit experts unless ``post_init(low_bit=True)``, fp32 experts, odd group
 sizes, raw act-order), CPU tensors (which ``QuantLinear`` refuses), and -- by default -- calls under grad where ``hidden_states`` or ``top_k_weights`` require grad: training through the experts gets
 dX and the router-weight gradient from the existing backward of ``QuantLinear``.  After ``post_init(backward=True)`` such a call is ONE autograd node
@@ -107,7 +108,10 @@ class QuantMoEExperts(nn.Module):
         self._low_bit = False
         self._prefill = False
         self._low_bit_decode = False
+        self.low_bit_batch = False                  # the switch of the batch path for 2- / 3-bit experts: set before post_init (read there; see its docstring)
+        self._low_bit_batch = False                 # ... what post_init made of it
         self.batch_max_tokens = 64
+        self.low_bit_batch_max_tokens = 64          # 2- / 3-bit experts with low_bit_batch = True: the batch path for 5..this many tokens (the kernels take 64)
         self.low_bit_decode_max_tokens = 4          # 2- / 3-bit experts with low_bit_decode=True: the decode path up to this many tokens (the kernels take 4)
         for e in range(num_experts):
             self.add_module(str(e), _Expert(self.names, bits, group_size, hidden_dim, intermediate_dim, weight_dtype, zero_mode))
@@ -121,9 +125,11 @@ class QuantMoEExperts(nn.Module):
 
     def _invalidate(self):
         self._moe = None
+        self._moe_batch = None
         self._decode_table = None
         self._grad_table = None
         self._batch_ok = False
+        self._low_bit_batch_ok = False
         self._prefill_ok = False
         self.decode_copy_bytes = 0
         self._keep = ()
@@ -163,14 +169,25 @@ class QuantMoEExperts(nn.Module):
         flag.  ``low_bit_decode=True`` (opt-in as well; implies ``decode_copy=True`` for such experts): 2- and 3-bit experts get their decode copy and
         calls of 1..``low_bit_decode_max_tokens`` (4) tokens run the decode kernels (``plan(T)["path"] == "decode"``); more tokens run the grouped
         path with ``low_bit=True``, else the per-expert composition.  ``batch=True`` / ``prefill=True`` have no effect on such experts (logged, dropped);
-        the keyword changes nothing for 4- and 8-bit experts.  ``decode_copy_bytes`` reports what the copies hold.  A checkpoint-layout release does not apply to expert layers."""
+        the keyword changes nothing for 4- and 8-bit experts.  The attribute ``low_bit_batch = True``, set before this call (opt-in as well; an attribute like
+        ``batch_max_tokens``, so every later re-initialisation keeps it; builds the decode copy and its table for such experts if nothing else did):
+        calls of 5..min(64, ``low_bit_batch_max_tokens``) tokens on 2- and 3-bit experts run the batch kernels on the copy (``plan(T)["path"] == "batch"``, gptq_moe_batch_forward with GPTQ_MOE_LOW_BIT_BATCH); with ``low_bit_decode=True`` as well the decode path serves
+        1..4 tokens and the batch path 5..64; fewer or more tokens run the grouped path with ``low_bit=True``, else the per-expert composition.  Experts the
+        batch plan declines log the reason once and behave as without the flag; it has no effect on 4- and 8-bit experts (``batch=True`` is their
+        switch).  ``decode_copy_bytes`` reports what the copies hold.  A checkpoint-layout release does not apply to expert layers."""
         dev = self[0].layers()[0].qweight.device
         if dev.type != "cuda":
             raise RuntimeError(f"mi355x QuantMoEExperts.post_init needs the module on a ROCm GPU device (got {dev}); there is no CPU path.")
         want_decode, self._batch, self._backward, self._low_bit = bool(decode_copy), bool(batch), bool(backward), bool(low_bit)
         self._prefill, self._low_bit_decode = bool(prefill), bool(low_bit_decode)
+        self._low_bit_batch = bool(self.low_bit_batch) and self.bits in (2, 3)      # (no effect on 4- and 8-bit experts)
         if self._low_bit_decode and self.bits in (2, 3):
             want_decode = True
+        if self._low_bit_batch:
+            why = self._copy_path_declined("batch", 128, _BATCH_GROUPS, low_bit=True)
+            if why:
+                logger.warning("QuantMoEExperts.low_bit_batch = True has no effect for these experts (%s)", why)
+                self._low_bit_batch = self.low_bit_batch = False
         if self._prefill:
             why = self._prefill_declined()
             if why:
@@ -181,12 +198,12 @@ class QuantMoEExperts(nn.Module):
             if why:
                 logger.warning("QuantMoEExperts.post_init(batch=True) has no effect for these experts (%s)", why)
                 self._batch = False
-        self._decode_copy = want_decode or self._batch or self._prefill
+        self._decode_copy = want_decode or self._batch or self._prefill or self._low_bit_batch
         if self._decode_copy:
             why = self._decode_copy_declined()
             if why:                                          # known from the metadata: no copy is built for a set the decode plan would decline
                 logger.warning("QuantMoEExperts.post_init(decode_copy=True) has no effect for these experts (%s): no decode copy is built", why)
-                self._decode_copy = self._batch = self._prefill = False
+                self._decode_copy = self._batch = self._prefill = self._low_bit_batch = False
         extra = 0
         for e in range(self.num_experts):
             for l in self[e].layers():
@@ -200,12 +217,17 @@ class QuantMoEExperts(nn.Module):
         m.E = self.num_experts
         m.flags = (_lib.MOE_LOW_BIT if self._low_bit else 0) | (_lib.MOE_LOW_BIT_DECODE if self._low_bit_decode else 0)
         m.gate, m.up, m.down = (ctypes.addressof(a) for a in arrs)
+        mb = None
+        if self._low_bit_batch:          # the batch path's own struct over the same layer arrays: the grouped and backward entry points refuse the bit
+            mb = _lib.GptqMoe()
+            mb.E, mb.flags, mb.gate, mb.up, mb.down = m.E, m.flags | _lib.MOE_LOW_BIT_BATCH, m.gate, m.up, m.down
         table = torch.zeros(max(1, int(lib.gptq_moe_table_bytes(self.num_experts))), dtype=torch.uint8, device=dev)
-        self._moe, self._keep, self._plans = m, (arrs, table, gate, up, down), {}
+        self._moe, self._moe_batch, self._keep, self._plans = m, mb, (arrs, table, gate, up, down), {}
         self._table = table
         self._decode_table = None
         self._grad_table = None
         self._batch_ok = False
+        self._low_bit_batch_ok = False
         self._prefill_ok = False
         self.decode_copy_bytes = extra
         self._dev = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
@@ -224,12 +246,20 @@ class QuantMoEExperts(nn.Module):
                     _lib.check(lib.gptq_moe_build_grad_table(ctypes.byref(m), gtable.data_ptr(), _lib.current_stream_handle(self._dev)))
                 self._grad_table = gtable
         if self._decode_copy:
-            dplan = _lib.describe_moe_decode_plan(m, 1, self.top_k)
+            lbplan = _lib.describe_moe_batch_plan(mb, 5, self.top_k) if self._low_bit_batch else None
+            if lbplan is not None and lbplan["path"] != "batch":
+                logger.warning("QuantMoEExperts.low_bit_batch = True has no effect for these experts (%s)", _clean_reason(lbplan)["reason"])
+                self.low_bit_batch = False                       # (said once: the attribute is unset, the experts behave as without it)
+                return self.post_init(decode_copy=want_decode, batch=self._batch, backward=self._backward, low_bit=self._low_bit, prefill=self._prefill,
+                                      low_bit_decode=self._low_bit_decode)
+            # 2- / 3-bit experts opened for the batch path alone: the copy is the batch path's, the decode plan (which declines them) has no say
+            dplan = _lib.describe_moe_decode_plan(m, 1, self.top_k) if not (self._low_bit_batch and not self._low_bit_decode) else {"path": "decode"}
             if dplan["path"] != "decode":
                 # declined (2- / 3-bit, fp32, a group size the copy does not take, ...): nothing would read the copies -- say so and give their memory back
                 logger.warning("QuantMoEExperts.post_init(decode_copy=True) has no effect for these experts (%s): no decode copy is kept",
                                _clean_reason(dplan)["reason"])
-                return self.post_init(decode_copy=False, backward=self._backward, low_bit=self._low_bit)      # (batch, prefill and low_bit_decode need the copy: declined with it)
+                # (batch, prefill and low_bit_decode need the copy: declined with it; the low_bit_batch attribute then stands alone and asks the batch plan)
+                return self.post_init(decode_copy=False, backward=self._backward, low_bit=self._low_bit)
             bplan = _lib.describe_moe_batch_plan(m, 5, self.top_k) if self._batch else None
             if bplan is not None and bplan["path"] != "batch":
                 logger.warning("QuantMoEExperts.post_init(batch=True) has no effect for these experts (%s)", _clean_reason(bplan)["reason"])
@@ -242,9 +272,11 @@ class QuantMoEExperts(nn.Module):
                                       low_bit_decode=self._low_bit_decode)
             dtable = torch.zeros(max(1, int(lib.gptq_moe_decode_table_bytes(self.num_experts))), dtype=torch.uint8, device=dev)
             with torch.cuda.device(self._dev):
-                _lib.check(lib.gptq_moe_build_decode_table(ctypes.byref(m), dtable.data_ptr(), _lib.current_stream_handle(self._dev)))
+                _lib.check(lib.gptq_moe_build_decode_table(ctypes.byref(mb if mb is not None and not self._low_bit_decode else m), dtable.data_ptr(),
+                                                           _lib.current_stream_handle(self._dev)))
             self._decode_table = dtable
             self._batch_ok = self._batch
+            self._low_bit_batch_ok = self._low_bit_batch
             self._prefill_ok = self._prefill
             self._plans = {}
         return self
@@ -254,8 +286,13 @@ class QuantMoEExperts(nn.Module):
         if self._moe is None:
             self.post_init(self._decode_copy, self._batch, self._backward, self._low_bit, self._prefill, self._low_bit_decode)
 
-    def _copy_path_declined(self, word: str, multiple: int, group_rule) -> str:
-        """Why the `word` plan would decline these experts, as far as the layer metadata says (empty: build the copies and ask the plan)."""
+    def _moe_of(self, path: str):
+        """The gptq_moe_t a path's entry points take: the batch path of 2- / 3-bit experts has its own (GPTQ_MOE_LOW_BIT_BATCH set)."""
+        return self._moe_batch if path == "batch" and self._moe_batch is not None else self._moe
+
+    def _copy_path_declined(self, word: str, multiple: int, group_rule, low_bit: bool = False) -> str:
+        """Why the `word` plan would decline these experts, as far as the layer metadata says (empty: build the copies and ask the plan).  ``low_bit``: the
+        path's own 2- / 3-bit flag is set."""
         gate, _, down = self[0].layers()
         if self.hidden_dim % multiple or self.intermediate_dim % multiple:
             return f"hidden and intermediate sizes must be multiples of {multiple}"
@@ -264,7 +301,7 @@ class QuantMoEExperts(nn.Module):
             gs, q = l.group_size, l.group_size // base
             if not (gs in others or gs >= l.infeatures or (gs % base == 0 and q & (q - 1) == 0)):
                 return f"group_size {gs}: the {word} path takes {text}"
-        if self.bits in (2, 3):
+        if self.bits in (2, 3) and not low_bit:
             return f"{self.bits}-bit experts: the {word} path takes 4 or 8 bits"
         return self._decode_copy_declined().replace("the decode path", f"the {word} path")
 
@@ -279,7 +316,7 @@ class QuantMoEExperts(nn.Module):
     def _decode_copy_declined(self) -> str:
         """Why the decode plan would decline these experts, as far as the layer metadata says (empty: build the copies and ask the plan)."""
         gate, _, down = self[0].layers()
-        if self.bits not in (4, 8) and not (self._low_bit_decode and self.bits in (2, 3)):
+        if self.bits not in (4, 8) and not ((self._low_bit_decode or self._low_bit_batch) and self.bits in (2, 3)):
             return f"{self.bits}-bit experts: the decode path takes 4 or 8 bits"
         if gate.scales.dtype not in (torch.float16, torch.bfloat16):
             return "fp32 experts: the decode path takes fp16 / bf16"
@@ -298,8 +335,9 @@ class QuantMoEExperts(nn.Module):
     def workspace_bytes(self, T: int, top_k: "int | None" = None) -> int:
         """Scratch of one call with T tokens on the path ``plan(T)`` names."""
         self._ensure_init()
-        fn = _PATHS.get(self.plan(T, top_k)["path"], _PATHS["grouped"]).workspace          # (per_expert: the grouped entry point's answer, 0)
-        return int(getattr(_lib.load(), fn)(ctypes.byref(self._moe), T, top_k or self.top_k))
+        path = self.plan(T, top_k)["path"]
+        fn = _PATHS.get(path, _PATHS["grouped"]).workspace          # (per_expert: the grouped entry point's answer, 0)
+        return int(getattr(_lib.load(), fn)(ctypes.byref(self._moe_of(path)), T, top_k or self.top_k))
 
     def backward_workspace_bytes(self, T: int, top_k: "int | None" = None) -> int:
         """Scratch of one gptq_moe_backward call with T tokens (0 when the experts have no grouped backward)."""
@@ -312,21 +350,24 @@ class QuantMoEExperts(nn.Module):
         """{"path": "decode" | "batch" | "prefill" | "grouped" | "per_expert", "reason": ...} (+ the launch / tile geometry) for T tokens: what moe_forward runs
         without grad.  "decode" only when the experts carry a decode copy (``post_init(decode_copy=True)``) and the decode plan accepts (1..4 tokens);
         "batch" only after ``post_init(batch=True)``, for 5..``batch_max_tokens`` tokens; "prefill" only after ``post_init(prefill=True)``, for 65 tokens
-        and more; else the grouped path (or the composition)."""
+        and more; else the grouped path (or the composition).  2- and 3-bit experts: "decode" only after ``post_init(low_bit_decode=True)``, "batch" only
+        with the attribute ``low_bit_batch = True`` at ``post_init``, for 5..min(64, ``low_bit_batch_max_tokens``) tokens."""
         top_k = top_k or self.top_k
         if self[0].layers()[0].qweight.device.type != "cuda":
             return {"path": "per_expert", "reason": "cpu tensors"}
         self._ensure_init()
-        dmax = min(4, int(self.low_bit_decode_max_tokens)) if self.bits in (2, 3) else 4
-        key = (T, top_k, self.batch_max_tokens, dmax)
+        low = self.bits in (2, 3)
+        dmax = (min(4, int(self.low_bit_decode_max_tokens)) if self._low_bit_decode else 0) if low else 4
+        bmax = min(64, int(self.low_bit_batch_max_tokens if low else self.batch_max_tokens))
+        key = (T, top_k, bmax, dmax)
         d = self._plans.get(key)
         if d is None:
             copy = self._decode_table is not None
             for path, asked in (("decode", copy and 0 < T <= dmax),
-                                ("batch", copy and self._batch_ok and 4 < T <= min(64, self.batch_max_tokens)),
+                                ("batch", copy and (self._low_bit_batch_ok if low else self._batch_ok) and 4 < T <= bmax),
                                 ("prefill", copy and self._prefill_ok and T > 64)):      # (prefill declines more than 65535 routed rows: the grouped path)
                 if asked and d is None:
-                    d = _PATHS[path].describe(self._moe, T, top_k)
+                    d = _PATHS[path].describe(self._moe_of(path), T, top_k)
                     if d["path"] != path:
                         d = None
             if d is None:
@@ -387,7 +428,7 @@ def moe_forward(experts: QuantMoEExperts, x: torch.Tensor, top_k_index: torch.Te
         idx_dev = experts._dev.index
         with torch.cuda.device(idx_dev):
             entry = _PATHS[path]
-            rc = getattr(_lib.load(), entry.forward)(ctypes.byref(experts._moe), getattr(experts, entry.table).data_ptr(), xw.data_ptr(), idx.data_ptr(),
+            rc = getattr(_lib.load(), entry.forward)(ctypes.byref(experts._moe_of(path)), getattr(experts, entry.table).data_ptr(), xw.data_ptr(), idx.data_ptr(),
                                                      w.data_ptr(), T, topk, out.data_ptr(), _lib.ptr(h_out), buf.data_ptr(), buf.numel(), _raw_stream(idx_dev))
         if rc:
             _lib.check(rc)

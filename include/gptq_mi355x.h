@@ -375,13 +375,20 @@ int gptq_describe_adapter_rows_plan(const gptq_adapter_bank_t *const *banks, int
  * GPTQ_MOE_LOW_BIT_DECODE (independent of GPTQ_MOE_LOW_BIT; the two may be or-ed): the DECODE path (gptq_moe_build_decode_table /
  * gptq_moe_decode_forward and their describe / workspace twins, T <= 4) also takes 2- and 3-bit experts with a decode copy -- same contract, same
  * workspace, same plan keys; gate, up and down share one width there as at 4 / 8 bits.  The grouped and the backward entry points ignore it (flags 8 / 9
- * behave as 0 / 1); the batch, the prefill and the fused shared-expert entry points decline 2 / 3 bits whatever the flags say.  Without the flag every
- * entry point answers as it did.  Unknown flag bits (2 and 4 among them): GPTQ_ERR_UNSUPPORTED from the grouped and the backward entry points. */
+ * behave as 0 / 1); the batch, the prefill and the fused shared-expert entry points decline 2 / 3 bits whatever these two flags say.  Without the flag every
+ * entry point answers as it did.  Unknown flag bits (2 and 4 among them): GPTQ_ERR_UNSUPPORTED from the grouped and the backward entry points.
+ * GPTQ_MOE_LOW_BIT_BATCH (independent of the other two; they may be or-ed): the BATCH path (gptq_moe_batch_forward and its describe / workspace twins,
+ * T <= 64) also takes 2- and 3-bit experts with a decode copy -- same contract, same launches, the workspace of the 4-bit set of the same (T, topk, E, H, I);
+ * gptq_moe_build_decode_table then builds their table with this flag alone as well (the batch path's own checks apply: H and I multiples of 128, its group
+ * sizes).  The decode, prefill and fused shared-expert entry points ignore the bit.  The grouped and the backward entry points keep refusing it with their
+ * unknown-flag-bits message, as they did before it had a meaning: a caller that runs both paths on such experts keeps two gptq_moe_t over the same layer
+ * arrays, one with the bit for the batch path (and its table build), one without for the rest (autogptq_amd/moe.py does). */
 #define GPTQ_MOE_LOW_BIT 1
 #define GPTQ_MOE_LOW_BIT_DECODE 8
+#define GPTQ_MOE_LOW_BIT_BATCH 0x10
 typedef struct gptq_moe_t {
     int32_t E;
-    int32_t flags;                     /* 0 | GPTQ_MOE_LOW_BIT | GPTQ_MOE_LOW_BIT_DECODE (the field was `reserved`, 0, before: a zeroed struct means what it meant) */
+    int32_t flags;                     /* 0 | GPTQ_MOE_LOW_BIT | GPTQ_MOE_LOW_BIT_DECODE | GPTQ_MOE_LOW_BIT_BATCH (the field was `reserved`, 0, before: a zeroed struct means what it meant) */
     const gptq_layer_t *const *gate;   /* [E] */
     const gptq_layer_t *const *up;     /* [E] */
     const gptq_layer_t *const *down;   /* [E] */
@@ -478,7 +485,8 @@ int gptq_moe_shared_combine(const void *x, const void *gate_w, const void *ys, v
  * bit-reproducible, and the row of token t does not depend on the other tokens of the call.
  *   Launches: routing (bm = 16), gate|up + silu * mul, down, combine: FOUR; sets with act-order experts add one row gather through perm in front of either
  *   GEMM (five or six).  No host round trip; the grid is a bound from (T, topk, E), so a captured graph replays with new routing.
- * Takes 4- and 8-bit fp16 / bf16 experts, plain or act-order (gate and up may have different activation orders), group_size 32, 64, 128 2^n or one group,
+ * Takes 4- and 8-bit fp16 / bf16 experts (2- and 3-bit ones with GPTQ_MOE_LOW_BIT_BATCH in moe->flags: same launches and workspace; moe_rows_lowbit_kernel
+ * reads their copy in place), plain or act-order (gate and up may have different activation orders), group_size 32, 64, 128 2^n or one group,
  * H and I multiples of 128, E <= 256, topk <= 8, no bias, every expert with its decode copy.  Anything else: GPTQ_ERR_UNSUPPORTED with the reason.
  * `table` is the DECODE table (gptq_moe_build_decode_table): there is no table of its own.
  * Workspace of one call:  GPTQ_WORKSPACE_HEADER_BYTES (left untouched)
@@ -492,7 +500,8 @@ size_t gptq_moe_batch_workspace_bytes(const gptq_moe_t *moe, int T, int topk);
 int gptq_moe_batch_forward(const gptq_moe_t *moe, const void *table, const void *x, const int64_t *topk_idx, const float *topk_w, int T, int topk, void *out,
                            void *h_out, void *workspace, size_t workspace_bytes, void *stream);
 /* Host-only: "path=batch bm=16 s=4 tiles=10 launches=4 waves_pair=8 waves_down=8 lds_pair=... lds_down=..." (s: strip-chunks per wave and chunk -- the pair
- * form runs 2 strips of W1 and of W3, the down form 4 of W2) or "path=none reason=..." (no decode copy, T > 64, 2- / 3-bit, fp32, ...).  GPTQ_OK either way. */
+ * form runs 2 strips of W1 and of W3, the down form 4 of W2; 2- / 3-bit experts taken under GPTQ_MOE_LOW_BIT_BATCH: the same keys and a trailing "bits=3")
+ * or "path=none reason=..." (no decode copy, T > 64, 2- / 3-bit without GPTQ_MOE_LOW_BIT_BATCH, fp32, ...).  GPTQ_OK either way. */
 int gptq_describe_moe_batch_plan(const gptq_moe_t *moe, int T, int topk, char *out, size_t out_bytes);
 
 /* PREFILL path of the routed layer (additive in ABI 8): the same formulas and arithmetic contract on the experts' DECODE COPY at ANY token count (the Python

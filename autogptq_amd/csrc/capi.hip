@@ -81,7 +81,9 @@ int check_align(const void* x, const void* out, const void* ws) {
     return GPTQ_OK;
 }
 
-bool want_gemm(const gptq_layer_t* L, int M, const gptq_tuning_t* t) {
+// The GEMM step of the ladder (route_forward).  plan() is plan_gemm(*L, M, t), computed at most once; want_gemm below hands it to the caller.
+template <typename Plan>
+bool gemm_rule(const gptq_layer_t* L, int M, const gptq_tuning_t* t, Plan&& plan) {
     if (t && t->path == 3) return true;
     if (t && (t->path == 1 || t->path == 2 || t->path == 4 || t->path == 5)) return false;
     // M = 5..8 on wide layers: the GEMV needs two matrix-core passes per weight word there, and a wide N gives the tiled kernel
@@ -92,7 +94,7 @@ bool want_gemm(const gptq_layer_t* L, int M, const gptq_tuning_t* t) {
         // is faster or equal on every shape (tools/cliff_scan.py --slice D: 4096x11008 M = 8: 517 us against ~60; M = 64: 528 against
         // ~510; 4096x4096 M = 64 on 32 tiles: 455 against 85)
         if (M <= 64) return false;
-        const GemmPlan gf = plan_gemm(*L, M, t);
+        const GemmPlan& gf = plan();
         return gf.supported && (long)gf.nbm * gf.nbn >= 64;      // fewer tiles than a quarter of the chip: the GEMV still wins (4096x4096 M = 128: ~170 us against 455)
     }
     if (!t && L->epilogue == GPTQ_EPI_NONE && rows_pays(*L, M)) return true;      // 5 .. 128 rows from the decode copy (gemm_rows.hip; plan_gemm picks it)
@@ -109,33 +111,41 @@ bool want_gemm(const gptq_layer_t* L, int M, const gptq_tuning_t* t) {
         const bool int8_rows8 = L->bits == 8 && L->dtype == GPTQ_F16 && L->N <= 4096 && L->epilogue == GPTQ_EPI_NONE && !raw_act;
         const int min_m = raw_act ? (L->bits == 8 ? 3 : 5) : (L->bits == 8 ? (int8_rows8 ? 9 : 5) : ((L->bits == 2 && big) ? 5 : 9));
         if (M >= 5 && M < min_m && L->epilogue == GPTQ_EPI_NONE && !raw_act) {
-            const GemmPlan g8 = plan_gemm(*L, M, t);              // 5..8 rows: the 2- / 3- / 8-bit forms of gemm_mid_kernel where the planner takes them (tools/nonq4_batched.py:
-            if (g8.supported && g8.mid) return true;              // 11008x4096 M = 8 27.1 -> 16.1 us, 4096x4096 12.3 -> 11.1)
+            const GemmPlan& g8 = plan();                          // 5..8 rows: the 2- / 3- / 8-bit forms of gemm_mid_kernel where the planner takes them (tools/nonq4_batched.py:
+            if (g8.supported && g8.kernel == GEMM_MID) return true;             // 11008x4096 M = 8 27.1 -> 16.1 us, 4096x4096 12.3 -> 11.1)
         }
         if (M < min_m) return false;
-        return plan_gemm(*L, M, t).supported;
+        return plan().supported;
     }
     if (M <= 2) return false;
-    const GemmPlan g = plan_gemm(*L, M, t);
+    const GemmPlan& g = plan();
     // M = 3..4: only the unsplit streamed 64-column-strip kernel (160+ strips) beats the GEMVs there (tools/cliff_scan.py, us, M = 3 / 4 / 5:
     // 4096x11008 11.8 / 12.0 / 10.8, 5120x13824 15.0 / 15.8 / 13.1 -- the M = 5 column is that kernel, whose time barely depends on M up to 16)
-    if (M <= 4 && !(g.supported && g.stream64 && g.ksplit == 1 && L->epilogue == GPTQ_EPI_NONE)) return false;
+    if (M <= 4 && !(g.supported && g.kernel == GEMM_STREAM64 && g.ksplit == 1 && L->epilogue == GPTQ_EPI_NONE)) return false;
     // M = 5..8: the streamed 64-column-strip kernel (one matrix-core pass for up to 16 rows, weights by LDS DMA) where it exists;
     // layers with a fused epilogue keep the GEMV that applies it
     // (and the 16-column-strip kernel on narrow layers: 4096x4096 M = 5 / 8: 7.3 / 7.9 us against the GEMV's 8.0 / 8.3)
     // (28672x1024, M = 8: GEMV 14.8, 16-column strips 17.0 -- long K keeps the GEMV)
-    const bool small_batch_stream = g.supported && (g.stream64 || (g.strip16 && L->K <= 8192)) && L->epilogue == GPTQ_EPI_NONE;
+    const bool small_batch_stream = g.supported && (g.kernel == GEMM_STREAM64 || (g.kernel == GEMM_STRIP16 && L->K <= 8192)) && L->epilogue == GPTQ_EPI_NONE;
     if (M <= 8 && !wide_small_batch && !small_batch_stream) return false;
     return g.supported;
+}
+// *g: plan_gemm(*L, M, t) wherever the answer is yes (M <= 0 excepted: check_io refuses the call before anything reads the plan)
+bool want_gemm(const gptq_layer_t* L, int M, const gptq_tuning_t* t, GemmPlan* g) {
+    bool planned = false;
+    auto plan = [&]() -> const GemmPlan& { return planned ? *g : (planned = true, *g = plan_gemm(*L, M, t)); };
+    const bool want = gemm_rule(L, M, t, plan);
+    if (want && M > 0) plan();
+    return want;
 }
 
 // The streamed GEMV (weights by LDS DMA, in-launch K-split combine) for a single layer: forced by tuning.path = 6, else by
 // the planner's measured preference.
-bool want_stream(const gptq_layer_t* L, int M, const gptq_tuning_t* t) {
+bool want_stream(const gptq_layer_t* L, int M, const gptq_tuning_t* t, StreamPlan* plan_out) {
     if (M > 4 || L->epilogue != GPTQ_EPI_NONE) return false;
     if (t && t->path != 0 && t->path != 6) return false;
     const gptq_layer_t* one[1] = {L};
-    const StreamPlan sp = plan_stream(one, 1, M, t);
+    const StreamPlan& sp = *plan_out = plan_stream(one, 1, M, t);
     if (!sp.ok) return false;
     if (t && t->path == 6) return true;
     if (M >= 3) {                                      // 3..4 rows on layers of 160+ strips: the batched-decode kernel (want_gemm)
@@ -165,9 +175,8 @@ static bool tiled_rows8_pays(const gptq_layer_t* const* Ls, int n) {
     }
     return n >= 2 && strips >= 1024 && L.K <= 4096;
 }
-// plan_out: the plan the answer was derived from (the eager decode call computes it ONCE: a launch of this kernel runs for 4.5 us, the host side of an eager
-// call is measured in the same unit -- tools/host_cost.py)
-bool want_tiled(const gptq_layer_t* const* Ls, int n, int M, const gptq_tuning_t* t, TiledPlan* plan_out = nullptr) {
+// plan_out: the plan the answer was derived from
+bool want_tiled(const gptq_layer_t* const* Ls, int n, int M, const gptq_tuning_t* t, TiledPlan* plan_out) {
     if (M > TILED_ROWS_MAX || n < 1 || n > 4) return false;
     if (Ls[0]->qweight_tiled == nullptr) return false;
     if (Ls[0]->epilogue != GPTQ_EPI_NONE && (n != 1 || M > 4)) return false;     // a [gate | up] layer: the pair form of the kernel (gemv_tiled_pair.hip)
@@ -183,20 +192,19 @@ bool want_tiled(const gptq_layer_t* const* Ls, int n, int M, const gptq_tuning_t
     // ... and at 2 rows from K = 12288 (2 x 2 rows x K of LDS again leave one workgroup per CU): 13824x5120 21.4 us against 18.7 at THREE rows on the pre-pass + streamed kernel
     // (layers of more than 256 strips only: 14336x4096 runs one workgroup per CU either way and keeps this kernel)
     if (!(t && t->path == 8) && M == 2 && Ls[0]->g_idx && Ls[0]->K >= 12288 && Ls[0]->N > 4096 && n == 1) return false;
-    const TiledPlan tp = plan_tiled(Ls, n, M, t);                  // act-order layers: the copy holds the re-sequenced rows, the kernel gathers x through perm
-    if (plan_out) *plan_out = tp;
-    return tp.ok;
+    *plan_out = plan_tiled(Ls, n, M, t);                           // act-order layers: the copy holds the re-sequenced rows, the kernel gathers x through perm
+    return plan_out->ok;
 }
 
 // act-order layers on the streamed GEMV: x permuted once by the column-permute pre-pass, the kernel streams the re-sequenced rows of a
 // plain copy of the layer.  Where the streamed kernel is the planner's choice for that copy (tools/cliff_scan.py --slice F, us, in-kernel
 // gather / register kernel -> this: 13824x5120 M = 1 / 2 / 4 19.6 / 24.7 / 26.9 -> ~17 / 17.3 / 19.8; 8192x28672 M = 1 37.0 -> ~31); with
 // one row only from 33 MiB up -- below that the in-kernel gather is cheaper than the 2.6 us pre-pass (5120x5120: 9.7 against 10.1).
-static bool want_stream_seq(const gptq_layer_t* L, int M, const gptq_tuning_t* t, gptq_layer_t* P) {
+static bool want_stream_seq(const gptq_layer_t* L, int M, const gptq_tuning_t* t, gptq_layer_t* P, StreamPlan* plan_out) {
     if (t || !L->g_idx || !L->qweight_seq || !L->perm || L->epilogue != GPTQ_EPI_NONE || M > 4) return false;
     *P = *L;
     P->g_idx = nullptr; P->perm = nullptr; P->qweight = L->qweight_seq; P->qweight_seq = nullptr;
-    if (!want_stream(P, M, nullptr)) return false;
+    if (!want_stream(P, M, nullptr, plan_out)) return false;
     if (M == 1 && (size_t)L->K * L->N * L->bits / 8 < ((size_t)33 << 20)) return false;
     return true;
 }
@@ -207,6 +215,10 @@ struct WsView { void* header; void* body; size_t body_bytes; };
 WsView split_ws(void* ws, size_t ws_bytes) {
     if (!ws || ws_bytes <= WS_HEADER_BYTES) return WsView{nullptr, nullptr, 0};
     return WsView{ws, (char*)ws + WS_HEADER_BYTES, ws_bytes - WS_HEADER_BYTES};
+}
+int need_body(const WsView& wv, size_t body) {      // the refusal of a call whose workspace is shorter than the header + `body` bytes
+    if (wv.body_bytes >= body) return GPTQ_OK;
+    return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", WS_HEADER_BYTES + body, wv.header ? WS_HEADER_BYTES + wv.body_bytes : (size_t)0);
 }
 
 }  // namespace
@@ -255,49 +267,88 @@ static const gptq_tuning_t* inner_tuning(const gptq_layer_t* L, int M, const gpt
     }
     return nullptr;
 }
-static bool fused_epilogue_ok(const gptq_layer_t* L, int M, const gptq_tuning_t* tune) {
-    if (!tune && small_batch_stream_for_epilogue(L, M)) return false;
-    return L->epilogue == GPTQ_EPI_SILU_MUL && !want_gemm(L, M, tune) && plan_gemv(*L, M, tune).pair;
+
+// ---- the route of one dense forward call --------------------------------------------------------------------------------
+// route_forward walks the ladder of want_* questions ONCE, in the order below, stops at the first hit and computes the one sub-plan that answer came from
+// (a decode call -- tiled at the first step -- runs plan_tiled and nothing else: a launch of that kernel takes 4.5 us and the host side of an eager call is
+// measured in the same unit, tools/host_cost.py).  The launch (forward_impl), the workspace query (query_body_bytes), gptq_describe_plan, the MLP entry
+// points, separate_panels_pay and gptq_forward_scatter read the route; none of them asks a want_* question itself.
+enum RouteKind {
+    ROUTE_TILED,          // decode-copy kernel (tp)
+    ROUTE_TILED_PAIR,     // ... with SiLU * mul as its epilogue (round 5): decode rows of a [gate | up] layer that carries its copy, one launch, no scratch
+    ROUTE_STREAM,         // streamed GEMV (sp)
+    ROUTE_STREAM_SEQ,     // x permuted by the pre-pass into the front of the body, then the streamed GEMV on `seq`, the plain copy of the act-order layer (sp)
+    ROUTE_GEMM,           // gp
+    ROUTE_GEMV,           // vp
+};
+struct ForwardRoute {             // (only the scalars are initialised: a plan is written before its kind is set)
+    RouteKind kind;
+    int declined = 0;     // a forced tuning.path (8 / 6) the call does not fit: gptq_forward_ex returns route_decline(); the host-only queries have always
+                          // answered such a call with the rest of the ladder, so that is what kind / plans / body hold
+    // SILU_MUL as an elementwise pass of its own: y = [gate | up] sits in the first epi_bytes of the body, and everything else here is the route of the
+    // INNER call -- on `plain` (the layer without its epilogue), under tuning(): the caller's, or the `local` one inner_tuning made
+    bool unfused_epilogue = false, own_tuning = false;
+    gptq_layer_t plain, seq;
+    gptq_tuning_t local;
+    TiledPlan tp; StreamPlan sp; GemmPlan gp; GemvPlan vp;      // the ONE sub-plan of `kind`
+    size_t epi_bytes = 0, body = 0;      // body: bytes behind the ticket header this route needs (epi_bytes included)
+    const gptq_layer_t* layer(const gptq_layer_t* L) const { return unfused_epilogue ? &plain : L; }
+    const gptq_tuning_t* tuning(const gptq_tuning_t* t) const { return own_tuning ? &local : t; }
+    bool hit(RouteKind k, size_t need) { kind = k; body = epi_bytes + need; return true; }
+};
+static ForwardRoute route_forward(const gptq_layer_t* L, int M, const gptq_tuning_t* tune) {
+    ForwardRoute r;
+    const gptq_layer_t* one[1] = {L};
+    if (want_tiled(one, 1, M, tune, &r.tp) && r.hit(L->epilogue == GPTQ_EPI_NONE ? ROUTE_TILED : ROUTE_TILED_PAIR, r.tp.partial_bytes)) return r;
+    if (L->epilogue != GPTQ_EPI_NONE) {
+        // fused: the GEMV applies the epilogue itself, where the GEMV is the choice and has the pair form (path = 6 does not fit a layer with an epilogue)
+        if ((tune || !small_batch_stream_for_epilogue(L, M)) && L->epilogue == GPTQ_EPI_SILU_MUL && !want_gemm(L, M, tune, &r.gp)) {
+            r.vp = plan_gemv(*L, M, tune);
+            r.declined = (r.vp.pair && tune && tune->path == 6) ? 6 : 0;
+            if (r.vp.pair && r.hit(ROUTE_GEMV, r.vp.workspace_bytes)) return r;
+        }
+        r.unfused_epilogue = true;
+        r.epi_bytes = epi_scratch_bytes(L, M);
+        r.plain = *L;
+        r.plain.epilogue = GPTQ_EPI_NONE;
+        r.own_tuning = inner_tuning(L, M, tune, &r.local) == &r.local;
+        one[0] = L = &r.plain;
+        tune = r.tuning(tune);
+        if (want_tiled(one, 1, M, tune, &r.tp) && r.hit(ROUTE_TILED, r.tp.partial_bytes)) return r;
+    }
+    if (tune && tune->path == 8) r.declined = 8;
+    if (want_stream(L, M, tune, &r.sp) && r.hit(ROUTE_STREAM, r.sp.partial_bytes)) return r;
+    if (want_stream_seq(L, M, tune, &r.seq, &r.sp) && r.hit(ROUTE_STREAM_SEQ, xperm16_bytes(L, M) + r.sp.partial_bytes)) return r;
+    if (tune && tune->path == 6) r.declined = 6;
+    if (want_gemm(L, M, tune, &r.gp) && r.hit(ROUTE_GEMM, r.gp.supported ? r.gp.workspace_bytes : 0)) return r;
+    r.hit(ROUTE_GEMV, M > 0 ? (r.vp = plan_gemv(*L, M, tune)).workspace_bytes : 0);      // (M <= 0: check_io refuses the call before anything reads the plan)
+    return r;
+}
+static int route_decline(const ForwardRoute& r) {
+    if (r.declined == 8) return fail(GPTQ_ERR_UNSUPPORTED, "tuning.path = 8: the decode-copy kernel needs M <= 8 and a plain or re-sequenced act-order 3/4/8-bit fp16/bf16 layer that carries qweight_tiled / qconst_tiled "
+                                          "(gptq_prepack_decode; tiled_cols = %d)", GPTQ_STRIP_COLS);
+    return fail(GPTQ_ERR_UNSUPPORTED, "tuning.path = 6: the streamed GEMV needs M <= 4, a plain 4-bit fp16/bf16 layer (no act-order, no epilogue) "
+                                      "and a launch shape with rows-per-lane in {2, 4, 8} dividing the rows of a group");
 }
 
 // Body = what the kernels use behind the ticket header; the public figure adds the header whenever there is a body.
-static bool tiled_pair_call(const gptq_layer_t* L, int M, const gptq_tuning_t* tune) {
-    const gptq_layer_t* one[1] = {L};
-    return L->epilogue == GPTQ_EPI_SILU_MUL && want_tiled(one, 1, M, tune);
-}
-static size_t body_bytes(const gptq_layer_t* L, int M, const gptq_tuning_t* tune) {
-    if (tiled_pair_call(L, M, tune)) return 0;                                    // decode rows of a [gate | up] layer that carries its copy: one launch, no scratch
-    if (L->epilogue != GPTQ_EPI_NONE && !fused_epilogue_ok(L, M, tune)) {
-        gptq_layer_t Lc = *L;
-        Lc.epilogue = GPTQ_EPI_NONE;
-        gptq_tuning_t local;
-        const size_t inner = body_bytes(&Lc, M, inner_tuning(L, M, tune, &local));          // the inner call shares the ONE zeroed ticket header; its body starts behind y
-        return epi_scratch_bytes(L, M) + inner;
-    }
-    size_t a = plan_gemv(*L, M, tune).workspace_bytes;
-    GemmPlan g = plan_gemm(*L, M, tune);
-    size_t b = g.supported ? g.workspace_bytes : 0;
-    if (g.supported && (g.rows || g.panel) && want_gemm(L, M, tune)) return b;                 // the exchange-free batched-decode kernel: nothing but the permuted x of act-order layers
-    size_t c = 0;
-    {
-        const gptq_layer_t* one[1] = {L};
-        if (want_tiled(one, 1, M, tune)) return plan_tiled(one, 1, M, tune).partial_bytes;
-    }
-    if (want_stream(L, M, tune)) {
-        const gptq_layer_t* one[1] = {L};
-        c = plan_stream(one, 1, M, tune).partial_bytes;
-    }
-    gptq_layer_t P;
-    if (want_stream_seq(L, M, tune, &P)) {
-        const gptq_layer_t* one[1] = {&P};
-        c = std::max(c, xperm16_bytes(L, M) + plan_stream(one, 1, M, nullptr).partial_bytes);
-    }
-    return std::max(std::max(a, b), c);
+// The header documents gptq_workspace_bytes* as covering gptq_forward, gptq_gemv AND gptq_gemm on the layer: a caller may size one workspace with the query and
+// then call any of the three.  So the query is max(route need, GEMV need, GEMM need) -- except for the routes that exist only behind gptq_forward and need
+// (next to) nothing: the decode-copy kernel, and the exchange-free rows / panel GEMMs (nothing but the permuted x of act-order layers).
+static size_t query_body_bytes(const gptq_layer_t* L, int M, const gptq_tuning_t* tune) {
+    const ForwardRoute r = route_forward(L, M, tune);
+    if (r.kind == ROUTE_TILED || r.kind == ROUTE_TILED_PAIR) return r.body;
+    if (r.kind == ROUTE_GEMM && r.gp.supported && (r.gp.kernel == GEMM_ROWS || r.gp.kernel == GEMM_PANEL)) return r.body;
+    const gptq_layer_t* Lr = r.layer(L);
+    const size_t a = r.kind == ROUTE_GEMV ? r.vp.workspace_bytes : plan_gemv(*Lr, M, r.tuning(tune)).workspace_bytes;
+    const GemmPlan g = r.kind == ROUTE_GEMM ? r.gp : plan_gemm(*Lr, M, r.tuning(tune));
+    const size_t b = g.supported ? g.workspace_bytes : 0;
+    return std::max(r.body, r.epi_bytes + std::max(a, b));      // (the inner call of an unfused epilogue shares the ONE zeroed ticket header; its body starts behind y)
 }
 
 size_t gptq_workspace_bytes_ex(const gptq_layer_t* L, int M, const gptq_tuning_t* tune) {
     if (check_layer(L) != GPTQ_OK || M <= 0) return 0;
-    const size_t b = body_bytes(L, M, tune);
+    const size_t b = query_body_bytes(L, M, tune);
     return b ? WS_HEADER_BYTES + b : 0;
 }
 
@@ -336,16 +387,12 @@ int gptq_validate_g_idx(const int32_t* g_idx, int K, int G) {
 }
 
 // The kernels see the workspace as (ticket header, body): the header is the caller's zeroed first 64 KiB and is NEVER relocated -- a call
-// that nests another one (the unfused SILU_MUL epilogue) hands the inner call the same header and the rest of its body.
-static int gemv_core(const gptq_layer_t* L, const void* x, void* out, int M, const WsView& wv, void* stream, const gptq_tuning_t* tune) {
-    int rc = check_layer(L);
-    if (rc) return rc;
-    rc = check_io(x, out, M);
-    if (rc) return rc;
+// that nests another one (the unfused SILU_MUL epilogue) hands the inner call the same header and the rest of its body.  (The cores take the plan their
+// caller computed: the route's, or the public gptq_gemv / gptq_gemm's own.)
+static int gemv_core(const gptq_layer_t* L, const GemvPlan& pl, const void* x, void* out, int M, const WsView& wv, void* stream, const gptq_tuning_t* tune) {
     if (tune && tune->lanes_n && tune->lanes_n != 4 && tune->lanes_n != 8 && tune->lanes_n != 16 && tune->lanes_n != 64)   // = the header's list
         return fail(GPTQ_ERR_UNSUPPORTED, "tuning.lanes_n must be 4, 8, 16 or 64");
     if (tune && (tune->waves < 0 || tune->waves > 16)) return fail(GPTQ_ERR_UNSUPPORTED, "tuning.waves must be 1..16");
-    GemvPlan pl = plan_gemv(*L, M, tune);
     if (L->epilogue != GPTQ_EPI_NONE && !pl.pair)
         return fail(GPTQ_ERR_UNSUPPORTED, "this GEMV kernel has no fused epilogue; call gptq_forward[_ex], which stages y in the workspace");
     if (tune && tune->path == 5 && !pl.mfma && !pl.mfmag)
@@ -357,8 +404,7 @@ static int gemv_core(const gptq_layer_t* L, const void* x, void* out, int M, con
         return fail(GPTQ_ERR_UNSUPPORTED, "fp32-math GEMV: strips of 16 or 64 columns only (lanes_n = 4 / 16; fp32 layers also 8)");
     if (tune && (tune->path == 2 || tune->path == 4))
         return fail(GPTQ_ERR_UNSUPPORTED, "tuning.path = %d (round 1's LDS-staged / v_dot2 comparison GEMVs) was retired in round 6", tune->path);
-    if (pl.workspace_bytes > 0 && wv.body_bytes < pl.workspace_bytes)
-        return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", WS_HEADER_BYTES + pl.workspace_bytes, wv.header ? WS_HEADER_BYTES + wv.body_bytes : (size_t)0);
+    if (int rc = need_body(wv, pl.workspace_bytes)) return rc;
     hipError_t e = launch_gemv(*L, pl, x, out, M, wv.body, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "gptq_gemv launch");
     return GPTQ_OK;
@@ -366,23 +412,19 @@ static int gemv_core(const gptq_layer_t* L, const void* x, void* out, int M, con
 int gptq_gemv(const gptq_layer_t* L, const void* x, void* out, int M, void* ws, size_t ws_bytes, void* stream,
               const gptq_tuning_t* tune) {
     if (int rc = check_align(x, out, ws)) return rc;
-    return gemv_core(L, x, out, M, split_ws(ws, ws_bytes), stream, tune);
+    if (int rc = check_layer(L)) return rc;
+    if (int rc = check_io(x, out, M)) return rc;
+    return gemv_core(L, plan_gemv(*L, M, tune), x, out, M, split_ws(ws, ws_bytes), stream, tune);
 }
 
-static int gemm_core(const gptq_layer_t* L, const void* x, void* out, int M, const WsView& wv, void* stream, const gptq_tuning_t* tune) {
-    int rc = check_layer(L);
-    if (rc) return rc;
-    rc = check_io(x, out, M);
-    if (rc) return rc;
+static int gemm_core(const gptq_layer_t* L, const GemmPlan& pl, const void* x, void* out, int M, const WsView& wv, void* stream) {
     if (L->epilogue != GPTQ_EPI_NONE)
         return fail(GPTQ_ERR_UNSUPPORTED, "the MFMA GEMM has no fused epilogue; call gptq_forward[_ex], which stages y in the workspace");
-    GemmPlan pl = plan_gemm(*L, M, tune);
     if (!pl.supported)
         return fail(GPTQ_ERR_UNSUPPORTED,
                     "MFMA GEMM needs sequential or re-sequenced groups made of whole packing units (fp16/bf16: group_size %% 32 == 0) (bits=%d dtype=%d group_size=%d)",
                     L->bits, L->dtype, L->group_size);
-    if (pl.workspace_bytes > 0 && wv.body_bytes < pl.workspace_bytes)
-        return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", WS_HEADER_BYTES + pl.workspace_bytes, wv.header ? WS_HEADER_BYTES + wv.body_bytes : (size_t)0);
+    if (int rc = need_body(wv, pl.workspace_bytes)) return rc;
     hipError_t e = launch_gemm(*L, pl, x, out, M, wv.header, wv.body, (hipStream_t)stream);
     if (e != hipSuccess)
         return hip_fail(e, pl.kg == 2 ? "gptq_gemm launch (this kernel needs > 64 KiB of LDS: was gptq_init() called on this device?)"
@@ -392,100 +434,65 @@ static int gemm_core(const gptq_layer_t* L, const void* x, void* out, int M, con
 int gptq_gemm(const gptq_layer_t* L, const void* x, void* out, int M, void* ws, size_t ws_bytes, void* stream,
               const gptq_tuning_t* tune) {
     if (int rc = check_align(x, out, ws)) return rc;
-    return gemm_core(L, x, out, M, split_ws(ws, ws_bytes), stream, tune);
+    if (int rc = check_layer(L)) return rc;
+    if (int rc = check_io(x, out, M)) return rc;
+    return gemm_core(L, plan_gemm(*L, M, tune), x, out, M, split_ws(ws, ws_bytes), stream);
 }
 
 static int stream_call(const gptq_layer_t* const* Ls, int n, const StreamPlan& sp, const void* x, void* const* outs, int M, const WsView& wv,
                        void* stream) {
-    if (sp.partial_bytes > 0 && wv.body_bytes < sp.partial_bytes)
-        return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", WS_HEADER_BYTES + sp.partial_bytes, wv.header ? WS_HEADER_BYTES + wv.body_bytes : (size_t)0);
+    if (int rc = need_body(wv, sp.partial_bytes)) return rc;
     hipError_t e = launch_stream(Ls, sp, x, outs, M, wv.header, wv.body, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "gptq streamed GEMV launch (16 waves x U = 8 needs > 64 KiB of LDS: was gptq_init() called on this device?)");
     return GPTQ_OK;
 }
 
-static int tiled_call(const gptq_layer_t* const* Ls, int n, const void* x, void* const* outs, int M, const WsView& wv, void* stream, const gptq_tuning_t* tune,
-                      const TiledPlan* planned = nullptr) {
-    const TiledPlan tp = planned ? *planned : plan_tiled(Ls, n, M, tune);
-    if (tp.partial_bytes > 0 && wv.body_bytes < tp.partial_bytes)
-        return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", WS_HEADER_BYTES + tp.partial_bytes, wv.header ? WS_HEADER_BYTES + wv.body_bytes : (size_t)0);
+static int tiled_call(const gptq_layer_t* const* Ls, int n, const TiledPlan& tp, const void* x, void* const* outs, int M, const WsView& wv, void* stream) {
+    if (int rc = need_body(wv, tp.partial_bytes)) return rc;
     hipError_t e = launch_tiled(Ls, tp, x, outs, M, wv.header, wv.body, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "gptq strip-major decode launch (was gptq_init() called on this device?)");
     return GPTQ_OK;
 }
 
-static int forward_impl(const gptq_layer_t* L, const void* x, void* out, int M, const WsView& wv, void* stream,
-                        const gptq_tuning_t* tune) {
-    int rc = check_layer(L);
-    if (rc) return rc;
-    const size_t have = wv.header ? WS_HEADER_BYTES + wv.body_bytes : (size_t)0;
-    if (L->epilogue == GPTQ_EPI_NONE) {
-        const gptq_layer_t* one[1] = {L};
-        TiledPlan tp;
-        if (want_tiled(one, 1, M, tune, &tp)) {
-            rc = check_io(x, out, M);
-            if (rc) return rc;
-            void* outs[1] = {out};
-            return tiled_call(one, 1, x, outs, M, wv, stream, tune, &tp);
-        }
-        if (tune && tune->path == 8)
-            return fail(GPTQ_ERR_UNSUPPORTED, "tuning.path = 8: the decode-copy kernel needs M <= 8 and a plain or re-sequenced act-order 3/4/8-bit fp16/bf16 layer that carries qweight_tiled / qconst_tiled "
-                                              "(gptq_prepack_decode; tiled_cols = %d)", GPTQ_STRIP_COLS);
-    }
-    if (tiled_pair_call(L, M, tune)) {                                            // SiLU * mul as the epilogue of the decode-copy kernel (round 5)
-        rc = check_io(x, out, M);
-        if (rc) return rc;
-        const gptq_layer_t* one[1] = {L};
-        void* outs[1] = {out};
-        return tiled_call(one, 1, x, outs, M, wv, stream, tune);
-    }
-    if (L->epilogue != GPTQ_EPI_NONE && !fused_epilogue_ok(L, M, tune)) {
-        rc = check_io(x, out, M);
-        if (rc) return rc;
-        const size_t yb = epi_scratch_bytes(L, M);
-        if (wv.body_bytes < yb)
-            return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", gptq_workspace_bytes_ex(L, M, tune), have);
-        // y = [gate | up] at the front of the body; the inner call gets the SAME zeroed ticket header and the body behind y (a header carved
-        // out of the body would sit on whatever an earlier, larger call left there: its tickets would never reach ksplit - 1)
-        gptq_layer_t Lc = *L;
-        Lc.epilogue = GPTQ_EPI_NONE;
-        gptq_tuning_t local;
-        rc = forward_impl(&Lc, x, wv.body, M, WsView{wv.header, (char*)wv.body + yb, wv.body_bytes - yb}, stream, inner_tuning(L, M, tune, &local));
-        if (rc) return rc;
-        hipError_t e = launch_silu_mul(wv.body, out, M, L->N, L->dtype, (hipStream_t)stream);
-        if (e != hipSuccess) return hip_fail(e, "silu_mul launch");
-        return GPTQ_OK;
-    }
-    if (want_stream(L, M, tune)) {
-        rc = check_io(x, out, M);
-        if (rc) return rc;
-        const gptq_layer_t* one[1] = {L};
-        void* outs[1] = {out};
-        return stream_call(one, 1, plan_stream(one, 1, M, tune), x, outs, M, wv, stream);
-    }
-    {
-        gptq_layer_t P;
-        if (want_stream_seq(L, M, tune, &P)) {
-            rc = check_io(x, out, M);
-            if (rc) return rc;
-            const gptq_layer_t* one[1] = {&P};
-            void* outs[1] = {out};
-            const StreamPlan sp = plan_stream(one, 1, M, nullptr);
+// One routed call on the layer its route's kind applies to (the layer itself, or `plain` inside an unfused epilogue).
+static int forward_routed(const ForwardRoute& r, const gptq_layer_t* L, const void* x, void* out, int M, const WsView& wv, void* stream, const gptq_tuning_t* tune) {
+    if (r.declined) return route_decline(r);
+    if (int rc = check_io(x, out, M)) return rc;
+    const gptq_layer_t* one[1] = {r.kind == ROUTE_STREAM_SEQ ? &r.seq : L};
+    void* outs[1] = {out};
+    switch (r.kind) {
+        case ROUTE_TILED:
+        case ROUTE_TILED_PAIR: return tiled_call(one, 1, r.tp, x, outs, M, wv, stream);
+        case ROUTE_STREAM: return stream_call(one, 1, r.sp, x, outs, M, wv, stream);
+        case ROUTE_STREAM_SEQ: {
             const size_t xb = xperm16_bytes(L, M);
-            if (wv.body_bytes < xb + sp.partial_bytes)
-                return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", WS_HEADER_BYTES + xb + sp.partial_bytes, have);
+            if (int rc = need_body(wv, xb + r.sp.partial_bytes)) return rc;
             hipError_t e = launch_permute_columns(x, L->perm, M, L->K, L->dtype, wv.body, (hipStream_t)stream);
             if (e != hipSuccess) return hip_fail(e, "gptq_permute_columns launch");
-            e = launch_stream(one, sp, wv.body, outs, M, wv.header, (char*)wv.body + xb, (hipStream_t)stream);
+            e = launch_stream(one, r.sp, wv.body, outs, M, wv.header, (char*)wv.body + xb, (hipStream_t)stream);
             if (e != hipSuccess) return hip_fail(e, "gptq streamed GEMV launch (was gptq_init() called on this device?)");
             return GPTQ_OK;
         }
+        case ROUTE_GEMM: return gemm_core(L, r.gp, x, out, M, wv, stream);
+        case ROUTE_GEMV: return gemv_core(L, r.vp, x, out, M, wv, stream, tune);
     }
-    if (tune && tune->path == 6)
-        return fail(GPTQ_ERR_UNSUPPORTED, "tuning.path = 6: the streamed GEMV needs M <= 4, a plain 4-bit fp16/bf16 layer (no act-order, no epilogue) "
-                                          "and a launch shape with rows-per-lane in {2, 4, 8} dividing the rows of a group");
-    if (want_gemm(L, M, tune)) return gemm_core(L, x, out, M, wv, stream, tune);
-    return gemv_core(L, x, out, M, wv, stream, tune);
+    return fail(GPTQ_ERR_UNSUPPORTED, "unknown route %d", (int)r.kind);
+}
+
+static int forward_impl(const gptq_layer_t* L, const void* x, void* out, int M, const WsView& wv, void* stream, const gptq_tuning_t* tune) {
+    if (int rc = check_layer(L)) return rc;
+    const ForwardRoute r = route_forward(L, M, tune);
+    if (!r.unfused_epilogue) return forward_routed(r, L, x, out, M, wv, stream, tune);
+    if (int rc = check_io(x, out, M)) return rc;
+    const size_t yb = r.epi_bytes;
+    if (wv.body_bytes < yb)
+        return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", gptq_workspace_bytes_ex(L, M, tune), wv.header ? WS_HEADER_BYTES + wv.body_bytes : (size_t)0);
+    // y = [gate | up] at the front of the body; the inner call gets the SAME zeroed ticket header and the body behind y (a header carved
+    // out of the body would sit on whatever an earlier, larger call left there: its tickets would never reach ksplit - 1)
+    if (int rc = forward_routed(r, &r.plain, x, wv.body, M, WsView{wv.header, (char*)wv.body + yb, wv.body_bytes - yb}, stream, r.tuning(tune))) return rc;
+    hipError_t e = launch_silu_mul(wv.body, out, M, L->N, L->dtype, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "silu_mul launch");
+    return GPTQ_OK;
 }
 
 int gptq_forward_ex(const gptq_layer_t* L, const void* x, void* out, int M, void* ws, size_t ws_bytes, void* stream,
@@ -500,12 +507,12 @@ size_t gptq_workspace_bytes_multi(const gptq_layer_t* const* layers, int n_layer
 
 // Batched decode of 2..4 layers sharing x in ONE gemm_stream64_kernel launch: by the planner's measured preference, or forced
 // with tuning.path = 3 and tuning.reserved[2] = 4.
-static bool want_stream64_multi(const gptq_layer_t* const* layers, int n, int M, const gptq_tuning_t* t) {
+static bool want_stream64_multi(const gptq_layer_t* const* layers, int n, int M, const gptq_tuning_t* t, Stream64Plan* plan_out) {
     if (n < 2 || n > 4 || M > 64) return false;
     const bool forced = t && t->path == 3 && t->reserved[2] == 4;
     if (t && t->path != 0 && !forced) return false;
     if (M <= 2 && !forced) return false;                         // up to 2 rows: the streamed GEMV (or layer by layer)
-    const Stream64Plan sp = plan_stream64(layers, n, M, t);
+    const Stream64Plan& sp = *plan_out = plan_stream64(layers, n, M, t);
     // 3..4 rows: only one unsplit round of 16-wave workgroups beats the streamed GEMV (tools/misc_bench.py, us, GEMV at M = 4 against this kernel
     // at M = 8: q|k|v, 192 strips: 12.0 against 11.2; gate|up, 344 strips in 8-wave workgroups: 17.5 against 18.8)
     if (M <= 4 && !forced && !(sp.ok && sp.ksplit == 1 && sp.strips_total <= 256)) return false;
@@ -514,11 +521,11 @@ static bool want_stream64_multi(const gptq_layer_t* const* layers, int n, int M,
 
 // 17 .. 128 rows, 2..4 layers sharing x in ONE gemm_mid_kernel launch: by the planner's measured preference, or forced with tuning.path = 3 and
 // tuning.reserved[2] = 5.
-static bool want_mid_multi(const gptq_layer_t* const* layers, int n, int M, const gptq_tuning_t* t) {
+static bool want_mid_multi(const gptq_layer_t* const* layers, int n, int M, const gptq_tuning_t* t, MidPlan* plan_out) {
     if (n < 2 || n > 4 || M > 256) return false;
     const bool forced = t && t->path == 3 && t->reserved[2] == 5;
     if (t && t->path != 0 && !forced) return false;
-    const MidPlan mp = plan_mid(layers, n, M, t);
+    const MidPlan& mp = *plan_out = plan_mid(layers, n, M, t);
     return mp.ok && (mp.pays || forced);
 }
 
@@ -532,40 +539,81 @@ static bool separate_panels_pay(const gptq_layer_t* const* layers, int n, int M)
     for (int i = 0; i < n; ++i) {
         const size_t kn = (size_t)layers[i]->K * layers[i]->N;
         all += kn;
-        if (layers[i]->epilogue == GPTQ_EPI_NONE && want_gemm(layers[i], M, nullptr) && panel_pays_filled(*layers[i], M)) paneled += kn;
+        if (layers[i]->epilogue == GPTQ_EPI_NONE && route_forward(layers[i], M, nullptr).kind == ROUTE_GEMM && panel_pays_filled(*layers[i], M)) paneled += kn;      // (33+ rows: the GEMM step is the first that can hit)
     }
     return paneled * 4 >= all * 3;
+}
+
+// ---- the route of one layer-group call: to gptq_forward_multi_ex and gptq_workspace_bytes_multi_ex what route_forward is to the single-layer entry points ----
+enum MultiKind {
+    MULTI_TILED,          // ONE decode-copy launch over the strips of all layers (tp)
+    MULTI_ROWS,           // ONE gemm_rows.hip launch over the strip groups of all layers (rp); act-order layers of one order read one permuted x
+    MULTI_MID,            // ONE gemm_mid_kernel launch (mp)
+    MULTI_STREAM64,       // ONE gemm_stream64_kernel launch (s64)
+    MULTI_STREAM,         // ONE streamed-GEMV launch (sp)
+    MULTI_SHARED_PERM,    // a GEMM per layer (pls) behind ONE permuted x -- where the workspace that is passed fits every plan, else one by one
+    MULTI_ONE_BY_ONE,     // gptq_forward per layer
+};
+struct MultiRoute {
+    MultiKind kind;
+    int declined = 0;     // a forced route the group does not fit (multi_decline): tuning.path 8 / 6, or reserved[2] = 4 / 5 of path 3; the query answers with the rest of the ladder
+    TiledPlan tp; RowsPlan rp; MidPlan mp; Stream64Plan s64; StreamPlan sp; GemmPlan pls[4];      // the sub-plan(s) of `kind`
+    size_t body = 0;      // bytes behind the ticket header (MULTI_SHARED_PERM / MULTI_ONE_BY_ONE: every layer's own query)
+    bool hit(MultiKind k, size_t need) { kind = k; body = need; return true; }
+};
+static MultiRoute route_forward_multi(const gptq_layer_t* const* layers, int n_layers, int M, const gptq_tuning_t* tune) {
+    MultiRoute r;
+    // decode rows on layers that carry the decode copy: one launch over the strips of all layers (tools/tiled_sweep.py, M = 4, us: q|k|v 8.6 against
+    // 11.1 for the batched-decode kernel, gate|up 12.9 against 18.9)
+    // (no byte cap on the group for this kernel -- multi_preferred's 128 MB was measured on the round-2 kernels: 70B gate|up, 235 MB, M = 1 / 4 one by one
+    // 48.5 / 57.3 us, ONE decode-copy launch 42.2 / 50.9: profiles/r06_multi_geom_sweep.log)
+    if (want_tiled(layers, n_layers, M, tune, &r.tp) && (n_layers >= 2 || (tune && tune->path == 8)) && r.hit(MULTI_TILED, r.tp.partial_bytes)) return r;
+    if (tune && tune->path == 8) r.declined = 8;
+    // 5 .. 128 rows on layers that carry the decode copy: the exchange-free kernel over the strip groups of all layers (gemm_rows.hip); act-order layers of
+    // ONE order (the same perm pointer: QuantLinear.share_act_order) read one permuted x -- and nothing else is staged
+    const bool rows_forced = tune && tune->path == 3 && tune->reserved[3] == GPTQ_LAB_VARIANT_ROWS_ON && rows_multi_ok(layers, n_layers, M);      // lab knob 50
+    const bool separate = !tune && separate_panels_pay(layers, n_layers, M);
+    if (n_layers >= 2 && (rows_forced || (!tune && !separate && rows_multi_pays(layers, n_layers, M))) && (r.rp = plan_rows_multi(layers, n_layers, M, nullptr)).ok &&
+        r.hit(MULTI_ROWS, layers[0]->g_idx ? xperm16_bytes(layers[0], M) : 0))
+        return r;
+    if (!separate && want_mid_multi(layers, n_layers, M, tune, &r.mp) && r.hit(MULTI_MID, r.mp.partial_bytes)) return r;
+    if (!separate && want_stream64_multi(layers, n_layers, M, tune, &r.s64) && r.hit(MULTI_STREAM64, r.s64.partial_bytes)) return r;
+    if (n_layers <= 4 && M <= 4) {
+        if ((r.sp = plan_stream(layers, n_layers, M, tune)).ok && multi_preferred(layers, n_layers, M) && r.hit(MULTI_STREAM, r.sp.partial_bytes)) return r;
+        if (tune && tune->path == 6) r.declined = 6;
+    }
+    if (tune && tune->path == 3 && (tune->reserved[2] == 4 || tune->reserved[2] == 5)) r.declined = tune->reserved[2];
+    // Act-order layers that share ONE perm -- q / k / v and gate / up of a GPTQ checkpoint do: the activation order comes from the Hessian of the
+    // layers' common input (the reference's fused q/k/v caller relies on it: fused_llama_attn.py:188 hands the kernels q_proj's order for all three) --
+    // read ONE permuted x: the first layer's GEMM call permutes into the head of the workspace, the others find it there.  The caller says so by
+    // passing the same `perm` pointer (QuantLinear.share_act_order / forward_multi do that once the g_idx tensors compared equal).
+    bool shared = n_layers >= 2 && n_layers <= 4 && !tune && layers[0]->perm && layers[0]->qweight_seq && layers[0]->g_idx;
+    for (int i = 0; shared && i < n_layers; ++i) {
+        const gptq_layer_t* L = layers[i];
+        const GemmPlan& pl = r.pls[i];
+        shared = L->perm == layers[0]->perm && L->qweight_seq && L->g_idx && L->epilogue == GPTQ_EPI_NONE && L->K == layers[0]->K &&
+                 L->dtype == layers[0]->dtype && L->dtype != GPTQ_F32 && want_gemm(L, M, nullptr, &r.pls[i]) &&
+                 pl.supported && pl.use_seq && pl.kernel != GEMM_F32 && pl.xslot == r.pls[0].xslot && pl.xnat == r.pls[0].xnat && pl.xperm_bytes == r.pls[0].xperm_bytes;
+    }
+    r.kind = shared ? MULTI_SHARED_PERM : MULTI_ONE_BY_ONE;      // one by one: anything the one-launch kernels do not cover, the same result layer by layer
+    return r;
+}
+static int multi_decline(const MultiRoute& r) {
+    switch (r.declined) {
+        case 8: return fail(GPTQ_ERR_UNSUPPORTED, "tuning.path = 8: these layers do not fit one decode-copy launch (1..4 layers of one packing with qweight_tiled, all plain or all act-order, M <= 8)");
+        case 6: return fail(GPTQ_ERR_UNSUPPORTED, "tuning.path = 6: these layers / this launch shape do not fit the streamed GEMV");
+        case 4: return fail(GPTQ_ERR_UNSUPPORTED, "tuning.path = 3 / reserved[2] = 4: these layers do not fit one batched-decode launch (2..4 plain 4-bit layers, M <= 64)");
+        default: return fail(GPTQ_ERR_UNSUPPORTED, "tuning.path = 3 / reserved[2] = 5: these layers do not fit one gemm_mid_kernel launch (2..4 plain 4-bit layers, N %% 64 == 0, M <= 256)");
+    }
 }
 
 size_t gptq_workspace_bytes_multi_ex(const gptq_layer_t* const* layers, int n_layers, int M, const gptq_tuning_t* tune) {
     if (!layers || n_layers <= 0 || M <= 0) return 0;
     for (int i = 0; i < n_layers; ++i)
         if (check_layer(layers[i]) != GPTQ_OK) return 0;
+    const MultiRoute r = route_forward_multi(layers, n_layers, M, tune);
+    if (r.kind != MULTI_SHARED_PERM && r.kind != MULTI_ONE_BY_ONE) return r.body ? WS_HEADER_BYTES + r.body : 0;
     size_t need = 0;
-    if (want_tiled(layers, n_layers, M, tune) && (n_layers >= 2 || (tune && tune->path == 8))) {
-        const TiledPlan tp = plan_tiled(layers, n_layers, M, tune);
-        return tp.partial_bytes ? WS_HEADER_BYTES + tp.partial_bytes : 0;
-    }
-    const bool separate = !tune && separate_panels_pay(layers, n_layers, M);
-    if (!separate && n_layers >= 2 && ((tune && tune->path == 3 && tune->reserved[3] == GPTQ_LAB_VARIANT_ROWS_ON && rows_multi_ok(layers, n_layers, M)) || (!tune && rows_multi_pays(layers, n_layers, M))) &&
-        plan_rows_multi(layers, n_layers, M, nullptr).ok)
-        return layers[0]->g_idx ? WS_HEADER_BYTES + xperm16_bytes(layers[0], M) : 0;      // gemm_rows.hip over all layers: nothing but the permuted x of act-order layers
-    if (separate) {
-        for (int i = 0; i < n_layers; ++i) need = std::max(need, gptq_workspace_bytes_ex(layers[i], M, nullptr));
-        return need;
-    }
-    if (want_mid_multi(layers, n_layers, M, tune)) {
-        const MidPlan mp = plan_mid(layers, n_layers, M, tune);
-        return mp.partial_bytes ? WS_HEADER_BYTES + mp.partial_bytes : 0;
-    }
-    if (want_stream64_multi(layers, n_layers, M, tune)) {
-        const Stream64Plan sp = plan_stream64(layers, n_layers, M, tune);
-        return sp.partial_bytes ? WS_HEADER_BYTES + sp.partial_bytes : 0;
-    }
-    if (n_layers <= 4) {
-        const StreamPlan sp = plan_stream(layers, n_layers, M, tune);
-        if (sp.ok && multi_preferred(layers, n_layers, M)) return sp.partial_bytes ? WS_HEADER_BYTES + sp.partial_bytes : 0;
-    }
     for (int i = 0; i < n_layers; ++i) need = std::max(need, gptq_workspace_bytes_ex(layers[i], M, nullptr));
     return need;
 }
@@ -587,86 +635,46 @@ static int forward_multi_core(const gptq_layer_t* const* layers, int n_layers, c
         if (layers[i]->K != layers[0]->K) return fail(GPTQ_ERR_SHAPE, "layers of one gptq_forward_multi call read the same x: in_features %d != %d", layers[i]->K, layers[0]->K);
         if (layers[i]->dtype != layers[0]->dtype) return fail(GPTQ_ERR_UNSUPPORTED, "layers of one gptq_forward_multi call share the dtype of x");
     }
-    // decode rows on layers that carry the decode copy: one launch over the strips of all layers (tools/tiled_sweep.py, M = 4, us: q|k|v 8.6 against
-    // 11.1 for the batched-decode kernel, gate|up 12.9 against 18.9)
-    {
-        TiledPlan tp;
-        // (no byte cap on the group for this kernel -- multi_preferred's 128 MB was measured on the round-2 kernels: 70B gate|up, 235 MB, M = 1 / 4 one by one
-        // 48.5 / 57.3 us, ONE decode-copy launch 42.2 / 50.9: profiles/r06_multi_geom_sweep.log)
-        if (want_tiled(layers, n_layers, M, tune, &tp) && (n_layers >= 2 || (tune && tune->path == 8)))
-            return tiled_call(layers, n_layers, x, outs, M, wv, stream, tune, &tp);
-    }
-    if (tune && tune->path == 8) return fail(GPTQ_ERR_UNSUPPORTED, "tuning.path = 8: these layers do not fit one decode-copy launch (1..4 layers of one packing with qweight_tiled, all plain or all act-order, M <= 8)");
-    // 5 .. 128 rows on layers that carry the decode copy: the exchange-free kernel over the strip groups of all layers (gemm_rows.hip); act-order layers of
-    // ONE order (the same perm pointer: QuantLinear.share_act_order) read one permuted x
-    const bool rows_forced = tune && tune->path == 3 && tune->reserved[3] == GPTQ_LAB_VARIANT_ROWS_ON && rows_multi_ok(layers, n_layers, M);      // lab knob 50
-    const bool separate = !tune && separate_panels_pay(layers, n_layers, M);
-    if (n_layers >= 2 && (rows_forced || (!tune && !separate && rows_multi_pays(layers, n_layers, M)))) {
-        const RowsPlan rp = plan_rows_multi(layers, n_layers, M, nullptr);
-        if (rp.ok) {
+    const MultiRoute r = route_forward_multi(layers, n_layers, M, tune);
+    if (r.declined) return multi_decline(r);
+    if (r.kind == MULTI_ROWS || r.kind == MULTI_MID || r.kind == MULTI_STREAM64)
+        if (int rc = need_body(wv, r.body)) return rc;
+    hipError_t e;
+    switch (r.kind) {
+        case MULTI_TILED: return tiled_call(layers, n_layers, r.tp, x, outs, M, wv, stream);
+        case MULTI_ROWS: {
             const void* xin = x;
             if (layers[0]->g_idx) {
-                const size_t xb = xperm16_bytes(layers[0], M);
-                if (wv.body_bytes < xb) return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", WS_HEADER_BYTES + xb, wv.header ? WS_HEADER_BYTES + wv.body_bytes : (size_t)0);
-                hipError_t e = launch_permute_rows16(x, layers[0]->perm, M, layers[0]->K, wv.body, (hipStream_t)stream, false);
+                e = launch_permute_rows16(x, layers[0]->perm, M, layers[0]->K, wv.body, (hipStream_t)stream, false);
                 if (e != hipSuccess) return hip_fail(e, "gptq x permute launch");
                 xin = wv.body;
             }
-            hipError_t e = launch_gemm_rows_multi(layers, n_layers, rp, xin, outs, M, (hipStream_t)stream);
+            e = launch_gemm_rows_multi(layers, n_layers, r.rp, xin, outs, M, (hipStream_t)stream);
             if (e != hipSuccess) return hip_fail(e, "gptq batched-decode launch (gemm_rows; was gptq_init() called on this device?)");
             return GPTQ_OK;
         }
-    }
-    if (!separate && want_mid_multi(layers, n_layers, M, tune)) {
-        const MidPlan mp = plan_mid(layers, n_layers, M, tune);
-        if (mp.partial_bytes > 0 && wv.body_bytes < mp.partial_bytes)
-            return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", WS_HEADER_BYTES + mp.partial_bytes, wv.header ? WS_HEADER_BYTES + wv.body_bytes : (size_t)0);
-        hipError_t e = launch_mid(layers, mp, x, outs, M, wv.header, wv.body, nullptr, (hipStream_t)stream);
-        if (e != hipSuccess) return hip_fail(e, "gptq 17..128-row launch (needs > 64 KiB of LDS: was gptq_init() called on this device?)");
-        return GPTQ_OK;
-    }
-    if (!separate && want_stream64_multi(layers, n_layers, M, tune)) {
-        const Stream64Plan sp = plan_stream64(layers, n_layers, M, tune);
-        if (sp.partial_bytes > 0 && wv.body_bytes < sp.partial_bytes)
-            return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", WS_HEADER_BYTES + sp.partial_bytes, wv.header ? WS_HEADER_BYTES + wv.body_bytes : (size_t)0);
-        hipError_t e = launch_stream64(layers, sp, x, outs, M, wv.header, wv.body, nullptr, (hipStream_t)stream);
-        if (e != hipSuccess) return hip_fail(e, "gptq batched-decode launch (needs > 64 KiB of LDS: was gptq_init() called on this device?)");
-        return GPTQ_OK;
-    }
-    if (n_layers <= 4 && M <= 4) {
-        const StreamPlan sp = plan_stream(layers, n_layers, M, tune);
-        if (sp.ok && multi_preferred(layers, n_layers, M)) return stream_call(layers, n_layers, sp, x, outs, M, wv, stream);
-        if (tune && tune->path == 6) return fail(GPTQ_ERR_UNSUPPORTED, "tuning.path = 6: these layers / this launch shape do not fit the streamed GEMV");
-    }
-    if (tune && tune->path == 3 && tune->reserved[2] == 4)
-        return fail(GPTQ_ERR_UNSUPPORTED, "tuning.path = 3 / reserved[2] = 4: these layers do not fit one batched-decode launch (2..4 plain 4-bit layers, M <= 64)");
-    if (tune && tune->path == 3 && tune->reserved[2] == 5)
-        return fail(GPTQ_ERR_UNSUPPORTED, "tuning.path = 3 / reserved[2] = 5: these layers do not fit one gemm_mid_kernel launch (2..4 plain 4-bit layers, N %% 64 == 0, M <= 256)");
-    // Act-order layers that share ONE perm -- q / k / v and gate / up of a GPTQ checkpoint do: the activation order comes from the Hessian of the
-    // layers' common input (the reference's fused q/k/v caller relies on it: fused_llama_attn.py:188 hands the kernels q_proj's order for all three) --
-    // read ONE permuted x: the first layer's GEMM call permutes into the head of the workspace, the others find it there.  The caller says so by
-    // passing the same `perm` pointer (QuantLinear.share_act_order / forward_multi do that once the g_idx tensors compared equal).
-    if (n_layers >= 2 && !tune && layers[0]->perm && layers[0]->qweight_seq && layers[0]->g_idx) {
-        GemmPlan pls[4];
-        bool shared = n_layers <= 4;
-        for (int i = 0; shared && i < n_layers; ++i) {
-            const gptq_layer_t* L = layers[i];
-            shared = L->perm == layers[0]->perm && L->qweight_seq && L->g_idx && L->epilogue == GPTQ_EPI_NONE && L->K == layers[0]->K &&
-                     L->dtype == layers[0]->dtype && L->dtype != GPTQ_F32 && want_gemm(L, M, nullptr);
-            if (!shared) break;
-            pls[i] = plan_gemm(*L, M, nullptr);
-            shared = pls[i].supported && pls[i].use_seq && !pls[i].f32 && pls[i].xslot == pls[0].xslot && pls[i].xnat == pls[0].xnat && pls[i].xperm_bytes == pls[0].xperm_bytes &&
-                     pls[i].workspace_bytes <= wv.body_bytes;
-        }
-        if (shared) {
+        case MULTI_MID:
+            e = launch_mid(layers, r.mp, x, outs, M, wv.header, wv.body, nullptr, (hipStream_t)stream);
+            if (e != hipSuccess) return hip_fail(e, "gptq 17..128-row launch (needs > 64 KiB of LDS: was gptq_init() called on this device?)");
+            return GPTQ_OK;
+        case MULTI_STREAM64:
+            e = launch_stream64(layers, r.s64, x, outs, M, wv.header, wv.body, nullptr, (hipStream_t)stream);
+            if (e != hipSuccess) return hip_fail(e, "gptq batched-decode launch (needs > 64 KiB of LDS: was gptq_init() called on this device?)");
+            return GPTQ_OK;
+        case MULTI_STREAM: return stream_call(layers, n_layers, r.sp, x, outs, M, wv, stream);
+        case MULTI_SHARED_PERM: {
+            bool fits = true;
+            for (int i = 0; i < n_layers; ++i) fits = fits && r.pls[i].workspace_bytes <= wv.body_bytes;
+            if (!fits) break;
             for (int i = 0; i < n_layers; ++i) {
-                hipError_t e = launch_gemm(*layers[i], pls[i], x, outs[i], M, wv.header, wv.body, (hipStream_t)stream, i > 0);
+                e = launch_gemm(*layers[i], r.pls[i], x, outs[i], M, wv.header, wv.body, (hipStream_t)stream, i > 0);
                 if (e != hipSuccess) return hip_fail(e, "gptq_gemm launch (shared permuted x)");
             }
             return GPTQ_OK;
         }
+        case MULTI_ONE_BY_ONE: break;
     }
-    for (int i = 0; i < n_layers; ++i) {           // anything the one-launch kernel does not cover: the same result, layer by layer
+    for (int i = 0; i < n_layers; ++i) {
         int rc = forward_impl(layers[i], x, outs[i], M, wv, stream, nullptr);
         if (rc) return rc;
     }
@@ -714,15 +722,13 @@ size_t gptq_workspace_bytes_mlp_ex(const gptq_layer_t* gate, const gptq_layer_t*
 
 // down of gptq_mlp_forward: does its call at M rows run an MFMA GEMM that reads x permuted in NATURAL order of its re-sequenced rows (GemmPlan.xnat)?  Then the
 // SiLU * mul pass writes that permuted x itself.  (Decode rows gather inside the kernel, fp32 and the checkpoint-row kernels have their own orders: unchanged.)
-static bool mlp_fused_permute(const gptq_layer_t* down, int M, const gptq_tuning_t* tune) {
+// r: route_forward(down, M, nullptr) -- the GEMM plan the fused pass feeds is r.gp
+static bool mlp_fused_permute(const gptq_layer_t* down, int M, const gptq_tuning_t* tune, const ForwardRoute& r) {
     if (tune && tune->reserved[3] == GPTQ_LAB_VARIANT_MLP_TWO_PASSES) return false;      // lab (bench.py: the two passes of round 5, interleaved with the default)
     if (!down->g_idx || !down->perm || !down->qweight_seq || down->epilogue != GPTQ_EPI_NONE) return false;
     if (!silu_mul2_permute_ok(down->K, down->dtype)) return false;
-    const gptq_layer_t* one[1] = {down};
-    gptq_layer_t P;
-    if (want_tiled(one, 1, M, nullptr) || want_stream(down, M, nullptr) || want_stream_seq(down, M, nullptr, &P) || !want_gemm(down, M, nullptr)) return false;      // (forward_impl's order)
-    const GemmPlan pl = plan_gemm(*down, M, nullptr);
-    return pl.supported && pl.use_seq && pl.xnat && !pl.f32 && pl.xperm_bytes > 0;
+    const GemmPlan& pl = r.gp;
+    return r.kind == ROUTE_GEMM && pl.supported && pl.use_seq && pl.xnat && pl.kernel != GEMM_F32 && pl.xperm_bytes > 0;
 }
 
 int gptq_mlp_forward(const gptq_layer_t* gate, const gptq_layer_t* up, const gptq_layer_t* down, const void* x, void* out, int M,
@@ -754,8 +760,9 @@ int gptq_mlp_forward_ex(const gptq_layer_t* gate, const gptq_layer_t* up, const 
     if ((rc = forward_multi_core(gu, 2, x, outs, M, inner, stream, nullptr))) return rc;
     // An act-order `down` whose kernel reads x permuted in natural order (the decode-copy GEMMs: panel / rows / stream-K / wide tiles): SiLU * mul and that
     // permute are ONE pass into the spot down's own pre-pass would have filled (round 6; the reference's fused MLP, fused_llama_mlp.py:131-306)
-    if (mlp_fused_permute(down, M, tune)) {
-        const GemmPlan pl = plan_gemm(*down, M, nullptr);
+    const ForwardRoute rd = route_forward(down, M, nullptr);
+    if (mlp_fused_permute(down, M, tune, rd)) {
+        const GemmPlan& pl = rd.gp;
         if (pl.workspace_bytes > inner.body_bytes)
             return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", gptq_workspace_bytes_mlp_ex(gate, up, down, M, tune), have);
         hipError_t e = launch_silu_mul2_permute(hg, hu, down->perm, M, down->K, down->dtype, inner.body, (hipStream_t)stream);
@@ -766,7 +773,7 @@ int gptq_mlp_forward_ex(const gptq_layer_t* gate, const gptq_layer_t* up, const 
     }
     hipError_t e = launch_silu_mul2(hg, hu, hg, (size_t)M * gate->N, gate->dtype, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "silu_mul launch");
-    return forward_impl(down, hg, out, M, inner, stream, nullptr);
+    return forward_routed(rd, down, hg, out, M, inner, stream, nullptr);      // (check_mlp: down has no epilogue)
 }
 
 int gptq_describe_mlp_plan(const gptq_layer_t* gate, const gptq_layer_t* up, const gptq_layer_t* down, int M, const gptq_tuning_t* tune, char* out,
@@ -776,10 +783,10 @@ int gptq_describe_mlp_plan(const gptq_layer_t* gate, const gptq_layer_t* up, con
     int rc = check_mlp(gate, up, down);
     if (rc) return rc;
     if (M <= 0) return fail(GPTQ_ERR_SHAPE, "M must be > 0, got %d", M);
-    if (mlp_fused_permute(down, M, tune)) snprintf(out, out_bytes, "kernel=unfused launches=3 steps=forward_multi(gate,up)|silu_mul+permute|gemm(down) down_permute=fused");
+    const ForwardRoute rd = route_forward(down, M, nullptr);
+    if (mlp_fused_permute(down, M, tune, rd)) snprintf(out, out_bytes, "kernel=unfused launches=3 steps=forward_multi(gate,up)|silu_mul+permute|gemm(down) down_permute=fused");
     else {
-        const gptq_layer_t* one[1] = {down};
-        const char* dp = !down->g_idx ? "none" : (want_tiled(one, 1, M, nullptr) ? "in_kernel" : "own_pass");      // (decode rows: the decode kernel gathers x through perm itself)
+        const char* dp = !down->g_idx ? "none" : (rd.kind == ROUTE_TILED ? "in_kernel" : "own_pass");      // (decode rows: the decode kernel gathers x through perm itself)
         snprintf(out, out_bytes, "kernel=unfused launches=3+ steps=forward_multi(gate,up)|silu_mul|forward(down) down_permute=%s", dp);
     }
     return GPTQ_OK;
@@ -1660,48 +1667,37 @@ int gptq_describe_plan(const gptq_layer_t* L, int M, const gptq_tuning_t* tune, 
     if (rc) return rc;
     if (M <= 0) return fail(GPTQ_ERR_SHAPE, "M must be > 0, got %d", M);
     if (tune && (tune->path == 2 || tune->path == 4)) return fail(GPTQ_ERR_UNSUPPORTED, "tuning.path = %d was retired in round 6", tune->path);
-    if (tiled_pair_call(L, M, tune)) {
-        const gptq_layer_t* one[1] = {L};
-        const TiledPlan tp = plan_tiled(one, 1, M, tune);
-        snprintf(out, out_bytes, "path=gemv kernel=strips ln=4 waves=%d u=%d ksplit=%d mt=%d strips=%d pair=1 perm=0 epilogue=fused aligned=%d", tp.waves, tp.u, tp.ksplit, tp.mt,
-                 tp.strips_total, tp.aligned ? 1 : 0);
-        return GPTQ_OK;
-    }
-    const bool unfused_epilogue = L->epilogue != GPTQ_EPI_NONE && !fused_epilogue_ok(L, M, tune);
-    gptq_layer_t Lc = *L;
-    gptq_tuning_t local;
-    if (unfused_epilogue) {
-        Lc.epilogue = GPTQ_EPI_NONE;
-        tune = inner_tuning(L, M, tune, &local);
-    }
-    gptq_layer_t Pseq;
-    const gptq_layer_t* one_t[1] = {&Lc};
-    if (!unfused_epilogue && Lc.epilogue == GPTQ_EPI_NONE && want_tiled(one_t, 1, M, tune)) {
-        const TiledPlan tp = plan_tiled(one_t, 1, M, tune);
-        snprintf(out, out_bytes, "path=gemv kernel=strips ln=4 waves=%d u=%d ksplit=%d mt=%d strips=%d pair=0 perm=0 epilogue=none aligned=%d", tp.waves, tp.u, tp.ksplit, tp.mt,
-                 tp.strips_total, tp.aligned ? 1 : 0);
-    } else if (!unfused_epilogue && want_stream_seq(L, M, tune, &Pseq)) {
-        const gptq_layer_t* one[1] = {&Pseq};
-        const StreamPlan sp = plan_stream(one, 1, M, nullptr);
-        snprintf(out, out_bytes, "path=gemv kernel=stream ln=%d waves=%d u=%d ksplit=%d mt=%d strips=%d pair=0 perm=2 epilogue=none", sp.ln, sp.waves,
-                 sp.u, sp.ksplit, sp.mt, sp.strips_total);
-    } else if (want_stream(&Lc, M, tune)) {
-        const gptq_layer_t* one[1] = {&Lc};
-        const StreamPlan sp = plan_stream(one, 1, M, tune);
-        snprintf(out, out_bytes, "path=gemv kernel=stream ln=%d waves=%d u=%d ksplit=%d mt=%d strips=%d pair=0 perm=0 epilogue=none", sp.ln, sp.waves,
-                 sp.u, sp.ksplit, sp.mt, sp.strips_total);
-    } else if (want_gemm(&Lc, M, tune)) {
-        const GemmPlan g = plan_gemm(Lc, M, tune);
-        const char* kern = g.f32 ? "f32_mfma" : g.rows ? "rows" : g.panel ? "panel" : g.wsk ? "wide_sk" : g.wide ? (g.wide_tiled ? "wide_copy" : "wide") : g.mid ? "mid" : (g.stream64 ? "stream64" : (g.strip16 ? "strip16" : (g.skinny ? "skinny64" : "tiled")));
-        snprintf(out, out_bytes, "path=gemm kernel=%s mt=%d bk=%d kg=%d ksplit=%d tiles=%dx%d tail=%d tail_slices=%d perm=%d dma=%d waves=%d u=%d epilogue=%s", kern, g.mt, g.bk,
-                 g.kg == 2 ? 2 : 1, g.ksplit, g.nbm, g.nbn, g.tail, g.tail ? (1 << g.tail_lg) : 1, g.use_seq ? 1 : 0, (g.glds || g.stream64 || g.mid) ? 1 : 0, g.waves, g.u,
-                 unfused_epilogue ? "separate" : "none");
-    } else {
-        const GemvPlan v = plan_gemv(Lc, M, tune);
-        const char* kern = v.mfma ? "mfma" : (v.mfmag ? "mfma_generic" : "generic");
-        snprintf(out, out_bytes, "path=gemv kernel=%s ln=%d waves=%d u=%d ksplit=%d mt=%d strips=%d pair=%d perm=%d epilogue=%s%s", kern, v.ln,
-                 v.waves, v.u, v.ksplit, v.mt, v.strips, v.pair ? 1 : 0, v.xperm ? 2 : (v.use_seq ? 1 : 0),
-                 v.pair ? "fused" : (unfused_epilogue ? "separate" : "none"), v.magic ? " deq=magic" : "");
+    const ForwardRoute r = route_forward(L, M, tune);
+    const char* separate = r.unfused_epilogue ? "separate" : "none";
+    switch (r.kind) {
+        case ROUTE_TILED:
+        case ROUTE_TILED_PAIR: {
+            const bool pair = r.kind == ROUTE_TILED_PAIR;
+            snprintf(out, out_bytes, "path=gemv kernel=strips ln=4 waves=%d u=%d ksplit=%d mt=%d strips=%d pair=%d perm=0 epilogue=%s aligned=%d", r.tp.waves, r.tp.u, r.tp.ksplit, r.tp.mt,
+                     r.tp.strips_total, pair ? 1 : 0, pair ? "fused" : separate, r.tp.aligned ? 1 : 0);
+            break;
+        }
+        case ROUTE_STREAM:
+        case ROUTE_STREAM_SEQ:
+            snprintf(out, out_bytes, "path=gemv kernel=stream ln=%d waves=%d u=%d ksplit=%d mt=%d strips=%d pair=0 perm=%d epilogue=none", r.sp.ln, r.sp.waves,
+                     r.sp.u, r.sp.ksplit, r.sp.mt, r.sp.strips_total, r.kind == ROUTE_STREAM_SEQ ? 2 : 0);      // ("none" also in front of a separate SiLU * mul pass: the string this kernel has always had)
+            break;
+        case ROUTE_GEMM: {
+            const GemmPlan& g = r.gp;
+            const char* kern = (g.kernel == GEMM_WIDE && g.wide_tiled) ? "wide_copy" : gemm_kernel_names[g.kernel];
+            snprintf(out, out_bytes, "path=gemm kernel=%s mt=%d bk=%d kg=%d ksplit=%d tiles=%dx%d tail=%d tail_slices=%d perm=%d dma=%d waves=%d u=%d epilogue=%s", kern, g.mt, g.bk,
+                     g.kg == 2 ? 2 : 1, g.ksplit, g.nbm, g.nbn, g.tail, g.tail ? (1 << g.tail_lg) : 1, g.use_seq ? 1 : 0,
+                     (g.glds || g.kernel == GEMM_STREAM64 || g.kernel == GEMM_MID) ? 1 : 0, g.waves, g.u, separate);
+            break;
+        }
+        case ROUTE_GEMV: {
+            const GemvPlan& v = r.vp;
+            const char* kern = v.mfma ? "mfma" : (v.mfmag ? "mfma_generic" : "generic");
+            snprintf(out, out_bytes, "path=gemv kernel=%s ln=%d waves=%d u=%d ksplit=%d mt=%d strips=%d pair=%d perm=%d epilogue=%s%s", kern, v.ln,
+                     v.waves, v.u, v.ksplit, v.mt, v.strips, v.pair ? 1 : 0, v.xperm ? 2 : (v.use_seq ? 1 : 0),
+                     v.pair ? "fused" : separate, v.magic ? " deq=magic" : "");
+            break;
+        }
     }
     return GPTQ_OK;
 }
@@ -1783,13 +1779,13 @@ int gptq_forward_scatter(const gptq_layer_t* L, const void* x, int M, const gptq
     if ((rc = check_peer_group(pg, M, L->dtype))) return rc;
     if (L->N != pg->N / pg->world) return fail(GPTQ_ERR_SHAPE, "the layer's out_features (%d) must be the rank's shard N / world = %d", L->N, pg->N / pg->world);
     const gptq_layer_t* one[1] = {L};
-    if (M > 4 || L->epilogue != GPTQ_EPI_NONE || L->g_idx || !want_tiled(one, 1, M, nullptr) || (plan_tiled(one, 1, M, nullptr).u != 2 && plan_tiled(one, 1, M, nullptr).u != 4))
+    const ForwardRoute r = route_forward(L, M, nullptr);
+    const TiledPlan& tp = r.tp;
+    if (M > 4 || L->epilogue != GPTQ_EPI_NONE || L->g_idx || r.kind != ROUTE_TILED || (tp.u != 2 && tp.u != 4))
         return fail(GPTQ_ERR_UNSUPPORTED, "gptq_forward_scatter: the fused scatter is the epilogue of the decode-copy kernel (M <= 4, a plain 3/4/8-bit fp16/bf16 "
                                           "layer that carries qweight_tiled / qconst_tiled); use gptq_forward + gptq_peer_scatter for this call");
     const WsView wv = split_ws(ws, ws_bytes);
-    const TiledPlan tp = plan_tiled(one, 1, M, nullptr);
-    if (tp.partial_bytes > 0 && wv.body_bytes < tp.partial_bytes)
-        return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", WS_HEADER_BYTES + tp.partial_bytes, wv.header ? WS_HEADER_BYTES + wv.body_bytes : (size_t)0);
+    if (int rc = need_body(wv, tp.partial_bytes)) return rc;
     void* outs[1] = {nullptr};                                  // the rank's own slice travels through its own exchange buffer like every peer's
     hipError_t e = launch_tiled(one, tp, x, outs, M, wv.header, wv.body, (hipStream_t)stream, pg);
     if (e != hipSuccess) return hip_fail(e, "gptq_forward_scatter launch (was gptq_init() called on this device?)");

@@ -1891,7 +1891,7 @@ GemmPlan plan_gemm(const gptq_layer_t& L, int M, const gptq_tuning_t* tune) {
     const int kpu = unit_vals(L.bits);
     const bool seq = (L.g_idx == nullptr) || (L.qweight_seq != nullptr && L.perm != nullptr);
     if (L.dtype == GPTQ_F32) {               // exact-f32 matrix core, 128 x 128 tiles, any bit width; groups made of whole packing units
-        pl.f32 = true;
+        pl.kernel = GEMM_F32;
         pl.supported = seq && (L.group_size % kpu == 0) && (L.K % 32 == 0) && (L.N % 32 == 0);
         if (!pl.supported) return pl;
         pl.use_seq = (L.g_idx != nullptr);
@@ -1917,7 +1917,7 @@ GemmPlan plan_gemm(const gptq_layer_t& L, int M, const gptq_tuning_t* tune) {
         if (knob == GPTQ_LAB_VARIANT_PANEL_ON || (knob != GPTQ_LAB_VARIANT_PANEL_OFF && (!tune || tune->path != 3 || knob == 0) && force_skinny == 0 && panel_pays(L, M))) {
             const PanelPlan pp = plan_panel(L, M, knob == GPTQ_LAB_VARIANT_PANEL_ON ? tune : nullptr);
             if (pp.ok) {
-                pl.panel = true;
+                pl.kernel = GEMM_PANEL;
                 pl.panelp = pp;
                 pl.xnat = pl.use_seq;
                 pl.mt = pp.mt; pl.bk = 64; pl.bm = 32 * pp.mt; pl.bn = 32 * pp.nt; pl.nbm = pp.nbm; pl.nbn = pp.nbn;
@@ -1934,7 +1934,7 @@ GemmPlan plan_gemm(const gptq_layer_t& L, int M, const gptq_tuning_t* tune) {
         if (knob == GPTQ_LAB_VARIANT_ROWS_ON || (knob != GPTQ_LAB_VARIANT_ROWS_OFF && (!tune || tune->path != 3 || knob == 0) && force_skinny == 0 && rows_pays(L, M))) {
             const RowsPlan rp = plan_rows(L, M, knob == GPTQ_LAB_VARIANT_ROWS_ON ? tune : nullptr);
             if (rp.ok) {
-                pl.rows = true;
+                pl.kernel = GEMM_ROWS;
                 pl.rowsp = rp;
                 pl.xnat = pl.use_seq;
                 pl.mt = rp.rb; pl.bk = 128; pl.bm = 16 * rp.rb; pl.bn = 16 * rp.s; pl.nbm = rp.npm; pl.nbn = rp.nsg;
@@ -1951,17 +1951,15 @@ GemmPlan plan_gemm(const gptq_layer_t& L, int M, const gptq_tuning_t* tune) {
     //   4096x11008  strips16 19.5/22.4/31.4/53.7   skinny64 19.2/19.5/22.8/33.0   tiled 17.8/18.7/20.9/25.7
     // 16-column strips re-read x from L2 once per strip (M*K*N/8 bytes), so they only pay up to M = 16; a wide N gives the
     // tiled kernel enough 256-column tiles to fill the chip without help.
-    pl.skinny = (force_skinny == 1) || (force_skinny == 0 && M <= 64 && (L.N + 255) / 256 < 32);
-    if (pl.skinny && M > 128) pl.skinny = false;
+    const bool skinny = ((force_skinny == 1) || (force_skinny == 0 && M <= 64 && (L.N + 255) / 256 < 32)) && M <= 128;      // (asked last: mid, stream64 and strip16 go first)
     // 17 .. 128 rows: everything by LDS DMA (gemm_mid.hip)
     {
         const gptq_layer_t* one[1] = {&L};
         const MidPlan mp = plan_mid(one, 1, M, tune);
         // by default only without kernel-specific experiment knobs: tuning.reserved[0..3] mean different things to the tiled / stream64 kernels
         const bool plain_tuning = !tune || (tune->reserved[0] == 0 && tune->reserved[1] == 0 && tune->reserved[3] == 0);
-        pl.mid = mp.ok && (force_skinny == 5 || (force_skinny == 0 && mp.pays && plain_tuning));
-        if (pl.mid) {
-            pl.skinny = false;
+        if (mp.ok && (force_skinny == 5 || (force_skinny == 0 && mp.pays && plain_tuning))) {
+            pl.kernel = GEMM_MID;
             pl.midp = mp;
             pl.mt = mp.rt; pl.bk = 32; pl.bm = 16 * mp.rt; pl.bn = 64 * mp.cw;
             pl.nbm = mp.row_blocks; pl.nbn = mp.strips_total;
@@ -1972,13 +1970,12 @@ GemmPlan plan_gemm(const gptq_layer_t& L, int M, const gptq_tuning_t* tune) {
         }
     }
     // batched decode (4 < M <= 64, 4-bit): 64-column strips, weights by LDS DMA, K slices combined inside the launch
-    // batched decode (4 < M <= 64, 4-bit): 64-column strips, weights by LDS DMA, K slices combined inside the launch
     {
         const gptq_layer_t* one[1] = {&L};
         const Stream64Plan sp = plan_stream64(one, 1, M, tune);
-        pl.stream64 = sp.ok && (force_skinny == 4 || (force_skinny == 0 && M >= 3 && sp.pays));      // 3..4 rows: want_gemm takes it only unsplit
-        if (pl.stream64) {
-            pl.skinny = false;
+        if (sp.ok && (force_skinny == 4 || (force_skinny == 0 && M >= 3 && sp.pays))) {      // 3..4 rows: want_gemm takes it only unsplit
+            pl.kernel = GEMM_STREAM64;
+            pl.s64p = sp;                                 // the (possibly tuned) geometry launch_gemm hands to launch_stream64
             pl.mt = sp.mt; pl.bk = 32; pl.bm = 16 * sp.mt; pl.bn = 64;
             pl.nbm = 1; pl.nbn = sp.strips_total;
             pl.waves = sp.waves; pl.u = sp.u;
@@ -1989,9 +1986,8 @@ GemmPlan plan_gemm(const gptq_layer_t& L, int M, const gptq_tuning_t* tune) {
     }
     // 16-column strips on the 16x16x32 matrix core: 4-bit fp16/bf16, M <= 64
     const bool strip16_ok = L.bits == 4 && M <= 64 && L.group_size % 32 == 0 && L.K % 32 == 0 && L.N % 16 == 0;
-    pl.strip16 = strip16_ok && (force_skinny == 3 || (force_skinny == 0 && M <= 16 && L.N <= 8192));
-    if (pl.strip16) {
-        pl.skinny = false;
+    if (strip16_ok && (force_skinny == 3 || (force_skinny == 0 && M <= 16 && L.N <= 8192))) {
+        pl.kernel = GEMM_STRIP16;
         pl.mt = M <= 16 ? 1 : (M <= 32 ? 2 : 4);                  // row tiles of 16
         pl.bk = 32;
         pl.bm = 16 * pl.mt;
@@ -2012,7 +2008,8 @@ GemmPlan plan_gemm(const gptq_layer_t& L, int M, const gptq_tuning_t* tune) {
         pl.workspace_bytes = pl.xperm_bytes + (pl.ksplit > 1 ? (size_t)pl.ksplit * M * L.N * sizeof(float) : 0);
         return pl;
     }
-    if (pl.skinny) {
+    if (skinny) {
+        pl.kernel = GEMM_SKINNY;
         pl.mt = M <= 32 ? 1 : (M <= 64 ? 2 : 4);
         pl.bk = (L.group_size % 64 == 0 && L.K % 64 == 0) ? 64 : 32;      // = 16 * UNR
         pl.bm = 32 * pl.mt;
@@ -2112,24 +2109,25 @@ GemmPlan plan_gemm(const gptq_layer_t& L, int M, const gptq_tuning_t* tune) {
         // Act-order layers: the copy is made of the re-sequenced rows, so x is permuted in NATURAL order (xnat) instead of the row form's slot order -- and
         // bf16 act-order layers, which have no slot-ordered permute, get the wide tiles this way.
         const bool copy_ok = L.qweight_tiled != nullptr && L.tiled_cols == GPTQ_STRIP_COLS && L.N % GPTQ_STRIP_COLS == 0 && wide_knob != GPTQ_LAB_VARIANT_WIDE_ROWS && wide_knob != GPTQ_LAB_VARIANT_WIDE_ROWS_ON;
-        pl.wide = wide_knob != GPTQ_LAB_VARIANT_WIDE_OFF && (fills || wide_knob == GPTQ_LAB_VARIANT_WIDE_ON || wide_knob == GPTQ_LAB_VARIANT_WIDE_ROWS_ON) && pl.mt == 4 && pl.bk == 64 && pl.ksplit == 1 && pl.variant == 0 && tail_knob == 0 &&
+        const bool wide = wide_knob != GPTQ_LAB_VARIANT_WIDE_OFF && (fills || wide_knob == GPTQ_LAB_VARIANT_WIDE_ON || wide_knob == GPTQ_LAB_VARIANT_WIDE_ROWS_ON) && pl.mt == 4 && pl.bk == 64 && pl.ksplit == 1 && pl.variant == 0 && tail_knob == 0 &&
                   (wide_gemm_ok(L, M, pl.use_seq, pl.xslot && pl.glds) || (copy_ok && wide_gemm_ok(L, M, false, false)));
         // The same wave tile as a stream-K partition of 128 x 256 tiles (gemm_wide_sk.hip) everywhere else from ~768 rows: every CU runs the same number of
         // 128-deep K-chunks whatever the tile count -- BASELINE config 3 (M = 2048: 256 / 688 / 256 tiles on the three Llama-7B shapes).  Decode-copy layers
         // only (act-order: x permuted in natural order).
         if (pl.mt == 4 && pl.variant == 0 && wide_knob == 0 && tail_knob == 0 && sk_knob != GPTQ_LAB_VARIANT_WIDE_SK_OFF && copy_ok &&      // (wide_sk_ok has the kernel's own conditions: 3 / 4 bits, 32-wide groups too)
             !(tune && tune->ksplit > 0 && tune->path == 3 && tune->ksplit != 1) && wide_sk_ok(L, M) &&
-            (sk_knob == GPTQ_LAB_VARIANT_WIDE_SK_ON || (!pl.wide && wide_sk_pays(L, M)))) {
-            pl.wsk = true;
+            (sk_knob == GPTQ_LAB_VARIANT_WIDE_SK_ON || (!wide && wide_sk_pays(L, M)))) {
+            pl.kernel = GEMM_WIDE_SK;
             pl.wskg = wide_sk_geom(L, M);
-            pl.wide = false; pl.wide_tiled = true; pl.xnat = pl.use_seq; pl.xslot = false; pl.glds = true;
+            pl.wide_tiled = true; pl.xnat = pl.use_seq; pl.xslot = false; pl.glds = true;
             pl.bk = 64; pl.ksteps_total = L.K / 64;
             pl.tail = 0; pl.tail_lg = 0; pl.ksplit = 1; pl.ksteps_per_split = pl.ksteps_total; pl.kg = 2;
             pl.bn = 256; pl.nbm = pl.wskg.nbm; pl.nbn = pl.wskg.nbn;
             pl.workspace_bytes = pl.xperm_bytes + pl.wskg.slot_bytes;
             return pl;
         }
-        if (pl.wide) {
+        if (wide) {
+            pl.kernel = GEMM_WIDE;
             pl.wide_tiled = copy_ok;
             pl.xnat = pl.wide_tiled && pl.use_seq;
             pl.tail = 0; pl.tail_lg = 0;
@@ -2200,9 +2198,9 @@ static hipError_t launch_skinny(const GemmPlan& pl, const GemmParams& p, hipStre
 template <int BITS, typename T>
 static hipError_t launch_bits(const GemmPlan& pl, const GemmParams& p, hipStream_t st) {
     if constexpr (BITS == 4) {
-        if (pl.strip16) return launch_strip16<T>(pl, p, st);
+        if (pl.kernel == GEMM_STRIP16) return launch_strip16<T>(pl, p, st);
     }
-    if (pl.skinny) return launch_skinny<BITS, T>(pl, p, st);
+    if (pl.kernel == GEMM_SKINNY) return launch_skinny<BITS, T>(pl, p, st);
     if constexpr (BITS == 4) {
         if (pl.bk == 64) {
             if (pl.kg == 2) {
@@ -2273,12 +2271,12 @@ hipError_t launch_gemm(const gptq_layer_t& L, const GemmPlan& pl, const void* x,
     p.nbm = pl.nbm; p.nbn = pl.nbn; p.ksplit = pl.ksplit;
     p.ksteps_total = pl.ksteps_total; p.ksteps_per_split = pl.ksteps_per_split;
     p.qrows = L.K / 32 * L.bits;
-    if (!pl.f32) {
+    if (pl.kernel != GEMM_F32) {
         const unsigned long long kpg = (unsigned long long)(L.group_size >= pl.bk ? L.group_size / pl.bk : 1);       // K-steps per group (the stream-K kernel alone runs 64-deep steps on 32-wide groups and has its own parameters)
         p.kpg_inv = ((1ull << 32) + kpg - 1) / kpg;
     }
     hipError_t e;
-    if (pl.f32) {
+    if (pl.kernel == GEMM_F32) {
         if (pl.use_seq) {
             e = launch_permute_columns(x, L.perm, M, L.K, GPTQ_F32, workspace, st);
             if (e != hipSuccess) return e;
@@ -2314,24 +2312,17 @@ hipError_t launch_gemm(const gptq_layer_t& L, const GemmPlan& pl, const void* x,
         p.err = (unsigned*)((char*)ws_header + WS_HEADER_BYTES - WS_HEADER_TAIL_BYTES) + 2;
         p.max_spins = 1u << 22;
     }
-    if (pl.mid) {
-        const gptq_layer_t* one[1] = {&L};
-        void* outs[1] = {out};
-        return launch_mid(one, pl.midp, p.x, outs, M, ws_header, p.partial, pl.use_seq ? L.qweight_seq : nullptr, st);
+    const gptq_layer_t* one[1] = {&L};
+    void* outs[1] = {out};
+    switch (pl.kernel) {
+        case GEMM_MID: return launch_mid(one, pl.midp, p.x, outs, M, ws_header, p.partial, pl.use_seq ? L.qweight_seq : nullptr, st);
+        case GEMM_STREAM64: return launch_stream64(one, pl.s64p, p.x, outs, M, ws_header, p.partial, pl.use_seq ? L.qweight_seq : nullptr, st);
+        case GEMM_ROWS: return launch_gemm_rows(L, pl.rowsp, p.x, out, M, st);
+        case GEMM_PANEL: return launch_gemm_panel(L, pl.panelp, p.x, out, M, st);
+        case GEMM_WIDE_SK: return launch_gemm_wide_sk(L, p.x, out, M, ws_header, (char*)workspace + pl.xperm_bytes, st);
+        case GEMM_WIDE: return launch_gemm_wide(L, p.qweight, p.x, out, M, pl.use_seq, st, pl.wide_tiled);
+        default: break;                                   // GEMM_TILED / GEMM_STRIP16 / GEMM_SKINNY: by packing and dtype (launch_bits)
     }
-    if (pl.stream64) {
-        const gptq_layer_t* one[1] = {&L};
-        void* outs[1] = {out};
-        Stream64Plan sp = plan_stream64(one, 1, M, nullptr);
-        sp.waves = pl.waves; sp.u = pl.u; sp.ksplit = pl.ksplit; sp.ksteps_per_split = pl.ksteps_per_split;      // the (possibly tuned) geometry of plan_gemm
-        const size_t land = (size_t)sp.waves * sp.u * 1024, slabs = (size_t)sp.waves * sp.mt * 4096;
-        sp.lds_bytes = (land > slabs ? land : slabs) + 16;
-        return launch_stream64(one, sp, p.x, outs, M, ws_header, p.partial, pl.use_seq ? L.qweight_seq : nullptr, st);
-    }
-    if (pl.rows) return launch_gemm_rows(L, pl.rowsp, p.x, out, M, st);
-    if (pl.panel) return launch_gemm_panel(L, pl.panelp, p.x, out, M, st);
-    if (pl.wsk) return launch_gemm_wide_sk(L, p.x, out, M, ws_header, (char*)workspace + pl.xperm_bytes, st);
-    if (pl.wide) return launch_gemm_wide(L, p.qweight, p.x, out, M, pl.use_seq, st, pl.wide_tiled);
     e = (L.dtype == GPTQ_F16) ? launch_t<f16>(L, pl, p, st) : launch_t<bf16>(L, pl, p, st);
     if (e != hipSuccess) return e;
     if (pl.ksplit > 1) {

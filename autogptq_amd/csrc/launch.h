@@ -78,25 +78,36 @@ PanelPlan plan_panel(const gptq_layer_t& L, int M, const gptq_tuning_t* tune);
 hipError_t launch_gemm_panel(const gptq_layer_t& L, const PanelPlan& pl, const void* x, void* out, int M, hipStream_t st);
 hipError_t init_gemm_panel_device();
 
+// Batched decode (gemm_stream64_kernel): 1..4 plain 4-bit layers that read the same x, 1 <= M <= 64, one launch.
+struct Stream64Plan {
+    bool ok;                 // every layer qualifies and the geometry fits
+    bool pays;               // measured preference over the per-layer kernels (enough workgroups, not a small layer)
+    int nseg, mt, waves, u, ksplit, ksteps_total, ksteps_per_split, strips_total, nsum;
+    size_t lds_bytes;
+    size_t partial_bytes;    // behind the header (and the permuted x of an act-order layer): [ksplit][M][nsum] fp32 when ksplit > 1
+};
+// The ONE kernel a GemmPlan launches; gemm_kernel_names[] is what gptq_describe_plan prints (GEMM_WIDE reading the decode copy -- wide_tiled -- prints "wide_copy")
+enum GemmKernel {
+    GEMM_TILED,               // 128 / 64 / 32 x 256 tiles of gemm_kernel (gemm.hip): everything no other kernel takes
+    GEMM_F32,                 // fp32 I/O: exact-f32 matrix core kernel (128 x 128 tiles)
+    GEMM_PANEL,               // gemm_panel.hip (panelp holds its geometry); act-order layers: x permuted in natural order (xnat)
+    GEMM_ROWS,                // gemm_rows.hip (rowsp holds its geometry); act-order layers: x permuted in natural order (xnat)
+    GEMM_WIDE_SK,             // stream-K partition of 128 x 256 tiles with the 128 x 128 wave tile (gemm_wide_sk.hip; wskg); implies wide_tiled (+ xnat for act-order layers)
+    GEMM_WIDE,                // 128 x 512 tiles, 128 x 128 per wave, accumulators in AGPRs (gemm_wide.hip): large launches
+    GEMM_MID,                 // 17 .. 128 rows, 4-bit: gemm_mid_kernel (midp holds its geometry)
+    GEMM_STREAM64,            // batched decode 4 < M <= 64, 4-bit: 64-column strips by LDS DMA, in-launch K-split combine (s64p holds its geometry; u = K-steps in flight per wave)
+    GEMM_STRIP16,             // 8 < M <= 64, 4-bit: 16-column strips on v_mfma_f32_16x16x32 (mt = row tiles of 16)
+    GEMM_SKINNY,              // weight-streaming decomposition for 8 < M <= 128 (64-column strips, waves split K)
+};
+constexpr const char* gemm_kernel_names[] = {"tiled", "f32_mfma", "panel", "rows", "wide_sk", "wide", "mid", "stream64", "strip16", "skinny64"};
 struct GemmPlan {
     bool supported, use_seq;
-    bool panel;               // gemm_panel.hip (panelp holds its geometry); act-order layers: x permuted in natural order (xnat)
-    PanelPlan panelp;
-    bool rows;                // gemm_rows.hip (rowsp holds its geometry); act-order layers: x permuted in natural order (xnat)
-    RowsPlan rowsp;
-    bool wsk;                 // stream-K partition of 128 x 256 tiles with the 128 x 128 wave tile (gemm_wide_sk.hip); implies wide_tiled (+ xnat for act-order layers)
-    WideSkGeom wskg;
-    bool wide_tiled;          // ... reading the layer's decode copy, raw x staged by LDS DMA
+    GemmKernel kernel;
+    PanelPlan panelp; RowsPlan rowsp; WideSkGeom wskg; MidPlan midp; Stream64Plan s64p;      // the geometry of `kernel`, where it has a plan of its own
+    bool wide_tiled;          // GEMM_WIDE / GEMM_WIDE_SK reading the layer's decode copy, raw x staged by LDS DMA
     bool xnat;                // act-order + wide_tiled: x permuted in natural order (the copy is of the re-sequenced rows)
-    bool wide;                // 128 x 512 tiles, 128 x 128 per wave, accumulators in AGPRs (gemm_wide.hip): large launches
-    bool mid;                 // 17 .. 128 rows, 4-bit: gemm_mid_kernel (midp holds its geometry)
-    MidPlan midp;
     bool glds;                // ... and stages it with global_load_lds (DMA) into swizzled, unpadded LDS rows
     bool xslot;               // act-order: the x pre-pass writes k-slot order, the kernel copies x to LDS verbatim
-    bool strip16;             // 8 < M <= 64, 4-bit: 16-column strips on v_mfma_f32_16x16x32 (mt = row tiles of 16)
-    bool f32;                 // fp32 I/O: exact-f32 matrix core kernel (128 x 128 tiles)
-    bool skinny;              // weight-streaming decomposition for 8 < M <= 128 (64-column strips, waves split K)
-    bool stream64;            // batched decode 4 < M <= 64, 4-bit: 64-column strips by LDS DMA, in-launch K-split combine (u = K-steps in flight per wave)
     int waves, variant, u;
     int kg;                   // K groups inside a workgroup (2 = 8 waves, two K halves summed through LDS)
     int mt, bk, bm, bn;       // row tiles per wave, K-step, workgroup tile
@@ -122,14 +133,6 @@ struct StreamPlan {
 StreamPlan plan_stream(const gptq_layer_t* const* layers, int n, int M, const gptq_tuning_t* tune);
 hipError_t launch_stream(const gptq_layer_t* const* layers, const StreamPlan& pl, const void* x, void* const* outs, int M,
                          void* ws_header, void* ws_body, hipStream_t st);
-// Batched decode (gemm_stream64_kernel): 1..4 plain 4-bit layers that read the same x, 1 <= M <= 64, one launch.
-struct Stream64Plan {
-    bool ok;                 // every layer qualifies and the geometry fits
-    bool pays;               // measured preference over the per-layer kernels (enough workgroups, not a small layer)
-    int nseg, mt, waves, u, ksplit, ksteps_total, ksteps_per_split, strips_total, nsum;
-    size_t lds_bytes;
-    size_t partial_bytes;    // behind the header (and the permuted x of an act-order layer): [ksplit][M][nsum] fp32 when ksplit > 1
-};
 Stream64Plan plan_stream64(const gptq_layer_t* const* layers, int n, int M, const gptq_tuning_t* tune);
 // qweight_override: the re-sequenced rows of a single act-order layer (x is then the permuted copy), else NULL
 hipError_t launch_stream64(const gptq_layer_t* const* layers, const Stream64Plan& pl, const void* x, void* const* outs, int M,

@@ -120,7 +120,7 @@ int main(int argc, char** argv) {
             }
         for (auto& v : vs)
             printf("  %9.2f us  %8.1f TFLOP/s  %7.1f GB/s(w)  %-38s %s mt=%d bk=%d grid=%dx%d ksplit=%d\n", v.us, 2.0 * M * K * N / v.us / 1e6, qw_b / v.us / 1e3, v.name,
-                   v.pl.skinny ? "skinny" : "tiled", v.pl.mt, v.pl.bk, v.pl.nbm, v.pl.nbn, v.pl.ksplit);
+                   v.pl.kernel == GEMM_SKINNY ? "skinny" : "tiled", v.pl.mt, v.pl.bk, v.pl.nbm, v.pl.nbn, v.pl.ksplit);
         for (auto& v : vs) {
             if (v.id != 20 && v.id != 21) continue;
             // one more launch with a clean stamp area: per wave of workgroup 0 the cycle sums of the five phases of a K-step

@@ -65,7 +65,7 @@ class GptqTuning(Structure):
 
 
 class GptqMoe(Structure):
-    """gptq_moe_t: E experts, each a gate / up / down layer (arrays of E layer pointers); flags: 0 (the default), or any of MOE_LOW_BIT, MOE_LOW_BIT_DECODE and MOE_LOW_BIT_BATCH."""
+    """gptq_moe_t: E experts, each a gate / up / down layer (arrays of E layer pointers); flags: 0 (the default), or any of MOE_LOW_BIT, MOE_LOW_BIT_DECODE, MOE_LOW_BIT_BATCH and MOE_LOW_BIT_PREFILL."""
     _fields_ = [("E", c_int32), ("flags", c_int32), ("gate", c_void_p), ("up", c_void_p), ("down", c_void_p)]
 
 
@@ -77,6 +77,7 @@ class GptqMoeShared(Structure):
 MOE_LOW_BIT = 1          # GPTQ_MOE_LOW_BIT: the grouped path (forward and backward) also takes 2- and 3-bit experts
 MOE_LOW_BIT_DECODE = 8   # GPTQ_MOE_LOW_BIT_DECODE: the decode path (1..4 tokens on the decode copy) also takes 2- and 3-bit experts
 MOE_LOW_BIT_BATCH = 0x10  # GPTQ_MOE_LOW_BIT_BATCH: the batch path (5..64 tokens on the decode copy) also takes 2- and 3-bit experts
+MOE_LOW_BIT_PREFILL = 0x20  # GPTQ_MOE_LOW_BIT_PREFILL: the prefill path (any T; Python: 65 tokens and more, on the decode copy) also takes 2- and 3-bit experts
 ROUTER_RENORM = 1        # GPTQ_ROUTER_RENORM: gptq_moe_router divides the selected probabilities by their sum
 
 

@@ -1156,7 +1156,7 @@ static const MoePathRules MOE_DECODE = {"decode", 4, 0, 64, "decode_copy=True", 
 static const MoePathRules MOE_BATCH = {"batch", 64, 0, 128, "batch=True", moe_batch_group_ok, "32, 64, 128 times a power of two, or one group", false,
                                        GPTQ_MOE_LOW_BIT_BATCH, false};
 static const MoePathRules MOE_PREFILL = {"prefill", 0, GPTQ_MOE_PREFILL_MAX_ROWS, 128, "prefill=True", moe_prefill_group_ok, "64 times a power of two, or one group",
-                                         true, 0, false};
+                                         true, GPTQ_MOE_LOW_BIT_PREFILL, false};
 
 static int moe_check_bits(const MoePathRules& r, int bits, int flags) {
     if (bits == 4 || bits == 8) return GPTQ_OK;
@@ -1205,8 +1205,9 @@ static int moe_check_proj(const MoePathRules& r, const gptq_layer_t* const* Ls, 
 static int moe_check(const MoePathRules& r, const gptq_moe_t* m, int T, int topk) {
     const bool grouped = !r.copy_hint;
     if (!m) return fail(GPTQ_ERR_NULL, "moe is NULL");
-    // (GPTQ_MOE_LOW_BIT_DECODE: a known bit of the decode path's, nothing here reads it.  GPTQ_MOE_LOW_BIT_BATCH stays among the unknown ones here: 0x10 was
-    // refused by these entry points before the batch path gave it a meaning, and they answer as they did -- a caller of both paths keeps two gptq_moe_t)
+    // (GPTQ_MOE_LOW_BIT_DECODE: a known bit of the decode path's, nothing here reads it.  GPTQ_MOE_LOW_BIT_BATCH and GPTQ_MOE_LOW_BIT_PREFILL stay among the
+    // unknown ones here: 0x10 and 0x20 were refused by these entry points before the copy paths gave them a meaning, and they answer as they did -- a caller
+    // of both kinds of path keeps two gptq_moe_t)
     if (grouped && (m->flags & ~(GPTQ_MOE_LOW_BIT | GPTQ_MOE_LOW_BIT_DECODE)))
         return fail(GPTQ_ERR_UNSUPPORTED, "moe->flags = 0x%x: unknown flag bits (GPTQ_MOE_LOW_BIT and GPTQ_MOE_LOW_BIT_DECODE are the only ones)", (unsigned)m->flags);
     if (m->E < 1 || m->E > 256) return fail(GPTQ_ERR_UNSUPPORTED, "E = %d experts: the %s path takes 1..256", m->E, r.word);
@@ -1360,12 +1361,12 @@ int gptq_describe_moe_backward_plan(const gptq_moe_t* m, int T, int topk, char* 
 size_t gptq_moe_decode_table_bytes(int E) { return E > 0 ? 3 * (size_t)E * moe_decode_table_entry_bytes() : 0; }
 
 int gptq_moe_build_decode_table(const gptq_moe_t* m, void* table, void* stream) {
-    // 2- / 3-bit experts opened for the batch path alone (GPTQ_MOE_LOW_BIT_BATCH without GPTQ_MOE_LOW_BIT_DECODE): the batch path's check stands in front of
-    // the table it reads; every other set, flagged or not, is checked as before
-    const bool batch_only = m && (m->flags & GPTQ_MOE_LOW_BIT_BATCH) && !(m->flags & GPTQ_MOE_LOW_BIT_DECODE) && m->gate && m->gate[0] &&
-                            (m->gate[0]->bits == 2 || m->gate[0]->bits == 3);
-    return moe_build_table_impl(batch_only ? MOE_BATCH : MOE_DECODE, m, table, stream, moe_decode_table_entry_bytes(), moe_decode_table_entry,
-                                "gptq_moe_build_decode_table copy");
+    // 2- / 3-bit experts opened for a copy path other than the decode path (GPTQ_MOE_LOW_BIT_BATCH / GPTQ_MOE_LOW_BIT_PREFILL without
+    // GPTQ_MOE_LOW_BIT_DECODE): the check of the first such path whose flag is set -- batch, then prefill -- stands in front of the table it reads; every
+    // other set, flagged or not, is checked as before
+    const bool low_copy = m && !(m->flags & GPTQ_MOE_LOW_BIT_DECODE) && m->gate && m->gate[0] && (m->gate[0]->bits == 2 || m->gate[0]->bits == 3);
+    const MoePathRules& r = low_copy && (m->flags & GPTQ_MOE_LOW_BIT_BATCH) ? MOE_BATCH : (low_copy && (m->flags & GPTQ_MOE_LOW_BIT_PREFILL) ? MOE_PREFILL : MOE_DECODE);
+    return moe_build_table_impl(r, m, table, stream, moe_decode_table_entry_bytes(), moe_decode_table_entry, "gptq_moe_build_decode_table copy");
 }
 
 size_t gptq_moe_decode_workspace_bytes(const gptq_moe_t* m, int T, int topk) {
@@ -1525,8 +1526,10 @@ int gptq_describe_moe_prefill_plan(const gptq_moe_t* m, int T, int topk, char* o
     if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out is NULL");
     if (moe_check(MOE_PREFILL, m, T, topk)) return describe_decline(out, out_bytes, "none");
     const MoePrefillPlan pl = plan_moe_prefill(*m, T, topk);
-    snprintf(out, out_bytes, "path=prefill bm=%d launches=%d tiles=%d nt_pair=%d nt_down=%d waves=%d waves_pair=%d spw_pair=%d spw_down=%d lds=%d", pl.bm, pl.launches,
-             pl.tiles, pl.nt_pair, pl.nt_down, pl.waves_down, pl.waves_pair, pl.spw_pair, pl.spw_down, pl.lds_down);
+    const int n = snprintf(out, out_bytes, "path=prefill bm=%d launches=%d tiles=%d nt_pair=%d nt_down=%d waves=%d waves_pair=%d spw_pair=%d spw_down=%d lds=%d", pl.bm,
+                           pl.launches, pl.tiles, pl.nt_pair, pl.nt_down, pl.waves_down, pl.waves_pair, pl.spw_pair, pl.spw_down, pl.lds_down);
+    const int bits = m->gate[0]->bits;                         // 2 / 3 bits (GPTQ_MOE_LOW_BIT_PREFILL): the width is named; 4 / 8 bits answer as they did
+    if ((bits == 2 || bits == 3) && n > 0 && (size_t)n < out_bytes) snprintf(out + n, out_bytes - (size_t)n, " bits=%d", bits);
     return GPTQ_OK;
 }
 

@@ -1495,10 +1495,10 @@ __global__ void __launch_bounds__(RT == 1 ? 1024 : 512) gemm_stream64_kernel(S64
 //   x tile [128][32 k] fp32 through LDS (row stride 33 floats: the 32 rows of a ds_read_b32 hit 32 banks), double buffered;
 //   a lane owns column (l & 31) of each of its 2 column tiles: it loads that column's packing unit (1 word = 16/8/4 values,
 //   3 words = 32 values for 3-bit), extracts the fields, forms s * (w - z) and feeds k-pair (2j + (l >> 5)) to MFMA j.
+constexpr int F32_BM = 128, F32_BK = 32, F32_AS = F32_BK + 1;
 template <int BITS>
-__global__ void __launch_bounds__(256) gemm_f32_kernel(GemmParams p) {
-    constexpr int KPU = Pack<BITS>::vals, UW = Pack<BITS>::words, BK = 32, UPB = BK / KPU, BM = 128, AS = BK + 1;
-    __shared__ float As[2][BM * AS];
+__device__ __forceinline__ void gemm_f32_body(const GemmParams& p, float (*As)[F32_BM * F32_AS]) {
+    constexpr int KPU = Pack<BITS>::vals, UW = Pack<BITS>::words, BK = F32_BK, UPB = BK / KPU, BM = F32_BM, AS = F32_AS;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, half = lane >> 5;
     const int L = xcd_remap(blockIdx.x, p.nbm * p.nbn);
@@ -1601,11 +1601,21 @@ __global__ void __launch_bounds__(256) gemm_f32_kernel(GemmParams p) {
             }
     }
 }
+// bits is a run-time, workgroup-uniform argument: one instantiation, the four packings behind one switch (as utils.hip dequant_kernel); the x tile in LDS
+// is the same for all of them and belongs to the kernel
+__global__ void __launch_bounds__(256) gemm_f32_kernel(GemmParams p, int bits) {
+    __shared__ float As[2][F32_BM * F32_AS];
+    switch (bits) {
+        case 2: gemm_f32_body<2>(p, As); break;
+        case 3: gemm_f32_body<3>(p, As); break;
+        case 4: gemm_f32_body<4>(p, As); break;
+        default: gemm_f32_body<8>(p, As); break;
+    }
+}
 
 // out = sum_s partial[s] (+bias), fixed order; 4 columns per thread
 template <typename T>
-__global__ void __launch_bounds__(256) gemm_reduce_kernel(const float* __restrict__ partial, const T* __restrict__ bias,
-                                                          T* __restrict__ out, int S, int M, int N) {
+__device__ __forceinline__ void gemm_reduce_body(const float* __restrict__ partial, const T* __restrict__ bias, T* __restrict__ out, int S, int M, int N) {
     const size_t total4 = (size_t)M * N / 4;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (size_t)gridDim.x * blockDim.x) {
         f32x4 s = {0.f, 0.f, 0.f, 0.f};
@@ -1621,6 +1631,12 @@ __global__ void __launch_bounds__(256) gemm_reduce_kernel(const float* __restric
         u32x2 w = {(unsigned)o[0] | ((unsigned)o[1] << 16), (unsigned)o[2] | ((unsigned)o[3] << 16)};
         *(u32x2*)((unsigned short*)out + i * 4) = w;
     }
+}
+// one code object for both dtypes (a launch-uniform branch in front of the loop, as utils.hip silu_mul_kernel): the library keeps to its kernel count
+__global__ void __launch_bounds__(256) gemm_reduce_kernel(const float* __restrict__ partial, const void* __restrict__ bias, void* __restrict__ out, int S, int M,
+                                                          int N, int dtype) {
+    if (dtype == GPTQ_F16) gemm_reduce_body<f16>(partial, (const f16*)bias, (f16*)out, S, M, N);
+    else gemm_reduce_body<bf16>(partial, (const bf16*)bias, (bf16*)out, S, M, N);
 }
 
 // x_out[m, i] = x[m, perm[i]] for 2-byte elements: one row per workgroup pass, the row staged in LDS
@@ -2283,13 +2299,8 @@ hipError_t launch_gemm(const gptq_layer_t& L, const GemmPlan& pl, const void* x,
             p.x = workspace;
         }
         const dim3 grid(pl.nbm * pl.nbn), block(256);
-        switch (L.bits) {
-            case 2: hipLaunchKernelGGL(gemm_f32_kernel<2>, grid, block, 0, st, p); break;
-            case 3: hipLaunchKernelGGL(gemm_f32_kernel<3>, grid, block, 0, st, p); break;
-            case 4: hipLaunchKernelGGL(gemm_f32_kernel<4>, grid, block, 0, st, p); break;
-            case 8: hipLaunchKernelGGL(gemm_f32_kernel<8>, grid, block, 0, st, p); break;
-            default: return hipErrorInvalidValue;
-        }
+        if (L.bits != 2 && L.bits != 3 && L.bits != 4 && L.bits != 8) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(gemm_f32_kernel, grid, block, 0, st, p, L.bits);
         return hipGetLastError();
     }
     if (pl.use_seq) {
@@ -2329,10 +2340,7 @@ hipError_t launch_gemm(const gptq_layer_t& L, const GemmPlan& pl, const void* x,
         const size_t total4 = (size_t)M * L.N / 4;
         int blocks = (int)((total4 + 255) / 256);
         if (blocks > 2048) blocks = 2048;
-        if (L.dtype == GPTQ_F16)
-            hipLaunchKernelGGL(gemm_reduce_kernel<f16>, dim3(blocks), dim3(256), 0, st, p.partial, (const f16*)L.bias, (f16*)out, pl.ksplit, M, L.N);
-        else
-            hipLaunchKernelGGL(gemm_reduce_kernel<bf16>, dim3(blocks), dim3(256), 0, st, p.partial, (const bf16*)L.bias, (bf16*)out, pl.ksplit, M, L.N);
+        hipLaunchKernelGGL(gemm_reduce_kernel, dim3(blocks), dim3(256), 0, st, p.partial, L.bias, out, pl.ksplit, M, L.N, L.dtype);
         e = hipGetLastError();
     }
     return e;

@@ -271,7 +271,8 @@ hipError_t init_moe_batch_device();
 hipError_t launch_moe_gather_rows(const void* table, int planes, int topk, const int64_t* idx, const int* row_assign, const int* offsets, const void* in,
                                   void* out, int E, int K, int R, hipStream_t st);
 // moe_panel.hip: the same layer at any token count on the experts' decode copy (gptq_moe_prefill_forward; Python: 65 tokens and more): route with 64-row
-// tiles, x into sorted order, gate|up + silu * mul, down, combine -- five launches (act-order down projections: + the gather of H_sorted through perm)
+// tiles, x into sorted order, gate|up + silu * mul, down, combine -- five launches (act-order down projections: + the gather of H_sorted through perm).
+// 4 and 8 bits: moe_panel_kernel; 2 and 3 bits (GPTQ_MOE_LOW_BIT_PREFILL): moe_panel_lowbit_kernel on the copy's 8- / 12-byte lanes, chunks = K / 128 as at 4 bits
 constexpr int GPTQ_MOE_PREFILL_MAX_ROWS = 65535;    // T topk: the gather's grid
 struct MoePrefillPlan : RouteLayout {
     bool act_pair, act_down;                        // some gate / up (down) expert is act-order: two planes of x_sorted / the gather of H_sorted

@@ -88,7 +88,8 @@ def pack_model(model: nn.Module, quantizers: dict, bits: int, group_size: int, d
 def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_length: Optional[int] = None,
                        release_checkpoint_layout: Optional[bool] = None, decode_copy: Optional[bool] = None,
                        expert_decode_copy: bool = False, expert_batched_decode: bool = False, expert_backward: bool = False, expert_low_bit: bool = False,
-                       expert_prefill: bool = False, expert_low_bit_decode: bool = False, expert_low_bit_batch: bool = False) -> nn.Module:
+                       expert_prefill: bool = False, expert_low_bit_decode: bool = False, expert_low_bit_batch: bool = False,
+                       expert_low_bit_prefill: bool = False) -> nn.Module:
     """post_init every mi355x layer and size the per-device scratch once (so forward never allocates; needed before hipGraph
     capture).  ``max_input_length`` bounds the rows M the scratch is sized for (default 2048, the reference's exllama default).
     Memory (the model-level switches for what post_init keeps next to the checkpoint tensors): ``decode_copy=False`` builds no decode copy (1x the packed
@@ -112,7 +113,10 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
     expert copies) and calls of 1..4 tokens run the decode kernels on it; it stands next to ``expert_low_bit`` (which serves the larger calls) and
     ``expert_decode_copy``, and changes nothing for 4- and 8-bit experts.  ``expert_low_bit_batch=True`` (sets ``QuantMoEExperts.low_bit_batch`` before the module's post_init):
     2- and 3-bit experts get a decode copy (if nothing else built it) and calls of 5..64 tokens run the batch kernels on it; the scratch covers the batch
-    path's largest need; nothing changes for 4- and 8-bit experts.
+    path's largest need; nothing changes for 4- and 8-bit experts.  ``expert_low_bit_prefill=True`` (sets ``QuantMoEExperts.low_bit_prefill`` before the
+    module's post_init): 2- and 3-bit experts get a decode copy (if nothing else built it) and calls of 65 tokens and more
+    (``QuantMoEExperts.low_bit_prefill_min_tokens``) run the prefill kernels on it; the scratch covers ``gptq_moe_prefill_workspace_bytes`` of
+    ``max_input_length`` tokens and the largest need below the threshold; nothing changes for 4- and 8-bit experts.
     Blocks bound by ``inject_shared_expert`` before this call: the scratch also covers ``gptq_moe_shared_decode_workspace_bytes`` of 1..4 tokens."""
     from .moe import QuantMoEExperts
     rows = max_input_length or 2048
@@ -125,6 +129,8 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
             dev = sub[0].layers()[0].qweight.device
             if expert_low_bit_batch:
                 sub.low_bit_batch = True
+            if expert_low_bit_prefill:
+                sub.low_bit_prefill = True
             sub.post_init(decode_copy=expert_decode_copy, batch=expert_batched_decode, backward=expert_backward, low_bit=expert_low_bit,
                           prefill=expert_prefill, low_bit_decode=expert_low_bit_decode)
             for e in range(sub.num_experts):
@@ -137,6 +143,8 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
                 ts.add(min(rows, 64, int(sub.low_bit_batch_max_tokens)))      # the same for 2- / 3-bit experts on the batch path
             if expert_prefill:
                 ts.add(min(rows, 64))                            # the prefill path starts at 65 tokens (its need grows with T: `rows`); below, the other paths' largest T
+            if expert_low_bit_prefill and sub.bits in (2, 3):
+                ts.add(min(rows, max(64, int(sub.low_bit_prefill_min_tokens) - 1)))      # the largest T the other paths serve below the prefill path's threshold
             need[dev] = max([need.get(dev, 0)] + [sub.workspace_bytes(t, sub.top_k) for t in sorted(ts)])
             if sub._grad_table is not None:
                 need[dev] = max(need[dev], sub.backward_workspace_bytes(rows, sub.top_k))

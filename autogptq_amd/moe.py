@@ -27,7 +27,8 @@
 * ``pack_moe_experts``  pack the dense 3-D expert parameters of a model (``quantizers`` keyed ``...mlp.experts.{e}.w1`` as ``pack_model`` takes)
 
 2- and 3-bit experts: ``post_init(low_bit=True)`` opens the grouped path to them, ``post_init(low_bit_decode=True)`` the decode path (1..4 tokens),
-the attribute ``low_bit_batch = True`` (set before ``post_init``) the batch path (5..64 tokens).
+the attribute ``low_bit_batch = True`` (set before ``post_init``) the batch path (5..64 tokens), the attribute ``low_bit_prefill = True`` (likewise) the
+prefill path (65 tokens and more).
 The per-expert composition serves what the grouped kernels do not take (2- / 3-bit experts unless ``post_init(low_bit=True)``, fp32 experts, odd group
 sizes, raw act-order), CPU tensors (which ``QuantLinear`` refuses), and -- by default -- calls under grad where ``hidden_states`` or ``top_k_weights`` require grad: training through the experts gets
 dX and the router-weight gradient from the existing backward of ``QuantLinear``.  After ``post_init(backward=True)`` such a call is ONE autograd node
@@ -110,8 +111,11 @@ class QuantMoEExperts(nn.Module):
         self._low_bit_decode = False
         self.low_bit_batch = False                  # the switch of the batch path for 2- / 3-bit experts: set before post_init (read there; see its docstring)
         self._low_bit_batch = False                 # ... what post_init made of it
+        self.low_bit_prefill = False                # the switch of the prefill path for 2- / 3-bit experts: set before post_init, like low_bit_batch
+        self._low_bit_prefill = False               # ... what post_init made of it
         self.batch_max_tokens = 64
         self.low_bit_batch_max_tokens = 64          # 2- / 3-bit experts with low_bit_batch = True: the batch path for 5..this many tokens (the kernels take 64)
+        self.low_bit_prefill_min_tokens = 65        # 2- / 3-bit experts with low_bit_prefill = True: the prefill path from this many tokens on (never below 65)
         self.low_bit_decode_max_tokens = 4          # 2- / 3-bit experts with low_bit_decode=True: the decode path up to this many tokens (the kernels take 4)
         for e in range(num_experts):
             self.add_module(str(e), _Expert(self.names, bits, group_size, hidden_dim, intermediate_dim, weight_dtype, zero_mode))
@@ -130,6 +134,7 @@ class QuantMoEExperts(nn.Module):
         self._grad_table = None
         self._batch_ok = False
         self._low_bit_batch_ok = False
+        self._low_bit_prefill_ok = False
         self._prefill_ok = False
         self.decode_copy_bytes = 0
         self._keep = ()
@@ -174,7 +179,12 @@ class QuantMoEExperts(nn.Module):
         calls of 5..min(64, ``low_bit_batch_max_tokens``) tokens on 2- and 3-bit experts run the batch kernels on the copy (``plan(T)["path"] == "batch"``, gptq_moe_batch_forward with GPTQ_MOE_LOW_BIT_BATCH); with ``low_bit_decode=True`` as well the decode path serves
         1..4 tokens and the batch path 5..64; fewer or more tokens run the grouped path with ``low_bit=True``, else the per-expert composition.  Experts the
         batch plan declines log the reason once and behave as without the flag; it has no effect on 4- and 8-bit experts (``batch=True`` is their
-        switch).  ``decode_copy_bytes`` reports what the copies hold.  A checkpoint-layout release does not apply to expert layers."""
+        switch).  The attribute ``low_bit_prefill = True``, set before this call (opt-in, an attribute in the same way; builds the decode copy and its
+        table for such experts if nothing else did): calls of max(65, ``low_bit_prefill_min_tokens``) tokens and more on 2- and 3-bit experts run the prefill
+        kernels on the copy (``plan(T)["path"] == "prefill"``, gptq_moe_prefill_forward with GPTQ_MOE_LOW_BIT_PREFILL); fewer tokens run the ladder above
+        (decode, batch, grouped, composition).  Experts the prefill plan declines (sizes that are no multiples of 128, group sizes other than 64 times a
+        power of two or one group, fp32) log the reason once, the attribute is unset and they behave as without it; it has no effect on 4- and 8-bit
+        experts (``prefill=True`` is their switch).  ``decode_copy_bytes`` reports what the copies hold.  A checkpoint-layout release does not apply to expert layers."""
         dev = self[0].layers()[0].qweight.device
         if dev.type != "cuda":
             raise RuntimeError(f"mi355x QuantMoEExperts.post_init needs the module on a ROCm GPU device (got {dev}); there is no CPU path.")
@@ -188,6 +198,12 @@ class QuantMoEExperts(nn.Module):
             if why:
                 logger.warning("QuantMoEExperts.low_bit_batch = True has no effect for these experts (%s)", why)
                 self._low_bit_batch = self.low_bit_batch = False
+        self._low_bit_prefill = bool(self.low_bit_prefill) and self.bits in (2, 3)      # (no effect on 4- and 8-bit experts)
+        if self._low_bit_prefill:
+            why = self._copy_path_declined("prefill", 128, _PREFILL_GROUPS, low_bit=True)
+            if why:
+                logger.warning("QuantMoEExperts.low_bit_prefill = True has no effect for these experts (%s)", why)
+                self._low_bit_prefill = self.low_bit_prefill = False
         if self._prefill:
             why = self._prefill_declined()
             if why:
@@ -198,12 +214,12 @@ class QuantMoEExperts(nn.Module):
             if why:
                 logger.warning("QuantMoEExperts.post_init(batch=True) has no effect for these experts (%s)", why)
                 self._batch = False
-        self._decode_copy = want_decode or self._batch or self._prefill or self._low_bit_batch
+        self._decode_copy = want_decode or self._batch or self._prefill or self._low_bit_batch or self._low_bit_prefill
         if self._decode_copy:
             why = self._decode_copy_declined()
             if why:                                          # known from the metadata: no copy is built for a set the decode plan would decline
                 logger.warning("QuantMoEExperts.post_init(decode_copy=True) has no effect for these experts (%s): no decode copy is built", why)
-                self._decode_copy = self._batch = self._prefill = self._low_bit_batch = False
+                self._decode_copy = self._batch = self._prefill = self._low_bit_batch = self._low_bit_prefill = False
         extra = 0
         for e in range(self.num_experts):
             for l in self[e].layers():
@@ -218,9 +234,10 @@ class QuantMoEExperts(nn.Module):
         m.flags = (_lib.MOE_LOW_BIT if self._low_bit else 0) | (_lib.MOE_LOW_BIT_DECODE if self._low_bit_decode else 0)
         m.gate, m.up, m.down = (ctypes.addressof(a) for a in arrs)
         mb = None
-        if self._low_bit_batch:          # the batch path's own struct over the same layer arrays: the grouped and backward entry points refuse the bit
+        if self._low_bit_batch or self._low_bit_prefill:      # the copy paths' own struct over the same layer arrays (whichever of the two bits are on): the grouped and backward entry points refuse them
             mb = _lib.GptqMoe()
-            mb.E, mb.flags, mb.gate, mb.up, mb.down = m.E, m.flags | _lib.MOE_LOW_BIT_BATCH, m.gate, m.up, m.down
+            copy_bits = (_lib.MOE_LOW_BIT_BATCH if self._low_bit_batch else 0) | (_lib.MOE_LOW_BIT_PREFILL if self._low_bit_prefill else 0)
+            mb.E, mb.flags, mb.gate, mb.up, mb.down = m.E, m.flags | copy_bits, m.gate, m.up, m.down
         table = torch.zeros(max(1, int(lib.gptq_moe_table_bytes(self.num_experts))), dtype=torch.uint8, device=dev)
         self._moe, self._moe_batch, self._keep, self._plans = m, mb, (arrs, table, gate, up, down), {}
         self._table = table
@@ -228,6 +245,7 @@ class QuantMoEExperts(nn.Module):
         self._grad_table = None
         self._batch_ok = False
         self._low_bit_batch_ok = False
+        self._low_bit_prefill_ok = False
         self._prefill_ok = False
         self.decode_copy_bytes = extra
         self._dev = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
@@ -252,13 +270,20 @@ class QuantMoEExperts(nn.Module):
                 self.low_bit_batch = False                       # (said once: the attribute is unset, the experts behave as without it)
                 return self.post_init(decode_copy=want_decode, batch=self._batch, backward=self._backward, low_bit=self._low_bit, prefill=self._prefill,
                                       low_bit_decode=self._low_bit_decode)
-            # 2- / 3-bit experts opened for the batch path alone: the copy is the batch path's, the decode plan (which declines them) has no say
-            dplan = _lib.describe_moe_decode_plan(m, 1, self.top_k) if not (self._low_bit_batch and not self._low_bit_decode) else {"path": "decode"}
+            lpplan = _lib.describe_moe_prefill_plan(mb, 65, self.top_k) if self._low_bit_prefill else None
+            if lpplan is not None and lpplan["path"] != "prefill":
+                logger.warning("QuantMoEExperts.low_bit_prefill = True has no effect for these experts (%s)", _clean_reason(lpplan)["reason"])
+                self.low_bit_prefill = False                     # (said once, as above)
+                return self.post_init(decode_copy=want_decode, batch=self._batch, backward=self._backward, low_bit=self._low_bit, prefill=self._prefill,
+                                      low_bit_decode=self._low_bit_decode)
+            # 2- / 3-bit experts opened for the batch / the prefill path alone: the copy is those paths', the decode plan (which declines them) has no say
+            low_copy_only = (self._low_bit_batch or self._low_bit_prefill) and not self._low_bit_decode
+            dplan = _lib.describe_moe_decode_plan(m, 1, self.top_k) if not low_copy_only else {"path": "decode"}
             if dplan["path"] != "decode":
                 # declined (2- / 3-bit, fp32, a group size the copy does not take, ...): nothing would read the copies -- say so and give their memory back
                 logger.warning("QuantMoEExperts.post_init(decode_copy=True) has no effect for these experts (%s): no decode copy is kept",
                                _clean_reason(dplan)["reason"])
-                # (batch, prefill and low_bit_decode need the copy: declined with it; the low_bit_batch attribute then stands alone and asks the batch plan)
+                # (batch, prefill and low_bit_decode need the copy: declined with it; the low_bit_batch / low_bit_prefill attributes then stand alone and ask their plans)
                 return self.post_init(decode_copy=False, backward=self._backward, low_bit=self._low_bit)
             bplan = _lib.describe_moe_batch_plan(m, 5, self.top_k) if self._batch else None
             if bplan is not None and bplan["path"] != "batch":
@@ -277,6 +302,7 @@ class QuantMoEExperts(nn.Module):
             self._decode_table = dtable
             self._batch_ok = self._batch
             self._low_bit_batch_ok = self._low_bit_batch
+            self._low_bit_prefill_ok = self._low_bit_prefill
             self._prefill_ok = self._prefill
             self._plans = {}
         return self
@@ -287,8 +313,9 @@ class QuantMoEExperts(nn.Module):
             self.post_init(self._decode_copy, self._batch, self._backward, self._low_bit, self._prefill, self._low_bit_decode)
 
     def _moe_of(self, path: str):
-        """The gptq_moe_t a path's entry points take: the batch path of 2- / 3-bit experts has its own (GPTQ_MOE_LOW_BIT_BATCH set)."""
-        return self._moe_batch if path == "batch" and self._moe_batch is not None else self._moe
+        """The gptq_moe_t a path's entry points take: the batch and the prefill path of 2- / 3-bit experts have their own (GPTQ_MOE_LOW_BIT_BATCH /
+        GPTQ_MOE_LOW_BIT_PREFILL set, whichever are on)."""
+        return self._moe_batch if path in ("batch", "prefill") and self._moe_batch is not None else self._moe
 
     def _copy_path_declined(self, word: str, multiple: int, group_rule, low_bit: bool = False) -> str:
         """Why the `word` plan would decline these experts, as far as the layer metadata says (empty: build the copies and ask the plan).  ``low_bit``: the
@@ -316,7 +343,7 @@ class QuantMoEExperts(nn.Module):
     def _decode_copy_declined(self) -> str:
         """Why the decode plan would decline these experts, as far as the layer metadata says (empty: build the copies and ask the plan)."""
         gate, _, down = self[0].layers()
-        if self.bits not in (4, 8) and not ((self._low_bit_decode or self._low_bit_batch) and self.bits in (2, 3)):
+        if self.bits not in (4, 8) and not ((self._low_bit_decode or self._low_bit_batch or self._low_bit_prefill) and self.bits in (2, 3)):
             return f"{self.bits}-bit experts: the decode path takes 4 or 8 bits"
         if gate.scales.dtype not in (torch.float16, torch.bfloat16):
             return "fp32 experts: the decode path takes fp16 / bf16"
@@ -351,7 +378,8 @@ class QuantMoEExperts(nn.Module):
         without grad.  "decode" only when the experts carry a decode copy (``post_init(decode_copy=True)``) and the decode plan accepts (1..4 tokens);
         "batch" only after ``post_init(batch=True)``, for 5..``batch_max_tokens`` tokens; "prefill" only after ``post_init(prefill=True)``, for 65 tokens
         and more; else the grouped path (or the composition).  2- and 3-bit experts: "decode" only after ``post_init(low_bit_decode=True)``, "batch" only
-        with the attribute ``low_bit_batch = True`` at ``post_init``, for 5..min(64, ``low_bit_batch_max_tokens``) tokens."""
+        with the attribute ``low_bit_batch = True`` at ``post_init``, for 5..min(64, ``low_bit_batch_max_tokens``) tokens, "prefill" only with the attribute
+        ``low_bit_prefill = True`` at ``post_init``, for max(65, ``low_bit_prefill_min_tokens``) tokens and more."""
         top_k = top_k or self.top_k
         if self[0].layers()[0].qweight.device.type != "cuda":
             return {"path": "per_expert", "reason": "cpu tensors"}
@@ -359,13 +387,14 @@ class QuantMoEExperts(nn.Module):
         low = self.bits in (2, 3)
         dmax = (min(4, int(self.low_bit_decode_max_tokens)) if self._low_bit_decode else 0) if low else 4
         bmax = min(64, int(self.low_bit_batch_max_tokens if low else self.batch_max_tokens))
-        key = (T, top_k, bmax, dmax)
+        pmin = max(65, int(self.low_bit_prefill_min_tokens)) if low else 65
+        key = (T, top_k, bmax, dmax, pmin)
         d = self._plans.get(key)
         if d is None:
             copy = self._decode_table is not None
             for path, asked in (("decode", copy and 0 < T <= dmax),
                                 ("batch", copy and (self._low_bit_batch_ok if low else self._batch_ok) and 4 < T <= bmax),
-                                ("prefill", copy and self._prefill_ok and T > 64)):      # (prefill declines more than 65535 routed rows: the grouped path)
+                                ("prefill", copy and (self._low_bit_prefill_ok if low else self._prefill_ok) and T >= pmin)):      # (prefill declines more than 65535 routed rows: the grouped path)
                 if asked and d is None:
                     d = _PATHS[path].describe(self._moe_of(path), T, top_k)
                     if d["path"] != path:

@@ -382,13 +382,21 @@ int gptq_describe_adapter_rows_plan(const gptq_adapter_bank_t *const *banks, int
  * gptq_moe_build_decode_table then builds their table with this flag alone as well (the batch path's own checks apply: H and I multiples of 128, its group
  * sizes).  The decode, prefill and fused shared-expert entry points ignore the bit.  The grouped and the backward entry points keep refusing it with their
  * unknown-flag-bits message, as they did before it had a meaning: a caller that runs both paths on such experts keeps two gptq_moe_t over the same layer
- * arrays, one with the bit for the batch path (and its table build), one without for the rest (autogptq_amd/moe.py does). */
+ * arrays, one with the bit for the batch path (and its table build), one without for the rest (autogptq_amd/moe.py does).
+ * GPTQ_MOE_LOW_BIT_PREFILL (independent of the other three; they may be or-ed): the PREFILL path (gptq_moe_prefill_forward and its describe / workspace
+ * twins, any T up to GPTQ_MOE_PREFILL_MAX_ROWS routed rows) also takes 2- and 3-bit experts with a decode copy -- same contract, same launches
+ * (moe_panel_lowbit_kernel), the workspace of the 4-bit set of the same (T, topk, E, H, I), the same plan keys and a trailing "bits=N";
+ * gptq_moe_build_decode_table builds their table with this flag alone as well (without GPTQ_MOE_LOW_BIT_DECODE the check in front of the table is that of
+ * the first copy path whose flag is set: batch, then prefill).  The decode, batch and fused shared-expert entry points ignore the bit; the grouped and the
+ * backward entry points refuse it as an unknown flag bit, exactly as they do GPTQ_MOE_LOW_BIT_BATCH: the second gptq_moe_t of such a caller carries
+ * whichever of the two copy-path bits are on. */
 #define GPTQ_MOE_LOW_BIT 1
 #define GPTQ_MOE_LOW_BIT_DECODE 8
 #define GPTQ_MOE_LOW_BIT_BATCH 0x10
+#define GPTQ_MOE_LOW_BIT_PREFILL 0x20
 typedef struct gptq_moe_t {
     int32_t E;
-    int32_t flags;                     /* 0 | GPTQ_MOE_LOW_BIT | GPTQ_MOE_LOW_BIT_DECODE | GPTQ_MOE_LOW_BIT_BATCH (the field was `reserved`, 0, before: a zeroed struct means what it meant) */
+    int32_t flags;                     /* 0 | GPTQ_MOE_LOW_BIT | GPTQ_MOE_LOW_BIT_DECODE | GPTQ_MOE_LOW_BIT_BATCH | GPTQ_MOE_LOW_BIT_PREFILL (the field was `reserved`, 0, before: a zeroed struct means what it meant) */
     const gptq_layer_t *const *gate;   /* [E] */
     const gptq_layer_t *const *up;     /* [E] */
     const gptq_layer_t *const *down;   /* [E] */
@@ -511,7 +519,8 @@ int gptq_describe_moe_batch_plan(const gptq_moe_t *moe, int T, int topk, char *o
  *   Launches: routing (bm = 64), x into sorted order (act-order sets: through W1's and W3's perm, two planes), gate|up + silu * mul, down, combine: FIVE;
  *   sets with act-order down projections add the gather of H_sorted through W2's perm (six).  No host round trip; the grid is a bound from (T, topk, E),
  *   so a captured graph replays with new routing.
- * Takes 4- and 8-bit fp16 / bf16 experts, plain or act-order, group_size 64 2^n or one group, H and I multiples of 128, E <= 256, topk <= 8,
+ * Takes 4- and 8-bit fp16 / bf16 experts (2- and 3-bit ones with GPTQ_MOE_LOW_BIT_PREFILL in moe->flags: same launches and workspace;
+ * moe_panel_lowbit_kernel reads the copy's 8- / 12-byte lanes in place), plain or act-order, group_size 64 2^n or one group, H and I multiples of 128, E <= 256, topk <= 8,
  * T topk <= 65535, no bias, every expert with its 16-byte aligned decode copy.  Anything else: GPTQ_ERR_UNSUPPORTED with the reason.
  * `table` is the DECODE table (gptq_moe_build_decode_table).
  * Workspace of one call:  GPTQ_WORKSPACE_HEADER_BYTES (left untouched)
@@ -527,7 +536,8 @@ int gptq_moe_prefill_forward(const gptq_moe_t *moe, const void *table, const voi
                              void *h_out, void *workspace, size_t workspace_bytes, void *stream);
 /* Host-only: "path=prefill bm=64 launches=5 tiles=72 nt_pair=2 nt_down=4 waves=8 waves_pair=8 spw_pair=8 spw_down=28 lds=131072" (nt: 32-column blocks per
  * workgroup -- the pair form runs nt_pair blocks of W1 and of W3, the down form nt_down of W2; waves_pair = 4 for act-order gate / up layers; spw: 64-deep
- * steps per wave) or "path=none reason=..." (no decode copy, 2- / 3-bit, fp32, 32-wide groups, ...).  GPTQ_OK either way. */
+ * steps per wave; 2- / 3-bit experts taken under GPTQ_MOE_LOW_BIT_PREFILL: the same keys and a trailing "bits=3") or "path=none reason=..." (no decode
+ * copy, 2- / 3-bit without GPTQ_MOE_LOW_BIT_PREFILL, fp32, 32-wide groups, ...).  GPTQ_OK either way. */
 int gptq_describe_moe_prefill_plan(const gptq_moe_t *moe, int T, int topk, char *out, size_t out_bytes);
 
 /* BACKWARD of the routed layer (additive in ABI 8): the gradients of gptq_moe_forward's formulas with respect to x and topk_w, from the packed weights.

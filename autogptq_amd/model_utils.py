@@ -136,16 +136,7 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
             for e in range(sub.num_experts):
                 in_experts.update(id(l) for l in sub[e].layers())
             expert_copy_bytes += sub.decode_copy_bytes
-            ts = {rows, *range(1, min(rows, 4) + 1)}
-            if expert_batched_decode:
-                ts.add(min(rows, sub.batch_max_tokens))          # the batch path's need grows with T: its largest T
-            if expert_low_bit_batch and sub.bits in (2, 3):
-                ts.add(min(rows, 64, int(sub.low_bit_batch_max_tokens)))      # the same for 2- / 3-bit experts on the batch path
-            if expert_prefill:
-                ts.add(min(rows, 64))                            # the prefill path starts at 65 tokens (its need grows with T: `rows`); below, the other paths' largest T
-            if expert_low_bit_prefill and sub.bits in (2, 3):
-                ts.add(min(rows, max(64, int(sub.low_bit_prefill_min_tokens) - 1)))      # the largest T the other paths serve below the prefill path's threshold
-            need[dev] = max([need.get(dev, 0)] + [sub.workspace_bytes(t, sub.top_k) for t in sorted(ts)])
+            need[dev] = max([need.get(dev, 0)] + [sub.workspace_bytes(t, sub.top_k) for t in sub.workspace_token_counts(rows)])
             if sub._grad_table is not None:
                 need[dev] = max(need[dev], sub.backward_workspace_bytes(rows, sub.top_k))
     for _, sub in model.named_modules():

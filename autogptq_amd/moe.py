@@ -26,9 +26,14 @@
                         ``Glm4MoeMoE``s, on the instances.  Opt-in.
 * ``pack_moe_experts``  pack the dense 3-D expert parameters of a model (``quantizers`` keyed ``...mlp.experts.{e}.w1`` as ``pack_model`` takes)
 
-2- and 3-bit experts: ``post_init(low_bit=True)`` opens the grouped path to them, ``post_init(low_bit_decode=True)`` the decode path (1..4 tokens),
-the attribute ``low_bit_batch = True`` (set before ``post_init``) the batch path (5..64 tokens), the attribute ``low_bit_prefill = True`` (likewise) the
-prefill path (65 tokens and more).
+Which routed path serves a call, and the switch that opens it (``QuantMoEExperts.post_init`` has the rules; every copy path is opt-in):
+
+    path     tokens   4- / 8-bit experts      2- / 3-bit experts
+    decode   1..4     decode_copy=True        low_bit_decode=True
+    batch    5..64    batch=True              attribute low_bit_batch = True, set before post_init
+    prefill  65..     prefill=True            attribute low_bit_prefill = True, likewise
+    grouped  any      always                  low_bit=True
+
 The per-expert composition serves what the grouped kernels do not take (2- / 3-bit experts unless ``post_init(low_bit=True)``, fp32 experts, odd group
 sizes, raw act-order), CPU tensors (which ``QuantLinear`` refuses), and -- by default -- calls under grad where ``hidden_states`` or ``top_k_weights`` require grad: training through the experts gets
 dX and the router-weight gradient from the existing backward of ``QuantLinear``.  After ``post_init(backward=True)`` such a call is ONE autograd node
@@ -53,17 +58,26 @@ logger = getLogger(__name__)
 
 DEFAULT_NAMES = ("w1", "w3", "w2")          # gate, up, down (AutoGPTQ's Mixtral names)
 
-# The routed paths of the C ABI: the describe function, the workspace-bytes and the forward symbol, and the attribute that holds the table the forward reads.
-_Path = namedtuple("_Path", "describe workspace forward table")
+# The routed paths of the C ABI, one record each: the describe function, the workspace-bytes and the forward symbol, the attribute that holds the table the
+# forward reads -- and, for the three paths on the experts' decode copy, everything else the module knows of them: the post_init keyword that opens the
+# path to 4- / 8-bit experts, the switch that opens it to 2- / 3-bit experts (decode: a keyword; batch, prefill: attributes of the module) with its flag
+# bit, the token count its plan is asked at, the multiple the hidden and intermediate sizes must have, its group-size rule (base, other sizes taken, the
+# message's wording; gs >= K is one group; base 0: the copy's k-chunk, 16 values at 8 bits, else 32), and its token window (first, last or None) as a
+# function of the module's tunables and the width class.
+_Path = namedtuple("_Path", "describe workspace forward table switch low_switch low_flag probe multiple groups window", defaults=(None,) * 7)
 _PATHS = {
-    "decode": _Path(_lib.describe_moe_decode_plan, "gptq_moe_decode_workspace_bytes", "gptq_moe_decode_forward", "_decode_table"),
-    "batch": _Path(_lib.describe_moe_batch_plan, "gptq_moe_batch_workspace_bytes", "gptq_moe_batch_forward", "_decode_table"),
-    "prefill": _Path(_lib.describe_moe_prefill_plan, "gptq_moe_prefill_workspace_bytes", "gptq_moe_prefill_forward", "_decode_table"),
+    "decode": _Path(_lib.describe_moe_decode_plan, "gptq_moe_decode_workspace_bytes", "gptq_moe_decode_forward", "_decode_table",
+                    "decode_copy", "low_bit_decode", _lib.MOE_LOW_BIT_DECODE, 1, 64, (0, (), "the decode copy takes {} times a power of two, or one group"),
+                    lambda q, low: (1, min(4, int(q.low_bit_decode_max_tokens)) if low else 4)),
+    "batch": _Path(_lib.describe_moe_batch_plan, "gptq_moe_batch_workspace_bytes", "gptq_moe_batch_forward", "_decode_table",
+                   "batch", "low_bit_batch", _lib.MOE_LOW_BIT_BATCH, 5, 128, (128, (32, 64), "the batch path takes 32, 64, 128 times a power of two, or one group"),
+                   lambda q, low: (5, min(64, int(q.low_bit_batch_max_tokens if low else q.batch_max_tokens)))),
+    "prefill": _Path(_lib.describe_moe_prefill_plan, "gptq_moe_prefill_workspace_bytes", "gptq_moe_prefill_forward", "_decode_table",
+                     "prefill", "low_bit_prefill", _lib.MOE_LOW_BIT_PREFILL, 65, 128, (64, (), "the prefill path takes 64 times a power of two, or one group"),
+                     lambda q, low: (max(65, int(q.low_bit_prefill_min_tokens)) if low else 65, None)),      # (it declines more than 65535 routed rows: the grouped path)
     "grouped": _Path(_lib.describe_moe_plan, "gptq_moe_workspace_bytes", "gptq_moe_forward", "_table"),
 }
-# What the Python side knows of the batch / the prefill path's group-size rule: (base, other sizes taken, the message's wording); gs >= K is one group
-_BATCH_GROUPS = (128, (32, 64), "32, 64, 128 times a power of two, or one group")
-_PREFILL_GROUPS = (64, (), "64 times a power of two, or one group")
+_COPY_PATHS = ("decode", "batch", "prefill")
 
 
 def _clean_reason(d: dict) -> dict:
@@ -103,16 +117,10 @@ class QuantMoEExperts(nn.Module):
         self.top_k = top_k
         self.bits = bits
         self.names = tuple(names)
-        self._decode_copy = False
-        self._batch = False
-        self._backward = False
-        self._low_bit = False
-        self._prefill = False
-        self._low_bit_decode = False
+        # the post_init keywords as the last post_init settled them: what _ensure_init replays (a declined switch is said once, not at every move)
+        self._switches = dict(decode_copy=False, batch=False, backward=False, low_bit=False, prefill=False, low_bit_decode=False)
         self.low_bit_batch = False                  # the switch of the batch path for 2- / 3-bit experts: set before post_init (read there; see its docstring)
-        self._low_bit_batch = False                 # ... what post_init made of it
         self.low_bit_prefill = False                # the switch of the prefill path for 2- / 3-bit experts: set before post_init, like low_bit_batch
-        self._low_bit_prefill = False               # ... what post_init made of it
         self.batch_max_tokens = 64
         self.low_bit_batch_max_tokens = 64          # 2- / 3-bit experts with low_bit_batch = True: the batch path for 5..this many tokens (the kernels take 64)
         self.low_bit_prefill_min_tokens = 65        # 2- / 3-bit experts with low_bit_prefill = True: the prefill path from this many tokens on (never below 65)
@@ -129,13 +137,10 @@ class QuantMoEExperts(nn.Module):
 
     def _invalidate(self):
         self._moe = None
-        self._moe_batch = None
+        self._moe_batch = None                      # the struct of the batch / prefill entry points where it is not _moe (see _moe_of)
         self._decode_table = None
         self._grad_table = None
-        self._batch_ok = False
-        self._low_bit_batch_ok = False
-        self._low_bit_prefill_ok = False
-        self._prefill_ok = False
+        self._live = frozenset()                    # the copy paths ("decode", "batch", "prefill") that post_init settled on: what plan() may name
         self.decode_copy_bytes = 0
         self._keep = ()
         self._plans = {}
@@ -158,206 +163,183 @@ class QuantMoEExperts(nn.Module):
     # ------------------------------------------------------------------ post_init
     def post_init(self, decode_copy: bool = False, batch: bool = False, backward: bool = False, low_bit: bool = False, prefill: bool = False,
                   low_bit_decode: bool = False):
-        """post_init every expert layer and build the pointer table.  Default: WITHOUT a decode copy (1x the packed bytes; act-order layers add their
-        re-sequenced rows) -- calls of any row count run the grouped kernels.  ``decode_copy=True``: the layers also get their decode copy (2x the packed
-        bytes; both layouts stay resident: the grouped path still serves more than 4 tokens), the decode table is built, and calls of 1..4 tokens run the
-        decode kernels (``plan(T)["path"] == "decode"``).  ``batch=True`` (opt-in as well; builds the decode copy and its table if not asked for already):
-        calls of 5..``batch_max_tokens`` (64) tokens run the batch kernels on the copy (``plan(T)["path"] == "batch"``); experts the batch plan declines
-        log the reason once and behave as without the flag.  ``backward=True`` (opt-in as well): calls under grad whose ``hidden_states`` or
-        ``top_k_weights`` require grad run the grouped backward (``last_plan["backward"] == "grouped"``: one autograd node, one gptq_moe_backward call
-        on a pointer table of its own) instead of the per-expert composition; experts the backward plan declines log the reason once and keep the
-        composition.  ``low_bit=True`` (opt-in as well): 2- and 3-bit experts run the grouped kernels too (``plan(T)["path"] == "grouped"`` at every T, and
-        ``backward=True`` yields their grouped backward) instead of the per-expert composition; it changes nothing for 4- and 8-bit experts, and the
-        decode and batch paths keep declining 2 / 3 bits.  ``prefill=True`` (opt-in as well; builds the decode copy and its table if not asked for already): calls of 65
-        tokens and more run the prefill kernels on the copy (``plan(T)["path"] == "prefill"``: 64-row panels of the routed rows, one
-        gptq_moe_prefill_forward call) instead of the grouped path; experts the prefill plan declines log the reason once and behave as without the
-        flag.  ``low_bit_decode=True`` (opt-in as well; implies ``decode_copy=True`` for such experts): 2- and 3-bit experts get their decode copy and
-        calls of 1..``low_bit_decode_max_tokens`` (4) tokens run the decode kernels (``plan(T)["path"] == "decode"``); more tokens run the grouped
-        path with ``low_bit=True``, else the per-expert composition.  ``batch=True`` / ``prefill=True`` have no effect on such experts (logged, dropped);
-        the keyword changes nothing for 4- and 8-bit experts.  The attribute ``low_bit_batch = True``, set before this call (opt-in as well; an attribute like
-        ``batch_max_tokens``, so every later re-initialisation keeps it; builds the decode copy and its table for such experts if nothing else did):
-        calls of 5..min(64, ``low_bit_batch_max_tokens``) tokens on 2- and 3-bit experts run the batch kernels on the copy (``plan(T)["path"] == "batch"``, gptq_moe_batch_forward with GPTQ_MOE_LOW_BIT_BATCH); with ``low_bit_decode=True`` as well the decode path serves
-        1..4 tokens and the batch path 5..64; fewer or more tokens run the grouped path with ``low_bit=True``, else the per-expert composition.  Experts the
-        batch plan declines log the reason once and behave as without the flag; it has no effect on 4- and 8-bit experts (``batch=True`` is their
-        switch).  The attribute ``low_bit_prefill = True``, set before this call (opt-in, an attribute in the same way; builds the decode copy and its
-        table for such experts if nothing else did): calls of max(65, ``low_bit_prefill_min_tokens``) tokens and more on 2- and 3-bit experts run the prefill
-        kernels on the copy (``plan(T)["path"] == "prefill"``, gptq_moe_prefill_forward with GPTQ_MOE_LOW_BIT_PREFILL); fewer tokens run the ladder above
-        (decode, batch, grouped, composition).  Experts the prefill plan declines (sizes that are no multiples of 128, group sizes other than 64 times a
-        power of two or one group, fp32) log the reason once, the attribute is unset and they behave as without it; it has no effect on 4- and 8-bit
-        experts (``prefill=True`` is their switch).  ``decode_copy_bytes`` reports what the copies hold.  A checkpoint-layout release does not apply to expert layers."""
+        """post_init every expert layer and build the pointer tables.  Default: no decode copy (1x the packed bytes; act-order layers add their
+        re-sequenced rows) and every call runs the grouped kernels.  Each path below is opt-in, runs on the experts' decode copy (2x the packed bytes,
+        both layouts resident; ``decode_copy_bytes`` reports the copies) and is what ``plan(T)["path"]`` names inside its token window:
+
+            path     tokens                                      4- / 8-bit experts   2- / 3-bit experts            a decline
+            decode   1..4 (low_bit_decode_max_tokens)            decode_copy=True     low_bit_decode=True           logged; no copy is built or kept: batch=, prefill=
+                                                                                                                    and low_bit_decode= go with it, the two attributes
+                                                                                                                    then stand alone and ask their own plans
+            batch    5..64 (batch_max_tokens /                   batch=True           attribute low_bit_batch       logged; the switch is dropped (the attribute unset)
+                     low_bit_batch_max_tokens, at most 64)                                                          and the experts behave as without it
+            prefill  65.. (low_bit_prefill_min_tokens,           prefill=True         attribute low_bit_prefill     the same
+                     at least 65)
+
+        A switch of the other width class has no effect: ``batch=`` / ``prefill=`` on 2- / 3-bit experts are logged and dropped, the low-bit switches
+        change nothing for 4- / 8-bit experts.  Any switch of a path builds the copy; 2- / 3-bit experts opened for batch or prefill alone do not ask
+        the decode plan.  The attributes are set before this call (like the ``*_tokens`` tunables they survive every re-initialisation) and run
+        gptq_moe_batch_forward / gptq_moe_prefill_forward with GPTQ_MOE_LOW_BIT_BATCH / _PREFILL on a struct of their own.  Outside the windows:
+        the grouped path -- for 2- / 3-bit experts only with ``low_bit=True`` (forward and, with ``backward=True``, backward; nothing changes for
+        4- / 8-bit experts), else the per-expert composition.  ``backward=True``: calls under grad whose ``hidden_states`` or ``top_k_weights`` require
+        grad run the grouped backward (``last_plan["backward"] == "grouped"``: one autograd node, one gptq_moe_backward call on a pointer table of its
+        own); experts the backward plan declines log the reason and keep the composition.  A checkpoint-layout release does not apply to expert layers."""
         dev = self[0].layers()[0].qweight.device
         if dev.type != "cuda":
             raise RuntimeError(f"mi355x QuantMoEExperts.post_init needs the module on a ROCm GPU device (got {dev}); there is no CPU path.")
-        want_decode, self._batch, self._backward, self._low_bit = bool(decode_copy), bool(batch), bool(backward), bool(low_bit)
-        self._prefill, self._low_bit_decode = bool(prefill), bool(low_bit_decode)
-        self._low_bit_batch = bool(self.low_bit_batch) and self.bits in (2, 3)      # (no effect on 4- and 8-bit experts)
-        if self._low_bit_decode and self.bits in (2, 3):
-            want_decode = True
-        if self._low_bit_batch:
-            why = self._copy_path_declined("batch", 128, _BATCH_GROUPS, low_bit=True)
-            if why:
-                logger.warning("QuantMoEExperts.low_bit_batch = True has no effect for these experts (%s)", why)
-                self._low_bit_batch = self.low_bit_batch = False
-        self._low_bit_prefill = bool(self.low_bit_prefill) and self.bits in (2, 3)      # (no effect on 4- and 8-bit experts)
-        if self._low_bit_prefill:
-            why = self._copy_path_declined("prefill", 128, _PREFILL_GROUPS, low_bit=True)
-            if why:
-                logger.warning("QuantMoEExperts.low_bit_prefill = True has no effect for these experts (%s)", why)
-                self._low_bit_prefill = self.low_bit_prefill = False
-        if self._prefill:
-            why = self._prefill_declined()
-            if why:
-                logger.warning("QuantMoEExperts.post_init(prefill=True) has no effect for these experts (%s)", why)
-                self._prefill = False
-        if self._batch:
-            why = self._batch_declined()
-            if why:
-                logger.warning("QuantMoEExperts.post_init(batch=True) has no effect for these experts (%s)", why)
-                self._batch = False
-        self._decode_copy = want_decode or self._batch or self._prefill or self._low_bit_batch or self._low_bit_prefill
-        if self._decode_copy:
-            why = self._decode_copy_declined()
+        low = self.bits in (2, 3)
+        sw = dict(decode_copy=bool(decode_copy), batch=bool(batch), backward=bool(backward), low_bit=bool(low_bit), prefill=bool(prefill),
+                  low_bit_decode=bool(low_bit_decode))
+        want_decode = sw["decode_copy"] or (sw["low_bit_decode"] and low)
+
+        def drop(switch, why):
+            """Say once that a switch has no effect, and take it back: an attribute is unset, a keyword is not replayed."""
+            said = f"post_init({switch}=True)" if switch in sw else f"{switch} = True"
+            logger.warning("QuantMoEExperts.%s has no effect for these experts (%s)", said, why)
+            if switch in sw:
+                sw[switch] = False
+            else:
+                setattr(self, switch, False)
+
+        # 1. the one live switch per path for this width, as far as the layer metadata says (asked in the order the warnings have always come in: the
+        #    attributes -- no effect on 4- and 8-bit experts --, then prefill= and batch=, which 2- and 3-bit experts always decline)
+        live = set()
+        for name, attribute in (("batch", True), ("prefill", True), ("prefill", False), ("batch", False)):
+            switch = _PATHS[name].low_switch if attribute else _PATHS[name].switch
+            if (low and getattr(self, switch)) if attribute else sw[switch]:
+                why = self._declined(name, low_bit=attribute)
+                if why:
+                    drop(switch, why)
+                else:
+                    live.add(name)
+        built = gplan = None
+        while True:
+            # 2. the layers (again only when the need for a decode copy changed) and the structs
+            copy = want_decode or bool(live)
+            why = self._declined("decode", low_bit=sw["low_bit_decode"] or bool(live)) if copy else ""
             if why:                                          # known from the metadata: no copy is built for a set the decode plan would decline
                 logger.warning("QuantMoEExperts.post_init(decode_copy=True) has no effect for these experts (%s): no decode copy is built", why)
-                self._decode_copy = self._batch = self._prefill = self._low_bit_batch = self._low_bit_prefill = False
-        extra = 0
-        for e in range(self.num_experts):
-            for l in self[e].layers():
-                l.post_init(tiled=self._decode_copy, release_checkpoint_layout=False)
-                if l._qweight_tiled is not None:
-                    extra += l._qweight_tiled.numel() + l._qconst_tiled.numel()
+                copy = want_decode = sw["batch"] = sw["prefill"] = False
+                live.clear()
+            if copy != built:
+                built, extra = copy, 0
+                for e in range(self.num_experts):
+                    for l in self[e].layers():
+                        l.post_init(tiled=copy, release_checkpoint_layout=False)
+                        if l._qweight_tiled is not None:
+                            extra += l._qweight_tiled.numel() + l._qconst_tiled.numel()
+            gate, up, down = self.projections()
+            arrs = [(ctypes.POINTER(_lib.GptqLayer) * self.num_experts)(*[ctypes.pointer(l._layer) for l in ls]) for ls in (gate, up, down)]
+            m = _lib.GptqMoe()
+            m.E = self.num_experts
+            m.flags = (_lib.MOE_LOW_BIT if sw["low_bit"] else 0) | (_lib.MOE_LOW_BIT_DECODE if sw["low_bit_decode"] else 0)
+            m.gate, m.up, m.down = (ctypes.addressof(a) for a in arrs)
+            mb = None
+            if low and live:      # the copy paths' own struct over the same layer arrays (whichever of the two bits are on): the grouped and backward entry points refuse them
+                mb = _lib.GptqMoe()
+                mb.E, mb.flags, mb.gate, mb.up, mb.down = m.E, m.flags | sum(_PATHS[name].low_flag for name in live), m.gate, m.up, m.down
+            if sw["backward"] and gplan is None:
+                gplan = _lib.describe_moe_backward_plan(m, 1, self.top_k)
+                if gplan["path"] != "grouped_backward":
+                    logger.warning("QuantMoEExperts.post_init(backward=True) has no effect for these experts (%s): calls under grad keep the per-expert "
+                                   "composition", _clean_reason(gplan)["reason"])
+            # 3. the plans, in the order they have always been asked: the attributes' first on 2- / 3-bit experts, the decode plan first on 4- / 8-bit ones
+            declined = None
+            # 2- / 3-bit experts opened for the batch / the prefill path alone: the copy is those paths', the decode plan (which declines them) has no say
+            ask_decode = not (low and live and not sw["low_bit_decode"])
+            for name in (("batch", "prefill", "decode") if low else _COPY_PATHS):
+                if copy and (name in live or (name == "decode" and ask_decode)):
+                    d = _PATHS[name].describe(m if mb is None or name == "decode" else mb, _PATHS[name].probe, self.top_k)
+                    if d["path"] != name:
+                        declined = name
+                        break
+            if declined is None:
+                break
+            # 4. drop what declined, and what goes with it
+            why = _clean_reason(d)["reason"]
+            if declined == "decode":
+                # declined (fp32, a group size the copy does not take, ...): nothing would read the copies -- say so and give their memory back
+                logger.warning("QuantMoEExperts.post_init(decode_copy=True) has no effect for these experts (%s): no decode copy is kept", why)
+                # (batch, prefill and low_bit_decode need the copy: declined with it; the low_bit_batch / low_bit_prefill attributes then stand alone and ask their plans)
+                want_decode = sw["batch"] = sw["prefill"] = sw["low_bit_decode"] = False
+                if not low:
+                    live.clear()
+            else:
+                drop(getattr(_PATHS[declined], "low_switch" if low else "switch"), why)
+                live.discard(declined)
         lib = _lib.load()
-        gate, up, down = self.projections()
-        arrs = [(ctypes.POINTER(_lib.GptqLayer) * self.num_experts)(*[ctypes.pointer(l._layer) for l in ls]) for ls in (gate, up, down)]
-        m = _lib.GptqMoe()
-        m.E = self.num_experts
-        m.flags = (_lib.MOE_LOW_BIT if self._low_bit else 0) | (_lib.MOE_LOW_BIT_DECODE if self._low_bit_decode else 0)
-        m.gate, m.up, m.down = (ctypes.addressof(a) for a in arrs)
-        mb = None
-        if self._low_bit_batch or self._low_bit_prefill:      # the copy paths' own struct over the same layer arrays (whichever of the two bits are on): the grouped and backward entry points refuse them
-            mb = _lib.GptqMoe()
-            copy_bits = (_lib.MOE_LOW_BIT_BATCH if self._low_bit_batch else 0) | (_lib.MOE_LOW_BIT_PREFILL if self._low_bit_prefill else 0)
-            mb.E, mb.flags, mb.gate, mb.up, mb.down = m.E, m.flags | copy_bits, m.gate, m.up, m.down
         table = torch.zeros(max(1, int(lib.gptq_moe_table_bytes(self.num_experts))), dtype=torch.uint8, device=dev)
         self._moe, self._moe_batch, self._keep, self._plans = m, mb, (arrs, table, gate, up, down), {}
         self._table = table
-        self._decode_table = None
-        self._grad_table = None
-        self._batch_ok = False
-        self._low_bit_batch_ok = False
-        self._low_bit_prefill_ok = False
-        self._prefill_ok = False
+        self._decode_table = self._grad_table = None
+        self._live = frozenset()                             # (set with the decode table, below)
         self.decode_copy_bytes = extra
         self._dev = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
         self._w_dtype = gate[0].scales.dtype
-        if self.plan(1, self.top_k)["path"] == "grouped":          # (a declined layer set has no valid table: it runs per expert)
-            with torch.cuda.device(self._dev):
-                _lib.check(lib.gptq_moe_build_table(ctypes.byref(m), table.data_ptr(), _lib.current_stream_handle(self._dev)))
-        if self._backward:
-            gplan = _lib.describe_moe_backward_plan(m, 1, self.top_k)
-            if gplan["path"] != "grouped_backward":
-                logger.warning("QuantMoEExperts.post_init(backward=True) has no effect for these experts (%s): calls under grad keep the per-expert "
-                               "composition", _clean_reason(gplan)["reason"])
-            else:
+        sw["decode_copy"] = copy
+        self._switches = sw
+        with torch.cuda.device(self._dev):
+            stream = _lib.current_stream_handle(self._dev)
+            if _PATHS["grouped"].describe(m, 1, self.top_k)["path"] == "grouped":          # (a declined layer set has no valid table: it runs per expert)
+                _lib.check(lib.gptq_moe_build_table(ctypes.byref(m), table.data_ptr(), stream))
+            if gplan is not None and gplan["path"] == "grouped_backward":
                 gtable = torch.zeros(max(1, int(lib.gptq_moe_grad_table_bytes(self.num_experts))), dtype=torch.uint8, device=dev)
-                with torch.cuda.device(self._dev):
-                    _lib.check(lib.gptq_moe_build_grad_table(ctypes.byref(m), gtable.data_ptr(), _lib.current_stream_handle(self._dev)))
+                _lib.check(lib.gptq_moe_build_grad_table(ctypes.byref(m), gtable.data_ptr(), stream))
                 self._grad_table = gtable
-        if self._decode_copy:
-            lbplan = _lib.describe_moe_batch_plan(mb, 5, self.top_k) if self._low_bit_batch else None
-            if lbplan is not None and lbplan["path"] != "batch":
-                logger.warning("QuantMoEExperts.low_bit_batch = True has no effect for these experts (%s)", _clean_reason(lbplan)["reason"])
-                self.low_bit_batch = False                       # (said once: the attribute is unset, the experts behave as without it)
-                return self.post_init(decode_copy=want_decode, batch=self._batch, backward=self._backward, low_bit=self._low_bit, prefill=self._prefill,
-                                      low_bit_decode=self._low_bit_decode)
-            lpplan = _lib.describe_moe_prefill_plan(mb, 65, self.top_k) if self._low_bit_prefill else None
-            if lpplan is not None and lpplan["path"] != "prefill":
-                logger.warning("QuantMoEExperts.low_bit_prefill = True has no effect for these experts (%s)", _clean_reason(lpplan)["reason"])
-                self.low_bit_prefill = False                     # (said once, as above)
-                return self.post_init(decode_copy=want_decode, batch=self._batch, backward=self._backward, low_bit=self._low_bit, prefill=self._prefill,
-                                      low_bit_decode=self._low_bit_decode)
-            # 2- / 3-bit experts opened for the batch / the prefill path alone: the copy is those paths', the decode plan (which declines them) has no say
-            low_copy_only = (self._low_bit_batch or self._low_bit_prefill) and not self._low_bit_decode
-            dplan = _lib.describe_moe_decode_plan(m, 1, self.top_k) if not low_copy_only else {"path": "decode"}
-            if dplan["path"] != "decode":
-                # declined (2- / 3-bit, fp32, a group size the copy does not take, ...): nothing would read the copies -- say so and give their memory back
-                logger.warning("QuantMoEExperts.post_init(decode_copy=True) has no effect for these experts (%s): no decode copy is kept",
-                               _clean_reason(dplan)["reason"])
-                # (batch, prefill and low_bit_decode need the copy: declined with it; the low_bit_batch / low_bit_prefill attributes then stand alone and ask their plans)
-                return self.post_init(decode_copy=False, backward=self._backward, low_bit=self._low_bit)
-            bplan = _lib.describe_moe_batch_plan(m, 5, self.top_k) if self._batch else None
-            if bplan is not None and bplan["path"] != "batch":
-                logger.warning("QuantMoEExperts.post_init(batch=True) has no effect for these experts (%s)", _clean_reason(bplan)["reason"])
-                return self.post_init(decode_copy=want_decode, backward=self._backward, low_bit=self._low_bit, prefill=self._prefill,
-                                      low_bit_decode=self._low_bit_decode)
-            pplan = _lib.describe_moe_prefill_plan(m, 65, self.top_k) if self._prefill else None
-            if pplan is not None and pplan["path"] != "prefill":
-                logger.warning("QuantMoEExperts.post_init(prefill=True) has no effect for these experts (%s)", _clean_reason(pplan)["reason"])
-                return self.post_init(decode_copy=want_decode, batch=self._batch, backward=self._backward, low_bit=self._low_bit,
-                                      low_bit_decode=self._low_bit_decode)
-            dtable = torch.zeros(max(1, int(lib.gptq_moe_decode_table_bytes(self.num_experts))), dtype=torch.uint8, device=dev)
-            with torch.cuda.device(self._dev):
-                _lib.check(lib.gptq_moe_build_decode_table(ctypes.byref(mb if mb is not None and not self._low_bit_decode else m), dtable.data_ptr(),
-                                                           _lib.current_stream_handle(self._dev)))
-            self._decode_table = dtable
-            self._batch_ok = self._batch
-            self._low_bit_batch_ok = self._low_bit_batch
-            self._low_bit_prefill_ok = self._low_bit_prefill
-            self._prefill_ok = self._prefill
-            self._plans = {}
+            if copy:
+                dtable = torch.zeros(max(1, int(lib.gptq_moe_decode_table_bytes(self.num_experts))), dtype=torch.uint8, device=dev)
+                _lib.check(lib.gptq_moe_build_decode_table(ctypes.byref(self._moe_of("decode_table")), dtable.data_ptr(), stream))
+                self._decode_table = dtable
+                self._live = frozenset(live | {"decode"} if sw["low_bit_decode"] or not low else live)
         return self
 
     def _ensure_init(self):
-        """post_init with the stored flags when the tables were invalidated (a move, a state-dict load, a repack)."""
+        """post_init with the settled switches when the tables were invalidated (a move, a state-dict load, a repack)."""
         if self._moe is None:
-            self.post_init(self._decode_copy, self._batch, self._backward, self._low_bit, self._prefill, self._low_bit_decode)
+            self.post_init(**self._switches)
 
     def _moe_of(self, path: str):
-        """The gptq_moe_t a path's entry points take: the batch and the prefill path of 2- / 3-bit experts have their own (GPTQ_MOE_LOW_BIT_BATCH /
-        GPTQ_MOE_LOW_BIT_PREFILL set, whichever are on)."""
-        return self._moe_batch if path in ("batch", "prefill") and self._moe_batch is not None else self._moe
+        """The gptq_moe_t a path's entry points take ("decode_table": the one the decode table is built from): 2- / 3-bit experts with ``low_bit_batch`` /
+        ``low_bit_prefill`` have one of their own for those paths (GPTQ_MOE_LOW_BIT_BATCH / GPTQ_MOE_LOW_BIT_PREFILL set, whichever are on), which also
+        builds the decode table unless ``low_bit_decode`` opened ``_moe`` to it."""
+        if self._moe_batch is None:
+            return self._moe
+        own = path in ("batch", "prefill") or (path == "decode_table" and not self._switches["low_bit_decode"])
+        return self._moe_batch if own else self._moe
 
-    def _copy_path_declined(self, word: str, multiple: int, group_rule, low_bit: bool = False) -> str:
-        """Why the `word` plan would decline these experts, as far as the layer metadata says (empty: build the copies and ask the plan).  ``low_bit``: the
-        path's own 2- / 3-bit flag is set."""
+    def _declined(self, path: str, low_bit: bool = False) -> str:
+        """Why the plan of a copy path would decline these experts, as far as the layer metadata says (empty: build the copies and ask the plan).
+        ``low_bit``: a switch that opens the path to 2- / 3-bit experts is on."""
+        rule = _PATHS[path]
         gate, _, down = self[0].layers()
-        if self.hidden_dim % multiple or self.intermediate_dim % multiple:
-            return f"hidden and intermediate sizes must be multiples of {multiple}"
-        base, others, text = group_rule
-        for l in (gate, down):
+        sizes = groups = dtype = experts = ""
+        if self.hidden_dim % rule.multiple or self.intermediate_dim % rule.multiple:
+            sizes = f"hidden and intermediate sizes must be multiples of {rule.multiple}"
+        base, others, text = rule.groups
+        base = base or (16 if self.bits == 8 else 32)
+        for l in (down, gate):                               # (gate's group size is the one named where both are refused)
             gs, q = l.group_size, l.group_size // base
             if not (gs in others or gs >= l.infeatures or (gs % base == 0 and q & (q - 1) == 0)):
-                return f"group_size {gs}: the {word} path takes {text}"
-        if self.bits in (2, 3) and not low_bit:
-            return f"{self.bits}-bit experts: the {word} path takes 4 or 8 bits"
-        return self._decode_copy_declined().replace("the decode path", f"the {word} path")
-
-    def _batch_declined(self) -> str:
-        """Why the batch plan would decline these experts, as far as the layer metadata says."""
-        return self._copy_path_declined("batch", 128, _BATCH_GROUPS)
-
-    def _prefill_declined(self) -> str:
-        """Why the prefill plan would decline these experts, as far as the layer metadata says."""
-        return self._copy_path_declined("prefill", 128, _PREFILL_GROUPS)
-
-    def _decode_copy_declined(self) -> str:
-        """Why the decode plan would decline these experts, as far as the layer metadata says (empty: build the copies and ask the plan)."""
-        gate, _, down = self[0].layers()
-        if self.bits not in (4, 8) and not ((self._low_bit_decode or self._low_bit_batch or self._low_bit_prefill) and self.bits in (2, 3)):
-            return f"{self.bits}-bit experts: the decode path takes 4 or 8 bits"
+                groups = f"group_size {gs}: {text.format(base)}"
+        wide_only = f"{self.bits}-bit experts: the {path} path takes 4 or 8 bits" if self.bits in (2, 3) and not low_bit else ""
+        if path != "decode":      # the path's own rules, then the copy's in the path's name
+            return sizes or groups or wide_only or self._declined("decode", low_bit).replace("the decode path", f"the {path} path")
         if gate.scales.dtype not in (torch.float16, torch.bfloat16):
-            return "fp32 experts: the decode path takes fp16 / bf16"
-        if self.hidden_dim % 64 or self.intermediate_dim % 64:
-            return "hidden and intermediate sizes must be multiples of 64"
+            dtype = "fp32 experts: the decode path takes fp16 / bf16"
         if not 1 <= self.num_experts <= 256 or not 1 <= self.top_k <= 8:
-            return "the decode path takes up to 256 experts and topk up to 8"
-        kpl = 16 if self.bits == 8 else 32
-        for l in (gate, down):
-            gs, K = l.group_size, l.infeatures
-            gu = gs // kpl
-            if gs < K and (gs % kpl or gu & (gu - 1)):
-                return f"group_size {gs}: the decode copy takes {kpl} times a power of two, or one group"
-        return ""
+            experts = "the decode path takes up to 256 experts and topk up to 8"
+        return wide_only or dtype or sizes or experts or groups
+
+    def workspace_token_counts(self, rows: int) -> list:
+        """The token counts up to ``rows`` whose ``workspace_bytes`` a scratch for calls of 1..``rows`` tokens must cover: ``rows`` itself, the decode
+        path's 1..4, and where a window of a settled copy path ends or begins below ``rows`` (a path's need grows with T: its own largest T, or the
+        largest T of the paths below it)."""
+        self._ensure_init()
+        ts = {rows, *range(1, min(rows, 4) + 1)}
+        for name in self._live:
+            first, last = _PATHS[name].window(self, self.bits in (2, 3))
+            ts.add(min(rows, last or first - 1))
+        return sorted(ts)
 
     def workspace_bytes(self, T: int, top_k: "int | None" = None) -> int:
         """Scratch of one call with T tokens on the path ``plan(T)`` names."""
@@ -375,34 +357,27 @@ class QuantMoEExperts(nn.Module):
 
     def plan(self, T: int, top_k: "int | None" = None) -> dict:
         """{"path": "decode" | "batch" | "prefill" | "grouped" | "per_expert", "reason": ...} (+ the launch / tile geometry) for T tokens: what moe_forward runs
-        without grad.  "decode" only when the experts carry a decode copy (``post_init(decode_copy=True)``) and the decode plan accepts (1..4 tokens);
-        "batch" only after ``post_init(batch=True)``, for 5..``batch_max_tokens`` tokens; "prefill" only after ``post_init(prefill=True)``, for 65 tokens
-        and more; else the grouped path (or the composition).  2- and 3-bit experts: "decode" only after ``post_init(low_bit_decode=True)``, "batch" only
-        with the attribute ``low_bit_batch = True`` at ``post_init``, for 5..min(64, ``low_bit_batch_max_tokens``) tokens, "prefill" only with the attribute
-        ``low_bit_prefill = True`` at ``post_init``, for max(65, ``low_bit_prefill_min_tokens``) tokens and more."""
+        without grad.  A copy path only where ``post_init`` settled on it (its docstring has the switches), T lies in the path's window and its plan
+        accepts; else the grouped path (or the composition)."""
         top_k = top_k or self.top_k
         if self[0].layers()[0].qweight.device.type != "cuda":
             return {"path": "per_expert", "reason": "cpu tensors"}
         self._ensure_init()
-        low = self.bits in (2, 3)
-        dmax = (min(4, int(self.low_bit_decode_max_tokens)) if self._low_bit_decode else 0) if low else 4
-        bmax = min(64, int(self.low_bit_batch_max_tokens if low else self.batch_max_tokens))
-        pmin = max(65, int(self.low_bit_prefill_min_tokens)) if low else 65
-        key = (T, top_k, bmax, dmax, pmin)
+        key = (T, top_k, self.batch_max_tokens, self.low_bit_batch_max_tokens, self.low_bit_decode_max_tokens, self.low_bit_prefill_min_tokens)
         d = self._plans.get(key)
         if d is None:
-            copy = self._decode_table is not None
-            for path, asked in (("decode", copy and 0 < T <= dmax),
-                                ("batch", copy and (self._low_bit_batch_ok if low else self._batch_ok) and 4 < T <= bmax),
-                                ("prefill", copy and (self._low_bit_prefill_ok if low else self._prefill_ok) and T >= pmin)):      # (prefill declines more than 65535 routed rows: the grouped path)
-                if asked and d is None:
-                    d = _PATHS[path].describe(self._moe_of(path), T, top_k)
-                    if d["path"] != path:
-                        d = None
+            for name in _COPY_PATHS:
+                if name in self._live and d is None:
+                    first, last = _PATHS[name].window(self, self.bits in (2, 3))
+                    if first <= T and (last is None or T <= last):
+                        d = _PATHS[name].describe(self._moe_of(name), T, top_k)
+                        if d["path"] != name:
+                            d = None
             if d is None:
                 d = _PATHS["grouped"].describe(self._moe, T, top_k)
             self._plans[key] = _clean_reason(d)
         return dict(d)
+
 
     def forward(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor) -> torch.Tensor:
         return moe_forward(self, hidden_states, top_k_index, top_k_weights)
@@ -424,7 +399,7 @@ def moe_forward(experts: QuantMoEExperts, x: torch.Tensor, top_k_index: torch.Te
     grad = torch.is_grad_enabled() and (x.requires_grad or top_k_weights.requires_grad)
     if x.device.type != "cuda":
         experts.last_plan = {"path": "per_expert", "reason": "cpu tensors"}
-    elif grad and experts._backward and _grouped_backward_ready(experts):
+    elif grad and experts._switches["backward"] and _grouped_backward_ready(experts):
         if return_intermediate:
             raise RuntimeError("moe_forward: return_intermediate is not available under grad")
         return _MoEBackward.apply(experts, x, top_k_index, top_k_weights)

@@ -222,7 +222,7 @@ def test_the_switch_is_opt_in_and_composes(bits, caplog):
     q.low_bit_batch = True
     caplog.clear()
     q.post_init(batch=True)
-    assert "post_init(batch=True) has no effect" in caplog.text and not q._batch_ok and q._low_bit_batch_ok
+    assert "post_init(batch=True) has no effect" in caplog.text and not q._switches["batch"] and "batch" in q._live
     assert [q.plan(T)["path"] for T in (1, 4, 5, 64, 65)] == ["per_expert", "per_expert", "batch", "batch", "per_expert"]
     assert q._moe.flags == 0 and q._moe_batch.flags == BAT
     # with low_bit_decode and low_bit: decode up to 4, batch 5..64, grouped beyond; the band can be narrowed per module

@@ -264,7 +264,7 @@ def test_the_switch_is_opt_in_and_survives_a_re_init(bits, caplog):
     caplog.clear()
     q.post_init(batch=True, prefill=True, low_bit=True, low_bit_decode=True)
     assert "post_init(batch=True) has no effect" in caplog.text and "post_init(prefill=True) has no effect" in caplog.text and f"{bits}-bit" in caplog.text
-    assert q._decode_table is not None and not q._batch_ok and not q._prefill_ok
+    assert q._decode_table is not None and not q._switches["batch"] and not q._switches["prefill"] and q._live == {"decode"}
     assert [q.plan(T)["path"] for T in (1, 4, 5, 64, 65)] == ["decode", "decode", "grouped", "grouped", "grouped"]
     # without the keyword: as before
     q.post_init(decode_copy=True, batch=True, low_bit=True)

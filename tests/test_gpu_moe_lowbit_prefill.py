@@ -288,7 +288,7 @@ def test_the_switch_is_opt_in_and_composes(bits, caplog):
     q.low_bit_prefill = True
     caplog.clear()
     q.post_init(prefill=True)
-    assert "post_init(prefill=True) has no effect" in caplog.text and not q._prefill_ok and q._low_bit_prefill_ok
+    assert "post_init(prefill=True) has no effect" in caplog.text and not q._switches["prefill"] and "prefill" in q._live
     assert [q.plan(T)["path"] for T in (1, 4, 5, 64, 65, 300)] == ["per_expert"] * 4 + ["prefill"] * 2
     assert q._moe.flags == 0 and q._moe_batch.flags == PRE
     # the whole ladder: decode up to 4, batch 5..64, prefill from 65

@@ -188,7 +188,7 @@ def test_oracle_agrees_with_autograd_on_a_dense_fp64_twin():
 def test_cpu_module_under_grad_keeps_the_per_expert_composition(monkeypatch):
     from autogptq_amd import moe
     q = moe.QuantMoEExperts(4, 64, 128, 4, 32)
-    q._backward = True                                   # (post_init needs a GPU; the flag alone must not move a CPU call off the composition)
+    q._switches["backward"] = True                                   # (post_init needs a GPU; the flag alone must not move a CPU call off the composition)
     calls = []
     monkeypatch.setattr(moe, "_per_expert", lambda experts, x, idx, w: (calls.append(x.shape), x * 1.0)[1])
     x = torch.zeros((3, 64), dtype=torch.float16, requires_grad=True)

@@ -280,15 +280,14 @@ def test_no_instruction_touches_an_in_flight_register_in_the_new_kernels():
 
 def test_python_carries_the_switch():
     from autogptq_amd.model_utils import autogptq_post_init
-    from autogptq_amd.moe import QuantMoEExperts
+    from autogptq_amd.moe import _PATHS, QuantMoEExperts
     assert inspect.signature(autogptq_post_init).parameters["expert_low_bit_batch"].default is False
     ex = QuantMoEExperts(2, 256, 512, 3, 128)
-    assert ex.low_bit_batch is False and ex._low_bit_batch is False and ex.low_bit_batch_max_tokens == 64
-    assert "3-bit" in ex._decode_copy_declined() and "3-bit experts: the batch path" in ex._batch_declined()
-    assert ex._copy_path_declined("batch", 128, (128, (32, 64), "")) == ex._batch_declined()
-    ex._low_bit_batch = True                                        # what post_init makes of the attribute for 2- / 3-bit experts
-    assert ex._decode_copy_declined() == "" and "3-bit experts: the batch path" in ex._batch_declined()      # batch=True alone stays without effect
-    assert ex._copy_path_declined("batch", 128, (128, (32, 64), ""), low_bit=True) == ""
+    assert ex.low_bit_batch is False and "batch" not in ex._live and ex.low_bit_batch_max_tokens == 64
+    assert "3-bit" in ex._declined("decode") and "3-bit experts: the batch path" in ex._declined("batch")
+    assert (_PATHS["batch"].multiple, _PATHS["batch"].groups[:2]) == (128, (128, (32, 64)))
+    # what post_init makes of the attribute for 2- / 3-bit experts: the copy's and the path's pre-check with low_bit=True
+    assert ex._declined("decode", low_bit=True) == "" and "3-bit experts: the batch path" in ex._declined("batch")      # batch=True alone stays without effect
+    assert ex._declined("batch", low_bit=True) == ""
     odd = QuantMoEExperts(2, 256, 192, 3, 64)
-    odd._low_bit_batch = True
-    assert "multiples of 128" in odd._copy_path_declined("batch", 128, (128, (32, 64), ""), low_bit=True)
+    assert "multiples of 128" in odd._declined("batch", low_bit=True)

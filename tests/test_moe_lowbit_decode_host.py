@@ -178,10 +178,9 @@ def test_python_signatures_carry_the_switch():
     assert list(p) == ["self", "decode_copy", "batch", "backward", "low_bit", "prefill", "low_bit_decode"] and p["low_bit_decode"].default is False
     assert inspect.signature(autogptq_post_init).parameters["expert_low_bit_decode"].default is False
     ex = QuantMoEExperts(2, 256, 512, 3, 128)
-    assert ex._low_bit_decode is False and ex.low_bit_decode_max_tokens == 4
-    assert "3-bit" in ex._decode_copy_declined() and "3-bit" in ex._batch_declined() and "3-bit" in ex._prefill_declined()
-    ex._low_bit_decode = True
-    assert ex._decode_copy_declined() == "" and "3-bit experts: the batch path" in ex._batch_declined() and "3-bit experts: the prefill path" in ex._prefill_declined()
+    assert ex._switches["low_bit_decode"] is False and ex.low_bit_decode_max_tokens == 4
+    assert "3-bit" in ex._declined("decode") and "3-bit" in ex._declined("batch") and "3-bit" in ex._declined("prefill")
+    # with low_bit_decode=True the copy's pre-check is asked with low_bit=True; batch= and prefill= are asked as before
+    assert ex._declined("decode", low_bit=True) == "" and "3-bit experts: the batch path" in ex._declined("batch") and "3-bit experts: the prefill path" in ex._declined("prefill")
     ex4 = QuantMoEExperts(2, 256, 512, 4, 128)
-    ex4._low_bit_decode = True
-    assert ex4._decode_copy_declined() == "" and ex4._batch_declined() == ""
+    assert ex4._declined("decode", low_bit=True) == "" and ex4._declined("batch") == ""

@@ -145,4 +145,4 @@ def test_python_signatures_carry_the_switch():
     assert list(p)[:5] == ["self", "decode_copy", "batch", "backward", "low_bit"] and p["low_bit"].default is False
     p = inspect.signature(autogptq_post_init).parameters
     assert p["expert_low_bit"].default is False
-    assert QuantMoEExperts(2, 256, 512, 3, 128)._low_bit is False
+    assert QuantMoEExperts(2, 256, 512, 3, 128)._switches["low_bit"] is False

@@ -254,20 +254,19 @@ def test_no_instruction_touches_an_in_flight_register_in_the_new_kernels():
 
 def test_python_carries_the_switch():
     from autogptq_amd.model_utils import autogptq_post_init
-    from autogptq_amd.moe import _PREFILL_GROUPS, QuantMoEExperts
+    from autogptq_amd.moe import _PATHS, QuantMoEExperts
     import torch
     assert inspect.signature(autogptq_post_init).parameters["expert_low_bit_prefill"].default is False
     assert list(inspect.signature(QuantMoEExperts.post_init).parameters) == ["self", "decode_copy", "batch", "backward", "low_bit", "prefill", "low_bit_decode"]
     ex = QuantMoEExperts(2, 256, 512, 3, 128)
-    assert ex.low_bit_prefill is False and ex._low_bit_prefill is False and ex._low_bit_prefill_ok is False and ex.low_bit_prefill_min_tokens == 65
-    assert "3-bit" in ex._decode_copy_declined() and "3-bit experts: the prefill path" in ex._prefill_declined()
-    assert ex._copy_path_declined("prefill", 128, _PREFILL_GROUPS) == ex._prefill_declined()
-    ex._low_bit_prefill = True                                      # what post_init makes of the attribute for 2- / 3-bit experts
-    assert ex._decode_copy_declined() == "" and "3-bit experts: the prefill path" in ex._prefill_declined()      # prefill=True alone stays without effect
-    assert ex._copy_path_declined("prefill", 128, _PREFILL_GROUPS, low_bit=True) == ""
+    assert ex.low_bit_prefill is False and "prefill" not in ex._live and ex.low_bit_prefill_min_tokens == 65
+    assert "3-bit" in ex._declined("decode") and "3-bit experts: the prefill path" in ex._declined("prefill")
+    assert (_PATHS["prefill"].multiple, _PATHS["prefill"].groups[:2]) == (128, (64, ()))
+    # what post_init makes of the attribute for 2- / 3-bit experts: the copy's and the path's pre-check with low_bit=True
+    assert ex._declined("decode", low_bit=True) == "" and "3-bit experts: the prefill path" in ex._declined("prefill")      # prefill=True alone stays without effect
+    assert ex._declined("prefill", low_bit=True) == ""
     for args, kw, frag in (((2, 256, 192, 3, 64), {}, "multiples of 128"), ((2, 256, 512, 2, 32), {}, "group_size 32: the prefill path takes 64 times a power of two"),
                            ((2, 256, 512, 2, 96), {}, "group_size 96"), ((2, 256, 512, 3, 128), dict(weight_dtype=torch.float32), "fp32")):
         odd = QuantMoEExperts(*args, **kw)
-        odd._low_bit_prefill = True
-        assert frag in odd._copy_path_declined("prefill", 128, _PREFILL_GROUPS, low_bit=True), frag
+        assert frag in odd._declined("prefill", low_bit=True), frag
     assert ex.plan(300)["path"] == "per_expert"                     # cpu tensors: nothing to plan

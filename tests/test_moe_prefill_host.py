@@ -146,11 +146,11 @@ def test_python_switches_accept_the_flag():
     assert inspect.signature(autogptq_post_init).parameters["expert_prefill"].default is False
     import torch
     q = QuantMoEExperts(4, 256, 512, 4, 128)
-    assert q._prefill is False and q._prefill_declined() == ""
-    assert "group_size 32" in QuantMoEExperts(4, 256, 512, 4, 32)._prefill_declined()
-    assert "multiples of 128" in QuantMoEExperts(4, 256, 192, 4, 64)._prefill_declined()
-    assert "3-bit" in QuantMoEExperts(4, 256, 512, 3, 128)._prefill_declined()
-    assert "fp32" in QuantMoEExperts(4, 256, 512, 4, 128, weight_dtype=torch.float32)._prefill_declined()
+    assert q._switches["prefill"] is False and q._declined("prefill") == ""
+    assert "group_size 32" in QuantMoEExperts(4, 256, 512, 4, 32)._declined("prefill")
+    assert "multiples of 128" in QuantMoEExperts(4, 256, 192, 4, 64)._declined("prefill")
+    assert "3-bit" in QuantMoEExperts(4, 256, 512, 3, 128)._declined("prefill")
+    assert "fp32" in QuantMoEExperts(4, 256, 512, 4, 128, weight_dtype=torch.float32)._declined("prefill")
     assert q.plan(300)["path"] == "per_expert"                            # cpu tensors: nothing to plan
     with pytest.raises(RuntimeError):
         q.post_init(prefill=True)                                         # no CPU path

@@ -18,7 +18,8 @@ ABI_VERSION = 8
 
 GPTQ_F16, GPTQ_BF16, GPTQ_F32 = 0, 1, 2
 ZERO_WRAP, ZERO_NOWRAP = 0, 1
-EPI_NONE, EPI_SILU_MUL = 0, 1
+EPI_NONE, EPI_SILU_MUL, EPI_GELU_TANH_MUL = 0, 1, 2
+EPILOGUE_ENUM = {"none": EPI_NONE, "silu_mul": EPI_SILU_MUL, "gelu_tanh_mul": EPI_GELU_TANH_MUL}      # QuantLinear(epilogue=...) -> gptq_epilogue_t
 
 DTYPE_ENUM = {torch.float16: GPTQ_F16, torch.bfloat16: GPTQ_BF16, torch.float32: GPTQ_F32}
 
@@ -32,7 +33,7 @@ EXPORTS = (
     "gptq_init", "gptq_workspace_bytes_max", "gptq_validate_g_idx",
     "gptq_forward_multi", "gptq_workspace_bytes_multi", "gptq_forward_multi_ex", "gptq_workspace_bytes_multi_ex",
     "gptq_peer_scatter", "gptq_peer_collect", "gptq_peer_gather", "gptq_forward_scatter", "gptq_forward_gather", "gptq_peer_publish",
-    "gptq_mlp_forward", "gptq_mlp_forward_ex", "gptq_workspace_bytes_mlp", "gptq_workspace_bytes_mlp_ex", "gptq_describe_mlp_plan",
+    "gptq_mlp_forward", "gptq_mlp_forward_ex", "gptq_mlp_forward_act", "gptq_workspace_bytes_mlp", "gptq_workspace_bytes_mlp_ex", "gptq_describe_mlp_plan",
     "gptq_moe_table_bytes", "gptq_moe_build_table", "gptq_moe_workspace_bytes", "gptq_moe_forward", "gptq_describe_moe_plan",
     "gptq_moe_decode_table_bytes", "gptq_moe_build_decode_table", "gptq_moe_decode_workspace_bytes", "gptq_moe_decode_forward", "gptq_describe_moe_decode_plan",
     "gptq_moe_batch_workspace_bytes", "gptq_moe_batch_forward", "gptq_describe_moe_batch_plan",
@@ -199,6 +200,7 @@ def load() -> ctypes.CDLL:
     lib.gptq_workspace_bytes_mlp_ex.argtypes = [LP, LP, LP, c_int, POINTER(GptqTuning)]
     lib.gptq_mlp_forward.argtypes = [LP, LP, LP, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]
     lib.gptq_mlp_forward_ex.argtypes = lib.gptq_mlp_forward.argtypes + [POINTER(GptqTuning)]
+    lib.gptq_mlp_forward_act.argtypes = [LP, LP, LP, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]
     lib.gptq_describe_mlp_plan.argtypes = [LP, LP, LP, c_int, POINTER(GptqTuning), c_char_p, c_size_t]
     MP = POINTER(GptqMoe)
     lib.gptq_moe_table_bytes.restype = c_size_t

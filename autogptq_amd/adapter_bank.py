@@ -82,8 +82,8 @@ class LoraBankQuantLinear(nn.Module):
         super().__init__()
         if not isinstance(base, QuantLinear):
             raise TypeError(f"LoraBankQuantLinear wraps an mi355x QuantLinear, got {type(base).__name__}")
-        if getattr(base, "epilogue", "none") == "silu_mul":
-            raise ValueError("LoraBankQuantLinear: a 'silu_mul' layer applies its activation inside the kernel; the adapter term belongs before the "
+        if getattr(base, "epilogue", "none") != "none":      # 'silu_mul' / 'gelu_tanh_mul'
+            raise ValueError(f"LoraBankQuantLinear: a '{base.epilogue}' layer applies its activation inside the kernel; the adapter term belongs before the "
                              "activation -- wrap the gate and up layers instead")
         if r < 8 or r > 64 or r % 8:
             raise ValueError(f"LoraBankQuantLinear: r = {r}: the adapter kernels take r in 8, 16, .., 64 (smaller ranks are zero-padded by load_slot)")

@@ -61,10 +61,10 @@ int check_layer(const gptq_layer_t* L) {
     if ((L->qweight_tiled != nullptr) != (L->tiled_cols != 0) || (L->qweight_tiled != nullptr) != (L->qconst_tiled != nullptr) ||
         (L->tiled_cols != 0 && L->tiled_cols != GPTQ_STRIP_COLS))
         return fail(GPTQ_ERR_UNSUPPORTED, "qweight_tiled, qconst_tiled and tiled_cols (%d) must be given together, tiled_cols = %d", L->tiled_cols, GPTQ_STRIP_COLS);
-    if (L->epilogue != GPTQ_EPI_NONE && L->epilogue != GPTQ_EPI_SILU_MUL)
+    if (L->epilogue != GPTQ_EPI_NONE && !is_gated(L->epilogue))
         return fail(GPTQ_ERR_UNSUPPORTED, "unknown epilogue %d", L->epilogue);
-    if (L->epilogue == GPTQ_EPI_SILU_MUL && L->N % 64)
-        return fail(GPTQ_ERR_SHAPE, "the SILU_MUL epilogue needs out_features (%d) to be a multiple of 64 ([gate | up] halves)", L->N);
+    if (is_gated(L->epilogue) && L->N % 64)
+        return fail(GPTQ_ERR_SHAPE, "the %s epilogue needs out_features (%d) to be a multiple of 64 ([gate | up] halves)", L->epilogue == GPTQ_EPI_SILU_MUL ? "SILU_MUL" : "GELU_TANH_MUL", L->N);
     return GPTQ_OK;
 }
 
@@ -240,7 +240,7 @@ const char* gptq_status_string(int s) {
     }
 }
 
-// Unfused SILU_MUL: y[M, N] goes to the front of the workspace, the elementwise pass writes out[M, N/2].
+// Unfused SILU_MUL / GELU_TANH_MUL: y[M, N] goes to the front of the workspace, the elementwise pass writes out[M, N/2].
 static size_t epi_scratch_bytes(const gptq_layer_t* L, int M) {
     const size_t b = (size_t)M * L->N * dtype_size(L->dtype);
     return (b + 255) / 256 * 256;
@@ -250,7 +250,7 @@ static size_t epi_scratch_bytes(const gptq_layer_t* L, int M) {
 // M = 5 / 8 47.6 / 50.8 -> 19.3 / 19.5 us; M = 1 / 2 stay fused: 16.7 / 21.2 us).  Returns the tuning the inner (epilogue-stripped)
 // call runs with: the caller's, or -- for 3..4 rows, below the planner's own threshold for that kernel -- a local one that asks for it.
 static bool small_batch_stream_for_epilogue(const gptq_layer_t* L, int M) {
-    if (L->epilogue != GPTQ_EPI_SILU_MUL || M < 3 || M > 8) return false;
+    if (!is_gated(L->epilogue) || M < 3 || M > 8) return false;
     gptq_layer_t Lc = *L;
     Lc.epilogue = GPTQ_EPI_NONE;
     const gptq_layer_t* one[1] = {&Lc};
@@ -275,7 +275,7 @@ static const gptq_tuning_t* inner_tuning(const gptq_layer_t* L, int M, const gpt
 // points, separate_panels_pay and gptq_forward_scatter read the route; none of them asks a want_* question itself.
 enum RouteKind {
     ROUTE_TILED,          // decode-copy kernel (tp)
-    ROUTE_TILED_PAIR,     // ... with SiLU * mul as its epilogue (round 5): decode rows of a [gate | up] layer that carries its copy, one launch, no scratch
+    ROUTE_TILED_PAIR,     // ... with act(gate) * up as its epilogue (round 5): decode rows of a [gate | up] layer that carries its copy, one launch, no scratch
     ROUTE_STREAM,         // streamed GEMV (sp)
     ROUTE_STREAM_SEQ,     // x permuted by the pre-pass into the front of the body, then the streamed GEMV on `seq`, the plain copy of the act-order layer (sp)
     ROUTE_GEMM,           // gp
@@ -302,7 +302,7 @@ static ForwardRoute route_forward(const gptq_layer_t* L, int M, const gptq_tunin
     if (want_tiled(one, 1, M, tune, &r.tp) && r.hit(L->epilogue == GPTQ_EPI_NONE ? ROUTE_TILED : ROUTE_TILED_PAIR, r.tp.partial_bytes)) return r;
     if (L->epilogue != GPTQ_EPI_NONE) {
         // fused: the GEMV applies the epilogue itself, where the GEMV is the choice and has the pair form (path = 6 does not fit a layer with an epilogue)
-        if ((tune || !small_batch_stream_for_epilogue(L, M)) && L->epilogue == GPTQ_EPI_SILU_MUL && !want_gemm(L, M, tune, &r.gp)) {
+        if ((tune || !small_batch_stream_for_epilogue(L, M)) && is_gated(L->epilogue) && !want_gemm(L, M, tune, &r.gp)) {
             r.vp = plan_gemv(*L, M, tune);
             r.declined = (r.vp.pair && tune && tune->path == 6) ? 6 : 0;
             if (r.vp.pair && r.hit(ROUTE_GEMV, r.vp.workspace_bytes)) return r;
@@ -490,7 +490,7 @@ static int forward_impl(const gptq_layer_t* L, const void* x, void* out, int M, 
     // y = [gate | up] at the front of the body; the inner call gets the SAME zeroed ticket header and the body behind y (a header carved
     // out of the body would sit on whatever an earlier, larger call left there: its tickets would never reach ksplit - 1)
     if (int rc = forward_routed(r, &r.plain, x, wv.body, M, WsView{wv.header, (char*)wv.body + yb, wv.body_bytes - yb}, stream, r.tuning(tune))) return rc;
-    hipError_t e = launch_silu_mul(wv.body, out, M, L->N, L->dtype, (hipStream_t)stream);
+    hipError_t e = launch_silu_mul(wv.body, out, M, L->N, L->dtype, L->epilogue, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "silu_mul launch");
     return GPTQ_OK;
 }
@@ -733,11 +733,27 @@ static bool mlp_fused_permute(const gptq_layer_t* down, int M, const gptq_tuning
 
 int gptq_mlp_forward(const gptq_layer_t* gate, const gptq_layer_t* up, const gptq_layer_t* down, const void* x, void* out, int M,
                      void* ws, size_t ws_bytes, void* stream) {
-    return gptq_mlp_forward_ex(gate, up, down, x, out, M, ws, ws_bytes, stream, nullptr);
+    return gptq_mlp_forward_act(gate, up, down, GPTQ_EPI_SILU_MUL, x, out, M, ws, ws_bytes, stream);
 }
 
+static int mlp_forward_core(const gptq_layer_t* gate, const gptq_layer_t* up, const gptq_layer_t* down, int act, const void* x, void* out, int M,
+                            void* ws, size_t ws_bytes, void* stream, const gptq_tuning_t* tune);
+
+int gptq_mlp_forward_act(const gptq_layer_t* gate, const gptq_layer_t* up, const gptq_layer_t* down, int act, const void* x, void* out, int M,
+                         void* ws, size_t ws_bytes, void* stream) {
+    return mlp_forward_core(gate, up, down, act, x, out, M, ws, ws_bytes, stream, nullptr);
+}
+
+// (tuning: only the lab variant of reserved[3] and the refusal of a path override; without one this is gptq_mlp_forward_act)
 int gptq_mlp_forward_ex(const gptq_layer_t* gate, const gptq_layer_t* up, const gptq_layer_t* down, const void* x, void* out, int M,
                         void* ws, size_t ws_bytes, void* stream, const gptq_tuning_t* tune) {
+    if (!tune) return gptq_mlp_forward_act(gate, up, down, GPTQ_EPI_SILU_MUL, x, out, M, ws, ws_bytes, stream);
+    return mlp_forward_core(gate, up, down, GPTQ_EPI_SILU_MUL, x, out, M, ws, ws_bytes, stream, tune);
+}
+
+static int mlp_forward_core(const gptq_layer_t* gate, const gptq_layer_t* up, const gptq_layer_t* down, int act, const void* x, void* out, int M,
+                            void* ws, size_t ws_bytes, void* stream, const gptq_tuning_t* tune) {
+    if (!is_gated(act)) return fail(GPTQ_ERR_UNSUPPORTED, "gptq_mlp_forward_act: act must be GPTQ_EPI_SILU_MUL (1) or GPTQ_EPI_GELU_TANH_MUL (2), got %d", act);
     int rc = check_mlp(gate, up, down);
     if (rc) return rc;
     if ((rc = check_io(x, out, M))) return rc;
@@ -765,13 +781,13 @@ int gptq_mlp_forward_ex(const gptq_layer_t* gate, const gptq_layer_t* up, const 
         const GemmPlan& pl = rd.gp;
         if (pl.workspace_bytes > inner.body_bytes)
             return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", gptq_workspace_bytes_mlp_ex(gate, up, down, M, tune), have);
-        hipError_t e = launch_silu_mul2_permute(hg, hu, down->perm, M, down->K, down->dtype, inner.body, (hipStream_t)stream);
+        hipError_t e = launch_silu_mul2_permute(hg, hu, down->perm, M, down->K, down->dtype, act, inner.body, (hipStream_t)stream);
         if (e != hipSuccess) return hip_fail(e, "silu_mul + permute launch (was gptq_init() called on this device?)");
         e = launch_gemm(*down, pl, inner.body, out, M, inner.header, inner.body, (hipStream_t)stream, /*x_permuted=*/true);
         if (e != hipSuccess) return hip_fail(e, "gptq_gemm launch (down projection of gptq_mlp_forward)");
         return GPTQ_OK;
     }
-    hipError_t e = launch_silu_mul2(hg, hu, hg, (size_t)M * gate->N, gate->dtype, (hipStream_t)stream);
+    hipError_t e = launch_silu_mul2(hg, hu, hg, (size_t)M * gate->N, gate->dtype, act, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "silu_mul launch");
     return forward_routed(rd, down, hg, out, M, inner, stream, nullptr);      // (check_mlp: down has no epilogue)
 }

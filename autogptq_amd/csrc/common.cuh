@@ -47,6 +47,16 @@ template <> struct DType<float> {
 
 __host__ __device__ constexpr int dtype_size(int dt) { return dt == GPTQ_F32 ? 4 : 2; }
 
+// ---- gated pair layers ------------------------------------------------------------------------
+// A [gate | up] layer whose epilogue is act(gate) * up (gptq_epilogue_t): the one question every planner and entry point asks of L.epilogue.
+__host__ __device__ constexpr bool is_gated(int epilogue) { return epilogue == GPTQ_EPI_SILU_MUL || epilogue == GPTQ_EPI_GELU_TANH_MUL; }
+// The gate's activation on an fp32 sum, act = the gptq_epilogue_t of the launch (uniform): g * sigmoid(c(g)), SiLU c = g -- the expression every dense kernel
+// held before it became an argument, the same bits -- and tanh-GELU c = 2 sqrt(2/pi) (g + 0.044715 g^3)  (0.5 (1 + tanh(v)) = 1 / (1 + exp(-2 v))).
+__device__ __forceinline__ float gated_act(float g, int act) {
+    const float c = act == GPTQ_EPI_GELU_TANH_MUL ? 1.5957691216057308f * (g + 0.044715f * g * g * g) : g;
+    return g / (1.f + __expf(-c));
+}
+
 // ---- packed-field geometry ------------------------------------------------------------------
 // A "unit" is the smallest run of whole 32-bit words holding whole values:
 //   bits 2/4/8 : 1 word  = 16/8/4 values;   bits 3 : 3 words = 32 values (qlinear_cuda.py:144-162)

@@ -323,7 +323,7 @@ __global__ void __launch_bounds__(1024, (std::is_same_v<T, f16> && !PAIR && !PER
         if (n >= NH || row >= p.M) return;
         if constexpr (PAIR) {
             if (p.bias) { s0 += DType<T>::to_f32(((const T*)p.bias)[n]); s1 += DType<T>::to_f32(((const T*)p.bias)[n + p.pair_off]); }
-            const float g = s0 / (1.f + __expf(-s0));            // silu on the fp32 sum
+            const float g = gated_act(s0, p.act);               // SiLU / tanh-GELU on the fp32 sum
             ((T*)p.out)[(size_t)row * NH + n] = DType<T>::from_f32(g * s1);
         } else if (p.ksplit > 1) {
             p.partial[((size_t)blockIdx.y * p.M + row) * p.N + n] = s0;
@@ -986,7 +986,7 @@ static int pick_mt(int M) { return M >= 8 ? 8 : (M >= 4 ? 4 : (M >= 2 ? 2 : 1));
 static GemvPlan plan_gemv_n(const gptq_layer_t& L, int M, const gptq_tuning_t* tune, int N_cols);
 
 GemvPlan plan_gemv(const gptq_layer_t& L, int M, const gptq_tuning_t* tune) {
-    if (L.epilogue == GPTQ_EPI_SILU_MUL) {
+    if (is_gated(L.epilogue)) {
         // fused epilogue: the workgroup grid covers the N/2 output columns; only the matrix-core kernel implements it
         GemvPlan pl = plan_gemv_n(L, M, tune, L.N / 2);
         if (pl.mfma && pl.ksplit == 1 && pl.ln == 4 && M <= 4) {      // (5..8 rows: the unfused call -- the 8-row PAIR forms spilled and lost to it)
@@ -1110,7 +1110,7 @@ static GemvPlan plan_gemv_n(const gptq_layer_t& L, int M, const gptq_tuning_t* t
     pl.ksplit = ks;
     pl.units_per_split = (pl.units_total + ks - 1) / ks;
     int waves = (tune && tune->waves) ? tune->waves : 0;
-    const bool act_m1 = pl.mfma && pl.use_seq && M == 1 && L.epilogue != GPTQ_EPI_SILU_MUL;
+    const bool act_m1 = pl.mfma && pl.use_seq && M == 1 && !is_gated(L.epilogue);
     if (!waves) {
         waves = (pl.units_per_split + wr - 1) / wr;   // one unit per lane if possible
         if (waves > 16) waves = 16;
@@ -1619,6 +1619,7 @@ hipError_t launch_gemv(const gptq_layer_t& L, const GemvPlan& pl, const void* x,
     p.partial = (float*)workspace;
     p.M = M; p.K = L.K; p.N = L.N; p.group_size = L.group_size; p.zero_mode = L.zero_mode;
     p.pair_off = pl.pair ? L.N / 2 : 0;
+    p.act = L.epilogue;
     p.units_total = pl.units_total; p.units_per_split = pl.units_per_split;
     p.chunk_units = pl.chunk_units; p.ksplit = pl.ksplit;
     {

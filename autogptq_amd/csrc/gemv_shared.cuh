@@ -21,7 +21,8 @@ struct GemvParams {
     int M, K, N, group_size, zero_mode;
     int units_total, units_per_split, chunk_units, ksplit;
     int gu_shift;       // log2(group_size / 8) or -1 (matrix-core 4-bit kernel)
-    int pair_off;       // SILU_MUL epilogue: column distance between the gate and the up half (N / 2), else 0
+    int pair_off;       // gated epilogue: column distance between the gate and the up half (N / 2), else 0
+    int act;            // ... and its gptq_epilogue_t (gated_act)
 };
 // gemv_generic.hip: fp32-math GEMV for any bits / dtype / group structure (fp32 layers, raw act-order g_idx, odd group sizes)
 hipError_t launch_gemv_generic(const gptq_layer_t& L, const GemvPlan& pl, const GemvParams& p, hipStream_t st);

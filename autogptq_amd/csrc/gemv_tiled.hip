@@ -50,8 +50,8 @@ static int tiled_kpl(int bits) { return bits == 8 ? 16 : 32; }          // k per
 static int tiled_chunk_bytes(int bits) { return bits == 3 ? 768 : (bits == 2 ? 512 : 1024); }
 static int tiled_rec_bytes(int bits) { return bits == 8 ? 64 : 48; }
 
-// A [gate | up] layer with the SILU_MUL epilogue: a plain (no act-order) layer whose halves are whole strips
-static bool tiled_pair_layer(const gptq_layer_t& L) { return L.epilogue == GPTQ_EPI_SILU_MUL && L.g_idx == nullptr && L.N % (2 * GPTQ_STRIP_COLS) == 0; }
+// A [gate | up] layer with a gated epilogue (SILU_MUL / GELU_TANH_MUL): a plain (no act-order) layer whose halves are whole strips
+static bool tiled_pair_layer(const gptq_layer_t& L) { return is_gated(L.epilogue) && L.g_idx == nullptr && L.N % (2 * GPTQ_STRIP_COLS) == 0; }
 
 bool tiled_layer_ok(const gptq_layer_t& L) {
     if (!L.qweight_tiled || !L.qconst_tiled || L.tiled_cols != GPTQ_STRIP_COLS || (L.epilogue != GPTQ_EPI_NONE && !tiled_pair_layer(L))) return false;
@@ -79,7 +79,7 @@ TiledPlan plan_tiled(const gptq_layer_t* const* Ls, int n, int M, const gptq_tun
     const gptq_layer_t& A = *Ls[0];
     if (A.bits == 2 && M > 4) return pl;                                          // 2 bits: no 5..8-row form
     int strips = 0, nsum = 0;
-    const bool pair = A.epilogue == GPTQ_EPI_SILU_MUL;                             // one [gate | up] layer: a workgroup per PAIR of strips, M <= 4, no K slices
+    const bool pair = is_gated(A.epilogue);                                        // one [gate | up] layer: a workgroup per PAIR of strips, M <= 4, no K slices
     if (pair && (n != 1 || M > 4)) return pl;
     for (int i = 0; i < n; ++i) {
         const gptq_layer_t& L = *Ls[i];
@@ -231,18 +231,17 @@ hipError_t launch_tiled(const gptq_layer_t* const* Ls, const TiledPlan& pl, cons
         p.peer.owners = (unsigned)pl.strips_total;
     }
     int blk = 0, col = 0;
-    for (int i = 0; i < 4; ++i) p.blk_end[i] = 0x7fffffff;
+    for (int i = 0; i < 3; ++i) p.blk_end[i] = 0x7fffffff;
     for (int i = 0; i < pl.nseg; ++i) {
         const gptq_layer_t& L = *Ls[i];
         blk += L.N / GPTQ_STRIP_COLS / (pl.pair ? 2 : pl.nstr);
-        p.blk_end[i] = blk;
+        if (i < 3) p.blk_end[i] = blk;                                            // (the selector makes three compares: a fourth layer is reached by the first three)
         p.tq[i] = L.qweight_tiled;
         p.cst[i] = L.qconst_tiled;
         p.perm[i] = L.g_idx ? L.perm : nullptr;
         p.seg[i] = TiledSeg{L.bias, outs[i], L.N, col};
         col += L.N;
     }
-    p.blk_end[3] = 0x7fffffff;                                                    // the selector adds three compares: a fourth layer is reached by the first three
     const gptq_layer_t& A = *Ls[0];
     p.x = x;
     p.gran = (unsigned long long*)ws_body;
@@ -264,6 +263,7 @@ hipError_t launch_tiled(const gptq_layer_t* const* Ls, const TiledPlan& pl, cons
     p.waves = pl.waves;
     p.xraw_off = pl.xraw_off;
     p.pair_strips = pl.pair ? A.N / (2 * GPTQ_STRIP_COLS) : 0;
+    p.act = A.epilogue;
     if (pg) {                                                                     // plain layers, 2 or 4 chunks per wave in flight (the compiled forms)
         if (A.g_idx || A.bits == 2 || (pl.u != 2 && pl.u != 4)) return hipErrorInvalidValue;
         TiledPlan plg = pl;

@@ -31,7 +31,8 @@ struct PeerEpi {
 };
 struct TiledParams {
     // ---- bytes 0 .. 127: the entry batch
-    int blk_end[4];          // cumulative strip count up to and including layer i (unused entries, and [3]: INT_MAX)
+    int blk_end[3];          // cumulative strip count up to and including layer i (unused entries: INT_MAX); a fourth layer is reached by the first three compares
+    int act;                 // PAIR kernels: the gptq_epilogue_t of the layer (gated_act) -- in the entry batch, in the word no kernel read (it held blk_end[3] = INT_MAX)
     const void* x;
     int M, K;
     int chunks, chunks_per_split, ksplit, gu_shift, groups, xstride, waves;
@@ -120,7 +121,7 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
     constexpr bool ACT = XM == 1, PEER = XM == 3;          // 3: plain staging + the tensor-parallel epilogue (gemv_tiled_peer.hip)
     // XM = 4 (PAIR, round 5): a [gate | up] layer with the SILU_MUL epilogue (the reference's fused MLP: auto_gptq/nn_modules/fused_llama_mlp.py:131-306).  A
     // workgroup takes strip s of the gate half AND strip s of the up half (N / 32 strips further) behind ONE staged x: the first half of its waves
-    // streams the one, the second half the other; SiLU(gate) * up is formed on the fp32 sums behind the cross-wave reduction (no K slices: the planner).
+    // streams the one, the second half the other; act(gate) * up (SiLU or tanh-GELU: p.act) is formed on the fp32 sums behind the cross-wave reduction (no K slices: the planner).
     constexpr bool PAIR = XM == 4;
     // XM = 5 / 6 (MULTI, round 5): FOUR / TWO adjacent strips of a layer per workgroup behind ONE staged x -- the 5..8-row form staged 64 KiB of x per
     // 16-column strip (K = 4096), which the per-CU L2 pull rate (~50 GB/s, profiles/r03_xfetch_lab.log) turned into microseconds on layers of hundreds of
@@ -157,8 +158,8 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
     typedef unsigned long long u64x8 __attribute__((ext_vector_type(8)));
     typedef unsigned long long u64x4 __attribute__((ext_vector_type(4)));
     static_assert(offsetof(TiledParams, x) == 16 && offsetof(TiledParams, M) == 24 && offsetof(TiledParams, chunks) == 32 && offsetof(TiledParams, pair_strips) == 60 &&
-                  offsetof(TiledParams, tq) == 64 && offsetof(TiledParams, cst) == 96 && offsetof(TiledParams, perm) == 128 && offsetof(TiledParams, xraw_off) == 160, "the entry batch");
-    u32x16 ha;                                                                    // blk_end[4], x, M, K, chunks, chunks_per_split, ksplit, gu_shift, groups, xstride, waves, pair_strips
+                  offsetof(TiledParams, tq) == 64 && offsetof(TiledParams, cst) == 96 && offsetof(TiledParams, perm) == 128 && offsetof(TiledParams, xraw_off) == 160 && offsetof(TiledParams, act) == 12, "the entry batch");
+    u32x16 ha;                                                                    // blk_end[3], act, x, M, K, chunks, chunks_per_split, ksplit, gu_shift, groups, xstride, waves, pair_strips
     u64x8 hb;                                                                     // tq[4], cst[4]
     [[maybe_unused]] u64x4 hp = {};                                               // ACT: perm[4]
     [[maybe_unused]] int xraw_off = 0;
@@ -172,7 +173,7 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
     }
     const int be0 = (int)ha[0], be1 = (int)ha[1], be2 = (int)ha[2], Mrows = (int)ha[6], K = (int)ha[7], nchunks = (int)ha[8], cps = (int)ha[9], ksplit = (int)ha[10],
               gshift = (int)ha[11], G = (int)ha[12], xstride = (int)ha[13], W = (int)ha[14];
-    [[maybe_unused]] const int hstrips = (int)ha[15];                             // PAIR: strips of one half
+    [[maybe_unused]] const int hstrips = (int)ha[15], act = (int)ha[3];           // PAIR: strips of one half; the activation of the epilogue
     typedef __attribute__((address_space(1))) const char gchar;                   // (behind the asm the compiler no longer knows that these are global pointers)
     gchar* const xg = (gchar*)(((unsigned long long)ha[5] << 32) | ha[4]);
     // workgroup -> (strip over all layers, K slice); no XCD remap: strips share nothing but x, which every L2 holds.  A launch without K slices (every launch of
@@ -698,7 +699,7 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
     // pass, and store through pointers held in SGPRs since entry -- no kernel-argument load, no shuffle, no second barrier.  Other wave counts (a forced
     // geometry, a very short K) keep the run-time loops.
     if constexpr (PAIR) {
-        // entry e = (row m, column c): gate = the sum over the first half of the waves, up = over the second half (fixed order), SiLU on the fp32 sum --
+        // entry e = (row m, column c): gate = the sum over the first half of the waves, up = over the second half (fixed order), the activation on the fp32 sum --
         // the arithmetic of the fused GEMV epilogue of rounds 1-3 (gemv.hip) and, up to the one rounding it saves, of silu_mul_kernel (utils.hip)
         const int NH = N >> 1;
         if (tid < E) {
@@ -711,7 +712,7 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
             else for (int w = 0; w < Wh; ++w) { s0 += r[w * ES]; s1 += r[(Wh + w) * ES]; }
             if (m < Mrows && n_t < NH) {
                 if (biasp != nullptr) { s0 += bv0; s1 += bv1; }
-                const float g = s0 / (1.f + __expf(-s0));
+                const float g = gated_act(s0, act);
                 outg[(size_t)m * NH + n_t] = DType<T>::from_f32(g * s1);
             }
         }

@@ -161,9 +161,9 @@ hipError_t launch_prepack_decode(const uint32_t* qweight, const uint32_t* qzeros
 hipError_t launch_unprepack_decode(const uint32_t* tiled, int K, int N, int bits, uint32_t* qweight_out, hipStream_t st);      // the exact inverse (weights)
 bool stream_preferred(const gptq_layer_t& L, int M);                              // single layer: streamed kernel instead of the register one?
 bool multi_preferred(const gptq_layer_t* const* layers, int n, int M);             // several layers sharing x: one streamed launch?
-hipError_t launch_silu_mul2(const void* g, const void* u, void* out, size_t total, int dtype, hipStream_t st);
+hipError_t launch_silu_mul2(const void* g, const void* u, void* out, size_t total, int dtype, int act, hipStream_t st);
 bool silu_mul2_permute_ok(int K, int dtype);            // mlp.hip: SiLU * mul and the x permute of an act-order down projection in one pass
-hipError_t launch_silu_mul2_permute(const void* g, const void* u, const int32_t* perm, int M, int K, int dtype, void* out, hipStream_t st);
+hipError_t launch_silu_mul2_permute(const void* g, const void* u, const int32_t* perm, int M, int K, int dtype, int act, void* out, hipStream_t st);
 hipError_t init_mlp_device();
 // gemm_wide.hip: 128 x 512 prefill tiles, 128 x 128 per wave with the accumulators in AGPRs (4-bit fp16 / bf16; glds: x in k-slot order, staged by LDS DMA)
 bool wide_gemm_ok(const gptq_layer_t& L, int M, bool use_seq, bool xslot_glds);
@@ -351,7 +351,7 @@ hipError_t launch_resequence(const uint32_t* qweight, const int32_t* perm, int K
                              uint32_t* out, hipStream_t st);
 hipError_t launch_awq_unpack(const uint32_t* aq, const uint32_t* az, const void* scales, int K, int N, int group_size, void* w_kn, int8_t* zeros, hipStream_t st);
 hipError_t launch_awq_repack(const uint32_t* aq, const uint32_t* az, int K, int N, int group_size, uint32_t* qweight, uint32_t* qzeros, hipStream_t st);
-hipError_t launch_silu_mul(const void* y, void* out, int M, int N, int dtype, hipStream_t st);
+hipError_t launch_silu_mul(const void* y, void* out, int M, int N, int dtype, int act, hipStream_t st);      // act: GPTQ_EPI_SILU_MUL / GPTQ_EPI_GELU_TANH_MUL (gated_act)
 hipError_t launch_permute_rows16(const void* x, const int32_t* perm, int M, int K, void* x_out, hipStream_t st, bool slot_order = false);
 hipError_t launch_permute_columns(const void* x, const int32_t* perm, int M, int K, int dtype, void* x_out, hipStream_t st);
 // peer.hip: direct peer-store all-gather (y_local / out may be NULL: scatter-only / collect-only)

@@ -10,19 +10,20 @@ namespace gptq {
 namespace mlpk {
 
 template <typename T>
-__device__ __forceinline__ void silu_mul2_body(const T* __restrict__ g, const T* __restrict__ u, T* __restrict__ out, size_t total) {
+__device__ __forceinline__ void silu_mul2_body(const T* __restrict__ g, const T* __restrict__ u, T* __restrict__ out, size_t total, int act) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const float a = DType<T>::to_f32(g[i]), b = DType<T>::to_f32(u[i]);
-        out[i] = DType<T>::from_f32(a / (1.f + __expf(-a)) * b);
+        out[i] = DType<T>::from_f32(gated_act(a, act) * b);
     }
 }
 // one code object for the three dtypes (a launch-uniform branch): the library keeps to its kernel count
-__global__ void __launch_bounds__(256) silu_mul2_kernel(const void* __restrict__ g, const void* __restrict__ u, void* __restrict__ out, size_t total, int dtype) {
-    if (dtype == GPTQ_F16) silu_mul2_body<f16>((const f16*)g, (const f16*)u, (f16*)out, total);
-    else if (dtype == GPTQ_BF16) silu_mul2_body<bf16>((const bf16*)g, (const bf16*)u, (bf16*)out, total);
-    else silu_mul2_body<float>((const float*)g, (const float*)u, (float*)out, total);
+__global__ void __launch_bounds__(256) silu_mul2_kernel(const void* __restrict__ g, const void* __restrict__ u, void* __restrict__ out, size_t total, int dtype, int act) {
+    if (dtype == GPTQ_F16) silu_mul2_body<f16>((const f16*)g, (const f16*)u, (f16*)out, total, act);
+    else if (dtype == GPTQ_BF16) silu_mul2_body<bf16>((const bf16*)g, (const bf16*)u, (bf16*)out, total, act);
+    else silu_mul2_body<float>((const float*)g, (const float*)u, (float*)out, total, act);
 }
 
+// (act, in all three kernels of this file: the gptq_epilogue_t of the call, launch-uniform -- SiLU or tanh-GELU through gated_act, common.cuh)
 // SiLU * mul AND the x permute of an act-order `down` in ONE pass (round 6): out[m][i] = silu(g[m][perm[i]]) * u[m][perm[i]].  gptq_mlp_forward used to run the
 // elementwise pass and then down's own permute pre-pass (permute_rows4_kernel, gemm.hip: 23 us of the 171 of an 11008 -> 4096 act-order layer call at 2048 rows,
 // and a second round trip of the [M, I] activations through memory); the reference's fused MLP hands its c_proj the activations in the order that layer's rows
@@ -31,7 +32,7 @@ __global__ void __launch_bounds__(256) silu_mul2_kernel(const void* __restrict__
 // rows' values; the load phase computes silu(g) * u on fp32 and rounds once (the arithmetic of silu_mul2_kernel: the same bits as the two passes).
 template <typename T>
 __global__ void __launch_bounds__(1024) silu_mul2_permute_rows4_kernel(const unsigned short* __restrict__ g, const unsigned short* __restrict__ u, const int* __restrict__ perm,
-                                                                      int M, int K, unsigned short* __restrict__ out) {
+                                                                      int M, int K, unsigned short* __restrict__ out, int act) {
     extern __shared__ __attribute__((aligned(16))) char smem[];                // [K][4] values
     const int m0 = blockIdx.x * 4;
     size_t ro[4];
@@ -49,7 +50,7 @@ __global__ void __launch_bounds__(1024) silu_mul2_permute_rows4_kernel(const uns
                 for (int h = 0; h < 2; ++h) {
                     const float a = DType<T>::to_f32(__builtin_bit_cast(T, (unsigned short)(gv[w] >> (16 * h))));
                     const float b = DType<T>::to_f32(__builtin_bit_cast(T, (unsigned short)(uv[w] >> (16 * h))));
-                    const T y = DType<T>::from_f32(a / (1.f + __expf(-a)) * b);
+                    const T y = DType<T>::from_f32(gated_act(a, act) * b);
                     pk |= (unsigned)__builtin_bit_cast(unsigned short, y) << (16 * h);
                 }
                 v[r][w] = pk;
@@ -90,24 +91,24 @@ int g_cu_count[64] = {0};          // per device ordinal, filled by init_mlp_dev
 }  // namespace mlpk
 using namespace mlpk;
 
-hipError_t launch_silu_mul2(const void* g, const void* u, void* out, size_t total, int dtype, hipStream_t st) {
+hipError_t launch_silu_mul2(const void* g, const void* u, void* out, size_t total, int dtype, int act, hipStream_t st) {
     int blocks = (int)((total + 255) / 256);
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(silu_mul2_kernel, dim3(blocks), dim3(256), 0, st, g, u, out, total, dtype);
+    hipLaunchKernelGGL(silu_mul2_kernel, dim3(blocks), dim3(256), 0, st, g, u, out, total, dtype, act);
     return hipGetLastError();
 }
 
 // silu(g) * u gathered through perm into out (fp16 / bf16; K % 8 == 0 and 8 K bytes of LDS): hipErrorInvalidValue where the form does not apply (the caller then
 // runs the two passes)
 bool silu_mul2_permute_ok(int K, int dtype) { return (dtype == GPTQ_F16 || dtype == GPTQ_BF16) && K % 8 == 0 && (size_t)K * 8 <= 160 * 1024; }
-hipError_t launch_silu_mul2_permute(const void* g, const void* u, const int32_t* perm, int M, int K, int dtype, void* out, hipStream_t st) {
+hipError_t launch_silu_mul2_permute(const void* g, const void* u, const int32_t* perm, int M, int K, int dtype, int act, void* out, hipStream_t st) {
     if (!silu_mul2_permute_ok(K, dtype) || M <= 0) return hipErrorInvalidValue;
     const dim3 grid((M + 3) / 4), block(K >= 8192 ? 1024 : 512);      // one workgroup per CU at K = 11008 (88 KiB of LDS): 16 waves keep enough loads in flight
     if (dtype == GPTQ_F16)
-        hipLaunchKernelGGL(silu_mul2_permute_rows4_kernel<f16>, grid, block, (size_t)K * 8, st, (const unsigned short*)g, (const unsigned short*)u, perm, M, K, (unsigned short*)out);
+        hipLaunchKernelGGL(silu_mul2_permute_rows4_kernel<f16>, grid, block, (size_t)K * 8, st, (const unsigned short*)g, (const unsigned short*)u, perm, M, K, (unsigned short*)out, act);
     else
-        hipLaunchKernelGGL(silu_mul2_permute_rows4_kernel<bf16>, grid, block, (size_t)K * 8, st, (const unsigned short*)g, (const unsigned short*)u, perm, M, K, (unsigned short*)out);
+        hipLaunchKernelGGL(silu_mul2_permute_rows4_kernel<bf16>, grid, block, (size_t)K * 8, st, (const unsigned short*)g, (const unsigned short*)u, perm, M, K, (unsigned short*)out, act);
     return hipGetLastError();
 }
 

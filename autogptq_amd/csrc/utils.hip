@@ -375,27 +375,27 @@ __global__ void __launch_bounds__(256) permute_columns_kernel(const void* __rest
 // and the GEMV kernels that have no fused epilogue); y is the [M, N] = [gate | up] result already rounded to T, which is
 // exactly what the reference computes without its fused MLP: act_fn(gate_proj(x)) * up_proj(x).
 template <typename T>
-__device__ __forceinline__ void silu_mul_body(const T* __restrict__ y, T* __restrict__ out, int M, int N) {
+__device__ __forceinline__ void silu_mul_body(const T* __restrict__ y, T* __restrict__ out, int M, int N, int act) {
     const int NH = N / 2;
     const size_t total = (size_t)M * NH;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const size_t m = i / NH, n = i - m * NH;
         const float g = DType<T>::to_f32(y[m * N + n]), u = DType<T>::to_f32(y[m * N + n + NH]);
-        out[i] = DType<T>::from_f32(g / (1.f + __expf(-g)) * u);
+        out[i] = DType<T>::from_f32(gated_act(g, act) * u);
     }
 }
 // one code object for the three dtypes (a launch-uniform branch): the library keeps to its kernel count
-__global__ void __launch_bounds__(256) silu_mul_kernel(const void* __restrict__ y, void* __restrict__ out, int M, int N, int dtype) {
-    if (dtype == GPTQ_F16) silu_mul_body<f16>((const f16*)y, (f16*)out, M, N);
-    else if (dtype == GPTQ_BF16) silu_mul_body<bf16>((const bf16*)y, (bf16*)out, M, N);
-    else silu_mul_body<float>((const float*)y, (float*)out, M, N);
+__global__ void __launch_bounds__(256) silu_mul_kernel(const void* __restrict__ y, void* __restrict__ out, int M, int N, int dtype, int act) {
+    if (dtype == GPTQ_F16) silu_mul_body<f16>((const f16*)y, (f16*)out, M, N, act);
+    else if (dtype == GPTQ_BF16) silu_mul_body<bf16>((const bf16*)y, (bf16*)out, M, N, act);
+    else silu_mul_body<float>((const float*)y, (float*)out, M, N, act);
 }
 
-hipError_t launch_silu_mul(const void* y, void* out, int M, int N, int dtype, hipStream_t st) {
+hipError_t launch_silu_mul(const void* y, void* out, int M, int N, int dtype, int act, hipStream_t st) {
     const size_t total = (size_t)M * (N / 2);
     int blocks = (int)((total + 255) / 256);
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(silu_mul_kernel, dim3(blocks), dim3(256), 0, st, y, out, M, N, dtype);
+    hipLaunchKernelGGL(silu_mul_kernel, dim3(blocks), dim3(256), 0, st, y, out, M, N, dtype, act);
     return hipGetLastError();
 }
 

@@ -16,7 +16,7 @@ from typing import Sequence
 import torch
 import torch.nn as nn
 
-from .qlinear_mi355x import QuantLinear
+from .qlinear_mi355x import GATED_ACT, MLP_ACT, QuantLinear
 
 
 def fuse_quant_linears(layers: Sequence[QuantLinear], epilogue: str = "none") -> QuantLinear:
@@ -40,8 +40,8 @@ def fuse_quant_linears(layers: Sequence[QuantLinear], epilogue: str = "none") ->
             raise ValueError("fused layers must share g_idx (act-order projections with different g_idx cannot be fused)")
         if l.zero_mode != a.zero_mode:
             raise ValueError("fused layers must share zero_mode")
-    if epilogue == "silu_mul" and (len(layers) != 2 or layers[0].outfeatures != layers[1].outfeatures):
-        raise ValueError("epilogue='silu_mul' fuses exactly two layers (gate, up) of equal width")
+    if epilogue in GATED_ACT and (len(layers) != 2 or layers[0].outfeatures != layers[1].outfeatures):
+        raise ValueError(f"epilogue='{epilogue}' fuses exactly two layers (gate, up) of equal width")
     n_total = sum(l.outfeatures for l in layers)
     f = QuantLinear(a.bits, a.group_size, a.infeatures, n_total, a.bias is not None, weight_dtype=a.scales.dtype,
                     zero_mode=a.zero_mode, epilogue=epilogue)
@@ -59,9 +59,25 @@ def fuse_qkv(q: QuantLinear, k: QuantLinear, v: QuantLinear) -> QuantLinear:
     return fuse_quant_linears([q, k, v])
 
 
-def fuse_gate_up(gate: QuantLinear, up: QuantLinear) -> QuantLinear:
-    """One layer computing silu(gate(x)) * up(x)."""
-    return fuse_quant_linears([gate, up], epilogue="silu_mul")
+def fuse_gate_up(gate: QuantLinear, up: QuantLinear, act: str = "silu") -> QuantLinear:
+    """One layer computing act(gate(x)) * up(x), act = 'silu' or 'gelu_tanh' (Gemma's GeGLU)."""
+    if act not in MLP_ACT:
+        raise ValueError(f"act must be 'silu' or 'gelu_tanh', got {act!r}")
+    return fuse_quant_linears([gate, up], epilogue=MLP_ACT[act])
+
+
+def gated_act_name(fn) -> "str | None":
+    """The ``act`` of the fused MLP callers for an activation module of the host model, or None (not served: the module is left alone).
+    'gelu_tanh' is the tanh approximation of GELU under any of its names -- transformers' GELUTanh / PytorchGELUTanh, ``gelu_new`` (NewGELUActivation: the
+    same function written with tanh) and nn.GELU(approximate='tanh'); erf GELU is a different function and has no epilogue."""
+    name = type(fn).__name__
+    if name in ("SiLU", "SiLUActivation"):
+        return "silu"
+    if name in ("GELUTanh", "PytorchGELUTanh", "NewGELUActivation"):
+        return "gelu_tanh"
+    if isinstance(fn, nn.GELU) and fn.approximate == "tanh":
+        return "gelu_tanh"
+    return None
 
 
 class _FusedQKVState:
@@ -120,15 +136,19 @@ class FusedGateUpMLP(nn.Module):
     Three mi355x QuantLinears: ONE C-ABI call (gptq_mlp_forward: gate and up in one launch for decode rows, SiLU*mul on fp32, down) over the
     three checkpoint layers as they are -- no concatenated copy of the packed tensors (the reference builds one), so nothing is held twice and
     per-projection act-order is allowed.  A non-quantized down projection: the [gate | up] layer with the SiLU*mul epilogue when gate and up
-    share g_idx, else gate and up through ``forward_multi`` and an elementwise SiLU*mul."""
+    share g_idx, else gate and up through ``forward_multi`` and an elementwise SiLU*mul.
+    ``act``: 'silu' (Llama, Mistral, Qwen) or 'gelu_tanh' (Gemma's GeGLU) -- gptq_mlp_forward_act / the matching epilogue / the torch function."""
 
-    def __init__(self, gate: QuantLinear, up: QuantLinear, down: nn.Module):
+    def __init__(self, gate: QuantLinear, up: QuantLinear, down: nn.Module, act: str = "silu"):
         super().__init__()
+        if act not in MLP_ACT:
+            raise ValueError(f"act must be 'silu' or 'gelu_tanh', got {act!r}")
+        self.act = act
         self.gate_up = None
         self.gate_proj, self.up_proj = gate, up
         if not isinstance(down, QuantLinear):
             try:
-                self.gate_up = fuse_gate_up(gate, up).to(gate.qweight.device)
+                self.gate_up = fuse_gate_up(gate, up, act).to(gate.qweight.device)
                 self.gate_proj = self.up_proj = None
             except ValueError:                      # per-projection act-order
                 pass
@@ -139,10 +159,10 @@ class FusedGateUpMLP(nn.Module):
             return self.down_proj(self.gate_up(x))
         if isinstance(self.down_proj, QuantLinear):               # three mi355x layers: one C-ABI call (gptq_mlp_forward)
             from .qlinear_mi355x import mlp_forward
-            return mlp_forward(self.gate_proj, self.up_proj, self.down_proj, x)
+            return mlp_forward(self.gate_proj, self.up_proj, self.down_proj, x, act=self.act)
         from .qlinear_mi355x import forward_multi
         g, u = forward_multi([self.gate_proj, self.up_proj], x)
-        return self.down_proj(torch.nn.functional.silu(g) * u)
+        return self.down_proj(GATED_ACT[MLP_ACT[self.act]](g) * u)
 
 
 def inject_fused_llama(model: nn.Module, fuse_attention: bool = True, fuse_mlp: bool = True) -> int:
@@ -156,11 +176,11 @@ def inject_fused_llama(model: nn.Module, fuse_attention: bool = True, fuse_mlp: 
                 st = _FusedQKVState((q, k, v))
                 mod.q_proj, mod.k_proj, mod.v_proj = _QKVPart(st, 0), _QKVPart(st, 1), _QKVPart(st, 2)
                 n += 1
-        if fuse_mlp and all(isinstance(getattr(mod, a, None), QuantLinear) for a in ("gate_proj", "up_proj")) and hasattr(mod, "down_proj") \
-                and getattr(getattr(mod, "act_fn", None), "__class__", type(None)).__name__ in ("SiLU", "SiLUActivation"):
+        act = gated_act_name(getattr(mod, "act_fn", None)) if fuse_mlp else None
+        if act is not None and all(isinstance(getattr(mod, a, None), QuantLinear) for a in ("gate_proj", "up_proj")) and hasattr(mod, "down_proj"):
             gate, up = mod.gate_proj, mod.up_proj
             if gate.infeatures == up.infeatures and gate.outfeatures == up.outfeatures and gate.bits == up.bits:
-                fm = FusedGateUpMLP(gate, up, mod.down_proj)
+                fm = FusedGateUpMLP(gate, up, mod.down_proj, act)
                 mod.forward = fm.forward
                 if fm.gate_up is None:
                     # the fused caller only REFERENCES the three projections: it is kept out of the module tree (object.__setattr__), they stay
@@ -170,7 +190,55 @@ def inject_fused_llama(model: nn.Module, fuse_attention: bool = True, fuse_mlp: 
                     mod.fused_mlp = fm
                     del mod.gate_proj, mod.up_proj
                 n += 1
+        if fuse_mlp and _inject_gate_up_proj(mod):
+            n += 1
     return n
 
 
-__all__ = ["fuse_quant_linears", "fuse_qkv", "fuse_gate_up", "inject_fused_llama", "FusedGateUpMLP"]
+def _set_epilogue(layer: QuantLinear, epilogue: str) -> None:
+    """Change the epilogue of an existing layer in place: no tensor is touched; a layer that was initialised is initialised again (its decode copy of a
+    [gate | up] layer pairs the strips of the two halves: the C side decides per epilogue)."""
+    was_initialised = layer._layer is not None
+    layer.epilogue = epilogue
+    layer._invalidate()
+    if was_initialised:
+        layer.post_init()
+
+
+def _inject_gate_up_proj(mod: nn.Module) -> bool:
+    """The MLP of Phi-3 / Phi-4 and of GLM-4's dense blocks: the checkpoint stores [gate | up] as ONE linear ``gate_up_proj`` and the forward is
+    ``gate, up = y.chunk(2, -1); down(up * act(gate))`` -- what a layer with the matching gated epilogue computes.  The layer gets that epilogue in place
+    (state_dict() keys and tensors unchanged) and the module's forward becomes ``down_proj(gate_up_proj(x))``; remove_fused_mlp undoes both."""
+    gu = getattr(mod, "gate_up_proj", None)
+    if not isinstance(gu, QuantLinear) or not hasattr(mod, "down_proj") or gu.epilogue != "none":
+        return False
+    act = gated_act_name(getattr(mod, "activation_fn", None)) or gated_act_name(getattr(mod, "act_fn", None))
+    if act is None or gu.outfeatures % 64 != 0 or gu.g_idx.numel() != gu.infeatures:
+        return False
+    _set_epilogue(gu, MLP_ACT[act])
+
+    def forward(x):
+        return mod.down_proj(mod.gate_up_proj(x))
+    object.__setattr__(mod, "_fused_gate_up_undo", mod.__dict__.get("forward"))      # an instance-level forward someone else bound (None: the class's)
+    mod.forward = forward
+    return True
+
+
+def remove_fused_mlp(model: nn.Module) -> int:
+    """Undo inject_fused_llama's work on ``gate_up_proj`` modules: epilogue 'none' again, the module's own forward again.  Returns the number of modules
+    restored.  (The three-projection shape has no undo.)"""
+    n = 0
+    for mod in list(model.modules()):
+        if "_fused_gate_up_undo" not in mod.__dict__:
+            continue
+        prev = mod.__dict__.pop("_fused_gate_up_undo")
+        if prev is None:
+            del mod.__dict__["forward"]
+        else:
+            mod.forward = prev
+        _set_epilogue(mod.gate_up_proj, "none")
+        n += 1
+    return n
+
+
+__all__ = ["fuse_quant_linears", "fuse_qkv", "fuse_gate_up", "inject_fused_llama", "remove_fused_mlp", "gated_act_name", "FusedGateUpMLP"]

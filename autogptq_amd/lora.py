@@ -53,8 +53,8 @@ class LoraQuantLinear(nn.Module):
         super().__init__()
         if not isinstance(base, QuantLinear):
             raise TypeError(f"LoraQuantLinear wraps an mi355x QuantLinear, got {type(base).__name__}")
-        if getattr(base, "epilogue", "none") == "silu_mul":
-            raise ValueError("LoraQuantLinear: a 'silu_mul' layer applies its activation inside the kernel; the adapter term belongs before the "
+        if getattr(base, "epilogue", "none") != "none":      # 'silu_mul' / 'gelu_tanh_mul'
+            raise ValueError(f"LoraQuantLinear: a '{base.epilogue}' layer applies its activation inside the kernel; the adapter term belongs before the "
                              "activation -- wrap the gate and up layers instead")
         if r <= 0:
             raise ValueError(f"r must be positive, got {r}")

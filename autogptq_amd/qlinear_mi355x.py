@@ -96,6 +96,23 @@ def reserve_rows_scratch(device, nbytes: int) -> torch.Tensor:
     return buf
 
 
+# The gated epilogues (QuantLinear(epilogue=...)) and the activation names of the MLP callers (mlp_forward(act=...), fused.py): the torch function each one
+# fuses -- what the autograd composition and the fallbacks that run single calls apply -- and the gptq_epilogue_t the kernels take.
+def _gelu_tanh(g):
+    return torch.nn.functional.gelu(g, approximate="tanh")
+
+
+GATED_ACT = {"silu_mul": torch.nn.functional.silu, "gelu_tanh_mul": _gelu_tanh}
+MLP_ACT = {"silu": "silu_mul", "gelu_tanh": "gelu_tanh_mul"}      # act name -> epilogue name
+
+
+def _mlp_act(act: str):
+    """(torch function, gptq_epilogue_t) of an MLP caller's ``act``."""
+    if act not in MLP_ACT:
+        raise ValueError(f"act must be 'silu' or 'gelu_tanh', got {act!r}")
+    return GATED_ACT[MLP_ACT[act]], _lib.EPILOGUE_ENUM[MLP_ACT[act]]
+
+
 def _is_sequential_g_idx(g_idx: torch.Tensor, group_size: int) -> bool:
     k = g_idx.numel()
     ref = torch.arange(k, dtype=torch.int64, device=g_idx.device) // group_size
@@ -141,10 +158,10 @@ class QuantLinear(nn.Module):
             raise ValueError(f"weight_dtype must be float16, bfloat16 or float32, got {weight_dtype}")
         if zero_mode not in ("auto", "wrap", "nowrap"):
             raise ValueError("zero_mode must be 'auto', 'wrap' or 'nowrap'")
-        if epilogue not in ("none", "silu_mul"):
-            raise ValueError("epilogue must be 'none' or 'silu_mul'")
-        if epilogue == "silu_mul" and outfeatures % 64 != 0:
-            raise ValueError("epilogue='silu_mul' needs outfeatures divisible by 64 (columns are [gate | up])")
+        if epilogue not in _lib.EPILOGUE_ENUM:
+            raise ValueError("epilogue must be 'none', 'silu_mul' or 'gelu_tanh_mul'")
+        if epilogue in GATED_ACT and outfeatures % 64 != 0:
+            raise ValueError(f"epilogue='{epilogue}' needs outfeatures divisible by 64 (columns are [gate | up])")
 
         self.infeatures = infeatures
         self.outfeatures = outfeatures
@@ -155,7 +172,7 @@ class QuantLinear(nn.Module):
         self.use_cuda_fp16 = use_cuda_fp16            # accepted for make_quant compatibility; unused
         self.kernel_switch_threshold = kernel_switch_threshold
         self.zero_mode = zero_mode
-        # 'silu_mul': the layer holds [gate | up] and forward returns silu(gate(x)) * up(x), [.., outfeatures // 2]
+        # 'silu_mul' / 'gelu_tanh_mul': the layer holds [gate | up] and forward returns act(gate(x)) * up(x), [.., outfeatures // 2]
         self.epilogue = epilogue
 
         G = math.ceil(infeatures / self.group_size)
@@ -202,6 +219,11 @@ class QuantLinear(nn.Module):
     def _load_from_state_dict(self, *args, **kwargs):
         super()._load_from_state_dict(*args, **kwargs)
         self._invalidate()
+
+    @property
+    def out_width(self) -> int:
+        """Columns of forward's result: half of outfeatures for a gated [gate | up] layer."""
+        return self.outfeatures // 2 if self.epilogue in GATED_ACT else self.outfeatures
 
     def resolved_zero_mode(self) -> int:
         """'auto' = the convention of the reference class this backend stands in for: no act-order ->
@@ -273,7 +295,7 @@ class QuantLinear(nn.Module):
         L.zero_mode = self.resolved_zero_mode()
         L.qweight_seq = _lib.ptr(qweight_seq)
         L.perm = _lib.ptr(perm)
-        L.epilogue = _lib.EPI_SILU_MUL if self.epilogue == "silu_mul" else _lib.EPI_NONE
+        L.epilogue = _lib.EPILOGUE_ENUM[self.epilogue]
         L.qweight_tiled = L.qconst_tiled = None
         L.tiled_cols = 0
         # Decode copy (3-, 4- and 8-bit fp16 / bf16 layers; act-order ones from their re-sequenced rows -- the kernel gathers x through perm): what exllamav2's shuffle / Marlin's repack do at load time (q_matrix.cu:19-42,149;
@@ -298,7 +320,7 @@ class QuantLinear(nn.Module):
         self._dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
         self._dev = torch.device("cuda", self._dev_index)
         self._w_dtype = self.scales.dtype
-        self._n_out = self.outfeatures // 2 if self.epilogue == "silu_mul" else self.outfeatures
+        self._n_out = self.out_width
         self._keepalive = (self.qweight, self.qzeros, self.scales, self.g_idx, self.bias, qweight_seq, perm, qweight_tiled, qconst_tiled)
         self._qweight_tiled, self._qconst_tiled = qweight_tiled, qconst_tiled
         self._ws_need = {}
@@ -473,8 +495,8 @@ class QuantLinear(nn.Module):
     # ------------------------------------------------------------------ gradients
     def _forward_grad(self, x: torch.Tensor, tuning=None):
         """forward() when grad mode is on and x requires grad: one _GradInput node (dX = dY . W^T through gptq_grad_input; the buffers get no gradient).
-        The dtype casts either side are ordinary autograd ops, so x.grad comes back in x.dtype.  A 'silu_mul' layer is composed from differentiable
-        pieces: its plain [gate | up] product, then silu(g) * u."""
+        The dtype casts either side are ordinary autograd ops, so x.grad comes back in x.dtype.  A 'silu_mul' / 'gelu_tanh_mul' layer is composed from
+        differentiable pieces: its plain [gate | up] product, then act(g) * u."""
         if self._layer is None and getattr(self, "_parts", None) is None:
             if x.device.type != "cuda":
                 raise RuntimeError("mi355x QuantLinear.forward needs a ROCm GPU tensor "
@@ -484,16 +506,16 @@ class QuantLinear(nn.Module):
             return torch.cat(forward_multi(self._parts, x, tuning), dim=-1)
         w_dtype = self._w_dtype
         xw = x.to(w_dtype) if x.dtype != w_dtype else x
-        if self.epilogue == "silu_mul":
+        if self.epilogue in GATED_ACT:
             y = _GradInput.apply(xw, ((self, True),), tuning)[0]
             h = self.outfeatures // 2
-            y = torch.nn.functional.silu(y[..., :h]) * y[..., h:]
+            y = GATED_ACT[self.epilogue](y[..., :h]) * y[..., h:]
         else:
             y = _GradInput.apply(xw, ((self, False),), tuning)[0]
         return y.to(x.dtype) if x.dtype != w_dtype else y
 
     def _plain_product(self, x: torch.Tensor, tuning=None) -> torch.Tensor:
-        """x @ W + b of a 'silu_mul' layer BEFORE its epilogue ([.., outfeatures]): gptq_forward_ex on a copy of the layer struct with EPI_NONE."""
+        """x @ W + b of a 'silu_mul' / 'gelu_tanh_mul' layer BEFORE its epilogue ([.., outfeatures]): gptq_forward_ex on a copy of the layer struct with EPI_NONE."""
         L = getattr(self, "_layer_plain", None)
         if L is None or L[0] is not self._layer:
             c = _lib.GptqLayer()
@@ -844,24 +866,28 @@ def forward_multi(layers, x: torch.Tensor, tuning: "_lib.GptqTuning | None" = No
 _MULTI: dict = {}
 
 
-def mlp_forward(gate: QuantLinear, up: QuantLinear, down: QuantLinear, x: torch.Tensor, tuning: "_lib.GptqTuning | None" = None):
-    """``down(silu(gate(x)) * up(x))`` for three mi355x QuantLinears through ONE C-ABI call (gptq_mlp_forward): the role of the
+def mlp_forward(gate: QuantLinear, up: QuantLinear, down: QuantLinear, x: torch.Tensor, tuning: "_lib.GptqTuning | None" = None, act: str = "silu"):
+    """``down(act(gate(x)) * up(x))``, act = 'silu' (Llama) or 'gelu_tanh' (Gemma's GeGLU), for three mi355x QuantLinears through ONE C-ABI call
+    (gptq_mlp_forward_act; with a ``tuning``, SiLU only, gptq_mlp_forward_ex): the role of the
     reference's FusedLlamaMLPForQuantizedModel.forward (auto_gptq/nn_modules/fused_llama_mlp.py:157-242).  gate and up run as one
     multi-layer launch for decode rows, the SiLU * mul on fp32, then down -- any bits / act-order / row count the single layers take,
     checkpoint tensors untouched, one Python -> C transition instead of three.  (Round 3's one-launch persistent kernel was measured slower and is a lab
     now -- tools/lab/mlp_ring.hip; ``tuning`` with a path override is refused.)"""
+    act_fn, act_code = _mlp_act(act)
+    if tuning is not None and act != "silu":
+        raise RuntimeError("mlp_forward: a tuning override goes through gptq_mlp_forward_ex, which is the SiLU call")
     for l in (gate, up, down):
         if l._layer is None:
             l.post_init()
     if x.requires_grad and torch.is_grad_enabled():      # composed from differentiable pieces (gate | up as one node)
         g, u = forward_multi([gate, up], x)
-        return down(torch.nn.functional.silu(g) * u)
+        return down(act_fn(g) * u)
     if any(getattr(l, "_released", False) for l in (gate, up, down)):
         if tuning is not None:
             raise RuntimeError("mlp_forward: layers with release_checkpoint_layout=True take no tuning override")
         if x.numel() // max(1, gate.infeatures) > 4:
             g, u = forward_multi([gate, up], x)          # released layers (one shared rows scratch): composed from single calls
-            return down(torch.nn.functional.silu(g) * u)
+            return down(act_fn(g) * u)
     dev = gate._dev
     if x.device != dev:
         raise RuntimeError(f"mi355x mlp_forward: input is on {x.device}, the layers on {dev}")
@@ -900,7 +926,10 @@ def mlp_forward(gate: QuantLinear, up: QuantLinear, down: QuantLinear, x: torch.
         fast = _lib.fast
 
         def launch():
-            if fast is not None and tuning is None and hasattr(fast, "mlp_forward"):
+            if tuning is None and (act_code != _lib.EPI_SILU_MUL or fast is None or not hasattr(fast, "mlp_forward")):
+                return lib.gptq_mlp_forward_act(gate._layer_ref, up._layer_ref, down._layer_ref, act_code, x2.data_ptr(), out.data_ptr(), M,
+                                                buf.data_ptr(), buf.numel(), _raw_stream(idx))
+            if tuning is None:                              # the trampoline calls gptq_mlp_forward = gptq_mlp_forward_act(SILU_MUL)
                 return fast.mlp_forward(gate._layer_addr, up._layer_addr, down._layer_addr, x2.data_ptr(), out.data_ptr(), M,
                                         buf.data_ptr(), buf.numel(), _raw_stream(idx))
             return lib.gptq_mlp_forward_ex(gate._layer_ref, up._layer_ref, down._layer_ref, x2.data_ptr(), out.data_ptr(), M,

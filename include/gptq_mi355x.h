@@ -117,8 +117,12 @@ typedef enum gptq_zero_mode_t { GPTQ_ZERO_WRAP = 0, GPTQ_ZERO_NOWRAP = 1 } gptq_
  * whose columns are [gate | up] (the reference concatenates packed tensors along out_features the same way,
  * fused_llama_attn.py:171-173):  out[M, N/2] = silu(y[:, :N/2]) * y[:, N/2:]  with y = x @ W (+ bias), silu and the
  * product evaluated on the fp32 sums and rounded once -- the arithmetic of the reference's fused MLP kernel
- * (fused_llama_mlp.py:237-239).  Needs N % 64 == 0. */
-typedef enum gptq_epilogue_t { GPTQ_EPI_NONE = 0, GPTQ_EPI_SILU_MUL = 1 } gptq_epilogue_t;
+ * (fused_llama_mlp.py:237-239).  Needs N % 64 == 0.
+ * GELU_TANH_MUL is the same pair layer with the gate of Gemma's GeGLU MLP: layout, shape rules, plans, workspace sizes and gptq_describe_plan strings are
+ * those of SILU_MUL;  out[M, N/2] = T( gelu_tanh(y_gate) * y_up ),  gelu_tanh(g) = g / (1 + exp(-c(g))),  c(g) = 2 sqrt(2/pi) (g + 0.044715 g^3),
+ * 2 sqrt(2/pi) = 1.5957691216057308 -- the tanh approximation of GELU (torch: F.gelu(approximate='tanh'), "gelu_new"), since
+ * 0.5 (1 + tanh(v)) = 1 / (1 + exp(-2 v)); SiLU is the same form with c(g) = g.  Activation and product on the fp32 sums (bias included), rounded once. */
+typedef enum gptq_epilogue_t { GPTQ_EPI_NONE = 0, GPTQ_EPI_SILU_MUL = 1, GPTQ_EPI_GELU_TANH_MUL = 2 } gptq_epilogue_t;
 
 /* One quantized linear layer.  POD; the caller owns every pointer and keeps it alive. */
 typedef struct gptq_layer_t {
@@ -242,6 +246,11 @@ int gptq_mlp_forward(const gptq_layer_t *gate, const gptq_layer_t *up, const gpt
                      void *workspace, size_t workspace_bytes, void *stream);
 int gptq_mlp_forward_ex(const gptq_layer_t *gate, const gptq_layer_t *up, const gptq_layer_t *down, const void *x, void *out, int M,
                         void *workspace, size_t workspace_bytes, void *stream, const gptq_tuning_t *tuning);
+/* The same call with the gate's activation as an argument: out = down( act(gate(x)) * up(x) ), act = GPTQ_EPI_SILU_MUL (gptq_mlp_forward, bit for bit) or
+ * GPTQ_EPI_GELU_TANH_MUL (Gemma's GeGLU; the formula at gptq_epilogue_t).  Same steps, same workspace (gptq_workspace_bytes_mlp), same
+ * gptq_describe_mlp_plan; any other act: GPTQ_ERR_UNSUPPORTED.  gptq_mlp_forward and gptq_mlp_forward_ex are calls of it. */
+int gptq_mlp_forward_act(const gptq_layer_t *gate, const gptq_layer_t *up, const gptq_layer_t *down, int act, const void *x, void *out, int M,
+                         void *workspace, size_t workspace_bytes, void *stream);
 /* Host-only: "kernel=unfused launches=3+ steps=..." for (gate, up, down, M, tuning); as gptq_describe_plan. */
 int gptq_describe_mlp_plan(const gptq_layer_t *gate, const gptq_layer_t *up, const gptq_layer_t *down, int M, const gptq_tuning_t *tuning, char *out,
                            size_t out_bytes);

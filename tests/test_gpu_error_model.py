@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 import torch
 
+from _error_model import DECODE_KERNELS, ulp as _ulp      # shared with test_gpu_error_model_edges.py: the same spacing table, the same C = 4 families
 from autogptq_amd import _lib
 from autogptq_amd.qlinear_mi355x import QuantLinear
 from oracle import gptq_oracle as O
@@ -47,13 +48,6 @@ def _layer(K, N, bits, gs, dtype, act, seed):
     return q, W64, Sabs
 
 
-def _ulp(y64, dtype):
-    """Spacing of `dtype` at |y64| (normal range; the subnormal floor for tiny outputs)."""
-    mant, emin = (10, -14) if dtype == torch.float16 else (7, -126)
-    e = torch.floor(torch.log2(y64.abs().clamp_min(2.0 ** emin)))
-    return torch.pow(torch.tensor(2.0, dtype=torch.float64, device=y64.device), e - mant)
-
-
 CASES = [
     # K, N, bits, gs, act, dtype
     (4096, 4096, 4, 128, False, torch.float16),
@@ -69,7 +63,6 @@ CASES = [
     (2048, 2048, 4, -1, False, torch.float16),
 ]
 ROWS = (1, 2, 3, 4, 7, 16, 64, 128, 256, 512, 2048)
-DECODE_KERNELS = ("strips", "mfma", "mfma_generic", "generic", "stream")          # fp32 sums per group outside the matrix core's long chains: C = 4
 
 
 @pytest.mark.parametrize("K,N,bits,gs,act,dtype", CASES)

@@ -15,6 +15,7 @@
 //           wgrad_sum_kernel adds them in ascending slice order and applies s.  No atomics, fixed orders.
 // ONE launch covers the dA and dB units of all adapters of a call (the jobs travel by value; constant indices only, so they stay in scalar registers).
 #include "common.cuh"
+#include "mma_dequant.cuh"
 #include "launch.h"
 
 namespace gptq {
@@ -61,18 +62,6 @@ __device__ __forceinline__ Job locate(const Args& p, int& b) {
     }
     return j;
 }
-
-template <typename T> struct Mma;
-template <> struct Mma<f16> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mma<bf16> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    }
-};
 
 // the operand of one 16-wide block: rows 4 g .. 4 g + 3 and 16 + 4 g .. 16 + 4 g + 3 of its columns, transposed
 __device__ __forceinline__ u32x4 tr_operand(const unsigned short* at) {
@@ -134,7 +123,7 @@ __global__ void __launch_bounds__(THREADS) wgrad_kernel(Args p) {
         }
         const u32x4 a = tr_operand(bs + toff + 16 * wave);
 #pragma unroll
-        for (int jb = 0; jb < 4; ++jb) acc[jb] = Mma<T>::run(a, tr_operand(ss + toff + 16 * jb), acc[jb]);
+        for (int jb = 0; jb < 4; ++jb) acc[jb] = Mma16<T>::run(a, tr_operand(ss + toff + 16 * jb), acc[jb]);
     }
 
     // accumulator: column (lane & 15) is j within the block, rows 4 (lane >> 4) + reg are four consecutive indices of the large dimension

@@ -19,6 +19,7 @@
 #include <algorithm>
 
 #include "common.cuh"
+#include "mma_dequant.cuh"
 #include "launch.h"
 
 namespace gptq {
@@ -45,18 +46,6 @@ struct Args {
     const int4* tiles;                      // (slot, first sorted row, rows, 0)
     const int* row_assign;                  // sorted row -> m
     int n, K;
-};
-
-template <typename T> struct Mma;
-template <> struct Mma<f16> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mma<bf16> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    }
 };
 
 __host__ __device__ inline int down_units(int r) { return (r + 15) / 16; }
@@ -112,7 +101,7 @@ __global__ void __launch_bounds__(DOWN_THREADS) adapter_rows_down_kernel(Args p)
             aa[i] = in && aok ? *(const u32x4*)(ap + (size_t)t * 64) : zero;
         }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) acc = Mma<T>::run(xa[i], aa[i], acc);
+        for (int i = 0; i < 4; ++i) acc = Mma16<T>::run(xa[i], aa[i], acc);
     }
     // accumulator: column (l & 15) is j, rows 4 (l >> 4) + reg are the tile's rows
 #pragma unroll
@@ -160,8 +149,8 @@ __global__ void __launch_bounds__(UP_THREADS) adapter_rows_up_kernel(Args p) {
         const T* bp = B + (size_t)(nok ? nn + row : 0) * r;
         const u32x4 b0 = nok && ja < r ? *(const u32x4*)(bp + ja) : zero;
         const u32x4 b1 = nok && jb < r ? *(const u32x4*)(bp + jb) : zero;
-        f32x4 acc = Mma<T>::run(b0, u0, f32x4{0.f, 0.f, 0.f, 0.f});
-        if (two) acc = Mma<T>::run(b1, u1, acc);
+        f32x4 acc = Mma16<T>::run(b0, u0, f32x4{0.f, 0.f, 0.f, 0.f});
+        if (two) acc = Mma16<T>::run(b1, u1, acc);
         // accumulator: column (l & 15) is the tile's row, rows 4 (l >> 4) + reg are four consecutive n
         if (nok && mok) {
             T* o = out + (size_t)m * N + nn + 4 * kq;

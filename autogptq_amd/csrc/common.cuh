@@ -114,10 +114,17 @@ __device__ __forceinline__ void zero_points4(const unsigned* __restrict__ zrow, 
 // K-step, i.e. right after the next step's loads were issued (the whole memory latency lands on every step).  Hidden in asm the
 // instruction is not part of the compiler's vmcnt bookkeeping, which only ever makes its waits for ordinary loads longer
 // (vmcnt retires in order), never shorter; the kernel waits for the DMA data with a hand-counted s_waitcnt.
+// M0 holds the LDS destination base and belongs to the compiler, which neither sees the string write it nor accepts it as a clobber: M0 is written in the
+// SAME statement that reads it, saved before and restored after, so whatever hipcc keeps there survives; s_nop 0: the M0 write -> LDS-DMA hazard.
 __device__ __forceinline__ void lds_dma16(const void* gsrc, unsigned lds_dst_) {           // default cache policy
     const unsigned lds_dst = __builtin_amdgcn_readfirstlane(lds_dst_);   // wave-uniform by construction; an SGPR for the compiler too
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
+}
+__device__ __forceinline__ void lds_dma16_nt(const void* gsrc, unsigned lds_dst) {         // nontemporal (weight streams); lds_dst already wave-uniform for the compiler
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
 }
 __device__ __forceinline__ unsigned lds_addr_of(const void* p) { return (unsigned)(size_t)(__attribute__((address_space(3))) const char*)p; }

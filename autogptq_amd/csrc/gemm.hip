@@ -32,6 +32,7 @@
 #include <type_traits>
 
 #include "common.cuh"
+#include "mma_dequant.cuh"
 #include "launch.h"
 #include "../../include/gptq_mi355x_lab.h"
 
@@ -56,31 +57,6 @@ struct GemmParams {
     unsigned* err;                // sticky error word of the workspace header (a bounded wait gave up)
     unsigned max_spins;
 };
-
-__device__ __forceinline__ f16x8 as_f16x8(u32x4 v) { return __builtin_bit_cast(f16x8, v); }
-__device__ __forceinline__ bf16x8 as_bf16x8(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
-__device__ __forceinline__ unsigned f16x2_bits(f16x2 v) { return __builtin_bit_cast(unsigned, v); }
-// (a & mask) | orv in one VALU op (hipcc emits v_and + v_or for the C expression: VOP3 takes no literals on gfx9)
-__device__ __forceinline__ unsigned and_or(unsigned a, unsigned mask, unsigned orv) {
-    unsigned r;
-    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(mask), "v"(orv));
-    return r;
-}
-
-template <typename T> struct Mma;
-template <> struct Mma<f16> {
-    static __device__ __forceinline__ f32x16 run(u32x4 a, u32x4 b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(as_f16x8(a), as_f16x8(b), c, 0, 0, 0);
-    }
-};
-template <> struct Mma<bf16> {
-    static __device__ __forceinline__ f32x16 run(u32x4 a, u32x4 b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a), as_bf16x8(b), c, 0, 0, 0);
-    }
-};
-
-__device__ __forceinline__ unsigned short t_bits(f16 v) { return __builtin_bit_cast(unsigned short, v); }
-__device__ __forceinline__ unsigned short t_bits(bf16 v) { return __builtin_bit_cast(unsigned short, v); }
 
 // ---- per-lane weight words of one 16-deep MFMA k-step -----------------------------------------
 // The lane's 8 k values start at bit B0 = (k0 + 8*half) * BITS of its column's bit stream (words down the
@@ -313,15 +289,6 @@ template <> struct Deq<4, bf16> {
             c2[col] = c1[col] + k960;
         }
     }
-    static __device__ __forceinline__ unsigned scaled_pair(f16x2 h, float sc) {
-        // v_fma_mix_f32 reads either half of the packed fp16 register directly (fp32 result): no separate v_cvt_f32_f16
-        const unsigned hb = __builtin_bit_cast(unsigned, h);
-        float lo, hi;
-        asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel_hi:[1,0,0]" : "=v"(lo) : "v"(hb), "v"(sc));
-        asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(hi) : "v"(hb), "v"(sc));
-        const bf16x2 v = {(bf16)lo, (bf16)hi};
-        return __builtin_bit_cast(unsigned, v);
-    }
     __device__ __forceinline__ u32x4 frag(const BRaw<4>& r, int col, int) const {
         const unsigned q = r.w[0][col], q8 = q >> 8;
         const f16x2 r16 = {(f16)0.0625f, (f16)0.0625f};
@@ -330,10 +297,10 @@ template <> struct Deq<4, bf16> {
         const f16x2 h2 = as_f16x2(and_or(q8, 0x000f000fu, 0x64006400u)) + c1[col];
         const f16x2 h3 = as_f16x2(and_or(q8, 0x00f000f0u, 0x64006400u)) * r16 + c2[col];
         u32x4 o;
-        o[0] = scaled_pair(h0, s[col]);
-        o[1] = scaled_pair(h1, s[col]);
-        o[2] = scaled_pair(h2, s[col]);
-        o[3] = scaled_pair(h3, s[col]);
+        o[0] = bf16_scaled_pair(h0, s[col]);
+        o[1] = bf16_scaled_pair(h1, s[col]);
+        o[2] = bf16_scaled_pair(h2, s[col]);
+        o[3] = bf16_scaled_pair(h3, s[col]);
         return o;
     }
 };
@@ -635,7 +602,7 @@ __global__ void __launch_bounds__(256 * KG, 2 / KG) gemm_kernel(GemmParams p) {
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-                    for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = Mma<T>::run(a[ks & 1][mt], bq[ks & 1][nt], acc[mt][nt]);
+                    for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = Mma32<T>::run(a[ks & 1][mt], bq[ks & 1][nt], acc[mt][nt]);
             }
             dq_cur = dq_nx;
             return;
@@ -681,7 +648,7 @@ __global__ void __launch_bounds__(256 * KG, 2 / KG) gemm_kernel(GemmParams p) {
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-                    for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = Mma<T>::run(a[ks & 1][mt], bq[ks & 1][nt], acc[mt][nt]);
+                    for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = Mma32<T>::run(a[ks & 1][mt], bq[ks & 1][nt], acc[mt][nt]);
                 if constexpr (ILV && !GLDS) {
                     __builtin_amdgcn_sched_barrier(0);
                     if (ks == 0) { load_b(ktn, b_fill); load_c(ktn, c_fill); }
@@ -703,7 +670,7 @@ __global__ void __launch_bounds__(256 * KG, 2 / KG) gemm_kernel(GemmParams p) {
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-                    for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = Mma<T>::run(a[mt], b[nt], acc[mt][nt]);
+                    for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = Mma32<T>::run(a[mt], b[nt], acc[mt][nt]);
                 if constexpr (VAR == 2) __builtin_amdgcn_s_setprio(0);
             }
         }
@@ -963,7 +930,7 @@ __global__ void __launch_bounds__(512) gemm_skinny_kernel(GemmParams p) {
                 o[3] = __builtin_amdgcn_perm(t[3], t[1], 0x07060302u);
                 if (!live) o = u32x4{0u, 0u, 0u, 0u};
 #pragma unroll
-                for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = Mma<T>::run(o, b[nt], acc[mt][nt]);
+                for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = Mma32<T>::run(o, b[nt], acc[mt][nt]);
             }
         }
     }
@@ -1010,7 +977,9 @@ __global__ void __launch_bounds__(512) gemm_skinny_kernel(GemmParams p) {
 // again exactly one 4-bit word -- and of row l&15 of A.  A wave-load of weights is 4 packed rows x 64 B; x fragments are
 // 16-byte loads from L2 (x is M*K*2 bytes, shared by all strips).  Everything a wave needs for U k-steps is requested
 // before the first MFMA.  RT row tiles of 16 reuse every dequantised word.  Cross-wave sum through LDS as in the GEMV.
-template <typename T> struct Deq1;                       // one column: (scale bits, zero-point) -> fragment of one word
+// Private copy of mma_dequant.cuh's Deq1 (same arithmetic, one statement per word): with the shared layout gemm_strip16 / gemm_stream64 kernels change registers and hazard nops.
+namespace strip {
+template <typename T> struct Deq1;
 template <> struct Deq1<f16> {
     f16x2 s2, c1, c2;
     __device__ __forceinline__ void setup(unsigned sbits, unsigned z) {
@@ -1043,24 +1012,14 @@ template <> struct Deq1<bf16> {
         const unsigned q8 = q >> 8;
         const f16x2 r16 = {(f16)0.0625f, (f16)0.0625f};
         u32x4 o;
-        o[0] = Deq<4, bf16>::scaled_pair(as_f16x2(and_or(q, 0x000f000fu, 0x64006400u)) + c1, s);
-        o[1] = Deq<4, bf16>::scaled_pair(as_f16x2(and_or(q, 0x00f000f0u, 0x64006400u)) * r16 + c2, s);
-        o[2] = Deq<4, bf16>::scaled_pair(as_f16x2(and_or(q8, 0x000f000fu, 0x64006400u)) + c1, s);
-        o[3] = Deq<4, bf16>::scaled_pair(as_f16x2(and_or(q8, 0x00f000f0u, 0x64006400u)) * r16 + c2, s);
+        o[0] = bf16_scaled_pair(as_f16x2(and_or(q, 0x000f000fu, 0x64006400u)) + c1, s);
+        o[1] = bf16_scaled_pair(as_f16x2(and_or(q, 0x00f000f0u, 0x64006400u)) * r16 + c2, s);
+        o[2] = bf16_scaled_pair(as_f16x2(and_or(q8, 0x000f000fu, 0x64006400u)) + c1, s);
+        o[3] = bf16_scaled_pair(as_f16x2(and_or(q8, 0x00f000f0u, 0x64006400u)) * r16 + c2, s);
         return o;
     }
 };
-template <typename T> struct Mma16;
-template <> struct Mma16<f16> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(a), as_f16x8(b), c, 0, 0, 0);
-    }
-};
-template <> struct Mma16<bf16> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(a), as_bf16x8(b), c, 0, 0, 0);
-    }
-};
+}  // namespace strip
 
 template <typename T, int RT, int U>
 __global__ void __launch_bounds__(1024) gemm_strip16_kernel(GemmParams p) {
@@ -1119,7 +1078,7 @@ __global__ void __launch_bounds__(1024) gemm_strip16_kernel(GemmParams p) {
             const bool live = s0 + j < we;
             unsigned z = ((zraw[j] >> z_sh) & 15u) + 1u;
             if (p.zero_mode == GPTQ_ZERO_WRAP) z &= 15u;
-            Deq1<T> dq;
+            strip::Deq1<T> dq;
             dq.setup(sraw[j] & 0xffffu, z);
             const u32x4 b = dq.frag(braw[j]);
 #pragma unroll
@@ -1175,17 +1134,6 @@ __global__ void __launch_bounds__(1024) gemm_strip16_kernel(GemmParams p) {
 //   waves split the K range of the workgroup; cross-wave sum through LDS in fixed order (slabs alias the landing area);
 //   K slices of one tile are combined inside the launch like the decode kernel's: sc1 publish, ticket, last arriver sums
 //   the slices in index order.  Tickets: front of the workspace (gptq_mi355x.h), zero before and after every launch.
-__device__ __forceinline__ void lds_dma16_nt(const void* gsrc, unsigned lds_dst) {     // see common.cuh: lds_dma16 (this one: nontemporal)
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-
-template <typename T> __device__ __forceinline__ u32x2 pack4(f32x4 v) {
-    struct { T a, b, c, d; } o{DType<T>::from_f32(v[0]), DType<T>::from_f32(v[1]), DType<T>::from_f32(v[2]), DType<T>::from_f32(v[3])};
-    return __builtin_bit_cast(u32x2, o);
-}
-
 struct S64Seg {
     const unsigned* qweight;
     const unsigned* qzeros;
@@ -1256,7 +1204,7 @@ __global__ void __launch_bounds__(RT == 1 ? 1024 : 512) gemm_stream64_kernel(S64
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
         for (int t = 0; t < 4; ++t) acc[rt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    Deq1<T> dq[4];
+    strip::Deq1<T> dq[4];
     int g_cur = -1;
 
     if constexpr (PIPE) {

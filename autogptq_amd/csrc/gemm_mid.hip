@@ -23,6 +23,7 @@
 #include <utility>
 
 #include "common.cuh"
+#include "mma_dequant.cuh"
 #include "launch.h"
 
 namespace gptq {
@@ -57,16 +58,14 @@ struct MidParams {
     unsigned max_spins;
 };
 
-__device__ __forceinline__ unsigned and_or(unsigned q, unsigned mask, unsigned magic) { return (q & mask) | magic; }
-__device__ __forceinline__ unsigned f16x2_bits(f16x2 v) { return __builtin_bit_cast(unsigned, v); }
-
-// 16 bytes per lane global -> LDS (lds_dst + lane * 16); source = scalar base + 32-bit per-lane byte offset
-__device__ __forceinline__ void dma16_sv(const void* sbase, unsigned voff, unsigned lds_dst) {
+// 16 bytes per lane global -> LDS (lds_dst + lane * 16); source = scalar base + 32-bit per-lane byte offset.  M0 is saved and restored around the DMA like
+// lds_dma16 (common.cuh) does; the decode kernels' dma16_sv_drop_m0 (gemv_shared.cuh) is the form that does not
+__device__ __forceinline__ void dma16_sv_keep_m0(const void* sbase, unsigned voff, unsigned lds_dst) {
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
 }
-__device__ __forceinline__ void dma16_sv_nt(const void* sbase, unsigned voff, unsigned lds_dst) {
+__device__ __forceinline__ void dma16_sv_keep_m0_nt(const void* sbase, unsigned voff, unsigned lds_dst) {
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 nt\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
@@ -77,8 +76,8 @@ __device__ __forceinline__ void store16_sc1(void* dst, f32x4 v) {      // write-
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst), "v"(v) : "memory");
 }
 
-// one column: (scale bits, zero-point) -> fragment of one 4-bit word = 8 consecutive k in the slot order k0,k4,k1,k5,k2,k6,k3,k7;
-// exact w - z in packed fp16 (magic number 0x6400), then x scale: the reference's scales * (w - z), bit for bit
+// Private copy of mma_dequant.cuh's Deq1, which it hides inside midk (same arithmetic, one statement per word, and_or_c): with the shared body these kernels change
+// instructions and registers (v_and_or_b32 for v_and + v_or; the 8-row-tile XREG kernels spill).
 template <typename T> struct Deq1;
 template <> struct Deq1<f16> {
     f16x2 s2, c1, c2;
@@ -92,10 +91,10 @@ template <> struct Deq1<f16> {
         const unsigned q8 = q >> 8;
         const f16x2 r16 = {(f16)0.0625f, (f16)0.0625f};
         u32x4 o;
-        o[0] = f16x2_bits((as_f16x2(and_or(q, 0x000f000fu, 0x64006400u)) + c1) * s2);
-        o[1] = f16x2_bits((as_f16x2(and_or(q, 0x00f000f0u, 0x64006400u)) * r16 + c2) * s2);
-        o[2] = f16x2_bits((as_f16x2(and_or(q8, 0x000f000fu, 0x64006400u)) + c1) * s2);
-        o[3] = f16x2_bits((as_f16x2(and_or(q8, 0x00f000f0u, 0x64006400u)) * r16 + c2) * s2);
+        o[0] = f16x2_bits((as_f16x2(and_or_c(q, 0x000f000fu, 0x64006400u)) + c1) * s2);
+        o[1] = f16x2_bits((as_f16x2(and_or_c(q, 0x00f000f0u, 0x64006400u)) * r16 + c2) * s2);
+        o[2] = f16x2_bits((as_f16x2(and_or_c(q8, 0x000f000fu, 0x64006400u)) + c1) * s2);
+        o[3] = f16x2_bits((as_f16x2(and_or_c(q8, 0x00f000f0u, 0x64006400u)) * r16 + c2) * s2);
         return o;
     }
 };
@@ -108,22 +107,14 @@ template <> struct Deq1<bf16> {
         const f16x2 k960 = {(f16)960.f, (f16)960.f};
         c2 = c1 + k960;
     }
-    static __device__ __forceinline__ unsigned scaled_pair(f16x2 h, float sc) {      // exact fp32 product, one rounding to bf16
-        const unsigned hb = __builtin_bit_cast(unsigned, h);
-        float lo, hi;
-        asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel_hi:[1,0,0]" : "=v"(lo) : "v"(hb), "v"(sc));
-        asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(hi) : "v"(hb), "v"(sc));
-        const bf16x2 v = {(bf16)lo, (bf16)hi};
-        return __builtin_bit_cast(unsigned, v);
-    }
     __device__ __forceinline__ u32x4 frag(unsigned q) const {
         const unsigned q8 = q >> 8;
         const f16x2 r16 = {(f16)0.0625f, (f16)0.0625f};
         u32x4 o;
-        o[0] = scaled_pair(as_f16x2(and_or(q, 0x000f000fu, 0x64006400u)) + c1, s);
-        o[1] = scaled_pair(as_f16x2(and_or(q, 0x00f000f0u, 0x64006400u)) * r16 + c2, s);
-        o[2] = scaled_pair(as_f16x2(and_or(q8, 0x000f000fu, 0x64006400u)) + c1, s);
-        o[3] = scaled_pair(as_f16x2(and_or(q8, 0x00f000f0u, 0x64006400u)) * r16 + c2, s);
+        o[0] = bf16_scaled_pair(as_f16x2(and_or_c(q, 0x000f000fu, 0x64006400u)) + c1, s);
+        o[1] = bf16_scaled_pair(as_f16x2(and_or_c(q, 0x00f000f0u, 0x64006400u)) * r16 + c2, s);
+        o[2] = bf16_scaled_pair(as_f16x2(and_or_c(q8, 0x000f000fu, 0x64006400u)) + c1, s);
+        o[3] = bf16_scaled_pair(as_f16x2(and_or_c(q8, 0x00f000f0u, 0x64006400u)) * r16 + c2, s);
         return o;
     }
 };
@@ -141,10 +132,10 @@ template <> struct Deq8<f16> {
         const unsigned lo = __builtin_amdgcn_perm(w1, w0, 0x05040100u);      // f0 f1 | f4 f5
         const unsigned hi = __builtin_amdgcn_perm(w1, w0, 0x07060302u);      // f2 f3 | f6 f7
         u32x4 o;
-        o[0] = f16x2_bits((as_f16x2(and_or(lo, 0x00ff00ffu, 0x64006400u)) + c1) * s2);
-        o[1] = f16x2_bits((as_f16x2(and_or(lo >> 8, 0x00ff00ffu, 0x64006400u)) + c1) * s2);
-        o[2] = f16x2_bits((as_f16x2(and_or(hi, 0x00ff00ffu, 0x64006400u)) + c1) * s2);
-        o[3] = f16x2_bits((as_f16x2(and_or(hi >> 8, 0x00ff00ffu, 0x64006400u)) + c1) * s2);
+        o[0] = f16x2_bits((as_f16x2(and_or_c(lo, 0x00ff00ffu, 0x64006400u)) + c1) * s2);
+        o[1] = f16x2_bits((as_f16x2(and_or_c(lo >> 8, 0x00ff00ffu, 0x64006400u)) + c1) * s2);
+        o[2] = f16x2_bits((as_f16x2(and_or_c(hi, 0x00ff00ffu, 0x64006400u)) + c1) * s2);
+        o[3] = f16x2_bits((as_f16x2(and_or_c(hi >> 8, 0x00ff00ffu, 0x64006400u)) + c1) * s2);
         return o;
     }
 };
@@ -159,10 +150,10 @@ template <> struct Deq8<bf16> {
         const unsigned lo = __builtin_amdgcn_perm(w1, w0, 0x05040100u);
         const unsigned hi = __builtin_amdgcn_perm(w1, w0, 0x07060302u);
         u32x4 o;
-        o[0] = Deq1<bf16>::scaled_pair(as_f16x2(and_or(lo, 0x00ff00ffu, 0x64006400u)) + c1, s);
-        o[1] = Deq1<bf16>::scaled_pair(as_f16x2(and_or(lo >> 8, 0x00ff00ffu, 0x64006400u)) + c1, s);
-        o[2] = Deq1<bf16>::scaled_pair(as_f16x2(and_or(hi, 0x00ff00ffu, 0x64006400u)) + c1, s);
-        o[3] = Deq1<bf16>::scaled_pair(as_f16x2(and_or(hi >> 8, 0x00ff00ffu, 0x64006400u)) + c1, s);
+        o[0] = bf16_scaled_pair(as_f16x2(and_or_c(lo, 0x00ff00ffu, 0x64006400u)) + c1, s);
+        o[1] = bf16_scaled_pair(as_f16x2(and_or_c(lo >> 8, 0x00ff00ffu, 0x64006400u)) + c1, s);
+        o[2] = bf16_scaled_pair(as_f16x2(and_or_c(hi, 0x00ff00ffu, 0x64006400u)) + c1, s);
+        o[3] = bf16_scaled_pair(as_f16x2(and_or_c(hi >> 8, 0x00ff00ffu, 0x64006400u)) + c1, s);
         return o;
     }
 };
@@ -183,10 +174,10 @@ template <> struct Deq3<f16> {
         const unsigned t = __builtin_amdgcn_perm(v >> 12, v, 0x05040100u);
         const unsigned t6 = t >> 6;
         const f16x2 r8 = {(f16)0.125f, (f16)0.125f}, r64 = {(f16)0.015625f, (f16)0.015625f};
-        h[0] = as_f16x2(and_or(t, 0x00070007u, 0x64006400u)) + c1;             // k0,k4 : w - z
-        h[1] = as_f16x2(and_or(t, 0x00380038u, 0x64006400u)) * r8 + c3;        // k1,k5
-        h[2] = as_f16x2(and_or(t, 0x01C001C0u, 0x64006400u)) * r64 + c6;       // k2,k6
-        h[3] = as_f16x2(and_or(t6, 0x00380038u, 0x64006400u)) * r8 + c3;       // k3,k7
+        h[0] = as_f16x2(and_or_c(t, 0x00070007u, 0x64006400u)) + c1;             // k0,k4 : w - z
+        h[1] = as_f16x2(and_or_c(t, 0x00380038u, 0x64006400u)) * r8 + c3;        // k1,k5
+        h[2] = as_f16x2(and_or_c(t, 0x01C001C0u, 0x64006400u)) * r64 + c6;       // k2,k6
+        h[3] = as_f16x2(and_or_c(t6, 0x00380038u, 0x64006400u)) * r8 + c3;       // k3,k7
     }
     __device__ __forceinline__ u32x4 frag(unsigned v) const {
         f16x2 h[4];
@@ -204,7 +195,7 @@ template <> struct Deq3<bf16> {
     __device__ __forceinline__ u32x4 frag(unsigned v) const {
         f16x2 h[4];
         d.diffs(v, h);
-        return u32x4{Deq1<bf16>::scaled_pair(h[0], s), Deq1<bf16>::scaled_pair(h[1], s), Deq1<bf16>::scaled_pair(h[2], s), Deq1<bf16>::scaled_pair(h[3], s)};
+        return u32x4{bf16_scaled_pair(h[0], s), bf16_scaled_pair(h[1], s), bf16_scaled_pair(h[2], s), bf16_scaled_pair(h[3], s)};
     }
 };
 // 2-bit: the lane's 8 consecutive k of one column are 16 bits of a word (16 values per word: half kg & 1 of packed row kg >> 1); v_perm spreads the two
@@ -224,10 +215,10 @@ template <> struct Deq2<f16> {
     __device__ __forceinline__ void diffs(unsigned v16, f16x2 (&h)[4]) const {
         const unsigned t = __builtin_amdgcn_perm(v16, v16, 0x0c010c00u);       // byte 0 -> bits 0..7, byte 1 -> bits 16..23
         const f16x2 r4 = {(f16)0.25f, (f16)0.25f}, r16 = {(f16)0.0625f, (f16)0.0625f}, r64 = {(f16)0.015625f, (f16)0.015625f};
-        h[0] = as_f16x2(and_or(t, 0x00030003u, 0x64006400u)) + c1;             // k0,k4 : w - z
-        h[1] = as_f16x2(and_or(t, 0x000C000Cu, 0x64006400u)) * r4 + c2;        // k1,k5
-        h[2] = as_f16x2(and_or(t, 0x00300030u, 0x64006400u)) * r16 + c4;       // k2,k6
-        h[3] = as_f16x2(and_or(t, 0x00C000C0u, 0x64006400u)) * r64 + c6;       // k3,k7
+        h[0] = as_f16x2(and_or_c(t, 0x00030003u, 0x64006400u)) + c1;             // k0,k4 : w - z
+        h[1] = as_f16x2(and_or_c(t, 0x000C000Cu, 0x64006400u)) * r4 + c2;        // k1,k5
+        h[2] = as_f16x2(and_or_c(t, 0x00300030u, 0x64006400u)) * r16 + c4;       // k2,k6
+        h[3] = as_f16x2(and_or_c(t, 0x00C000C0u, 0x64006400u)) * r64 + c6;       // k3,k7
     }
     __device__ __forceinline__ u32x4 frag(unsigned v) const {
         f16x2 h[4];
@@ -245,25 +236,9 @@ template <> struct Deq2<bf16> {
     __device__ __forceinline__ u32x4 frag(unsigned v) const {
         f16x2 h[4];
         d.diffs(v, h);
-        return u32x4{Deq1<bf16>::scaled_pair(h[0], s), Deq1<bf16>::scaled_pair(h[1], s), Deq1<bf16>::scaled_pair(h[2], s), Deq1<bf16>::scaled_pair(h[3], s)};
+        return u32x4{bf16_scaled_pair(h[0], s), bf16_scaled_pair(h[1], s), bf16_scaled_pair(h[2], s), bf16_scaled_pair(h[3], s)};
     }
 };
-template <typename T> struct Mma16;
-template <> struct Mma16<f16> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mma16<bf16> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    }
-};
-template <typename T> __device__ __forceinline__ u32x2 pack4(f32x4 v) {
-    struct { T a, b, c, d; } o{DType<T>::from_f32(v[0]), DType<T>::from_f32(v[1]), DType<T>::from_f32(v[2]), DType<T>::from_f32(v[3])};
-    return __builtin_bit_cast(u32x2, o);
-}
-
 // RT = row tiles of 16 (M <= 16 RT); D = stages of one K-step in flight per wave.  512 threads: 8 waves split the K range.
 // XREG (experiment, tuning.reserved[1] = 1): x fragments by ordinary 16-byte loads (same coalesced lane layout) into registers, written to the
 // stage with ds_write_b128 when the stage is consumed -- the L1 path (64 B/clk per CU) instead of the LDS-DMA path (~17 B/clk measured).
@@ -387,14 +362,14 @@ __global__ void __launch_bounds__(512) gemm_mid_kernel(MidParams p) {
 #pragma unroll
             for (int h = 0; h < WD; ++h) {
                 if constexpr (BITS == 3 || BITS == 2) {
-                    if (lane < 16 * BITS) dma16_sv_nt(wsrc, woff[h], dst + h * 1024);   // three / two packed rows = 768 / 512 bytes of the 1 KiB slot
+                    if (lane < 16 * BITS) dma16_sv_keep_m0_nt(wsrc, woff[h], dst + h * 1024);   // three / two packed rows = 768 / 512 bytes of the 1 KiB slot
                 } else {
-                    dma16_sv_nt(wsrc, woff[h], dst + h * 1024);
+                    dma16_sv_keep_m0_nt(wsrc, woff[h], dst + h * 1024);
                 }
             }
             if constexpr (!XREG) {
 #pragma unroll
-                for (int rt = 0; rt < RT; ++rt) dma16_sv(xs, xoff[rt], dst + (WD + rt) * 1024);
+                for (int rt = 0; rt < RT; ++rt) dma16_sv_keep_m0(xs, xoff[rt], dst + (WD + rt) * 1024);
             }
         };
         using DQ = std::conditional_t<BITS == 8, Deq8<T>, std::conditional_t<BITS == 3, Deq3<T>, std::conditional_t<BITS == 2, Deq2<T>, Deq1<T>>>>;

@@ -20,8 +20,7 @@
 #include <type_traits>
 
 #include "common.cuh"
-#include "gemm_wide_common.cuh"
-#include "gemm_rows_kernel.cuh"      // rowsk::Deq1<T>: one column's constants, one word (8 weights) at a time
+#include "mma_dequant.cuh"          // Mma32<T>; DeqSel / Deq1<T>: one column's constants, one word (8 weights) at a time
 
 namespace gptq {
 namespace panel {
@@ -113,7 +112,7 @@ __device__ __forceinline__ void panel_body(const PanelParams& p) {
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) aoff[ks] = (unsigned)(l31 * 128 + (((half * 4 + ks) ^ ((l31 >> 1) & 7)) * 16));
 
-    using WV = std::conditional_t<BITS == 3, wide::u32x3, u32x4>;      // a lane's words of one load (written by ONE instruction)
+    using WV = std::conditional_t<BITS == 3, u32x3, u32x4>;      // a lane's words of one load (written by ONE instruction)
     struct Buf { WV w[NT][NH]; unsigned cs[NT], cz[NT]; };
     Buf q[DW];
     // Every constant register starts as ITS OWN opaque definition: initialised from one shared zero, the compiler kept scale and zero-point of a set in ONE register
@@ -180,7 +179,7 @@ __device__ __forceinline__ void panel_body(const PanelParams& p) {
         }
     };
 
-    typename rowsk::DeqSel<T, BITS>::type dq[NT];              // the current group's constants (set up where a group begins)
+    typename DeqSel<T, BITS>::type dq[NT];              // the current group's constants (set up where a group begins)
     f32x16 acc[MT][NT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
@@ -256,7 +255,7 @@ __device__ __forceinline__ void panel_body(const PanelParams& p) {
                     if (i + 1 < 4 * NT) bq[(i + 1) & 1] = frag_of((i + 1) % NT, (i + 1) / NT);
 #endif
 #pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = wide::Mma<T>::run(a[ks & 1][mt], bq[i & 1], acc[mt][nt]);
+                    for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = Mma32<T>::run(a[ks & 1][mt], bq[i & 1], acc[mt][nt]);
                     if (i + 1 < 4 * NT) {                     // MFMA, its share of the next fragment's 13 VALU, MFMA, ...
                         if constexpr (MT == 2) {
                             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);

@@ -4,7 +4,7 @@
 #include <type_traits>
 
 #include "common.cuh"
-#include "gemm_wide_common.cuh"
+#include "mma_dequant.cuh"
 #include "launch.h"
 
 namespace gptq {
@@ -30,146 +30,6 @@ struct RowsParams {
     int nsg;                      // strip groups of all layers
     int cpw;                      // chunks per wave (the last waves may run short or empty)
 };
-
-template <typename T> struct Mma16;
-template <> struct Mma16<f16> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mma16<bf16> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    }
-};
-
-// one column's constants, one word (8 weights in pair order) at a time: w - z exactly in packed fp16, times the scale with ONE rounding to T
-template <typename T> struct Deq1;
-template <> struct Deq1<f16> {
-    f16x2 s2, c1, c2;
-    __device__ __forceinline__ void setup(unsigned sraw, unsigned z) {
-        const f16x2 k960 = {(f16)960.f, (f16)960.f};
-        s2 = as_f16x2(sraw * 0x00010001u);
-        c1 = as_f16x2(z * 0x00010001u + 0xE400E400u);                // -(1024 + z)
-        c2 = c1 + k960;                                               // -(64 + z)
-    }
-    __device__ __forceinline__ u32x4 frag(unsigned q) const {
-        const unsigned q8 = q >> 8;
-        const f16x2 r16 = {(f16)0.0625f, (f16)0.0625f};
-        const f16x2 h0 = as_f16x2(wide::and_or(q, 0x000f000fu, 0x64006400u)) + c1;
-        const f16x2 h1 = as_f16x2(wide::and_or(q, 0x00f000f0u, 0x64006400u)) * r16 + c2;
-        const f16x2 h2 = as_f16x2(wide::and_or(q8, 0x000f000fu, 0x64006400u)) + c1;
-        const f16x2 h3 = as_f16x2(wide::and_or(q8, 0x00f000f0u, 0x64006400u)) * r16 + c2;
-        return u32x4{wide::f16x2_bits(h0 * s2), wide::f16x2_bits(h1 * s2), wide::f16x2_bits(h2 * s2), wide::f16x2_bits(h3 * s2)};
-    }
-};
-template <> struct Deq1<bf16> {
-    float s;
-    f16x2 c1, c2;
-    __device__ __forceinline__ void setup(unsigned sraw, unsigned z) {
-        const f16x2 k960 = {(f16)960.f, (f16)960.f};
-        s = (float)__builtin_bit_cast(bf16, (unsigned short)sraw);
-        c1 = as_f16x2(z * 0x00010001u + 0xE400E400u);
-        c2 = c1 + k960;
-    }
-    __device__ __forceinline__ u32x4 frag(unsigned q) const {
-        const unsigned q8 = q >> 8;
-        const f16x2 r16 = {(f16)0.0625f, (f16)0.0625f};
-        const f16x2 h0 = as_f16x2(wide::and_or(q, 0x000f000fu, 0x64006400u)) + c1;
-        const f16x2 h1 = as_f16x2(wide::and_or(q, 0x00f000f0u, 0x64006400u)) * r16 + c2;
-        const f16x2 h2 = as_f16x2(wide::and_or(q8, 0x000f000fu, 0x64006400u)) + c1;
-        const f16x2 h3 = as_f16x2(wide::and_or(q8, 0x00f000f0u, 0x64006400u)) * r16 + c2;
-        return u32x4{wide::bf16_scaled_pair(h0, s), wide::bf16_scaled_pair(h1, s), wide::bf16_scaled_pair(h2, s), wide::bf16_scaled_pair(h3, s)};
-    }
-};
-
-// 3 bits (utils.hip prepack_decode_weights_kernel<3>): word j of the lane's three holds pairs 5 j + i at bit 3 i of its halves, bit 15 / 31 = bit j of k30 / k31;
-// fields inside the fp16 mantissa are read in place (gemm_wide_common.cuh: Deq3 is the four-column form of the same arithmetic)
-template <typename T> struct Deq1_3 {
-    wide::Scale4<T> sc;                                            // (column 0 of it)
-    f16x2 c0, c1, c2;
-    __device__ __forceinline__ void setup(unsigned sraw, unsigned z) {
-        sc.setup(u32x2{sraw & 0xffffu, 0u});
-        c0 = as_f16x2(z * 0x00010001u + 0xE400E400u);                 // -(1024 + z)
-        c1 = as_f16x2(z * 0x00080008u + 0xD800D800u);                 // -(128 + z)
-        c2 = as_f16x2(z * 0x00400040u + 0xCC00CC00u);                 // -(16 + z)
-    }
-    __device__ __forceinline__ f16x2 p0(unsigned q) const { return as_f16x2(wide::and_or(q, 0x00070007u, 0x64006400u)) + c0; }
-    __device__ __forceinline__ f16x2 p1(unsigned q) const {
-        const f16x2 rr = {(f16)0.125f, (f16)0.125f};
-        return as_f16x2(wide::and_or(q, 0x00380038u, 0x64006400u)) * rr + c1;
-    }
-    __device__ __forceinline__ f16x2 p2(unsigned q) const {
-        const f16x2 rr = {(f16)0.015625f, (f16)0.015625f};
-        return as_f16x2(wide::and_or(q, 0x01c001c0u, 0x64006400u)) * rr + c2;
-    }
-    __device__ __forceinline__ u32x4 frag(const wide::u32x3& w, int ks) const {      // k = 8 ks .. 8 ks + 7 of the lane's 32
-        f16x2 h[4];
-        if (ks == 0) {
-            h[0] = p0(w[0]); h[1] = p1(w[0]); h[2] = p2(w[0]); h[3] = p1(w[0] >> 6);
-        } else if (ks == 1) {
-            h[0] = p2(w[0] >> 6); h[1] = p0(w[1]); h[2] = p1(w[1]); h[3] = p2(w[1]);
-        } else if (ks == 2) {
-            const unsigned q6 = w[1] >> 6;
-            h[0] = p1(q6); h[1] = p2(q6); h[2] = p0(w[2]); h[3] = p1(w[2]);
-        } else {
-            const unsigned q6 = w[2] >> 6;
-            unsigned t = (w[0] >> 15) & 0x00010001u;
-            t = wide::and_or(w[1] >> 14, 0x00020002u, t);
-            t = wide::and_or(w[2] >> 13, 0x00040004u, t);
-            h[0] = p2(w[2]); h[1] = p1(q6); h[2] = p2(q6); h[3] = p0(t);
-        }
-        return u32x4{sc.mul(h[0], 0), sc.mul(h[1], 0), sc.mul(h[2], 0), sc.mul(h[3], 0)};
-    }
-};
-// 8 bits: stored byte p of word w = k 4 w + {0, 2, 1, 3}[p]
-template <typename T> struct Deq1_8 {
-    wide::Scale4<T> sc;
-    f16x2 c1;
-    __device__ __forceinline__ void setup(unsigned sraw, unsigned z) {
-        sc.setup(u32x2{sraw & 0xffffu, 0u});
-        c1 = as_f16x2(z * 0x00010001u + 0xE400E400u);
-    }
-    __device__ __forceinline__ u32x4 frag(unsigned q0, unsigned q1) const {
-        const f16x2 h0 = as_f16x2(wide::and_or(q0, 0x00ff00ffu, 0x64006400u)) + c1;
-        const f16x2 h1 = as_f16x2(wide::and_or(q0 >> 8, 0x00ff00ffu, 0x64006400u)) + c1;
-        const f16x2 h2 = as_f16x2(wide::and_or(q1, 0x00ff00ffu, 0x64006400u)) + c1;
-        const f16x2 h3 = as_f16x2(wide::and_or(q1 >> 8, 0x00ff00ffu, 0x64006400u)) + c1;
-        return u32x4{sc.mul(h0, 0), sc.mul(h1, 0), sc.mul(h2, 0), sc.mul(h3, 0)};
-    }
-};
-// 2 bits: fields i = 0..3 at bit 2 i of both halves of w (pairs (i, 4 + i)), read in place like the 3-bit ones: OR-ing the exponent of 1024 over field i
-// gives 1024 + 4^i f, and one fma with 4^-i and -(1024 / 4^i + z) leaves f - z exactly
-template <typename T> struct Deq1_2 {
-    wide::Scale4<T> sc;                                            // (column 0 of it)
-    f16x2 c0, c1, c2, c3;
-    __device__ __forceinline__ void setup(unsigned sraw, unsigned z) {
-        sc.setup(u32x2{sraw & 0xffffu, 0u});
-        c0 = as_f16x2(z * 0x00010001u + 0xE400E400u);                 // -(1024 + z)
-        c1 = as_f16x2(z * 0x00040004u + 0xDC00DC00u);                 // -(256 + z)
-        c2 = as_f16x2(z * 0x00100010u + 0xD400D400u);                 // -(64 + z)
-        c3 = as_f16x2(z * 0x00400040u + 0xCC00CC00u);                 // -(16 + z)
-    }
-    __device__ __forceinline__ f16x2 p0(unsigned q) const { return as_f16x2(wide::and_or(q, 0x00030003u, 0x64006400u)) + c0; }
-    __device__ __forceinline__ f16x2 p1(unsigned q) const {
-        const f16x2 rr = {(f16)0.25f, (f16)0.25f};
-        return as_f16x2(wide::and_or(q, 0x000c000cu, 0x64006400u)) * rr + c1;
-    }
-    __device__ __forceinline__ f16x2 p2(unsigned q) const {
-        const f16x2 rr = {(f16)0.0625f, (f16)0.0625f};
-        return as_f16x2(wide::and_or(q, 0x00300030u, 0x64006400u)) * rr + c2;
-    }
-    __device__ __forceinline__ f16x2 p3(unsigned q) const {
-        const f16x2 rr = {(f16)0.015625f, (f16)0.015625f};
-        return as_f16x2(wide::and_or(q, 0x00c000c0u, 0x64006400u)) * rr + c3;
-    }
-    __device__ __forceinline__ u32x4 frag(unsigned w) const {         // k order (0,4,1,5,2,6,3,7)
-        return u32x4{sc.mul(p0(w), 0), sc.mul(p1(w), 0), sc.mul(p2(w), 0), sc.mul(p3(w), 0)};
-    }
-};
-template <typename T, int BITS> struct DeqSel { typedef Deq1<T> type; };
-template <typename T> struct DeqSel<T, 3> { typedef Deq1_3<T> type; };
-template <typename T> struct DeqSel<T, 8> { typedef Deq1_8<T> type; };
 
 // GM: 0 = group_size a multiple of 128 (one group per chunk), 1 = 64 (k-slots 0, 1 | 2, 3), 2 = 32 (one group per k-slot)
 // BITS = 8: the copy's chunks are 64 deep (a lane = 16 k of one column): a 128-deep x chunk takes two of them, MFMA step w reads words 2 (w & 1), + 1 of
@@ -226,7 +86,7 @@ __global__ void __launch_bounds__(RB == 2 ? 512 : 1024) gemm_rows_kernel(RowsPar
     // chunks of weights is kept in flight per wave (issued up front, refilled behind each chunk's MFMAs).
     constexpr int RING4 = 4 * S * (BITS == 8 ? 12 : (BITS == 3 ? 5 : 6));      // registers of a four-chunk ring
     constexpr int DW = RING4 <= (RB == 1 ? 56 : 120) ? 4 : 2;
-    using WV = std::conditional_t<BITS == 3, wide::u32x3, u32x4>;      // a lane's words of one chunk of the copy (written by ONE load: no copies between the load and the wait)
+    using WV = std::conditional_t<BITS == 3, u32x3, u32x4>;      // a lane's words of one chunk of the copy (written by ONE load: no copies between the load and the wait)
     struct Buf { WV wq[S][NH]; unsigned cs[S][NH], cz[S][NH]; };
     Buf q[DW];
     auto issue_w = [&](int c, Buf& B) __attribute__((always_inline)) {

@@ -248,7 +248,7 @@ __global__ void __launch_bounds__(256, 1) gemm_wide_kernel(WideParams p) {
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = Mma<T>::run(a[ks & 1][mt], bq[ks & 1][nt], acc[mt][nt]);
+                for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = Mma32<T>::run(a[ks & 1][mt], bq[ks & 1][nt], acc[mt][nt]);
             if (ks == 0) {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {

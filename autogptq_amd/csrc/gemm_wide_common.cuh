@@ -1,31 +1,14 @@
 // gemm_wide_common.cuh -- device helpers shared by the 128 x 128-per-wave prefill kernels (gemm_wide.hip: whole tiles; gemm_wide_sk.hip: stream-K units):
-// the exact magic-number dequantisation of four adjacent columns (Deq4), the 32x32x16 matrix-core step (Mma) and the group-constant record (CRaw).
+// the exact magic-number dequantisation of four adjacent columns (Deq4, Deq3, Deq8) and the group-constant records (CRaw, CRaw8).  The 32x32x16 matrix-core step
+// (Mma32), and_or, Scale4 and bf16_scaled_pair come from mma_dequant.cuh.
 #pragma once
 #include <type_traits>
 
 #include "common.cuh"
+#include "mma_dequant.cuh"
 
 namespace gptq {
 namespace wide {
-
-__device__ __forceinline__ unsigned and_or(unsigned a, unsigned mask, unsigned orv) {
-    unsigned r;
-    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(mask), "v"(orv));      // safe here: all 256 accumulator registers are live
-    return r;
-}
-__device__ __forceinline__ unsigned f16x2_bits(f16x2 v) { return __builtin_bit_cast(unsigned, v); }
-
-template <typename T> struct Mma;
-template <> struct Mma<f16> {
-    static __device__ __forceinline__ f32x16 run(u32x4 a, u32x4 b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mma<bf16> {
-    static __device__ __forceinline__ f32x16 run(u32x4 a, u32x4 b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    }
-};
 
 // group constants of a lane's 4 columns: 4 scales (8 bytes) + the qzeros word holding its 4 nibbles
 struct CRaw { u32x2 s; unsigned z; };
@@ -73,14 +56,6 @@ template <> struct Deq4<bf16> {            // w - z exactly in packed fp16, time
             c2[col] = c1[col] + k960;
         }
     }
-    static __device__ __forceinline__ unsigned scaled_pair(f16x2 h, float sc) {
-        const unsigned hb = __builtin_bit_cast(unsigned, h);
-        float lo, hi;
-        asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel_hi:[1,0,0]" : "=v"(lo) : "v"(hb), "v"(sc));
-        asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(hi) : "v"(hb), "v"(sc));
-        const bf16x2 v = {(bf16)lo, (bf16)hi};
-        return __builtin_bit_cast(unsigned, v);
-    }
     __device__ __forceinline__ u32x4 frag(unsigned q, int col) const {
         const unsigned q8 = q >> 8;
         const f16x2 r16 = {(f16)0.0625f, (f16)0.0625f};
@@ -88,7 +63,7 @@ template <> struct Deq4<bf16> {            // w - z exactly in packed fp16, time
         const f16x2 h1 = as_f16x2(and_or(q, 0x00f000f0u, 0x64006400u)) * r16 + c2[col];
         const f16x2 h2 = as_f16x2(and_or(q8, 0x000f000fu, 0x64006400u)) + c1[col];
         const f16x2 h3 = as_f16x2(and_or(q8, 0x00f000f0u, 0x64006400u)) * r16 + c2[col];
-        return u32x4{scaled_pair(h0, s[col]), scaled_pair(h1, s[col]), scaled_pair(h2, s[col]), scaled_pair(h3, s[col])};
+        return u32x4{bf16_scaled_pair(h0, s[col]), bf16_scaled_pair(h1, s[col]), bf16_scaled_pair(h2, s[col]), bf16_scaled_pair(h3, s[col])};
     }
 };
 
@@ -96,40 +71,6 @@ template <> struct Deq4<bf16> {            // w - z exactly in packed fp16, time
 // Constants come from the decode copy's records (qconst_tiled: 16 scales + 16 zero-points AS USED per strip and group): 4 scales (8 bytes) and the
 // zero-points of the lane's 4 columns -- one byte each at 3 bits (z <= 8), 16 bits each at 8 bits (z <= 256).
 struct CRaw8 { u32x2 s; u32x2 z; };
-typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
-
-__device__ __forceinline__ unsigned bf16_scaled_pair(f16x2 h, float sc) {      // (w - z) exact in fp16, times the scale in fp32, ONE rounding to bf16
-    const unsigned hb = __builtin_bit_cast(unsigned, h);
-    float lo, hi;
-    asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel_hi:[1,0,0]" : "=v"(lo) : "v"(hb), "v"(sc));
-    asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(hi) : "v"(hb), "v"(sc));
-    const bf16x2 v = {(bf16)lo, (bf16)hi};
-    return __builtin_bit_cast(unsigned, v);
-}
-template <typename T> struct Scale4;           // the 4 columns' scales and the last step of every pair: (w - z) * scale, rounded once to T
-template <> struct Scale4<f16> {
-    f16x2 s2[4];
-    __device__ __forceinline__ void setup(u32x2 s) {
-#pragma unroll
-        for (int col = 0; col < 4; ++col) {
-            const unsigned sw = s[col >> 1];
-            s2[col] = as_f16x2(((col & 1) ? (sw >> 16) : (sw & 0xffffu)) * 0x00010001u);
-        }
-    }
-    __device__ __forceinline__ unsigned mul(f16x2 h, int col) const { return f16x2_bits(h * s2[col]); }
-};
-template <> struct Scale4<bf16> {
-    float s[4];
-    __device__ __forceinline__ void setup(u32x2 sv) {
-#pragma unroll
-        for (int col = 0; col < 4; ++col) {
-            const unsigned sw = sv[col >> 1];
-            s[col] = (float)__builtin_bit_cast(bf16, (unsigned short)((col & 1) ? (sw >> 16) : (sw & 0xffffu)));
-        }
-    }
-    __device__ __forceinline__ unsigned mul(f16x2 h, int col) const { return bf16_scaled_pair(h, s[col]); }
-};
-
 // 3 bits (decode copy, utils.hip prepack_decode_weights_kernel<3>): word j of a lane's three holds pair 5 j + i = (k 2p, k 2p + 1) at bit 3 i of its low / high
 // half, i = 0..4; bit 15 / 31 of word j = bit j of k30 / k31.  A field inside the fp16 mantissa (bits 0..9) is read in place: OR-ing the exponent of 1024
 // gives 1024 + 2^(3i) w, and one fma with 2^(-3i) and -(2^(10-3i) + z) leaves w - z exactly; fields i = 3, 4 are read from q >> 6 as i = 1, 2.
@@ -198,9 +139,6 @@ template <typename T> struct Deq8 {
         return u32x4{sc.mul(h0, col), sc.mul(h1, col), sc.mul(h2, col), sc.mul(h3, col)};
     }
 };
-
-__device__ __forceinline__ unsigned short t_bits(f16 v) { return __builtin_bit_cast(unsigned short, v); }
-__device__ __forceinline__ unsigned short t_bits(bf16 v) { return __builtin_bit_cast(unsigned short, v); }
 
 }  // namespace wide
 }  // namespace gptq

@@ -214,7 +214,7 @@ __device__ __forceinline__ void wsk_body(const WskParams& p) {
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = Mma<T>::run(a[ks & 1][mt], bq[ks & 1][nt], acc[mt][nt]);
+                for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = Mma32<T>::run(a[ks & 1][mt], bq[ks & 1][nt], acc[mt][nt]);
             if (ks == 0) {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {

@@ -33,6 +33,7 @@
 #include "common.cuh"
 #include "launch.h"
 #include "gemv_shared.cuh"
+#include "mma_dequant.cuh"
 
 namespace gptq {
 
@@ -400,7 +401,6 @@ struct MagicConsts {
         asm("s_mov_b32 %0, 0x00c000c0" : "=s"(q6));
     }
 };
-__device__ __forceinline__ unsigned f16x2_bits(f16x2 v) { return __builtin_bit_cast(unsigned, v); }
 
 template <int BITS> struct MagicF16;
 template <> struct MagicF16<8> {
@@ -566,7 +566,7 @@ __global__ void __launch_bounds__(1024, WPS) gemv_q4_stream_kernel(GemvStreamPar
 #pragma unroll
         for (int j = 0; j < U; ++j) {
             const int ul = min(u0 + j, ue - 1);
-            dma16_nt(qweight + (size_t)ul * N + nload, wq_lds + j * 1024);
+            lds_dma16_nt(qweight + (size_t)ul * N + nload, wq_lds + j * 1024);
         }
         __builtin_amdgcn_sched_barrier(0);
         const unsigned zw_ = zw >> ((nload & 7) * 4), s0_ = sraw[0], s1_ = sraw[1];
@@ -718,7 +718,7 @@ __global__ void __launch_bounds__(1024, 4) gemv_qx_stream_kernel(GemvStreamParam
         for (int j = 0; j < U; ++j) {
             const int ul = min(u0 + j, ue - 1);
 #pragma unroll
-            for (int w = 0; w < UW; ++w) dma16_nt(qweight + (size_t)(ul * UW + w) * N + nload, wq_lds + (j * UW + w) * 1024);
+            for (int w = 0; w < UW; ++w) lds_dma16_nt(qweight + (size_t)(ul * UW + w) * N + nload, wq_lds + (j * UW + w) * 1024);
         }
         __builtin_amdgcn_sched_barrier(0);
         const unsigned long long zv = (((unsigned long long)zhi << 32) | zlo) >> zsh;

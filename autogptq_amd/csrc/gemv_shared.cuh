@@ -92,22 +92,12 @@ template <> struct Mma4<bf16> {
     static __device__ __forceinline__ unsigned short bits_of_int(int d) { return (unsigned short)(as_u32((float)d) >> 16); }  // exact
 };
 
-// 16 bytes per lane, global -> LDS (destination = lds_dst + lane * 16), nontemporal.  Inline asm on purpose: with the
-// builtin, hipcc (ROCm 7.2) puts an s_waitcnt vmcnt(0) behind EVERY LDS-DMA instruction of a burst (it cannot prove that two
-// DMA writes into the one __shared__ array do not overlap), which serialises the burst into dependent round trips.  Hidden
-// in asm the instruction is not counted by the compiler's own vmcnt bookkeeping -- that only ever makes its waits for
-// ordinary loads longer, never shorter (vmcnt retires in order) -- and the kernel waits for the DMA data explicitly.
-__device__ __forceinline__ void dma16_nt(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-
-// The same DMA from a 64-bit SCALAR base plus a 32-bit lane offset (global_load_lds with saddr), for a burst whose lanes keep one offset register: M0 is set
+// The 16-byte LDS DMA of common.cuh (lds_dma16 / lds_dma16_nt: why it is issued from asm) from a 64-bit SCALAR base plus a 32-bit lane offset
+// (global_load_lds with saddr), for a burst whose lanes keep one offset register.  Unlike those two, and unlike gemm_mid's dma16_sv_keep_m0, M0 is set
 // per DMA and NOT saved -- nothing else in these kernels reads it (gfx9 LDS instructions do not; the compiler emits no other M0 user here), and the save /
 // restore pair was two of five instructions.  sbase must come from scalar arithmetic on kernel arguments (no VALU-written SGPR: the VMEM read of it would
 // need wait states the compiler cannot see inside the string); s_nop 0: the M0 write -> LDS-DMA hazard.
-template <bool NT> __device__ __forceinline__ void dma16_sv(__attribute__((address_space(1))) const char* sbase, unsigned voff, unsigned lds_dst) {
+template <bool NT> __device__ __forceinline__ void dma16_sv_drop_m0(__attribute__((address_space(1))) const char* sbase, unsigned voff, unsigned lds_dst) {
     if constexpr (NT) asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 nt" : : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
     else asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
 }
@@ -121,18 +111,18 @@ __device__ __forceinline__ void stage_rows(__attribute__((address_space(1))) con
     if (w64 >= pieces) return;
     if (tid < pieces) {
 #pragma unroll
-        for (int r = 0; r < ROWS; ++r) dma16_sv<NT>(base[r], (unsigned)tid * 16u, lds[r] + (unsigned)w64 * 16u);
+        for (int r = 0; r < ROWS; ++r) dma16_sv_drop_m0<NT>(base[r], (unsigned)tid * 16u, lds[r] + (unsigned)w64 * 16u);
     }
     if (w64 + step >= pieces) return;
     if (tid + step < pieces) {
 #pragma unroll
-        for (int r = 0; r < ROWS; ++r) dma16_sv<NT>(base[r], (unsigned)(tid + step) * 16u, lds[r] + (unsigned)(w64 + step) * 16u);
+        for (int r = 0; r < ROWS; ++r) dma16_sv_drop_m0<NT>(base[r], (unsigned)(tid + step) * 16u, lds[r] + (unsigned)(w64 + step) * 16u);
     }
     if (__builtin_expect(w64 + 2 * step >= pieces, 1)) return;
     for (int a = 2 * step; w64 + a < pieces; a += step) {                         // wave-uniform trip count
         if (tid + a < pieces) {
 #pragma unroll
-            for (int r = 0; r < ROWS; ++r) dma16_sv<NT>(base[r], (unsigned)(tid + a) * 16u, lds[r] + (unsigned)(w64 + a) * 16u);
+            for (int r = 0; r < ROWS; ++r) dma16_sv_drop_m0<NT>(base[r], (unsigned)(tid + a) * 16u, lds[r] + (unsigned)(w64 + a) * 16u);
         }
     }
 }

@@ -22,6 +22,7 @@
 // Epilogue: the fp32 accumulators go through LDS (the same 64 KiB) to rows of 8 consecutive k: 16-byte stores, + dX in fp32 first when accumulating.
 // bits, the group mode and the tile height are runtime-uniform: one kernel per dtype (3 instantiations).
 #include "common.cuh"
+#include "mma_dequant.cuh"
 #include "launch.h"
 
 namespace gptq {
@@ -29,31 +30,8 @@ namespace gin {
 
 constexpr int THREADS = 256;                // 4 waves: 2 (rows) x 2 (k halves of 64)
 constexpr int BK = 128;                     // k (output columns) per workgroup
-constexpr int ROW_BYTES = 128;              // one LDS image row per stage: 8 slots of 16 bytes
+constexpr int ROW_BYTES = 128;              // one LDS image row per stage: 8 slots of 16 bytes (the row swz() of mma_dequant.cuh lays out)
 constexpr int LDS_BYTES = 65536;            // 2 x (BM + BK) x 128 (BM = 128) = the fp32 epilogue tile [128][128]
-
-__device__ __forceinline__ int swz(int r, int s) { return r * ROW_BYTES + ((s ^ ((r >> 1) & 7)) << 4); }
-
-template <typename T> struct Mma;
-template <> struct Mma<f16> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mma<bf16> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mma<float> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        c = __builtin_amdgcn_mfma_f32_16x16x4f32(as_f32(a.x), as_f32(b.x), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x4f32(as_f32(a.y), as_f32(b.y), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x4f32(as_f32(a.z), as_f32(b.z), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x4f32(as_f32(a.w), as_f32(b.w), c, 0, 0, 0);
-        return c;
-    }
-};
 
 struct Args {
     const unsigned* qweight;
@@ -229,7 +207,7 @@ __device__ __forceinline__ void run(const Args& p, char* smem, int m0, int k0) {
 #pragma unroll
             for (int i = 0; i < RB; ++i)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = Mma<T>::run(a[i], b[j], acc[i][j]);
+                for (int j = 0; j < 4; ++j) acc[i][j] = Mma16<T>::run(a[i], b[j], acc[i][j]);
         }
         if (more) store(st, (it + 1) * BN, smem + ((it + 1) & 1) * BUF);
         __syncthreads();

@@ -19,6 +19,7 @@
 //   up, 1-8 rows:   plain VALU: a thread owns one n, reads B[n, :] in 16-byte loads and u (as fp32) from LDS, ascending j.
 // The row regime is a launch-uniform branch: one instantiation per kernel and dtype (4 in all).
 #include "common.cuh"
+#include "mma_dequant.cuh"
 #include "launch.h"
 
 namespace gptq {
@@ -44,25 +45,6 @@ struct Args {
     const void* x;
     int n, M, K, gemv;
 };
-
-template <typename T> struct Mma;
-template <> struct Mma<f16> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mma<bf16> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    }
-};
-
-template <typename T>
-__device__ __forceinline__ void unpack8(u32x4 v, float (&f)[8]) {
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int c = 0; c < 8; ++c) f[c] = DType<T>::to_f32(__builtin_bit_cast(T, (unsigned short)(w[c >> 1] >> (16 * (c & 1)))));
-}
 
 __host__ __device__ inline int down_units(int r, int gemv) { return gemv ? r : (r + 15) / 16; }
 __host__ __device__ inline int up_units(int N, int gemv) { return gemv ? (N + UP_GEMV_THREADS - 1) / UP_GEMV_THREADS : (N + UP_COLS - 1) / UP_COLS; }
@@ -150,7 +132,7 @@ __global__ void __launch_bounds__(DOWN_THREADS) lora_down_kernel(Args p) {
             aa[i] = in && aok ? *(const u32x4*)(ap + (size_t)t * 64) : zero;
         }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) acc = Mma<T>::run(xa[i], aa[i], acc);
+        for (int i = 0; i < 4; ++i) acc = Mma16<T>::run(xa[i], aa[i], acc);
     }
     // accumulator: column (l & 15) is j, rows 4 (l >> 4) + reg are m
 #pragma unroll
@@ -223,8 +205,8 @@ __global__ void __launch_bounds__(UP_THREADS) lora_up_kernel(Args p) {
         const T* bp = B + (size_t)(nok ? nn + row : 0) * r;
         const u32x4 b0 = nok && ja < r ? *(const u32x4*)(bp + ja) : zero;
         const u32x4 b1 = nok && jb < r ? *(const u32x4*)(bp + jb) : zero;
-        f32x4 acc = Mma<T>::run(b0, u0, f32x4{0.f, 0.f, 0.f, 0.f});
-        if (two) acc = Mma<T>::run(b1, u1, acc);
+        f32x4 acc = Mma16<T>::run(b0, u0, f32x4{0.f, 0.f, 0.f, 0.f});
+        if (two) acc = Mma16<T>::run(b1, u1, acc);
         // accumulator: column (l & 15) is m, rows 4 (l >> 4) + reg are four consecutive n
         if (nok && mok) {
             T* o = out + (size_t)(m0 + row) * N + nn + 4 * kq;

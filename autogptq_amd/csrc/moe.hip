@@ -20,12 +20,12 @@
 //   * loads the 16 bytes qweight[k0 / 8 + ks][n0 + 4 cq .. + 3] of the checkpoint rows (qweight_seq for act-order experts): at 4 bits each word is the 8
 //     consecutive k of one column that lane (n = lane & 15, k-slot = lane >> 4) of v_mfma_f32_16x16x32_{f16,bf16} takes -- 4 words = 4 MFMAs, column c of
 //     the quad in MFMA c; at 8 bits a fragment is two words (rows k0 / 4 + 2 ks, + 1);
-//   * dequantises them with the magic-number form of the panel / rows kernels (rowsk::Deq1, Deq1_8: w - z exact in packed fp16, times the scale with one
+//   * dequantises them with the magic-number form of the panel / rows kernels (Deq1, Deq1_8: w - z exact in packed fp16, times the scale with one
 //     rounding: bit-exact W).  On checkpoint words that form yields the k of a fragment in the order (0,4,1,5,2,6,3,7) (8 bits: (0,2,1,3,4,6,5,7)), so
 //     the A fragment is permuted the same way (4 v_perm_b32) -- the MFMA pairs A and B element by element;
 //     2 and 3 bits (GPTQ_MOE_LOW_BIT): the lane cuts its 8 fields out of the step's rows -- 3 bits: bits 24 ks .. 24 ks + 23 of the column's 96 (rows
 //     3 st + lo and 3 st + min(lo + 1, 2), lo = 24 ks >> 5: two 16-byte loads and one v_alignbit_b32 per column), 2 bits: half ks & 1 of row
-//     2 st + (ks >> 1) -- moves fields 0..3 | 4..7 to the two halves of a register and reads them in place (rowsk::Deq1_3's readers, Deq1_2): the
+//     2 st + (ks >> 1) -- moves fields 0..3 | 4..7 to the two halves of a register and reads them in place (Deq1_3's readers, Deq1_2): the
 //     4-bit k order, so order_a is the 4-bit one;
 //   * reads its A fragment (row lane & 15 of each 16-row block of the tile, 8 consecutive k) straight from global memory: x gathered through the sorted row's
 //     token (pair mode) or the H_sorted row (down mode); act-order experts gather the 8 columns through the expert's perm (W3 through its own when it has
@@ -41,7 +41,7 @@
 
 #include "common.cuh"
 #include "launch.h"
-#include "gemm_rows_kernel.cuh"      // rowsk::Deq1<T> / Deq1_8<T> / Deq1_3<T> / Deq1_2<T>: the magic-number dequantisation
+#include "mma_dequant.cuh"           // Mma16<T>, Scale4<T>, Deq1<T> / Deq1_8<T> / Deq1_3<T> / Deq1_2<T>: the magic-number dequantisation
 
 namespace gptq {
 namespace moe {
@@ -169,7 +169,7 @@ struct Proj {                                   // one projection's weights for 
     const unsigned* qz;
     const T* sc;
     int gcur;
-    wide::Scale4<T> s4;                         // the 4 columns' scales
+    Scale4<T> s4;                         // the 4 columns' scales
     f16x2 k[4][4];                              // column c's constants -(2^m + z), shared by the widths: 4 bits k[c][0..1] (Deq1's c1, c2), 8 bits k[c][0],
                                                 // 3 bits k[c][0..2] (Deq1_3's c0..c2), 2 bits k[c][0..3] (Deq1_2's c0..c3); the rest is never read
 
@@ -222,28 +222,28 @@ struct Proj {                                   // one projection's weights for 
     }
     __device__ __forceinline__ u32x4 frag(const GemmArgs& p, int c, int ks, const u32x4& q0, const u32x4& q1) const {
         f16x2 h0, h1, h2, h3;
-        if (p.bits == 4) {                      // rowsk::Deq1: (0,4) (1,5) (2,6) (3,7)
+        if (p.bits == 4) {                      // Deq1: (0,4) (1,5) (2,6) (3,7)
             const unsigned q = q0[c], q8 = q >> 8;
             const f16x2 r16 = {(f16)0.0625f, (f16)0.0625f};
-            h0 = as_f16x2(wide::and_or(q, 0x000f000fu, 0x64006400u)) + k[c][0];
-            h1 = as_f16x2(wide::and_or(q, 0x00f000f0u, 0x64006400u)) * r16 + k[c][1];
-            h2 = as_f16x2(wide::and_or(q8, 0x000f000fu, 0x64006400u)) + k[c][0];
-            h3 = as_f16x2(wide::and_or(q8, 0x00f000f0u, 0x64006400u)) * r16 + k[c][1];
-        } else if (p.bits == 8) {               // rowsk::Deq1_8: (0,2) (1,3) (4,6) (5,7)
-            h0 = as_f16x2(wide::and_or(q0[c], 0x00ff00ffu, 0x64006400u)) + k[c][0];
-            h1 = as_f16x2(wide::and_or(q0[c] >> 8, 0x00ff00ffu, 0x64006400u)) + k[c][0];
-            h2 = as_f16x2(wide::and_or(q1[c], 0x00ff00ffu, 0x64006400u)) + k[c][0];
-            h3 = as_f16x2(wide::and_or(q1[c] >> 8, 0x00ff00ffu, 0x64006400u)) + k[c][0];
+            h0 = as_f16x2(and_or(q, 0x000f000fu, 0x64006400u)) + k[c][0];
+            h1 = as_f16x2(and_or(q, 0x00f000f0u, 0x64006400u)) * r16 + k[c][1];
+            h2 = as_f16x2(and_or(q8, 0x000f000fu, 0x64006400u)) + k[c][0];
+            h3 = as_f16x2(and_or(q8, 0x00f000f0u, 0x64006400u)) * r16 + k[c][1];
+        } else if (p.bits == 8) {               // Deq1_8: (0,2) (1,3) (4,6) (5,7)
+            h0 = as_f16x2(and_or(q0[c], 0x00ff00ffu, 0x64006400u)) + k[c][0];
+            h1 = as_f16x2(and_or(q0[c] >> 8, 0x00ff00ffu, 0x64006400u)) + k[c][0];
+            h2 = as_f16x2(and_or(q1[c], 0x00ff00ffu, 0x64006400u)) + k[c][0];
+            h3 = as_f16x2(and_or(q1[c] >> 8, 0x00ff00ffu, 0x64006400u)) + k[c][0];
         } else if (p.bits == 3) {               // the 24-bit window, fields 0..3 | 4..7 moved to bit 0 / 3 / 6 / 9 of the halves: Deq1_3's in-place readers
             const unsigned v = __builtin_amdgcn_alignbit(q1[c], q0[c], (unsigned)(24 * ks) & 31u) & 0xffffffu;
             const unsigned w = (v & 0xfffu) | ((v >> 12) << 16);
-            rowsk::Deq1_3<T> d;
+            Deq1_3<T> d;
             d.c0 = k[c][0]; d.c1 = k[c][1]; d.c2 = k[c][2];
             h0 = d.p0(w); h1 = d.p1(w); h2 = d.p2(w); h3 = d.p1(w >> 6);
         } else {                                // half ks & 1 of the word, its bytes moved to the halves: Deq1_2's readers
             const unsigned v = q0[c] >> (16 * (ks & 1));
             const unsigned w = (v & 0xffu) | ((v & 0xff00u) << 8);
-            rowsk::Deq1_2<T> d;
+            Deq1_2<T> d;
             d.c0 = k[c][0]; d.c1 = k[c][1]; d.c2 = k[c][2]; d.c3 = k[c][3];
             h0 = d.p0(w); h1 = d.p1(w); h2 = d.p2(w); h3 = d.p3(w);
         }
@@ -324,12 +324,12 @@ __global__ void __launch_bounds__(THREADS) moe_gemm_kernel(GemmArgs p) {
             const u32x4 bg = pg.frag(p, c, ks, qg0, qg1);
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                if (i < rb) ag[i][c] = rowsk::Mma16<T>::run(a[i], bg, ag[i][c]);
+                if (i < rb) ag[i][c] = Mma16<T>::run(a[i], bg, ag[i][c]);
             if (p.pair) {
                 const u32x4 bu = pu.frag(p, c, ks, qu0, qu1);
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
-                    if (i < rb) au[i][c] = rowsk::Mma16<T>::run(sep ? a3[i] : a[i], bu, au[i][c]);
+                    if (i < rb) au[i][c] = Mma16<T>::run(sep ? a3[i] : a[i], bu, au[i][c]);
             }
         }
     }

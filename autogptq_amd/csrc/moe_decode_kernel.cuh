@@ -14,7 +14,7 @@
 // over ITS OWN count W (so the routed segments sum in the order of the routed launch, bit for bit), and a wave >= W sees clamped chunks only and adds
 // nothing (W < block waves implies W U >= chunks: one pass, every chunk of such a wave is past the end).  The cross-wave slab sits behind BOTH layouts.
 #pragma once
-#include "gemv_tiled_kernel.cuh"     // TiledFmt<BITS>, WordsOf, and through gemv_shared.cuh: Mma4, kslot_sum_swap, dma16_nt
+#include "gemv_tiled_kernel.cuh"     // TiledFmt<BITS>, WordsOf, and through gemv_shared.cuh: Mma4, kslot_sum_swap; common.cuh: lds_dma16_nt
 
 namespace gptq {
 namespace moedec {
@@ -207,11 +207,11 @@ __device__ __forceinline__ void moe_decode_body(const Args& p, const Shared& sp)
             const int cpieces = (G * REC) >> 4;                                   // REC is a multiple of 16
             const char* const cg0 = cst0 + (size_t)strip * G * REC;
             for (int pc0 = wave * 64; pc0 < cpieces; pc0 += WB * 64)
-                if (pc0 + lane < cpieces) dma16_nt(cg0 + (size_t)(pc0 + lane) * 16, __builtin_amdgcn_readfirstlane(c_lds + pc0 * 16));
+                if (pc0 + lane < cpieces) lds_dma16_nt(cg0 + (size_t)(pc0 + lane) * 16, __builtin_amdgcn_readfirstlane(c_lds + pc0 * 16));
             if constexpr (PAIR) {
                 const char* const cg1 = cst1 + (size_t)strip * G * REC;
                 for (int pc0 = wave * 64; pc0 < cpieces; pc0 += WB * 64)
-                    if (pc0 + lane < cpieces) dma16_nt(cg1 + (size_t)(pc0 + lane) * 16, __builtin_amdgcn_readfirstlane(c_lds + (unsigned)cpad + pc0 * 16));
+                    if (pc0 + lane < cpieces) lds_dma16_nt(cg1 + (size_t)(pc0 + lane) * 16, __builtin_amdgcn_readfirstlane(c_lds + (unsigned)cpad + pc0 * 16));
             }
         }
         const char* const xw = pm ? ((same || !sel) ? xs0 : xs1) : xraw;          // the row this wave multiplies: gathered through its perm, or raw

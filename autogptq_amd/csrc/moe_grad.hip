@@ -30,6 +30,7 @@
 #include <algorithm>
 
 #include "common.cuh"
+#include "mma_dequant.cuh"
 #include "launch.h"
 
 namespace gptq {
@@ -38,25 +39,11 @@ namespace mgrad {
 constexpr int THREADS = 256;                // 4 waves: 2 (rows) x 2 (column halves of 64)
 constexpr int BM = 64;                      // tile height (the routing kernel's bm)
 constexpr int BK = 128;                     // output columns per workgroup
-constexpr int ROW_BYTES = 128;              // one LDS image row per stage: 8 slots of 16 bytes
+constexpr int ROW_BYTES = 128;              // one LDS image row per stage: 8 slots of 16 bytes (the row swz() of mma_dequant.cuh lays out)
 constexpr int BN = 64;                      // reduction elements per stage (16-bit dtypes)
 constexpr int CQ = BN / 4;                  // column quads per stage
 constexpr int BUF = (BM + BK) * ROW_BYTES;  // one buffer: A image + B image
 constexpr int LDS_BYTES = 2 * BUF;          // 48 KiB >= the fp32 epilogue tile [64][128] (32 KiB)
-
-__device__ __forceinline__ int swz(int r, int s) { return r * ROW_BYTES + ((s ^ ((r >> 1) & 7)) << 4); }
-
-template <typename T> struct Mma;
-template <> struct Mma<f16> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mma<bf16> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    }
-};
 
 struct ExpertPtrs {                         // one entry of the backward table: [3 projections][E], the checkpoint rows
     const unsigned* qweight;
@@ -225,7 +212,7 @@ __device__ __forceinline__ void walk(const Weights& p, const T* a0, const T* a1,
             for (int i = 0; i < 2; ++i) {
                 if (2 * wm + i >= rb) continue;           // a 16-row block the tile does not have (uniform over the wave)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = Mma<T>::run(a[i], b[j], acc[i][j]);
+                for (int j = 0; j < 4; ++j) acc[i][j] = Mma16<T>::run(a[i], b[j], acc[i][j]);
             }
         }
         if (more) store(st, (it + 1) * BN, smem + ((it + 1) & 1) * BUF);

@@ -29,7 +29,7 @@
 // 2- AND 3-BIT EXPERTS (opt-in: GPTQ_MOE_LOW_BIT_PREFILL in gptq_moe_t.flags): moe_panel_lowbit_kernel<T, 2 | 3>, the same body (moe_panel_body.inc,
 // included into both kernel templates) with the constants of the narrower copy: a strip-chunk is 768 / 512 bytes instead of 1024, a 64-deep step 384 / 256,
 // a lane's share 12 / 8 bytes, fetched by ONE global_load_dwordx3 / dwordx2 into a ring element of that size and dequantised in place by
-// rowsk::Deq1_3::frag(words, ks) / rowsk::Deq1_2::frag(word[ks >> 1] >> 8 (ks & 1)) -- MFMA step ks gets the lane's k = 8 ks .. 8 ks + 7 in the order the A
+// Deq1_3::frag(words, ks) / Deq1_2::frag(word[ks >> 1] >> 8 (ks & 1)) -- MFMA step ks gets the lane's k = 8 ks .. 8 ks + 7 in the order the A
 // operand has them, as at 4 bits.  NT = 4, DW = 2, the constant record (48 bytes, one-byte zero-point), the x side, the loads per step (4 + 8 where a
 // group begins: the vmcnt counts) and the reduction are the 4-bit form's.  Four more instantiations under a name of their own, so that "moe_panel_kernel"
 // keeps meaning the 4- / 8-bit forms, whose code objects are instruction for instruction what they were.  Registers (read off the code object): 232 (fp16) /
@@ -40,8 +40,7 @@
 
 #include "common.cuh"
 #include "launch.h"
-#include "gemm_wide_common.cuh"      // wide::Mma<T>
-#include "gemm_rows_kernel.cuh"      // rowsk::Deq1<T> / Deq1_8<T>
+#include "mma_dequant.cuh"           // DeqSel: Deq1<T> / Deq1_8<T> / Deq1_3<T>, Deq1_2<T>; Mma32<T>
 #include "moe_entry.cuh"             // moerows::Entry, load_entry
 
 namespace gptq {
@@ -65,9 +64,9 @@ struct Args {
     void* out;                                  // pair: H_sorted [R][N] (T); down: Y [R][N] fp32
 };
 
-// 2 bits: the two-word lanes of the copy (rowsk::DeqSel has the 3-, 4- and 8-bit forms) -- moerows::DeqOf of moe_rows.hip, restated for this file
-template <typename T, int BITS> struct DeqOf { typedef typename rowsk::DeqSel<T, BITS>::type type; };
-template <typename T> struct DeqOf<T, 2> { typedef rowsk::Deq1_2<T> type; };
+// 2 bits: the two-word lanes of the copy (DeqSel has the 3-, 4- and 8-bit forms) -- moerows::DeqOf of moe_rows.hip, restated for this file
+template <typename T, int BITS> struct DeqOf { typedef typename DeqSel<T, BITS>::type type; };
+template <typename T> struct DeqOf<T, 2> { typedef Deq1_2<T> type; };
 
 template <typename T, int BITS>
 __global__ void __launch_bounds__(512, 1) moe_panel_kernel(Args p) {

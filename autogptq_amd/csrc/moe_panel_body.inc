@@ -66,7 +66,7 @@
     const unsigned a3off = planes > 1 ? (unsigned)XB : 0u;     // W3's blocks read plane 1 when there is one
 
     // a lane's words of one k-slot of the copy, written by ONE load (no copies between the load and the wait): 3 words at 3 bits, 2 at 2 bits
-    using WV = std::conditional_t<BITS == 3, wide::u32x3, std::conditional_t<BITS == 2, u32x2, u32x4>>;
+    using WV = std::conditional_t<BITS == 3, u32x3, std::conditional_t<BITS == 2, u32x2, u32x4>>;
     struct Buf { WV w[NT][NH]; unsigned cs[NT], cz[NT]; };
     Buf q[DW];
     // every register of the ring starts as its own opaque definition: the compiler cannot share one between two loads' destinations and split them with a
@@ -194,7 +194,7 @@
                     }
                     if (i + 1 < 4 * NT) bq[(i + 1) & 1] = frag_of((i + 1) % NT, (i + 1) / NT);
 #pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = wide::Mma<T>::run(a[h & 1][mt], bq[i & 1], acc[mt][nt]);
+                    for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = Mma32<T>::run(a[h & 1][mt], bq[i & 1], acc[mt][nt]);
                     if (i + 1 < 4 * NT) {                     // MFMA, its share of the next fragment's VALU, MFMA, ...
                         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                         __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);

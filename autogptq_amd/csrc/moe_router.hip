@@ -30,6 +30,7 @@
 // values P apart and keep a (largest, second) pair of keys, log2 P shuffle steps merge the pairs; a group's rank is counted over G lane reads of the
 // group scores (no butterfly), one ballot marks the groups that stay, and the wave-wide arg-max rounds run on keys cleared outside them.
 #include "common.cuh"
+#include "mma_dequant.cuh"
 #include "launch.h"
 
 namespace gptq {
@@ -54,25 +55,6 @@ struct Args {
     const float* bias;                      // [E] or NULL
     float* scores;                          // fp32 [T, E] or NULL
 };
-
-template <typename T> struct Mma;
-template <> struct Mma<f16> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mma<bf16> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    }
-};
-
-template <typename T>
-__device__ __forceinline__ void unpack8(u32x4 v, float (&f)[8]) {
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int c = 0; c < 8; ++c) f[c] = DType<T>::to_f32(__builtin_bit_cast(T, (unsigned short)(w[c >> 1] >> (16 * (c & 1)))));
-}
 
 template <typename T>
 __device__ __forceinline__ float round_to(float v) { return DType<T>::to_f32(DType<T>::from_f32(v)); }
@@ -273,7 +255,7 @@ __device__ __forceinline__ void tiles_kloop(const char* xp, bool xok, const char
         for (int i = 0; i < U; ++i)
 #pragma unroll
             for (int n = 0; n < NT; ++n)
-                if (n < ntiles) acc[n] = Mma<T>::run(xa[i], wa[i][n], acc[n]);
+                if (n < ntiles) acc[n] = Mma16<T>::run(xa[i], wa[i][n], acc[n]);
     }
 }
 

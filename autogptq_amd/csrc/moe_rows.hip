@@ -18,15 +18,15 @@
 //   * stages its 16 rows x 128 k of the A operand by LDS DMA into wave-private double buffers (no barrier in the K loop).  The DMA's per-lane global address
 //     gathers the rows: row r of the tile is x[row_assign[first + r] / topk] (pair form) or H_sorted[first + r] (down form); the XOR swizzle against the
 //     256-byte row pitch is applied on the global side, as in the rows kernel.  Rows past the tile's count repeat its last row and are not stored;
-//   * dequantises with rowsk::Deq1 / Deq1_8 (bit-exact W, one rounding) and runs v_mfma_f32_16x16x32_{f16,bf16} (rowsk::Mma16).
+//   * dequantises with Deq1 / Deq1_8 (bit-exact W, one rounding) and runs v_mfma_f32_16x16x32_{f16,bf16} (Mma16).
 // No K slices, no atomics: every output is one fixed-order sum -- bit-reproducible, and a token's row depends only on that token's x, indices and weights
 // (the fp32 sum of a row does not depend on which other rows share its tile: the MFMA rows are independent).
 // The pair / down form, the group mode and the number of staged planes are run-time uniform: T x BITS = four instantiations.
 //
 // 2- AND 3-BIT EXPERTS (opt-in: GPTQ_MOE_LOW_BIT_BATCH in gptq_moe_t.flags): moe_rows_lowbit_kernel<T, 2 | 3>, the same body (moe_rows_body.inc, included
 // into both kernel templates) with three template constants: the strip-chunk of the copy is 768 / 512 bytes instead of 1024, a lane's share 12 / 8 bytes
-// instead of 16, fetched by ONE global_load_dwordx3 / dwordx2 into a ring element of that size, and dequantised in place by rowsk::Deq1_3::frag(words, ks) /
-// rowsk::Deq1_2::frag(word[ks >> 1] >> 8 (ks & 1)) -- MFMA step ks gets the lane's k = 8 ks .. 8 ks + 7 in the order the A operand has them, as at 4 bits.
+// instead of 16, fetched by ONE global_load_dwordx3 / dwordx2 into a ring element of that size, and dequantised in place by Deq1_3::frag(words, ks) /
+// Deq1_2::frag(word[ks >> 1] >> 8 (ks & 1)) -- MFMA step ks gets the lane's k = 8 ks .. 8 ks + 7 in the order the A operand has them, as at 4 bits.
 // The constant record (48 bytes, one-byte zero-point), the group offsets, the x side, the ring depth, the loads per chunk (3 NS: the vmcnt counts) and the
 // reduction are the 4-bit form's.  Four more instantiations under a name of their own, so that "moe_rows_kernel" keeps meaning the 4- / 8-bit forms, whose
 // code objects are instruction for instruction what they were.  Registers (read off the code object): 124 (fp16) / 125 (bf16) VGPRs at both widths, no
@@ -55,7 +55,7 @@
 
 #include "common.cuh"
 #include "launch.h"
-#include "gemm_rows_kernel.cuh"      // rowsk::Deq1<T> / Deq1_8<T>, rowsk::Mma16<T>
+#include "mma_dequant.cuh"           // DeqSel: Deq1<T> / Deq1_8<T> / Deq1_3<T>, Deq1_2<T>; Mma16<T>
 #include "moe_entry.cuh"             // moerows::Entry, load_entry
 
 namespace gptq {
@@ -83,8 +83,8 @@ struct Args {
 // 2 / 3 bits (opt-in: GPTQ_MOE_LOW_BIT_BATCH): the copy of utils.hip prepack_decode_weights_kernel read in place -- Deq1_3::frag(words, ks) as the dense rows
 // kernel does, Deq1_2::frag(word[ks >> 1] >> 8 (ks & 1)): pair p = (k 16 w + 2 p, + 1) sits at bit 2 p of the halves of word w, so fields 0..3 of the
 // (shifted) word are k = 8 ks .. 8 ks + 7 of the lane's 32 in the order the A operand has them
-template <typename T, int BITS> struct DeqOf { typedef typename rowsk::DeqSel<T, BITS>::type type; };
-template <typename T> struct DeqOf<T, 2> { typedef rowsk::Deq1_2<T> type; };
+template <typename T, int BITS> struct DeqOf { typedef typename DeqSel<T, BITS>::type type; };
+template <typename T> struct DeqOf<T, 2> { typedef Deq1_2<T> type; };
 
 // 2 / 3 / 4 bits: compiled for 128 registers (two 8-wave workgroups per CU); 8 bits: a ring slot is twice as large -- 256 registers, one workgroup per CU
 template <typename T, int BITS>

@@ -56,7 +56,7 @@
     const int c0 = wave * p.cpw, c1 = min(c0 + p.cpw, p.chunks);
 
     // a lane's words of one chunk of the copy, written by ONE load (no copies between the load and the wait): 3 words at 3 bits, 2 at 2 bits
-    using WV = std::conditional_t<BITS == 3, wide::u32x3, std::conditional_t<BITS == 2, u32x2, u32x4>>;
+    using WV = std::conditional_t<BITS == 3, u32x3, std::conditional_t<BITS == 2, u32x2, u32x4>>;
     struct Buf { WV wq[NS][NH]; unsigned cs[NS][NH], cz[NS][NH]; };
     Buf q[DW];
     // every register of the ring starts as its own opaque definition: the compiler cannot share one between two loads' destinations and split them with a
@@ -140,7 +140,7 @@
                 else if constexpr (BITS == 3) bq = dq[v][0].frag(B.wq[v][0], w);
                 else if constexpr (BITS == 2) bq = dq[v][0].frag(B.wq[v][0][w >> 1] >> (8 * (w & 1)));
                 else bq = dq[v][w >> 1].frag(B.wq[v][w >> 1][2 * (w & 1)], B.wq[v][w >> 1][2 * (w & 1) + 1]);
-                acc[v] = rowsk::Mma16<T>::run(v < NS / 2 ? a1[w] : a3[w], bq, acc[v]);
+                acc[v] = Mma16<T>::run(v < NS / 2 ? a1[w] : a3[w], bq, acc[v]);
             }
             if (has_x) issue_x(cn, b ^ 1, w, w + 1);
         }

@@ -138,7 +138,7 @@ __global__ void __launch_bounds__(1024) gemm_strips_kernel(StripsParams p) {
             const char* cg = (const char*)p.cst + (size_t)strip_l * p.G * 48;
             const int cpieces = (p.G * 48) >> 4;
             for (int pc0 = 0; pc0 < cpieces; pc0 += 64)
-                if (pc0 + lane < cpieces) dma16_nt(cg + (size_t)(pc0 + lane) * 16, __builtin_amdgcn_readfirstlane(cs_lds + (unsigned)st * (unsigned)p.cpad + (unsigned)pc0 * 16u));
+                if (pc0 + lane < cpieces) lds_dma16_nt(cg + (size_t)(pc0 + lane) * 16, __builtin_amdgcn_readfirstlane(cs_lds + (unsigned)st * (unsigned)p.cpad + (unsigned)pc0 * 16u));
         }
     }
     // ---- this wave's chunks: quarter kq of the slice

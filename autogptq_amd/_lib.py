@@ -29,7 +29,7 @@ EXPORTS = (
     "gptq_forward", "gptq_forward_ex", "gptq_gemv", "gptq_gemm", "gptq_dequant", "gptq_grad_input",
     "gptq_unpack_weights", "gptq_unpack_zeros", "gptq_pack_weights", "gptq_pack_zeros",
     "gptq_make_sequential", "gptq_resequence_qweight", "gptq_permute_columns", "gptq_prepack_decode", "gptq_prepack_decode_bytes", "gptq_unprepack_decode",
-    "gptq_awq_unpack", "gptq_awq_repack", "gptq_describe_plan",
+    "gptq_awq_unpack", "gptq_awq_repack", "gptq_describe_plan", "gptq_describe_plan_xstage",
     "gptq_init", "gptq_workspace_bytes_max", "gptq_validate_g_idx",
     "gptq_forward_multi", "gptq_workspace_bytes_multi", "gptq_forward_multi_ex", "gptq_workspace_bytes_multi_ex",
     "gptq_peer_scatter", "gptq_peer_collect", "gptq_peer_gather", "gptq_forward_scatter", "gptq_forward_gather", "gptq_peer_publish",
@@ -191,6 +191,7 @@ def load() -> ctypes.CDLL:
     lib.gptq_prepack_decode.argtypes = [POINTER(GptqLayer), c_void_p, c_void_p, c_void_p]
     lib.gptq_unprepack_decode.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
     lib.gptq_describe_plan.argtypes = [POINTER(GptqLayer), c_int, POINTER(GptqTuning), c_char_p, c_size_t]
+    lib.gptq_describe_plan_xstage.argtypes = [POINTER(GptqLayer), c_int, POINTER(GptqTuning)]
     lib.gptq_awq_unpack.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
     lib.gptq_awq_repack.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
     LP = POINTER(GptqLayer)
@@ -350,7 +351,11 @@ def _pointer_array(ctype, items):
 
 def describe_plan(layer: "GptqLayer", M: int, tuning: "GptqTuning | None" = None) -> dict:
     """Kernel and launch geometry gptq_forward_ex would pick (host-only query, see gptq_describe_plan in the header)."""
-    return _describe("gptq_describe_plan", ctypes.byref(layer), M, ctypes.byref(tuning) if tuning is not None else None)
+    tp = ctypes.byref(tuning) if tuning is not None else None
+    d = _describe("gptq_describe_plan", ctypes.byref(layer), M, tp)
+    if d.get("kernel") == "strips":      # the decode-copy kernel: x and the constants staged in one step or two (gptq_describe_plan_xstage; the C line itself is pinned)
+        d["xstage"] = int(load().gptq_describe_plan_xstage(ctypes.byref(layer), M, tp))
+    return d
 
 
 def describe_mlp_plan(gate: "GptqLayer", up: "GptqLayer", down: "GptqLayer", M: int, tuning: "GptqTuning | None" = None) -> dict:

@@ -1679,6 +1679,12 @@ int gptq_permute_columns(const void* x, const int32_t* perm, int M, int K, int d
     return GPTQ_OK;
 }
 
+int gptq_describe_plan_xstage(const gptq_layer_t* L, int M, const gptq_tuning_t* tune) {
+    if (check_layer(L) || M <= 0 || (tune && (tune->path == 2 || tune->path == 4))) return 0;
+    const ForwardRoute r = route_forward(L, M, tune);
+    return (r.kind == ROUTE_TILED || r.kind == ROUTE_TILED_PAIR) ? r.tp.xsteps : 0;
+}
+
 int gptq_describe_plan(const gptq_layer_t* L, int M, const gptq_tuning_t* tune, char* out, size_t out_bytes) {
     if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out must be non-NULL");
     out[0] = 0;

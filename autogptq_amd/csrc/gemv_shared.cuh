@@ -133,6 +133,13 @@ __device__ __forceinline__ int scalar_ge(int a, int b) {
     return r;
 }
 
+// (c != 0 ? a : b) on the scalar unit, for the reason scalar_ge gives
+__device__ __forceinline__ int scalar_sel_nz(unsigned c, int a, int b) {
+    int r;
+    asm("s_cmp_lg_u32 %1, 0\n\ts_cselect_b32 %0, %2, %3" : "=s"(r) : "s"(c), "s"(a), "s"(b) : "scc");
+    return r;
+}
+
 struct GemvSeg {
     const unsigned* qweight;
     const unsigned* qzeros;

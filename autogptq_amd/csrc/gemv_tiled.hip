@@ -22,7 +22,8 @@
 //
 // Kernel (one strip, or one K slice of it, per workgroup; W waves x U chunks in flight per wave):
 //   * x (M rows, the slice's k range) and the strip's constants go global -> LDS by DMA FIRST (they return first), the wave's U weight loads behind them;
-//     one barrier, by which time the weights are in flight;
+//     one barrier, by which time the weights are in flight (a plain 4-bit fp16 launch deeper than one pass of its workgroup: only the first pass's part in front of the
+//     weights, the rest behind that barrier, visible by a second one between the first and the second pass -- TiledPlan.xsteps);
 //   * per chunk and lane: 16 bytes of weights (registers, nontemporal), x fragments by 4 ds_read_b128 (lane i of a 4-lane group reads x row i: the A
 //     operand of v_mfma_f32_4x4x4), scale + zero-point by ds_read_u16 / ds_read_u8; w - z exactly in packed fp16, 8 matrix-core steps into one fp32
 //     group sum, times the scale: the arithmetic of every other decode kernel here (one-hot rows return the reference's exact scales * (w - z));
@@ -203,6 +204,12 @@ TiledPlan plan_tiled(const gptq_layer_t* const* Ls, int n, int M, const gptq_tun
     // plain layers (no act-order, no pair epilogue), where the form is compiled.  tuning.reserved[GPTQ_LAB_GEMM_VARIANT] = GPTQ_LAB_VARIANT_TILED_GENERAL keeps the general form.
     pl.aligned = A.K % cke == 0 && !A.g_idx && !pair && tiled_has_aligned(A.bits, pl.mt, u, nstr) &&
                  !(tune && tune->reserved[GPTQ_LAB_GEMM_VARIANT] == GPTQ_LAB_VARIANT_TILED_GENERAL);
+    // Two-step staging: a plain 4-bit fp16 launch without K slices whose K is deeper than one pass of its workgroup (waves x u chunks) stages only that
+    // pass's x and constants in front of the first weight burst.  One step everywhere else: act-order layers (the gather runs over all of x behind the barrier), bf16 and
+    // 2- / 3- / 8-bit layers (run sums / block floats over all of x; not priced), pair and multi-strip forms (profiles/two_step_staging_ablate.log: nothing to gain),
+    // K slices (they stage a slice); the tensor-parallel launch keeps one step in launch_tiled.  tuning.reserved[GPTQ_LAB_GEMM_VARIANT] = GPTQ_LAB_VARIANT_TILED_ONE_STEP keeps one step.
+    pl.xsteps = (!A.g_idx && !pair && nstr == 1 && A.bits == 4 && A.dtype == GPTQ_F16 && pl.ksplit == 1 && A.K > waves * u * cke &&
+                 !(tune && tune->reserved[GPTQ_LAB_GEMM_VARIANT] == GPTQ_LAB_VARIANT_TILED_ONE_STEP)) ? 2 : 1;
     pl.xstride = cps * cke * 2 + 16;
     pl.lds_bytes = lds_need(pl.ksplit, waves);
     pl.xraw_off = A.g_idx ? (int)((pl.lds_bytes - ((size_t)pl.mt * ((size_t)A.K * 2 + 16) + 16) + 15) & ~(size_t)15) : 0;
@@ -264,6 +271,12 @@ hipError_t launch_tiled(const gptq_layer_t* const* Ls, const TiledPlan& pl, cons
     p.xraw_off = pl.xraw_off;
     p.pair_strips = pl.pair ? A.N / (2 * GPTQ_STRIP_COLS) : 0;
     p.act = A.epilogue;
+    if (pl.xsteps == 2 && !pg && !pl.pair) {                                      // (the plain kernels read the word the pair kernels read as pair_strips: 0 = one step)
+        const int kpl = tiled_kpl(A.bits), k1 = pl.waves * pl.u * 4 * kpl;        // the first pass: what step 1 stages of every row of x ...
+        const int gt = (((k1 - 1) / kpl) >> p.gu_shift) + 1, g1 = gt < pl.groups ? gt : pl.groups;      // ... and the groups it touches
+        const unsigned xp = (unsigned)k1 / 8u, cp = (unsigned)g1 * (unsigned)tiled_rec_bytes(A.bits) / 16u;
+        if (k1 < A.K && xp < 65536u && cp < 65536u) p.xstep1 = xp | (cp << 16);
+    }
     if (pg) {                                                                     // plain layers, 2 or 4 chunks per wave in flight (the compiled forms)
         if (A.g_idx || A.bits == 2 || (pl.u != 2 && pl.u != 4)) return hipErrorInvalidValue;
         TiledPlan plg = pl;

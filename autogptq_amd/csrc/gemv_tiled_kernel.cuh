@@ -36,7 +36,10 @@ struct TiledParams {
     const void* x;
     int M, K;
     int chunks, chunks_per_split, ksplit, gu_shift, groups, xstride, waves;
-    int pair_strips;         // PAIR kernels: strips of one half of the [gate | up] layer (N / 32)
+    union {
+        int pair_strips;     // PAIR kernels: strips of one half of the [gate | up] layer (N / 32)
+        unsigned xstep1;     // plain 4-bit fp16 kernels: 0 = x and the constants are staged in ONE step; else what the first of TWO steps stages, in 16-byte pieces --
+    };                       // bits 0..15 of a row of x (the workgroup's first pass: waves * U chunks), bits 16..31 of the constants (the groups that range touches)
     const unsigned* tq[4];   // qweight_tiled of layer i
     const void* cst[4];      // qconst_tiled
     // ---- act-order kernels: part of their entry batch
@@ -92,6 +95,7 @@ template <int N_> struct WordsOf { typedef unsigned type __attribute__((ext_vect
 template <int BITS, int MT, int U, typename T, int MAXW, int XM = 0, int FL = 0>
 __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kernel(TiledParams p) {
     constexpr int ZM2 = FL & 1;
+    constexpr bool BF_ = std::is_same_v<T, bf16>;
     // Lab (tools/ab_tiled.sh ABLn -DGPTQ_TILED_ABL=n; timing only, the outputs are WRONG by design; never in the product library; fp16 4-bit forms): bit 1 = every
     // kernel takes the aligned form's addressing, 2 = no decode (raw words to the matrix core), 4 = no x reads from the LDS, 8 = no matrix-core steps.
 #ifdef GPTQ_TILED_ABL
@@ -174,6 +178,15 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
     const int be0 = (int)ha[0], be1 = (int)ha[1], be2 = (int)ha[2], Mrows = (int)ha[6], K = (int)ha[7], nchunks = (int)ha[8], cps = (int)ha[9], ksplit = (int)ha[10],
               gshift = (int)ha[11], G = (int)ha[12], xstride = (int)ha[13], W = (int)ha[14];
     [[maybe_unused]] const int hstrips = (int)ha[15], act = (int)ha[3];           // PAIR: strips of one half; the activation of the epilogue
+    // Two-step staging: a launch deeper than one pass of its workgroup stages in front of the first weight burst only what the first pass reads; the
+    // rest of x and of the constants follows BEHIND the staging barrier and is in the LDS by a second barrier in front of the second pass.  The planner's word
+    // (TiledPlan.xsteps): 0 = one step -- such a launch runs what it ran before plus two selects in the head and two compares on this word.
+#if defined(GPTQ_TILED_NO_ROLL) || defined(GPTQ_TILED_WEIGHTS_FIRST)                   // (lab loops without the second barrier: every launch stages in one step)
+    constexpr bool TWO = false;
+#else
+    constexpr bool TWO = XM == 0 && BITS == 4 && !BF_;
+#endif
+    [[maybe_unused]] const unsigned xstep1 = TWO ? ha[15] : 0u;
     typedef __attribute__((address_space(1))) const char gchar;                   // (behind the asm the compiler no longer knows that these are global pointers)
     gchar* const xg = (gchar*)(((unsigned long long)ha[5] << 32) | ha[4]);
     // workgroup -> (strip over all layers, K slice); no XCD remap: strips share nothing but x, which every L2 holds.  A launch without K slices (every launch of
@@ -241,7 +254,13 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
                 xrow[m] = xg + (unsigned)((m == 0 ? 0 : min(m, Mrows - 1)) * K + kbeg) * 2u;
                 xdst[m] = xs_lds + m * xstride;
             }
-            stage_rows<MT, false>(xrow, xdst, tid, w64, step, (kend - kbeg) >> 3);      // default cache policy: every workgroup reads x
+#ifdef GPTQ_TILED_STAGE1                                                           // lab (tools/ab_tiled.sh STAGE1; timing only, the outputs are WRONG by design): only what the first pass reads is staged
+            stage_rows<MT, false>(xrow, xdst, tid, w64, step, min(kend - kbeg, Wh * U * CKE) >> 3);
+#else
+            int xpieces = (kend - kbeg) >> 3;
+            if constexpr (TWO) xpieces = scalar_sel_nz(xstep1, (int)(xstep1 & 0xffffu), xpieces);      // two steps: the first pass's part of every row
+            stage_rows<MT, false>(xrow, xdst, tid, w64, step, xpieces);         // default cache policy: every workgroup reads x
+#endif
         } else if constexpr (ACT) {
             // act-order: the RAW rows, whole K (a slice's positions map to any original k), by the same DMA; the gather through perm is LDS -> LDS
 #pragma unroll
@@ -251,7 +270,12 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
             }
             stage_rows<MT, false>(xrow, xdst, tid, w64, step, K >> 3);
         }
-        const int cpieces = (int)(crec >> 4) * (MULTI ? NSTR : 1);                // REC is a multiple of 16 (MULTI: adjacent strips' records are adjacent, cpad = G * REC)
+#ifdef GPTQ_TILED_STAGE1                                                           // (the byte count of the first pass's groups; multi-strip forms: not where the strips' records lie)
+        const int cpieces = (ACT ? G : min(G, ((min(kend - kbeg, Wh * U * CKE) - 1) >> LKPL >> gshift) + 1)) * (REC >> 4) * (MULTI ? NSTR : 1);
+#else
+        int cpieces = (int)(crec >> 4) * (MULTI ? NSTR : 1);                      // REC is a multiple of 16 (MULTI: adjacent strips' records are adjacent, cpad = G * REC)
+        if constexpr (TWO) cpieces = scalar_sel_nz(xstep1, (int)(xstep1 >> 16), cpieces);          // two steps: the records of the groups the first pass touches
+#endif
         if constexpr (PAIR) {                                                     // the up strip's constants behind the gate strip's
             gchar* const crow[2] = {cg, cg + (size_t)(unsigned)hstrips * crec};
             const unsigned cdst[2] = {cs_lds, cs_lds + (unsigned)cpad};
@@ -260,6 +284,31 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
             gchar* const crow[1] = {cg};
             const unsigned cdst[1] = {cs_lds};
             stage_rows<1, true>(crow, cdst, tid, w64, step, cpieces);
+        }
+    };
+    // Step 2 of a two-step launch (xstep1 != 0; no K slices: kbeg = 0, kend = K): the rest of every row of x and of the constants, to the places the one-step launch
+    // puts them, by the same DMAs over all waves, issued BEHIND the staging barrier -- so behind the first weight burst, and older than every refill: a wave's loads
+    // return in issue order, so the wait in front of the wave's LAST first-pass chunk retires its step-2 DMAs, and the earlier chunks of the pass are decoded, and
+    // their registers refilled, while step 2 is still on its way.
+    // (Measured and not taken, profiles/two_step_staging_ab.log: step 2 by the last quarter of the waves only, so that the others never wait for a DMA -- 1.2 %
+    // SLOWER than the one-step launch; step 2 in front of the staging barrier with a counted wait that leaves it in flight -- no gain over the one-step launch.)
+    auto stage_rest = [&]() __attribute__((always_inline)) {
+        if constexpr (TWO) {
+            const unsigned xs_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)xs, cs_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)cs;
+            const int w64 = wave * 64, step = W * 64;
+            const int xp1 = (int)(xstep1 & 0xffffu), cp1 = (int)(xstep1 >> 16);  // pieces of step 1: per row of x, of the constants
+            const int xp2 = (K >> 3) - xp1, cp2 = (int)(crec >> 4) - cp1;         // ... and of step 2
+            gchar* xrow[MT];
+            unsigned xdst[MT];
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+                xrow[m] = xg + ((unsigned)((m == 0 ? 0 : min(m, Mrows - 1)) * K) * 2u + (unsigned)xp1 * 16u);
+                xdst[m] = xs_lds + m * xstride + (unsigned)xp1 * 16u;
+            }
+            stage_rows<MT, false>(xrow, xdst, tid, w64, step, xp2);
+            gchar* const crow[1] = {cg + (unsigned)cp1 * 16u};
+            const unsigned cdst[1] = {cs_lds + (unsigned)cp1 * 16u};
+            stage_rows<1, true>(crow, cdst, tid, w64, step, cp2);
         }
     };
 #ifndef GPTQ_TILED_WEIGHTS_FIRST
@@ -469,6 +518,9 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
             x_gather();
         }
         __syncthreads();
+        if constexpr (TWO) {
+            if (__builtin_expect(xstep1 != 0u, 0)) stage_rest();            // two steps: younger than the U weight loads in flight, older than every refill
+        }
         if constexpr (XC) x_to_f16();
         if constexpr (XS) x_sums();
         seg_pin();
@@ -660,16 +712,42 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
         for (int j = 0; j < U; ++j) q[j] = wload(c0 + j);
         first_pass();
         if constexpr (AL) { xpass = (unsigned)(size_t)xll + (unsigned)(c0 - cb) * (unsigned)(CKE * 2); asm volatile("" : "+v"(xpass)); }
-        for (int cn = c0 + Wh * U; cn < ce; cn += Wh * U) {                       // this wave has a live chunk in the next pass
+        int cn = c0 + Wh * U;
+        auto steady = [&](const int stop) __attribute__((always_inline)) {
+            for (; cn < stop; cn += Wh * U) {                                     // this wave has a live chunk in the next pass
 #pragma unroll
-            for (int j = 0; j < U; ++j) {
-                chunk(std::true_type{}, c0 + j, j, q[j]);
-                __builtin_amdgcn_sched_barrier(0);
-                q[j] = wload(cn + j);
-                __builtin_amdgcn_sched_barrier(0);
+                for (int j = 0; j < U; ++j) {
+                    chunk(std::true_type{}, c0 + j, j, q[j]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    q[j] = wload(cn + j);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                c0 = cn;
+                if constexpr (AL) { xpass += (unsigned)(Wh * U) * (unsigned)(CKE * 2); asm volatile("" : "+v"(xpass)); }
             }
-            c0 = cn;
-            if constexpr (AL) { xpass += (unsigned)(Wh * U) * (unsigned)(CKE * 2); asm volatile("" : "+v"(xpass)); }
+        };
+        if constexpr (TWO) {
+            // Two steps: the steady loop stops ONCE behind the wave's first pass -- or in front of it, where the wave has no chunk in a second one --
+            // for the barrier that makes step 2 visible: straight-line code between two runs of the SAME loop, reached exactly once by every wave whatever its
+            // chunk count, never inside the loop block.  The wave's own step-2 DMAs are older than every refill: the wait in front of its last first-pass chunk
+            // (at most U - 1 refills, and the bias, are younger) has retired them; vmcnt(U) says so again and changes nothing.  A wave that will not enter the loop
+            // has its U first chunks and its DMAs outstanding, the DMAs youngest: vmcnt(0), where the run is set up -- it decodes those chunks next.  A raw s_barrier, not
+            // __syncthreads(): the refills stay in flight across it.
+            int stop = ce, pend = 0;
+            if (__builtin_expect(xstep1 != 0u, 0)) {
+                pend = 1; stop = min(cn + 1, ce);
+                if (cn >= ce) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+        second_run:
+            asm volatile("" : "+s"(stop), "+s"(pend));                            // (opaque: one copy of the loop, not one per run)
+            steady(stop);
+            if (__builtin_expect(pend != 0, 0)) {
+                asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(U) : "memory");
+                pend = 0; stop = ce;
+                goto second_run;
+            }
+        } else {
+            steady(ce);
         }
 #ifdef GPTQ_TILED_STAMPS
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); TILED_STAMP(3);          // the last pass's chunks have landed

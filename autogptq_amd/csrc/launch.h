@@ -147,6 +147,7 @@ struct TiledPlan {
     size_t partial_bytes;    // behind the header: [ksplit - 1][M][nsum] granules when ksplit > 1
     bool zm2;                // bf16 4-bit layers at 2 rows, launches below 1024 workgroups: the zero-point on the matrix core (gemv_tiled_kernel<..., FL bit 0>)
     bool aligned;            // 4-bit layers whose K is a whole number of chunks, in the forms that have an aligned twin: the K loop with scalar per-chunk addressing (FL bit 1)
+    int xsteps;              // 1 or 2: plain 4-bit fp16 launches without K slices that are deeper than one pass of their workgroup stage x and the constants in two steps
 };
 bool tiled_layer_ok(const gptq_layer_t& L);
 TiledPlan plan_tiled(const gptq_layer_t* const* layers, int n, int M, const gptq_tuning_t* tune);

@@ -684,6 +684,11 @@ int gptq_permute_columns(const void *x, const int32_t *perm, int M, int K, int d
  *   "path=gemm kernel=tiled mt=4 bk=64 kg=2 ksplit=1 tiles=16x16 perm=1 dma=1"
  * (the reference's dispatch thresholds, SURVEY §8 a15, are constants in its sources; here they are queryable.) */
 int gptq_describe_plan(const gptq_layer_t *layer, int M, const gptq_tuning_t *tuning, char *out, size_t out_bytes);
+/* Host-only, beside gptq_describe_plan (whose line is pinned byte for byte by tests/test_forward_entry_contract.py and so does not grow): in how many steps the
+ * decode-copy kernel ("kernel=strips") stages x and the constants for (layer, M, tuning) -- 2: a plain 4-bit fp16 launch without K slices that is deeper than one
+ * pass of its workgroup (waves * u chunks) stages only that pass's part in front of the first weight burst and the rest behind it; 1: every other decode-copy
+ * launch; 0: another kernel, or arguments gptq_describe_plan would refuse.  The Python wrapper reports it as "xstage" of describe_plan(). */
+int gptq_describe_plan_xstage(const gptq_layer_t *layer, int M, const gptq_tuning_t *tuning);
 
 /* ---- AWQ checkpoint ingest (4-bit only, as the reference: auto_gptq/modeling/_utils.py:525-701) ----------------
  * AWQ side: awq_qweight u32 [K, N/8] (nibble p of word c = column 8c + {0,2,4,6,1,3,5,7}[p]), awq_qzeros u32 [G, N/8]

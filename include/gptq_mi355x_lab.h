@@ -51,6 +51,7 @@
 #define GPTQ_LAB_VARIANT_PANEL_OFF 53     /* never that kernel */
 #define GPTQ_LAB_VARIANT_MLP_TWO_PASSES 54 /* gptq_mlp_forward_ex (path = 0): SiLU * mul and the x permute of an act-order down projection as the two passes of round 5 */
 #define GPTQ_LAB_VARIANT_TILED_GENERAL 60  /* decode-copy kernel: the general K loop where the planner would take the aligned form (TiledPlan.aligned; any path) */
+#define GPTQ_LAB_VARIANT_TILED_ONE_STEP 61 /* decode-copy kernel: x and the constants staged in one step where the planner would take two (TiledPlan.xsteps; any path) */
 /* (9..24, 32: ablation / timeline / ping-pong variants compiled only into tools/gemmlab with -DGPTQ_GEMM_ABLATIONS) */
 
 #endif /* GPTQ_MI355X_LAB_H */

@@ -4,6 +4,8 @@
 # (gemv_tiled*.hip include gemv_tiled_kernel.cuh) rebuilt with the flags; select the library with GPTQ_MI355X_LIB=tools/libgptq_ZM1.so
 #   tools/ab_tiled.sh ABL1 -DGPTQ_TILED_ABL=1  -> the K-loop ablations of DESIGN.md 14 (TIMING ONLY: the outputs are wrong by design).  Bits, or-ed: 1 = every kernel
 #   takes the aligned form's addressing, 2 = no decode (raw words to the matrix core), 4 = no x reads from the LDS, 8 = no matrix-core steps (fp16 4-bit forms).
+#   tools/ab_tiled.sh STAGE1 -DGPTQ_TILED_STAGE1 -> the staging ablation of DESIGN.md 15 (TIMING ONLY: wrong outputs by design): every plain, pair and multi-strip launch
+#   stages only what its first pass reads of x and of the constants and skips the rest -- the ceiling of two-step staging, per launch type.
 set -eu
 NAME=$1; shift
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

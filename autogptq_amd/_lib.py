@@ -19,7 +19,9 @@ ABI_VERSION = 8
 GPTQ_F16, GPTQ_BF16, GPTQ_F32 = 0, 1, 2
 ZERO_WRAP, ZERO_NOWRAP = 0, 1
 EPI_NONE, EPI_SILU_MUL, EPI_GELU_TANH_MUL = 0, 1, 2
-EPILOGUE_ENUM = {"none": EPI_NONE, "silu_mul": EPI_SILU_MUL, "gelu_tanh_mul": EPI_GELU_TANH_MUL}      # QuantLinear(epilogue=...) -> gptq_epilogue_t
+EPI_RELU, EPI_GELU, EPI_GELU_TANH = 16, 17, 18      # the ungated epilogues: out is [M, N]
+EPILOGUE_ENUM = {"none": EPI_NONE, "silu_mul": EPI_SILU_MUL, "gelu_tanh_mul": EPI_GELU_TANH_MUL,
+                 "relu": EPI_RELU, "gelu": EPI_GELU, "gelu_tanh": EPI_GELU_TANH}      # QuantLinear(epilogue=...) -> gptq_epilogue_t
 
 DTYPE_ENUM = {torch.float16: GPTQ_F16, torch.bfloat16: GPTQ_BF16, torch.float32: GPTQ_F32}
 

@@ -61,7 +61,7 @@ int check_layer(const gptq_layer_t* L) {
     if ((L->qweight_tiled != nullptr) != (L->tiled_cols != 0) || (L->qweight_tiled != nullptr) != (L->qconst_tiled != nullptr) ||
         (L->tiled_cols != 0 && L->tiled_cols != GPTQ_STRIP_COLS))
         return fail(GPTQ_ERR_UNSUPPORTED, "qweight_tiled, qconst_tiled and tiled_cols (%d) must be given together, tiled_cols = %d", L->tiled_cols, GPTQ_STRIP_COLS);
-    if (L->epilogue != GPTQ_EPI_NONE && !is_gated(L->epilogue))
+    if (L->epilogue != GPTQ_EPI_NONE && !is_gated(L->epilogue) && !is_plain_act(L->epilogue))
         return fail(GPTQ_ERR_UNSUPPORTED, "unknown epilogue %d", L->epilogue);
     if (is_gated(L->epilogue) && L->N % 64)
         return fail(GPTQ_ERR_SHAPE, "the %s epilogue needs out_features (%d) to be a multiple of 64 ([gate | up] halves)", L->epilogue == GPTQ_EPI_SILU_MUL ? "SILU_MUL" : "GELU_TANH_MUL", L->N);
@@ -241,7 +241,9 @@ const char* gptq_status_string(int s) {
 }
 
 // Unfused SILU_MUL / GELU_TANH_MUL: y[M, N] goes to the front of the workspace, the elementwise pass writes out[M, N/2].
+// Unfused RELU / GELU / GELU_TANH: y goes to out[M, N] and the pass runs on it in place -- nothing is staged.
 static size_t epi_scratch_bytes(const gptq_layer_t* L, int M) {
+    if (is_plain_act(L->epilogue)) return 0;
     const size_t b = (size_t)M * L->N * dtype_size(L->dtype);
     return (b + 255) / 256 * 256;
 }
@@ -489,6 +491,12 @@ static int forward_impl(const gptq_layer_t* L, const void* x, void* out, int M, 
         return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", gptq_workspace_bytes_ex(L, M, tune), wv.header ? WS_HEADER_BYTES + wv.body_bytes : (size_t)0);
     // y = [gate | up] at the front of the body; the inner call gets the SAME zeroed ticket header and the body behind y (a header carved
     // out of the body would sit on whatever an earlier, larger call left there: its tickets would never reach ksplit - 1)
+    if (is_plain_act(L->epilogue)) {      // an ungated layer: y = out, the whole workspace is the inner call's, the pass runs in place
+        if (int rc = forward_routed(r, &r.plain, x, out, M, wv, stream, r.tuning(tune))) return rc;
+        hipError_t e = launch_silu_mul(out, out, M, L->N, L->dtype, L->epilogue, (hipStream_t)stream);
+        if (e != hipSuccess) return hip_fail(e, "activation pass launch");
+        return GPTQ_OK;
+    }
     if (int rc = forward_routed(r, &r.plain, x, wv.body, M, WsView{wv.header, (char*)wv.body + yb, wv.body_bytes - yb}, stream, r.tuning(tune))) return rc;
     hipError_t e = launch_silu_mul(wv.body, out, M, L->N, L->dtype, L->epilogue, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "silu_mul launch");
@@ -1631,7 +1639,9 @@ static int decode_copy_source(const gptq_layer_t* L, gptq_layer_t* S) {
     S->qconst_tiled = (const void*)(uintptr_t)16;
     S->tiled_cols = GPTQ_STRIP_COLS;
     // a plain [gate | up] layer with the fused epilogue gets a copy too (round 5: its decode kernel pairs strip s of the two halves); act-order ones do not
-    if (L->epilogue != GPTQ_EPI_NONE && (L->g_idx != nullptr || L->N % (2 * GPTQ_STRIP_COLS) != 0)) S->epilogue = -1;
+    // an ungated layer (RELU / GELU / GELU_TANH) gets whatever copy the layer without its epilogue gets: the pair form reads it where it fits, the inner call of the separate pass elsewhere
+    if (is_plain_act(L->epilogue)) S->epilogue = GPTQ_EPI_NONE;
+    if (S->epilogue != GPTQ_EPI_NONE && (L->g_idx != nullptr || L->N % (2 * GPTQ_STRIP_COLS) != 0)) S->epilogue = -1;
     if (S->epilogue == -1 || !tiled_layer_ok(*S))
         return fail(GPTQ_ERR_UNSUPPORTED, "the decode copy needs a 2-, 3-, 4- or 8-bit fp16/bf16 layer (2 bits: no fused epilogue), group_size a power-of-two multiple of 32 (16 at 8 bits) or >= K, "
                                           "and for act-order layers qweight_seq + perm (bits=%d dtype=%d group_size=%d)", L->bits, L->dtype, L->group_size);
@@ -1704,8 +1714,9 @@ int gptq_describe_plan(const gptq_layer_t* L, int M, const gptq_tuning_t* tune, 
         }
         case ROUTE_STREAM:
         case ROUTE_STREAM_SEQ:
-            snprintf(out, out_bytes, "path=gemv kernel=stream ln=%d waves=%d u=%d ksplit=%d mt=%d strips=%d pair=0 perm=%d epilogue=none", r.sp.ln, r.sp.waves,
-                     r.sp.u, r.sp.ksplit, r.sp.mt, r.sp.strips_total, r.kind == ROUTE_STREAM_SEQ ? 2 : 0);      // ("none" also in front of a separate SiLU * mul pass: the string this kernel has always had)
+            snprintf(out, out_bytes, "path=gemv kernel=stream ln=%d waves=%d u=%d ksplit=%d mt=%d strips=%d pair=0 perm=%d epilogue=%s", r.sp.ln, r.sp.waves,
+                     r.sp.u, r.sp.ksplit, r.sp.mt, r.sp.strips_total, r.kind == ROUTE_STREAM_SEQ ? 2 : 0,
+                     is_plain_act(L->epilogue) ? separate : "none");      // ("none" also in front of a separate SiLU * mul pass: the string this kernel has always had; the ungated epilogues say what runs)
             break;
         case ROUTE_GEMM: {
             const GemmPlan& g = r.gp;

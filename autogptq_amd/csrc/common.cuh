@@ -56,6 +56,14 @@ __device__ __forceinline__ float gated_act(float g, int act) {
     const float c = act == GPTQ_EPI_GELU_TANH_MUL ? 1.5957691216057308f * (g + 0.044715f * g * g * g) : g;
     return g / (1.f + __expf(-c));
 }
+// The ungated epilogues, act(y) of an [M, N] layer (gptq_epilogue_t 16 .. 18): the second question asked of L.epilogue.
+__host__ __device__ constexpr bool is_plain_act(int epilogue) { return epilogue == GPTQ_EPI_RELU || epilogue == GPTQ_EPI_GELU || epilogue == GPTQ_EPI_GELU_TANH; }
+// ... and the activation on an fp32 sum (act launch-uniform): max(s, 0), erf GELU as torch's F.gelu, tanh-GELU = gated_act's expression without the product.
+__device__ __forceinline__ float plain_act(float s, int act) {
+    if (act == GPTQ_EPI_RELU) return s < 0.f ? 0.f : s;      // (a NaN stays one, as in torch)
+    if (act == GPTQ_EPI_GELU) return 0.5f * s * (1.f + erff(s * 0.70710678118654752f));
+    return s / (1.f + __expf(-1.5957691216057308f * (s + 0.044715f * s * s * s)));
+}
 
 // ---- packed-field geometry ------------------------------------------------------------------
 // A "unit" is the smallest run of whole 32-bit words holding whole values:

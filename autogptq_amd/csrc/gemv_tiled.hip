@@ -51,8 +51,9 @@ static int tiled_kpl(int bits) { return bits == 8 ? 16 : 32; }          // k per
 static int tiled_chunk_bytes(int bits) { return bits == 3 ? 768 : (bits == 2 ? 512 : 1024); }
 static int tiled_rec_bytes(int bits) { return bits == 8 ? 64 : 48; }
 
-// A [gate | up] layer with a gated epilogue (SILU_MUL / GELU_TANH_MUL): a plain (no act-order) layer whose halves are whole strips
-static bool tiled_pair_layer(const gptq_layer_t& L) { return is_gated(L.epilogue) && L.g_idx == nullptr && L.N % (2 * GPTQ_STRIP_COLS) == 0; }
+// A [gate | up] layer with a gated epilogue (SILU_MUL / GELU_TANH_MUL): a plain (no act-order) layer whose halves are whole strips -- and an ungated layer with
+// RELU / GELU / GELU_TANH under the same conditions: the pair form streams strip s of its columns [0, N/2) and strip s + N/32 of [N/2, N) and stores both
+static bool tiled_pair_layer(const gptq_layer_t& L) { return (is_gated(L.epilogue) || is_plain_act(L.epilogue)) && L.g_idx == nullptr && L.N % (2 * GPTQ_STRIP_COLS) == 0; }
 
 bool tiled_layer_ok(const gptq_layer_t& L) {
     if (!L.qweight_tiled || !L.qconst_tiled || L.tiled_cols != GPTQ_STRIP_COLS || (L.epilogue != GPTQ_EPI_NONE && !tiled_pair_layer(L))) return false;
@@ -80,7 +81,7 @@ TiledPlan plan_tiled(const gptq_layer_t* const* Ls, int n, int M, const gptq_tun
     const gptq_layer_t& A = *Ls[0];
     if (A.bits == 2 && M > 4) return pl;                                          // 2 bits: no 5..8-row form
     int strips = 0, nsum = 0;
-    const bool pair = is_gated(A.epilogue);                                        // one [gate | up] layer: a workgroup per PAIR of strips, M <= 4, no K slices
+    const bool pair = is_gated(A.epilogue) || is_plain_act(A.epilogue);           // one [gate | up] layer (or an ungated one, both halves stored): a workgroup per PAIR of strips, M <= 4, no K slices
     if (pair && (n != 1 || M > 4)) return pl;
     for (int i = 0; i < n; ++i) {
         const gptq_layer_t& L = *Ls[i];

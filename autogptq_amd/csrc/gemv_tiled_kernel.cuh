@@ -32,7 +32,7 @@ struct PeerEpi {
 struct TiledParams {
     // ---- bytes 0 .. 127: the entry batch
     int blk_end[3];          // cumulative strip count up to and including layer i (unused entries: INT_MAX); a fourth layer is reached by the first three compares
-    int act;                 // PAIR kernels: the gptq_epilogue_t of the layer (gated_act) -- in the entry batch, in the word no kernel read (it held blk_end[3] = INT_MAX)
+    int act;                 // PAIR kernels: the gptq_epilogue_t of the layer (gated_act; is_plain_act: split mode, both halves stored) -- in the entry batch, in the word no kernel read (it held blk_end[3] = INT_MAX)
     const void* x;
     int M, K;
     int chunks, chunks_per_split, ksplit, gu_shift, groups, xstride, waves;
@@ -790,8 +790,15 @@ __global__ void __launch_bounds__(MAXW * 64, MAXW == 16 ? 4 : 2) gemv_tiled_kern
             else for (int w = 0; w < Wh; ++w) { s0 += r[w * ES]; s1 += r[(Wh + w) * ES]; }
             if (m < Mrows && n_t < NH) {
                 if (biasp != nullptr) { s0 += bv0; s1 += bv1; }
-                const float g = gated_act(s0, act);
-                outg[(size_t)m * NH + n_t] = DType<T>::from_f32(g * s1);
+                if (__builtin_expect(is_plain_act(act), 0)) {
+                    // split mode (an ungated layer, RELU / GELU / GELU_TANH): the two strips are columns n and n + N/2 of ONE [M, N] output -- the same sums,
+                    // the same bias registers, two stores with the row stride N in place of the product
+                    outg[(size_t)m * N + n_t] = DType<T>::from_f32(plain_act(s0, act));
+                    outg[(size_t)m * N + n_t + NH] = DType<T>::from_f32(plain_act(s1, act));
+                } else {
+                    const float g = gated_act(s0, act);
+                    outg[(size_t)m * NH + n_t] = DType<T>::from_f32(g * s1);
+                }
             }
         }
         TILED_STAMP(6);

@@ -374,8 +374,16 @@ __global__ void __launch_bounds__(256) permute_columns_kernel(const void* __rest
 // out[m, n] = T( silu(y[m, n]) * y[m, n + N/2] ): the unfused form of the SILU_MUL epilogue (used after the GEMM paths
 // and the GEMV kernels that have no fused epilogue); y is the [M, N] = [gate | up] result already rounded to T, which is
 // exactly what the reference computes without its fused MLP: act_fn(gate_proj(x)) * up_proj(x).
+// The ungated epilogues (RELU / GELU / GELU_TANH, is_plain_act): out[m, n] = T( plain_act(out[m, n]) ) over all M N elements, IN PLACE -- the caller passes
+// y == out, and this mode reads and writes through `out` alone.
 template <typename T>
 __device__ __forceinline__ void silu_mul_body(const T* __restrict__ y, T* __restrict__ out, int M, int N, int act) {
+    if (is_plain_act(act)) {
+        const size_t all = (size_t)M * N;
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < all; i += (size_t)gridDim.x * blockDim.x)
+            out[i] = DType<T>::from_f32(plain_act(DType<T>::to_f32(out[i]), act));
+        return;
+    }
     const int NH = N / 2;
     const size_t total = (size_t)M * NH;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -392,7 +400,7 @@ __global__ void __launch_bounds__(256) silu_mul_kernel(const void* __restrict__ 
 }
 
 hipError_t launch_silu_mul(const void* y, void* out, int M, int N, int dtype, int act, hipStream_t st) {
-    const size_t total = (size_t)M * (N / 2);
+    const size_t total = is_plain_act(act) ? (size_t)M * N : (size_t)M * (N / 2);      // elements written
     int blocks = (int)((total + 255) / 256);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(silu_mul_kernel, dim3(blocks), dim3(256), 0, st, y, out, M, N, dtype, act);

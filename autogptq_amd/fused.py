@@ -80,6 +80,74 @@ def gated_act_name(fn) -> "str | None":
     return None
 
 
+def plain_act_name(fn) -> "str | None":
+    """The ungated epilogue ('relu', 'gelu', 'gelu_tanh') that computes an activation module of the host model, or None (not served: quick GELU, ReLU^2,
+    clipped GELU, ...).  'gelu' is the erf form (transformers' GELUActivation, nn.GELU()); 'gelu_tanh' is every name gated_act_name knows for the tanh
+    approximation.  BloomGelu and FastGELUActivation write the same expression with sqrt(2/pi) cut to 0.79788456 / 0.7978845608: in fp64 they differ from
+    the epilogue's function by up to 2.6e-10 / 9.1e-13, not by rounding, so they are not mapped (tests/test_plain_act_host.py measures both)."""
+    name = type(fn).__name__
+    if name in ("ReLU", "ReLUActivation"):
+        return "relu"
+    if name == "GELUActivation" or (isinstance(fn, nn.GELU) and fn.approximate == "none"):
+        return "gelu"
+    if gated_act_name(fn) == "gelu_tanh":
+        return "gelu_tanh"
+    return None
+
+
+# class name of the host model's module -> (its first linear, the attribute that holds its activation): the ungated MLPs, act(fc1(x) + b)
+PLAIN_ACT_SITES = {
+    "OPTDecoderLayer": ("fc1", "activation_fn"),
+    "GPTNeoXMLP": ("dense_h_to_4h", "act"),
+    "FalconMLP": ("dense_h_to_4h", "act"),
+    "BloomMLP": ("dense_h_to_4h", "gelu_impl"),
+    "GPTJMLP": ("fc_in", "act"),
+    "CodeGenMLP": ("fc_in", "act"),
+    "Starcoder2MLP": ("c_fc", "act"),
+    "PhiMLP": ("fc1", "activation_fn"),
+}
+
+
+def inject_fused_act(model: nn.Module) -> int:
+    """Fuse the activation of every ungated MLP of PLAIN_ACT_SITES into its first linear: where that linear is an mi355x QuantLinear with epilogue 'none'
+    and its own g_idx and plain_act_name serves the activation, the linear gets the epilogue in place (no tensor is touched: state_dict() keys and storage
+    stay) and the activation attribute becomes nn.Identity() -- the host forward runs as it is, one launch and one [M, 4H] round trip shorter at decode
+    rows.  The original activation is kept in the module's __dict__ for remove_fused_act.  Returns the number of modules changed."""
+    n = 0
+    for mod in list(model.modules()):
+        site = PLAIN_ACT_SITES.get(type(mod).__name__)
+        if site is None or "_fused_act_undo" in mod.__dict__:
+            continue
+        lin, fn = getattr(mod, site[0], None), getattr(mod, site[1], None)
+        act = plain_act_name(fn)
+        if not isinstance(lin, QuantLinear) or act is None or lin.epilogue != "none" or lin.g_idx.numel() != lin.infeatures:
+            continue
+        _set_epilogue(lin, act)
+        object.__setattr__(mod, "_fused_act_undo", fn)
+        if isinstance(fn, nn.Module):
+            setattr(mod, site[1], nn.Identity())
+        else:                                       # a plain callable attribute
+            object.__setattr__(mod, site[1], nn.Identity())
+        n += 1
+    return n
+
+
+def remove_fused_act(model: nn.Module) -> int:
+    """Undo inject_fused_act: epilogue 'none' again, the module's own activation object back in its attribute.  Returns the number of modules restored."""
+    n = 0
+    for mod in list(model.modules()):
+        if "_fused_act_undo" not in mod.__dict__:
+            continue
+        fn = mod.__dict__.pop("_fused_act_undo")
+        lin_name, act_name = PLAIN_ACT_SITES[type(mod).__name__]
+        if act_name in mod.__dict__:
+            del mod.__dict__[act_name]
+        setattr(mod, act_name, fn)
+        _set_epilogue(getattr(mod, lin_name), "none")
+        n += 1
+    return n
+
+
 class _FusedQKVState:
     """y_q, y_k, y_v computed by ONE gptq_forward_multi call when the q_proj stand-in runs, handed to the k/v stand-ins."""
 
@@ -241,4 +309,5 @@ def remove_fused_mlp(model: nn.Module) -> int:
     return n
 
 
-__all__ = ["fuse_quant_linears", "fuse_qkv", "fuse_gate_up", "inject_fused_llama", "remove_fused_mlp", "gated_act_name", "FusedGateUpMLP"]
+__all__ = ["fuse_quant_linears", "fuse_qkv", "fuse_gate_up", "inject_fused_llama", "remove_fused_mlp", "gated_act_name", "FusedGateUpMLP",
+           "plain_act_name", "inject_fused_act", "remove_fused_act"]

@@ -104,6 +104,8 @@ def _gelu_tanh(g):
 
 GATED_ACT = {"silu_mul": torch.nn.functional.silu, "gelu_tanh_mul": _gelu_tanh}
 MLP_ACT = {"silu": "silu_mul", "gelu_tanh": "gelu_tanh_mul"}      # act name -> epilogue name
+# The ungated epilogues, act(fc1(x) + b) of OPT / GPT-NeoX / Falcon / Phi: [.., outfeatures] -- the torch function the autograd composition applies.
+PLAIN_ACT = {"relu": torch.nn.functional.relu, "gelu": torch.nn.functional.gelu, "gelu_tanh": _gelu_tanh}
 
 
 def _mlp_act(act: str):
@@ -159,7 +161,7 @@ class QuantLinear(nn.Module):
         if zero_mode not in ("auto", "wrap", "nowrap"):
             raise ValueError("zero_mode must be 'auto', 'wrap' or 'nowrap'")
         if epilogue not in _lib.EPILOGUE_ENUM:
-            raise ValueError("epilogue must be 'none', 'silu_mul' or 'gelu_tanh_mul'")
+            raise ValueError("epilogue must be 'none', 'silu_mul', 'gelu_tanh_mul', 'relu', 'gelu' or 'gelu_tanh'")
         if epilogue in GATED_ACT and outfeatures % 64 != 0:
             raise ValueError(f"epilogue='{epilogue}' needs outfeatures divisible by 64 (columns are [gate | up])")
 
@@ -173,6 +175,7 @@ class QuantLinear(nn.Module):
         self.kernel_switch_threshold = kernel_switch_threshold
         self.zero_mode = zero_mode
         # 'silu_mul' / 'gelu_tanh_mul': the layer holds [gate | up] and forward returns act(gate(x)) * up(x), [.., outfeatures // 2]
+        # 'relu' / 'gelu' / 'gelu_tanh': forward returns act(x @ W + b), [.., outfeatures] (the first linear of an ungated MLP)
         self.epilogue = epilogue
 
         G = math.ceil(infeatures / self.group_size)
@@ -496,7 +499,7 @@ class QuantLinear(nn.Module):
     def _forward_grad(self, x: torch.Tensor, tuning=None):
         """forward() when grad mode is on and x requires grad: one _GradInput node (dX = dY . W^T through gptq_grad_input; the buffers get no gradient).
         The dtype casts either side are ordinary autograd ops, so x.grad comes back in x.dtype.  A 'silu_mul' / 'gelu_tanh_mul' layer is composed from
-        differentiable pieces: its plain [gate | up] product, then act(g) * u."""
+        differentiable pieces: its plain [gate | up] product, then act(g) * u; a 'relu' / 'gelu' / 'gelu_tanh' layer from its plain product, then act(y)."""
         if self._layer is None and getattr(self, "_parts", None) is None:
             if x.device.type != "cuda":
                 raise RuntimeError("mi355x QuantLinear.forward needs a ROCm GPU tensor "
@@ -510,12 +513,14 @@ class QuantLinear(nn.Module):
             y = _GradInput.apply(xw, ((self, True),), tuning)[0]
             h = self.outfeatures // 2
             y = GATED_ACT[self.epilogue](y[..., :h]) * y[..., h:]
+        elif self.epilogue in PLAIN_ACT:
+            y = PLAIN_ACT[self.epilogue](_GradInput.apply(xw, ((self, True),), tuning)[0])
         else:
             y = _GradInput.apply(xw, ((self, False),), tuning)[0]
         return y.to(x.dtype) if x.dtype != w_dtype else y
 
     def _plain_product(self, x: torch.Tensor, tuning=None) -> torch.Tensor:
-        """x @ W + b of a 'silu_mul' / 'gelu_tanh_mul' layer BEFORE its epilogue ([.., outfeatures]): gptq_forward_ex on a copy of the layer struct with EPI_NONE."""
+        """x @ W + b of a layer with an epilogue BEFORE that epilogue ([.., outfeatures]): gptq_forward_ex on a copy of the layer struct with EPI_NONE."""
         L = getattr(self, "_layer_plain", None)
         if L is None or L[0] is not self._layer:
             c = _lib.GptqLayer()
@@ -768,6 +773,8 @@ def forward_multi(layers, x: torch.Tensor, tuning: "_lib.GptqTuning | None" = No
     # Everything that depends only on the GROUP is checked and resolved once per group (keyed by the layers' C structs) and kept in _MULTI: a decode
     # launch here takes 4.5 - 12 us, and the reference's callers are eager (generate() under inference_mode) -- per call only what depends on x remains.
     if x.requires_grad and torch.is_grad_enabled():      # one autograd node for the group (its backward sums the layers' dY . W^T)
+        if any(l.epilogue != "none" for l in layers):    # a layer with an epilogue composes its activation behind its own node: single calls
+            return [l(x, tuning) for l in layers]
         w_dtype = layers[0].scales.dtype
         xw = x.to(w_dtype) if x.dtype != w_dtype else x
         outs = _GradInput.apply(xw, tuple((l, False) for l in layers), tuning)

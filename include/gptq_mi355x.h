@@ -121,8 +121,21 @@ typedef enum gptq_zero_mode_t { GPTQ_ZERO_WRAP = 0, GPTQ_ZERO_NOWRAP = 1 } gptq_
  * GELU_TANH_MUL is the same pair layer with the gate of Gemma's GeGLU MLP: layout, shape rules, plans, workspace sizes and gptq_describe_plan strings are
  * those of SILU_MUL;  out[M, N/2] = T( gelu_tanh(y_gate) * y_up ),  gelu_tanh(g) = g / (1 + exp(-c(g))),  c(g) = 2 sqrt(2/pi) (g + 0.044715 g^3),
  * 2 sqrt(2/pi) = 1.5957691216057308 -- the tanh approximation of GELU (torch: F.gelu(approximate='tanh'), "gelu_new"), since
- * 0.5 (1 + tanh(v)) = 1 / (1 + exp(-2 v)); SiLU is the same form with c(g) = g.  Activation and product on the fp32 sums (bias included), rounded once. */
-typedef enum gptq_epilogue_t { GPTQ_EPI_NONE = 0, GPTQ_EPI_SILU_MUL = 1, GPTQ_EPI_GELU_TANH_MUL = 2 } gptq_epilogue_t;
+ * 0.5 (1 + tanh(v)) = 1 / (1 + exp(-2 v)); SiLU is the same form with c(g) = g.  Activation and product on the fp32 sums (bias included), rounded once.
+ * RELU / GELU / GELU_TANH (16 .. 18; 3 .. 15 are unassigned and refused) are the activation of an UNGATED MLP, act(fc1(x) + b) of OPT, GPT-NeoX, Falcon, BLOOM,
+ * GPT-J, Phi-1/2, StarCoder2:  out[M, N] = T( act(y) ),  y = x @ W (+ bias) -- any legal layer, no N % 64 rule, the activation on the fp32 sum, rounded once.
+ *   RELU       max(y, 0)
+ *   GELU       0.5 y (1 + erf(y / sqrt(2)))                      torch: F.gelu(y)
+ *   GELU_TANH  y / (1 + exp(-c(y))), c as above                  torch: F.gelu(y, approximate='tanh'), "gelu_new"
+ * Decode rows (M <= 4) of a plain 3- / 4- / 8-bit fp16 / bf16 layer that carries its decode copy run as ONE launch (the pair form of the decode kernel with
+ * two stores in place of the product: gptq_describe_plan says pair=1 epilogue=fused).  Every other call (M >= 5, act-order, 2-bit, fp32, no copy) runs the
+ * layer without its epilogue INTO `out` and then an elementwise pass IN PLACE on `out` (epilogue=separate): y is rounded to T once in between, nothing is
+ * staged, and gptq_workspace_bytes* of the layer equal those of the same layer with epilogue NONE.  gptq_gemv / gptq_gemm / gptq_mlp_forward_act,
+ * the grouped, tensor-parallel and MoE entry points take no such layer (gptq_forward_multi runs it as a single call). */
+typedef enum gptq_epilogue_t {
+    GPTQ_EPI_NONE = 0, GPTQ_EPI_SILU_MUL = 1, GPTQ_EPI_GELU_TANH_MUL = 2,
+    GPTQ_EPI_RELU = 16, GPTQ_EPI_GELU = 17, GPTQ_EPI_GELU_TANH = 18
+} gptq_epilogue_t;
 
 /* One quantized linear layer.  POD; the caller owns every pointer and keeps it alive. */
 typedef struct gptq_layer_t {
@@ -140,7 +153,7 @@ typedef struct gptq_layer_t {
      * position i, so group(i) = i / group_size. */
     const uint32_t *qweight_seq;  /* [K/32*bits, N] or NULL */
     const int32_t  *perm;         /* [K] or NULL */
-    int32_t epilogue;             /* gptq_epilogue_t; with SILU_MUL `out` is [M, N/2] */
+    int32_t epilogue;             /* gptq_epilogue_t; with SILU_MUL / GELU_TANH_MUL `out` is [M, N/2] */
     int32_t tiled_cols;           /* GPTQ_STRIP_COLS when the two side buffers below are given, else 0 */
     /* Optional derived (post_init) DECODE COPY of a 2-, 3-, 4- or 8-bit layer, built by gptq_prepack_decode (sizes: gptq_prepack_decode_bytes); both NULL =
      * decode streams the checkpoint layout.  With w[k][n] the layer's unpacked integers (rows taken from qweight_seq when the layer has one, else qweight;

@@ -49,6 +49,13 @@ EXPORTS = (
 )
 WS_HEADER_BYTES = 65536
 STRIP_COLS = 16          # GPTQ_STRIP_COLS: columns per strip of the decode copy (gptq_prepack_decode)
+COPY_ROWS_INT2 = 0x100   # GPTQ_COPY_ROWS_INT2: OR-ed into GptqLayer.tiled_cols -- this 2-bit layer's copy is also read at 5+ rows (opt-in; copy_cols() masks it)
+COPY_ROWS_INT2_WIDE = 0x200   # GPTQ_COPY_ROWS_INT2_WIDE: ... in the whole band of the 4-bit twin (a layer whose checkpoint rows are not resident)
+
+
+def copy_cols(tiled_cols: int) -> int:
+    """GPTQ_COPY_COLS: the strip width of a layer's decode copy (0: none) -- tiled_cols without the opt-in flag it may carry."""
+    return int(tiled_cols) & ~(COPY_ROWS_INT2 | COPY_ROWS_INT2_WIDE)
 
 
 class GptqLayer(Structure):

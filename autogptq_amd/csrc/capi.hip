@@ -58,8 +58,9 @@ int check_layer(const gptq_layer_t* L) {
     if (L->group_size <= 0) return fail(GPTQ_ERR_SHAPE, "group_size must be > 0 (resolve -1 to in_features), got %d", L->group_size);
     if ((L->qweight_seq == nullptr) != (L->perm == nullptr))
         return fail(GPTQ_ERR_NULL, "qweight_seq and perm must be given together");
-    if ((L->qweight_tiled != nullptr) != (L->tiled_cols != 0) || (L->qweight_tiled != nullptr) != (L->qconst_tiled != nullptr) ||
-        (L->tiled_cols != 0 && L->tiled_cols != GPTQ_STRIP_COLS))
+    // (tiled_cols may carry GPTQ_COPY_ROWS_INT2: copy_cols masks it; the flag on a layer without a copy, or of another width, means nothing)
+    if ((L->qweight_tiled != nullptr) != (copy_cols(*L) != 0) || (L->qweight_tiled != nullptr) != (L->qconst_tiled != nullptr) ||
+        (copy_cols(*L) != 0 && copy_cols(*L) != GPTQ_STRIP_COLS))
         return fail(GPTQ_ERR_UNSUPPORTED, "qweight_tiled, qconst_tiled and tiled_cols (%d) must be given together, tiled_cols = %d", L->tiled_cols, GPTQ_STRIP_COLS);
     if (L->epilogue != GPTQ_EPI_NONE && !is_gated(L->epilogue) && !is_plain_act(L->epilogue))
         return fail(GPTQ_ERR_UNSUPPORTED, "unknown epilogue %d", L->epilogue);
@@ -98,6 +99,7 @@ bool gemm_rule(const gptq_layer_t* L, int M, const gptq_tuning_t* t, Plan&& plan
         return gf.supported && (long)gf.nbm * gf.nbn >= 64;      // fewer tiles than a quarter of the chip: the GEMV still wins (4096x4096 M = 128: ~170 us against 455)
     }
     if (!t && L->epilogue == GPTQ_EPI_NONE && rows_pays(*L, M)) return true;      // 5 .. 128 rows from the decode copy (gemm_rows.hip; plan_gemm picks it)
+    if (!t && L->epilogue == GPTQ_EPI_NONE && dense_int2_choice(*L, M)) return true;      // a flagged 2-bit layer where its 4-bit twin has the rows / panel kernel (plan_gemm picks the low-bit form)
     if (L->bits != 4) {
         // 2/3/8-bit: the matrix-core GEMV handles 4 rows of x per pass over the weights and the generic (act-order) kernel fewer, so the
         // weight-streaming GEMMs take over early (tools/cliff_scan.py --slice C, 4096x11008, us: int8 M = 8: 47.6 GEMV, 25.6 tiled at
@@ -580,7 +582,10 @@ static MultiRoute route_forward_multi(const gptq_layer_t* const* layers, int n_l
     // 5 .. 128 rows on layers that carry the decode copy: the exchange-free kernel over the strip groups of all layers (gemm_rows.hip); act-order layers of
     // ONE order (the same perm pointer: QuantLinear.share_act_order) read one permuted x -- and nothing else is staged
     const bool rows_forced = tune && tune->path == 3 && tune->reserved[3] == GPTQ_LAB_VARIANT_ROWS_ON && rows_multi_ok(layers, n_layers, M);      // lab knob 50
-    const bool separate = !tune && separate_panels_pay(layers, n_layers, M);
+    // (a group with a flagged 2-bit layer in the band where that layer runs on its copy: layer by layer too -- the low-bit forms have no group launch)
+    bool lowbit_single = false;
+    for (int i = 0; !tune && i < n_layers; ++i) lowbit_single = lowbit_single || (layers[i]->epilogue == GPTQ_EPI_NONE && dense_int2_choice(*layers[i], M) != 0);
+    const bool separate = !tune && (lowbit_single || separate_panels_pay(layers, n_layers, M));
     if (n_layers >= 2 && (rows_forced || (!tune && !separate && rows_multi_pays(layers, n_layers, M))) && (r.rp = plan_rows_multi(layers, n_layers, M, nullptr)).ok &&
         r.hit(MULTI_ROWS, layers[0]->g_idx ? xperm16_bytes(layers[0], M) : 0))
         return r;
@@ -1721,9 +1726,10 @@ int gptq_describe_plan(const gptq_layer_t* L, int M, const gptq_tuning_t* tune, 
         case ROUTE_GEMM: {
             const GemmPlan& g = r.gp;
             const char* kern = (g.kernel == GEMM_WIDE && g.wide_tiled) ? "wide_copy" : gemm_kernel_names[g.kernel];
-            snprintf(out, out_bytes, "path=gemm kernel=%s mt=%d bk=%d kg=%d ksplit=%d tiles=%dx%d tail=%d tail_slices=%d perm=%d dma=%d waves=%d u=%d epilogue=%s", kern, g.mt, g.bk,
+            snprintf(out, out_bytes, "path=gemm kernel=%s mt=%d bk=%d kg=%d ksplit=%d tiles=%dx%d tail=%d tail_slices=%d perm=%d dma=%d waves=%d u=%d epilogue=%s%s", kern, g.mt, g.bk,
                      g.kg == 2 ? 2 : 1, g.ksplit, g.nbm, g.nbn, g.tail, g.tail ? (1 << g.tail_lg) : 1, g.use_seq ? 1 : 0,
-                     (g.glds || g.kernel == GEMM_STREAM64 || g.kernel == GEMM_MID) ? 1 : 0, g.waves, g.u, separate);
+                     (g.glds || g.kernel == GEMM_STREAM64 || g.kernel == GEMM_MID) ? 1 : 0, g.waves, g.u, separate,
+                     g.lowbit ? " body=lowbit" : "");      // (a flagged 2-bit layer on the dense form of the low-bit routed-expert kernels; every other line is what it was)
             break;
         }
         case ROUTE_GEMV: {

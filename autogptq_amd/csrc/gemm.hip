@@ -1850,6 +1850,32 @@ hipError_t launch_stream64(const gptq_layer_t* const* Ls, const Stream64Plan& pl
     return (Ls[0]->dtype == GPTQ_F16) ? launch_stream64_t<f16>(pl, p, st) : launch_stream64_t<bf16>(pl, p, st);
 }
 
+// A flagged 2-bit layer, no tuning.  The BAND is borrowed from the 4-bit kernels: 5 .. 64 rows -> the rows form where rows_pays takes the 4-bit layer of the same K,
+// N, group size, dtype and act-order; 65 rows and more -> the panel form where panel_pays does.  Measured at 2 bits (tools/dense_int2_ab.py, plain layers, fp16 / bf16,
+// g128 / g64, rotating HBM-cold layers in a hipGraph; unflagged plan -> these forms, us per layer call):
+//   checkpoint rows NOT resident (released layers: the unflagged plan pays gptq_unprepack_decode per call): the whole band wins, 1.96 - 8.7x
+//     (profiles/dense_int2_ab.log: 4096^2 at 16 rows 41.8 -> 9.8, 4096x11008 at 128 rows ... no cell loses) -- GPTQ_COPY_ROWS_INT2_WIDE takes all of it.
+//   both layouts resident: the 2-bit forms of gemm_mid_kernel are hard to beat below 128 rows (a 2-bit layer is half the bytes of its 4-bit twin, and the rows form's fixed
+//     4-strip groups leave CUs idle on 4096-wide layers: 11008x4096 at 5 .. 32 rows 13.3 - 15.1 -> 19.9 - 20.1 us, 0.57 - 0.77x; 4096^2 bf16 0.85x; 8192^2 0.83 - 0.97x;
+//     4096^2 / 8192^2 at 65 rows on the panel form 0.65 - 0.84x).  What won by more than the repeat spread of the log (6.4 %) in both dtypes and group sizes, and is kept:
+//       rows form   5 .. 16 rows where N >= 8192 and K <= 4096           (4096x11008: 12.1 - 14.9 -> 10.1 - 12.4 us, 1.15 - 1.25x)
+//       panel form  256 rows and more                                     (4096^2 256 / 512 rows 1.22 - 1.56x, 8192^2 1.31 - 1.44x; 11008x4096 at 256 rows 0.95 - 1.04x: inside the spread)
+//                   128 rows and more where N >= 8192                     (4096x11008 1.32 - 1.52x, 5120x13824 1.31 - 1.51x, 8192^2 1.00 - 1.23x; 4096^2 at 128 rows 0.66 - 0.71x: excluded)
+//     65 .. 127 rows were measured at 65 only (0.65 - 1.08x) and stay with the unflagged plan.  Act-order layers: not measured, the same rule.
+int dense_int2_choice(const gptq_layer_t& L, int M) {
+    if (!copy_rows_int2(L) || M < 5) return 0;
+    const bool wide = copy_rows_int2_wide(L);
+    gptq_layer_t T4 = L;
+    T4.bits = 4;
+    T4.tiled_cols = GPTQ_STRIP_COLS;
+    if (M <= 64) {
+        if (!wide && !(L.N >= 8192 && L.K <= 4096 && M <= 16)) return 0;
+        return dense_rows_int2_ok(L, M) && rows_pays(T4, M) ? (int)GEMM_ROWS : 0;
+    }
+    if (!wide && !(M >= 256 || (M >= 128 && L.N >= 8192))) return 0;
+    return dense_panel_int2_ok(L, M) && panel_pays(T4, M) ? (int)GEMM_PANEL : 0;
+}
+
 GemmPlan plan_gemm(const gptq_layer_t& L, int M, const gptq_tuning_t* tune) {
     GemmPlan pl{};
     const int kpu = unit_vals(L.bits);
@@ -1874,6 +1900,42 @@ GemmPlan plan_gemm(const gptq_layer_t& L, int M, const gptq_tuning_t* tune) {
     pl.use_seq = (L.g_idx != nullptr);
     pl.xperm_bytes = pl.use_seq ? align_up((size_t)M * L.K * 2, 256) : 0;
     const int force_skinny = tune ? tune->reserved[2] : 0;      // experiment knob: 1 = skinny, 2 = tiled
+    // OPT-IN (GPTQ_COPY_ROWS_INT2 in tiled_cols): a 2-bit layer on its decode copy from 5 rows up -- the dense forms of the low-bit routed-expert kernels
+    // (moe_rows.hip / moe_panel.hip), where the rules below would give the 4-bit layer of the same shape the rows / panel kernel (dense_int2_choice); lab knobs
+    // 50 / 52 force either form at any shape it takes, 51 / 53 keep it off.  Everything else about a flagged layer is the unflagged plan.
+    if (copy_rows_int2(L)) {
+        const int knob = tune ? tune->reserved[3] : 0;
+        const bool own = (!tune || tune->path != 3 || knob == 0) && force_skinny == 0;
+        const int choice = own ? dense_int2_choice(L, M) : 0;
+        if (knob == GPTQ_LAB_VARIANT_PANEL_ON || (knob != GPTQ_LAB_VARIANT_PANEL_OFF && choice == GEMM_PANEL)) {
+            const PanelPlan pp = plan_dense_panel_int2(L, M);
+            if (pp.ok) {
+                pl.kernel = GEMM_PANEL;
+                pl.lowbit = true;
+                pl.panelp = pp;
+                pl.xnat = pl.use_seq;
+                pl.mt = pp.mt; pl.bk = 64; pl.bm = 32 * pp.mt; pl.bn = 32 * pp.nt; pl.nbm = pp.nbm; pl.nbn = pp.nbn;
+                pl.waves = pp.kp; pl.u = 2; pl.kg = pp.kp;
+                pl.ksplit = 1; pl.ksteps_total = pl.ksteps_per_split = L.K / 64;
+                pl.workspace_bytes = pl.xperm_bytes;
+                return pl;
+            }
+        }
+        if (knob == GPTQ_LAB_VARIANT_ROWS_ON || (knob != GPTQ_LAB_VARIANT_ROWS_OFF && choice == GEMM_ROWS)) {
+            const RowsPlan rp = plan_dense_rows_int2(L, M);
+            if (rp.ok) {
+                pl.kernel = GEMM_ROWS;
+                pl.lowbit = true;
+                pl.rowsp = rp;
+                pl.xnat = pl.use_seq;
+                pl.mt = rp.rb; pl.bk = 128; pl.bm = 16 * rp.rb; pl.bn = 16 * rp.s; pl.nbm = rp.npm; pl.nbn = rp.nsg;
+                pl.waves = rp.waves; pl.u = 2; pl.kg = 1;
+                pl.ksplit = 1; pl.ksteps_total = pl.ksteps_per_split = L.K / 128;
+                pl.workspace_bytes = pl.xperm_bytes;
+                return pl;
+            }
+        }
+    }
     // 64 .. ~1024 rows of a layer that carries its decode copy where its tiles fill the chip (panel_pays): whole-K panels of 64 x 32 nt tiles, no exchange
     // (gemm_panel.hip); lab knobs 52 / 53 force it on / off.  Asked before the rows kernel: from ~96 rows it is the faster of the two (profiles/r06_panel_sweep.log)
     {
@@ -2072,7 +2134,7 @@ GemmPlan plan_gemm(const gptq_layer_t& L, int M, const gptq_tuning_t* tune) {
         // layers that carry their decode copy: weights from it, raw x by LDS DMA (gemm_wide_kernel<T, true, true>); knob 46 / 47 keep the checkpoint rows (A/B).
         // Act-order layers: the copy is made of the re-sequenced rows, so x is permuted in NATURAL order (xnat) instead of the row form's slot order -- and
         // bf16 act-order layers, which have no slot-ordered permute, get the wide tiles this way.
-        const bool copy_ok = L.qweight_tiled != nullptr && L.tiled_cols == GPTQ_STRIP_COLS && L.N % GPTQ_STRIP_COLS == 0 && wide_knob != GPTQ_LAB_VARIANT_WIDE_ROWS && wide_knob != GPTQ_LAB_VARIANT_WIDE_ROWS_ON;
+        const bool copy_ok = L.qweight_tiled != nullptr && copy_cols(L) == GPTQ_STRIP_COLS && L.N % GPTQ_STRIP_COLS == 0 && wide_knob != GPTQ_LAB_VARIANT_WIDE_ROWS && wide_knob != GPTQ_LAB_VARIANT_WIDE_ROWS_ON;
         const bool wide = wide_knob != GPTQ_LAB_VARIANT_WIDE_OFF && (fills || wide_knob == GPTQ_LAB_VARIANT_WIDE_ON || wide_knob == GPTQ_LAB_VARIANT_WIDE_ROWS_ON) && pl.mt == 4 && pl.bk == 64 && pl.ksplit == 1 && pl.variant == 0 && tail_knob == 0 &&
                   (wide_gemm_ok(L, M, pl.use_seq, pl.xslot && pl.glds) || (copy_ok && wide_gemm_ok(L, M, false, false)));
         // The same wave tile as a stream-K partition of 128 x 256 tiles (gemm_wide_sk.hip) everywhere else from ~768 rows: every CU runs the same number of
@@ -2276,8 +2338,8 @@ hipError_t launch_gemm(const gptq_layer_t& L, const GemmPlan& pl, const void* x,
     switch (pl.kernel) {
         case GEMM_MID: return launch_mid(one, pl.midp, p.x, outs, M, ws_header, p.partial, pl.use_seq ? L.qweight_seq : nullptr, st);
         case GEMM_STREAM64: return launch_stream64(one, pl.s64p, p.x, outs, M, ws_header, p.partial, pl.use_seq ? L.qweight_seq : nullptr, st);
-        case GEMM_ROWS: return launch_gemm_rows(L, pl.rowsp, p.x, out, M, st);
-        case GEMM_PANEL: return launch_gemm_panel(L, pl.panelp, p.x, out, M, st);
+        case GEMM_ROWS: return pl.lowbit ? launch_dense_rows_int2(L, p.x, out, M, pl.rowsp, st) : launch_gemm_rows(L, pl.rowsp, p.x, out, M, st);
+        case GEMM_PANEL: return pl.lowbit ? launch_dense_panel_int2(L, p.x, out, M, pl.panelp, st) : launch_gemm_panel(L, pl.panelp, p.x, out, M, st);
         case GEMM_WIDE_SK: return launch_gemm_wide_sk(L, p.x, out, M, ws_header, (char*)workspace + pl.xperm_bytes, st);
         case GEMM_WIDE: return launch_gemm_wide(L, p.qweight, p.x, out, M, pl.use_seq, st, pl.wide_tiled);
         default: break;                                   // GEMM_TILED / GEMM_STRIP16 / GEMM_SKINNY: by packing and dtype (launch_bits)

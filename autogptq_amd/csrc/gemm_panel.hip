@@ -31,7 +31,7 @@ static int panel_gsh(const gptq_layer_t& L) {                 // group of the 64
 
 bool panel_ok(const gptq_layer_t& L, int M) {
     if ((L.bits != 4 && L.bits != 3 && L.bits != 8) || (L.dtype != GPTQ_F16 && L.dtype != GPTQ_BF16)) return false;
-    if (L.qweight_tiled == nullptr || L.qconst_tiled == nullptr || L.tiled_cols != GPTQ_STRIP_COLS) return false;
+    if (L.qweight_tiled == nullptr || L.qconst_tiled == nullptr || copy_cols(L) != GPTQ_STRIP_COLS) return false;
     if (L.g_idx != nullptr && !(L.perm && L.qweight_seq)) return false;
     if (L.K % 128 || L.N % 32 || L.epilogue != GPTQ_EPI_NONE) return false;
     const int gsh = panel_gsh(L);

@@ -36,7 +36,7 @@ static int rows_group_mode(const gptq_layer_t& L) {
 
 bool rows_ok(const gptq_layer_t& L, int M) {
     if ((L.bits != 4 && L.bits != 3 && L.bits != 8) || (L.dtype != GPTQ_F16 && L.dtype != GPTQ_BF16)) return false;
-    if (L.qweight_tiled == nullptr || L.qconst_tiled == nullptr || L.tiled_cols != GPTQ_STRIP_COLS) return false;
+    if (L.qweight_tiled == nullptr || L.qconst_tiled == nullptr || copy_cols(L) != GPTQ_STRIP_COLS) return false;
     if (L.K % 128 || L.N % 16 || L.epilogue != GPTQ_EPI_NONE || rows_group_mode(L) < 0) return false;
     if ((size_t)M * L.K * 2 >= ((size_t)1 << 32)) return false;            // 32-bit x offsets per lane
     return M >= 1 && M <= 1024;

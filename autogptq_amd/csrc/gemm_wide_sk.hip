@@ -40,7 +40,7 @@ int wide_sk_group_mode(int group_size) { return group_size % 128 == 0 ? 0 : (gro
 
 bool wide_sk_ok(const gptq_layer_t& L, int M) {
     if ((L.bits != 4 && L.bits != 3 && L.bits != 8) || (L.dtype != GPTQ_F16 && L.dtype != GPTQ_BF16)) return false;
-    if (L.qweight_tiled == nullptr || L.tiled_cols != GPTQ_STRIP_COLS) return false;
+    if (L.qweight_tiled == nullptr || copy_cols(L) != GPTQ_STRIP_COLS) return false;
     if (L.bits != 4 && L.qconst_tiled == nullptr) return false;                                      // 3 / 8 bits read the copy's constant records
     if (L.K % 256 || wide_sk_group_mode(L.group_size) < 0 || L.N % 32 || L.epilogue != GPTQ_EPI_NONE) return false;      // two K parts of whole 128-deep chunks
     return M >= 128;

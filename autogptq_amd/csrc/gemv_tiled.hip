@@ -56,7 +56,7 @@ static int tiled_rec_bytes(int bits) { return bits == 8 ? 64 : 48; }
 static bool tiled_pair_layer(const gptq_layer_t& L) { return (is_gated(L.epilogue) || is_plain_act(L.epilogue)) && L.g_idx == nullptr && L.N % (2 * GPTQ_STRIP_COLS) == 0; }
 
 bool tiled_layer_ok(const gptq_layer_t& L) {
-    if (!L.qweight_tiled || !L.qconst_tiled || L.tiled_cols != GPTQ_STRIP_COLS || (L.epilogue != GPTQ_EPI_NONE && !tiled_pair_layer(L))) return false;
+    if (!L.qweight_tiled || !L.qconst_tiled || copy_cols(L) != GPTQ_STRIP_COLS || (L.epilogue != GPTQ_EPI_NONE && !tiled_pair_layer(L))) return false;
     if (L.bits != 4 && L.bits != 8 && L.bits != 3 && L.bits != 2) return false;
     if (L.bits == 2 && L.epilogue != GPTQ_EPI_NONE) return false;                 // 2 bits (round 6): the plain and the act-order decode forms, up to 4 rows
     if (L.g_idx != nullptr && !(L.perm && L.qweight_seq)) return false;           // act-order: only with the re-sequenced rows (the copy is made of them) and perm

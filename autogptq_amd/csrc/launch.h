@@ -6,6 +6,15 @@
 
 namespace gptq {
 
+// The strip width of the layer's decode copy (0: none) -- tiled_cols without the opt-in flag it may carry; every comparison with GPTQ_STRIP_COLS goes through here.
+inline int copy_cols(const gptq_layer_t& L) { return GPTQ_COPY_COLS(L.tiled_cols); }
+// ... and the opt-in itself: a 2-bit layer that carries its copy and GPTQ_COPY_ROWS_INT2 (on any other layer the flag means nothing)
+inline bool copy_rows_int2(const gptq_layer_t& L) {
+    return L.bits == 2 && (L.tiled_cols & GPTQ_COPY_ROWS_INT2) != 0 && copy_cols(L) == GPTQ_STRIP_COLS && L.qweight_tiled != nullptr && L.qconst_tiled != nullptr;
+}
+// ... with GPTQ_COPY_ROWS_INT2_WIDE: the whole band of the 4-bit twin (a layer whose checkpoint rows are not resident)
+inline bool copy_rows_int2_wide(const gptq_layer_t& L) { return copy_rows_int2(L) && (L.tiled_cols & GPTQ_COPY_ROWS_INT2_WIDE) != 0; }
+
 struct GemvPlan {
     int ln, waves, ksplit, strips, mt, mtiles;
     int units_total, units_per_split, chunk_units;
@@ -104,6 +113,7 @@ struct GemmPlan {
     bool supported, use_seq;
     GemmKernel kernel;
     PanelPlan panelp; RowsPlan rowsp; WideSkGeom wskg; MidPlan midp; Stream64Plan s64p;      // the geometry of `kernel`, where it has a plan of its own
+    bool lowbit;              // GEMM_ROWS / GEMM_PANEL on a flagged 2-bit layer: the dense form of moe_rows_lowbit_kernel / moe_panel_lowbit_kernel (rowsp / panelp: its geometry)
     bool wide_tiled;          // GEMM_WIDE / GEMM_WIDE_SK reading the layer's decode copy, raw x staged by LDS DMA
     bool xnat;                // act-order + wide_tiled: x permuted in natural order (the copy is of the re-sequenced rows)
     bool glds;                // ... and stages it with global_load_lds (DMA) into swizzled, unpadded LDS rows
@@ -267,6 +277,13 @@ MoeBatchPlan plan_moe_batch(const gptq_moe_t& m, int T, int topk);
 hipError_t launch_moe_batch(const gptq_moe_t& m, const void* table, const MoeBatchPlan& pl, const void* x, const int64_t* idx, const float* w, int T, int topk,
                             void* out, char* ws, hipStream_t st);
 hipError_t init_moe_batch_device();
+// ... and the DENSE form of moe_rows_lowbit_kernel<T, 2> (opt-in: copy_rows_int2): one 2-bit QuantLinear layer on its decode copy, out = T(x W + bias), a workgroup
+// = 16 rows x 4 strips x the whole K.  x: the rows as the copy wants them (act-order layers: permuted in natural order by the caller).  RowsPlan: rb = 1, s = 4.
+bool dense_rows_int2_ok(const gptq_layer_t& L, int M);
+RowsPlan plan_dense_rows_int2(const gptq_layer_t& L, int M);
+hipError_t launch_dense_rows_int2(const gptq_layer_t& L, const void* x, void* out, int M, const RowsPlan& pl, hipStream_t st);
+// 0: the unflagged plan; GEMM_ROWS / GEMM_PANEL: what the planner, left to itself, gives a flagged 2-bit layer at M rows (gemm.hip; the rule of the 4-bit twin)
+int dense_int2_choice(const gptq_layer_t& L, int M);
 // ... and its row gather (moe_gather_rows_kernel) for the prefill path: out[plane][r] = in[src(r)] through the perm of expert e(r)'s entry of projection
 // `plane` of `table` (entries without a perm: a copy); src(r) = row_assign[r] / topk (topk > 0) or r (topk = 0).  R <= 65535 (a grid dimension).
 hipError_t launch_moe_gather_rows(const void* table, int planes, int topk, const int64_t* idx, const int* row_assign, const int* offsets, const void* in,
@@ -287,6 +304,10 @@ MoePrefillPlan plan_moe_prefill(const gptq_moe_t& m, int T, int topk);
 hipError_t launch_moe_prefill(const gptq_moe_t& m, const void* table, const MoePrefillPlan& pl, const void* x, const int64_t* idx, const float* w, int T, int topk,
                               void* out, char* ws, hipStream_t st);
 hipError_t init_moe_prefill_device();
+// ... and the DENSE form of moe_panel_lowbit_kernel<T, 2> (opt-in: copy_rows_int2): a workgroup = 64 rows x 128 columns x the whole K.  PanelPlan: mt = 2, nt = 4, kp = 8.
+bool dense_panel_int2_ok(const gptq_layer_t& L, int M);
+PanelPlan plan_dense_panel_int2(const gptq_layer_t& L, int M);
+hipError_t launch_dense_panel_int2(const gptq_layer_t& L, const void* x, void* out, int M, const PanelPlan& pl, hipStream_t st);
 // lora.hip: the adapter branch out += scale * (x . A^T) . B^T for up to GPTQ_LORA_MAX adapters that share x: one down launch, one up launch
 constexpr int GPTQ_LORA_GEMV_ROWS = 8;              // up to here the VALU forms, above the matrix-core forms
 struct LoraPlan {

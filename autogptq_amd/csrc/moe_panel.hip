@@ -52,16 +52,20 @@ constexpr int LDS_BYTES = 128 * 1024;           // 8 waves x 2 buffers x 1 plane
 constexpr int UB = 16;                          // accumulator units (float4 per lane) per batch of the cross-wave sum: 16 x 8 waves x 1 KiB
 constexpr int nt_of(int bits) { return bits == 8 ? 2 : 4; }
 
+// The dense form (pair == 2, 2 bits only) reads no table: the four fields that describe the tables carry the layer instead (the second name of each union; the
+// layout, and with it the 3- / 4- / 8-bit kernels' argument block, is what it was)
 struct Args {
-    const moerows::Entry* table;                // entries of the first projection (pair: W1; W3 is table + E)
-    int E, pair;
+    union { const moerows::Entry* table;        // entries of the first projection (pair: W1; W3 is table + E)
+            const unsigned* dense_tq; };        // dense: the layer's qweight_tiled
+    union { int E; int dense_M; };              // dense: rows of x / out
+    int pair;                                   // 0: down, 1: pair, 2: dense (moe_panel_lowbit_kernel<T, 2> only)
     const void* a;                              // sorted rows of the A operand [planes][R][K]; plane q at a + q * plane_bytes
     size_t plane_bytes;
     int planes;
-    const int* tile_count;
-    const int4* tiles;
+    union { const int* tile_count; const void* dense_bias; };      // dense: bias [N] (T) or NULL
+    union { const int4* tiles; const void* dense_cst; };           // dense: the layer's qconst_tiled
     int K, N, chunks, groups, gsh, steps, spw, nct;
-    void* out;                                  // pair: H_sorted [R][N] (T); down: Y [R][N] fp32
+    void* out;                                  // pair: H_sorted [R][N] (T); down: Y [R][N] fp32; dense: out [M][N] (T)
 };
 
 // 2 bits: the two-word lanes of the copy (DeqSel has the 3-, 4- and 8-bit forms) -- moerows::DeqOf of moe_rows.hip, restated for this file
@@ -188,6 +192,43 @@ hipError_t launch_moe_prefill(const gptq_moe_t& m, const void* table, const MoeP
     if ((e = launch_any(D.dtype, D.bits, d, (long)pl.tiles * d.nct, pl.waves_down, st)) != hipSuccess) return e;
 
     return launch_moe_combine(pos, w, (const float*)(ws + pl.off_y), out, T, topk, H, 1, R, G.dtype, st);
+}
+
+// ---- the dense form (one flagged 2-bit QuantLinear layer; moe_panel_body.inc) --------------------------------------------------------------------
+// What the down form takes: fp16 / bf16, K a whole number of 128-deep chunks of the copy, N a whole number of 32 NT-column tiles, a group size of 64 2^n or one
+// group; act-order layers with their re-sequenced rows (the copy is made of them; the caller permutes x).  The lane offsets are 32-bit: one strip's bytes.
+bool dense_panel_int2_ok(const gptq_layer_t& L, int M) {
+    if (!copy_rows_int2(L) || (L.dtype != GPTQ_F16 && L.dtype != GPTQ_BF16) || L.epilogue != GPTQ_EPI_NONE) return false;
+    if (L.g_idx != nullptr && !(L.perm && L.qweight_seq)) return false;
+    if (L.K % 128 || L.N % (32 * moepanel::nt_of(2)) || moepanel::group_shift(L) < 0) return false;
+    return M >= 1 && M <= GPTQ_MOE_PREFILL_MAX_ROWS;
+}
+
+PanelPlan plan_dense_panel_int2(const gptq_layer_t& L, int M) {
+    PanelPlan pl{};
+    if (!dense_panel_int2_ok(L, M)) return pl;
+    pl.mt = 2; pl.nt = moepanel::nt_of(2); pl.kp = 8;            // the K split is a function of the layer alone (ROW INDEPENDENCE above)
+    pl.nbm = (M + moepanel::BM - 1) / moepanel::BM;
+    pl.nbn = L.N / (32 * pl.nt);
+    pl.spw = (L.K / 64 + pl.kp - 1) / pl.kp;                     // (fewer steps than waves: the last waves run empty)
+    pl.lds_bytes = moepanel::LDS_BYTES;
+    pl.ok = true;
+    return pl;
+}
+
+hipError_t launch_dense_panel_int2(const gptq_layer_t& L, const void* x, void* out, int M, const PanelPlan& pl, hipStream_t st) {
+    if (!pl.ok || !dense_panel_int2_ok(L, M)) return hipErrorInvalidValue;
+    moepanel::Args a{};
+    a.dense_tq = L.qweight_tiled; a.dense_cst = L.qconst_tiled; a.dense_bias = L.bias; a.dense_M = M;
+    a.pair = 2;
+    a.a = x; a.plane_bytes = 0; a.planes = 1;
+    a.K = L.K; a.N = L.N;
+    a.chunks = L.K / 128;
+    a.groups = (L.K + L.group_size - 1) / L.group_size;
+    a.gsh = moepanel::group_shift(L);
+    a.steps = L.K / 64; a.spw = pl.spw; a.nct = pl.nbn;
+    a.out = out;
+    return moepanel::launch_any(L.dtype, 2, a, (long)pl.nbm * pl.nbn, pl.kp, st);
 }
 
 // grants the 128 KiB of dynamic LDS the kernel runs in

@@ -2,6 +2,10 @@
 // (moe_panel.hip: the design, the names it uses).  In scope: T, BITS, Args p.  Text inclusion rather than a shared __device__ function: the 4- and 8-bit
 // kernels keep their code objects instruction for instruction (moe_rows_body.inc: an inlined function body changed the scalar prologue and the registers).
 //
+// DENSE form (2 bits only, p.pair == 2, launch-uniform: launch_dense_panel_int2): one QuantLinear layer on its decode copy.  No tables: tile t is rows
+// [64 t, min(64 t + 64, M)) of x [M][K], the copy / constants / bias / M are launch arguments (Args: dense_tq, dense_cst, dense_bias, dense_M), the K loop is
+// the down form's (NT column blocks, one plane) and the store is out[m][n] = T(sum + bias[n]) into out [M][N].
+//
 // What the width changes (utils.hip prepack_decode_weights_kernel: a chunk of the copy = [4 k-slots][16 columns][WPL words], 128 k deep; 8 bits: 64 k):
 //                 8 bits   4 bits   3 bits   2 bits
 //   STRIP_CH       1024     1024      768      512     bytes of one chunk of one 16-column strip
@@ -24,15 +28,22 @@
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = blockDim.x >> 6;
     const int l31 = lane & 31, half = lane >> 5;
     const int ct = blockIdx.x % p.nct, tile = blockIdx.x / p.nct;
-    if (tile >= *p.tile_count) return;
-    const int4 tl = p.tiles[tile];
+    bool dense = false;                                        // (a constant everywhere but at 2 bits)
+    if constexpr (BITS == 2) dense = p.pair == 2;
+    int4 tl;
+    if (dense) {
+        tl = int4{0, tile * BM, min(BM, p.dense_M - tile * BM), 0};      // the grid is exactly the tiles: none is empty
+    } else {
+        if (tile >= *p.tile_count) return;
+        tl = p.tiles[tile];
+    }
     const int e = __builtin_amdgcn_readfirstlane(tl.x), row0 = __builtin_amdgcn_readfirstlane(tl.y), rows = __builtin_amdgcn_readfirstlane(tl.z);
-    const int pair = p.pair, planes = p.planes;
+    const int pair = dense ? 0 : p.pair, planes = p.planes;
     const int n0 = ct * 32 * (pair ? HB : NT);
     // rows past the tile's count re-read its last row: DMA i fetches rows 8 min(i, imax) + min(r8, rlast) (the panel body's PART form)
     const int imax = (rows - 1) >> 3, rlast = (rows - 1) & 7;
 
-    const moerows::Entry e0 = moerows::load_entry(p.table + e);
+    const moerows::Entry e0 = dense ? moerows::Entry{p.dense_tq, p.dense_cst, nullptr, nullptr} : moerows::load_entry(p.table + e);
     const moerows::Entry e1 = pair ? moerows::load_entry(p.table + p.E + e) : e0;
     const char* wbase[NT];
     const char* cbase[NT];
@@ -247,6 +258,19 @@
                     const int row = 32 * mt + 8 * rq + 4 * half + i;
                     const float gv = sg[i];
                     if (row < rows) ((T*)p.out)[(size_t)(row0 + row) * N + n] = DType<T>::from_f32(gv / (1.f + __expf(-gv)) * su[i]);
+                }
+            }
+        } else if (dense) {
+            for (int lu = wave; lu < UBC; lu += nw) {
+                const int u = b0 + lu;
+                const int mt = u / (4 * NT), rq = (u / NT) % 4, nt = u % NT;
+                const f32x4 s = wsum(lu);
+                const int n = n0 + 32 * nt + l31;
+                const float b = p.dense_bias ? DType<T>::to_f32(((const T*)p.dense_bias)[n]) : 0.f;      // (a 2-byte load: no dwordx4 in this kernel but the x DMAs)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int row = 32 * mt + 8 * rq + 4 * half + i;
+                    if (row < rows) ((T*)p.out)[(size_t)(row0 + row) * N + n] = DType<T>::from_f32(s[i] + b);
                 }
             }
         } else {

@@ -67,17 +67,21 @@ constexpr int BM = 16;
 constexpr int XB = 4096;                        // 16 rows x 128 k x 2 bytes
 constexpr int MAX_LDS = 160 * 1024;
 
+// The dense form (pair == 2, 2 bits only) reads no table: the four fields that describe the tables carry the layer instead (the second name of each union; the
+// layout, and with it the 3- / 4- / 8-bit kernels' argument block, is what it was)
 struct Args {
-    const Entry* table;                         // entries of the first projection (pair: W1; W3 is table + E)
-    int E, pair;
+    union { const Entry* table;                 // entries of the first projection (pair: W1; W3 is table + E)
+            const unsigned* dense_tq; };        // dense: the layer's qweight_tiled
+    union { int E; int dense_M; };              // dense: rows of x / out
+    int pair;                                   // 0: down, 1: pair, 2: dense (moe_rows_lowbit_kernel<T, 2> only)
     const void* a;                              // rows of the A operand [.][K]; planes > 1: plane q at a + q * plane_bytes
     size_t plane_bytes;
     const int* row_assign;                      // non-NULL: row r of the tile is a[row_assign[first + r] / topk]; NULL: a[first + r]
     int topk, planes;
-    const int* tile_count;
-    const int4* tiles;
+    union { const int* tile_count; const void* dense_bias; };      // dense: bias [N] (T) or NULL
+    union { const int4* tiles; const void* dense_cst; };           // dense: the layer's qconst_tiled
     int K, N, chunks, groups, gshift, gm, cpw, nsg;
-    void* out;                                  // pair: H_sorted [R][N] (T); down: Y [R][N] fp32
+    void* out;                                  // pair: H_sorted [R][N] (T); down: Y [R][N] fp32; dense: out [M][N] (T)
 };
 
 // 2 / 3 bits (opt-in: GPTQ_MOE_LOW_BIT_BATCH): the copy of utils.hip prepack_decode_weights_kernel read in place -- Deq1_3::frag(words, ks) as the dense rows
@@ -260,6 +264,48 @@ hipError_t launch_moe_batch(const gptq_moe_t& m, const void* table, const MoeBat
     if ((e = moerows::launch_any(D.dtype, D.bits, d, (long)pl.tiles * d.nsg, pl.waves_down, pl.lds_down, st)) != hipSuccess) return e;
 
     return launch_moe_combine(pos, w, (const float*)(ws + pl.off_y), out, T, topk, H, 1, R, G.dtype, st);
+}
+
+// ---- the dense form (one flagged 2-bit QuantLinear layer; moe_rows_body.inc) ---------------------------------------------------------------------
+// What the down form takes: fp16 / bf16, K a whole number of 128-deep chunks, N a whole number of NS-strip groups, a group size of the rows family; 32-bit x
+// offsets per lane (gemm_rows.hip); act-order layers with their re-sequenced rows (the copy is made of them; the caller permutes x)
+bool dense_rows_int2_ok(const gptq_layer_t& L, int M) {
+    if (!copy_rows_int2(L) || (L.dtype != GPTQ_F16 && L.dtype != GPTQ_BF16) || L.epilogue != GPTQ_EPI_NONE) return false;
+    if (L.g_idx != nullptr && !(L.perm && L.qweight_seq)) return false;
+    if (L.K % 128 || L.N % (16 * moerows::NS) || moerows::group_mode(L) < 0) return false;
+    if ((size_t)M * L.K * 2 >= ((size_t)1 << 32)) return false;
+    return M >= 1 && M <= 1024;
+}
+
+RowsPlan plan_dense_rows_int2(const gptq_layer_t& L, int M) {
+    RowsPlan pl{};
+    if (!dense_rows_int2_ok(L, M)) return pl;
+    const int chunks = L.K / 128;
+    pl.rb = 1; pl.s = moerows::NS; pl.xbufs = 2;
+    pl.waves = std::max(1, std::min(moerows::MAX_WAVES, chunks / 2));      // plan_moe_batch's: every wave runs at least two chunks behind its ring
+    pl.cpw = (chunks + pl.waves - 1) / pl.waves;
+    pl.waves = (chunks + pl.cpw - 1) / pl.cpw;                             // no wave without a chunk
+    pl.npm = (M + moerows::BM - 1) / moerows::BM;
+    pl.nsg = L.N / (16 * moerows::NS);
+    pl.lds_bytes = (size_t)pl.waves * 2 * moerows::XB;                     // >= the waves' sums (waves x NS x 1 KiB)
+    pl.ok = true;
+    return pl;
+}
+
+hipError_t launch_dense_rows_int2(const gptq_layer_t& L, const void* x, void* out, int M, const RowsPlan& pl, hipStream_t st) {
+    if (!pl.ok || !dense_rows_int2_ok(L, M)) return hipErrorInvalidValue;
+    moerows::Args a{};
+    a.dense_tq = L.qweight_tiled; a.dense_cst = L.qconst_tiled; a.dense_bias = L.bias; a.dense_M = M;
+    a.pair = 2;
+    a.a = x; a.plane_bytes = 0; a.row_assign = nullptr; a.topk = 1; a.planes = 1;
+    a.K = L.K; a.N = L.N; a.chunks = L.K / 128;
+    a.groups = (L.K + L.group_size - 1) / L.group_size;
+    a.gshift = 31;
+    if (L.group_size >= 128 && L.group_size < L.K) a.gshift = __builtin_ctz((unsigned)(L.group_size / 128));
+    a.gm = moerows::group_mode(L);
+    a.cpw = pl.cpw; a.nsg = pl.nsg;
+    a.out = out;
+    return moerows::launch_any(L.dtype, 2, a, (long)pl.npm * pl.nsg, pl.waves, (int)pl.lds_bytes, st);
 }
 
 // grants > 64 KiB of dynamic LDS (act-order pair form: two planes of x buffers)

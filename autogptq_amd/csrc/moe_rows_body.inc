@@ -1,6 +1,10 @@
 // moe_rows_body.inc -- the body of moe_rows_kernel<T, BITS> (4 / 8 bits) and moe_rows_lowbit_kernel<T, BITS> (2 / 3 bits), included into both (moe_rows.hip:
 // the design, the names it uses).  In scope: T, BITS, Args p.  Text inclusion rather than a shared __device__ function: the 4- and 8-bit kernels keep their
 // code objects instruction for instruction (an inlined function body changed their scalar prologue and register assignment).
+//
+// DENSE form (2 bits only, p.pair == 2, launch-uniform: launch_dense_rows_int2): one QuantLinear layer on its decode copy.  No tables: tile t is rows
+// [16 t, min(16 t + 16, M)) of x [M][K], the copy / constants / bias / M are launch arguments (Args: dense_tq, dense_cst, dense_bias, dense_M), the K loop is
+// the down form's (NS strips behind one staged chunk, one plane, rows as they lie) and the store is out[m][n] = T(sum + bias[n]) into out [M][N].
     constexpr int NH = BITS == 8 ? 2 : 1;                      // chunks of the copy per 128-deep chunk of the rows
     constexpr unsigned REC = BITS == 8 ? 64u : 48u;            // constant record (2 / 3 bits: the 4-bit record, a one-byte zero-point)
     constexpr unsigned WCH = BITS == 3 ? 768u : (BITS == 2 ? 512u : 1024u), WLANE = BITS == 3 ? 12u : (BITS == 2 ? 8u : 16u);      // strip-chunk of the copy, a lane's bytes of it
@@ -11,20 +15,37 @@
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = blockDim.x >> 6;
     const int sgi = blockIdx.x % p.nsg, tile = blockIdx.x / p.nsg;
-    if (tile >= *p.tile_count) return;
-    const int4 tl = p.tiles[tile];
+    // 2 bits: p.pair == 2 is the dense form.  PAIR is p.pair itself at every other width (the condition folds in the front end: those kernels read the
+    // argument where and as often as they did)
+#define PAIR (BITS == 2 ? p.pair == 1 : p.pair != 0)
+    bool dense = false;
+    if constexpr (BITS == 2) dense = p.pair == 2;
+    int4 tl;
+    if constexpr (BITS == 2) {
+        if (dense) {
+            tl = int4{0, tile * BM, min(BM, p.dense_M - tile * BM), 0};      // the grid is exactly the tiles: none is empty
+        } else {
+            if (tile >= *p.tile_count) return;
+            tl = p.tiles[tile];
+        }
+    } else {
+        if (tile >= *p.tile_count) return;
+        tl = p.tiles[tile];
+    }
     const int e = __builtin_amdgcn_readfirstlane(tl.x), row0 = __builtin_amdgcn_readfirstlane(tl.y), rows = __builtin_amdgcn_readfirstlane(tl.z);
-    const int S = p.pair ? NS / 2 : NS, s0 = sgi * S;
+    const int S = PAIR ? NS / 2 : NS, s0 = sgi * S;
     const int planes = p.planes;
     const int r = lane & 15, g = lane >> 4;
 
-    const Entry e0 = load_entry(p.table + e);
-    const Entry e1 = p.pair ? load_entry(p.table + p.E + e) : e0;
+    Entry e0;
+    if constexpr (BITS == 2) e0 = dense ? Entry{p.dense_tq, p.dense_cst, nullptr, nullptr} : load_entry(p.table + e);
+    else e0 = load_entry(p.table + e);
+    const Entry e1 = PAIR ? load_entry(p.table + p.E + e) : e0;
     const char* wb[NS];
     const char* cb[NS];
 #pragma unroll
     for (int v = 0; v < NS; ++v) {
-        const bool up = p.pair && v >= NS / 2;
+        const bool up = PAIR && v >= NS / 2;
         const int strip = s0 + (up ? v - NS / 2 : v);
         wb[v] = (const char*)(up ? e1.tq : e0.tq) + (size_t)strip * (size_t)(p.chunks * NH) * WCH;
         cb[v] = (const char*)(up ? e1.cst : e0.cst) + (size_t)strip * (size_t)p.groups * REC;
@@ -191,7 +212,18 @@
         const int l = item & 63, v = item >> 6;
         const int n = (s0 + v) * 16 + (l & 15);
         const f32x4 sg = wsum(v, l);
-        if (p.pair) {
+        if constexpr (BITS == 2) {
+            if (dense) {
+                const float b = p.dense_bias ? DType<T>::to_f32(((const T*)p.dense_bias)[n]) : 0.f;      // (a 2-byte load: no dwordx4 in this kernel but the x DMAs)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int row = 4 * (l >> 4) + i;
+                    if (row < rows) ((T*)p.out)[(size_t)(row0 + row) * N + n] = DType<T>::from_f32(sg[i] + b);
+                }
+                continue;
+            }
+        }
+        if (PAIR) {
             const f32x4 su = wsum(v + NS / 2, l);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {                      // C/D layout of the 16x16 MFMA: row = 4 (lane >> 4) + i, column = lane & 15
@@ -207,3 +239,4 @@
             }
         }
     }
+#undef PAIR

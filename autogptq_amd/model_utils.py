@@ -89,7 +89,7 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
                        release_checkpoint_layout: Optional[bool] = None, decode_copy: Optional[bool] = None,
                        expert_decode_copy: bool = False, expert_batched_decode: bool = False, expert_backward: bool = False, expert_low_bit: bool = False,
                        expert_prefill: bool = False, expert_low_bit_decode: bool = False, expert_low_bit_batch: bool = False,
-                       expert_low_bit_prefill: bool = False) -> nn.Module:
+                       expert_low_bit_prefill: bool = False, low_bit_rows: bool = False) -> nn.Module:
     """post_init every mi355x layer and size the per-device scratch once (so forward never allocates; needed before hipGraph
     capture).  ``max_input_length`` bounds the rows M the scratch is sized for (default 2048, the reference's exllama default).
     Memory (the model-level switches for what post_init keeps next to the checkpoint tensors): ``decode_copy=False`` builds no decode copy (1x the packed
@@ -117,6 +117,9 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
     module's post_init): 2- and 3-bit experts get a decode copy (if nothing else built it) and calls of 65 tokens and more
     (``QuantMoEExperts.low_bit_prefill_min_tokens``) run the prefill kernels on it; the scratch covers ``gptq_moe_prefill_workspace_bytes`` of
     ``max_input_length`` tokens and the largest need below the threshold; nothing changes for 4- and 8-bit experts.
+    ``low_bit_rows=True`` (``QuantLinear.post_init(low_bit_rows=True)``): dense 2-bit layers that got a decode copy also run 5+ rows on it, in the row bands
+    where the planner gives a 4-bit layer of the same shape its rows / panel kernel (with ``release_checkpoint_layout=True`` those calls then need no rebuilt
+    rows); nothing changes for 3-, 4- and 8-bit layers, and with the default every plan is what it was.
     Blocks bound by ``inject_shared_expert`` before this call: the scratch also covers ``gptq_moe_shared_decode_workspace_bytes`` of 1..4 tokens."""
     from .moe import QuantMoEExperts
     rows = max_input_length or 2048
@@ -145,7 +148,7 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
         if sub.qweight.device.type != "cuda":
             continue
         dev = sub.qweight.device                      # read BEFORE post_init: release_checkpoint_layout moves qweight to pinned host memory, and the scratch belongs to the layer's GPU
-        sub.post_init(tiled=decode_copy, release_checkpoint_layout=release_checkpoint_layout)
+        sub.post_init(tiled=decode_copy, release_checkpoint_layout=release_checkpoint_layout, low_bit_rows=(True if low_bit_rows else None))
         lib = _lib.load()
         # the need is not monotone in M (K splits come and go with the kernel the planner picks): maximum over 1..rows
         parts = getattr(sub, "_parts", None)

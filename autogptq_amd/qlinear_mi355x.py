@@ -132,6 +132,12 @@ class QuantLinear(nn.Module):
     # kernel reads packed ROWS (the batched-decode band) rebuild them per call into a scratch shared by all layers of the device (gptq_unprepack_decode: the
     # exact inverse, ~10 us for a 4096 x 11008 layer).  Act-order layers keep their buffers (the copy is made of their re-sequenced rows).
     RELEASE_CHECKPOINT_LAYOUT = False
+    # Opt-in: a 2-bit layer that got a decode copy also runs 5+ rows on it (GPTQ_COPY_ROWS_INT2: the dense forms of the low-bit routed-expert kernels) instead of
+    # the checkpoint-row kernels.  A RELEASED 2-bit layer (+ GPTQ_COPY_ROWS_INT2_WIDE) does so in the whole band where the planner gives the 4-bit layer of the
+    # same shape its rows / panel kernel, and pays no rebuild pass there (1.96 - 8.7x, profiles/dense_int2_ab.log); with both layouts resident only where the
+    # forms measured faster (5 .. 16 rows of wide layers, 128 / 256+ rows: include/gptq_mi355x.h).  post_init(low_bit_rows=True) /
+    # autogptq_post_init(..., low_bit_rows=True) set it per call.  Off: every plan is what it was.  Changes nothing for 3-, 4- and 8-bit layers.
+    LOW_BIT_ROWS = False
     _extra_bytes_logged = False
 
     def __init__(
@@ -240,7 +246,7 @@ class QuantLinear(nn.Module):
         return _lib.ZERO_WRAP
 
     # ------------------------------------------------------------------ post_init
-    def post_init(self, temp_dq=None, tiled=None, release_checkpoint_layout=None):
+    def post_init(self, temp_dq=None, tiled=None, release_checkpoint_layout=None, low_bit_rows=None):
         """Snapshot device pointers and, for act-order layers, derive the group-sorted copy of
         qweight plus the x permutation (side buffers; qweight itself is never modified -- the
         reference's exllama backends overwrite it in place, q4_matrix.cu:160)."""
@@ -315,6 +321,10 @@ class QuantLinear(nn.Module):
                 with torch.cuda.device(dev):
                     _lib.check(lib.gptq_prepack_decode(ctypes.byref(L), qweight_tiled.data_ptr(), qconst_tiled.data_ptr(), _lib.current_stream_handle(dev)))
                 L.qweight_tiled, L.qconst_tiled, L.tiled_cols = qweight_tiled.data_ptr(), qconst_tiled.data_ptr(), _lib.STRIP_COLS
+        if low_bit_rows is None:
+            low_bit_rows = self.LOW_BIT_ROWS
+        if low_bit_rows and self.bits == 2 and qweight_tiled is not None:      # only on 2-bit layers that got a copy
+            L.tiled_cols |= _lib.COPY_ROWS_INT2
         self._layer = L
         self._layer_ref = ctypes.byref(L)
         self._layer_addr = ctypes.addressof(L)
@@ -345,6 +355,8 @@ class QuantLinear(nn.Module):
                 L.qweight = reserve_rows_scratch(dev, self._qweight_rows_bytes).data_ptr()
                 self._keepalive = (None,) + tuple(self._keepalive[1:])
                 self._released = True
+                if L.tiled_cols & _lib.COPY_ROWS_INT2:      # no resident rows: every call the low-bit forms take is one rebuild pass less -- their whole band
+                    L.tiled_cols |= _lib.COPY_ROWS_INT2_WIDE
             elif not QuantLinear._extra_bytes_logged:
                 QuantLinear._extra_bytes_logged = True
                 logger.info("mi355x QuantLinear: post_init keeps a decode copy of the packed weights next to the checkpoint tensors (+%d bytes for this layer; "

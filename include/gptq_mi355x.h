@@ -154,7 +154,7 @@ typedef struct gptq_layer_t {
     const uint32_t *qweight_seq;  /* [K/32*bits, N] or NULL */
     const int32_t  *perm;         /* [K] or NULL */
     int32_t epilogue;             /* gptq_epilogue_t; with SILU_MUL / GELU_TANH_MUL `out` is [M, N/2] */
-    int32_t tiled_cols;           /* GPTQ_STRIP_COLS when the two side buffers below are given, else 0 */
+    int32_t tiled_cols;           /* GPTQ_STRIP_COLS when the two side buffers below are given, else 0; | GPTQ_COPY_ROWS_INT2: opt-in, below */
     /* Optional derived (post_init) DECODE COPY of a 2-, 3-, 4- or 8-bit layer, built by gptq_prepack_decode (sizes: gptq_prepack_decode_bytes); both NULL =
      * decode streams the checkpoint layout.  With w[k][n] the layer's unpacked integers (rows taken from qweight_seq when the layer has one, else qweight;
      * k past K read as 0), KPL = 32 (16 at 8 bits) and WPL = 4 (3 at 3 bits, 2 at 2 bits):
@@ -165,7 +165,14 @@ typedef struct gptq_layer_t {
      *                   3 bits  word j: pair p = 5 j + i (i = 0..4) at bit 3 i of the low (k0 + 2 p) and high (k0 + 2 p + 1) 16 bits; bit 15 / 31 = bit j of
      *                           w[k0 + 30] / w[k0 + 31] -- the checkpoint's word-straddling values are resolved here, once
      *                   2 bits  (round 6) word w: pair p (0..7) at bit 2 p of the low (k0 + 16 w + 2 p) and high (k0 + 16 w + 2 p + 1) 16 bits; read by the
-     *                           decode kernel only (plain and act-order layers, up to 4 rows; no fused epilogue) -- the batched / prefill kernels keep the checkpoint rows
+     *                           decode kernel (plain and act-order layers, up to 4 rows; no fused epilogue) and -- OPT-IN, per layer: tiled_cols =
+     *                           GPTQ_STRIP_COLS | GPTQ_COPY_ROWS_INT2 -- from 5 rows up by the dense forms of the low-bit routed-expert kernels
+     *                           (moe_rows_lowbit_kernel<T, 2> at 5 .. 64 rows, moe_panel_lowbit_kernel<T, 2> from 65 rows through the panel band, inside the band
+     *                           where the planner would give the 4-bit layer of the same shape the rows / panel kernel -- all of it with
+     *                           GPTQ_COPY_ROWS_INT2_WIDE, the measured part of it without: below; gptq_describe_plan: kernel=rows|panel ... body=lowbit).
+     *                           Without the flag, and outside those bands, the batched / prefill kernels keep the checkpoint rows.
+     *                           The flag rides in tiled_cols because the struct's layout is the ABI: every reader masks it (GPTQ_COPY_COLS), a layer of
+     *                           another width, or one without a copy, that carries it behaves exactly as without it
      *                 A strip is one contiguous run, a chunk one contiguous 1024 (3 bits: 768, 2 bits: 512) bytes = one wave load;
      *   qconst_tiled  [strip][group g][REC bytes] = 16 scales (layer dtype) at byte 0, then from byte 32 the 16 zero-points AS USED (zero_mode applied):
      *                 uint8 each, REC = 48, at 2 / 3 / 4 bits; uint16 each, REC = 64, at 8 bits (no-wrap reaches 256).
@@ -176,6 +183,15 @@ typedef struct gptq_layer_t {
 } gptq_layer_t;
 
 #define GPTQ_STRIP_COLS 16
+/* OR-ed into gptq_layer_t.tiled_cols: this 2-bit layer's copy is also read at 5+ rows (see qweight_tiled above).  GPTQ_COPY_COLS(tiled_cols) is the strip width.
+ * GPTQ_COPY_ROWS_INT2 alone: where the forms measured faster than the checkpoint-row kernels with both layouts resident (profiles/dense_int2_ab.log):
+ *   rows form   5 .. 16 rows of layers with N >= 8192 and K <= 4096;   panel form   from 256 rows, and from 128 rows where N >= 8192
+ * -- each inside the band where the planner gives the 4-bit layer of the same shape its rows / panel kernel.
+ * | GPTQ_COPY_ROWS_INT2_WIDE (means nothing without the first bit): that whole band (5 .. 64 rows: rows form, 65 rows and more: panel form) -- for a layer whose
+ * checkpoint rows are NOT resident (QuantLinear sets it on a released layer), where every call that reads rows first pays gptq_unprepack_decode. */
+#define GPTQ_COPY_ROWS_INT2 0x100
+#define GPTQ_COPY_ROWS_INT2_WIDE 0x200
+#define GPTQ_COPY_COLS(tiled_cols) ((tiled_cols) & ~(GPTQ_COPY_ROWS_INT2 | GPTQ_COPY_ROWS_INT2_WIDE))
 
 /* Kernel families a caller may force with gptq_tuning_t.path ("does not fit" is then an error instead of a silent fallback). */
 typedef enum gptq_path_t {

@@ -252,7 +252,7 @@ __global__ void __launch_bounds__(1024) gemm_strips_kernel(StripsParams p) {
 // ---- host side -------------------------------------------------------------------------------------------------------------------------------
 bool strips_layer_ok(const gptq_layer_t& L) {
     if (L.bits != 4 || (L.dtype != GPTQ_F16 && L.dtype != GPTQ_BF16) || L.epilogue != GPTQ_EPI_NONE) return false;
-    if (!L.qweight_tiled || !L.qconst_tiled || L.tiled_cols != GPTQ_STRIP_COLS) return false;
+    if (!L.qweight_tiled || !L.qconst_tiled || GPTQ_COPY_COLS(L.tiled_cols) != GPTQ_STRIP_COLS) return false;
     if (L.g_idx != nullptr && !(L.perm && L.qweight_seq)) return false;
     if (L.K % 128 || L.N % GPTQ_STRIP_COLS) return false;
     const int gu = L.group_size / 32;

@@ -519,7 +519,8 @@ size_t gptq_workspace_bytes_multi(const gptq_layer_t* const* layers, int n_layer
 // with tuning.path = 3 and tuning.reserved[2] = 4.
 static bool want_stream64_multi(const gptq_layer_t* const* layers, int n, int M, const gptq_tuning_t* t, Stream64Plan* plan_out) {
     if (n < 2 || n > 4 || M > 64) return false;
-    const bool forced = t && t->path == 3 && t->reserved[2] == 4;
+    const GemmKnobs k = GemmKnobs::decode(t);
+    const bool forced = k.forced && k.kernel == GPTQ_LAB_GEMM_STREAM64;
     if (t && t->path != 0 && !forced) return false;
     if (M <= 2 && !forced) return false;                         // up to 2 rows: the streamed GEMV (or layer by layer)
     const Stream64Plan& sp = *plan_out = plan_stream64(layers, n, M, t);
@@ -533,7 +534,8 @@ static bool want_stream64_multi(const gptq_layer_t* const* layers, int n, int M,
 // tuning.reserved[2] = 5.
 static bool want_mid_multi(const gptq_layer_t* const* layers, int n, int M, const gptq_tuning_t* t, MidPlan* plan_out) {
     if (n < 2 || n > 4 || M > 256) return false;
-    const bool forced = t && t->path == 3 && t->reserved[2] == 5;
+    const GemmKnobs k = GemmKnobs::decode(t);
+    const bool forced = k.forced && k.kernel == GPTQ_LAB_GEMM_MID;
     if (t && t->path != 0 && !forced) return false;
     const MidPlan& mp = *plan_out = plan_mid(layers, n, M, t);
     return mp.ok && (mp.pays || forced);
@@ -581,7 +583,8 @@ static MultiRoute route_forward_multi(const gptq_layer_t* const* layers, int n_l
     if (tune && tune->path == 8) r.declined = 8;
     // 5 .. 128 rows on layers that carry the decode copy: the exchange-free kernel over the strip groups of all layers (gemm_rows.hip); act-order layers of
     // ONE order (the same perm pointer: QuantLinear.share_act_order) read one permuted x -- and nothing else is staged
-    const bool rows_forced = tune && tune->path == 3 && tune->reserved[3] == GPTQ_LAB_VARIANT_ROWS_ON && rows_multi_ok(layers, n_layers, M);      // lab knob 50
+    const GemmKnobs k = GemmKnobs::decode(tune);
+    const bool rows_forced = k.forced && k.rows == GemmKnobs::ON && rows_multi_ok(layers, n_layers, M);      // lab knob 50
     // (a group with a flagged 2-bit layer in the band where that layer runs on its copy: layer by layer too -- the low-bit forms have no group launch)
     bool lowbit_single = false;
     for (int i = 0; !tune && i < n_layers; ++i) lowbit_single = lowbit_single || (layers[i]->epilogue == GPTQ_EPI_NONE && dense_int2_choice(*layers[i], M) != 0);
@@ -595,7 +598,7 @@ static MultiRoute route_forward_multi(const gptq_layer_t* const* layers, int n_l
         if ((r.sp = plan_stream(layers, n_layers, M, tune)).ok && multi_preferred(layers, n_layers, M) && r.hit(MULTI_STREAM, r.sp.partial_bytes)) return r;
         if (tune && tune->path == 6) r.declined = 6;
     }
-    if (tune && tune->path == 3 && (tune->reserved[2] == 4 || tune->reserved[2] == 5)) r.declined = tune->reserved[2];
+    if (k.forced && (k.kernel == GPTQ_LAB_GEMM_STREAM64 || k.kernel == GPTQ_LAB_GEMM_MID)) r.declined = k.kernel;
     // Act-order layers that share ONE perm -- q / k / v and gate / up of a GPTQ checkpoint do: the activation order comes from the Hessian of the
     // layers' common input (the reference's fused q/k/v caller relies on it: fused_llama_attn.py:188 hands the kernels q_proj's order for all three) --
     // read ONE permuted x: the first layer's GEMM call permutes into the head of the workspace, the others find it there.  The caller says so by

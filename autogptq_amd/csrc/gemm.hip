@@ -309,7 +309,7 @@ template <> struct Deq<4, bf16> {
 // Workgroup = 4 waves side by side along N: tile BM = 32*MT rows x 256 columns, K-step BK.
 // VAR selects the inner-loop schedule: 1 (default) = explicit software pipeline over the MFMA k-steps, 0 = plain loop
 // scheduled by hipcc, 2 = plain + s_setprio around the MFMA groups, 3 = the pipeline carried across K-steps (+-1 %: kept as
-// an experiment, tuning.reserved[3] = 3).  Within-run A/B on MI355X (tools/gemmlab, min of 3
+// an experiment, GPTQ_LAB_VARIANT_CROSS_STEP).  Within-run A/B on MI355X (tools/gemmlab, min of 3
 // rounds, TFLOP/s at M=2048 4096^2 / M=4096 4096^2 / 4096x11008 / 11008x4096): VAR1 793/1002/908/889, VAR0 678/990/888/840,
 // VAR2 743/972/852/815.  (Also tried: 8 waves per workgroup, one column of each pair per wave -- slower everywhere.)
 // XPRE: x already arrives in k-slot order (act-order layers: the column-permute pre-pass writes it that way).
@@ -1698,7 +1698,7 @@ hipError_t launch_permute_rows16(const void* x, const int32_t* perm, int M, int 
 }
 
 // ---- host side ----------------------------------------------------------------------------------
-// Balanced tail of the tiled kernel by default?  (tuning.reserved[3] = 40 / 41 forces the rule on / off for A/B runs.)
+// Balanced tail of the tiled kernel by default?  (GPTQ_LAB_VARIANT_TAIL_ON / _TAIL_OFF force the rule on / off for A/B runs.)
 constexpr bool GEMM_TAIL_DEFAULT = true;
 
 template <int BITS, typename T, int MT, int BK, int VAR, bool XPRE, bool GLDS, int KG>
@@ -1850,6 +1850,44 @@ hipError_t launch_stream64(const gptq_layer_t* const* Ls, const Stream64Plan& pl
     return (Ls[0]->dtype == GPTQ_F16) ? launch_stream64_t<f16>(pl, p, st) : launch_stream64_t<bf16>(pl, p, st);
 }
 
+// ---- plan_gemm: one function per rung of the ladder, in the order plan_gemm asks them.  Each fills `pl` and returns true where it takes the call. ----
+static bool plan_f32(const gptq_layer_t& L, int M, const GemmKnobs&, const gptq_tuning_t*, GemmPlan& pl) {
+    if (L.dtype != GPTQ_F32) return false;   // exact-f32 matrix core, 128 x 128 tiles, any bit width; groups made of whole packing units
+    pl.mt = 4; pl.bk = 32; pl.bm = 128; pl.bn = 128; pl.waves = 4; pl.kg = 1;
+    pl.nbm = (M + 127) / 128;
+    pl.nbn = (L.N + 127) / 128;
+    pl.ksplit = 1;
+    pl.ksteps_total = pl.ksteps_per_split = L.K / 32;
+    pl.workspace_bytes = pl.xperm_bytes;
+    return true;
+}
+
+// GEMM_PANEL / GEMM_ROWS from the kernel's own plan, where that plan is ok; lowbit: the dense 2-bit form of the routed-expert kernel
+static bool fill_from_panel(GemmPlan& pl, const gptq_layer_t& L, const PanelPlan& pp, bool lowbit) {
+    if (!pp.ok) return false;
+    pl.kernel = GEMM_PANEL;
+    pl.lowbit = lowbit;
+    pl.panelp = pp;
+    pl.xnat = pl.use_seq;
+    pl.mt = pp.mt; pl.bk = 64; pl.bm = 32 * pp.mt; pl.bn = 32 * pp.nt; pl.nbm = pp.nbm; pl.nbn = pp.nbn;
+    pl.waves = pp.kp; pl.u = 2; pl.kg = pp.kp;
+    pl.ksplit = 1; pl.ksteps_total = pl.ksteps_per_split = L.K / 64;
+    pl.workspace_bytes = pl.xperm_bytes;
+    return true;
+}
+static bool fill_from_rows(GemmPlan& pl, const gptq_layer_t& L, const RowsPlan& rp, bool lowbit) {
+    if (!rp.ok) return false;
+    pl.kernel = GEMM_ROWS;
+    pl.lowbit = lowbit;
+    pl.rowsp = rp;
+    pl.xnat = pl.use_seq;
+    pl.mt = rp.rb; pl.bk = 128; pl.bm = 16 * rp.rb; pl.bn = 16 * rp.s; pl.nbm = rp.npm; pl.nbn = rp.nsg;
+    pl.waves = rp.waves; pl.u = 2; pl.kg = 1;
+    pl.ksplit = 1; pl.ksteps_total = pl.ksteps_per_split = L.K / 128;
+    pl.workspace_bytes = pl.xperm_bytes;
+    return true;
+}
+
 // A flagged 2-bit layer, no tuning.  The BAND is borrowed from the 4-bit kernels: 5 .. 64 rows -> the rows form where rows_pays takes the 4-bit layer of the same K,
 // N, group size, dtype and act-order; 65 rows and more -> the panel form where panel_pays does.  Measured at 2 bits (tools/dense_int2_ab.py, plain layers, fp16 / bf16,
 // g128 / g64, rotating HBM-cold layers in a hipGraph; unflagged plan -> these forms, us per layer call):
@@ -1862,8 +1900,8 @@ hipError_t launch_stream64(const gptq_layer_t* const* Ls, const Stream64Plan& pl
 //       panel form  256 rows and more                                     (4096^2 256 / 512 rows 1.22 - 1.56x, 8192^2 1.31 - 1.44x; 11008x4096 at 256 rows 0.95 - 1.04x: inside the spread)
 //                   128 rows and more where N >= 8192                     (4096x11008 1.32 - 1.52x, 5120x13824 1.31 - 1.51x, 8192^2 1.00 - 1.23x; 4096^2 at 128 rows 0.66 - 0.71x: excluded)
 //     65 .. 127 rows were measured at 65 only (0.65 - 1.08x) and stay with the unflagged plan.  Act-order layers: not measured, the same rule.
-int dense_int2_choice(const gptq_layer_t& L, int M) {
-    if (!copy_rows_int2(L) || M < 5) return 0;
+int dense_int2_choice(const gptq_layer_t& L, int M, const GemmKnobs& k) {
+    if (!k.planner_free() || !copy_rows_int2(L) || M < 5) return 0;
     const bool wide = copy_rows_int2_wide(L);
     gptq_layer_t T4 = L;
     T4.bits = 4;
@@ -1876,204 +1914,207 @@ int dense_int2_choice(const gptq_layer_t& L, int M) {
     return dense_panel_int2_ok(L, M) && panel_pays(T4, M) ? (int)GEMM_PANEL : 0;
 }
 
-GemmPlan plan_gemm(const gptq_layer_t& L, int M, const gptq_tuning_t* tune) {
-    GemmPlan pl{};
-    const int kpu = unit_vals(L.bits);
-    const bool seq = (L.g_idx == nullptr) || (L.qweight_seq != nullptr && L.perm != nullptr);
-    if (L.dtype == GPTQ_F32) {               // exact-f32 matrix core, 128 x 128 tiles, any bit width; groups made of whole packing units
-        pl.kernel = GEMM_F32;
-        pl.supported = seq && (L.group_size % kpu == 0) && (L.K % 32 == 0) && (L.N % 32 == 0);
-        if (!pl.supported) return pl;
-        pl.use_seq = (L.g_idx != nullptr);
-        pl.xperm_bytes = pl.use_seq ? align_up((size_t)M * L.K * 4, 256) : 0;
-        pl.mt = 4; pl.bk = 32; pl.bm = 128; pl.bn = 128; pl.waves = 4; pl.kg = 1;
-        pl.nbm = (M + 127) / 128;
-        pl.nbn = (L.N + 127) / 128;
-        pl.ksplit = 1;
-        pl.ksteps_total = pl.ksteps_per_split = L.K / 32;
-        pl.workspace_bytes = pl.xperm_bytes;
-        return pl;
+// OPT-IN (GPTQ_COPY_ROWS_INT2 in tiled_cols): a 2-bit layer on its decode copy from 5 rows up -- the dense forms of the low-bit routed-expert kernels
+// (moe_rows.hip / moe_panel.hip), where the rules below would give the 4-bit layer of the same shape the rows / panel kernel (dense_int2_choice); lab knobs
+// 50 / 52 force either form at any shape it takes, 51 / 53 keep it off.  Everything else about a flagged layer is the unflagged plan.
+static bool try_int2_copy(const gptq_layer_t& L, int M, const GemmKnobs& k, const gptq_tuning_t*, GemmPlan& pl) {
+    if (!copy_rows_int2(L)) return false;
+    const int choice = dense_int2_choice(L, M, k);
+    if ((k.panel == GemmKnobs::ON || (k.panel != GemmKnobs::OFF && choice == GEMM_PANEL)) && fill_from_panel(pl, L, plan_dense_panel_int2(L, M), true)) return true;
+    return (k.rows == GemmKnobs::ON || (k.rows != GemmKnobs::OFF && choice == GEMM_ROWS)) && fill_from_rows(pl, L, plan_dense_rows_int2(L, M), true);
+}
+
+// 64 .. ~1024 rows of a layer that carries its decode copy where its tiles fill the chip (panel_pays): whole-K panels of 64 x 32 nt tiles, no exchange
+// (gemm_panel.hip); lab knobs 52 / 53 force it on / off.  Asked before the rows kernel: from ~96 rows it is the faster of the two (profiles/r06_panel_sweep.log)
+static bool try_panel(const gptq_layer_t& L, int M, const GemmKnobs& k, const gptq_tuning_t* tune, GemmPlan& pl) {
+    if (!(k.panel == GemmKnobs::ON || (k.panel != GemmKnobs::OFF && k.planner_free() && panel_pays(L, M)))) return false;
+    return fill_from_panel(pl, L, plan_panel(L, M, k.panel == GemmKnobs::ON ? tune : nullptr), false);
+}
+
+// 5 .. ~256 rows of a layer that carries its decode copy: whole-K workgroups, no exchange (gemm_rows.hip); lab knobs 50 / 51 force it on / off
+static bool try_rows(const gptq_layer_t& L, int M, const GemmKnobs& k, const gptq_tuning_t* tune, GemmPlan& pl) {
+    if (!(k.rows == GemmKnobs::ON || (k.rows != GemmKnobs::OFF && k.planner_free() && rows_pays(L, M)))) return false;
+    return fill_from_rows(pl, L, plan_rows(L, M, k.rows == GemmKnobs::ON ? tune : nullptr), false);
+}
+
+// 17 .. 128 rows: everything by LDS DMA (gemm_mid.hip)
+static bool try_mid(const gptq_layer_t& L, int M, const GemmKnobs& k, const gptq_tuning_t* tune, GemmPlan& pl) {
+    const gptq_layer_t* one[1] = {&L};
+    const MidPlan mp = plan_mid(one, 1, M, tune);
+    // by default only without kernel-specific experiment knobs: tuning.reserved[0..3] mean different things to the tiled / stream64 kernels
+    const bool plain_tuning = !tune || (tune->reserved[GPTQ_LAB_DEPTH] == 0 && tune->reserved[GPTQ_LAB_OPT] == 0 && !k.variant_set);
+    if (!(mp.ok && (k.kernel == GPTQ_LAB_GEMM_MID || (k.kernel == 0 && mp.pays && plain_tuning)))) return false;
+    pl.kernel = GEMM_MID;
+    pl.midp = mp;
+    pl.mt = mp.rt; pl.bk = 32; pl.bm = 16 * mp.rt; pl.bn = 64 * mp.cw;
+    pl.nbm = mp.row_blocks; pl.nbn = mp.strips_total;
+    pl.waves = mp.waves; pl.u = mp.stages;
+    pl.ksteps_total = mp.ksteps_total; pl.ksteps_per_split = mp.ksteps_per_split; pl.ksplit = mp.ksplit;
+    pl.workspace_bytes = pl.xperm_bytes + mp.partial_bytes;
+    return true;
+}
+
+// batched decode (4 < M <= 64, 4-bit): 64-column strips, weights by LDS DMA, K slices combined inside the launch
+static bool try_stream64(const gptq_layer_t& L, int M, const GemmKnobs& k, const gptq_tuning_t* tune, GemmPlan& pl) {
+    const gptq_layer_t* one[1] = {&L};
+    const Stream64Plan sp = plan_stream64(one, 1, M, tune);
+    if (!(sp.ok && (k.kernel == GPTQ_LAB_GEMM_STREAM64 || (k.kernel == 0 && M >= 3 && sp.pays)))) return false;      // 3..4 rows: want_gemm takes it only unsplit
+    pl.kernel = GEMM_STREAM64;
+    pl.s64p = sp;                                 // the (possibly tuned) geometry launch_gemm hands to launch_stream64
+    pl.mt = sp.mt; pl.bk = 32; pl.bm = 16 * sp.mt; pl.bn = 64;
+    pl.nbm = 1; pl.nbn = sp.strips_total;
+    pl.waves = sp.waves; pl.u = sp.u;
+    pl.ksteps_total = sp.ksteps_total; pl.ksteps_per_split = sp.ksteps_per_split; pl.ksplit = sp.ksplit;
+    pl.workspace_bytes = pl.xperm_bytes + sp.partial_bytes;
+    return true;
+}
+
+// K slices of the strip kernels (S steps): the forced split, else doubled while the launch stays below `target` workgroups and a slice keeps `floor` steps;
+// slices of whole `chunk`-step chunks, no empty slices; fp32 partial slabs behind the permuted x
+static void split_k_strips(const gptq_layer_t& L, int M, const GemmKnobs& k, GemmPlan& pl, int S, int target, int floor, int chunk) {
+    int ks = k.ksplit;
+    if (!ks) {
+        ks = 1;
+        while ((long)pl.nbm * pl.nbn * ks < target && S / (ks * 2) >= floor) ks *= 2;
     }
-    pl.supported = (L.dtype == GPTQ_F16 || L.dtype == GPTQ_BF16) && seq && (L.group_size % 32 == 0) && (L.K % 32 == 0) &&
-                   (L.N % 32 == 0) && (L.group_size % kpu == 0) && ((size_t)L.K * 2 <= 64 * 1024 || L.g_idx == nullptr);
-    if (!pl.supported) return pl;
-    pl.use_seq = (L.g_idx != nullptr);
-    pl.xperm_bytes = pl.use_seq ? align_up((size_t)M * L.K * 2, 256) : 0;
-    const int force_skinny = tune ? tune->reserved[2] : 0;      // experiment knob: 1 = skinny, 2 = tiled
-    // OPT-IN (GPTQ_COPY_ROWS_INT2 in tiled_cols): a 2-bit layer on its decode copy from 5 rows up -- the dense forms of the low-bit routed-expert kernels
-    // (moe_rows.hip / moe_panel.hip), where the rules below would give the 4-bit layer of the same shape the rows / panel kernel (dense_int2_choice); lab knobs
-    // 50 / 52 force either form at any shape it takes, 51 / 53 keep it off.  Everything else about a flagged layer is the unflagged plan.
-    if (copy_rows_int2(L)) {
-        const int knob = tune ? tune->reserved[3] : 0;
-        const bool own = (!tune || tune->path != 3 || knob == 0) && force_skinny == 0;
-        const int choice = own ? dense_int2_choice(L, M) : 0;
-        if (knob == GPTQ_LAB_VARIANT_PANEL_ON || (knob != GPTQ_LAB_VARIANT_PANEL_OFF && choice == GEMM_PANEL)) {
-            const PanelPlan pp = plan_dense_panel_int2(L, M);
-            if (pp.ok) {
-                pl.kernel = GEMM_PANEL;
-                pl.lowbit = true;
-                pl.panelp = pp;
-                pl.xnat = pl.use_seq;
-                pl.mt = pp.mt; pl.bk = 64; pl.bm = 32 * pp.mt; pl.bn = 32 * pp.nt; pl.nbm = pp.nbm; pl.nbn = pp.nbn;
-                pl.waves = pp.kp; pl.u = 2; pl.kg = pp.kp;
-                pl.ksplit = 1; pl.ksteps_total = pl.ksteps_per_split = L.K / 64;
-                pl.workspace_bytes = pl.xperm_bytes;
-                return pl;
-            }
-        }
-        if (knob == GPTQ_LAB_VARIANT_ROWS_ON || (knob != GPTQ_LAB_VARIANT_ROWS_OFF && choice == GEMM_ROWS)) {
-            const RowsPlan rp = plan_dense_rows_int2(L, M);
-            if (rp.ok) {
-                pl.kernel = GEMM_ROWS;
-                pl.lowbit = true;
-                pl.rowsp = rp;
-                pl.xnat = pl.use_seq;
-                pl.mt = rp.rb; pl.bk = 128; pl.bm = 16 * rp.rb; pl.bn = 16 * rp.s; pl.nbm = rp.npm; pl.nbn = rp.nsg;
-                pl.waves = rp.waves; pl.u = 2; pl.kg = 1;
-                pl.ksplit = 1; pl.ksteps_total = pl.ksteps_per_split = L.K / 128;
-                pl.workspace_bytes = pl.xperm_bytes;
-                return pl;
-            }
-        }
-    }
-    // 64 .. ~1024 rows of a layer that carries its decode copy where its tiles fill the chip (panel_pays): whole-K panels of 64 x 32 nt tiles, no exchange
-    // (gemm_panel.hip); lab knobs 52 / 53 force it on / off.  Asked before the rows kernel: from ~96 rows it is the faster of the two (profiles/r06_panel_sweep.log)
-    {
-        const int knob = tune ? tune->reserved[3] : 0;
-        if (knob == GPTQ_LAB_VARIANT_PANEL_ON || (knob != GPTQ_LAB_VARIANT_PANEL_OFF && (!tune || tune->path != 3 || knob == 0) && force_skinny == 0 && panel_pays(L, M))) {
-            const PanelPlan pp = plan_panel(L, M, knob == GPTQ_LAB_VARIANT_PANEL_ON ? tune : nullptr);
-            if (pp.ok) {
-                pl.kernel = GEMM_PANEL;
-                pl.panelp = pp;
-                pl.xnat = pl.use_seq;
-                pl.mt = pp.mt; pl.bk = 64; pl.bm = 32 * pp.mt; pl.bn = 32 * pp.nt; pl.nbm = pp.nbm; pl.nbn = pp.nbn;
-                pl.waves = pp.kp; pl.u = 2; pl.kg = pp.kp;
-                pl.ksplit = 1; pl.ksteps_total = pl.ksteps_per_split = L.K / 64;
-                pl.workspace_bytes = pl.xperm_bytes;
-                return pl;
-            }
-        }
-    }
-    // 5 .. ~256 rows of a layer that carries its decode copy: whole-K workgroups, no exchange (gemm_rows.hip); lab knobs 50 / 51 force it on / off
-    {
-        const int knob = tune ? tune->reserved[3] : 0;
-        if (knob == GPTQ_LAB_VARIANT_ROWS_ON || (knob != GPTQ_LAB_VARIANT_ROWS_OFF && (!tune || tune->path != 3 || knob == 0) && force_skinny == 0 && rows_pays(L, M))) {
-            const RowsPlan rp = plan_rows(L, M, knob == GPTQ_LAB_VARIANT_ROWS_ON ? tune : nullptr);
-            if (rp.ok) {
-                pl.kernel = GEMM_ROWS;
-                pl.rowsp = rp;
-                pl.xnat = pl.use_seq;
-                pl.mt = rp.rb; pl.bk = 128; pl.bm = 16 * rp.rb; pl.bn = 16 * rp.s; pl.nbm = rp.npm; pl.nbn = rp.nsg;
-                pl.waves = rp.waves; pl.u = 2; pl.kg = 1;
-                pl.ksplit = 1; pl.ksteps_total = pl.ksteps_per_split = L.K / 128;
-                pl.workspace_bytes = pl.xperm_bytes;
-                return pl;
-            }
-        }
-    }
-    // Measured crossovers (tools/midm_bench.py, us per launch at M = 9/16/32/64):
-    //   4096x4096   strips16  8.0/ 9.1/12.3/19.6   skinny64 12.1/12.3/12.7/15.5   tiled 15.5/15.7/17.1/22.6
-    //   11008x4096  strips16 17.9/20.1/27.9/47.9   skinny64 23.2/23.1/24.0/27.4   tiled 27.6/28.0/28.8/37.2
-    //   4096x11008  strips16 19.5/22.4/31.4/53.7   skinny64 19.2/19.5/22.8/33.0   tiled 17.8/18.7/20.9/25.7
-    // 16-column strips re-read x from L2 once per strip (M*K*N/8 bytes), so they only pay up to M = 16; a wide N gives the
-    // tiled kernel enough 256-column tiles to fill the chip without help.
-    const bool skinny = ((force_skinny == 1) || (force_skinny == 0 && M <= 64 && (L.N + 255) / 256 < 32)) && M <= 128;      // (asked last: mid, stream64 and strip16 go first)
-    // 17 .. 128 rows: everything by LDS DMA (gemm_mid.hip)
-    {
-        const gptq_layer_t* one[1] = {&L};
-        const MidPlan mp = plan_mid(one, 1, M, tune);
-        // by default only without kernel-specific experiment knobs: tuning.reserved[0..3] mean different things to the tiled / stream64 kernels
-        const bool plain_tuning = !tune || (tune->reserved[0] == 0 && tune->reserved[1] == 0 && tune->reserved[3] == 0);
-        if (mp.ok && (force_skinny == 5 || (force_skinny == 0 && mp.pays && plain_tuning))) {
-            pl.kernel = GEMM_MID;
-            pl.midp = mp;
-            pl.mt = mp.rt; pl.bk = 32; pl.bm = 16 * mp.rt; pl.bn = 64 * mp.cw;
-            pl.nbm = mp.row_blocks; pl.nbn = mp.strips_total;
-            pl.waves = mp.waves; pl.u = mp.stages;
-            pl.ksteps_total = mp.ksteps_total; pl.ksteps_per_split = mp.ksteps_per_split; pl.ksplit = mp.ksplit;
-            pl.workspace_bytes = pl.xperm_bytes + mp.partial_bytes;
-            return pl;
-        }
-    }
-    // batched decode (4 < M <= 64, 4-bit): 64-column strips, weights by LDS DMA, K slices combined inside the launch
-    {
-        const gptq_layer_t* one[1] = {&L};
-        const Stream64Plan sp = plan_stream64(one, 1, M, tune);
-        if (sp.ok && (force_skinny == 4 || (force_skinny == 0 && M >= 3 && sp.pays))) {      // 3..4 rows: want_gemm takes it only unsplit
-            pl.kernel = GEMM_STREAM64;
-            pl.s64p = sp;                                 // the (possibly tuned) geometry launch_gemm hands to launch_stream64
-            pl.mt = sp.mt; pl.bk = 32; pl.bm = 16 * sp.mt; pl.bn = 64;
-            pl.nbm = 1; pl.nbn = sp.strips_total;
-            pl.waves = sp.waves; pl.u = sp.u;
-            pl.ksteps_total = sp.ksteps_total; pl.ksteps_per_split = sp.ksteps_per_split; pl.ksplit = sp.ksplit;
-            pl.workspace_bytes = pl.xperm_bytes + sp.partial_bytes;
-            return pl;
-        }
-    }
-    // 16-column strips on the 16x16x32 matrix core: 4-bit fp16/bf16, M <= 64
+    if (ks > S) ks = S;
+    pl.ksteps_total = S;
+    pl.ksteps_per_split = (S + ks - 1) / ks;
+    pl.ksteps_per_split = (pl.ksteps_per_split + chunk - 1) / chunk * chunk;
+    pl.ksplit = (S + pl.ksteps_per_split - 1) / pl.ksteps_per_split;
+    pl.workspace_bytes = pl.xperm_bytes + (pl.ksplit > 1 ? (size_t)pl.ksplit * M * L.N * sizeof(float) : 0);
+}
+
+// Measured crossovers (tools/midm_bench.py, us per launch at M = 9/16/32/64):
+//   4096x4096   strips16  8.0/ 9.1/12.3/19.6   skinny64 12.1/12.3/12.7/15.5   tiled 15.5/15.7/17.1/22.6
+//   11008x4096  strips16 17.9/20.1/27.9/47.9   skinny64 23.2/23.1/24.0/27.4   tiled 27.6/28.0/28.8/37.2
+//   4096x11008  strips16 19.5/22.4/31.4/53.7   skinny64 19.2/19.5/22.8/33.0   tiled 17.8/18.7/20.9/25.7
+// 16-column strips re-read x from L2 once per strip (M*K*N/8 bytes), so they only pay up to M = 16; a wide N gives the
+// tiled kernel enough 256-column tiles to fill the chip without help.
+// 16-column strips on the 16x16x32 matrix core: 4-bit fp16/bf16, M <= 64
+static bool try_strip16(const gptq_layer_t& L, int M, const GemmKnobs& k, const gptq_tuning_t*, GemmPlan& pl) {
     const bool strip16_ok = L.bits == 4 && M <= 64 && L.group_size % 32 == 0 && L.K % 32 == 0 && L.N % 16 == 0;
-    if (strip16_ok && (force_skinny == 3 || (force_skinny == 0 && M <= 16 && L.N <= 8192))) {
-        pl.kernel = GEMM_STRIP16;
-        pl.mt = M <= 16 ? 1 : (M <= 32 ? 2 : 4);                  // row tiles of 16
-        pl.bk = 32;
-        pl.bm = 16 * pl.mt;
-        pl.bn = 16;
-        pl.nbm = (M + pl.bm - 1) / pl.bm;
-        pl.nbn = L.N / 16;
-        pl.waves = 16;
-        const int S = L.K / 32;
-        int ks = (tune && tune->ksplit > 0 && tune->path == 3) ? tune->ksplit : 0;
-        if (!ks) {
-            ks = 1;
-            while ((long)pl.nbm * pl.nbn * ks < 192 && S / (ks * 2) >= pl.waves) ks *= 2;
-        }
-        if (ks > S) ks = S;
-        pl.ksteps_total = S;
-        pl.ksteps_per_split = (S + ks - 1) / ks;
-        pl.ksplit = (S + pl.ksteps_per_split - 1) / pl.ksteps_per_split;
-        pl.workspace_bytes = pl.xperm_bytes + (pl.ksplit > 1 ? (size_t)pl.ksplit * M * L.N * sizeof(float) : 0);
-        return pl;
+    if (!(strip16_ok && (k.kernel == GPTQ_LAB_GEMM_STRIP16 || (k.kernel == 0 && M <= 16 && L.N <= 8192)))) return false;
+    pl.kernel = GEMM_STRIP16;
+    pl.mt = M <= 16 ? 1 : (M <= 32 ? 2 : 4);                  // row tiles of 16
+    pl.bk = 32;
+    pl.bm = 16 * pl.mt;
+    pl.bn = 16;
+    pl.nbm = (M + pl.bm - 1) / pl.bm;
+    pl.nbn = L.N / 16;
+    pl.waves = 16;
+    split_k_strips(L, M, k, pl, L.K / 32, 192, pl.waves, 1);
+    return true;
+}
+
+// ... and the 64-column strips of the skinny kernel (the crossovers above): up to 64 rows where N gives the tiled kernel fewer than 32 tiles of 256 columns
+static bool try_skinny(const gptq_layer_t& L, int M, const GemmKnobs& k, const gptq_tuning_t*, GemmPlan& pl) {
+    if (!(((k.kernel == GPTQ_LAB_GEMM_SKINNY) || (k.kernel == 0 && M <= 64 && (L.N + 255) / 256 < 32)) && M <= 128)) return false;
+    pl.kernel = GEMM_SKINNY;
+    pl.mt = M <= 32 ? 1 : (M <= 64 ? 2 : 4);
+    pl.bk = (L.group_size % 64 == 0 && L.K % 64 == 0) ? 64 : 32;      // = 16 * UNR
+    pl.bm = 32 * pl.mt;
+    pl.bn = 64;
+    pl.nbm = (M + pl.bm - 1) / pl.bm;
+    pl.nbn = (L.N + 63) / 64;
+    pl.waves = 8;
+    split_k_strips(L, M, k, pl, L.K / 16, 224, pl.waves * 4, pl.bk / 16);   // chunk aligned
+    return true;
+}
+
+// ---- the tiled kernel's own rules: plan_tiled (below) lays out the 128 / 64 / 32 x 256 tiles, then asks these in order ----
+// Balanced tail (see gemm_kernel, TAIL): the tiles past the last full round of 256 are cut into 2 / 4 / 8 K slices when the time model says
+// it pays -- a round costs ksteps x ~1.05 us, the tail round shrinks to ceil(tail * s / 256) / s of it, and the fix-up moves 128 KiB per
+// published slice and direction at ~3 TB/s plus ~1 us per slice on the last arrival.  Measured
+// (profiles/r03_gemm_balanced_tail_ab.log, us per layer, whole tiles -> balanced): 4096x4096 M = 2176 / 2560 / 2944 / 4224: 111 -> 87,
+// 124 -> 99, 122 -> 106, 182 -> 153; 4096x11008 M = 768 / 1024 / 1536 / 2304: 106 -> 85, 120 -> 102, 187 -> 161, 242 -> 221;
+// 11008x4096 M = 2176: 281 -> 221.  A tail the model refuses (4096x11008 at M = 2048: 176 tiles) measured 0.97 - 1.0x with two slices.
+// Lab switches 40 / 41 / 42: by the rule / off / the rule without its tile limit.
+static void tail_rule(const gptq_layer_t& L, const GemmKnobs& k, GemmPlan& pl) {
+    pl.tail = 0; pl.tail_lg = 0;
+    const long tiles = (long)pl.nbm * pl.nbn, rem = tiles % 256;
+    // every 128-row form of the kernel: 4-bit BK = 64 (act-order fp16 only in its DMA-staged form) and the BK = 32 forms of 2- / 3- / 8-bit and g32 layers
+    const bool legal = pl.mt == 4 && pl.ksplit == 1 && pl.variant == 0 && L.N % 256 == 0 &&
+                       (pl.bk == 32 || !pl.use_seq || (pl.xslot && pl.glds) || L.dtype == GPTQ_BF16);
+    const bool wanted = k.tail == GPTQ_LAB_VARIANT_TAIL_ON || k.tail == GPTQ_LAB_VARIANT_TAIL_NO_LIMIT || (k.tail == 0 && GEMM_TAIL_DEFAULT);
+    if (!(legal && wanted && tiles > 256 && (tiles <= 1024 || k.tail == GPTQ_LAB_VARIANT_TAIL_NO_LIMIT) && rem > 0)) return;      // above ~4 rounds: +5 - 7 % in one harness, -4 % in another
+    const double t_round = 1.05 * (L.K / 64.0) * (L.bits != 4 ? 1.35 : (pl.bk == 32 ? 1.1 : 1.0));      // 2- / 3- / 8-bit prefill: 660 - 770 TFLOP/s
+    double best = 0.0;
+    for (int lg = 1; lg <= 3; ++lg) {
+        const int s = 1 << lg;
+        if (pl.ksteps_total % s != 0 || (pl.ksteps_total / s) * pl.bk < 256) break;
+        const double gain = t_round * (1.0 - (double)((rem * s + 255) / 256) / s);
+        const double cost = (double)rem * (s - 1) * (2.0 * 131072.0) / 3.0e6 + 1.0 * (s - 1);      // us
+        if (gain - cost > best + 0.5) { best = gain - cost; pl.tail_lg = lg; }
     }
-    if (skinny) {
-        pl.kernel = GEMM_SKINNY;
-        pl.mt = M <= 32 ? 1 : (M <= 64 ? 2 : 4);
-        pl.bk = (L.group_size % 64 == 0 && L.K % 64 == 0) ? 64 : 32;      // = 16 * UNR
-        pl.bm = 32 * pl.mt;
-        pl.bn = 64;
-        pl.nbm = (M + pl.bm - 1) / pl.bm;
-        pl.nbn = (L.N + 63) / 64;
-        pl.waves = 8;
-        const int S = L.K / 16;
-        int ks = (tune && tune->ksplit > 0 && tune->path == 3) ? tune->ksplit : 0;
-        if (!ks) {
-            ks = 1;
-            while ((long)pl.nbm * pl.nbn * ks < 224 && S / (ks * 2) >= pl.waves * 4) ks *= 2;
-        }
-        if (ks > S) ks = S;
-        pl.ksteps_total = S;
-        pl.ksteps_per_split = (S + ks - 1) / ks;
-        pl.ksteps_per_split = (pl.ksteps_per_split + pl.bk / 16 - 1) / (pl.bk / 16) * (pl.bk / 16);   // chunk aligned
-        pl.ksplit = (S + pl.ksteps_per_split - 1) / pl.ksteps_per_split;
-        pl.workspace_bytes = pl.xperm_bytes + (pl.ksplit > 1 ? (size_t)pl.ksplit * M * L.N * sizeof(float) : 0);
-        return pl;
-    }
+    // The model is about twice too optimistic on the gain (two co-resident workgroups overlap: a round of two is shorter than two rounds); the
+    // measured gains are 0.35 - 0.75 of the predicted ones at every round count.  Accept from 7.5 % predicted = ~3 % real: 4096x11008 at
+    // M = 4096 (96 tiles x 2, 6.7 % predicted) measured +5 % in one session and -5 % in the next and stays on whole tiles.
+    if (best >= 0.075 * t_round * (double)tiles / 256.0) pl.tail = (int)rem;
+    else pl.tail_lg = 0;
+    if (pl.tail) pl.workspace_bytes = pl.xperm_bytes + ((size_t)pl.tail << pl.tail_lg) * (32 * 256 * 16);
+}
+
+// layers that carry their decode copy: weights from it, raw x by LDS DMA (gemm_wide_kernel<T, true, true>); knob 46 / 47 keep the checkpoint rows (A/B).
+// Act-order layers: the copy is made of the re-sequenced rows, so x is permuted in NATURAL order (xnat) instead of the row form's slot order -- and
+// bf16 act-order layers, which have no slot-ordered permute, get the wide tiles this way.
+static bool wide_copy_ok(const gptq_layer_t& L, const GemmKnobs& k) {
+    return L.qweight_tiled != nullptr && copy_cols(L) == GPTQ_STRIP_COLS && L.N % GPTQ_STRIP_COLS == 0 && k.wide != GPTQ_LAB_VARIANT_WIDE_ROWS && k.wide != GPTQ_LAB_VARIANT_WIDE_ROWS_ON;
+}
+// 128 x 512 tiles with a 128 x 128 tile per wave (gemm_wide.hip) where they fill the chip: whole rounds of 256, or enough rounds that the last one
+// hardly matters (tools/widelab, us per layer, 128 x 256 -> 128 x 512: M = 4096 on 4096^2 131.5 -> 122.8 (256 tiles), 11008x4096 337 -> 314 (256),
+// 4096x11008 360 -> 342 (704); M = 2048 on 4096x11008 (352 tiles = 1.4 rounds) 187 -> 214 and on 4096^2 (128 tiles) 67 -> 102: those stay here)
+static bool wide_wanted(const gptq_layer_t& L, int M, const GemmKnobs& k, const GemmPlan& pl, bool copy_ok) {
+    const long wt = (long)((M + 127) / 128) * ((L.N + 511) / 512);
+    const long rounds = (wt + 255) / 256;
+    const bool fills = wt >= 256 && (double)wt / (double)(rounds * 256) >= 0.9;
+    // lab switches (include/gptq_mi355x_lab.h): the 128 x 512 kernel off / forced; by the rule / forced on the checkpoint rows even when the layer has a decode copy
+    return k.wide != GPTQ_LAB_VARIANT_WIDE_OFF && (fills || k.wide == GPTQ_LAB_VARIANT_WIDE_ON || k.wide == GPTQ_LAB_VARIANT_WIDE_ROWS_ON) && pl.mt == 4 && pl.bk == 64 && pl.ksplit == 1 && pl.variant == 0 && k.tail == 0 &&
+           (wide_gemm_ok(L, M, pl.use_seq, pl.xslot && pl.glds) || (copy_ok && wide_gemm_ok(L, M, false, false)));
+}
+
+// The same wave tile as a stream-K partition of 128 x 256 tiles (gemm_wide_sk.hip) everywhere else from ~768 rows: every CU runs the same number of
+// 128-deep K-chunks whatever the tile count -- BASELINE config 3 (M = 2048: 256 / 688 / 256 tiles on the three Llama-7B shapes).  Decode-copy layers
+// only (act-order: x permuted in natural order).  copy_ok, wide: wide_copy_ok and wide_wanted, asked once by plan_tiled.
+static bool try_wide_sk(const gptq_layer_t& L, int M, const GemmKnobs& k, GemmPlan& pl, bool copy_ok, bool wide) {
+    if (!(pl.mt == 4 && pl.variant == 0 && k.wide == 0 && k.tail == 0 && k.wide_sk != GemmKnobs::OFF && copy_ok &&      // (wide_sk_ok has the kernel's own conditions: 3 / 4 bits, 32-wide groups too)
+          k.ksplit <= 1 && wide_sk_ok(L, M) && (k.wide_sk == GemmKnobs::ON || (!wide && wide_sk_pays(L, M)))))
+        return false;
+    pl.kernel = GEMM_WIDE_SK;
+    pl.wskg = wide_sk_geom(L, M);
+    pl.wide_tiled = true; pl.xnat = pl.use_seq; pl.xslot = false; pl.glds = true;
+    pl.bk = 64; pl.ksteps_total = L.K / 64;
+    pl.tail = 0; pl.tail_lg = 0; pl.ksplit = 1; pl.ksteps_per_split = pl.ksteps_total; pl.kg = 2;
+    pl.bn = 256; pl.nbm = pl.wskg.nbm; pl.nbn = pl.wskg.nbn;
+    pl.workspace_bytes = pl.xperm_bytes + pl.wskg.slot_bytes;
+    return true;
+}
+
+// ... and the whole-tile 128 x 512 kernel itself where wide_wanted asked for it: on the decode copy where the layer carries one (copy_ok), else on the checkpoint rows
+static bool try_wide(const gptq_layer_t& L, GemmPlan& pl, bool copy_ok, bool wide) {
+    if (!wide) return false;
+    pl.kernel = GEMM_WIDE;
+    pl.wide_tiled = copy_ok;
+    pl.xnat = pl.wide_tiled && pl.use_seq;
+    pl.tail = 0; pl.tail_lg = 0;
+    pl.bn = 512; pl.nbn = (L.N + 511) / 512;
+    pl.workspace_bytes = pl.xperm_bytes;
+    pl.kg = 1;
+    return true;
+}
+
+// 128 / 64 / 32 x 256 tiles of gemm_kernel: everything no other kernel took -- or its wide / stream-K forms, asked once the tiles are laid out
+static bool plan_tiled(const gptq_layer_t& L, int M, const GemmKnobs& k, const gptq_tuning_t*, GemmPlan& pl) {
     pl.mt = M <= 32 ? 1 : (M <= 64 ? 2 : 4);
     pl.bk = (L.bits == 4 && pl.mt == 4 && L.K % 64 == 0 && L.group_size % 64 == 0) ? 64 : 32;
-    if (tune && tune->reserved[1] == 32) pl.bk = 32;
-    pl.variant = tune ? tune->reserved[3] : 0;            // experiment knob: inner-loop schedule variant
-    // lab switches (include/gptq_mi355x_lab.h): the 128 x 512 kernel off / forced; by the rule / forced on the checkpoint rows even when the layer has a decode copy
-    const int wide_knob = (pl.variant >= GPTQ_LAB_VARIANT_WIDE_OFF && pl.variant <= GPTQ_LAB_VARIANT_WIDE_ROWS_ON) ? pl.variant : 0;
-    if (wide_knob) pl.variant = 0;
-    const int tail_knob = (pl.variant >= GPTQ_LAB_VARIANT_TAIL_ON && pl.variant <= GPTQ_LAB_VARIANT_TAIL_NO_LIMIT) ? pl.variant : 0;      // balanced tail: by the rule below / off / the rule without its tile limit
-    if (tail_knob) pl.variant = 0;
-    const int sk_knob = (pl.variant == GPTQ_LAB_VARIANT_WIDE_SK_ON || pl.variant == GPTQ_LAB_VARIANT_WIDE_SK_OFF) ? pl.variant : 0;
-    if (sk_knob) pl.variant = 0;
+    if (k.bk32) pl.bk = 32;
+    pl.variant = k.schedule;            // experiment knob: inner-loop schedule variant
     pl.bm = 32 * pl.mt;
     pl.bn = 256;
     pl.nbm = (M + pl.bm - 1) / pl.bm;
     pl.nbn = (L.N + 255) / 256;
     pl.ksteps_total = L.K / pl.bk;
-    int ks = (tune && tune->ksplit > 0 && tune->path == 3) ? tune->ksplit : 0;
+    int ks = k.ksplit;
     if (!ks) {
         ks = 1;
         const long blocks = (long)pl.nbm * pl.nbn;
@@ -2089,81 +2130,34 @@ GemmPlan plan_gemm(const gptq_layer_t& L, int M, const gptq_tuning_t* tune) {
     // act-order + the 4-bit fp16 128x256x64 kernel: the permute pre-pass delivers x in k-slot order
     pl.xslot = pl.use_seq && L.bits == 4 && L.dtype == GPTQ_F16 && pl.mt == 4 && pl.bk == 64 && (pl.variant == 0 || pl.variant == 3 || pl.variant == 5 || pl.variant == 6 || pl.variant == 7 || pl.variant == 32);
     pl.glds = pl.xslot && pl.variant != 5;            // variant 5 (experiment): register-staged x
+    tail_rule(L, k, pl);
+    const bool copy_ok = wide_copy_ok(L, k), wide = wide_wanted(L, M, k, pl, copy_ok);
+    if (try_wide_sk(L, M, k, pl, copy_ok, wide) || try_wide(L, pl, copy_ok, wide)) return true;
     // At most one tile per CU: run the tile's K range as two concurrent halves inside the workgroup (8 waves).
     const bool even_slices = pl.ksteps_total % pl.ksteps_per_split == 0 && pl.ksteps_per_split % 2 == 0 && pl.ksteps_per_split >= 4;
     const bool kg_ok = L.bits == 4 && pl.bk == 64 && pl.mt == 4 && even_slices && (pl.variant == 0 || pl.variant == 6 || pl.variant == 7 || pl.variant == 16 || pl.variant == 17 || pl.variant == 32) &&
                        (!pl.use_seq || pl.xslot == pl.glds);
-    // Balanced tail (see gemm_kernel, TAIL): the tiles past the last full round of 256 are cut into 2 / 4 / 8 K slices when the time model says
-    // it pays -- a round costs ksteps x ~1.05 us, the tail round shrinks to ceil(tail * s / 256) / s of it, and the fix-up moves 128 KiB per
-    // published slice and direction at ~3 TB/s plus ~1 us per slice on the last arrival.  Measured
-    // (profiles/r03_gemm_balanced_tail_ab.log, us per layer, whole tiles -> balanced): 4096x4096 M = 2176 / 2560 / 2944 / 4224: 111 -> 87,
-    // 124 -> 99, 122 -> 106, 182 -> 153; 4096x11008 M = 768 / 1024 / 1536 / 2304: 106 -> 85, 120 -> 102, 187 -> 161, 242 -> 221;
-    // 11008x4096 M = 2176: 281 -> 221.  A tail the model refuses (4096x11008 at M = 2048: 176 tiles) measured 0.97 - 1.0x with two slices.
-    pl.tail = 0; pl.tail_lg = 0;
-    {
-        const long tiles = (long)pl.nbm * pl.nbn, rem = tiles % 256;
-        // every 128-row form of the kernel: 4-bit BK = 64 (act-order fp16 only in its DMA-staged form) and the BK = 32 forms of 2- / 3- / 8-bit and g32 layers
-        const bool legal = pl.mt == 4 && pl.ksplit == 1 && pl.variant == 0 && L.N % 256 == 0 &&
-                           (pl.bk == 32 || !pl.use_seq || (pl.xslot && pl.glds) || L.dtype == GPTQ_BF16);
-        const bool wanted = tail_knob == GPTQ_LAB_VARIANT_TAIL_ON || tail_knob == GPTQ_LAB_VARIANT_TAIL_NO_LIMIT || (tail_knob == 0 && GEMM_TAIL_DEFAULT);
-        if (legal && wanted && tiles > 256 && (tiles <= 1024 || tail_knob == GPTQ_LAB_VARIANT_TAIL_NO_LIMIT) && rem > 0) {      // above ~4 rounds: +5 - 7 % in one harness, -4 % in another
-            const double t_round = 1.05 * (L.K / 64.0) * (L.bits != 4 ? 1.35 : (pl.bk == 32 ? 1.1 : 1.0));      // 2- / 3- / 8-bit prefill: 660 - 770 TFLOP/s
-            double best = 0.0;
-            for (int lg = 1; lg <= 3; ++lg) {
-                const int s = 1 << lg;
-                if (pl.ksteps_total % s != 0 || (pl.ksteps_total / s) * pl.bk < 256) break;
-                const double gain = t_round * (1.0 - (double)((rem * s + 255) / 256) / s);
-                const double cost = (double)rem * (s - 1) * (2.0 * 131072.0) / 3.0e6 + 1.0 * (s - 1);      // us
-                if (gain - cost > best + 0.5) { best = gain - cost; pl.tail_lg = lg; }
-            }
-            // The model is about twice too optimistic on the gain (two co-resident workgroups overlap: a round of two is shorter than two rounds); the
-            // measured gains are 0.35 - 0.75 of the predicted ones at every round count.  Accept from 7.5 % predicted = ~3 % real: 4096x11008 at
-            // M = 4096 (96 tiles x 2, 6.7 % predicted) measured +5 % in one session and -5 % in the next and stays on whole tiles.
-            if (best >= 0.075 * t_round * (double)tiles / 256.0) pl.tail = (int)rem;
-            else pl.tail_lg = 0;
-        }
-        if (pl.tail) pl.workspace_bytes = pl.xperm_bytes + ((size_t)pl.tail << pl.tail_lg) * (32 * 256 * 16);
-    }
-    // 128 x 512 tiles with a 128 x 128 tile per wave (gemm_wide.hip) where they fill the chip: whole rounds of 256, or enough rounds that the last one
-    // hardly matters (tools/widelab, us per layer, 128 x 256 -> 128 x 512: M = 4096 on 4096^2 131.5 -> 122.8 (256 tiles), 11008x4096 337 -> 314 (256),
-    // 4096x11008 360 -> 342 (704); M = 2048 on 4096x11008 (352 tiles = 1.4 rounds) 187 -> 214 and on 4096^2 (128 tiles) 67 -> 102: those stay here)
-    {
-        const long wt = (long)((M + 127) / 128) * ((L.N + 511) / 512);
-        const long rounds = (wt + 255) / 256;
-        const bool fills = wt >= 256 && (double)wt / (double)(rounds * 256) >= 0.9;
-        // layers that carry their decode copy: weights from it, raw x by LDS DMA (gemm_wide_kernel<T, true, true>); knob 46 / 47 keep the checkpoint rows (A/B).
-        // Act-order layers: the copy is made of the re-sequenced rows, so x is permuted in NATURAL order (xnat) instead of the row form's slot order -- and
-        // bf16 act-order layers, which have no slot-ordered permute, get the wide tiles this way.
-        const bool copy_ok = L.qweight_tiled != nullptr && copy_cols(L) == GPTQ_STRIP_COLS && L.N % GPTQ_STRIP_COLS == 0 && wide_knob != GPTQ_LAB_VARIANT_WIDE_ROWS && wide_knob != GPTQ_LAB_VARIANT_WIDE_ROWS_ON;
-        const bool wide = wide_knob != GPTQ_LAB_VARIANT_WIDE_OFF && (fills || wide_knob == GPTQ_LAB_VARIANT_WIDE_ON || wide_knob == GPTQ_LAB_VARIANT_WIDE_ROWS_ON) && pl.mt == 4 && pl.bk == 64 && pl.ksplit == 1 && pl.variant == 0 && tail_knob == 0 &&
-                  (wide_gemm_ok(L, M, pl.use_seq, pl.xslot && pl.glds) || (copy_ok && wide_gemm_ok(L, M, false, false)));
-        // The same wave tile as a stream-K partition of 128 x 256 tiles (gemm_wide_sk.hip) everywhere else from ~768 rows: every CU runs the same number of
-        // 128-deep K-chunks whatever the tile count -- BASELINE config 3 (M = 2048: 256 / 688 / 256 tiles on the three Llama-7B shapes).  Decode-copy layers
-        // only (act-order: x permuted in natural order).
-        if (pl.mt == 4 && pl.variant == 0 && wide_knob == 0 && tail_knob == 0 && sk_knob != GPTQ_LAB_VARIANT_WIDE_SK_OFF && copy_ok &&      // (wide_sk_ok has the kernel's own conditions: 3 / 4 bits, 32-wide groups too)
-            !(tune && tune->ksplit > 0 && tune->path == 3 && tune->ksplit != 1) && wide_sk_ok(L, M) &&
-            (sk_knob == GPTQ_LAB_VARIANT_WIDE_SK_ON || (!wide && wide_sk_pays(L, M)))) {
-            pl.kernel = GEMM_WIDE_SK;
-            pl.wskg = wide_sk_geom(L, M);
-            pl.wide_tiled = true; pl.xnat = pl.use_seq; pl.xslot = false; pl.glds = true;
-            pl.bk = 64; pl.ksteps_total = L.K / 64;
-            pl.tail = 0; pl.tail_lg = 0; pl.ksplit = 1; pl.ksteps_per_split = pl.ksteps_total; pl.kg = 2;
-            pl.bn = 256; pl.nbm = pl.wskg.nbm; pl.nbn = pl.wskg.nbn;
-            pl.workspace_bytes = pl.xperm_bytes + pl.wskg.slot_bytes;
-            return pl;
-        }
-        if (wide) {
-            pl.kernel = GEMM_WIDE;
-            pl.wide_tiled = copy_ok;
-            pl.xnat = pl.wide_tiled && pl.use_seq;
-            pl.tail = 0; pl.tail_lg = 0;
-            pl.bn = 512; pl.nbn = (L.N + 511) / 512;
-            pl.workspace_bytes = pl.xperm_bytes;
-            pl.kg = 1;
-            return pl;
-        }
-    }
     pl.kg = (kg_ok && pl.tail == 0 && pl.variant != 6 && pl.variant != 16 && ((long)pl.nbm * pl.nbn * pl.ksplit <= 256 || pl.variant == 7 || pl.variant == 17 || pl.variant == 32)) ? 2 : 1;   // 16 / 17: gemmlab timeline variants (one / two K groups); 32: ping-pong
+    return true;
+}
+
+// The ladder of a dense call above the decode rows: the first rung that takes the call plans it.  Runs on every dense call, so the rungs are inlined
+// (flatten): the inliner rates every call behind a few `||` as cold and leaves it out of line, which cost a plan that ends in plan_tiled 11 - 16 ns of ~300
+// (profiles/gemm_plan_host_cost.log)
+__attribute__((flatten)) GemmPlan plan_gemm(const gptq_layer_t& L, int M, const gptq_tuning_t* tune) {
+    GemmPlan pl{};
+    const GemmKnobs k = GemmKnobs::decode(tune);
+    const int kpu = unit_vals(L.bits);
+    const bool f32 = L.dtype == GPTQ_F32, seq = (L.g_idx == nullptr) || (L.qweight_seq != nullptr && L.perm != nullptr);
+    pl.kernel = f32 ? GEMM_F32 : GEMM_TILED;
+    pl.supported = seq && (L.group_size % kpu == 0) && (L.K % 32 == 0) && (L.N % 32 == 0) &&
+                   (f32 || ((L.dtype == GPTQ_F16 || L.dtype == GPTQ_BF16) && (L.group_size % 32 == 0) && ((size_t)L.K * 2 <= 64 * 1024 || L.g_idx == nullptr)));
+    if (!pl.supported) return pl;
+    pl.use_seq = (L.g_idx != nullptr);
+    pl.xperm_bytes = pl.use_seq ? align_up((size_t)M * L.K * (f32 ? 4 : 2), 256) : 0;
+    if (!(plan_f32(L, M, k, tune, pl) || try_int2_copy(L, M, k, tune, pl) || try_panel(L, M, k, tune, pl) || try_rows(L, M, k, tune, pl) ||
+          try_mid(L, M, k, tune, pl) || try_stream64(L, M, k, tune, pl) || try_strip16(L, M, k, tune, pl) || try_skinny(L, M, k, tune, pl)))
+        plan_tiled(L, M, k, tune, pl);      // takes whatever is left
     return pl;
 }
 

@@ -3,8 +3,43 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include "../../include/gptq_mi355x.h"
+#include "../../include/gptq_mi355x_lab.h"
 
 namespace gptq {
+
+// The lab knobs of a dense GEMM call (gptq_mi355x_lab.h), decoded ONCE: plan_gemm's rules and the group routes of capi.hip read these names, never tuning.path,
+// .ksplit or .reserved[2 / 3] themselves.  (The family planners plan_rows / plan_panel / plan_mid / plan_stream64 take the tuning itself: reserved[0 / 1] mean
+// something else to each of them, and plan_mid / plan_stream64, which also serve the group routes, read their own forced K split.)
+struct GemmKnobs {
+    enum Switch { RULE, ON, OFF };      // the planner's rule / the kernel wherever it is legal / never
+    bool forced;                        // tuning.path = GPTQ_PATH_GEMM
+    bool variant_set;                   // reserved[GPTQ_LAB_GEMM_VARIANT] != 0, whatever it selects
+    int kernel;                         // reserved[GPTQ_LAB_GEMM_KERNEL]: 0 or GPTQ_LAB_GEMM_*
+    int ksplit;                         // the forced K split (path = GPTQ_PATH_GEMM only), or 0
+    bool bk32;                          // GPTQ_LAB_OPT_GEMM_BK32
+    Switch rows, panel, wide_sk;        // GPTQ_LAB_VARIANT_ROWS_* / PANEL_* / WIDE_SK_*
+    int wide, tail;                     // 0, or the GPTQ_LAB_VARIANT_WIDE_* / GPTQ_LAB_VARIANT_TAIL_* switch that is set
+    int schedule;                       // what is left for the tiled kernel's inner loop (pl.variant): reserved[3] unless it was a wide / tail / wide-sk switch
+    // the planner is free to choose: no kernel forced, and no variant under path = GPTQ_PATH_GEMM
+    bool planner_free() const { return (!forced || !variant_set) && kernel == 0; }
+    static GemmKnobs decode(const gptq_tuning_t* t) {
+        GemmKnobs k{};
+        if (!t) return k;
+        const int v = t->reserved[GPTQ_LAB_GEMM_VARIANT];
+        k.forced = t->path == GPTQ_PATH_GEMM;
+        k.variant_set = v != 0;
+        k.kernel = t->reserved[GPTQ_LAB_GEMM_KERNEL];
+        k.ksplit = (k.forced && t->ksplit > 0) ? t->ksplit : 0;
+        k.bk32 = t->reserved[GPTQ_LAB_OPT] == GPTQ_LAB_OPT_GEMM_BK32;
+        k.rows = v == GPTQ_LAB_VARIANT_ROWS_ON ? ON : (v == GPTQ_LAB_VARIANT_ROWS_OFF ? OFF : RULE);
+        k.panel = v == GPTQ_LAB_VARIANT_PANEL_ON ? ON : (v == GPTQ_LAB_VARIANT_PANEL_OFF ? OFF : RULE);
+        k.wide_sk = v == GPTQ_LAB_VARIANT_WIDE_SK_ON ? ON : (v == GPTQ_LAB_VARIANT_WIDE_SK_OFF ? OFF : RULE);
+        k.wide = (v >= GPTQ_LAB_VARIANT_WIDE_OFF && v <= GPTQ_LAB_VARIANT_WIDE_ROWS_ON) ? v : 0;
+        k.tail = (v >= GPTQ_LAB_VARIANT_TAIL_ON && v <= GPTQ_LAB_VARIANT_TAIL_NO_LIMIT) ? v : 0;
+        k.schedule = (k.wide || k.tail || k.wide_sk != RULE) ? 0 : v;
+        return k;
+    }
+};
 
 // The strip width of the layer's decode copy (0: none) -- tiled_cols without the opt-in flag it may carry; every comparison with GPTQ_STRIP_COLS goes through here.
 inline int copy_cols(const gptq_layer_t& L) { return GPTQ_COPY_COLS(L.tiled_cols); }
@@ -283,7 +318,8 @@ bool dense_rows_int2_ok(const gptq_layer_t& L, int M);
 RowsPlan plan_dense_rows_int2(const gptq_layer_t& L, int M);
 hipError_t launch_dense_rows_int2(const gptq_layer_t& L, const void* x, void* out, int M, const RowsPlan& pl, hipStream_t st);
 // 0: the unflagged plan; GEMM_ROWS / GEMM_PANEL: what the planner, left to itself, gives a flagged 2-bit layer at M rows (gemm.hip; the rule of the 4-bit twin)
-int dense_int2_choice(const gptq_layer_t& L, int M);
+// (k: the call's lab knobs -- a forced kernel or variant leaves nothing to choose; the default is a call without tuning)
+int dense_int2_choice(const gptq_layer_t& L, int M, const GemmKnobs& k = GemmKnobs{});
 // ... and its row gather (moe_gather_rows_kernel) for the prefill path: out[plane][r] = in[src(r)] through the perm of expert e(r)'s entry of projection
 // `plane` of `table` (entries without a perm: a copy); src(r) = row_assign[r] / topk (topk > 0) or r (topk = 0).  R <= 65535 (a grid dimension).
 hipError_t launch_moe_gather_rows(const void* table, int planes, int topk, const int64_t* idx, const int* row_assign, const int* offsets, const void* in,

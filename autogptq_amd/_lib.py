@@ -46,6 +46,7 @@ EXPORTS = (
     "gptq_adapter_route_bytes", "gptq_adapter_route", "gptq_adapter_rows_apply", "gptq_describe_adapter_rows_plan",
     "gptq_moe_router", "gptq_describe_moe_router_plan", "gptq_moe_router_grouped", "gptq_describe_moe_router_grouped_plan",
     "gptq_moe_shared_decode_workspace_bytes", "gptq_moe_shared_decode_forward", "gptq_describe_moe_shared_decode_plan", "gptq_moe_shared_combine",
+    "gptq_act_int8_workspace_bytes", "gptq_act_quant", "gptq_gemm_a8", "gptq_forward_a8", "gptq_describe_a8_plan",
 )
 WS_HEADER_BYTES = 65536
 STRIP_COLS = 16          # GPTQ_STRIP_COLS: columns per strip of the decode copy (gptq_prepack_decode)
@@ -275,6 +276,12 @@ def load() -> ctypes.CDLL:
     lib.gptq_peer_publish.argtypes = [POINTER(GptqPeerGroup), c_void_p]
     lib.gptq_forward_scatter.argtypes = [LP, c_void_p, c_int, POINTER(GptqPeerGroup), c_void_p, c_size_t, c_void_p]
     lib.gptq_forward_gather.argtypes = [LP, c_void_p, c_void_p, c_int, POINTER(GptqPeerGroup), ctypes.c_uint32, c_void_p, c_size_t, c_void_p]
+    lib.gptq_act_int8_workspace_bytes.restype = c_size_t
+    lib.gptq_act_int8_workspace_bytes.argtypes = [LP, c_int]
+    lib.gptq_act_quant.argtypes = [LP, c_void_p, c_int, c_void_p, c_size_t, c_void_p]
+    lib.gptq_gemm_a8.argtypes = [LP, c_void_p, c_void_p, c_int, c_void_p]
+    lib.gptq_forward_a8.argtypes = [LP, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]
+    lib.gptq_describe_a8_plan.argtypes = [LP, c_int, c_char_p, c_size_t]
     for name in EXPORTS:
         if name not in ("gptq_last_error", "gptq_status_string", "gptq_workspace_bytes", "gptq_workspace_bytes_ex",
                         "gptq_workspace_bytes_max", "gptq_workspace_bytes_multi", "gptq_workspace_bytes_multi_ex",
@@ -282,7 +289,7 @@ def load() -> ctypes.CDLL:
                         "gptq_moe_decode_table_bytes", "gptq_moe_decode_workspace_bytes", "gptq_moe_batch_workspace_bytes",
                         "gptq_moe_prefill_workspace_bytes",
                         "gptq_moe_grad_table_bytes", "gptq_moe_backward_workspace_bytes", "gptq_lora_backward_workspace_bytes",
-                        "gptq_moe_shared_decode_workspace_bytes"):
+                        "gptq_moe_shared_decode_workspace_bytes", "gptq_act_int8_workspace_bytes"):
             getattr(lib, name).restype = c_int
     got = lib.gptq_abi_version()
     if got != ABI_VERSION:
@@ -414,6 +421,12 @@ def describe_moe_router_grouped_plan(T: int, H: int, E: int, topk: int, n_group:
     """What gptq_moe_router_grouped would run: path=router_grouped with its row regime, grid, LDS bytes and groups, or path=none with the reason
     (host-only query)."""
     return _describe("gptq_describe_moe_router_grouped_plan", T, H, E, topk, n_group, topk_group, dtype, flags)
+
+
+def describe_a8_plan(layer: "GptqLayer", M: int) -> dict:
+    """What gptq_forward_a8 would run for (layer, M): path=act_int8 with its tile, group mode, zero-point form, grids and workspace, or path=none with the
+    reason (host-only query)."""
+    return _describe("gptq_describe_a8_plan", ctypes.byref(layer), M)
 
 
 def describe_lora_plan(loras, M: int) -> dict:

@@ -93,6 +93,7 @@ class LoraBankQuantLinear(nn.Module):
         if dtype not in (torch.float16, torch.bfloat16):
             raise ValueError(f"LoraBankQuantLinear: the adapter kernels take fp16 / bf16 layers, this one is {dtype}")
         self.base = base
+        base._a8_hold, base._a8_rows = True, 0      # under an adapter the base keeps its 16-bit kernels, whatever post_init(act_int8=...) is asked later
         self.r, self.num_slots = int(r), int(num_slots)
         self.in_features, self.out_features = base.infeatures, base.outfeatures
         if self.in_features % 32 or self.out_features % 16:

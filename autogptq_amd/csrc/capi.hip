@@ -1747,6 +1747,58 @@ int gptq_describe_plan(const gptq_layer_t* L, int M, const gptq_tuning_t* tune, 
     return GPTQ_OK;
 }
 
+// ---- W4A8 (opt-in): int8 activations on the i8 matrix core (act_int8.hip) ------------------------------------------------------
+// One checker for the five entry points: the layer alone decides (no planner, no tuning); everything else is declined with the reason.
+static int a8_plan(const gptq_layer_t* L, int M, A8Plan* pl) {
+    if (!L) return fail(GPTQ_ERR_NULL, "layer is NULL");
+    *pl = plan_a8(*L, M);
+    if (!pl->ok) return fail(GPTQ_ERR_UNSUPPORTED, "%s (bits=%d dtype=%d group_size=%d K=%d N=%d M=%d)", pl->why, L->bits, L->dtype, L->group_size, L->K, L->N, M);
+    return GPTQ_OK;
+}
+
+size_t gptq_act_int8_workspace_bytes(const gptq_layer_t* L, int M) {
+    A8Plan pl;
+    return a8_plan(L, M, &pl) ? 0 : pl.bytes;
+}
+
+int gptq_act_quant(const gptq_layer_t* L, const void* x, int M, void* ws, size_t ws_bytes, void* stream) {
+    A8Plan pl;
+    if (int rc = a8_plan(L, M, &pl)) return rc;
+    if (!x || !ws) return fail(GPTQ_ERR_NULL, "x/workspace must be non-NULL");
+    if (int rc = check_align(x, nullptr, ws)) return rc;
+    if (ws_bytes < pl.bytes) return fail(GPTQ_ERR_WORKSPACE, "workspace of %zu bytes, gptq_act_int8_workspace_bytes() = %zu", ws_bytes, pl.bytes);
+    hipError_t e = launch_act_quant(*L, pl, x, M, ws, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "gptq_act_quant launch");
+    return GPTQ_OK;
+}
+
+int gptq_gemm_a8(const gptq_layer_t* L, const void* ws, void* out, int M, void* stream) {
+    A8Plan pl;
+    if (int rc = a8_plan(L, M, &pl)) return rc;
+    if (!ws || !out) return fail(GPTQ_ERR_NULL, "workspace/out must be non-NULL");
+    if (int rc = check_align(nullptr, out, ws)) return rc;
+    hipError_t e = launch_gemm_a8(*L, pl, ws, out, M, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "gptq_gemm_a8 launch");
+    return GPTQ_OK;
+}
+
+int gptq_forward_a8(const gptq_layer_t* L, const void* x, void* out, int M, void* ws, size_t ws_bytes, void* stream) {
+    if (!out) return fail(GPTQ_ERR_NULL, "out must be non-NULL");
+    if (int rc = check_align(x, out, ws)) return rc;
+    if (int rc = gptq_act_quant(L, x, M, ws, ws_bytes, stream)) return rc;
+    return gptq_gemm_a8(L, ws, out, M, stream);
+}
+
+int gptq_describe_a8_plan(const gptq_layer_t* L, int M, char* out, size_t out_bytes) {
+    if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out must be non-NULL");
+    out[0] = 0;
+    A8Plan pl;
+    if (a8_plan(L, M, &pl)) return describe_decline(out, out_bytes, "none");
+    snprintf(out, out_bytes, "path=act_int8 tile=128x128 waves=4 mfma=32x32x32_i8 group_mode=%s zero=signed_bytes tiles=%dx%d chunks=%d groups=%d wg_quant=%d workspace=%zu launches=2",
+             pl.gm == 2 ? "g32" : (pl.gm == 1 ? "g64" : (pl.groups == 1 ? "one" : "g128")), pl.npm, pl.npn, pl.chunks, pl.groups, M < 4096 ? M : 4096, pl.bytes);
+    return GPTQ_OK;
+}
+
 static int awq_shape_check(int K, int N, int group_size) {
     if (K <= 0 || N <= 0 || group_size <= 0) return fail(GPTQ_ERR_SHAPE, "K (%d), N (%d), group_size (%d) must be > 0", K, N, group_size);
     if (K % 8 || N % 8) return fail(GPTQ_ERR_SHAPE, "K (%d) and N (%d) must be multiples of 8 (4-bit words)", K, N);

@@ -412,6 +412,18 @@ hipError_t launch_awq_repack(const uint32_t* aq, const uint32_t* az, int K, int 
 hipError_t launch_silu_mul(const void* y, void* out, int M, int N, int dtype, int act, hipStream_t st);      // act: GPTQ_EPI_SILU_MUL / GPTQ_EPI_GELU_TANH_MUL (gated_act), or RELU / GELU / GELU_TANH (plain_act) with y == out: all M N elements in place
 hipError_t launch_permute_rows16(const void* x, const int32_t* perm, int M, int K, void* x_out, hipStream_t st, bool slot_order = false);
 hipError_t launch_permute_columns(const void* x, const int32_t* perm, int M, int K, int dtype, void* x_out, hipStream_t st);
+// act_int8.hip: W4A8 (opt-in) -- per-token int8 activations (act_quant_kernel) and the i8 matrix-core GEMM on the 4-bit decode copy (gemm_a8_kernel)
+struct A8Plan {
+    bool ok;
+    const char* why;         // !ok: the reason
+    int gm, gshift;          // group mode (0: 128-multiples / one group, 1: 64, 2: 32) and, for mode 0, group of chunk c = c >> gshift
+    int groups, chunks, Kp;  // Kp = 128 chunks: the stored row length of xq
+    size_t off_xq, bytes;    // workspace: sx [M] fp32 at 0, xq [M][Kp] at off_xq = a256(4 M); bytes = off_xq + a256(M Kp)
+    int npm, npn;            // 128 x 128 tiles
+};
+A8Plan plan_a8(const gptq_layer_t& L, int M);
+hipError_t launch_act_quant(const gptq_layer_t& L, const A8Plan& pl, const void* x, int M, void* ws, hipStream_t st);
+hipError_t launch_gemm_a8(const gptq_layer_t& L, const A8Plan& pl, const void* ws, void* out, int M, hipStream_t st);
 // peer.hip: direct peer-store all-gather (y_local / out may be NULL: scatter-only / collect-only)
 hipError_t launch_peer_scatter(const gptq_peer_group_t& pg, const void* y_local, int M, int n_local, int dtype, hipStream_t st);
 hipError_t launch_peer_publish(const gptq_peer_group_t& pg, hipStream_t st);

@@ -262,7 +262,13 @@ __global__ void __launch_bounds__(256) resequence_kernel(const unsigned* __restr
 //   3-bit  word j of the lane's three: pair 5j + i (i = 0..4) = (k 2p, k 2p + 1) at bit 3i of the low / high 16 bits; bit 15 / 31 = bit j of k30 / k31
 //   2-bit  (round 6) a lane holds TWO words = 32 k: word w holds pair p (p = 0..7) = (k 16w + 2p, k 16w + 2p + 1) at bit 2p of its low / high 16 bits
 // (bits is a run-time, workgroup-uniform argument: one instantiation)
-__global__ void __launch_bounds__(256) prepack_decode_weights_kernel(const unsigned* __restrict__ q, int K, int N, int chunks, int bits, unsigned* __restrict__ out) {
+// One code object for the two passes of gptq_prepack_decode (the library's kernel budget): scales != nullptr, launch-uniform, selects the CONSTANTS pass
+// (prepack_decode_consts_body below: its own grid, q = qzeros, out = qconst_tiled, G and zero_mode as named; K and chunks are not read).
+__device__ __forceinline__ void prepack_decode_consts_body(const unsigned* __restrict__ qzeros, const unsigned short* __restrict__ scales, int G, int N,
+                                                           int bits, int zero_mode, unsigned char* __restrict__ out);
+__global__ void __launch_bounds__(256) prepack_decode_weights_kernel(const unsigned* __restrict__ q, int K, int N, int chunks, int bits, unsigned* __restrict__ out,
+                                                                     const unsigned short* __restrict__ scales, int G, int zero_mode) {
+    if (scales) return prepack_decode_consts_body(q, scales, G, N, bits, zero_mode, (unsigned char*)out);
     const int WPL = bits == 3 ? 3 : (bits == 2 ? 2 : 4), KPL = bits == 8 ? 16 : 32, CKE = 4 * KPL;
     const int UV = unit_vals(bits), UWD = unit_words(bits);
     const int c = blockIdx.x, s = blockIdx.y, t = threadIdx.x;
@@ -344,8 +350,8 @@ __global__ void __launch_bounds__(256) unprepack_decode_weights_kernel(const uns
 }
 
 // one thread = one (strip, group, column): 2 bytes of scale (bit copy) + the zero-point as used (1 byte; 2 bytes at 8 bits, where it reaches 256)
-__global__ void __launch_bounds__(256) prepack_decode_consts_kernel(const unsigned* __restrict__ qzeros, const unsigned short* __restrict__ scales, int G, int N,
-                                                                    int bits, int zero_mode, unsigned char* __restrict__ out) {
+__device__ __forceinline__ void prepack_decode_consts_body(const unsigned* __restrict__ qzeros, const unsigned short* __restrict__ scales, int G, int N,
+                                                           int bits, int zero_mode, unsigned char* __restrict__ out) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x, g = blockIdx.y;
     if (n >= N) return;
     const int s = n >> 4, col = n & 15, rec_bytes = bits == 8 ? 64 : 48;
@@ -469,11 +475,11 @@ hipError_t launch_prepack_decode(const uint32_t* qweight, const uint32_t* qzeros
     const dim3 grid(chunks, N / 16);
     if (bits != 2 && bits != 3 && bits != 4 && bits != 8) return hipErrorInvalidValue;
     const int threads = bits == 3 ? 192 : (bits == 2 ? 128 : 256);                // 4 k-slots x WPL words x 16 columns
-    hipLaunchKernelGGL(prepack_decode_weights_kernel, grid, dim3(threads), 0, st, qweight, K, N, chunks, bits, tiled_out);
+    hipLaunchKernelGGL(prepack_decode_weights_kernel, grid, dim3(threads), 0, st, qweight, K, N, chunks, bits, tiled_out, (const unsigned short*)nullptr, 0, 0);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(prepack_decode_consts_kernel, dim3((N + 255) / 256, G), dim3(256), 0, st, qzeros, (const unsigned short*)scales, G, N, bits, zero_mode,
-                       (unsigned char*)const_out);
+    hipLaunchKernelGGL(prepack_decode_weights_kernel, dim3((N + 255) / 256, G), dim3(256), 0, st, qzeros, 0, N, 0, bits, (unsigned*)const_out,
+                       (const unsigned short*)scales, G, zero_mode);
     return hipGetLastError();
 }
 
@@ -525,7 +531,11 @@ __global__ void __launch_bounds__(256) awq_unpack_kernel(const unsigned* __restr
 }
 
 // unpack_awq + pack_from_tensors as one integer pass: 8 AWQ rows x 1 word column -> 1 GPTQ packed row x 8 columns
-__global__ void __launch_bounds__(256) awq_repack_kernel(const unsigned* __restrict__ aq, int K, int N, unsigned* __restrict__ qweight) {
+// One code object for the two passes of gptq_awq_repack (the library's kernel budget): zeros_total > 0, launch-uniform, selects the QZEROS pass
+// (awq_repack_zeros_body below: its own grid, aq = the AWQ qzeros, qweight = the GPTQ qzeros, zeros_total words; K and N are not read).
+__device__ __forceinline__ void awq_repack_zeros_body(const unsigned* __restrict__ az, int total, unsigned* __restrict__ qzeros);
+__global__ void __launch_bounds__(256) awq_repack_kernel(const unsigned* __restrict__ aq, int K, int N, unsigned* __restrict__ qweight, int zeros_total) {
+    if (zeros_total > 0) return awq_repack_zeros_body(aq, zeros_total, qweight);
     const int NW = N / 8;
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= NW) return;
@@ -548,7 +558,7 @@ __global__ void __launch_bounds__(256) awq_repack_kernel(const unsigned* __restr
 }
 
 // GPTQ qzeros word (g, c): field i = (z[g, 8c + i] - 1) & 15   (pack_from_tensors, _utils.py:679-680)
-__global__ void __launch_bounds__(256) awq_repack_zeros_kernel(const unsigned* __restrict__ az, int total, unsigned* __restrict__ qzeros) {
+__device__ __forceinline__ void awq_repack_zeros_body(const unsigned* __restrict__ az, int total, unsigned* __restrict__ qzeros) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= total) return;
     const unsigned q = az[t];
@@ -570,9 +580,9 @@ hipError_t launch_awq_repack(const uint32_t* aq, const uint32_t* az, int K, int 
                              hipStream_t st) {
     const int NW = N / 8, R = K / 8;
     dim3 grid((NW + 255) / 256, R < 4096 ? R : 4096), block(256);
-    hipLaunchKernelGGL(awq_repack_kernel, grid, block, 0, st, aq, K, N, qweight);
+    hipLaunchKernelGGL(awq_repack_kernel, grid, block, 0, st, aq, K, N, qweight, 0);
     const int total = (K / group_size) * NW;
-    hipLaunchKernelGGL(awq_repack_zeros_kernel, dim3((total + 255) / 256), dim3(256), 0, st, az, total, qzeros);
+    hipLaunchKernelGGL(awq_repack_kernel, dim3((total + 255) / 256), dim3(256), 0, st, az, K, N, qzeros, total);
     return hipGetLastError();
 }
 

@@ -59,6 +59,7 @@ class LoraQuantLinear(nn.Module):
         if r <= 0:
             raise ValueError(f"r must be positive, got {r}")
         self.base = base
+        base._a8_hold, base._a8_rows = True, 0      # under an adapter the base keeps its 16-bit kernels, whatever post_init(act_int8=...) is asked later
         self.r, self.lora_alpha, self.lora_dropout = int(r), lora_alpha, float(lora_dropout)
         self.scaling = lora_alpha / r
         self.in_features, self.out_features = base.infeatures, base.outfeatures

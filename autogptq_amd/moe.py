@@ -225,7 +225,7 @@ class QuantMoEExperts(nn.Module):
                 built, extra = copy, 0
                 for e in range(self.num_experts):
                     for l in self[e].layers():
-                        l.post_init(tiled=copy, release_checkpoint_layout=False)
+                        l.post_init(tiled=copy, release_checkpoint_layout=False, act_int8=False)      # (int8 activations are a dense-layer option)
                         if l._qweight_tiled is not None:
                             extra += l._qweight_tiled.numel() + l._qconst_tiled.numel()
             gate, up, down = self.projections()

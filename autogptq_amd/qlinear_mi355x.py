@@ -138,6 +138,15 @@ class QuantLinear(nn.Module):
     # forms measured faster (5 .. 16 rows of wide layers, 128 / 256+ rows: include/gptq_mi355x.h).  post_init(low_bit_rows=True) /
     # autogptq_post_init(..., low_bit_rows=True) set it per call.  Off: every plan is what it was.  Changes nothing for 3-, 4- and 8-bit layers.
     LOW_BIT_ROWS = False
+    # Opt-in, CHANGES NUMERICS: W4A8.  A plain forward call of ACT_INT8_MIN_ROWS rows and more on a supported layer (4 bits, fp16 / bf16, decode copy, no epilogue)
+    # rounds each row of x to int8 with its own scale and multiplies on the i8 matrix core (gptq_forward_a8: csrc/act_int8.hip; the scheme of QQQ / QServe).
+    # post_init(act_int8=True) / autogptq_post_init(..., act_int8=True) set it per call.  "Plain" = QuantLinear.forward without a tuning, on a call that records
+    # no autograd node (grad mode off, or x does not require grad).  Everything else keeps the 16-bit kernels: calls that record a node, forward_multi and
+    # mlp_forward (their layer-by-layer fallbacks included: they pass act_int8=False), layers under a LoRA / adapter-bank wrapper or a tensor-parallel wrapper
+    # (the wrappers set _a8_hold: post_init then leaves the path off), the expert layers of QuantMoEExperts.  128 = the kernel's tile height (below it a tile is mostly padding); where the path pays is in
+    # profiles/act_int8_ab.log, not in this default.  Off: every plan, kernel and result is what it was.
+    ACT_INT8 = False
+    ACT_INT8_MIN_ROWS = 128
     _extra_bytes_logged = False
 
     def __init__(
@@ -201,6 +210,8 @@ class QuantLinear(nn.Module):
         self._qweight_tiled = self._qconst_tiled = None    # the decode copy (post_init), never part of state_dict
         self._released = False        # post_init(release_checkpoint_layout=True): qweight lives in pinned host memory, rows are rebuilt on demand
         self._ws_need = {}            # M -> workspace bytes
+        self._a8_hold = False         # set by the LoRA wrappers around this layer: the int8-activation path stays off
+        self._a8_rows = 0             # post_init(act_int8=True) on a layer the int8-activation path takes: its first row count; 0 = off
         self._ws0_mask = 0            # bit M set: M rows (1..63) are known to need no workspace -- what the C++ fast path (cext/fastfwd.cpp) serves; 0 = never
         self.act_order = None         # resolved by post_init
 
@@ -222,6 +233,7 @@ class QuantLinear(nn.Module):
         self._qweight_tiled = self._qconst_tiled = None
         self._ws_need = {}
         self._ws0_mask = 0
+        self._a8_rows = 0
         self._rows_need = {}
         object.__setattr__(self, "_parts", None)
 
@@ -246,7 +258,7 @@ class QuantLinear(nn.Module):
         return _lib.ZERO_WRAP
 
     # ------------------------------------------------------------------ post_init
-    def post_init(self, temp_dq=None, tiled=None, release_checkpoint_layout=None, low_bit_rows=None):
+    def post_init(self, temp_dq=None, tiled=None, release_checkpoint_layout=None, low_bit_rows=None, act_int8=None, act_int8_min_rows=None):
         """Snapshot device pointers and, for act-order layers, derive the group-sorted copy of
         qweight plus the x permutation (side buffers; qweight itself is never modified -- the
         reference's exllama backends overwrite it in place, q4_matrix.cu:160)."""
@@ -341,6 +353,15 @@ class QuantLinear(nn.Module):
         self._dt_code = _lib.fwd.dtype_code(self.scales) if _lib.fwd is not None else -1
         self._released = False
         self._rows_need = {}
+        self._perm = perm
+        self._a8_rows, self._a8_need = 0, {}
+        if act_int8 is None:
+            act_int8 = self.ACT_INT8
+        if act_int8 and not self._a8_hold:
+            if lib.gptq_act_int8_workspace_bytes(ctypes.byref(L), 1):
+                self._a8_rows = max(1, int(self.ACT_INT8_MIN_ROWS if act_int8_min_rows is None else act_int8_min_rows))
+            else:
+                _warn_once(f"mi355x QuantLinear: act_int8=True has no effect on this layer ({lib.gptq_last_error().decode()}); it keeps the 16-bit kernels")
         if release_checkpoint_layout is None:
             release_checkpoint_layout = self.RELEASE_CHECKPOINT_LAYOUT
         if qweight_tiled is not None:
@@ -419,7 +440,7 @@ class QuantLinear(nn.Module):
                                                             ctypes.byref(tuning) if tuning is not None else None))
             if tuning is None:
                 self._ws_need[M] = need
-                if need == 0 and 0 < M < 64 and _lib.fwd is not None:
+                if need == 0 and 0 < M < 64 and _lib.fwd is not None and not (self._a8_rows and M >= self._a8_rows):      # (the C++ fast path never serves a row count the int8 path owns)
                     self._ws0_mask |= 1 << M
         if need == 0:
             return None, 0
@@ -427,7 +448,7 @@ class QuantLinear(nn.Module):
         exchange_tick(device)
         return buf.data_ptr(), buf.numel()
 
-    def forward(self, x: torch.Tensor, tuning: "_lib.GptqTuning | None" = None):
+    def forward(self, x: torch.Tensor, tuning: "_lib.GptqTuning | None" = None, act_int8: bool = True):
         # The reference's callers are eager (generate() under inference_mode, auto_gptq/modeling/_base.py:415-418), and a decode
         # kernel here runs for ~5 us: everything per call that is not the launch is kept to attribute reads -- device, dtype,
         # ctypes handles and the layer pointer are resolved once in post_init.  Row counts already known to need no workspace (decode rows: the mask is 0 until
@@ -475,9 +496,13 @@ class QuantLinear(nn.Module):
         M = x2.shape[0]
         n_out = self._n_out
         out = torch.empty((M, n_out), dtype=w_dtype, device=dev)
-        if M != 0 and self._released:
+        a8 = self._a8_rows
+        use_a8 = a8 != 0 and M >= a8 and act_int8 and tuning is None      # opt-in W4A8 (callers that keep the 16-bit kernels pass act_int8=False; a8 >= 1, so M != 0)
+        if use_a8:
+            self._forward_a8(x2, out, M)                        # quantise + i8 GEMM, two launches
+        elif M != 0 and self._released:
             self._rebuild_rows(M, tuning)
-        if M != 0:
+        if M != 0 and not use_a8:
             need = self._ws_need.get(M) if tuning is None else None
             if need == 0:
                 ws_ptr, ws_bytes = None, 0
@@ -506,6 +531,43 @@ class QuantLinear(nn.Module):
         if x.dim() != 2:
             out = out.reshape(x.shape[:-1] + (n_out,))
         return out
+
+    # ------------------------------------------------------------------ W4A8 (opt-in)
+    def _a8_workspace(self, M: int):
+        """(pointer, bytes) for gptq_act_quant / gptq_forward_a8 at M rows: the stream's scratch BEHIND its header (which belongs to the 16-bit kernels' exchanges)."""
+        need = self._a8_need.get(M)
+        if need is None:
+            need = self._a8_need[M] = int(_lib.load().gptq_act_int8_workspace_bytes(self._layer_ref, M))
+            if need == 0:
+                _lib.check(3)      # GPTQ_ERR_UNSUPPORTED: raises with the reason the query left in the last-error string
+        buf = reserve_workspace(self._dev, _lib.WS_HEADER_BYTES + need)
+        return buf.data_ptr() + _lib.WS_HEADER_BYTES, buf.numel() - _lib.WS_HEADER_BYTES
+
+    def _forward_a8(self, x2: torch.Tensor, out: torch.Tensor, M: int) -> None:
+        ws_ptr, ws_bytes = self._a8_workspace(M)
+        idx = self._dev_index
+        with torch.cuda.device(idx):
+            rc = _lib.load().gptq_forward_a8(self._layer_ref, x2.data_ptr(), out.data_ptr(), M, ws_ptr, ws_bytes, _raw_stream(idx))
+        if rc:
+            _lib.check(rc)
+
+    def quantize_activations(self, x: torch.Tensor):
+        """``(xq, sx)`` of the int8-activation path for ``x`` [.., infeatures]: xq int8 [M, infeatures] in NATURAL k order, sx fp32 [M], with
+        ``sx = amax / 127`` and ``xq = rint(x / sx)`` per row in IEEE fp32 (gptq_act_quant; the kernel's own buffer is in the k order of the GEMM's operands
+        and, for act-order layers, behind ``perm`` -- both are undone here).  For tests and for users who want to see the rounding."""
+        if self._layer is None:
+            self.post_init()
+        K, dev = self.infeatures, self._dev
+        x2 = x.reshape(-1, K).to(self._w_dtype).contiguous()
+        if x2.data_ptr() & 15:
+            x2 = x2.clone()
+        M = x2.shape[0]
+        lib = _lib.load()
+        need = int(lib.gptq_act_int8_workspace_bytes(self._layer_ref, M))
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(self._dev_index):
+            _lib.check(lib.gptq_act_quant(self._layer_ref, x2.data_ptr(), M, ws.data_ptr(), need, _raw_stream(self._dev_index)))
+        return unpack_act_int8_workspace(ws, M, K, self.group_size, self._perm)
 
     # ------------------------------------------------------------------ gradients
     def _forward_grad(self, x: torch.Tensor, tuning=None):
@@ -700,6 +762,28 @@ class QuantLinear(nn.Module):
         return qweight, qzeros, s_cast
 
 
+def unpack_act_int8_workspace(ws: torch.Tensor, M: int, K: int, group_size: int, perm=None):
+    """``(xq, sx)`` from a workspace gptq_act_quant has filled (uint8 tensor, layout in include/gptq_mi355x.h): xq int8 [M, K] in NATURAL k order, sx fp32 [M].
+    The kernel stores xq in the k order of the GEMM's operands (a8_k_of_pos of csrc/act_int8.hip; it depends on group_size == 32 alone) and, for act-order
+    layers, behind ``perm`` (int32 [K]: stored position i is x[perm[i]]); both are undone here.  For tests and for users who want to see the rounding."""
+    Kp, off = (K + 127) // 128 * 128, (4 * M + 255) // 256 * 256
+    sx = ws[:4 * M].view(torch.float32).clone()
+    stored = ws[off:off + M * Kp].view(torch.int8).reshape(M, Kp)
+    p = torch.arange(Kp, device=ws.device)
+    q = p & 127
+    t, h, w, b = q >> 5, (q >> 4) & 1, (q >> 2) & 3, q & 3
+    g32 = group_size == 32
+    k = (p - q) + 32 * (t if g32 else 2 * (t >> 1) + h) + 8 * w + 4 * (b & 1) + (b >> 1) + 2 * (h if g32 else t & 1)
+    seq = torch.empty_like(stored)
+    seq[:, k] = stored
+    seq = seq[:, :K]
+    if perm is None:
+        return seq.contiguous(), sx
+    xq = torch.empty_like(seq)
+    xq[:, perm.long()] = seq
+    return xq, sx
+
+
 def _pack_fields(vals_u32: torch.Tensor, bits: int) -> torch.Tensor:
     """Pack uint32 values (held in int64) along dim 0 into int32 words, OR-ing whole (unmasked)
     values exactly as the reference does (qlinear_cuda.py:139-162)."""
@@ -745,7 +829,7 @@ class _GradInput(torch.autograd.Function):
             outs = forward_multi([l for l, _ in specs], x, tuning)
         else:
             l, plain = specs[0]
-            outs = [l._plain_product(x, tuning) if plain else l.forward(x, tuning)]      # (forward, not __call__: the module's hooks ran for the outer call)
+            outs = [l._plain_product(x, tuning) if plain else l.forward(x, tuning, False)]      # (forward, not __call__: the module's hooks ran for the outer call)
         return tuple(outs)
 
     @staticmethod
@@ -800,7 +884,7 @@ def forward_multi(layers, x: torch.Tensor, tuning: "_lib.GptqTuning | None" = No
         raise RuntimeError("forward_multi: layers with release_checkpoint_layout=True take no tuning override in the grouped entry points; call them one by one")
     if released and x.numel() // max(1, a.infeatures) > 4:
         # layers whose checkpoint rows left the HBM share ONE rows scratch: beyond the decode rows (which run from the copies) they are called one by one
-        return [l(x, tuning) for l in layers]
+        return [l(x, tuning, act_int8=False) for l in layers]      # (a grouped call keeps the 16-bit kernels)
     key = tuple([id(l._layer) for l in layers]) if a._layer is not None else None
     ent = _MULTI.get(key) if key is not None else None
     if ent is None:
@@ -906,7 +990,7 @@ def mlp_forward(gate: QuantLinear, up: QuantLinear, down: QuantLinear, x: torch.
             raise RuntimeError("mlp_forward: layers with release_checkpoint_layout=True take no tuning override")
         if x.numel() // max(1, gate.infeatures) > 4:
             g, u = forward_multi([gate, up], x)          # released layers (one shared rows scratch): composed from single calls
-            return down(act_fn(g) * u)
+            return down(act_fn(g) * u, act_int8=False)      # (an MLP call keeps the 16-bit kernels)
     dev = gate._dev
     if x.device != dev:
         raise RuntimeError(f"mi355x mlp_forward: input is on {x.device}, the layers on {dev}")
@@ -1004,4 +1088,4 @@ def exchange_error(device=None, clear: bool = False) -> bool:
 mlp_exchange_error = exchange_error      # round-3 name
 
 
-__all__ = ["QuantLinear", "reserve_workspace", "forward_multi", "mlp_forward", "exchange_error", "exchange_tick", "mlp_exchange_error"]
+__all__ = ["QuantLinear", "reserve_workspace", "unpack_act_int8_workspace", "forward_multi", "mlp_forward", "exchange_error", "exchange_tick", "mlp_exchange_error"]

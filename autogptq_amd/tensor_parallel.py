@@ -58,6 +58,8 @@ class ColumnParallelQuantLinear(nn.Module):
         if exchange not in ("all_gather", "peer_store"):
             raise ValueError(f"exchange must be 'all_gather' or 'peer_store', got {exchange!r}")
         self.local = local
+        if hasattr(local, "_a8_hold"):                  # (local may be any callable)
+            local._a8_hold, local._a8_rows = True, 0    # a shard keeps its 16-bit kernels (every rank the same arithmetic), whatever post_init(act_int8=...) is asked later
         self.outfeatures = outfeatures
         self.group = group
         self.gather_output = gather_output
@@ -181,6 +183,8 @@ class RowParallelQuantLinear(nn.Module):
         and a partial sum beyond 65504 overflows fp16 where the fp32 total would not.  None = always fp32.  bf16 layers cannot overflow this way."""
         super().__init__()
         self.local = local
+        if hasattr(local, "_a8_hold"):                  # (local may be any callable)
+            local._a8_hold, local._a8_rows = True, 0    # a shard keeps its 16-bit kernels (every rank the same arithmetic), whatever post_init(act_int8=...) is asked later
         self.k0, self.k1 = k_range
         self.bias = bias
         self.group = group

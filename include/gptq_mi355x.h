@@ -734,6 +734,31 @@ int gptq_awq_unpack(const uint32_t *awq_qweight, const uint32_t *awq_qzeros, con
 int gptq_awq_repack(const uint32_t *awq_qweight, const uint32_t *awq_qzeros, int K, int N, int group_size,
                     uint32_t *qweight_out, uint32_t *qzeros_out, void *stream);
 
+/* ---- W4A8 (OPT-IN): int8 activations on the i8 matrix core (csrc/act_int8.hip) ------------------------------------------------------
+ * The scheme of QQQ / QServe for GPTQ checkpoints: every row of x is rounded to int8 with its own scale, the 4-bit fields become operand bytes
+ * without a floating-point decode, and the product runs on v_mfma_i32_32x32x32_i8.  It CHANGES NUMERICS (each activation is rounded by up to
+ * half a step sx[m] / 2), so no planner ever picks it: only these entry points run it.  Per row m, in IEEE fp32:
+ *     amax = max_k |float(x[m][k])|,   sx[m] = amax / 127.0f,   xq[m][k] = (int8) rintf(float(x[m][k]) / sx[m])      (a zero row: sx = 0, xq = 0;
+ *     a row that holds an inf or a NaN is UNSPECIFIED: the maximum drops NaNs, an infinite scale sends the row to 0 or NaN -- check inputs upstream)
+ *     out[m][n] = T( sx[m] * sum_g s[g][n] * I[m][g][n] + bias[n] ),   I[m][g][n] = sum_{k in g} xq[m][k] * (q[k][n] - z[g][n])   exact int32
+ * (true division, round-to-nearest-even: a CPU restatement gives the same bits; the fp32 sums over g in ascending order, one FMA each, one
+ * rounding to T).  Layers: 4 bits, fp16 / bf16, carrying the decode copy (qweight_tiled / qconst_tiled -- the only tensors read besides bias and
+ * perm; N a multiple of 16), plain or act-order with perm (the quantise pass writes x through perm: an act-order layer pays nothing extra),
+ * group_size 32, 64, 128 times a power of two, or >= K; K a multiple of 32 up to 32736; no epilogue; any M >= 1.  Everything else is declined
+ * with GPTQ_ERR_UNSUPPORTED and the reason in the last-error string.  Two launches on the caller's stream, no allocation, no atomics, no exchange
+ * between workgroups: bit-reproducible, legal inside hipGraph capture, and the bits of row m depend on row m alone.
+ * Workspace (caller-owned, 16-byte aligned, no header, nothing to clear):  a256(4 M) + a256(M * 128 * ceil(K / 128)),  a256 = round up to 256:
+ * sx [M] fp32 at byte 0, then xq [M][128 ceil(K / 128)] int8 in the k order of the GEMM's operands (the library owns it; the query below returns
+ * 0 for a declined call).  The quantise and the GEMM are separate calls so that layers reading one x can share one quantised copy: every layer
+ * with the same K, perm and group mode (32 | anything else) reads the same workspace.
+ * The describe call is host-only: "path=act_int8 tile=128x128 waves=4 mfma=32x32x32_i8 group_mode=g32|g64|g128|one zero=signed_bytes tiles=RxC chunks=..
+ * groups=.. wg_quant=.. workspace=.. launches=2", or "path=none reason=..."; GPTQ_OK either way. */
+size_t gptq_act_int8_workspace_bytes(const gptq_layer_t *layer, int M);
+int gptq_act_quant(const gptq_layer_t *layer, const void *x, int M, void *workspace, size_t workspace_bytes, void *stream);
+int gptq_gemm_a8(const gptq_layer_t *layer, const void *workspace, void *out, int M, void *stream);
+int gptq_forward_a8(const gptq_layer_t *layer, const void *x, void *out, int M, void *workspace, size_t workspace_bytes, void *stream);
+int gptq_describe_a8_plan(const gptq_layer_t *layer, int M, char *out, size_t out_bytes);
+
 /* ---- direct peer-store all-gather for out_features-parallel layers; experimental, off by default ----------
  * The reference runs a layer on one GPU only (tests/test_q4.py:1224-1226: `test_multigpu` is a TODO); the column split is the
  * property its fused q/k/v caller relies on (fused_llama_attn.py:171-186).  Rank r of T computes out[:, r*N/T : (r+1)*N/T]; the

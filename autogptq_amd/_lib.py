@@ -29,6 +29,7 @@ DTYPE_ENUM = {torch.float16: GPTQ_F16, torch.bfloat16: GPTQ_BF16, torch.float32:
 EXPORTS = (
     "gptq_abi_version", "gptq_last_error", "gptq_status_string", "gptq_workspace_bytes", "gptq_workspace_bytes_ex",
     "gptq_forward", "gptq_forward_ex", "gptq_gemv", "gptq_gemm", "gptq_dequant", "gptq_grad_input",
+    "gptq_grad_input_ex", "gptq_describe_grad_input_plan",
     "gptq_unpack_weights", "gptq_unpack_zeros", "gptq_pack_weights", "gptq_pack_zeros",
     "gptq_make_sequential", "gptq_resequence_qweight", "gptq_permute_columns", "gptq_prepack_decode", "gptq_prepack_decode_bytes", "gptq_unprepack_decode",
     "gptq_awq_unpack", "gptq_awq_repack", "gptq_describe_plan", "gptq_describe_plan_xstage",
@@ -51,6 +52,7 @@ EXPORTS = (
 WS_HEADER_BYTES = 65536
 STRIP_COLS = 16          # GPTQ_STRIP_COLS: columns per strip of the decode copy (gptq_prepack_decode)
 COPY_ROWS_INT2 = 0x100   # GPTQ_COPY_ROWS_INT2: OR-ed into GptqLayer.tiled_cols -- this 2-bit layer's copy is also read at 5+ rows (opt-in; copy_cols() masks it)
+GRAD_ON_COPY = 1         # GPTQ_GRAD_ON_COPY: gptq_grad_input_ex's flag -- the backward on the decode copy (opt-in)
 COPY_ROWS_INT2_WIDE = 0x200   # GPTQ_COPY_ROWS_INT2_WIDE: ... in the whole band of the 4-bit twin (a layer whose checkpoint rows are not resident)
 
 
@@ -189,6 +191,8 @@ def load() -> ctypes.CDLL:
         getattr(lib, name).argtypes = fw + [POINTER(GptqTuning)]
     lib.gptq_dequant.argtypes = [POINTER(GptqLayer), c_void_p, c_void_p]
     lib.gptq_grad_input.argtypes = [POINTER(GptqLayer), c_void_p, c_void_p, c_int, c_int, c_void_p]
+    lib.gptq_grad_input_ex.argtypes = [POINTER(GptqLayer), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]
+    lib.gptq_describe_grad_input_plan.argtypes = [POINTER(GptqLayer), c_int, c_int, c_char_p, c_size_t]
     lib.gptq_unpack_weights.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
     lib.gptq_unpack_zeros.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
     lib.gptq_pack_weights.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
@@ -372,6 +376,14 @@ def describe_plan(layer: "GptqLayer", M: int, tuning: "GptqTuning | None" = None
     if d.get("kernel") == "strips":      # the decode-copy kernel: x and the constants staged in one step or two (gptq_describe_plan_xstage; the C line itself is pinned)
         d["xstage"] = int(load().gptq_describe_plan_xstage(ctypes.byref(layer), M, tp))
     return d
+
+
+def describe_grad_input_plan(layer: "GptqLayer", M: int, flags: int = 0) -> str:
+    """What gptq_grad_input_ex would launch for (layer, M, flags), as the C line: "kernel=grad_copy bm=.. stages=.. gm=.. act=.." or
+    "kernel=grad_rows reason=.." (host-only query)."""
+    buf = ctypes.create_string_buffer(128)
+    check(load().gptq_describe_grad_input_plan(ctypes.byref(layer), M, flags, buf, len(buf)))
+    return buf.value.decode()
 
 
 def describe_mlp_plan(gate: "GptqLayer", up: "GptqLayer", down: "GptqLayer", M: int, tuning: "GptqTuning | None" = None) -> dict:

@@ -847,6 +847,43 @@ int gptq_grad_input(const gptq_layer_t* L, const void* dy, void* dx, int M, int 
     return GPTQ_OK;
 }
 
+// check_layer of a layer that may run on its decode copy alone: with GPTQ_GRAD_ON_COPY and a copy present, a NULL qweight passes this check (the copy's
+// address stands in for it); whether the rows are needed after all is the plan's answer
+static int check_layer_grad(const gptq_layer_t* L, int flags) {
+    if (!L) return fail(GPTQ_ERR_NULL, "layer is NULL");
+    if (flags & ~GPTQ_GRAD_ON_COPY) return fail(GPTQ_ERR_UNSUPPORTED, "unknown gptq_grad_input_ex flags 0x%x", flags);
+    gptq_layer_t c = *L;
+    if ((flags & GPTQ_GRAD_ON_COPY) && !c.qweight && c.qweight_tiled) c.qweight = c.qweight_tiled;
+    return check_layer(&c);
+}
+
+int gptq_grad_input_ex(const gptq_layer_t* L, const void* dy, void* dx, int M, int accumulate, int flags, void* stream) {
+    int rc = check_layer_grad(L, flags);
+    if (rc) return rc;
+    if ((rc = check_io(dy, dx, M))) return rc;
+    if (((uintptr_t)dy | (uintptr_t)dx) & 15) return fail(GPTQ_ERR_UNSUPPORTED, "dy / dx must be 16-byte aligned");
+    const GradCopyPlan pl = plan_grad_copy(*L, M, flags);
+    if (!pl.ok) {
+        if (!L->qweight) return fail(GPTQ_ERR_NULL, "qweight is NULL and the layer does not run on its decode copy (%s)", pl.why);
+        return gptq_grad_input(L, dy, dx, M, accumulate, stream);
+    }
+    hipError_t e = launch_grad_copy(*L, pl, dy, dx, M, accumulate, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "gptq_grad_input_ex launch");
+    return GPTQ_OK;
+}
+
+int gptq_describe_grad_input_plan(const gptq_layer_t* L, int M, int flags, char* out, size_t out_bytes) {
+    if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out must be non-NULL");
+    out[0] = 0;
+    int rc = check_layer_grad(L, flags);
+    if (rc) return rc;
+    if (M <= 0) return fail(GPTQ_ERR_SHAPE, "M must be > 0, got %d", M);
+    const GradCopyPlan pl = plan_grad_copy(*L, M, flags);
+    if (pl.ok) snprintf(out, out_bytes, "kernel=grad_copy bm=%d stages=%d gm=%d act=%d", pl.bm, pl.stages, pl.gm, pl.act ? 1 : 0);
+    else snprintf(out, out_bytes, "kernel=grad_rows reason=%s", pl.why);
+    return GPTQ_OK;
+}
+
 // ---- the router of a routed layer (moe_router.hip) ----
 static int router_check(int T, int H, int E, int topk, int dtype, int flags) {
     if (dtype == GPTQ_F32) return fail(GPTQ_ERR_UNSUPPORTED, "fp32 router: the router kernel takes fp16 / bf16");

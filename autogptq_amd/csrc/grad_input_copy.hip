@@ -1,0 +1,268 @@
+// grad_input_copy.hip -- the input gradient on the DECODE COPY: dX[M, K] (+)= dY[M, N] . W^T from qweight_tiled / qconst_tiled alone (gptq_grad_input_ex with
+// GPTQ_GRAD_ON_COPY; opt-in).  The contract is grad_input.hip's: every weight is T(s * float(q - z)), bit-exact to gptq_dequant; products and sums in fp32 on the
+// matrix core; one rounding at the store (accumulate: the old dX is added in fp32 first); no atomics, no workspace, a fixed summation order.  The checkpoint rows
+// (qweight, qzeros, scales, g_idx) are never read, so a layer whose rows have left the device needs no rebuild pass in front of its backward.
+//
+// The copy holds, per strip of 16 columns and chunk of 128 k, one contiguous KiB in which lane (k-slot g = lane >> 4, column r = lane & 15) owns 16 bytes: 32
+// consecutive k of ONE column n.  The reduction of this product runs over n, so the matrix core wants 8 consecutive n at one k: the kernel transposes through LDS.
+//   work     a workgroup of 4 waves owns BM rows x 128 k (one chunk of the copy) of dX and walks N in stages of 4 strips (64 n); BM = 128, or 64 where 128-row
+//            tiles give fewer than 256 workgroups (runtime-uniform).  The workgroup-id remap is grad_input.hip's: the k tiles of a row block share an XCD.
+//   weights  per stage wave w loads the strip-chunk of strip 4 stage + w: ONE 16-byte load per lane; scale and zero-point from the (strip, group) record as the
+//            rows kernel reads them (scale at 2 r, zero-point at 32 + r; group per chunk, per half or per k-slot by group mode -- stage-invariant per lane).
+//            Deq1<T>::frag (mma_dequant.cuh, the packed magic-number decode) turns each of the lane's 4 words into 8 consecutive k of its column, in memory order.
+//   image    each frag is ONE 16-byte LDS write into an [n][k] image: 64 rows (n) of 256 bytes (128 k).  The B fragments of v_mfma_f32_16x16x32 -- lane
+//            (column k = lane & 15, g = lane >> 4) wants n = 8 g .. 8 g + 7 at its k -- come out of it with ds_read_b64_tr_b16, two per fragment: a 16-lane
+//            group reads 4 rows (n) x 16 columns (k), lane 4 q + pp gives the address of row q, columns 4 pp .. 4 pp + 3, and lane i receives column i
+//            (adapter_grad.hip uses the same mapping).  The first read takes n = 8 g + 0 .. 3, the second 8 g + 4 .. 7: the order ds_read_b128 gives dY.
+//   swizzle  16-byte slot c (0 .. 15) of image row n lies at slot c ^ f(n & 15), f(v) = (v0 << 1) | (v1 << 2) | (v3 << 3) | v2 (a permutation of v's bits).
+//            Write: the 16 lanes of a ds_write_b128 group hold 16 rows at one slot -> 16 different slots, all 64 banks.  Transposing read: a half-wave (g = 0, 1)
+//            reads rows 8 g + q (+ 4), 32 bytes (an aligned slot pair) each: f >> 1 differs over those 8 rows -> 8 different pairs, all 64 banks.  Both free of
+//            conflicts by the bank model the rest of the library uses (mma_dequant.cuh: swz); not measured with counters.
+//   dY       [BM][64 n] copied to LDS as it lies (16-byte loads, swz() rows of 128 bytes), A fragments by ds_read_b128.  Rows past M repeat the last row (not
+//            stored); a last stage with fewer than 4 strips clamps its strip index and zero-fills its dY columns.
+//   pipeline two stage buffers (2 x (BM x 128 + 64 x 256) bytes = 64 KiB at BM = 128); the next stage's raw words (weights, constants, dY) are loaded into
+//            registers before this stage's MFMAs and written to the other buffer behind them; one barrier per stage.
+//   epilogue fp32 accumulators through LDS (the same 64 KiB) to rows.  Plain layers: 16-byte stores of 8 consecutive k.  Act-order layers: the copy is made of the
+//            re-sequenced rows, so column k' of the tile is dX[:, perm[k']] (gptq_permute_columns: x_seq[:, i] = x[:, perm[i]]): each thread loads its 8 perm
+//            entries once and stores 2-byte elements to the scattered columns (accumulate: the old value from the same address first).  No g_idx lookups,
+//            no pre- or post-pass.
+// BM, the group mode, act-order and accumulate are launch-uniform: one kernel per dtype.
+#include "common.cuh"
+#include "mma_dequant.cuh"
+#include "launch.h"
+
+namespace gptq {
+namespace gcopy {
+
+constexpr int THREADS = 256;                // 4 waves: a strip each while dequantising; 2 (rows) x 2 (k halves of 64) on the matrix core
+constexpr int BK = 128;                     // k per workgroup: one chunk of the copy
+constexpr int BN = 64;                      // n per stage: 4 strips
+constexpr int B_ROW = 256;                  // bytes of a weight image row: 128 k of one n
+constexpr int B_BYTES = BN * B_ROW;
+constexpr int LDS_BYTES = 65536;            // 2 x (BM x 128 + B_BYTES) at BM = 128 = the fp32 epilogue tile [128][128]
+constexpr unsigned WCH = 1024u, REC = 48u;  // a strip-chunk of the copy, a constant record
+
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+
+struct Args {
+    const char* qw;              // qweight_tiled
+    const char* qc;              // qconst_tiled
+    const int* perm;             // act-order: original k of re-sequenced position i, else NULL
+    const void* dy;
+    void* dx;
+    int M, K, N, strips, chunks, groups, gshift, gm, bm, nkt, accumulate;
+};
+
+// the raw words one thread loads for a stage
+struct Stage {
+    u32x4 a[4];                  // dY: 16-byte slots of the A image
+    u32x4 q;                     // 32 k of the lane's column
+    unsigned cs, cz;             // its scale bits and zero-point
+};
+
+// image slot swizzle: a permutation of the row's low four bits whose upper three differ over rows {0..3, 8..11} and over {4..7, 12..15}
+__device__ __forceinline__ int fswz(int v) { return ((v & 3) << 1) | (v & 8) | ((v >> 2) & 1); }
+
+// B fragment: n = 8 g .. 8 g + 7 (rows at, at + 4 rows) at the lane's k, transposed out of the image
+__device__ __forceinline__ u32x4 tr_fragment(const char* lo_at, const char* hi_at) {
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)lo_at);
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)hi_at);
+    const u32x2 l = __builtin_bit_cast(u32x2, lo), h = __builtin_bit_cast(u32x2, hi);
+    return u32x4{l.x, l.y, h.x, h.y};
+}
+
+template <typename T, int RB>
+__device__ __forceinline__ void run(const Args& p, char* smem, int m0, int kt) {
+    constexpr int BM = RB * 32;
+    constexpr int NA = BM * 8 / THREADS;                  // dY slots per thread
+    constexpr int BUF = BM * 128 + B_BYTES;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 15, g = lane >> 4;
+    const int wm = wave >> 1, wk = wave & 1;
+    const int M = p.M, K = p.K, N = p.N, k0 = kt * BK;
+    const T* __restrict__ dy = (const T*)p.dy;
+
+    // constants: the lane's group is the same in every stage
+    int grp = p.gm == 0 ? (kt >> p.gshift) : (p.gm == 1 ? 2 * kt + (g >> 1) : 4 * kt + g);
+    grp = min(grp, p.groups - 1);                          // (one group; the k-slots past K of a last, partial chunk)
+    const unsigned coff = (unsigned)grp * REC + 2u * (unsigned)r, zoff = (unsigned)grp * REC + 32u + (unsigned)r;
+    const size_t strip_w = (size_t)p.chunks * WCH, strip_c = (size_t)p.groups * REC;
+    const char* const wsrc = p.qw + (size_t)kt * WCH + (size_t)lane * 16u;
+
+    auto fetch = [&](Stage& s, int it) {
+        const int n0 = it * BN;
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+            const int c = tid + THREADS * i, row = c >> 3, sl = c & 7;
+            const int m = min(m0 + row, M - 1);            // rows past M repeat the last one (their outputs are not stored)
+            s.a[i] = n0 + sl * 8 < N ? *(const u32x4*)(dy + (size_t)m * N + n0 + sl * 8) : u32x4{0, 0, 0, 0};
+        }
+        const int strip = min(4 * it + wave, p.strips - 1);   // past the last strip: a strip again, against zero dY columns
+        s.q = *(const u32x4*)(wsrc + (size_t)strip * strip_w);
+        const char* rec = p.qc + (size_t)strip * strip_c;
+        s.cs = *(const unsigned short*)(rec + coff);
+        s.cz = *(const unsigned char*)(rec + zoff);
+    };
+
+    // image offsets: the lane's four writes (slot 4 g + w of row 16 wave + r) ...
+    const int wrow = (16 * wave + r) * B_ROW, wf = fswz(r);
+    auto store = [&](const Stage& s, char* buf) {
+        char* As = buf;
+        char* Bs = buf + BM * 128;
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+            const int c = tid + THREADS * i;
+            *(u32x4*)(As + swz(c >> 3, c & 7)) = s.a[i];
+        }
+        Deq1<T> dq;
+        dq.setup(s.cs, s.cz);
+#pragma unroll
+        for (int w = 0; w < 4; ++w) *(u32x4*)(Bs + wrow + (((4 * g + w) ^ wf) << 4)) = dq.frag(s.q[w]);
+    };
+    // ... and its transposing reads: row 8 g + q (second read: + 4), the 8 bytes at k = 64 wk + 16 j + 4 pp -> slot 8 wk + 2 j + (pp >> 1), half pp & 1.
+    // 2 j touches bits 1, 2 of the slot alone, so block j is the j = 0 address ^ 32 j; the second row flips bit 0 of f
+    const int q = r >> 2, pp = r & 3;
+    const int rf = fswz(8 * (g & 1) + q);
+    const int rd_lo = (8 * g + q) * B_ROW + (((8 * wk + (pp >> 1)) ^ rf) << 4) + 8 * (pp & 1);
+    const int rd_hi = (8 * g + q + 4) * B_ROW + (((8 * wk + (pp >> 1)) ^ rf ^ 1) << 4) + 8 * (pp & 1);
+
+    f32x4 acc[RB][4];
+#pragma unroll
+    for (int i = 0; i < RB; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const int stages = (N + BN - 1) / BN;
+    Stage st;
+    fetch(st, 0);
+    store(st, smem);
+    __syncthreads();
+    const int arow = wm * (BM / 2) + r;
+    for (int it = 0; it < stages; ++it) {
+        const bool more = it + 1 < stages;
+        if (more) fetch(st, it + 1);
+        const char* As = smem + (it & 1) * BUF;
+        const char* Bs = As + BM * 128;
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            u32x4 a[RB], b[4];
+#pragma unroll
+            for (int i = 0; i < RB; ++i) a[i] = *(const u32x4*)(As + swz(arow + 16 * i, 4 * s + g));
+#pragma unroll
+            for (int j = 0; j < 4; ++j) b[j] = tr_fragment(Bs + s * 32 * B_ROW + (rd_lo ^ (32 * j)), Bs + s * 32 * B_ROW + (rd_hi ^ (32 * j)));
+#pragma unroll
+            for (int i = 0; i < RB; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] = Mma16<T>::run(a[i], b[j], acc[i][j]);
+        }
+        if (more) store(st, smem + ((it + 1) & 1) * BUF);
+        __syncthreads();
+    }
+
+    // epilogue: [BM][128] fp32 through LDS (column ^ 16 on odd rows, as grad_input.hip)
+    float* E = (float*)smem;
+#pragma unroll
+    for (int i = 0; i < RB; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int row = wm * (BM / 2) + 16 * i + 4 * g + e, col = wk * 64 + 16 * j + r;
+                E[row * BK + (col ^ ((row & 1) << 4))] = acc[i][j][e];
+            }
+    __syncthreads();
+    T* __restrict__ dx = (T*)p.dx;
+    const int c8 = (tid & 15) * 8, k = k0 + c8;           // the thread's 8 columns: the same in every item (THREADS % 16 == 0)
+    if (k >= K) return;                                    // (K % 32 == 0: 8 columns are inside or outside as a whole; no barrier follows)
+    int pk[8];
+    if (p.perm) {
+        const u32x4 p0 = *(const u32x4*)(p.perm + k), p1 = *(const u32x4*)(p.perm + k + 4);
+        pk[0] = p0.x; pk[1] = p0.y; pk[2] = p0.z; pk[3] = p0.w; pk[4] = p1.x; pk[5] = p1.y; pk[6] = p1.z; pk[7] = p1.w;
+    }
+#pragma unroll
+    for (int i = 0; i < BM * 16 / THREADS; ++i) {
+        const int row = (tid + THREADS * i) >> 4;
+        const int m = m0 + row;
+        if (m >= M) continue;
+        const float* e = E + row * BK + (c8 ^ ((row & 1) << 4));
+        const f32x4 lo = *(const f32x4*)e, hi = *(const f32x4*)(e + 4);
+        float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        T* orow = dx + (size_t)m * K;
+        if (p.perm) {
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                T* o = orow + pk[c];
+                if (p.accumulate) v[c] += DType<T>::to_f32(*o);
+                *o = DType<T>::from_f32(v[c]);
+            }
+        } else {
+            T* out = orow + k;
+            if (p.accumulate) {
+                float old[8];
+                unpack8<T>(*(const u32x4*)out, old);
+#pragma unroll
+                for (int c = 0; c < 8; ++c) v[c] += old[c];
+            }
+            const u32x2 w0 = pack4<T>(f32x4{v[0], v[1], v[2], v[3]}), w1 = pack4<T>(f32x4{v[4], v[5], v[6], v[7]});
+            *(u32x4*)out = u32x4{w0.x, w0.y, w1.x, w1.y};
+        }
+    }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(THREADS, 2) grad_copy_kernel(Args p) {
+    __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
+    const int b = xcd_remap(blockIdx.x, gridDim.x);        // consecutive k tiles of one row block on one XCD: they share dY in its L2
+    const int kt = b % p.nkt, mt = b / p.nkt;
+    if (p.bm == 128) run<T, 4>(p, smem, mt * 128, kt);
+    else run<T, 2>(p, smem, mt * 64, kt);
+}
+
+}  // namespace gcopy
+
+// The one place the qualification rule lives: gptq_describe_grad_input_plan prints it, gptq_grad_input_ex launches by it.  Pure host arithmetic.
+GradCopyPlan plan_grad_copy(const gptq_layer_t& L, int M, int flags) {
+    GradCopyPlan pl{};
+    auto no = [&](const char* why) { pl.why = why; return pl; };
+    if (!(flags & GPTQ_GRAD_ON_COPY)) return no("flag_off");
+    if (L.bits != 4) return no("bits");
+    if (L.dtype != GPTQ_F16 && L.dtype != GPTQ_BF16) return no("dtype");
+    // (an act-order layer's copy is made of its re-sequenced rows: without perm the kernel cannot name its output columns)
+    if (!L.qweight_tiled || !L.qconst_tiled || copy_cols(L) != GPTQ_STRIP_COLS || (L.g_idx && !L.perm) || L.K % 32 || L.N % GPTQ_STRIP_COLS) return no("no_copy");
+    const int gs = L.group_size;
+    if (gs == 32) pl.gm = 2;
+    else if (gs == 64) pl.gm = 1;
+    else if (gs >= L.K) pl.gshift = 31;
+    else if (gs > 0 && gs % 128 == 0 && ((gs / 128) & (gs / 128 - 1)) == 0) {
+        while ((128 << pl.gshift) < gs) ++pl.gshift;
+    } else return no("group_size");
+    pl.groups = gs >= L.K ? 1 : (L.K + gs - 1) / gs;
+    pl.chunks = (L.K + 127) / 128;
+    pl.stages = (L.N + gcopy::BN - 1) / gcopy::BN;
+    pl.act = L.g_idx != nullptr;
+    // 128-row tiles where they still give 256 workgroups (a full round at one per CU), else 64 rows: grad_input.hip's rule
+    pl.bm = ((long)(M + 127) / 128) * pl.chunks >= 256 ? 128 : 64;
+    pl.blocks = (long)pl.chunks * ((M + pl.bm - 1) / pl.bm);
+    pl.ok = M > 0 && pl.blocks <= 0x7fffffffL;
+    if (!pl.ok) pl.why = "no_copy";
+    return pl;
+}
+
+hipError_t launch_grad_copy(const gptq_layer_t& L, const GradCopyPlan& pl, const void* dy, void* dx, int M, int accumulate, hipStream_t st) {
+    if (!pl.ok) return hipErrorInvalidValue;
+    gcopy::Args p;
+    p.qw = (const char*)L.qweight_tiled;
+    p.qc = (const char*)L.qconst_tiled;
+    p.perm = pl.act ? L.perm : nullptr;
+    p.dy = dy;
+    p.dx = dx;
+    p.M = M, p.K = L.K, p.N = L.N, p.strips = L.N / GPTQ_STRIP_COLS, p.chunks = pl.chunks, p.groups = pl.groups, p.gshift = pl.gshift, p.gm = pl.gm;
+    p.bm = pl.bm, p.nkt = pl.chunks, p.accumulate = accumulate ? 1 : 0;
+    const dim3 grid((unsigned)pl.blocks), block(gcopy::THREADS);
+    if (L.dtype == GPTQ_F16) hipLaunchKernelGGL(gcopy::grad_copy_kernel<f16>, grid, block, 0, st, p);
+    else hipLaunchKernelGGL(gcopy::grad_copy_kernel<bf16>, grid, block, 0, st, p);
+    return hipGetLastError();
+}
+
+}  // namespace gptq

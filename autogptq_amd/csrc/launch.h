@@ -226,6 +226,17 @@ hipError_t launch_dequant(const gptq_layer_t& L, void* W_out, hipStream_t st);
 // grad_input.hip: dX (+)= dY . W^T on the packed rows (L.qweight, L.g_idx); BM x 128 output tiles (grad_input_bm: BM = 128 or 64)
 int grad_input_bm(const gptq_layer_t& L, int M);
 hipError_t launch_grad_input(const gptq_layer_t& L, const void* dy, void* dx, int M, int accumulate, hipStream_t st);
+// grad_input_copy.hip: the same product on the decode copy alone (opt-in: GPTQ_GRAD_ON_COPY in gptq_grad_input_ex's flags); BM x 128 output tiles, N in stages of 4 strips
+struct GradCopyPlan {
+    bool ok;
+    const char* why;         // !ok: flag_off / bits / dtype / no_copy / group_size
+    bool act;                // act-order: the tile's columns are scattered through perm
+    int gm, gshift;          // group mode (0: 128-multiples / one group, 1: 64, 2: 32) and, for mode 0, group of chunk c = c >> gshift
+    int groups, chunks, stages, bm;
+    long blocks;
+};
+GradCopyPlan plan_grad_copy(const gptq_layer_t& L, int M, int flags);
+hipError_t launch_grad_copy(const gptq_layer_t& L, const GradCopyPlan& pl, const void* dy, void* dx, int M, int accumulate, hipStream_t st);
 
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }      // the rounding of every workspace segment
 inline bool any_perm_of(const gptq_layer_t* const* Ls, int E) {

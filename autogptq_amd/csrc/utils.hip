@@ -15,8 +15,12 @@ namespace gptq {
 
 // ---------------------------------------------------------------------------------------------
 // (bits is a run-time, workgroup-uniform argument: a load-time integer kernel needs one instantiation, not one per packing)
+// One code object for gptq_unpack_weights and gptq_unpack_zeros (the library's kernel budget): zout != NULL, launch-uniform, selects the ZEROS pass
+// (unpack_zeros_body below: its own grid, qweight = qzeros, units = G groups; out is not written).
+__device__ __forceinline__ void unpack_zeros_body(const unsigned* __restrict__ qzeros, int G, int N, int bits, int zero_mode, int* __restrict__ out);
 __global__ void __launch_bounds__(256) unpack_weights_kernel(const unsigned* __restrict__ qweight, int units, int N, int bits,
-                                                             uint8_t* __restrict__ out) {
+                                                             uint8_t* __restrict__ out, int zero_mode, int* __restrict__ zout) {
+    if (zout) return unpack_zeros_body(qweight, units, N, bits, zero_mode, zout);
     const int UW = unit_words(bits), KPU = unit_vals(bits);
     const int n0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
     const int u = blockIdx.y;
@@ -48,8 +52,7 @@ __global__ void __launch_bounds__(256) unpack_weights_kernel(const unsigned* __r
     }
 }
 
-__global__ void __launch_bounds__(256) unpack_zeros_kernel(const unsigned* __restrict__ qzeros, int G, int N, int bits,
-                                                           int zero_mode, int* __restrict__ out) {
+__device__ __forceinline__ void unpack_zeros_body(const unsigned* __restrict__ qzeros, int G, int N, int bits, int zero_mode, int* __restrict__ out) {
     const int n0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
     const int g = blockIdx.y;
     if (n0 >= N || g >= G) return;
@@ -417,13 +420,14 @@ hipError_t launch_silu_mul(const void* y, void* out, int M, int N, int dtype, in
 hipError_t launch_unpack_weights(const uint32_t* qweight, int K, int N, int bits, uint8_t* w_out, hipStream_t st) {
     const int units = K / unit_vals(bits);
     dim3 grid((N / 4 + 255) / 256, units), block(256);
-    hipLaunchKernelGGL(unpack_weights_kernel, grid, block, 0, st, qweight, units, N, bits, w_out);
+    hipLaunchKernelGGL(unpack_weights_kernel, grid, block, 0, st, qweight, units, N, bits, w_out, 0, (int*)nullptr);
     return hipGetLastError();
 }
 
 hipError_t launch_unpack_zeros(const uint32_t* qzeros, int G, int N, int bits, int zero_mode, int32_t* z_out, hipStream_t st) {
+    if (!z_out) return hipErrorInvalidValue;               // (the pointer is the kernel's switch)
     dim3 grid((N / 4 + 255) / 256, G), block(256);
-    hipLaunchKernelGGL(unpack_zeros_kernel, grid, block, 0, st, qzeros, G, N, bits, zero_mode, z_out);
+    hipLaunchKernelGGL(unpack_weights_kernel, grid, block, 0, st, qzeros, G, N, bits, (uint8_t*)nullptr, zero_mode, z_out);
     return hipGetLastError();
 }
 
@@ -501,9 +505,10 @@ __device__ __forceinline__ unsigned awq_nibble(unsigned word, int i) {
 }
 
 // unpack_awq (_utils.py:556-621): w_kn[k, n] = half(w * s) - half(z * s), zeros[g, n] = z; grid.y walks k
-__global__ void __launch_bounds__(256) awq_unpack_kernel(const unsigned* __restrict__ aq, const unsigned* __restrict__ az,
-                                                         const f16* __restrict__ scales, int K, int N, int group_size,
-                                                         f16* __restrict__ w_kn, signed char* __restrict__ zeros) {
+// (a launch-uniform part of awq_repack_kernel below, with its own grid: the library's kernel budget)
+__device__ __forceinline__ void awq_unpack_body(const unsigned* __restrict__ aq, const unsigned* __restrict__ az,
+                                                const f16* __restrict__ scales, int K, int N, int group_size,
+                                                f16* __restrict__ w_kn, signed char* __restrict__ zeros) {
     const int NW = N / 8;
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= NW) return;
@@ -533,8 +538,18 @@ __global__ void __launch_bounds__(256) awq_unpack_kernel(const unsigned* __restr
 // unpack_awq + pack_from_tensors as one integer pass: 8 AWQ rows x 1 word column -> 1 GPTQ packed row x 8 columns
 // One code object for the two passes of gptq_awq_repack (the library's kernel budget): zeros_total > 0, launch-uniform, selects the QZEROS pass
 // (awq_repack_zeros_body below: its own grid, aq = the AWQ qzeros, qweight = the GPTQ qzeros, zeros_total words; K and N are not read).
+// ... and for gptq_awq_unpack: un.w_kn != NULL, launch-uniform, selects awq_unpack_body above (its own grid; qweight and zeros_total are not read).
+struct AwqUnpackArgs {
+    const unsigned* az;
+    const f16* scales;
+    f16* w_kn;
+    signed char* zeros;
+    int group_size;
+};
 __device__ __forceinline__ void awq_repack_zeros_body(const unsigned* __restrict__ az, int total, unsigned* __restrict__ qzeros);
-__global__ void __launch_bounds__(256) awq_repack_kernel(const unsigned* __restrict__ aq, int K, int N, unsigned* __restrict__ qweight, int zeros_total) {
+__global__ void __launch_bounds__(256) awq_repack_kernel(const unsigned* __restrict__ aq, int K, int N, unsigned* __restrict__ qweight, int zeros_total,
+                                                         AwqUnpackArgs un) {
+    if (un.w_kn) return awq_unpack_body(aq, un.az, un.scales, K, N, un.group_size, un.w_kn, un.zeros);
     if (zeros_total > 0) return awq_repack_zeros_body(aq, zeros_total, qweight);
     const int NW = N / 8;
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -572,7 +587,9 @@ hipError_t launch_awq_unpack(const uint32_t* aq, const uint32_t* az, const void*
                              int8_t* zeros, hipStream_t st) {
     const int NW = N / 8;
     dim3 grid((NW + 255) / 256, K < 4096 ? K : 4096), block(256);
-    hipLaunchKernelGGL(awq_unpack_kernel, grid, block, 0, st, aq, az, (const f16*)scales, K, N, group_size, (f16*)w_kn, (signed char*)zeros);
+    if (!w_kn) return hipErrorInvalidValue;                // (the pointer is the kernel's switch)
+    const AwqUnpackArgs un{az, (const f16*)scales, (f16*)w_kn, (signed char*)zeros, group_size};
+    hipLaunchKernelGGL(awq_repack_kernel, grid, block, 0, st, aq, K, N, (unsigned*)nullptr, 0, un);
     return hipGetLastError();
 }
 
@@ -580,9 +597,10 @@ hipError_t launch_awq_repack(const uint32_t* aq, const uint32_t* az, int K, int 
                              hipStream_t st) {
     const int NW = N / 8, R = K / 8;
     dim3 grid((NW + 255) / 256, R < 4096 ? R : 4096), block(256);
-    hipLaunchKernelGGL(awq_repack_kernel, grid, block, 0, st, aq, K, N, qweight, 0);
+    const AwqUnpackArgs none{};
+    hipLaunchKernelGGL(awq_repack_kernel, grid, block, 0, st, aq, K, N, qweight, 0, none);
     const int total = (K / group_size) * NW;
-    hipLaunchKernelGGL(awq_repack_kernel, dim3((total + 255) / 256), dim3(256), 0, st, az, K, N, qzeros, total);
+    hipLaunchKernelGGL(awq_repack_kernel, dim3((total + 255) / 256), dim3(256), 0, st, az, K, N, qzeros, total, none);
     return hipGetLastError();
 }
 

@@ -89,7 +89,7 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
                        release_checkpoint_layout: Optional[bool] = None, decode_copy: Optional[bool] = None,
                        expert_decode_copy: bool = False, expert_batched_decode: bool = False, expert_backward: bool = False, expert_low_bit: bool = False,
                        expert_prefill: bool = False, expert_low_bit_decode: bool = False, expert_low_bit_batch: bool = False,
-                       expert_low_bit_prefill: bool = False, low_bit_rows: bool = False, act_int8: bool = False) -> nn.Module:
+                       expert_low_bit_prefill: bool = False, low_bit_rows: bool = False, act_int8: bool = False, grad_on_copy: bool = False) -> nn.Module:
     """post_init every mi355x layer and size the per-device scratch once (so forward never allocates; needed before hipGraph
     capture).  ``max_input_length`` bounds the rows M the scratch is sized for (default 2048, the reference's exllama default).
     Memory (the model-level switches for what post_init keeps next to the checkpoint tensors): ``decode_copy=False`` builds no decode copy (1x the packed
@@ -123,6 +123,9 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
     ``act_int8=True`` (``QuantLinear.post_init(act_int8=True)``; CHANGES NUMERICS): plain forward calls of ``QuantLinear.ACT_INT8_MIN_ROWS`` rows and more on
     4-bit fp16 / bf16 layers with a decode copy round x to int8 per row and run on the i8 matrix core (W4A8, gptq_forward_a8); the scratch covers that path's
     need at ``max_input_length`` rows; with the default every plan and result is what it was.
+    ``grad_on_copy=True`` (``QuantLinear.post_init(grad_on_copy=True)``): the input gradient of 4-bit fp16 / bf16 layers with a decode copy runs on that copy
+    (gptq_grad_input_ex, grad_copy_kernel) -- with ``release_checkpoint_layout=True`` a backward call then rebuilds no rows; needs no scratch; other layers and
+    the default keep the rows kernel.
     Blocks bound by ``inject_shared_expert`` before this call: the scratch also covers ``gptq_moe_shared_decode_workspace_bytes`` of 1..4 tokens."""
     from .moe import QuantMoEExperts
     rows = max_input_length or 2048
@@ -152,7 +155,7 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
             continue
         dev = sub.qweight.device                      # read BEFORE post_init: release_checkpoint_layout moves qweight to pinned host memory, and the scratch belongs to the layer's GPU
         sub.post_init(tiled=decode_copy, release_checkpoint_layout=release_checkpoint_layout, low_bit_rows=(True if low_bit_rows else None),
-                      act_int8=(True if act_int8 else None))
+                      act_int8=(True if act_int8 else None), grad_on_copy=(True if grad_on_copy else None))
         lib = _lib.load()
         # the need is not monotone in M (K splits come and go with the kernel the planner picks): maximum over 1..rows
         parts = getattr(sub, "_parts", None)

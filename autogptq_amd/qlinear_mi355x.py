@@ -147,6 +147,12 @@ class QuantLinear(nn.Module):
     # profiles/act_int8_ab.log, not in this default.  Off: every plan, kernel and result is what it was.
     ACT_INT8 = False
     ACT_INT8_MIN_ROWS = 128
+    # Opt-in: the backward on the decode copy.  grad_input() of a 4-bit fp16 / bf16 layer that carries its copy (group size 32, 64, 128 x 2^n or one group; plain or
+    # act-order) runs grad_copy_kernel (gptq_grad_input_ex with GPTQ_GRAD_ON_COPY: csrc/grad_input_copy.hip), which never reads the checkpoint rows -- a RELEASED
+    # layer then pays no gptq_unprepack_decode in front of its backward.  Same contract as the rows kernel (exact weights, fp32 sums, one rounding), another summation
+    # order.  post_init(grad_on_copy=True) / autogptq_post_init(..., grad_on_copy=True) set it per call; describe_grad_plan(M) says which kernel a call gets.  Every
+    # caller of grad_input() (autograd, fused-QKV parts, forward_multi, mlp_forward under grad, the LoRA wrappers) follows.  Off: nothing changes, not even a launch.
+    GRAD_ON_COPY = False
     _extra_bytes_logged = False
 
     def __init__(
@@ -211,6 +217,7 @@ class QuantLinear(nn.Module):
         self._released = False        # post_init(release_checkpoint_layout=True): qweight lives in pinned host memory, rows are rebuilt on demand
         self._ws_need = {}            # M -> workspace bytes
         self._a8_hold = False         # set by the LoRA wrappers around this layer: the int8-activation path stays off
+        self._grad_flags = 0          # post_init(grad_on_copy=True): GPTQ_GRAD_ON_COPY, the flags of gptq_grad_input_ex
         self._a8_rows = 0             # post_init(act_int8=True) on a layer the int8-activation path takes: its first row count; 0 = off
         self._ws0_mask = 0            # bit M set: M rows (1..63) are known to need no workspace -- what the C++ fast path (cext/fastfwd.cpp) serves; 0 = never
         self.act_order = None         # resolved by post_init
@@ -258,7 +265,7 @@ class QuantLinear(nn.Module):
         return _lib.ZERO_WRAP
 
     # ------------------------------------------------------------------ post_init
-    def post_init(self, temp_dq=None, tiled=None, release_checkpoint_layout=None, low_bit_rows=None, act_int8=None, act_int8_min_rows=None):
+    def post_init(self, temp_dq=None, tiled=None, release_checkpoint_layout=None, low_bit_rows=None, act_int8=None, act_int8_min_rows=None, grad_on_copy=None):
         """Snapshot device pointers and, for act-order layers, derive the group-sorted copy of
         qweight plus the x permutation (side buffers; qweight itself is never modified -- the
         reference's exllama backends overwrite it in place, q4_matrix.cu:160)."""
@@ -270,7 +277,7 @@ class QuantLinear(nn.Module):
                                f"(got {dev}); there is no CPU path.")
         lib = _lib.load()
         if self.g_idx.numel() != self.infeatures:
-            return self._post_init_fused_g_idx(temp_dq, tiled)
+            return self._post_init_fused_g_idx(temp_dq, tiled, grad_on_copy)
         # raw device pointers go to the kernels: every buffer has to live on the module's GPU (a host pointer would fault there)
         for name in ("qzeros", "scales", "g_idx", "bias"):
             t = getattr(self, name)
@@ -355,6 +362,8 @@ class QuantLinear(nn.Module):
         self._rows_need = {}
         self._perm = perm
         self._a8_rows, self._a8_need = 0, {}
+        self._grad_flags = _lib.GRAD_ON_COPY if (self.GRAD_ON_COPY if grad_on_copy is None else grad_on_copy) else 0
+        self._grad_plans = {}
         if act_int8 is None:
             act_int8 = self.ACT_INT8
         if act_int8 and not self._a8_hold:
@@ -404,7 +413,7 @@ class QuantLinear(nn.Module):
                 _lib.check(_lib.load().gptq_unprepack_decode(self._qweight_tiled.data_ptr(), self.infeatures, self.outfeatures, self.bits, buf.data_ptr(),
                                                              _lib.current_stream_handle(dev)))
 
-    def _post_init_fused_g_idx(self, temp_dq, tiled):
+    def _post_init_fused_g_idx(self, temp_dq, tiled, grad_on_copy=None):
         """``len(g_idx) == n * infeatures``: the reference's fused q/k/v module of act-order projections (fused_llama_attn.py:186 concatenates the three g_idx;
         qlinear_cuda.py:300-312 then dequantises column block i -- ``infeatures`` columns wide, its ``num_dim`` -- with g_idx[i K : (i + 1) K]).  Here the n
         column blocks become n internal layers, each with its own activation order (side copies of the column slices: the checkpoint tensors stay as they
@@ -426,7 +435,7 @@ class QuantLinear(nn.Module):
             p.g_idx = self.g_idx[i * K:(i + 1) * K].to(torch.int32).contiguous()
             if self.bias is not None:
                 p.bias = self.bias[i * K:(i + 1) * K].contiguous()
-            p.post_init(temp_dq, tiled)
+            p.post_init(temp_dq, tiled, grad_on_copy=grad_on_copy)
             parts.append(p)
         object.__setattr__(self, "_parts", parts)       # not registered submodules: derived state, never part of state_dict
         self.act_order = any(p.act_order for p in parts)
@@ -655,10 +664,28 @@ class QuantLinear(nn.Module):
         if M:
             lib = _lib.load()
             with torch.cuda.device(self._dev_index):
+                if self._grad_flags:        # opt-in: the kernel on the decode copy where the plan takes the layer (a released one then needs no rows)
+                    if self._released and not self.describe_grad_plan(M).startswith("kernel=grad_copy"):
+                        self._rebuild_rows_now()
+                    _lib.check(lib.gptq_grad_input_ex(self._layer_ref, dy2.data_ptr(), dx.data_ptr(), M, 1 if acc else 0, self._grad_flags,
+                                                      _raw_stream(self._dev_index)))
+                    return dx
                 if self._released:          # the checkpoint rows are rebuilt into the shared scratch right in front of the kernel (stream order)
                     self._rebuild_rows_now()
                 _lib.check(lib.gptq_grad_input(self._layer_ref, dy2.data_ptr(), dx.data_ptr(), M, 1 if acc else 0, _raw_stream(self._dev_index)))
         return dx
+
+    def describe_grad_plan(self, M: int) -> str:
+        """The kernel grad_input() launches for M rows of dY (gptq_describe_grad_input_plan; host-only, cached per M): "kernel=grad_copy bm=.. stages=.. gm=..
+        act=.." or "kernel=grad_rows reason=..".  A fused-QKV module answers for its first column block (the blocks share every property the plan reads)."""
+        if self._layer is None and getattr(self, "_parts", None) is None:
+            self.post_init()
+        if getattr(self, "_parts", None) is not None:
+            return self._parts[0].describe_grad_plan(M)
+        d = self._grad_plans.get(M)
+        if d is None:
+            d = self._grad_plans[M] = _lib.describe_grad_input_plan(self._layer, M, self._grad_flags)
+        return d
 
     # ------------------------------------------------------------------ dequant / unpack helpers
     def dequantize(self) -> torch.Tensor:

@@ -28,7 +28,7 @@
  *          decode launches at 1..4 tokens, and its linear / sigmoid / mul / add tail as one launch at any token count
  *   gptq_moe_backward
  *       <- autograd through the same expert loop (dequantise + torch.matmul per expert), as one routed, grouped call
- *   gptq_grad_input
+ *   gptq_grad_input, gptq_grad_input_ex
  *       <- the backward of the reference's training route: dequantise + torch.matmul under autograd
  *                                                                     qlinear_cuda_old.py:291-355, qlinear_cuda.py:253-317
  *          and the triton backend's QuantLinearFunction.backward      auto_gptq/nn_modules/triton_utils/kernels.py:408-426
@@ -306,6 +306,19 @@ int gptq_dequant(const gptq_layer_t *layer, void *W_out, void *stream);
  * Caller's stream, no allocation, no workspace, capturable in a graph.  GPTQ_ERR_NULL / _SHAPE / _UNSUPPORTED as for gptq_forward
  * (dy and dx must also be 16-byte aligned).  Products and sums in fp32, one rounding at the store (accumulate: dX + the sum in fp32, one rounding). */
 int gptq_grad_input(const gptq_layer_t *layer, const void *dy, void *dx, int M, int accumulate, void *stream);
+/* The same product with `flags`.  0: gptq_grad_input, call for call.  GPTQ_GRAD_ON_COPY (opt-in): a 4-bit fp16 / bf16 layer that carries its decode copy
+ * (qweight_tiled / qconst_tiled, 16-column strips; act-order layers: + perm), with a group size of 32, 64, 128 times a power of two or one group, runs
+ * grad_copy_kernel (csrc/grad_input_copy.hip), which reads the copy, its constants, perm and dY ONLY: layer->qweight may be NULL then (a layer whose checkpoint
+ * rows are not on the device needs no gptq_unprepack_decode in front of its backward).  Same contract: every weight is T(s * float(q - z)) as gptq_dequant
+ * writes it, products and sums in fp32, one rounding at the store, accumulate adds the old dX in fp32 first; no workspace, no atomics, fixed summation order,
+ * capturable.  A layer that does not qualify (2, 3, 8 bits, fp32, no copy, another group size) runs gptq_grad_input's kernel, and needs qweight.  Same
+ * argument checks and status codes as gptq_grad_input; unknown flag bits: GPTQ_ERR_UNSUPPORTED. */
+#define GPTQ_GRAD_ON_COPY 1
+int gptq_grad_input_ex(const gptq_layer_t *layer, const void *dy, void *dx, int M, int accumulate, int flags, void *stream);
+/* Host-only: what gptq_grad_input_ex would launch for (layer, M, flags) --
+ *   "kernel=grad_copy bm=<64|128> stages=<N / 64, rounded up> gm=<0|1|2> act=<0|1>"   or   "kernel=grad_rows reason=<flag_off|bits|dtype|no_copy|group_size>".
+ * The layer's pointers are compared with NULL, never dereferenced; qweight may be NULL. */
+int gptq_describe_grad_input_plan(const gptq_layer_t *layer, int M, int flags, char *out, size_t out_bytes);
 
 /* LoRA adapters beside a quantized layer (the reference's GPTQLoraLinear, auto_gptq/utils/peft_utils.py:58-123, whose merge() must refuse: W is int4 on a
  * fixed grid, so W + s B A has no packed form and every call pays the adapter branch at run time).  For each adapter i of a call:

@@ -19,6 +19,9 @@ ap.add_argument("--reps", type=int, default=10)
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--quick", action="store_true", help="fp16 4-bit g128 sequential on the 7B shapes only")
 ap.add_argument("--launch", default="", help="K,N,M[,act]: only 20 plain launches of the fp16 4-bit g128 kernel (a target for rocprofv3 --pmc)")
+ap.add_argument("--on-copy", action="store_true", help="with --launch: the kernel on the decode copy (post_init(grad_on_copy=True))")
+ap.add_argument("--ab", action="store_true", help="rows kernel against the kernel on the decode copy, same session (profiles/grad_copy_ab.log)")
+ap.add_argument("--ab-rounds", type=int, default=9)
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 lib = _lib.load()
@@ -73,9 +76,71 @@ def run(fam, K, N, dtype, bits, gs, act):
         del forms
 
 
+def ab():
+    """--ab: the rows kernel (gptq_grad_input) against the kernel on the decode copy (gptq_grad_input_ex, GPTQ_GRAD_ON_COPY) in ONE session, beside (a) dense and
+    (b) deq + mm, on the four layers of DESIGN 4.7's table at M = 64 / 512 / 2048; for the plain layers also RELEASED (one copy on the device): QuantLinear.grad_input
+    without the flag (rebuild pass + rows kernel) and with it.  One call per timing, HIP events around it, a 512 MiB write in front of every call (weights, dY
+    and dX out of the caches); the forms alternate inside each of --ab-rounds rounds; reported: median us and the spread (min .. max) of the rounds."""
+    flush = torch.empty(512 << 20, dtype=torch.uint8, device=dev)
+    st = lambda: torch.cuda.current_stream().cuda_stream
+
+    def one(fn):
+        flush.fill_(1)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3
+
+    layers = [(4096, 4096, torch.float16, False), (4096, 11008, torch.float16, False), (11008, 4096, torch.float16, False), (4096, 11008, torch.bfloat16, True)]
+    for K, N, dtype, act in layers:
+        q = bench.make_layer(K, N, dev, act_order=act, dtype=dtype, seed=K + N)
+        q.post_init(grad_on_copy=True)
+        W16 = q.dequantize()
+        rel = {}
+        if not act:                                        # (act-order layers keep their rows: nothing to release)
+            for flag in (False, True):
+                rel[flag] = bench.make_layer(K, N, dev, dtype=dtype, seed=K + N)
+                rel[flag].post_init(release_checkpoint_layout=True, grad_on_copy=flag)
+        for M in (64, 512, 2048):
+            dy = (torch.randn(M, N, device=dev) * 0.5).to(dtype)
+            dx, dxc, ref = (torch.empty(M, K, dtype=dtype, device=dev) for _ in range(3))
+            forms = {
+                "rows": lambda: _lib.check(lib.gptq_grad_input(q._layer_ref, dy.data_ptr(), dx.data_ptr(), M, 0, st())),
+                "copy": lambda: _lib.check(lib.gptq_grad_input_ex(q._layer_ref, dy.data_ptr(), dxc.data_ptr(), M, 0, _lib.GRAD_ON_COPY, st())),
+                "dense": lambda: torch.matmul(dy, W16.t(), out=ref),
+                "deq+mm": lambda: torch.matmul(dy, q.dequantize().t()),
+            }
+            if rel:
+                forms["released rebuild+rows"] = lambda: rel[False].grad_input(dy)
+                forms["released copy"] = lambda: rel[True].grad_input(dy)
+            assert q.describe_grad_plan(M).startswith("kernel=grad_copy") and (not rel or rel[True].describe_grad_plan(M).startswith("kernel=grad_copy"))
+            t = {k: [] for k in forms}
+            for fn in forms.values():
+                fn()                                       # warm-up of every form and shape
+            for _ in range(args.ab_rounds):
+                for k, fn in forms.items():
+                    t[k].append(one(fn))
+            err = float((dxc.float() - ref.float()).abs().max() / ref.float().abs().max().clamp_min(1e-30))
+            med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+            cells = "  ".join(f"{k} {med[k]:7.1f} ({min(v):.1f} .. {max(v):.1f})" for k, v in t.items())
+            gap = med["rows"] - med["copy"]
+            spread = max(max(t[k]) - min(t[k]) for k in ("rows", "copy"))
+            print(f"{K:5d}x{N:<5d} {str(dtype)[6:]:8s} {'act' if act else 'seq'} M={M:5d} [{q.describe_grad_plan(M)}]  {cells}  rows/copy {med['rows'] / med['copy']:.2f} "
+                  f"({'beyond' if gap > spread else 'WITHIN'} the repeat spread)  copy {2.0 * M * N * K / med['copy'] / 1e-6 / PEAK:.2f} of peak  "
+                  f"same bits as rows: {bool(torch.equal(dx, dxc))}  rel.err vs dense {err:.1e}", flush=True)
+
+
+if args.ab:
+    ab()
+    sys.exit(0)
+
 if args.launch:
     K, N, M, *rest = (int(v) for v in args.launch.split(","))
     q = bench.make_layer(K, N, dev, act_order=bool(rest and rest[0]), seed=1)
+    if args.on_copy:
+        q.post_init(grad_on_copy=True)
     dy = (torch.randn(M, N, device=dev) * 0.5).half()
     for _ in range(20):
         q.grad_input(dy)

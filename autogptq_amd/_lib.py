@@ -42,6 +42,7 @@ EXPORTS = (
     "gptq_moe_batch_workspace_bytes", "gptq_moe_batch_forward", "gptq_describe_moe_batch_plan",
     "gptq_moe_prefill_workspace_bytes", "gptq_moe_prefill_forward", "gptq_describe_moe_prefill_plan",
     "gptq_moe_grad_table_bytes", "gptq_moe_build_grad_table", "gptq_moe_backward_workspace_bytes", "gptq_moe_backward", "gptq_describe_moe_backward_plan",
+    "gptq_moe_backward_ex", "gptq_describe_moe_backward_plan_ex",
     "gptq_lora_down", "gptq_lora_up", "gptq_lora_apply", "gptq_describe_lora_plan",
     "gptq_lora_backward_workspace_bytes", "gptq_lora_backward", "gptq_describe_lora_backward_plan",
     "gptq_adapter_route_bytes", "gptq_adapter_route", "gptq_adapter_rows_apply", "gptq_describe_adapter_rows_plan",
@@ -248,6 +249,9 @@ def load() -> ctypes.CDLL:
     lib.gptq_moe_backward.argtypes = [MP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_size_t, c_void_p]
     lib.gptq_describe_moe_backward_plan.argtypes = [MP, c_int, c_int, c_char_p, c_size_t]
+    lib.gptq_moe_backward_ex.argtypes = [MP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_size_t, c_int, c_void_p]
+    lib.gptq_describe_moe_backward_plan_ex.argtypes = [MP, c_int, c_int, c_int, c_char_p, c_size_t]
     lib.gptq_moe_router.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.gptq_describe_moe_router_plan.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int, c_char_p, c_size_t]
     lib.gptq_moe_router_grouped.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_float, c_int, c_int,
@@ -400,6 +404,12 @@ def describe_moe_plan(moe: "GptqMoe", T: int, topk: int) -> dict:
 def describe_moe_backward_plan(moe: "GptqMoe", T: int, topk: int) -> dict:
     """What gptq_moe_backward would run for (moe, T, topk): path=grouped_backward with its grids, or path=per_expert with the reason (host-only query)."""
     return _describe("gptq_describe_moe_backward_plan", ctypes.byref(moe), T, topk)
+
+
+def describe_moe_backward_plan_ex(moe: "GptqMoe", T: int, topk: int, flags: int = 0) -> dict:
+    """What gptq_moe_backward_ex would run for (moe, T, topk, flags): with GRAD_ON_COPY path=grouped_backward_copy (up_launches, gm, act, ...) where the
+    experts' decode copies serve the two transposed stages, else path=grouped_backward with copy_reason (host-only query)."""
+    return _describe("gptq_describe_moe_backward_plan_ex", ctypes.byref(moe), T, topk, flags)
 
 
 def describe_moe_decode_plan(moe: "GptqMoe", T: int, topk: int) -> dict:

@@ -1392,19 +1392,24 @@ size_t gptq_moe_backward_workspace_bytes(const gptq_moe_t* m, int T, int topk) {
     return plan_moe_grad(m->E, T, topk, G->K, G->N, G->dtype).bytes;
 }
 
-int gptq_moe_backward(const gptq_moe_t* m, const void* table, const void* grad_table, const void* x, const int64_t* idx, const float* w, const void* dout,
-                      int T, int topk, void* dx, float* dw, void* dgu_out, void* ws, size_t ws_bytes, void* stream) {
+// flags = 0 (gptq_moe_backward): the stages on the checkpoint rows.  GPTQ_GRAD_ON_COPY: on the decode table where plan_moe_grad_copy takes the experts.
+static int moe_backward_impl(const char* fn, const gptq_moe_t* m, const void* table, const void* grad_table, const void* decode_table, const void* x,
+                             const int64_t* idx, const float* w, const void* dout, int T, int topk, void* dx, float* dw, void* dgu_out, void* ws,
+                             size_t ws_bytes, int flags, void* stream) {
+    if (flags & ~GPTQ_GRAD_ON_COPY) return fail(GPTQ_ERR_UNSUPPORTED, "unknown %s flags 0x%x", fn, flags);
     if (int rc = moe_check(MOE_GROUPED, m, T, topk)) return rc;
     if (T == 0) return GPTQ_OK;
     if (!dx && !dw) return fail(GPTQ_ERR_NULL, "dx and dw are both NULL: nothing to compute");
-    if (!table || !grad_table || !x || !idx || !w || !dout)
-        return fail(GPTQ_ERR_NULL, "table / grad_table / x / topk_idx / topk_w / dout must be non-NULL");
+    const MoeGradCopyPlan cp = plan_moe_grad_copy(*m, flags);
+    if (cp.ok ? (!table || !decode_table || !x || !idx || !w || !dout) : (!table || !grad_table || !x || !idx || !w || !dout))
+        return fail(GPTQ_ERR_NULL, "table / %s / x / topk_idx / topk_w / dout must be non-NULL", cp.ok ? "decode_table" : "grad_table");
     if (((uintptr_t)x | (uintptr_t)dout | (uintptr_t)dx | (uintptr_t)ws) & 15)
         return fail(GPTQ_ERR_UNSUPPORTED, "x / dout / dx / workspace must be 16-byte aligned");
     const gptq_layer_t* G = m->gate[0];
     const MoeGradPlan pl = plan_moe_grad(m->E, T, topk, G->K, G->N, G->dtype);
     if (!ws || ws_bytes < pl.bytes) return fail(GPTQ_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", pl.bytes, ws ? ws_bytes : (size_t)0);
-    hipError_t e = launch_moe_grad(*m, table, grad_table, pl, x, idx, w, dout, T, topk, dx, dw, (char*)ws, (hipStream_t)stream);
+    hipError_t e = launch_moe_grad(*m, table, grad_table, pl, x, idx, w, dout, T, topk, dx, dw, (char*)ws, (hipStream_t)stream, cp.ok ? &cp : nullptr,
+                                   decode_table);
     if (e != hipSuccess) return hip_fail(e, "gptq_moe_backward launch");
     if (dgu_out) {
         const size_t R = (size_t)T * topk, gb = R * G->N * dtype_size(G->dtype);
@@ -1416,14 +1421,45 @@ int gptq_moe_backward(const gptq_moe_t* m, const void* table, const void* grad_t
     return GPTQ_OK;
 }
 
-int gptq_describe_moe_backward_plan(const gptq_moe_t* m, int T, int topk, char* out, size_t out_bytes) {
+int gptq_moe_backward(const gptq_moe_t* m, const void* table, const void* grad_table, const void* x, const int64_t* idx, const float* w, const void* dout,
+                      int T, int topk, void* dx, float* dw, void* dgu_out, void* ws, size_t ws_bytes, void* stream) {
+    return moe_backward_impl("gptq_moe_backward", m, table, grad_table, nullptr, x, idx, w, dout, T, topk, dx, dw, dgu_out, ws, ws_bytes, 0, stream);
+}
+
+int gptq_moe_backward_ex(const gptq_moe_t* m, const void* table, const void* grad_table, const void* decode_table, const void* x, const int64_t* idx,
+                         const float* w, const void* dout, int T, int topk, void* dx, float* dw, void* dgu_out, void* ws, size_t ws_bytes, int flags,
+                         void* stream) {
+    return moe_backward_impl("gptq_moe_backward_ex", m, table, grad_table, decode_table, x, idx, w, dout, T, topk, dx, dw, dgu_out, ws, ws_bytes, flags,
+                             stream);
+}
+
+// flags = 0: gptq_describe_moe_backward_plan's line, byte for byte.  With the flag: the copy form's line, or the rows form's with the reason it stays.
+static int describe_moe_backward_impl(const gptq_moe_t* m, int T, int topk, int flags, char* out, size_t out_bytes) {
     if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out is NULL");
+    if (flags & ~GPTQ_GRAD_ON_COPY) return fail(GPTQ_ERR_UNSUPPORTED, "unknown gptq_describe_moe_backward_plan_ex flags 0x%x", flags);
     if (moe_check(MOE_GROUPED, m, T, topk)) return describe_decline(out, out_bytes, "per_expert");
     const gptq_layer_t* G = m->gate[0];
     const MoeGradPlan pl = plan_moe_grad(m->E, T, topk, G->K, G->N, G->dtype);
-    snprintf(out, out_bytes, "path=grouped_backward tiles=%d launches=%d wg_recompute=%ld wg_down=%ld wg_up=%ld", pl.tiles, T > 0 ? 5 : 0,
-             (long)pl.tiles * (G->N / 64), (long)pl.tiles * pl.nblk_i, (long)pl.tiles * pl.nblk_h);
+    const long wg_re = (long)pl.tiles * (G->N / 64), wg_down = (long)pl.tiles * pl.nblk_i, wg_up = (long)pl.tiles * pl.nblk_h;
+    const MoeGradCopyPlan cp = plan_moe_grad_copy(*m, flags);
+    if (cp.ok)
+        snprintf(out, out_bytes, "path=grouped_backward_copy tiles=%d launches=%d up_launches=%d gm=%d act=%d gm_down=%d wg_recompute=%ld wg_down=%ld wg_up=%ld",
+                 pl.tiles, T > 0 ? 4 + cp.up_launches : 0, cp.up_launches, cp.gm1, cp.act ? 1 : 0, cp.gm2, wg_re, wg_down, wg_up);
+    else if (flags)
+        snprintf(out, out_bytes, "path=grouped_backward tiles=%d launches=%d wg_recompute=%ld wg_down=%ld wg_up=%ld copy_reason=%s", pl.tiles, T > 0 ? 5 : 0,
+                 wg_re, wg_down, wg_up, cp.why);
+    else
+        snprintf(out, out_bytes, "path=grouped_backward tiles=%d launches=%d wg_recompute=%ld wg_down=%ld wg_up=%ld", pl.tiles, T > 0 ? 5 : 0, wg_re, wg_down,
+                 wg_up);
     return GPTQ_OK;
+}
+
+int gptq_describe_moe_backward_plan(const gptq_moe_t* m, int T, int topk, char* out, size_t out_bytes) {
+    return describe_moe_backward_impl(m, T, topk, 0, out, out_bytes);
+}
+
+int gptq_describe_moe_backward_plan_ex(const gptq_moe_t* m, int T, int topk, int flags, char* out, size_t out_bytes) {
+    return describe_moe_backward_impl(m, T, topk, flags, out, out_bytes);
 }
 
 // ---- the same layers at 1..4 tokens on the experts' decode copy (moe_decode.hip) ----

@@ -26,7 +26,8 @@
 //            re-sequenced rows, so column k' of the tile is dX[:, perm[k']] (gptq_permute_columns: x_seq[:, i] = x[:, perm[i]]): each thread loads its 8 perm
 //            entries once and stores 2-byte elements to the scattered columns (accumulate: the old value from the same address first).  No g_idx lookups,
 //            no pre- or post-pass.
-// BM, the group mode, act-order and accumulate are launch-uniform: one kernel per dtype.
+// BM, the group mode, act-order and accumulate are launch-uniform: one kernel per dtype.  So is the GROUPED form (moe_grad_copy.cuh, included behind the dense
+// body): the down and the up stage of the routed layer's backward on the experts' copies, behind the mode word of the kernel's second argument.
 #include "common.cuh"
 #include "mma_dequant.cuh"
 #include "launch.h"
@@ -210,13 +211,25 @@ __device__ __forceinline__ void run(const Args& p, char* smem, int m0, int kt) {
     }
 }
 
+}  // namespace gcopy
+}  // namespace gptq
+
+#include "moe_grad_copy.cuh"
+
+namespace gptq {
+namespace gcopy {
+
 template <typename T>
-__global__ void __launch_bounds__(THREADS, 2) grad_copy_kernel(Args p) {
+__global__ void __launch_bounds__(THREADS, 2) grad_copy_kernel(Args p, Grouped q) {
     __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
-    const int b = xcd_remap(blockIdx.x, gridDim.x);        // consecutive k tiles of one row block on one XCD: they share dY in its L2
-    const int kt = b % p.nkt, mt = b / p.nkt;
-    if (p.bm == 128) run<T, 4>(p, smem, mt * 128, kt);
-    else run<T, 2>(p, smem, mt * 64, kt);
+    if (__builtin_expect(q.mode == GR_DENSE, 1)) {         // (launch-uniform; the dense bodies first in the code, as they were)
+        const int b = xcd_remap(blockIdx.x, gridDim.x);    // consecutive k tiles of one row block on one XCD: they share dY in its L2
+        const int kt = b % p.nkt, mt = b / p.nkt;
+        if (p.bm == 128) run<T, 4>(p, smem, mt * 128, kt);
+        else run<T, 2>(p, smem, mt * 64, kt);
+        return;
+    }
+    run_grouped<T>(q, smem);
 }
 
 }  // namespace gcopy
@@ -260,9 +273,66 @@ hipError_t launch_grad_copy(const gptq_layer_t& L, const GradCopyPlan& pl, const
     p.M = M, p.K = L.K, p.N = L.N, p.strips = L.N / GPTQ_STRIP_COLS, p.chunks = pl.chunks, p.groups = pl.groups, p.gshift = pl.gshift, p.gm = pl.gm;
     p.bm = pl.bm, p.nkt = pl.chunks, p.accumulate = accumulate ? 1 : 0;
     const dim3 grid((unsigned)pl.blocks), block(gcopy::THREADS);
-    if (L.dtype == GPTQ_F16) hipLaunchKernelGGL(gcopy::grad_copy_kernel<f16>, grid, block, 0, st, p);
-    else hipLaunchKernelGGL(gcopy::grad_copy_kernel<bf16>, grid, block, 0, st, p);
+    gcopy::Grouped q{};                                    // GR_DENSE
+    if (L.dtype == GPTQ_F16) hipLaunchKernelGGL(gcopy::grad_copy_kernel<f16>, grid, block, 0, st, p, q);
+    else hipLaunchKernelGGL(gcopy::grad_copy_kernel<bf16>, grid, block, 0, st, p, q);
     return hipGetLastError();
+}
+
+// The grouped form's qualification: every layer of the three projections by the dense rule above (4 bits -- mixed widths are declined as a whole --, fp16 /
+// bf16, a 16-column copy, the group sizes), its copies 16-byte aligned.  W1 and W3 share one up-stage launch where every expert's gate and up name the same
+// output columns: both plain, or one perm pointer.
+MoeGradCopyPlan plan_moe_grad_copy(const gptq_moe_t& m, int flags) {
+    MoeGradCopyPlan pl{};
+    pl.up_launches = 1;
+    const gptq_layer_t* const* proj[3] = {m.gate, m.up, m.down};
+    auto cols = [](const gptq_layer_t& L) { return L.qweight_seq ? L.perm : nullptr; };      // as the decode table's entry names them
+    for (int ps = 0; ps < 3; ++ps)
+        for (int e = 0; e < m.E; ++e) {
+            const gptq_layer_t& L = *proj[ps][e];
+            const GradCopyPlan lp = plan_grad_copy(L, gcopy::GBM, flags);
+            if (!lp.ok) { pl.why = lp.why; return pl; }
+            if (((uintptr_t)L.qweight_tiled | (uintptr_t)L.qconst_tiled) & 15) { pl.why = "no_copy"; return pl; }
+            pl.act = pl.act || lp.act;
+            if (e == 0 && ps == 0) pl.gm1 = lp.gm, pl.gshift1 = lp.gshift, pl.groups1 = lp.groups;
+            if (e == 0 && ps == 2) pl.gm2 = lp.gm, pl.gshift2 = lp.gshift, pl.groups2 = lp.groups;
+        }
+    for (int e = 0; e < m.E; ++e)
+        if (cols(*m.gate[e]) != cols(*m.up[e])) pl.up_launches = 2;
+    pl.ok = true;
+    return pl;
+}
+
+// The down stage and the up stage (one launch, or W1 then W3 in stream order) of launch_moe_grad on the decode table.
+hipError_t launch_moe_grad_copy_stages(const gptq_moe_t& m, const MoeGradCopyPlan& cp, const void* decode_table, const MoeGradPlan& pl, const void* dout,
+                                       const float* w, int topk, bool want_dx, bool want_dw, char* ws, hipStream_t st) {
+    if (!cp.ok || !decode_table) return hipErrorInvalidValue;
+    const gptq_layer_t& G = *m.gate[0];
+    gcopy::Args none{};
+    gcopy::Grouped q{};
+    q.E = m.E; q.topk = topk; q.H = G.K; q.I = G.N;
+    q.table = (const moerows::Entry*)decode_table;
+    q.dout = dout; q.w = w;
+    q.row_assign = (const int*)(ws + pl.off_rows); q.tile_count = (const int*)(ws + pl.off_tile_count); q.tiles = (const int4*)(ws + pl.off_tiles);
+    q.g = ws + pl.off_g; q.u = ws + pl.off_u;
+    q.dwp = want_dw ? (float*)(ws + pl.off_dwp) : nullptr;
+    q.dxr = (float*)(ws + pl.off_dxr);
+    q.gm1 = cp.gm1; q.gshift1 = cp.gshift1; q.groups1 = cp.groups1;
+    q.gm2 = cp.gm2; q.gshift2 = cp.gshift2; q.groups2 = cp.groups2;
+    auto stage = [&](int mode, int nkt) -> hipError_t {
+        const long blocks = (long)pl.tiles * nkt;
+        if (blocks <= 0) return hipSuccess;
+        if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
+        q.mode = mode; q.nkt = nkt;
+        if (G.dtype == GPTQ_F16) hipLaunchKernelGGL(gcopy::grad_copy_kernel<f16>, dim3((unsigned)blocks), dim3(gcopy::THREADS), 0, st, none, q);
+        else hipLaunchKernelGGL(gcopy::grad_copy_kernel<bf16>, dim3((unsigned)blocks), dim3(gcopy::THREADS), 0, st, none, q);
+        return hipGetLastError();
+    };
+    hipError_t e = stage(gcopy::GR_DOWN, pl.nblk_i);
+    if (e != hipSuccess || !want_dx) return e;
+    if (cp.up_launches == 1) return stage(gcopy::GR_UP, pl.nblk_h);
+    if ((e = stage(gcopy::GR_UP1, pl.nblk_h)) != hipSuccess) return e;
+    return stage(gcopy::GR_UP3, pl.nblk_h);
 }
 
 }  // namespace gptq

@@ -282,8 +282,22 @@ struct MoeGradPlan : RouteLayout {
 MoeGradPlan plan_moe_grad(int E, int T, int topk, int H, int I, int dtype);
 size_t moe_grad_table_entry_bytes();
 void moe_grad_table_entry(const gptq_layer_t& L, void* dst);
+// grad_input_copy.hip / moe_grad_copy.cuh: the down and up stages on the experts' decode copies (opt-in: GPTQ_GRAD_ON_COPY in gptq_moe_backward_ex's
+// flags), the grouped mode of grad_copy_kernel; routing, recompute and combine stay moe_grad.hip's
+struct MoeGradCopyPlan {
+    bool ok;
+    const char* why;         // !ok: flag_off / bits / dtype / no_copy / group_size
+    bool act;                // some expert scatters its output columns through perm
+    int up_launches;         // 1: W1 and W3 into one set of accumulators; 2: gate and up name different columns (W1 stores, W3 continues from DXR)
+    int gm1, gshift1, groups1, gm2, gshift2, groups2;      // GradCopyPlan's group mode of the gate / up and of the down copies
+};
+MoeGradCopyPlan plan_moe_grad_copy(const gptq_moe_t& m, int flags);
+hipError_t launch_moe_grad_copy_stages(const gptq_moe_t& m, const MoeGradCopyPlan& cp, const void* decode_table, const MoeGradPlan& pl, const void* dout,
+                                       const float* w, int topk, bool want_dx, bool want_dw, char* ws, hipStream_t st);
+// cp NULL: the stages on the checkpoint rows (grad_table); else on the decode table
 hipError_t launch_moe_grad(const gptq_moe_t& m, const void* table, const void* grad_table, const MoeGradPlan& pl, const void* x, const int64_t* idx,
-                           const float* w, const void* dout, int T, int topk, void* dx, float* dw, char* ws, hipStream_t st);
+                           const float* w, const void* dout, int T, int topk, void* dx, float* dw, char* ws, hipStream_t st,
+                           const MoeGradCopyPlan* cp = nullptr, const void* decode_table = nullptr);
 // moe_decode.hip: the same layer at 1..4 tokens on the experts' decode copy (gptq_moe_decode_forward): gate|up + silu * mul, down + combine -- two launches
 struct MoeDecodePlan {
     bool ok;                                        // the staged rows and constants fit the LDS

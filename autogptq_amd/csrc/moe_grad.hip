@@ -25,6 +25,8 @@
 // v_mfma_f32_16x16x32_{f16,bf16}, two LDS buffers and one barrier per stage.  What differs: the A rows come from a per-row pointer (a row past the tile is
 // zero, and 16-row blocks the tile does not have are skipped), the weight pointers come from the expert's entry of a device table, and the epilogue is the
 // stage's own.  The tile is always 64 rows, so the summation order of every output element is that of the stages: independent of the routing.
+// gptq_moe_backward_ex with GPTQ_GRAD_ON_COPY runs launches 3 and 4 on the experts' decode copies instead (moe_grad_copy.cuh: the grouped mode of
+// grad_copy_kernel); launches 1, 2 and 5 and the workspace are these.
 #include <string.h>
 
 #include <algorithm>
@@ -399,7 +401,8 @@ void moe_grad_table_entry(const gptq_layer_t& L, void* dst) {
 }
 
 hipError_t launch_moe_grad(const gptq_moe_t& m, const void* table, const void* grad_table, const MoeGradPlan& pl, const void* x, const int64_t* idx,
-                           const float* w, const void* dout, int T, int topk, void* dx, float* dw, char* ws, hipStream_t st) {
+                           const float* w, const void* dout, int T, int topk, void* dx, float* dw, char* ws, hipStream_t st, const MoeGradCopyPlan* cp,
+                           const void* decode_table) {
     const gptq_layer_t& G = *m.gate[0];
     const gptq_layer_t& D = *m.down[0];
     const int E = m.E, H = G.K, I = G.N;
@@ -427,8 +430,11 @@ hipError_t launch_moe_grad(const gptq_moe_t& m, const void* table, const void* g
         else hipLaunchKernelGGL(mgrad::moe_grad_kernel<bf16>, dim3((unsigned)blocks), dim3(mgrad::THREADS), 0, st, s);
         return hipGetLastError();
     };
-    if ((e = stage(a, (long)pl.tiles * pl.nblk_i)) != hipSuccess) return e;
-    if (dx) {
+    if (cp) {      // the two stages on the experts' decode copies (grad_input_copy.hip): the same G / U / dw partials / DXR in, the same out
+        if ((e = launch_moe_grad_copy_stages(m, *cp, decode_table, pl, dout, w, topk, dx != nullptr, dw != nullptr, ws, st)) != hipSuccess) return e;
+    } else if ((e = stage(a, (long)pl.tiles * pl.nblk_i)) != hipSuccess) {
+        return e;
+    } else if (dx) {
         a.up = 1; a.nkt = pl.nblk_h;
         if ((e = stage(a, (long)pl.tiles * pl.nblk_h)) != hipSuccess) return e;
     }

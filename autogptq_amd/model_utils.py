@@ -89,7 +89,8 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
                        release_checkpoint_layout: Optional[bool] = None, decode_copy: Optional[bool] = None,
                        expert_decode_copy: bool = False, expert_batched_decode: bool = False, expert_backward: bool = False, expert_low_bit: bool = False,
                        expert_prefill: bool = False, expert_low_bit_decode: bool = False, expert_low_bit_batch: bool = False,
-                       expert_low_bit_prefill: bool = False, low_bit_rows: bool = False, act_int8: bool = False, grad_on_copy: bool = False) -> nn.Module:
+                       expert_low_bit_prefill: bool = False, low_bit_rows: bool = False, act_int8: bool = False, grad_on_copy: bool = False,
+                       expert_backward_on_copy: bool = False) -> nn.Module:
     """post_init every mi355x layer and size the per-device scratch once (so forward never allocates; needed before hipGraph
     capture).  ``max_input_length`` bounds the rows M the scratch is sized for (default 2048, the reference's exllama default).
     Memory (the model-level switches for what post_init keeps next to the checkpoint tensors): ``decode_copy=False`` builds no decode copy (1x the packed
@@ -126,6 +127,9 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
     ``grad_on_copy=True`` (``QuantLinear.post_init(grad_on_copy=True)``): the input gradient of 4-bit fp16 / bf16 layers with a decode copy runs on that copy
     (gptq_grad_input_ex, grad_copy_kernel) -- with ``release_checkpoint_layout=True`` a backward call then rebuilds no rows; needs no scratch; other layers and
     the default keep the rows kernel.
+    ``expert_backward_on_copy=True`` (with ``expert_backward=True``; sets ``QuantMoEExperts.backward_on_copy`` before the module's ``post_init(backward=True)``; implies the expert
+    decode copy): the two transposed stages of the grouped backward of 4-bit fp16 / bf16 experts run on that copy (gptq_moe_backward_ex, the grouped mode
+    of grad_copy_kernel); the scratch is the same; other experts and the default keep the checkpoint rows.
     Blocks bound by ``inject_shared_expert`` before this call: the scratch also covers ``gptq_moe_shared_decode_workspace_bytes`` of 1..4 tokens."""
     from .moe import QuantMoEExperts
     rows = max_input_length or 2048
@@ -140,6 +144,8 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
                 sub.low_bit_batch = True
             if expert_low_bit_prefill:
                 sub.low_bit_prefill = True
+            if expert_backward_on_copy:
+                sub.backward_on_copy = True
             sub.post_init(decode_copy=expert_decode_copy, batch=expert_batched_decode, backward=expert_backward, low_bit=expert_low_bit,
                           prefill=expert_prefill, low_bit_decode=expert_low_bit_decode)
             for e in range(sub.num_experts):

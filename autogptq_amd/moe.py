@@ -38,7 +38,9 @@ The per-expert composition serves what the grouped kernels do not take (2- / 3-b
 sizes, raw act-order), CPU tensors (which ``QuantLinear`` refuses), and -- by default -- calls under grad where ``hidden_states`` or ``top_k_weights`` require grad: training through the experts gets
 dX and the router-weight gradient from the existing backward of ``QuantLinear``.  After ``post_init(backward=True)`` such a call is ONE autograd node
 instead: the forward runs the ordinary no-grad path, the backward is one gptq_moe_backward call (route, recompute of gate / up, two grouped transposed
-dequant-GEMM stages on the checkpoint rows, combine -- five launches, nothing saved but the inputs).
+dequant-GEMM stages on the checkpoint rows, combine -- five launches, nothing saved but the inputs).  ``backward_on_copy = True`` (an attribute, set before ``post_init(backward=True)``)
+moves the two transposed stages of 4-bit fp16 / bf16 experts onto the experts' decode copy (gptq_moe_backward_ex with GPTQ_GRAD_ON_COPY: the grouped mode
+of grad_copy_kernel, ``last_plan["backward"] == "grouped_copy"``; opt-in).
 """
 from __future__ import annotations
 
@@ -52,7 +54,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .qlinear_mi355x import QuantLinear, _raw_stream, exchange_tick, forward_multi, mlp_forward, reserve_workspace
+from .qlinear_mi355x import QuantLinear, _raw_stream, exchange_tick, forward_multi, mlp_forward, reserve_workspace, share_act_order
 
 logger = getLogger(__name__)
 
@@ -120,6 +122,7 @@ class QuantMoEExperts(nn.Module):
         # the post_init keywords as the last post_init settled them: what _ensure_init replays (a declined switch is said once, not at every move)
         self._switches = dict(decode_copy=False, batch=False, backward=False, low_bit=False, prefill=False, low_bit_decode=False)
         self.low_bit_batch = False                  # the switch of the batch path for 2- / 3-bit experts: set before post_init (read there; see its docstring)
+        self.backward_on_copy = False               # the switch of the backward on the decode copy: set before post_init(backward=True), like low_bit_batch
         self.low_bit_prefill = False                # the switch of the prefill path for 2- / 3-bit experts: set before post_init, like low_bit_batch
         self.batch_max_tokens = 64
         self.low_bit_batch_max_tokens = 64          # 2- / 3-bit experts with low_bit_batch = True: the batch path for 5..this many tokens (the kernels take 64)
@@ -140,6 +143,7 @@ class QuantMoEExperts(nn.Module):
         self._moe_batch = None                      # the struct of the batch / prefill entry points where it is not _moe (see _moe_of)
         self._decode_table = None
         self._grad_table = None
+        self._backward_on_copy = False              # post_init settled on the backward's copy form
         self._live = frozenset()                    # the copy paths ("decode", "batch", "prefill") that post_init settled on: what plan() may name
         self.decode_copy_bytes = 0
         self._keep = ()
@@ -183,11 +187,18 @@ class QuantMoEExperts(nn.Module):
         the grouped path -- for 2- / 3-bit experts only with ``low_bit=True`` (forward and, with ``backward=True``, backward; nothing changes for
         4- / 8-bit experts), else the per-expert composition.  ``backward=True``: calls under grad whose ``hidden_states`` or ``top_k_weights`` require
         grad run the grouped backward (``last_plan["backward"] == "grouped"``: one autograd node, one gptq_moe_backward call on a pointer table of its
-        own); experts the backward plan declines log the reason and keep the composition.  A checkpoint-layout release does not apply to expert layers."""
+        own); experts the backward plan declines log the reason and keep the composition.  The attribute ``backward_on_copy = True`` (set before this call, with ``backward=True``; opt-in) implies
+        ``decode_copy=True`` and runs the backward's two transposed stages on that copy (gptq_moe_backward_ex with GPTQ_GRAD_ON_COPY,
+        ``last_plan["backward"] == "grouped_copy"``): 4-bit fp16 / bf16 experts, group_size 32, 64, 128 times a power of two or one group; act-order gate
+        and up layers of one g_idx are pointed at one ``perm`` buffer (``share_act_order``) so that W1 and W3 share one up-stage launch.  Experts the
+        copy plan declines log the reason once and keep the backward on the checkpoint rows.  A checkpoint-layout release does not apply to expert
+        layers."""
         dev = self[0].layers()[0].qweight.device
         if dev.type != "cuda":
             raise RuntimeError(f"mi355x QuantMoEExperts.post_init needs the module on a ROCm GPU device (got {dev}); there is no CPU path.")
         low = self.bits in (2, 3)
+        on_copy = bool(self.backward_on_copy) and bool(backward)
+        decode_copy = bool(decode_copy) or on_copy
         sw = dict(decode_copy=bool(decode_copy), batch=bool(batch), backward=bool(backward), low_bit=bool(low_bit), prefill=bool(prefill),
                   low_bit_decode=bool(low_bit_decode))
         want_decode = sw["decode_copy"] or (sw["low_bit_decode"] and low)
@@ -267,6 +278,17 @@ class QuantMoEExperts(nn.Module):
             else:
                 drop(getattr(_PATHS[declined], "low_switch" if low else "switch"), why)
                 live.discard(declined)
+        if on_copy and gplan is not None and gplan["path"] == "grouped_backward":
+            for e in range(self.num_experts):
+                share_act_order(list(self[e].layers()[:2]))          # gate and up of one g_idx: one perm pointer, one up-stage launch
+            cplan = _lib.describe_moe_backward_plan_ex(m, 1, self.top_k, _lib.GRAD_ON_COPY)
+            if cplan["path"] != "grouped_backward_copy":
+                logger.warning("QuantMoEExperts.backward_on_copy = True has no effect for these experts (%s): the backward keeps the checkpoint "
+                               "rows", str(cplan.get("copy_reason", cplan.get("reason", ""))).replace("_", " "))
+                on_copy = False
+        else:
+            on_copy = False
+        self._backward_on_copy = on_copy                     # (the attribute stays as it was set: a declined set says so again after a move)
         lib = _lib.load()
         table = torch.zeros(max(1, int(lib.gptq_moe_table_bytes(self.num_experts))), dtype=torch.uint8, device=dev)
         self._moe, self._moe_batch, self._keep, self._plans = m, mb, (arrs, table, gate, up, down), {}
@@ -483,7 +505,7 @@ class _MoEBackward(torch.autograd.Function):
     def forward(ctx, experts, x, top_k_index, top_k_weights):
         with torch.no_grad():
             out = moe_forward(experts, x.detach(), top_k_index, top_k_weights.detach())
-        experts.last_plan = dict(experts.last_plan, backward="grouped")
+        experts.last_plan = dict(experts.last_plan, backward="grouped_copy" if experts._backward_on_copy else "grouped")
         ctx.experts = experts
         ctx.save_for_backward(x, top_k_index, top_k_weights)
         return out
@@ -512,9 +534,11 @@ class _MoEBackward(torch.autograd.Function):
             buf = reserve_workspace(dev, need)
             exchange_tick(dev)
             with torch.cuda.device(dev.index):
-                rc = _lib.load().gptq_moe_backward(ctypes.byref(experts._moe), experts._table.data_ptr(), experts._grad_table.data_ptr(), x2.data_ptr(),
-                                                   idx.data_ptr(), w.data_ptr(), dout.data_ptr(), T, topk, _lib.ptr(dx), _lib.ptr(dw), None,
-                                                   buf.data_ptr(), buf.numel(), _raw_stream(dev.index))
+                on_copy = experts._backward_on_copy and experts._decode_table is not None
+                rc = _lib.load().gptq_moe_backward_ex(ctypes.byref(experts._moe), experts._table.data_ptr(), experts._grad_table.data_ptr(),
+                                                      _lib.ptr(experts._decode_table), x2.data_ptr(), idx.data_ptr(), w.data_ptr(), dout.data_ptr(), T, topk,
+                                                      _lib.ptr(dx), _lib.ptr(dw), None, buf.data_ptr(), buf.numel(), _lib.GRAD_ON_COPY if on_copy else 0,
+                                                      _raw_stream(dev.index))
             if rc:
                 _lib.check(rc)
         gx = dx.to(x.dtype).reshape(x.shape) if want_x else None

@@ -623,6 +623,25 @@ int gptq_moe_backward(const gptq_moe_t *moe, const void *table, const void *grad
 /* Host-only: "path=grouped_backward tiles=3 launches=5 wg_recompute=... wg_down=... wg_up=..." or "path=per_expert reason=...", for (moe, T, topk).
  * GPTQ_OK either way (GPTQ_ERR_NULL for a NULL out). */
 int gptq_describe_moe_backward_plan(const gptq_moe_t *moe, int T, int topk, char *out, size_t out_bytes);
+/* The same call with `flags` (additive in ABI 8).  0: gptq_moe_backward, launch for launch (decode_table is not read).  GPTQ_GRAD_ON_COPY (opt-in): where
+ * every expert layer is what gptq_grad_input_ex takes on its decode copy -- 4 bits in all three projections, fp16 / bf16, a 16-column copy (16-byte
+ * aligned), group_size 32, 64, 128 times a power of two or one group, plain or act-order with `perm` -- the down and the up stage run the grouped mode of
+ * the decode-copy kernel and read qweight_tiled / qconst_tiled / perm through `decode_table` (gptq_moe_build_decode_table) alone: grad_table may be NULL,
+ * and no checkpoint row is read by those two stages (the recompute of g / u still reads `table`).  Same contract, workspace and outputs.  Every fp32
+ * matrix sum runs in gptq_moe_backward's order (given the same dg / du rows, dx has the same bits; du has them always); the scalar fp32 epilogue of
+ * the down stage is rounded as this kernel's object code fuses it, so about one dg element in 10^5 differs from gptq_moe_backward's by one ulp (and
+ * its token's dx row follows) and dw differs in the last bits of its sums -- both forms are inside the contract above, and each is bit-reproducible
+ * against itself.  Launches: five, or SIX where an expert's gate and up layers name different
+ * output columns (different `perm` pointers: W1's launch stores the fp32 rows, W3's continues from them), four when dx is NULL.  Experts the copy form
+ * declines run gptq_moe_backward's stages (grad_table required).  Unknown flag bits: GPTQ_ERR_UNSUPPORTED. */
+int gptq_moe_backward_ex(const gptq_moe_t *moe, const void *table, const void *grad_table, const void *decode_table, const void *x, const int64_t *topk_idx,
+                         const float *topk_w, const void *dout, int T, int topk, void *dx, float *dw, void *dgu_out, void *workspace,
+                         size_t workspace_bytes, int flags, void *stream);
+/* Host-only: what gptq_moe_backward_ex would run for (moe, T, topk, flags).  flags = 0: gptq_describe_moe_backward_plan's line.  GPTQ_GRAD_ON_COPY:
+ * "path=grouped_backward_copy tiles=3 launches=5 up_launches=1 gm=0 act=0 gm_down=0 wg_recompute=... wg_down=... wg_up=..." (gm / gm_down: the group mode
+ * of the gate | up and of the down copies; wg_up per up-stage launch), or the rows form's line with a trailing "copy_reason=bits|dtype|no_copy|group_size";
+ * "path=per_expert reason=..." as before. */
+int gptq_describe_moe_backward_plan_ex(const gptq_moe_t *moe, int T, int topk, int flags, char *out, size_t out_bytes);
 
 /* The ROUTER in front of the routed layer (additive in ABI 8): logits, softmax and top-k of a softmax-then-top-k router (Mixtral, Qwen2-MoE, Qwen3-MoE) in
  * ONE launch.  The router weight is not quantized (auto_gptq/modeling/mixtral.py lists only w1 / w2 / w3 and the attention projections): a dense kernel.

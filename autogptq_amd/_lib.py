@@ -55,6 +55,17 @@ STRIP_COLS = 16          # GPTQ_STRIP_COLS: columns per strip of the decode copy
 COPY_ROWS_INT2 = 0x100   # GPTQ_COPY_ROWS_INT2: OR-ed into GptqLayer.tiled_cols -- this 2-bit layer's copy is also read at 5+ rows (opt-in; copy_cols() masks it)
 GRAD_ON_COPY = 1         # GPTQ_GRAD_ON_COPY: gptq_grad_input_ex's flag -- the backward on the decode copy (opt-in)
 COPY_ROWS_INT2_WIDE = 0x200   # GPTQ_COPY_ROWS_INT2_WIDE: ... in the whole band of the 4-bit twin (a layer whose checkpoint rows are not resident)
+GRAD_COPY_ANY_BITS = 4   # GPTQ_GRAD_COPY_ANY_BITS: with GRAD_ON_COPY (flags 5), 2-, 3- and 8-bit layers / experts run the backward on their copy too
+
+
+def grad_copy_flags(value) -> int:
+    """The flags word of gptq_grad_input_ex / gptq_moe_backward_ex for the Python switches (grad_on_copy, backward_on_copy): False / None -> 0,
+    True -> GRAD_ON_COPY (4-bit layers), "any_bits" -> GRAD_ON_COPY | GRAD_COPY_ANY_BITS (2, 3, 4 and 8 bits)."""
+    if isinstance(value, str):
+        if value != "any_bits":
+            raise ValueError(f'the backward-on-copy switch takes False, True or "any_bits", got {value!r}')
+        return GRAD_ON_COPY | GRAD_COPY_ANY_BITS
+    return GRAD_ON_COPY if value else 0
 
 
 def copy_cols(tiled_cols: int) -> int:

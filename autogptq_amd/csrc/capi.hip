@@ -849,9 +849,13 @@ int gptq_grad_input(const gptq_layer_t* L, const void* dy, void* dx, int M, int 
 
 // check_layer of a layer that may run on its decode copy alone: with GPTQ_GRAD_ON_COPY and a copy present, a NULL qweight passes this check (the copy's
 // address stands in for it); whether the rows are needed after all is the plan's answer
+// (the known flags of the four _ex entries below: GPTQ_GRAD_ON_COPY, and GPTQ_GRAD_COPY_ANY_BITS only together with it)
+static bool grad_flags_known(int flags) {
+    return !(flags & ~(GPTQ_GRAD_ON_COPY | GPTQ_GRAD_COPY_ANY_BITS)) && (!(flags & GPTQ_GRAD_COPY_ANY_BITS) || (flags & GPTQ_GRAD_ON_COPY));
+}
 static int check_layer_grad(const gptq_layer_t* L, int flags) {
     if (!L) return fail(GPTQ_ERR_NULL, "layer is NULL");
-    if (flags & ~GPTQ_GRAD_ON_COPY) return fail(GPTQ_ERR_UNSUPPORTED, "unknown gptq_grad_input_ex flags 0x%x", flags);
+    if (!grad_flags_known(flags)) return fail(GPTQ_ERR_UNSUPPORTED, "unknown gptq_grad_input_ex flags 0x%x", flags);
     gptq_layer_t c = *L;
     if ((flags & GPTQ_GRAD_ON_COPY) && !c.qweight && c.qweight_tiled) c.qweight = c.qweight_tiled;
     return check_layer(&c);
@@ -879,7 +883,10 @@ int gptq_describe_grad_input_plan(const gptq_layer_t* L, int M, int flags, char*
     if (rc) return rc;
     if (M <= 0) return fail(GPTQ_ERR_SHAPE, "M must be > 0, got %d", M);
     const GradCopyPlan pl = plan_grad_copy(*L, M, flags);
-    if (pl.ok) snprintf(out, out_bytes, "kernel=grad_copy bm=%d stages=%d gm=%d act=%d", pl.bm, pl.stages, pl.gm, pl.act ? 1 : 0);
+    if (pl.ok) {
+        const int n = snprintf(out, out_bytes, "kernel=grad_copy bm=%d stages=%d gm=%d act=%d", pl.bm, pl.stages, pl.gm, pl.act ? 1 : 0);
+        if (pl.bits != 4 && n > 0 && (size_t)n < out_bytes) snprintf(out + n, out_bytes - n, " bits=%d", pl.bits);
+    }
     else snprintf(out, out_bytes, "kernel=grad_rows reason=%s", pl.why);
     return GPTQ_OK;
 }
@@ -1396,7 +1403,7 @@ size_t gptq_moe_backward_workspace_bytes(const gptq_moe_t* m, int T, int topk) {
 static int moe_backward_impl(const char* fn, const gptq_moe_t* m, const void* table, const void* grad_table, const void* decode_table, const void* x,
                              const int64_t* idx, const float* w, const void* dout, int T, int topk, void* dx, float* dw, void* dgu_out, void* ws,
                              size_t ws_bytes, int flags, void* stream) {
-    if (flags & ~GPTQ_GRAD_ON_COPY) return fail(GPTQ_ERR_UNSUPPORTED, "unknown %s flags 0x%x", fn, flags);
+    if (!grad_flags_known(flags)) return fail(GPTQ_ERR_UNSUPPORTED, "unknown %s flags 0x%x", fn, flags);
     if (int rc = moe_check(MOE_GROUPED, m, T, topk)) return rc;
     if (T == 0) return GPTQ_OK;
     if (!dx && !dw) return fail(GPTQ_ERR_NULL, "dx and dw are both NULL: nothing to compute");
@@ -1436,15 +1443,17 @@ int gptq_moe_backward_ex(const gptq_moe_t* m, const void* table, const void* gra
 // flags = 0: gptq_describe_moe_backward_plan's line, byte for byte.  With the flag: the copy form's line, or the rows form's with the reason it stays.
 static int describe_moe_backward_impl(const gptq_moe_t* m, int T, int topk, int flags, char* out, size_t out_bytes) {
     if (!out || out_bytes == 0) return fail(GPTQ_ERR_NULL, "out is NULL");
-    if (flags & ~GPTQ_GRAD_ON_COPY) return fail(GPTQ_ERR_UNSUPPORTED, "unknown gptq_describe_moe_backward_plan_ex flags 0x%x", flags);
+    if (!grad_flags_known(flags)) return fail(GPTQ_ERR_UNSUPPORTED, "unknown gptq_describe_moe_backward_plan_ex flags 0x%x", flags);
     if (moe_check(MOE_GROUPED, m, T, topk)) return describe_decline(out, out_bytes, "per_expert");
     const gptq_layer_t* G = m->gate[0];
     const MoeGradPlan pl = plan_moe_grad(m->E, T, topk, G->K, G->N, G->dtype);
     const long wg_re = (long)pl.tiles * (G->N / 64), wg_down = (long)pl.tiles * pl.nblk_i, wg_up = (long)pl.tiles * pl.nblk_h;
     const MoeGradCopyPlan cp = plan_moe_grad_copy(*m, flags);
-    if (cp.ok)
-        snprintf(out, out_bytes, "path=grouped_backward_copy tiles=%d launches=%d up_launches=%d gm=%d act=%d gm_down=%d wg_recompute=%ld wg_down=%ld wg_up=%ld",
-                 pl.tiles, T > 0 ? 4 + cp.up_launches : 0, cp.up_launches, cp.gm1, cp.act ? 1 : 0, cp.gm2, wg_re, wg_down, wg_up);
+    if (cp.ok) {
+        const int n = snprintf(out, out_bytes, "path=grouped_backward_copy tiles=%d launches=%d up_launches=%d gm=%d act=%d gm_down=%d wg_recompute=%ld wg_down=%ld wg_up=%ld",
+                               pl.tiles, T > 0 ? 4 + cp.up_launches : 0, cp.up_launches, cp.gm1, cp.act ? 1 : 0, cp.gm2, wg_re, wg_down, wg_up);
+        if (cp.bits != 4 && n > 0 && (size_t)n < out_bytes) snprintf(out + n, out_bytes - n, " bits=%d", cp.bits);
+    }
     else if (flags)
         snprintf(out, out_bytes, "path=grouped_backward tiles=%d launches=%d wg_recompute=%ld wg_down=%ld wg_up=%ld copy_reason=%s", pl.tiles, T > 0 ? 5 : 0,
                  wg_re, wg_down, wg_up, cp.why);

@@ -28,6 +28,20 @@
 //            no pre- or post-pass.
 // BM, the group mode, act-order and accumulate are launch-uniform: one kernel per dtype.  So is the GROUPED form (moe_grad_copy.cuh, included behind the dense
 // body): the down and the up stage of the routed layer's backward on the experts' copies, behind the mode word of the kernel's second argument.
+//
+// 2, 3 AND 8 BITS (GPTQ_GRAD_COPY_ANY_BITS; opt-in).  The width is a launch-uniform word too (Args::bits / Grouped::bits, the 4-bit bodies first in the code);
+// only the weight FRONT-END (Front<T, BITS> below: the lane's raw loads and its image writes) differs, everything above is shared.  Every decoder returns 8
+// consecutive k of the lane's column in memory order, so each frag is still ONE 16-byte write at slot (k of the frag) / 8 of row n, swizzled by the same f:
+// the 16 lanes of a write group hold 16 rows at ONE logical slot whatever the slot is, so the write argument above holds for every width, and the reads are
+// the 4-bit reads.
+//   3 bits   a strip-chunk is 768 B; the lane's 3 words (32 k) in ONE 12-byte load; Deq1_3::frag(w, ks), ks = 0 .. 3 -> slot 4 g + ks.
+//   2 bits   a strip-chunk is 512 B; the lane's 2 words (32 k) in ONE 8-byte load; the copy puts pair p = (k 16 w + 2 p, + 1) at bit 2 p of the halves of
+//            word w, so Deq1_2::frag(word[ks >> 1] >> 8 (ks & 1)) is k = 8 ks .. 8 ks + 7 in memory order (as moe_rows.hip reads it) -> slot 4 g + ks:
+//            no relabelling of dX columns is left to absorb.
+//   8 bits   a chunk of the copy is 64 k (a lane owns 16 k), the tile two chunks: TWO 16-byte loads per lane, at k-slot 16 g of chunk 2 kt and of chunk
+//            2 kt + 1; two Deq1_8::frag(q0, q1) per load -> slots 8 h + 2 g, 8 h + 2 g + 1 (h: the chunk).  The lane's two runs lie 64 k apart: it holds
+//            two (scale, zero-point) pairs (group kt >> gshift | 2 kt + h | 4 kt + 2 h + (g >> 1)); the record is 64 B, the zero-point 2 bytes at 32 + 2 r
+//            (gemm_rows_kernel.cuh).  A last tile with one chunk inside K reads that chunk twice (clamped index); its second half is never stored.
 #include "common.cuh"
 #include "mma_dequant.cuh"
 #include "launch.h"
@@ -41,7 +55,6 @@ constexpr int BN = 64;                      // n per stage: 4 strips
 constexpr int B_ROW = 256;                  // bytes of a weight image row: 128 k of one n
 constexpr int B_BYTES = BN * B_ROW;
 constexpr int LDS_BYTES = 65536;            // 2 x (BM x 128 + B_BYTES) at BM = 128 = the fp32 epilogue tile [128][128]
-constexpr unsigned WCH = 1024u, REC = 48u;  // a strip-chunk of the copy, a constant record
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
@@ -52,18 +65,98 @@ struct Args {
     const int* perm;             // act-order: original k of re-sequenced position i, else NULL
     const void* dy;
     void* dx;
-    int M, K, N, strips, chunks, groups, gshift, gm, bm, nkt, accumulate;
-};
-
-// the raw words one thread loads for a stage
-struct Stage {
-    u32x4 a[4];                  // dY: 16-byte slots of the A image
-    u32x4 q;                     // 32 k of the lane's column
-    unsigned cs, cz;             // its scale bits and zero-point
+    int M, K, N, strips, chunks, groups, gshift, gm, bm, nkt, accumulate;      // chunks: of the copy (128 k; 8 bits: 64 k); nkt: 128-k tiles
+    int bits;
 };
 
 // image slot swizzle: a permutation of the row's low four bits whose upper three differ over rows {0..3, 8..11} and over {4..7, 12..15}
 __device__ __forceinline__ int fswz(int v) { return ((v & 3) << 1) | (v & 8) | ((v >> 2) & 1); }
+
+// The weight front-end of one lane: what it loads per stage (Raw) and how it writes the [n][k] image.  The lane's groups are the same in every stage.
+struct W3 { unsigned x, y, z; };             // 12 bytes, 4-byte aligned: one global_load_dwordx3 that touches nothing behind them
+template <typename T, int BITS>
+struct Front {
+    static constexpr int NH = BITS == 8 ? 2 : 1;                                  // chunks of the copy per tile = loads per lane and stage
+    static constexpr unsigned LB = BITS == 3 ? 12u : (BITS == 2 ? 8u : 16u);      // a lane's bytes of a strip-chunk
+    static constexpr unsigned WCH = 64u * LB, REC = BITS == 8 ? 64u : 48u;       // a strip-chunk of the copy, a constant record
+    struct Raw {
+        u32x4 q[NH];             // the lane's words (3 bits: x y z, 2 bits: x y)
+        unsigned cs[NH], cz[NH]; // scale bits and zero-point of each run
+    };
+    const char* wsrc[NH];
+    const char* qc;
+    unsigned coff[NH], zoff[NH];
+    size_t strip_w, strip_c;
+    int wrow, wf, g;
+
+    // chunks, groups, gshift, gm: the copy's (chunks of 128 k, at 8 bits of 64 k); kt: the 128-k tile
+    __device__ __forceinline__ void init(const char* qw, const char* qc_, int chunks, int groups, int gshift, int gm, int kt, int lane, int wave) {
+        const int r = lane & 15;
+        g = lane >> 4;
+        qc = qc_;
+#pragma unroll
+        for (int h = 0; h < NH; ++h) {
+            int grp;
+            if constexpr (BITS == 8) grp = gm == 0 ? (kt >> gshift) : (gm == 1 ? 2 * kt + h : 4 * kt + 2 * h + (g >> 1));
+            else grp = gm == 0 ? (kt >> gshift) : (gm == 1 ? 2 * kt + (g >> 1) : 4 * kt + g);
+            grp = min(grp, groups - 1);                    // (one group; the k-slots past K of a last, partial chunk)
+            coff[h] = (unsigned)grp * REC + 2u * (unsigned)r;
+            zoff[h] = (unsigned)grp * REC + 32u + (BITS == 8 ? 2u : 1u) * (unsigned)r;
+            const int c = BITS == 8 ? min(2 * kt + h, chunks - 1) : kt;      // (8 bits, a last tile with one chunk inside K: that chunk again, never stored)
+            wsrc[h] = qw + (size_t)c * WCH + (size_t)lane * LB;
+        }
+        strip_w = (size_t)chunks * WCH, strip_c = (size_t)groups * REC;
+        wrow = (16 * wave + r) * B_ROW, wf = fswz(r);      // image row 16 wave + r
+    }
+    __device__ __forceinline__ void fetch(Raw& s, int strip) const {
+        const char* rec = qc + (size_t)strip * strip_c;
+#pragma unroll
+        for (int h = 0; h < NH; ++h) {
+            const char* src = wsrc[h] + (size_t)strip * strip_w;
+            if constexpr (BITS == 3) {
+                const W3 w = *(const W3*)src;
+                s.q[h] = u32x4{w.x, w.y, w.z, 0u};
+            } else if constexpr (BITS == 2) {
+                const u32x2 w = *(const u32x2*)src;
+                s.q[h] = u32x4{w.x, w.y, 0u, 0u};
+            } else {
+                s.q[h] = *(const u32x4*)src;
+            }
+            s.cs[h] = *(const unsigned short*)(rec + coff[h]);
+            if constexpr (BITS == 8) s.cz[h] = *(const unsigned short*)(rec + zoff[h]);
+            else s.cz[h] = *(const unsigned char*)(rec + zoff[h]);
+        }
+    }
+    // the lane's four writes: 8 consecutive k each, slot (k / 8) of its row
+    __device__ __forceinline__ void store(const Raw& s, char* Bs) const {
+        char* row = Bs + wrow;
+        if constexpr (BITS == 4) {
+            Deq1<T> dq;
+            dq.setup(s.cs[0], s.cz[0]);
+#pragma unroll
+            for (int w = 0; w < 4; ++w) *(u32x4*)(row + (((4 * g + w) ^ wf) << 4)) = dq.frag(s.q[0][w]);
+        } else if constexpr (BITS == 3) {
+            Deq1_3<T> dq;
+            dq.setup(s.cs[0], s.cz[0]);
+            const u32x3 w3 = {s.q[0].x, s.q[0].y, s.q[0].z};
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) *(u32x4*)(row + (((4 * g + ks) ^ wf) << 4)) = dq.frag(w3, ks);
+        } else if constexpr (BITS == 2) {
+            Deq1_2<T> dq;
+            dq.setup(s.cs[0], s.cz[0]);
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) *(u32x4*)(row + (((4 * g + ks) ^ wf) << 4)) = dq.frag(s.q[0][ks >> 1] >> (8 * (ks & 1)));
+        } else {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                Deq1_8<T> dq;
+                dq.setup(s.cs[h], s.cz[h]);
+                *(u32x4*)(row + (((8 * h + 2 * g) ^ wf) << 4)) = dq.frag(s.q[h].x, s.q[h].y);
+                *(u32x4*)(row + (((8 * h + 2 * g + 1) ^ wf) << 4)) = dq.frag(s.q[h].z, s.q[h].w);
+            }
+        }
+    }
+};
 
 // B fragment: n = 8 g .. 8 g + 7 (rows at, at + 4 rows) at the lane's k, transposed out of the image
 __device__ __forceinline__ u32x4 tr_fragment(const char* lo_at, const char* hi_at) {
@@ -73,7 +166,7 @@ __device__ __forceinline__ u32x4 tr_fragment(const char* lo_at, const char* hi_a
     return u32x4{l.x, l.y, h.x, h.y};
 }
 
-template <typename T, int RB>
+template <typename T, int RB, int BITS>
 __device__ __forceinline__ void run(const Args& p, char* smem, int m0, int kt) {
     constexpr int BM = RB * 32;
     constexpr int NA = BM * 8 / THREADS;                  // dY slots per thread
@@ -84,12 +177,14 @@ __device__ __forceinline__ void run(const Args& p, char* smem, int m0, int kt) {
     const int M = p.M, K = p.K, N = p.N, k0 = kt * BK;
     const T* __restrict__ dy = (const T*)p.dy;
 
-    // constants: the lane's group is the same in every stage
-    int grp = p.gm == 0 ? (kt >> p.gshift) : (p.gm == 1 ? 2 * kt + (g >> 1) : 4 * kt + g);
-    grp = min(grp, p.groups - 1);                          // (one group; the k-slots past K of a last, partial chunk)
-    const unsigned coff = (unsigned)grp * REC + 2u * (unsigned)r, zoff = (unsigned)grp * REC + 32u + (unsigned)r;
-    const size_t strip_w = (size_t)p.chunks * WCH, strip_c = (size_t)p.groups * REC;
-    const char* const wsrc = p.qw + (size_t)kt * WCH + (size_t)lane * 16u;
+    typedef Front<T, BITS> F;
+    F fr;
+    fr.init(p.qw, p.qc, p.chunks, p.groups, p.gshift, p.gm, kt, lane, wave);
+    // the raw words one thread loads for a stage
+    struct Stage {
+        u32x4 a[NA];             // dY: 16-byte slots of the A image
+        typename F::Raw w;       // the lane's weights and their constants
+    };
 
     auto fetch = [&](Stage& s, int it) {
         const int n0 = it * BN;
@@ -99,27 +194,18 @@ __device__ __forceinline__ void run(const Args& p, char* smem, int m0, int kt) {
             const int m = min(m0 + row, M - 1);            // rows past M repeat the last one (their outputs are not stored)
             s.a[i] = n0 + sl * 8 < N ? *(const u32x4*)(dy + (size_t)m * N + n0 + sl * 8) : u32x4{0, 0, 0, 0};
         }
-        const int strip = min(4 * it + wave, p.strips - 1);   // past the last strip: a strip again, against zero dY columns
-        s.q = *(const u32x4*)(wsrc + (size_t)strip * strip_w);
-        const char* rec = p.qc + (size_t)strip * strip_c;
-        s.cs = *(const unsigned short*)(rec + coff);
-        s.cz = *(const unsigned char*)(rec + zoff);
+        fr.fetch(s.w, min(4 * it + wave, p.strips - 1));   // past the last strip: a strip again, against zero dY columns
     };
 
-    // image offsets: the lane's four writes (slot 4 g + w of row 16 wave + r) ...
-    const int wrow = (16 * wave + r) * B_ROW, wf = fswz(r);
+    // image offsets: the lane's writes (Front::store: row 16 wave + r) ...
     auto store = [&](const Stage& s, char* buf) {
         char* As = buf;
-        char* Bs = buf + BM * 128;
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             const int c = tid + THREADS * i;
             *(u32x4*)(As + swz(c >> 3, c & 7)) = s.a[i];
         }
-        Deq1<T> dq;
-        dq.setup(s.cs, s.cz);
-#pragma unroll
-        for (int w = 0; w < 4; ++w) *(u32x4*)(Bs + wrow + (((4 * g + w) ^ wf) << 4)) = dq.frag(s.q[w]);
+        fr.store(s.w, buf + BM * 128);
     };
     // ... and its transposing reads: row 8 g + q (second read: + 4), the 8 bytes at k = 64 wk + 16 j + 4 pp -> slot 8 wk + 2 j + (pp >> 1), half pp & 1.
     // 2 j touches bits 1, 2 of the slot alone, so block j is the j = 0 address ^ 32 j; the second row flips bit 0 of f
@@ -211,6 +297,14 @@ __device__ __forceinline__ void run(const Args& p, char* smem, int m0, int kt) {
     }
 }
 
+template <typename T, int BITS>
+__device__ __forceinline__ void run_dense(const Args& p, char* smem) {
+    const int b = xcd_remap(blockIdx.x, gridDim.x);        // consecutive k tiles of one row block on one XCD: they share dY in its L2
+    const int kt = b % p.nkt, mt = b / p.nkt;
+    if (p.bm == 128) run<T, 4, BITS>(p, smem, mt * 128, kt);
+    else run<T, 2, BITS>(p, smem, mt * 64, kt);
+}
+
 }  // namespace gcopy
 }  // namespace gptq
 
@@ -222,24 +316,30 @@ namespace gcopy {
 template <typename T>
 __global__ void __launch_bounds__(THREADS, 2) grad_copy_kernel(Args p, Grouped q) {
     __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
-    if (__builtin_expect(q.mode == GR_DENSE, 1)) {         // (launch-uniform; the dense bodies first in the code, as they were)
-        const int b = xcd_remap(blockIdx.x, gridDim.x);    // consecutive k tiles of one row block on one XCD: they share dY in its L2
-        const int kt = b % p.nkt, mt = b / p.nkt;
-        if (p.bm == 128) run<T, 4>(p, smem, mt * 128, kt);
-        else run<T, 2>(p, smem, mt * 64, kt);
+    if (__builtin_expect(q.mode == GR_DENSE, 1)) {         // (launch-uniform; the dense bodies first in the code, the 4-bit ones first among them)
+        if (__builtin_expect(p.bits == 4, 1)) run_dense<T, 4>(p, smem);
+        else if (p.bits == 3) run_dense<T, 3>(p, smem);
+        else if (p.bits == 2) run_dense<T, 2>(p, smem);
+        else run_dense<T, 8>(p, smem);
         return;
     }
-    run_grouped<T>(q, smem);
+    if (__builtin_expect(q.bits == 4, 1)) run_grouped<T, 4>(q, smem);
+    else if (q.bits == 3) run_grouped<T, 3>(q, smem);
+    else if (q.bits == 2) run_grouped<T, 2>(q, smem);
+    else run_grouped<T, 8>(q, smem);
 }
 
 }  // namespace gcopy
 
 // The one place the qualification rule lives: gptq_describe_grad_input_plan prints it, gptq_grad_input_ex launches by it.  Pure host arithmetic.
+// GPTQ_GRAD_ON_COPY alone takes 4-bit layers; | GPTQ_GRAD_COPY_ANY_BITS also 2, 3 and 8 bits.  (A 2-bit layer's copy has ONE layout, whether or not
+// tiled_cols carries GPTQ_COPY_ROWS_INT2 / _WIDE -- those bits choose forward kernels; copy_cols() masks them.)
 GradCopyPlan plan_grad_copy(const gptq_layer_t& L, int M, int flags) {
     GradCopyPlan pl{};
     auto no = [&](const char* why) { pl.why = why; return pl; };
     if (!(flags & GPTQ_GRAD_ON_COPY)) return no("flag_off");
-    if (L.bits != 4) return no("bits");
+    const bool any = (flags & GPTQ_GRAD_COPY_ANY_BITS) != 0;
+    if (L.bits != 4 && !(any && (L.bits == 2 || L.bits == 3 || L.bits == 8))) return no("bits");
     if (L.dtype != GPTQ_F16 && L.dtype != GPTQ_BF16) return no("dtype");
     // (an act-order layer's copy is made of its re-sequenced rows: without perm the kernel cannot name its output columns)
     if (!L.qweight_tiled || !L.qconst_tiled || copy_cols(L) != GPTQ_STRIP_COLS || (L.g_idx && !L.perm) || L.K % 32 || L.N % GPTQ_STRIP_COLS) return no("no_copy");
@@ -250,6 +350,7 @@ GradCopyPlan plan_grad_copy(const gptq_layer_t& L, int M, int flags) {
     else if (gs > 0 && gs % 128 == 0 && ((gs / 128) & (gs / 128 - 1)) == 0) {
         while ((128 << pl.gshift) < gs) ++pl.gshift;
     } else return no("group_size");
+    pl.bits = L.bits;
     pl.groups = gs >= L.K ? 1 : (L.K + gs - 1) / gs;
     pl.chunks = (L.K + 127) / 128;
     pl.stages = (L.N + gcopy::BN - 1) / gcopy::BN;
@@ -270,8 +371,9 @@ hipError_t launch_grad_copy(const gptq_layer_t& L, const GradCopyPlan& pl, const
     p.perm = pl.act ? L.perm : nullptr;
     p.dy = dy;
     p.dx = dx;
-    p.M = M, p.K = L.K, p.N = L.N, p.strips = L.N / GPTQ_STRIP_COLS, p.chunks = pl.chunks, p.groups = pl.groups, p.gshift = pl.gshift, p.gm = pl.gm;
-    p.bm = pl.bm, p.nkt = pl.chunks, p.accumulate = accumulate ? 1 : 0;
+    p.M = M, p.K = L.K, p.N = L.N, p.strips = L.N / GPTQ_STRIP_COLS, p.groups = pl.groups, p.gshift = pl.gshift, p.gm = pl.gm;
+    p.chunks = pl.bits == 8 ? (L.K + 63) / 64 : pl.chunks;      // (the 8-bit copy's chunks are 64 k deep)
+    p.bm = pl.bm, p.nkt = pl.chunks, p.accumulate = accumulate ? 1 : 0, p.bits = pl.bits;
     const dim3 grid((unsigned)pl.blocks), block(gcopy::THREADS);
     gcopy::Grouped q{};                                    // GR_DENSE
     if (L.dtype == GPTQ_F16) hipLaunchKernelGGL(gcopy::grad_copy_kernel<f16>, grid, block, 0, st, p, q);
@@ -279,12 +381,13 @@ hipError_t launch_grad_copy(const gptq_layer_t& L, const GradCopyPlan& pl, const
     return hipGetLastError();
 }
 
-// The grouped form's qualification: every layer of the three projections by the dense rule above (4 bits -- mixed widths are declined as a whole --, fp16 /
+// The grouped form's qualification: every layer of the three projections by the dense rule above (ONE width -- mixed widths are declined as a whole --, fp16 /
 // bf16, a 16-column copy, the group sizes), its copies 16-byte aligned.  W1 and W3 share one up-stage launch where every expert's gate and up name the same
 // output columns: both plain, or one perm pointer.
 MoeGradCopyPlan plan_moe_grad_copy(const gptq_moe_t& m, int flags) {
     MoeGradCopyPlan pl{};
     pl.up_launches = 1;
+    pl.bits = m.gate[0]->bits;
     const gptq_layer_t* const* proj[3] = {m.gate, m.up, m.down};
     auto cols = [](const gptq_layer_t& L) { return L.qweight_seq ? L.perm : nullptr; };      // as the decode table's entry names them
     for (int ps = 0; ps < 3; ++ps)
@@ -292,6 +395,7 @@ MoeGradCopyPlan plan_moe_grad_copy(const gptq_moe_t& m, int flags) {
             const gptq_layer_t& L = *proj[ps][e];
             const GradCopyPlan lp = plan_grad_copy(L, gcopy::GBM, flags);
             if (!lp.ok) { pl.why = lp.why; return pl; }
+            if (L.bits != pl.bits) { pl.why = "bits"; return pl; }
             if (((uintptr_t)L.qweight_tiled | (uintptr_t)L.qconst_tiled) & 15) { pl.why = "no_copy"; return pl; }
             pl.act = pl.act || lp.act;
             if (e == 0 && ps == 0) pl.gm1 = lp.gm, pl.gshift1 = lp.gshift, pl.groups1 = lp.groups;
@@ -311,6 +415,7 @@ hipError_t launch_moe_grad_copy_stages(const gptq_moe_t& m, const MoeGradCopyPla
     gcopy::Args none{};
     gcopy::Grouped q{};
     q.E = m.E; q.topk = topk; q.H = G.K; q.I = G.N;
+    q.bits = cp.bits;
     q.table = (const moerows::Entry*)decode_table;
     q.dout = dout; q.w = w;
     q.row_assign = (const int*)(ws + pl.off_rows); q.tile_count = (const int*)(ws + pl.off_tile_count); q.tiles = (const int4*)(ws + pl.off_tiles);

@@ -232,7 +232,8 @@ struct GradCopyPlan {
     const char* why;         // !ok: flag_off / bits / dtype / no_copy / group_size
     bool act;                // act-order: the tile's columns are scattered through perm
     int gm, gshift;          // group mode (0: 128-multiples / one group, 1: 64, 2: 32) and, for mode 0, group of chunk c = c >> gshift
-    int groups, chunks, stages, bm;
+    int groups, chunks, stages, bm;      // chunks: 128-k tiles of dX (= chunks of the copy, except at 8 bits)
+    int bits;                // the layer's width: 4, or 2 / 3 / 8 under GPTQ_GRAD_COPY_ANY_BITS
     long blocks;
 };
 GradCopyPlan plan_grad_copy(const gptq_layer_t& L, int M, int flags);
@@ -288,6 +289,7 @@ struct MoeGradCopyPlan {
     bool ok;
     const char* why;         // !ok: flag_off / bits / dtype / no_copy / group_size
     bool act;                // some expert scatters its output columns through perm
+    int bits;                // the experts' one width
     int up_launches;         // 1: W1 and W3 into one set of accumulators; 2: gate and up name different columns (W1 stores, W3 continues from DXR)
     int gm1, gshift1, groups1, gm2, gshift2, groups2;      // GradCopyPlan's group mode of the gate / up and of the down copies
 };

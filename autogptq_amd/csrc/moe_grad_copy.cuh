@@ -16,6 +16,7 @@
 //            W3's perm) before it walks W3 and stores them back -- the fp32 sums continue exactly where W1's ended, so every element sums its reduction
 //            axis in the order of the one-launch form (and of moe_grad_kernel), and no two workgroups touch one element within a launch.
 // 2 x (64 x 128 + 64 x 256) = 48 KiB of the kernel's 64; the fp32 epilogue tile [64][128] reuses them.
+// 2, 3 and 8 bits (Grouped::bits, launch-uniform; GPTQ_GRAD_COPY_ANY_BITS): the dense body's front-ends (grad_input_copy.hip Front<T, BITS>), nothing else.
 #pragma once
 #include "moe_entry.cuh"
 
@@ -26,6 +27,7 @@ enum { GR_DENSE = 0, GR_DOWN = 1, GR_UP = 2, GR_UP1 = 3, GR_UP3 = 4 };
 
 struct Grouped {
     int mode;                                // GR_DENSE: the dense layer of Args, nothing below is read
+    int bits;                                // the experts' width (one for gate, up and down)
     int E, topk, H, I, nkt;                  // nkt: 128-column blocks (chunks of the copy) of this stage's output
     const moerows::Entry* table;             // the decode table [3][E]: W1, W3, W2
     const void* dout;                        // [T][H]
@@ -41,12 +43,6 @@ struct Grouped {
     int gm2, gshift2, groups2;               // the down copies (over I)
 };
 
-struct GStage {                              // the raw words one thread loads for a stage
-    u32x4 a[2];                              // A: slot tid & 7 of rows tid >> 3 and (tid >> 3) + 32
-    u32x4 q;                                 // 32 k of the lane's column
-    unsigned cs, cz;                         // its scale bits and zero-point
-};
-
 constexpr int GBM = 64;                      // tile height (the routing kernel's bm): RB = 2
 constexpr int GBUF = GBM * 128 + B_BYTES;    // one stage buffer: A image + weight image
 
@@ -54,44 +50,36 @@ constexpr int GBUF = GBM * 128 + B_BYTES;    // one stage buffer: A image + weig
 struct Copy {
     const char* qw;
     const char* qc;
-    int N, chunks, groups, gshift, gm;
+    int N, chunks, groups, gshift, gm;       // chunks: of the copy (128 k; 8 bits: 64 k)
 };
 
 // acc += A[64][N] . W^T[N][128 kt .. 128 kt + 127]: a0 / a1 are rows (tid >> 3) and (tid >> 3) + 32 of A (NULL: a row the tile does not have), rb the
 // number of 16-row blocks the tile has.  Ends behind a barrier: the LDS is free again.
-template <typename T>
+template <typename T, int BITS>
 __device__ __forceinline__ void walk(const Copy& p, const T* a0, const T* a1, int rb, char* smem, int kt, f32x4 (&acc)[2][4]) {
     const T* const arow[2] = {a0, a1};
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 15, g = lane >> 4;
     const int wm = wave >> 1, wk = wave & 1;
 
-    // constants: the lane's group is the same in every stage (the k-slots past K of a partial last chunk: the last group)
-    int grp = p.gm == 0 ? (kt >> p.gshift) : (p.gm == 1 ? 2 * kt + (g >> 1) : 4 * kt + g);
-    grp = min(grp, p.groups - 1);
-    const unsigned coff = (unsigned)grp * REC + 2u * (unsigned)r, zoff = (unsigned)grp * REC + 32u + (unsigned)r;
-    const size_t strip_w = (size_t)p.chunks * WCH, strip_c = (size_t)p.groups * REC;
-    const char* const wsrc = p.qw + (size_t)kt * WCH + (size_t)lane * 16u;
+    typedef Front<T, BITS> F;
+    F fr;
+    fr.init(p.qw, p.qc, p.chunks, p.groups, p.gshift, p.gm, kt, lane, wave);
+    struct GStage {                          // the raw words one thread loads for a stage
+        u32x4 a[2];                          // A: slot tid & 7 of rows tid >> 3 and (tid >> 3) + 32
+        typename F::Raw w;                   // the lane's weights and their constants
+    };
 
     auto fetch = [&](GStage& s, int it) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
             s.a[i] = arow[i] ? *(const u32x4*)((const char*)(arow[i] + it * BN) + (tid & 7) * 16) : u32x4{0, 0, 0, 0};
-        const int strip = 4 * it + wave;                  // (N % 64 == 0: the stage has its 4 strips)
-        s.q = *(const u32x4*)(wsrc + (size_t)strip * strip_w);
-        const char* rec = p.qc + (size_t)strip * strip_c;
-        s.cs = *(const unsigned short*)(rec + coff);
-        s.cz = *(const unsigned char*)(rec + zoff);
+        fr.fetch(s.w, 4 * it + wave);                     // (N % 64 == 0: the stage has its 4 strips)
     };
-    const int wrow = (16 * wave + r) * B_ROW, wf = fswz(r);
     auto store = [&](const GStage& s, char* buf) {
-        char* Bs = buf + GBM * 128;
 #pragma unroll
         for (int i = 0; i < 2; ++i) *(u32x4*)(buf + swz((tid >> 3) + 32 * i, tid & 7)) = s.a[i];
-        Deq1<T> dq;
-        dq.setup(s.cs, s.cz);
-#pragma unroll
-        for (int w = 0; w < 4; ++w) *(u32x4*)(Bs + wrow + (((4 * g + w) ^ wf) << 4)) = dq.frag(s.q[w]);
+        fr.store(s.w, buf + GBM * 128);
     };
     // the transposing reads: grad_input_copy.hip's run() derives the addresses
     const int q = r >> 2, pp = r & 3;
@@ -153,7 +141,7 @@ __device__ __forceinline__ float h_mix<f16>(float silu, float u) {
     return DType<f16>::to_f32(__builtin_bit_cast(f16, (unsigned short)d));
 }
 
-template <typename T>
+template <typename T, int BITS>
 __device__ __forceinline__ void run_grouped(const Grouped& p, char* smem) {
     const int b = xcd_remap(blockIdx.x, gridDim.x);        // consecutive column blocks of one tile on one XCD: they share the A rows in its L2
     const int kt = b % p.nkt, tile = b / p.nkt;
@@ -185,8 +173,9 @@ __device__ __forceinline__ void run_grouped(const Grouped& p, char* smem) {
         perm = en.perm;
         Copy W;
         W.qw = (const char*)en.tq; W.qc = (const char*)en.cst;
-        if (up) { W.N = I; W.chunks = (H + 127) >> 7; W.groups = p.groups1; W.gshift = p.gshift1; W.gm = p.gm1; }
-        else { W.N = H; W.chunks = (I + 127) >> 7; W.groups = p.groups2; W.gshift = p.gshift2; W.gm = p.gm2; }
+        constexpr int CK = BITS == 8 ? 64 : 128;          // k of a chunk of the copy
+        if (up) { W.N = I; W.chunks = (H + CK - 1) / CK; W.groups = p.groups1; W.gshift = p.gshift1; W.gm = p.gm1; }
+        else { W.N = H; W.chunks = (I + CK - 1) / CK; W.groups = p.groups2; W.gshift = p.gshift2; W.gm = p.gm2; }
         if (p.mode == GR_UP3) {
             // the sums continue where the W1 launch ended: its fp32 rows, in the accumulators' own layout, through THIS projection's columns
 #pragma unroll
@@ -211,7 +200,7 @@ __device__ __forceinline__ void run_grouped(const Grouped& p, char* smem) {
             else if (up) arow[i] = (const T*)(ps ? p.u : p.g) + (size_t)(row0 + rr) * I;
             else arow[i] = (const T*)p.dout + (size_t)(p.row_assign[row0 + rr] / p.topk) * H;
         }
-        walk<T>(W, arow[0], arow[1], rb, smem, kt, acc);
+        walk<T, BITS>(W, arow[0], arow[1], rb, smem, kt, acc);
     }
 
     // epilogue: [64][128] fp32 through LDS (column ^ 16 on odd rows, as the dense body)

@@ -126,10 +126,11 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
     need at ``max_input_length`` rows; with the default every plan and result is what it was.
     ``grad_on_copy=True`` (``QuantLinear.post_init(grad_on_copy=True)``): the input gradient of 4-bit fp16 / bf16 layers with a decode copy runs on that copy
     (gptq_grad_input_ex, grad_copy_kernel) -- with ``release_checkpoint_layout=True`` a backward call then rebuilds no rows; needs no scratch; other layers and
-    the default keep the rows kernel.
+    the default keep the rows kernel.  ``grad_on_copy="any_bits"``: 2-, 3- and 8-bit layers too (GPTQ_GRAD_COPY_ANY_BITS; 4-bit layers as under ``True``).
     ``expert_backward_on_copy=True`` (with ``expert_backward=True``; sets ``QuantMoEExperts.backward_on_copy`` before the module's ``post_init(backward=True)``; implies the expert
     decode copy): the two transposed stages of the grouped backward of 4-bit fp16 / bf16 experts run on that copy (gptq_moe_backward_ex, the grouped mode
-    of grad_copy_kernel); the scratch is the same; other experts and the default keep the checkpoint rows.
+    of grad_copy_kernel); the scratch is the same; other experts and the default keep the checkpoint rows.  ``expert_backward_on_copy="any_bits"``: experts of
+    one width out of 2, 3, 4, 8 bits (2 and 3 bits: with ``expert_low_bit=True``, and a decode copy they are given -- ``expert_low_bit_decode=True``).
     Blocks bound by ``inject_shared_expert`` before this call: the scratch also covers ``gptq_moe_shared_decode_workspace_bytes`` of 1..4 tokens."""
     from .moe import QuantMoEExperts
     rows = max_input_length or 2048
@@ -145,7 +146,7 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
             if expert_low_bit_prefill:
                 sub.low_bit_prefill = True
             if expert_backward_on_copy:
-                sub.backward_on_copy = True
+                sub.backward_on_copy = expert_backward_on_copy          # True, or "any_bits"
             sub.post_init(decode_copy=expert_decode_copy, batch=expert_batched_decode, backward=expert_backward, low_bit=expert_low_bit,
                           prefill=expert_prefill, low_bit_decode=expert_low_bit_decode)
             for e in range(sub.num_experts):
@@ -161,7 +162,7 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
             continue
         dev = sub.qweight.device                      # read BEFORE post_init: release_checkpoint_layout moves qweight to pinned host memory, and the scratch belongs to the layer's GPU
         sub.post_init(tiled=decode_copy, release_checkpoint_layout=release_checkpoint_layout, low_bit_rows=(True if low_bit_rows else None),
-                      act_int8=(True if act_int8 else None), grad_on_copy=(True if grad_on_copy else None))
+                      act_int8=(True if act_int8 else None), grad_on_copy=(grad_on_copy if grad_on_copy else None))
         lib = _lib.load()
         # the need is not monotone in M (K splits come and go with the kernel the planner picks): maximum over 1..rows
         parts = getattr(sub, "_parts", None)

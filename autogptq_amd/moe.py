@@ -144,6 +144,7 @@ class QuantMoEExperts(nn.Module):
         self._decode_table = None
         self._grad_table = None
         self._backward_on_copy = False              # post_init settled on the backward's copy form
+        self._backward_flags = 0                    # ... and on these flags of gptq_moe_backward_ex
         self._live = frozenset()                    # the copy paths ("decode", "batch", "prefill") that post_init settled on: what plan() may name
         self.decode_copy_bytes = 0
         self._keep = ()
@@ -281,13 +282,14 @@ class QuantMoEExperts(nn.Module):
         if on_copy and gplan is not None and gplan["path"] == "grouped_backward":
             for e in range(self.num_experts):
                 share_act_order(list(self[e].layers()[:2]))          # gate and up of one g_idx: one perm pointer, one up-stage launch
-            cplan = _lib.describe_moe_backward_plan_ex(m, 1, self.top_k, _lib.GRAD_ON_COPY)
+            cplan = _lib.describe_moe_backward_plan_ex(m, 1, self.top_k, _lib.grad_copy_flags(self.backward_on_copy))
             if cplan["path"] != "grouped_backward_copy":
                 logger.warning("QuantMoEExperts.backward_on_copy = True has no effect for these experts (%s): the backward keeps the checkpoint "
                                "rows", str(cplan.get("copy_reason", cplan.get("reason", ""))).replace("_", " "))
                 on_copy = False
         else:
             on_copy = False
+        self._backward_flags = _lib.grad_copy_flags(self.backward_on_copy) if on_copy else 0      # True: 4-bit experts; "any_bits": 2, 3, 4, 8
         self._backward_on_copy = on_copy                     # (the attribute stays as it was set: a declined set says so again after a move)
         lib = _lib.load()
         table = torch.zeros(max(1, int(lib.gptq_moe_table_bytes(self.num_experts))), dtype=torch.uint8, device=dev)
@@ -537,7 +539,7 @@ class _MoEBackward(torch.autograd.Function):
                 on_copy = experts._backward_on_copy and experts._decode_table is not None
                 rc = _lib.load().gptq_moe_backward_ex(ctypes.byref(experts._moe), experts._table.data_ptr(), experts._grad_table.data_ptr(),
                                                       _lib.ptr(experts._decode_table), x2.data_ptr(), idx.data_ptr(), w.data_ptr(), dout.data_ptr(), T, topk,
-                                                      _lib.ptr(dx), _lib.ptr(dw), None, buf.data_ptr(), buf.numel(), _lib.GRAD_ON_COPY if on_copy else 0,
+                                                      _lib.ptr(dx), _lib.ptr(dw), None, buf.data_ptr(), buf.numel(), experts._backward_flags if on_copy else 0,
                                                       _raw_stream(dev.index))
             if rc:
                 _lib.check(rc)

@@ -152,6 +152,7 @@ class QuantLinear(nn.Module):
     # layer then pays no gptq_unprepack_decode in front of its backward.  Same contract as the rows kernel (exact weights, fp32 sums, one rounding), another summation
     # order.  post_init(grad_on_copy=True) / autogptq_post_init(..., grad_on_copy=True) set it per call; describe_grad_plan(M) says which kernel a call gets.  Every
     # caller of grad_input() (autograd, fused-QKV parts, forward_multi, mlp_forward under grad, the LoRA wrappers) follows.  Off: nothing changes, not even a launch.
+    # True takes 4-bit layers (GPTQ_GRAD_ON_COPY); "any_bits" also 2-, 3- and 8-bit ones (| GPTQ_GRAD_COPY_ANY_BITS: the kernel's other weight front-ends).
     GRAD_ON_COPY = False
     _extra_bytes_logged = False
 
@@ -362,7 +363,7 @@ class QuantLinear(nn.Module):
         self._rows_need = {}
         self._perm = perm
         self._a8_rows, self._a8_need = 0, {}
-        self._grad_flags = _lib.GRAD_ON_COPY if (self.GRAD_ON_COPY if grad_on_copy is None else grad_on_copy) else 0
+        self._grad_flags = _lib.grad_copy_flags(self.GRAD_ON_COPY if grad_on_copy is None else grad_on_copy)      # True: 4 bits; "any_bits": 2, 3, 4, 8
         self._grad_plans = {}
         if act_int8 is None:
             act_int8 = self.ACT_INT8

@@ -312,11 +312,16 @@ int gptq_grad_input(const gptq_layer_t *layer, const void *dy, void *dx, int M, 
  * rows are not on the device needs no gptq_unprepack_decode in front of its backward).  Same contract: every weight is T(s * float(q - z)) as gptq_dequant
  * writes it, products and sums in fp32, one rounding at the store, accumulate adds the old dX in fp32 first; no workspace, no atomics, fixed summation order,
  * capturable.  A layer that does not qualify (2, 3, 8 bits, fp32, no copy, another group size) runs gptq_grad_input's kernel, and needs qweight.  Same
- * argument checks and status codes as gptq_grad_input; unknown flag bits: GPTQ_ERR_UNSUPPORTED. */
+ * argument checks and status codes as gptq_grad_input; unknown flag bits: GPTQ_ERR_UNSUPPORTED.
+ * GPTQ_GRAD_ON_COPY | GPTQ_GRAD_COPY_ANY_BITS (flags 5; opt-in): 2-, 3- and 8-bit layers qualify by the same rule (the same kernel behind a launch-uniform
+ * width: one weight front-end per packing of the copy; a 2-bit copy qualifies with or without GPTQ_COPY_ROWS_INT2 / _WIDE in tiled_cols).  4-bit layers
+ * run as under flags 1, bit for bit.  GPTQ_GRAD_COPY_ANY_BITS without GPTQ_GRAD_ON_COPY is an unknown flag (GPTQ_ERR_UNSUPPORTED). */
 #define GPTQ_GRAD_ON_COPY 1
+#define GPTQ_GRAD_COPY_ANY_BITS 4
 int gptq_grad_input_ex(const gptq_layer_t *layer, const void *dy, void *dx, int M, int accumulate, int flags, void *stream);
 /* Host-only: what gptq_grad_input_ex would launch for (layer, M, flags) --
  *   "kernel=grad_copy bm=<64|128> stages=<N / 64, rounded up> gm=<0|1|2> act=<0|1>"   or   "kernel=grad_rows reason=<flag_off|bits|dtype|no_copy|group_size>".
+ * A grad_copy line of a 2-, 3- or 8-bit layer (flags 5) ends in " bits=<2|3|8>"; the 4-bit line is the one above.
  * The layer's pointers are compared with NULL, never dereferenced; qweight may be NULL. */
 int gptq_describe_grad_input_plan(const gptq_layer_t *layer, int M, int flags, char *out, size_t out_bytes);
 
@@ -633,13 +638,16 @@ int gptq_describe_moe_backward_plan(const gptq_moe_t *moe, int T, int topk, char
  * its token's dx row follows) and dw differs in the last bits of its sums -- both forms are inside the contract above, and each is bit-reproducible
  * against itself.  Launches: five, or SIX where an expert's gate and up layers name different
  * output columns (different `perm` pointers: W1's launch stores the fp32 rows, W3's continues from them), four when dx is NULL.  Experts the copy form
- * declines run gptq_moe_backward's stages (grad_table required).  Unknown flag bits: GPTQ_ERR_UNSUPPORTED. */
+ * declines run gptq_moe_backward's stages (grad_table required).  Unknown flag bits: GPTQ_ERR_UNSUPPORTED.
+ * | GPTQ_GRAD_COPY_ANY_BITS (flags 5): experts of ONE width out of 2, 3, 4, 8 in all three projections are taken (2 and 3 bits: where gptq_moe_backward
+ * takes them, GPTQ_MOE_LOW_BIT); mixed widths are declined as a whole.  Routing, recompute and combine are the rows forms' as before. */
 int gptq_moe_backward_ex(const gptq_moe_t *moe, const void *table, const void *grad_table, const void *decode_table, const void *x, const int64_t *topk_idx,
                          const float *topk_w, const void *dout, int T, int topk, void *dx, float *dw, void *dgu_out, void *workspace,
                          size_t workspace_bytes, int flags, void *stream);
 /* Host-only: what gptq_moe_backward_ex would run for (moe, T, topk, flags).  flags = 0: gptq_describe_moe_backward_plan's line.  GPTQ_GRAD_ON_COPY:
  * "path=grouped_backward_copy tiles=3 launches=5 up_launches=1 gm=0 act=0 gm_down=0 wg_recompute=... wg_down=... wg_up=..." (gm / gm_down: the group mode
- * of the gate | up and of the down copies; wg_up per up-stage launch), or the rows form's line with a trailing "copy_reason=bits|dtype|no_copy|group_size";
+ * of the gate | up and of the down copies; wg_up per up-stage launch; flags 5 and 2-, 3- or 8-bit experts: a trailing " bits=<2|3|8>"), or the rows
+ * form's line with a trailing "copy_reason=bits|dtype|no_copy|group_size";
  * "path=per_expert reason=..." as before. */
 int gptq_describe_moe_backward_plan_ex(const gptq_moe_t *moe, int T, int topk, int flags, char *out, size_t out_bytes);
 

@@ -22,6 +22,7 @@ ap.add_argument("--launch", default="", help="K,N,M[,act]: only 20 plain launche
 ap.add_argument("--on-copy", action="store_true", help="with --launch: the kernel on the decode copy (post_init(grad_on_copy=True))")
 ap.add_argument("--ab", action="store_true", help="rows kernel against the kernel on the decode copy, same session (profiles/grad_copy_ab.log)")
 ap.add_argument("--ab-rounds", type=int, default=9)
+ap.add_argument("--ab-bits", default="4:128", help="with --ab: WIDTH:GROUP_SIZE of the layers; 2, 3, 8 run under grad_on_copy=\"any_bits\" (profiles/grad_copy_bits_ab.log)")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 lib = _lib.load()
@@ -82,6 +83,9 @@ def ab():
     without the flag (rebuild pass + rows kernel) and with it.  One call per timing, HIP events around it, a 512 MiB write in front of every call (weights, dY
     and dX out of the caches); the forms alternate inside each of --ab-rounds rounds; reported: median us and the spread (min .. max) of the rounds."""
     flush = torch.empty(512 << 20, dtype=torch.uint8, device=dev)
+    bits, gs = (int(v) for v in args.ab_bits.split(":"))
+    on = True if bits == 4 else "any_bits"
+    F = _lib.grad_copy_flags(on)
     st = lambda: torch.cuda.current_stream().cuda_stream
 
     def one(fn):
@@ -95,20 +99,20 @@ def ab():
 
     layers = [(4096, 4096, torch.float16, False), (4096, 11008, torch.float16, False), (11008, 4096, torch.float16, False), (4096, 11008, torch.bfloat16, True)]
     for K, N, dtype, act in layers:
-        q = bench.make_layer(K, N, dev, act_order=act, dtype=dtype, seed=K + N)
-        q.post_init(grad_on_copy=True)
+        q = bench.make_layer(K, N, dev, bits=bits, gs=gs, act_order=act, dtype=dtype, seed=K + N)
+        q.post_init(grad_on_copy=on)
         W16 = q.dequantize()
         rel = {}
         if not act:                                        # (act-order layers keep their rows: nothing to release)
             for flag in (False, True):
-                rel[flag] = bench.make_layer(K, N, dev, dtype=dtype, seed=K + N)
-                rel[flag].post_init(release_checkpoint_layout=True, grad_on_copy=flag)
+                rel[flag] = bench.make_layer(K, N, dev, bits=bits, gs=gs, dtype=dtype, seed=K + N)
+                rel[flag].post_init(release_checkpoint_layout=True, grad_on_copy=on if flag else False)
         for M in (64, 512, 2048):
             dy = (torch.randn(M, N, device=dev) * 0.5).to(dtype)
             dx, dxc, ref = (torch.empty(M, K, dtype=dtype, device=dev) for _ in range(3))
             forms = {
                 "rows": lambda: _lib.check(lib.gptq_grad_input(q._layer_ref, dy.data_ptr(), dx.data_ptr(), M, 0, st())),
-                "copy": lambda: _lib.check(lib.gptq_grad_input_ex(q._layer_ref, dy.data_ptr(), dxc.data_ptr(), M, 0, _lib.GRAD_ON_COPY, st())),
+                "copy": lambda: _lib.check(lib.gptq_grad_input_ex(q._layer_ref, dy.data_ptr(), dxc.data_ptr(), M, 0, F, st())),
                 "dense": lambda: torch.matmul(dy, W16.t(), out=ref),
                 "deq+mm": lambda: torch.matmul(dy, q.dequantize().t()),
             }
@@ -127,7 +131,7 @@ def ab():
             cells = "  ".join(f"{k} {med[k]:7.1f} ({min(v):.1f} .. {max(v):.1f})" for k, v in t.items())
             gap = med["rows"] - med["copy"]
             spread = max(max(t[k]) - min(t[k]) for k in ("rows", "copy"))
-            print(f"{K:5d}x{N:<5d} {str(dtype)[6:]:8s} {'act' if act else 'seq'} M={M:5d} [{q.describe_grad_plan(M)}]  {cells}  rows/copy {med['rows'] / med['copy']:.2f} "
+            print(f"{K:5d}x{N:<5d} {str(dtype)[6:]:8s} int{bits} g{gs} {'act' if act else 'seq'} M={M:5d} [{q.describe_grad_plan(M)}]  {cells}  rows/copy {med['rows'] / med['copy']:.2f} "
                   f"({'beyond' if gap > spread else 'WITHIN'} the repeat spread)  copy {2.0 * M * N * K / med['copy'] / 1e-6 / PEAK:.2f} of peak  "
                   f"same bits as rows: {bool(torch.equal(dx, dxc))}  rel.err vs dense {err:.1e}", flush=True)
 

@@ -26,6 +26,7 @@ ap.add_argument("--models", default="mixtral,qwen")
 ap.add_argument("--ts", default="512,2048,8192")
 ap.add_argument("--act", default="0,1")
 ap.add_argument("--gs", type=int, default=128)
+ap.add_argument("--bits", type=int, default=4, help="the experts' width; 2, 3, 8 run under backward_on_copy = \"any_bits\" (profiles/grad_copy_bits_ab.log)")
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--blocks", type=int, default=2, help="expert blocks the graph rotates over (one block is already larger than the 256 MiB Infinity Cache)")
@@ -34,6 +35,7 @@ ap.add_argument("--out", default="")
 a = ap.parse_args()
 dev, dt = torch.device("cuda:0"), torch.float16
 lib = _lib.load()
+FLAGS = _lib.grad_copy_flags(True if a.bits == 4 else "any_bits")
 log = open(a.out, "w") if a.out else None
 
 
@@ -46,8 +48,8 @@ def say(s):
 
 def fill(l, act, g):
     K, N, G = l.infeatures, l.outfeatures, -(-l.infeatures // a.gs)
-    l.qweight = torch.randint(-2**31, 2**31 - 1, (K // 8, N), dtype=torch.int64, device=dev, generator=g).to(torch.int32)
-    l.qzeros = torch.randint(-2**31, 2**31 - 1, (G, N // 8), dtype=torch.int64, device=dev, generator=g).to(torch.int32)
+    l.qweight = torch.randint(-2**31, 2**31 - 1, (K // 32 * a.bits, N), dtype=torch.int64, device=dev, generator=g).to(torch.int32)
+    l.qzeros = torch.randint(-2**31, 2**31 - 1, (G, N // 32 * a.bits), dtype=torch.int64, device=dev, generator=g).to(torch.int32)
     l.scales = (0.002 * (1 + 0.1 * torch.rand(G, N, device=dev, generator=g))).to(dt)
     gi = torch.arange(K, device=dev, dtype=torch.int32) // a.gs
     l.g_idx = (gi[torch.randperm(K, device=dev, generator=g)] if act else gi).contiguous()
@@ -55,15 +57,15 @@ def fill(l, act, g):
 
 def block(H, I, E, topk, act, seed):
     g = torch.Generator(device=dev).manual_seed(seed)
-    q = QuantMoEExperts(E, H, I, 4, a.gs, top_k=topk, weight_dtype=dt)
+    q = QuantMoEExperts(E, H, I, a.bits, a.gs, top_k=topk, weight_dtype=dt)
     for e in range(E):
         gate, up, down = q[e].layers()
         fill(gate, act, g), fill(up, act, g), fill(down, act, g)
         if act:
             up.g_idx = gate.g_idx.clone()          # one order for gate and up, as a GPTQ checkpoint has them
     q = q.to(dev)
-    q.backward_on_copy = True
-    q.post_init(backward=True)
+    q.backward_on_copy = True if a.bits == 4 else "any_bits"
+    q.post_init(backward=True, low_bit=a.bits < 4, low_bit_decode=a.bits < 4)
     assert q._backward_on_copy, "the experts were declined"
     return q
 
@@ -99,7 +101,7 @@ def stat(ts):
     return statistics.median(ts), max(ts) / min(ts) - 1
 
 
-say(f"# MoE backward: rows form (flags = 0) against the copy form (GPTQ_GRAD_ON_COPY) on the same 4-bit g{a.gs} fp16 experts; ms per whole call (route, "
+say(f"# MoE backward: rows form (flags = 0) against the copy form (GPTQ_GRAD_ON_COPY) on the same {a.bits}-bit g{a.gs} fp16 experts; ms per whole call (route, "
     f"recompute, down, up, combine), median of {a.rounds} rounds x {a.reps} graph replays over {a.blocks} rotating expert blocks; spread = max / min - 1")
 cells, spreads = [], []
 for name in filter(None, a.models.split(",")):      # (--models "" with --parent-lib: the dense A/B alone)
@@ -113,7 +115,7 @@ for name in filter(None, a.models.split(",")):      # (--models "" with --parent
             w = torch.full((T, topk), 1.0 / topk, device=dev)
             need = int(lib.gptq_moe_backward_workspace_bytes(ctypes.byref(qs[0]._moe), T, topk))
             ws = torch.zeros(need, dtype=torch.uint8, device=dev)
-            dx = {f: torch.empty((T, H), dtype=dt, device=dev) for f in (0, 1)}
+            dx = {f: torch.empty((T, H), dtype=dt, device=dev) for f in (0, FLAGS)}
             dw = torch.empty((T, topk), dtype=torch.float32, device=dev)
             st = torch.cuda.current_stream
 
@@ -124,11 +126,11 @@ for name in filter(None, a.models.split(",")):      # (--models "" with --parent
                                                         dw.data_ptr(), None, ws.data_ptr(), need, flags, st(dev).cuda_stream))
                 return len(qs)
 
-            t = ab({"rows": lambda: call(0), "copy": lambda: call(_lib.GRAD_ON_COPY)}, a.reps)
-            nd, md = int((dx[0] != dx[1]).sum()), float((dx[0].float() - dx[1].float()).abs().max())
+            t = ab({"rows": lambda: call(0), "copy": lambda: call(FLAGS)}, a.reps)
+            nd, md = int((dx[0] != dx[FLAGS]).sum()), float((dx[0].float() - dx[FLAGS].float()).abs().max())
             (m0, s0), (m1, s1) = stat(t["rows"]), stat(t["copy"])
             spreads += [s0, s1]
-            plan = _lib.describe_moe_backward_plan_ex(qs[0]._moe, T, topk, _lib.GRAD_ON_COPY)
+            plan = _lib.describe_moe_backward_plan_ex(qs[0]._moe, T, topk, FLAGS)
             cells.append((name, act, T, m0, m1))
             say(f"{name:7s} H={H} I={I} E={E} topk={topk} {'act-order' if act else 'plain    '} T={T:5d} launches={plan['launches']} | rows {m0 * 1e3:8.3f} ms "
                 f"(spread {s0 * 100:4.1f} %) | copy {m1 * 1e3:8.3f} ms (spread {s1 * 100:4.1f} %) | {m0 / m1:5.2f}x | dX: {nd} of {T * H} elements differ, max |diff| {md:.1e}")

@@ -488,11 +488,15 @@ def describe_adapter_rows_plan(banks, M: int) -> dict:
 _INITED = set()
 
 
+def _device_index(device) -> int:
+    """The index of a GPU device given as a torch.device, a string or an index (no index: the current device)."""
+    idx = torch.device(device).index
+    return torch.cuda.current_device() if idx is None else idx
+
+
 def ensure_init(device) -> None:
     """gptq_init() once per device (outside stream capture: QuantLinear.post_init calls this)."""
-    idx = torch.device(device).index
-    if idx is None:
-        idx = torch.cuda.current_device()
+    idx = _device_index(device)
     if idx in _INITED:
         return
     with torch.cuda.device(idx):
@@ -504,5 +508,44 @@ def ptr(t):
     return None if t is None else t.data_ptr()
 
 
+# The one name for "the current stream": the raw hipStream_t of device ``idx`` (an int), without building a torch.cuda.Stream object.  A released layer's rows
+# rebuild and the kernel that reads the rows are ordered only because both ask here.
+try:
+    _raw_stream = torch._C._cuda_getCurrentRawStream
+except AttributeError:                 # pragma: no cover
+    def _raw_stream(idx):
+        return torch.cuda.current_stream(idx).cuda_stream
+
+
 def current_stream_handle(device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
+    """_raw_stream for a torch.device or a device string (the older name; the package itself calls _raw_stream)."""
+    return _raw_stream(_device_index(device))
+
+
+# The C ABI reads and writes dense rows: contiguous, data pointer a multiple of 16 (include/gptq_mi355x.h).  Every entry point prepares its inputs here.
+def _is_dense16(t: torch.Tensor) -> bool:
+    """The predicate, for the places that test an OUTPUT (y, out, ys) and fall back instead of copying."""
+    return t.is_contiguous() and not t.data_ptr() & 15
+
+
+def _dense16(t: torch.Tensor, dtype=None) -> torch.Tensor:
+    """``t`` in ``dtype`` (if given and different: a cast), contiguous and 16-byte aligned: ``t`` itself when nothing is needed.  Without a cast at most one
+    copy: .contiguous() allocates (aligned), so only a contiguous view at an odd element offset takes the clone."""
+    if dtype is not None and t.dtype != dtype:
+        t = t.to(dtype)
+    if not t.is_contiguous():
+        return t.contiguous()
+    if t.data_ptr() & 15:
+        return t.clone()
+    return t
+
+
+def _rows16(x: torch.Tensor, K: int, dtype):
+    """``(x2, M)``: x viewed as dense, aligned rows [M, K] in ``dtype`` -- cast, reshape, contiguous, align, in this order.  Whatever comes back is
+    [M, K]: a tensor whose element count is no multiple of K raises in the reshape, so no kernel is ever told a width its buffer does not have."""
+    if x.dtype != dtype:
+        x = x.to(dtype)
+    if x.dim() != 2 or x.shape[1] != K:
+        x = x.reshape(-1, K)
+    x = _dense16(x)
+    return x, x.shape[0]

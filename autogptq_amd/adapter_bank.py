@@ -22,7 +22,7 @@ import torch.nn as nn
 
 from . import _lib
 from .lora import _matches, parse_adapter_key
-from .qlinear_mi355x import QuantLinear, _raw_stream, _warn_once, forward_multi
+from .qlinear_mi355x import QuantLinear, _on_device, _raw_stream, _warn_once, forward_multi
 
 NO_ADAPTER = -1
 
@@ -66,9 +66,8 @@ class AdapterRouting:
             self.rows = rows
         if self.rows:
             idx = self.device.index
-            with torch.cuda.device(idx):
-                _lib.check(_lib.load().gptq_adapter_route(self.ids.data_ptr(), self.rows, self.num_slots, self.route.data_ptr(), self.route_bytes,
-                                                         _raw_stream(idx)))
+            _lib.check(_on_device(idx, _lib.load().gptq_adapter_route, self.ids.data_ptr(), self.rows, self.num_slots, self.route.data_ptr(),
+                                  self.route_bytes, _raw_stream(idx)))
         return self
 
 
@@ -186,10 +185,8 @@ class LoraBankQuantLinear(nn.Module):
 def _apply_banks(layers, x: torch.Tensor, ys, routing: AdapterRouting, M: int):
     """ys[i] += the routed adapter term of layers[i], in place (a copy where the base output is not dense and aligned): one gptq_adapter_rows_apply per
     group of up to 4 layers."""
-    x2 = x.reshape(-1, x.shape[-1])
-    if not x2.is_contiguous() or x2.data_ptr() % 16:
-        x2 = x2.clone(memory_format=torch.contiguous_format)
-    ys = [y if y.is_contiguous() and y.data_ptr() % 16 == 0 else y.clone(memory_format=torch.contiguous_format) for y in ys]
+    x2 = _lib._dense16(x.reshape(-1, x.shape[-1]))
+    ys = [_lib._dense16(y) for y in ys]
     lib = _lib.load()
     idx = x2.device.index
     for i in range(0, len(layers), _lib.LORA_MAX):
@@ -203,8 +200,7 @@ def _apply_banks(layers, x: torch.Tensor, ys, routing: AdapterRouting, M: int):
             arr = (ctypes.POINTER(_lib.GptqAdapterBank) * n)(*[ctypes.pointer(l._bank_struct()[0]) for l in grp])
             uptr = (ctypes.c_void_p * n)(*[u.data_ptr() for u in us])
             optr = (ctypes.c_void_p * n)(*[y.data_ptr() for y in gys])
-        with torch.cuda.device(idx):
-            _lib.check(lib.gptq_adapter_rows_apply(arr, n, x2.data_ptr(), uptr, optr, routing.route.data_ptr(), M, _raw_stream(idx)))
+        _lib.check(_on_device(idx, lib.gptq_adapter_rows_apply, arr, n, x2.data_ptr(), uptr, optr, routing.route.data_ptr(), M, _raw_stream(idx)))
     return ys
 
 
@@ -218,7 +214,7 @@ def lora_bank_forward_multi(layers, x: torch.Tensor):
     T = a.lora_A_bank.dtype
     if any(l.lora_A_bank.dtype != T or l.in_features != a.in_features or l.routing is not a.routing for l in layers):
         raise RuntimeError("lora_bank_forward_multi: the layers must share the input's feature count, the weight dtype and the routing")
-    if any(getattr(l.base, "_parts", None) is not None for l in layers):
+    if any(l.base._parts is not None for l in layers):
         return [l(x) for l in layers]
     x_dtype = x.dtype
     xw = x.to(T) if x_dtype != T else x

@@ -65,7 +65,7 @@ def unpack_awq(awq_qweight: torch.Tensor, awq_qzeros: torch.Tensor, awq_scales: 
     zeros = torch.empty((G, N), dtype=torch.int8, device=dev)
     lib = _lib.load()
     _lib.check(lib.gptq_awq_unpack(qw.data_ptr(), qz.data_ptr(), sc.data_ptr(), K, N, group_size, w_kn.data_ptr(), zeros.data_ptr(),
-                                   _lib.current_stream_handle(dev)))
+                                   _lib._raw_stream(dev.index)))
     return w_kn.T, zeros
 
 
@@ -91,7 +91,7 @@ def pack_from_tensors(unpacked_qweight: torch.Tensor, unpacked_qzeros: torch.Ten
     qzeros = torch.empty((G, N // 8), dtype=torch.int32, device=dev)
     scales_out = torch.empty((G, N), dtype=W.dtype, device=dev)
     lib = _lib.load()
-    st = _lib.current_stream_handle(dev)
+    st = _lib._raw_stream(dev.index)
     _lib.check(lib.gptq_pack_weights(W.data_ptr(), sc.data_ptr(), z_f.data_ptr(), g_idx.data_ptr(), K, N, 4, group_size,
                                      _lib.DTYPE_ENUM[W.dtype], _lib.DTYPE_ENUM[sc.dtype], qweight.data_ptr(), scales_out.data_ptr(), st))
     # pack() ORs the unmasked zero-1 (an all-ones word for z = 0); pack_from_tensors masks the field first: hand the
@@ -116,5 +116,5 @@ def repack_awq_to_gptq(awq_qweight: torch.Tensor, awq_qzeros: torch.Tensor, grou
     qzeros = torch.empty((G, NW), dtype=torch.int32, device=dev)
     lib = _lib.load()
     _lib.check(lib.gptq_awq_repack(qw.data_ptr(), qz.data_ptr(), K, N, group_size, qweight.data_ptr(), qzeros.data_ptr(),
-                                   _lib.current_stream_handle(dev)))
+                                   _lib._raw_stream(dev.index)))
     return qweight, qzeros

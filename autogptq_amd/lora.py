@@ -26,7 +26,7 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .qlinear_mi355x import QuantLinear, _raw_stream, _warn_once, forward_multi
+from .qlinear_mi355x import QuantLinear, _on_device, _raw_stream, _warn_once, forward_multi
 
 MERGE_MESSAGE = "gptq model not support merge lora adapter"          # peft_utils.py:94-98
 
@@ -162,15 +162,13 @@ class LoraQuantLinear(nn.Module):
         M = x2.shape[0]
         if M == 0:
             return y, x2.new_empty((0, self.r))
-        if self.fused_ok(A16.dtype) and y.is_contiguous() and y.data_ptr() % 16 == 0:
-            if not x2.is_contiguous() or x2.data_ptr() % 16:
-                x2 = x2.clone(memory_format=torch.contiguous_format)
+        if self.fused_ok(A16.dtype) and _lib._is_dense16(y):
+            x2 = _lib._dense16(x2)
             L, arr, uptr, optr, _, _ = self._lora_struct(A16, B16)
             u = torch.empty((M, self.r), dtype=A16.dtype, device=y.device)
             uptr[0], optr[0] = u.data_ptr(), y.data_ptr()
             idx = y.device.index
-            with torch.cuda.device(idx):
-                rc = _lib.load().gptq_lora_apply(arr, 1, x2.data_ptr(), uptr, optr, M, _raw_stream(idx))
+            rc = _on_device(idx, _lib.load().gptq_lora_apply, arr, 1, x2.data_ptr(), uptr, optr, M, _raw_stream(idx))
             if rc == 0:
                 return y, u
             if rc != 3:                                             # GPTQ_ERR_UNSUPPORTED falls through to the composition
@@ -262,17 +260,13 @@ def _fused_backward(x2: torch.Tensor, items, need_x: bool, dx: torch.Tensor = No
     if M == 0:
         return (dx if need_x else None), [(torch.zeros((a.shape[0], K), dtype=torch.float32, device=dev) if na else None,
                                            torch.zeros(tuple(b.shape), dtype=torch.float32, device=dev) if nb else None) for a, b, _, _, _, na, nb in items]
-    if not x2.is_contiguous() or x2.data_ptr() % 16:
-        x2 = x2.clone(memory_format=torch.contiguous_format)
+    x2 = _lib._dense16(x2)
     lib = _lib.load()
     loras, grads, keep, outs = [], [], [], []
     for A16, B16, u, dy, scale, need_a, need_b in items:
         N, r = B16.shape
-        dy2 = dy.reshape(-1, N)
-        if dy2.dtype != T or not dy2.is_contiguous() or dy2.data_ptr() % 16:
-            dy2 = dy2.to(T).clone(memory_format=torch.contiguous_format)
-        if not u.is_contiguous() or u.data_ptr() % 16:
-            u = u.clone(memory_format=torch.contiguous_format)
+        dy2 = _lib._dense16(dy.reshape(-1, N), T)
+        u = _lib._dense16(u)
         At, Bt = A16.t().contiguous(), B16.t().contiguous()        # r-sized copies: the reused kernels' operands as they want them
         du = torch.empty((M, r), dtype=T, device=dev)
         da = torch.empty((r, K), dtype=torch.float32, device=dev) if need_a else None
@@ -289,11 +283,9 @@ def _fused_backward(x2: torch.Tensor, items, need_x: bool, dx: torch.Tensor = No
     la = (ctypes.POINTER(_lib.GptqLora) * n)(*[ctypes.pointer(L) for L in loras])
     ga = (ctypes.POINTER(_lib.GptqLoraGrad) * n)(*[ctypes.pointer(G) for G in grads])
     idx = dev.index
-    with torch.cuda.device(idx):
-        nbytes = lib.gptq_lora_backward_workspace_bytes(la, n, M)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
-        rc = lib.gptq_lora_backward(la, ga, n, x2.data_ptr(), dx.data_ptr() if need_x else None, M, ws.data_ptr() if nbytes else None, nbytes,
-                                    _raw_stream(idx))
+    nbytes = lib.gptq_lora_backward_workspace_bytes(la, n, M)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    rc = _on_device(idx, lib.gptq_lora_backward, la, ga, n, x2.data_ptr(), dx.data_ptr() if need_x else None, M, _lib.ptr(ws), nbytes, _raw_stream(idx))
     if rc == 3:                                                     # GPTQ_ERR_UNSUPPORTED: nothing was launched
         _warn_once(f"LoraQuantLinear: gptq_lora_backward declined a call ({lib.gptq_last_error().decode()}); the adapter's backward runs on torch matmuls")
         return None
@@ -312,9 +304,7 @@ class _LoraGroupApply(torch.autograd.Function):
         ys, As, Bs = rest[:n], rest[n:2 * n], rest[2 * n:]
         T = ys[0].dtype
         K = layers[0].in_features
-        x2 = xw.reshape(-1, K)
-        if not x2.is_contiguous() or x2.data_ptr() % 16:
-            x2 = x2.clone(memory_format=torch.contiguous_format)
+        x2 = _lib._dense16(xw.reshape(-1, K))
         M = x2.shape[0]
         A16 = [a.detach().to(T).contiguous() for a in As]
         B16 = [b.detach().to(T).contiguous() for b in Bs]
@@ -330,8 +320,7 @@ class _LoraGroupApply(torch.autograd.Function):
         uptr = (ctypes.c_void_p * n)(*[u.data_ptr() for u in us])
         optr = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
         idx = x2.device.index
-        with torch.cuda.device(idx):
-            _lib.check(_lib.load().gptq_lora_apply(arr, n, x2.data_ptr(), uptr, optr, M, _raw_stream(idx)))
+        _lib.check(_on_device(idx, _lib.load().gptq_lora_apply, arr, n, x2.data_ptr(), uptr, optr, M, _raw_stream(idx)))
         ctx.save_for_backward(x2, *us, *A16, *B16)
         ctx.n = n
         ctx.x_shape = xw.shape
@@ -385,7 +374,7 @@ def lora_forward_multi(layers, x: torch.Tensor):
     gradients, bases that are not single layers, or adapters the kernels decline: per-layer calls.  A call that records gradients whose layers all have
     ``fused_backward`` on (and are accepted by gptq_lora_backward) stays grouped: one autograd node per group of up to 4 (_LoraGroupApply)."""
     layers = list(layers)
-    plain = all(isinstance(l, LoraQuantLinear) and getattr(l.base, "_parts", None) is None for l in layers)
+    plain = all(isinstance(l, LoraQuantLinear) and l.base._parts is None for l in layers)
     if not plain or any(l.training and l.lora_dropout > 0.0 for l in layers):
         return [l(x) for l in layers]
     a = layers[0]
@@ -399,7 +388,7 @@ def lora_forward_multi(layers, x: torch.Tensor):
     K = a.in_features
     x2 = xw.reshape(-1, K)
     M = x2.shape[0]
-    fused = not grad and M > 0 and all(l.fused_ok(T) for l in layers) and all(y.is_contiguous() and y.data_ptr() % 16 == 0 for y in ys)
+    fused = not grad and M > 0 and all(l.fused_ok(T) for l in layers) and all(_lib._is_dense16(y) for y in ys)
     group = (grad and M > 0 and x2.is_cuda and all(l.fused_backward and l.fused_ok(T) and l.fused_backward_ok(T) for l in layers))
     if group:
         outs = []
@@ -409,8 +398,7 @@ def lora_forward_multi(layers, x: torch.Tensor):
     elif not fused:
         outs = [l._after_base(y, xw) for l, y in zip(layers, ys)]
     else:
-        if not x2.is_contiguous() or x2.data_ptr() % 16:
-            x2 = x2.clone(memory_format=torch.contiguous_format)
+        x2 = _lib._dense16(x2)
         lib = _lib.load()
         idx = x2.device.index
         for i in range(0, len(layers), _lib.LORA_MAX):
@@ -421,8 +409,7 @@ def lora_forward_multi(layers, x: torch.Tensor):
             us = [torch.empty((M, l.r), dtype=T, device=x2.device) for l in grp]
             uptr = (ctypes.c_void_p * n)(*[u.data_ptr() for u in us])
             optr = (ctypes.c_void_p * n)(*[y.data_ptr() for y in gys])
-            with torch.cuda.device(idx):
-                _lib.check(lib.gptq_lora_apply(arr, n, x2.data_ptr(), uptr, optr, M, _raw_stream(idx)))
+            _lib.check(_on_device(idx, lib.gptq_lora_apply, arr, n, x2.data_ptr(), uptr, optr, M, _raw_stream(idx)))
         outs = list(ys)
     return [o.to(x_dtype) for o in outs] if x_dtype != T else outs
 

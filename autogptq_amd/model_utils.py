@@ -165,7 +165,7 @@ def autogptq_post_init(model: nn.Module, use_act_order: bool = False, max_input_
                       act_int8=(True if act_int8 else None), grad_on_copy=(grad_on_copy if grad_on_copy else None))
         lib = _lib.load()
         # the need is not monotone in M (K splits come and go with the kernel the planner picks): maximum over 1..rows
-        parts = getattr(sub, "_parts", None)
+        parts = sub._parts
         if parts is not None:
             # fused-QKV g_idx (len n * K): the module runs its n column blocks through forward_multi -- the blocks' own needs and the one-launch need of the group
             b = max(int(lib.gptq_workspace_bytes_max(ctypes.byref(p._layer), rows)) for p in parts)

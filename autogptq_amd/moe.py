@@ -54,7 +54,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .qlinear_mi355x import QuantLinear, _raw_stream, exchange_tick, forward_multi, mlp_forward, reserve_workspace, share_act_order
+from .qlinear_mi355x import QuantLinear, _on_device, _raw_stream, exchange_tick, forward_multi, mlp_forward, reserve_workspace, share_act_order
 
 logger = getLogger(__name__)
 
@@ -303,7 +303,7 @@ class QuantMoEExperts(nn.Module):
         sw["decode_copy"] = copy
         self._switches = sw
         with torch.cuda.device(self._dev):
-            stream = _lib.current_stream_handle(self._dev)
+            stream = _raw_stream(self._dev.index)
             if _PATHS["grouped"].describe(m, 1, self.top_k)["path"] == "grouped":          # (a declined layer set has no valid table: it runs per expert)
                 _lib.check(lib.gptq_moe_build_table(ctypes.byref(m), table.data_ptr(), stream))
             if gplan is not None and gplan["path"] == "grouped_backward":
@@ -439,7 +439,7 @@ def moe_forward(experts: QuantMoEExperts, x: torch.Tensor, top_k_index: torch.Te
     dev, w_dtype = experts._dev, experts._w_dtype
     if x.device != dev:
         raise RuntimeError(f"mi355x moe_forward: input is on {x.device}, the experts on {dev}")
-    xw = _aligned(x2, w_dtype)
+    xw = _lib._dense16(x2, w_dtype)
     idx, w = _routing(top_k_index, top_k_weights, T, topk)
     out = torch.empty((T, H), dtype=w_dtype, device=dev)
     h_out = None
@@ -454,10 +454,9 @@ def moe_forward(experts: QuantMoEExperts, x: torch.Tensor, top_k_index: torch.Te
         buf = reserve_workspace(dev, need)
         exchange_tick(dev)
         idx_dev = experts._dev.index
-        with torch.cuda.device(idx_dev):
-            entry = _PATHS[path]
-            rc = getattr(_lib.load(), entry.forward)(ctypes.byref(experts._moe_of(path)), getattr(experts, entry.table).data_ptr(), xw.data_ptr(), idx.data_ptr(),
-                                                     w.data_ptr(), T, topk, out.data_ptr(), _lib.ptr(h_out), buf.data_ptr(), buf.numel(), _raw_stream(idx_dev))
+        entry = _PATHS[path]
+        rc = _on_device(idx_dev, getattr(_lib.load(), entry.forward), ctypes.byref(experts._moe_of(path)), getattr(experts, entry.table).data_ptr(), xw.data_ptr(),
+                        idx.data_ptr(), w.data_ptr(), T, topk, out.data_ptr(), _lib.ptr(h_out), buf.data_ptr(), buf.numel(), _raw_stream(idx_dev))
         if rc:
             _lib.check(rc)
     res = out.to(x.dtype) if x.dtype != w_dtype else out
@@ -475,17 +474,6 @@ def _grouped_backward_ready(experts: QuantMoEExperts) -> bool:
     """The experts were post-initialised with backward=True and the backward plan took them (post_init runs here when the tables were invalidated)."""
     experts._ensure_init()
     return experts._grad_table is not None
-
-
-def _aligned(t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
-    """t as a contiguous, 16-byte aligned tensor of ``dtype`` (the C ABI's rule for x / dout)."""
-    if t.dtype != dtype:
-        t = t.to(dtype)
-    if not t.is_contiguous():
-        t = t.contiguous()
-    if t.data_ptr() & 15:                 # a contiguous view at an odd element offset
-        t = t.clone()
-    return t
 
 
 def _routing(top_k_index: torch.Tensor, top_k_weights: torch.Tensor, T: int, topk: int):
@@ -522,10 +510,10 @@ class _MoEBackward(torch.autograd.Function):
         want_x, want_w = ctx.needs_input_grad[1], ctx.needs_input_grad[3]
         H = experts.hidden_dim
         dev, w_dtype = experts._dev, experts._w_dtype
-        x2 = _aligned(x.reshape(-1, H), w_dtype)
+        x2 = _lib._dense16(x.reshape(-1, H), w_dtype)
         T = x2.shape[0]
         topk = top_k_index.shape[-1] if top_k_index.dim() else 1
-        dout = _aligned(grad_out.reshape(-1, H), w_dtype)
+        dout = _lib._dense16(grad_out.reshape(-1, H), w_dtype)
         idx, w = _routing(top_k_index, top_k_weights, T, topk)
         dx = torch.empty((T, H), dtype=w_dtype, device=dev) if want_x else None
         dw = torch.empty((T, topk), dtype=torch.float32, device=dev) if want_w else None
@@ -535,12 +523,11 @@ class _MoEBackward(torch.autograd.Function):
                 need = experts._plans[("bws", T, topk)] = experts.backward_workspace_bytes(T, topk)
             buf = reserve_workspace(dev, need)
             exchange_tick(dev)
-            with torch.cuda.device(dev.index):
-                on_copy = experts._backward_on_copy and experts._decode_table is not None
-                rc = _lib.load().gptq_moe_backward_ex(ctypes.byref(experts._moe), experts._table.data_ptr(), experts._grad_table.data_ptr(),
-                                                      _lib.ptr(experts._decode_table), x2.data_ptr(), idx.data_ptr(), w.data_ptr(), dout.data_ptr(), T, topk,
-                                                      _lib.ptr(dx), _lib.ptr(dw), None, buf.data_ptr(), buf.numel(), experts._backward_flags if on_copy else 0,
-                                                      _raw_stream(dev.index))
+            on_copy = experts._backward_on_copy and experts._decode_table is not None
+            rc = _on_device(dev.index, _lib.load().gptq_moe_backward_ex, ctypes.byref(experts._moe), experts._table.data_ptr(), experts._grad_table.data_ptr(),
+                            _lib.ptr(experts._decode_table), x2.data_ptr(), idx.data_ptr(), w.data_ptr(), dout.data_ptr(), T, topk,
+                            _lib.ptr(dx), _lib.ptr(dw), None, buf.data_ptr(), buf.numel(), experts._backward_flags if on_copy else 0,
+                            _raw_stream(dev.index))
             if rc:
                 _lib.check(rc)
         gx = dx.to(x.dtype).reshape(x.shape) if want_x else None
@@ -611,7 +598,7 @@ def moe_route(x: torch.Tensor, weight: torch.Tensor, top_k: int, renorm: bool = 
         plan = {"path": "none", "reason": "grad enabled and x / weight require grad"}
     elif x2.dtype != weight.dtype:
         plan = {"path": "none", "reason": f"x is {x2.dtype}, weight {weight.dtype}"}
-    elif not weight.is_contiguous() or weight.data_ptr() & 15:
+    elif not _lib._is_dense16(weight):
         plan = {"path": "none", "reason": "weight must be contiguous and 16-byte aligned"}
     else:
         plan = router_plan(T, H, E, top_k, x2.dtype, renorm)
@@ -619,17 +606,13 @@ def moe_route(x: torch.Tensor, weight: torch.Tensor, top_k: int, renorm: bool = 
     if plan["path"] != "router":
         return _route_composition(x2, weight, top_k, renorm, return_logits)
     dev = x2.device
-    if not x2.is_contiguous():
-        x2 = x2.contiguous()
-    if x2.data_ptr() & 15:                # a contiguous view at an odd element offset: the C ABI takes 16-byte aligned x
-        x2 = x2.clone()
+    x2 = _lib._dense16(x2)
     logits = torch.empty((T, E), dtype=x2.dtype, device=dev) if return_logits else None
     idx = torch.empty((T, top_k), dtype=torch.int64, device=dev)
     w = torch.empty((T, top_k), dtype=torch.float32, device=dev)
     if T:
-        with torch.cuda.device(dev.index):
-            rc = _lib.load().gptq_moe_router(x2.data_ptr(), weight.data_ptr(), T, H, E, top_k, _lib.DTYPE_ENUM[x2.dtype],
-                                             _lib.ROUTER_RENORM if renorm else 0, _lib.ptr(logits), idx.data_ptr(), w.data_ptr(), _raw_stream(dev.index))
+        rc = _on_device(dev.index, _lib.load().gptq_moe_router, x2.data_ptr(), weight.data_ptr(), T, H, E, top_k, _lib.DTYPE_ENUM[x2.dtype],
+                        _lib.ROUTER_RENORM if renorm else 0, _lib.ptr(logits), idx.data_ptr(), w.data_ptr(), _raw_stream(dev.index))
         if rc:
             _lib.check(rc)
     return logits, w, idx
@@ -715,7 +698,7 @@ def moe_route_grouped(x: torch.Tensor, weight: torch.Tensor, bias: "torch.Tensor
         plan = {"path": "none", "reason": "grad enabled and x / weight require grad"}
     elif x2.dtype != weight.dtype:
         plan = {"path": "none", "reason": f"x is {x2.dtype}, weight {weight.dtype}"}
-    elif not weight.is_contiguous() or weight.data_ptr() & 15:
+    elif not _lib._is_dense16(weight):
         plan = {"path": "none", "reason": "weight must be contiguous and 16-byte aligned"}
     elif bias is not None and tuple(bias.shape) != (E,):
         plan = {"path": "none", "reason": f"bias must be [{E}]"}
@@ -727,19 +710,15 @@ def moe_route_grouped(x: torch.Tensor, weight: torch.Tensor, bias: "torch.Tensor
     if plan["path"] != "router_grouped":
         return _route_grouped_composition(x2, weight, bias, top_k, n_group, topk_group, renorm, scale, return_logits)
     dev = x2.device
-    if not x2.is_contiguous():
-        x2 = x2.contiguous()
-    if x2.data_ptr() & 15:
-        x2 = x2.clone()
+    x2 = _lib._dense16(x2)
     b = _bias_f32(bias) if bias is not None else None
     logits = torch.empty((T, E), dtype=torch.float32, device=dev) if return_logits else None
     idx = torch.empty((T, top_k), dtype=torch.int64, device=dev)
     w = torch.empty((T, top_k), dtype=torch.float32, device=dev)
     if T:
-        with torch.cuda.device(dev.index):
-            rc = _lib.load().gptq_moe_router_grouped(x2.data_ptr(), weight.data_ptr(), _lib.ptr(b), T, H, E, top_k, n_group, topk_group, scale,
-                                                     _lib.DTYPE_ENUM[x2.dtype], _lib.ROUTER_RENORM if renorm else 0, _lib.ptr(logits), None, idx.data_ptr(),
-                                                     w.data_ptr(), _raw_stream(dev.index))
+        rc = _on_device(dev.index, _lib.load().gptq_moe_router_grouped, x2.data_ptr(), weight.data_ptr(), _lib.ptr(b), T, H, E, top_k, n_group, topk_group, scale,
+                        _lib.DTYPE_ENUM[x2.dtype], _lib.ROUTER_RENORM if renorm else 0, _lib.ptr(logits), None, idx.data_ptr(), w.data_ptr(),
+                        _raw_stream(dev.index))
         if rc:
             _lib.check(rc)
     return logits, w, idx
@@ -884,7 +863,7 @@ def moe_shared_forward(experts: QuantMoEExperts, shared_layers, gate_weight: "to
             why = f"gate_weight is {gate_weight.dtype} on {gate_weight.device}, the shared layers {w_dtype} on {x.device}"
         elif w_dtype not in (torch.float16, torch.bfloat16) or H % 8:
             why = "the shared combine kernel takes fp16 / bf16 and H % 8 == 0"
-        elif gate_weight is not None and (gate_weight.numel() != H or not gate_weight.is_contiguous() or gate_weight.data_ptr() & 15):
+        elif gate_weight is not None and (gate_weight.numel() != H or not _lib._is_dense16(gate_weight)):
             why = "gate_weight must be [1, H], contiguous and 16-byte aligned"
     if why:
         if return_intermediate:
@@ -894,7 +873,7 @@ def moe_shared_forward(experts: QuantMoEExperts, shared_layers, gate_weight: "to
         out = routed + shared if gate_weight is None else routed + torch.sigmoid(F.linear(x2, gate_weight.reshape(1, H))) * shared
         experts.last_plan = dict(experts.last_plan or {}, shared="torch", shared_reason=why)
         return out.reshape(lead + (H,))
-    xw = _aligned(x2, w_dtype)
+    xw = _lib._dense16(x2, w_dtype)
     fused = 0 < T <= min(4, experts.__dict__.get("shared_decode_max_tokens", SHARED_DECODE_MAX_TOKENS)) and \
         shared_plan(experts, shared_layers, T, topk)["path"] == "decode_shared"
     if not fused:
@@ -903,13 +882,12 @@ def moe_shared_forward(experts: QuantMoEExperts, shared_layers, gate_weight: "to
                                f"({shared_plan(experts, shared_layers, T, topk).get('reason', '') if T else 'no tokens'})")
         out = moe_forward(experts, xw, top_k_index, top_k_weights)
         out = out.reshape(T, H)
-        if out.dtype != w_dtype or not out.is_contiguous() or out.data_ptr() & 15 or out.data_ptr() == xw.data_ptr():
+        if out.dtype != w_dtype or not _lib._is_dense16(out) or out.data_ptr() == xw.data_ptr():
             out = out.to(w_dtype).clone()
         if T:
-            ys = _aligned(mlp_forward(gate, up, down, xw), w_dtype)
-            with torch.cuda.device(xw.device.index):
-                rc = _lib.load().gptq_moe_shared_combine(xw.data_ptr(), _lib.ptr(gate_weight), ys.data_ptr(), out.data_ptr(), T, H, _lib.DTYPE_ENUM[w_dtype],
-                                                         _raw_stream(xw.device.index))
+            ys = _lib._dense16(mlp_forward(gate, up, down, xw), w_dtype)
+            rc = _on_device(xw.device.index, _lib.load().gptq_moe_shared_combine, xw.data_ptr(), _lib.ptr(gate_weight), ys.data_ptr(), out.data_ptr(), T, H,
+                            _lib.DTYPE_ENUM[w_dtype], _raw_stream(xw.device.index))
             if rc:
                 _lib.check(rc)
         experts.last_plan = dict(experts.last_plan or {}, shared="combine")
@@ -930,10 +908,8 @@ def moe_shared_forward(experts: QuantMoEExperts, shared_layers, gate_weight: "to
     buf = reserve_workspace(dev, need)
     exchange_tick(dev)
     sh.gate_w = _lib.ptr(gate_weight)
-    with torch.cuda.device(dev.index):
-        rc = _lib.load().gptq_moe_shared_decode_forward(ctypes.byref(experts._moe), ctypes.byref(sh), experts._decode_table.data_ptr(), xw.data_ptr(),
-                                                        idx.data_ptr(), w.data_ptr(), T, topk, out.data_ptr(), _lib.ptr(h_out), buf.data_ptr(), buf.numel(),
-                                                        _raw_stream(dev.index))
+    rc = _on_device(dev.index, _lib.load().gptq_moe_shared_decode_forward, ctypes.byref(experts._moe), ctypes.byref(sh), experts._decode_table.data_ptr(),
+                    xw.data_ptr(), idx.data_ptr(), w.data_ptr(), T, topk, out.data_ptr(), _lib.ptr(h_out), buf.data_ptr(), buf.numel(), _raw_stream(dev.index))
     if rc:
         _lib.check(rc)
     experts.last_plan = dict(experts.plan(T, topk), shared="decode")

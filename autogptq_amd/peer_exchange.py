@@ -237,7 +237,7 @@ class PeerExchange:
         M, nl = y_local.shape
         if out is None:
             out = torch.empty((M, self.N), dtype=self.dtype, device=self.device)
-        st = _lib.current_stream_handle(self.device)
+        st = _lib._raw_stream(_lib._device_index(self.device))
         _lib.check(_lib.load().gptq_peer_gather(ctypes.byref(self.pg), y_local.data_ptr(), out.data_ptr(), M, nl,
                                                 _lib.DTYPE_ENUM[self.dtype], self.max_spins, st))
         return out
@@ -247,7 +247,7 @@ class PeerExchange:
         decode-copy kernel -- M <= 4, a PLAIN (no act-order: the gather-through-perm form has no scatter epilogue) 3/4/8-bit layer with its copy."""
         if qlinear._layer is None:
             qlinear.post_init()
-        return (M <= 4 and getattr(qlinear, "_qweight_tiled", None) is not None and getattr(qlinear, "epilogue", "none") == "none"
+        return (M <= 4 and qlinear._qweight_tiled is not None and qlinear.epilogue == "none"
                 and not qlinear.act_order and qlinear.outfeatures * self.world == self.N and qlinear.scales.dtype == self.dtype)
 
     def forward_gather(self, qlinear, x2: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -257,8 +257,7 @@ class PeerExchange:
 
         if qlinear._layer is None:
             qlinear.post_init()
-        if not x2.is_contiguous() or x2.data_ptr() & 15:          # the C ABI takes a dense, 16-byte aligned x
-            x2 = x2.clone(memory_format=torch.contiguous_format)
+        x2 = _lib._dense16(x2)
         M = x2.shape[0]
         if out is None:
             out = torch.empty((M, self.N), dtype=self.dtype, device=self.device)
@@ -269,7 +268,7 @@ class PeerExchange:
             buf = reserve_workspace(self.device, need)
             ws_ptr, ws_bytes = buf.data_ptr(), buf.numel()
             exchange_tick(self.device)
-        st = _lib.current_stream_handle(self.device)
+        st = _lib._raw_stream(_lib._device_index(self.device))
         _lib.check(lib.gptq_forward_gather(ctypes.byref(qlinear._layer), x2.data_ptr(), out.data_ptr(), M, ctypes.byref(self.pg), self.max_spins,
                                            ws_ptr, ws_bytes, st))
         return out

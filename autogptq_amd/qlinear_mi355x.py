@@ -72,11 +72,27 @@ def reserve_workspace(device, nbytes: int, stream=None) -> torch.Tensor:
     return buf
 
 
-try:                                   # raw hipStream_t of the current stream without building a torch.cuda.Stream object
-    _raw_stream = torch._C._cuda_getCurrentRawStream
-except AttributeError:                 # pragma: no cover
-    def _raw_stream(idx):
-        return torch.cuda.current_stream(idx).cuda_stream
+_raw_stream = _lib._raw_stream         # (tools import it from here)
+
+
+def _on_device(idx: int, fn, *args):
+    """``fn(*args)`` with device ``idx`` current: the launch scope of every C call.  Called directly where ``idx`` already is the current device (the
+    usual case: no context manager on the call path)."""
+    if idx == torch.cuda.current_device():
+        return fn(*args)
+    with torch.cuda.device(idx):
+        return fn(*args)
+
+
+def _cached_need(cache: dict, M: int, tuning, query):
+    """A per-row-count answer of a host-only query (workspace bytes, "does the plan read rows"): cached in ``cache[M]`` for calls without a tuning; a call with
+    a tuning asks every time and neither reads nor writes the cache."""
+    if tuning is not None:
+        return query()
+    need = cache.get(M)
+    if need is None:
+        need = cache[M] = query()
+    return need
 
 
 _ROWS_SCRATCH: dict = {}    # device index -> uint8 tensor: packed rows rebuilt from a decode copy (layers whose checkpoint layout was released)
@@ -211,19 +227,40 @@ class QuantLinear(nn.Module):
         else:
             self.bias = None
 
-        # derived, non-persistent state (never part of state_dict; checkpoint tensors stay intact)
-        self._layer = None            # ctypes GptqLayer
-        self._keepalive = ()          # tensors the raw pointers in _layer refer to
-        self._qweight_tiled = self._qconst_tiled = None    # the decode copy (post_init), never part of state_dict
+        self.act_order = None         # resolved by post_init (from g_idx; kept across _invalidate)
         self._released = False        # post_init(release_checkpoint_layout=True): qweight lives in pinned host memory, rows are rebuilt on demand
-        self._ws_need = {}            # M -> workspace bytes
-        self._a8_hold = False         # set by the LoRA wrappers around this layer: the int8-activation path stays off
-        self._grad_flags = 0          # post_init(grad_on_copy=True): GPTQ_GRAD_ON_COPY, the flags of gptq_grad_input_ex
-        self._a8_rows = 0             # post_init(act_int8=True) on a layer the int8-activation path takes: its first row count; 0 = off
-        self._ws0_mask = 0            # bit M set: M rows (1..63) are known to need no workspace -- what the C++ fast path (cext/fastfwd.cpp) serves; 0 = never
-        self.act_order = None         # resolved by post_init
+        self._a8_hold = False         # set by the LoRA / tensor-parallel wrappers around this layer: the int8-activation path stays off
+        self._reset_derived()
 
     # ------------------------------------------------------------------ state handling
+    def _reset_derived(self):
+        """Every piece of derived, non-persistent state (never part of state_dict; checkpoint tensors stay intact) at its "not initialised" value: what
+        post_init and the call path fill in.  __init__ and _invalidate both come here, so state added here cannot survive a .to().
+        Two attributes are declared in __init__ and deliberately NOT reset: ``_released`` (post_init reads it to bring a released layer's rows back to the
+        device first) and ``_a8_hold`` (owned by the wrappers around this layer)."""
+        self._layer = None            # ctypes GptqLayer ...
+        self._layer_ref = None        # ... ctypes.byref of it ...
+        self._layer_addr = 0          # ... and its address (the trampolines take integers)
+        self._layer_plain = None      # (_layer it was copied from, copy with EPI_NONE): _plain_product
+        self._parts = None            # fused-QKV g_idx: the n column blocks as internal layers (not registered submodules)
+        self._keepalive = ()          # tensors the raw pointers in _layer refer to
+        self._qweight_tiled = self._qconst_tiled = None    # the decode copy (post_init), never part of state_dict
+        self._qweight_rows_bytes = 0  # a released layer: bytes of the packed rows a rebuild writes
+        self._perm = None             # act-order: the x permutation
+        self._fwd = None              # lib.gptq_forward_ex
+        self._dev = None              # torch.device("cuda", _dev_index)
+        self._dev_index = -1
+        self._w_dtype = None          # scales.dtype
+        self._n_out = 0               # out_width
+        self._dt_code = -1            # the C++ fast path's dtype code
+        self._ws_need = {}            # M -> workspace bytes
+        self._ws0_mask = 0            # bit M set: M rows (1..63) are known to need no workspace -- what the C++ fast path (cext/fastfwd.cpp) serves; 0 = never
+        self._rows_need = {}          # M -> a released layer's plan for M rows reads packed rows
+        self._a8_rows = 0             # post_init(act_int8=True) on a layer the int8-activation path takes: its first row count; 0 = off
+        self._a8_need = {}            # M -> workspace bytes of the int8-activation path
+        self._grad_flags = 0          # post_init(grad_on_copy=True): GPTQ_GRAD_ON_COPY, the flags of gptq_grad_input_ex
+        self._grad_plans = {}         # M -> describe_grad_plan's line
+
     def _apply(self, fn, *args, **kwargs):
         out = super()._apply(fn, *args, **kwargs)
         self._invalidate()
@@ -236,14 +273,7 @@ class QuantLinear(nn.Module):
             lid = id(self._layer)
             for key in [k for k in _MULTI if lid in k]:
                 del _MULTI[key]
-        self._layer = None
-        self._keepalive = ()
-        self._qweight_tiled = self._qconst_tiled = None
-        self._ws_need = {}
-        self._ws0_mask = 0
-        self._a8_rows = 0
-        self._rows_need = {}
-        object.__setattr__(self, "_parts", None)
+        self._reset_derived()
 
     def _load_from_state_dict(self, *args, **kwargs):
         super()._load_from_state_dict(*args, **kwargs)
@@ -270,7 +300,7 @@ class QuantLinear(nn.Module):
         """Snapshot device pointers and, for act-order layers, derive the group-sorted copy of
         qweight plus the x permutation (side buffers; qweight itself is never modified -- the
         reference's exllama backends overwrite it in place, q4_matrix.cu:160)."""
-        if self.qweight.device.type != "cuda" and self.scales.device.type == "cuda" and getattr(self, "_released", False):
+        if self.qweight.device.type != "cuda" and self.scales.device.type == "cuda" and self._released:
             self.qweight = self.qweight.to(self.scales.device)      # a released layer initialised again: the rows come back first
         dev = self.qweight.device
         if dev.type != "cuda":
@@ -312,7 +342,7 @@ class QuantLinear(nn.Module):
                 with torch.cuda.device(dev):
                     _lib.check(lib.gptq_resequence_qweight(self.qweight.data_ptr(), perm.data_ptr(), self.infeatures,
                                                            self.outfeatures, self.bits, qweight_seq.data_ptr(),
-                                                           _lib.current_stream_handle(dev)))
+                                                           _raw_stream(_lib._device_index(dev))))
         L = _lib.GptqLayer()
         L.qweight = self.qweight.data_ptr()
         L.qzeros = self.qzeros.data_ptr()
@@ -339,7 +369,7 @@ class QuantLinear(nn.Module):
                 qweight_tiled = torch.empty(tb.value, dtype=torch.uint8, device=dev)
                 qconst_tiled = torch.empty(cb.value, dtype=torch.uint8, device=dev)
                 with torch.cuda.device(dev):
-                    _lib.check(lib.gptq_prepack_decode(ctypes.byref(L), qweight_tiled.data_ptr(), qconst_tiled.data_ptr(), _lib.current_stream_handle(dev)))
+                    _lib.check(lib.gptq_prepack_decode(ctypes.byref(L), qweight_tiled.data_ptr(), qconst_tiled.data_ptr(), _raw_stream(_lib._device_index(dev))))
                 L.qweight_tiled, L.qconst_tiled, L.tiled_cols = qweight_tiled.data_ptr(), qconst_tiled.data_ptr(), _lib.STRIP_COLS
         if low_bit_rows is None:
             low_bit_rows = self.LOW_BIT_ROWS
@@ -349,8 +379,7 @@ class QuantLinear(nn.Module):
         self._layer_ref = ctypes.byref(L)
         self._layer_addr = ctypes.addressof(L)
         self._fwd = lib.gptq_forward_ex
-        self._dev = dev
-        self._dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
+        self._dev_index = _lib._device_index(dev)
         self._dev = torch.device("cuda", self._dev_index)
         self._w_dtype = self.scales.dtype
         self._n_out = self.out_width
@@ -399,20 +428,21 @@ class QuantLinear(nn.Module):
     def _rebuild_rows(self, M: int, tuning=None) -> None:
         """Released layers: if the kernel planned for M rows reads packed ROWS, rebuild them from the decode copy into the device's shared scratch (whose address
         the layer struct already carries) -- in stream order right in front of the call.  The answer per row count is cached."""
-        need = self._rows_need.get(M) if tuning is None else None
-        if need is None:
-            d = _lib.describe_plan(self._layer, M, tuning)
-            need = not (d.get("kernel") in ("strips", "rows", "panel", "wide_sk", "wide_copy"))          # the kernels that read the decode copy
-            if tuning is None:
-                self._rows_need[M] = need
-        if need:
-            dev = self._dev
-            buf = reserve_rows_scratch(dev, self._qweight_rows_bytes)
-            if buf.data_ptr() != self._layer.qweight:
-                self._layer.qweight = buf.data_ptr()
-            with torch.cuda.device(dev):
-                _lib.check(_lib.load().gptq_unprepack_decode(self._qweight_tiled.data_ptr(), self.infeatures, self.outfeatures, self.bits, buf.data_ptr(),
-                                                             _lib.current_stream_handle(dev)))
+        def reads_rows():
+            kernel = _lib.describe_plan(self._layer, M, tuning).get("kernel")
+            return kernel not in ("strips", "rows", "panel", "wide_sk", "wide_copy")          # the kernels that read the decode copy
+
+        if _cached_need(self._rows_need, M, tuning, reads_rows):
+            self._rebuild_rows_now()
+
+    def _rebuild_rows_now(self) -> None:
+        """Released layers: the packed rows back into the device's shared scratch, in stream order, whatever kernel comes next.  The ONE place that launches
+        gptq_unprepack_decode for a released layer and points the layer struct at the scratch -- on the stream every kernel call reads (_raw_stream)."""
+        buf = reserve_rows_scratch(self._dev, self._qweight_rows_bytes)
+        self._layer.qweight = buf.data_ptr()
+        idx = self._dev_index
+        _lib.check(_on_device(idx, _lib.load().gptq_unprepack_decode, self._qweight_tiled.data_ptr(), self.infeatures, self.outfeatures, self.bits,
+                              buf.data_ptr(), _raw_stream(idx)))
 
     def _post_init_fused_g_idx(self, temp_dq, tiled, grad_on_copy=None):
         """``len(g_idx) == n * infeatures``: the reference's fused q/k/v module of act-order projections (fused_llama_attn.py:186 concatenates the three g_idx;
@@ -438,21 +468,30 @@ class QuantLinear(nn.Module):
                 p.bias = self.bias[i * K:(i + 1) * K].contiguous()
             p.post_init(temp_dq, tiled, grad_on_copy=grad_on_copy)
             parts.append(p)
-        object.__setattr__(self, "_parts", parts)       # not registered submodules: derived state, never part of state_dict
+        self._parts = parts                             # a plain list, so not registered submodules: derived state, never part of state_dict
         self.act_order = any(p.act_order for p in parts)
         return self
 
     # ------------------------------------------------------------------ forward
+    @staticmethod
+    def _need_gpu_tensor(x: torch.Tensor) -> None:
+        if x.device.type != "cuda":
+            raise RuntimeError("mi355x QuantLinear.forward needs a ROCm GPU tensor "
+                               f"(got {x.device}); there is no CPU path in this backend.")
+
+    def _ensure_init(self, x: "torch.Tensor | None" = None) -> None:
+        """post_init() on first use: a layer that has neither its struct nor its fused-QKV parts.  ``x``: the call's input, which must be a ROCm tensor then."""
+        if self._layer is None and self._parts is None:
+            if x is not None:
+                self._need_gpu_tensor(x)
+            self.post_init()
+
     def _workspace(self, M: int, device, tuning=None):
-        need = self._ws_need.get(M) if tuning is None else None
-        if need is None:
-            need = int(_lib.load().gptq_workspace_bytes_ex(ctypes.byref(self._layer), M,
-                                                            ctypes.byref(tuning) if tuning is not None else None))
-            if tuning is None:
-                self._ws_need[M] = need
-                if need == 0 and 0 < M < 64 and _lib.fwd is not None and not (self._a8_rows and M >= self._a8_rows):      # (the C++ fast path never serves a row count the int8 path owns)
-                    self._ws0_mask |= 1 << M
+        need = _cached_need(self._ws_need, M, tuning, lambda: int(_lib.load().gptq_workspace_bytes_ex(
+            self._layer_ref, M, ctypes.byref(tuning) if tuning is not None else None)))
         if need == 0:
+            if tuning is None and 0 < M < 64 and _lib.fwd is not None and not (self._a8_rows and M >= self._a8_rows):      # (the C++ fast path never serves a row count the int8 path owns)
+                self._ws0_mask |= 1 << M
             return None, 0
         buf = reserve_workspace(device, need)
         exchange_tick(device)
@@ -474,66 +513,42 @@ class QuantLinear(nn.Module):
         if x.requires_grad and torch.is_grad_enabled():       # an autograd node (the C++ fast path above declines these calls)
             return self._forward_grad(x, tuning)
         if self._layer is None:
-            if getattr(self, "_parts", None) is None:
-                if x.device.type != "cuda":
-                    raise RuntimeError("mi355x QuantLinear.forward needs a ROCm GPU tensor "
-                                       f"(got {x.device}); there is no CPU path in this backend.")
-                self.post_init()
-            if getattr(self, "_parts", None) is not None:      # fused-QKV g_idx: n column blocks with their own activation orders
+            self._ensure_init(x)
+            if self._parts is not None:      # fused-QKV g_idx: n column blocks with their own activation orders
                 return torch.cat(forward_multi(self._parts, x, tuning), dim=-1)
         dev = self._dev
         if x.device != dev:
-            if x.device.type != "cuda":
-                raise RuntimeError("mi355x QuantLinear.forward needs a ROCm GPU tensor "
-                                   f"(got {x.device}); there is no CPU path in this backend.")
+            self._need_gpu_tensor(x)
             raise RuntimeError(f"mi355x QuantLinear.forward: input is on {x.device}, the layer on {dev}")
         K = self.infeatures
         if x.shape[-1] != K:
             raise RuntimeError(f"input has {x.shape[-1]} features, layer expects {K}")
         w_dtype = self._w_dtype
         x_dtype = x.dtype
-        x2 = x
         if x_dtype != w_dtype:
             _warn_once(f"mi355x QuantLinear: activation dtype {x_dtype} != weight dtype {w_dtype}; casting the "
                        f"activation to {w_dtype} (the result is cast back).")
-            x2 = x2.to(w_dtype)
-        if x2.dim() != 2:
-            x2 = x2.reshape(-1, K)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
-        if x2.data_ptr() & 15:            # a contiguous view at an odd element offset: the C ABI takes 16-byte aligned x (gptq_mi355x.h)
-            x2 = x2.clone()
-        M = x2.shape[0]
+        x2, M = _lib._rows16(x, K, w_dtype)
         n_out = self._n_out
         out = torch.empty((M, n_out), dtype=w_dtype, device=dev)
         a8 = self._a8_rows
         use_a8 = a8 != 0 and M >= a8 and act_int8 and tuning is None      # opt-in W4A8 (callers that keep the 16-bit kernels pass act_int8=False; a8 >= 1, so M != 0)
         if use_a8:
             self._forward_a8(x2, out, M)                        # quantise + i8 GEMM, two launches
-        elif M != 0 and self._released:
-            self._rebuild_rows(M, tuning)
-        if M != 0 and not use_a8:
-            need = self._ws_need.get(M) if tuning is None else None
-            if need == 0:
+        elif M != 0:
+            if self._released:
+                self._rebuild_rows(M, tuning)
+            if tuning is None and self._ws_need.get(M) == 0:      # known to need none: nothing to reserve, and the fast-path mask is settled
                 ws_ptr, ws_bytes = None, 0
             else:
                 ws_ptr, ws_bytes = self._workspace(M, dev, tuning)
             idx = self._dev_index
             fast = _lib.fast
             if fast is not None:           # METH_FASTCALL trampoline: integers only
-                taddr = ctypes.addressof(tuning) if tuning is not None else 0
-                if idx != torch.cuda.current_device():
-                    with torch.cuda.device(idx):
-                        rc = fast.forward(self._layer_addr, x2.data_ptr(), out.data_ptr(), M, ws_ptr or 0, ws_bytes, _raw_stream(idx), taddr)
-                else:
-                    rc = fast.forward(self._layer_addr, x2.data_ptr(), out.data_ptr(), M, ws_ptr or 0, ws_bytes, _raw_stream(idx), taddr)
+                fn, layer, ws_ptr, tn = fast.forward, self._layer_addr, ws_ptr or 0, ctypes.addressof(tuning) if tuning is not None else 0
             else:
-                tref = ctypes.byref(tuning) if tuning is not None else None
-                if idx != torch.cuda.current_device():
-                    with torch.cuda.device(idx):
-                        rc = self._fwd(self._layer_ref, x2.data_ptr(), out.data_ptr(), M, ws_ptr, ws_bytes, _raw_stream(idx), tref)
-                else:
-                    rc = self._fwd(self._layer_ref, x2.data_ptr(), out.data_ptr(), M, ws_ptr, ws_bytes, _raw_stream(idx), tref)
+                fn, layer, tn = self._fwd, self._layer_ref, ctypes.byref(tuning) if tuning is not None else None
+            rc = _on_device(idx, fn, layer, x2.data_ptr(), out.data_ptr(), M, ws_ptr, ws_bytes, _raw_stream(idx), tn)
             if rc:
                 _lib.check(rc)
         if x_dtype != w_dtype:
@@ -556,8 +571,7 @@ class QuantLinear(nn.Module):
     def _forward_a8(self, x2: torch.Tensor, out: torch.Tensor, M: int) -> None:
         ws_ptr, ws_bytes = self._a8_workspace(M)
         idx = self._dev_index
-        with torch.cuda.device(idx):
-            rc = _lib.load().gptq_forward_a8(self._layer_ref, x2.data_ptr(), out.data_ptr(), M, ws_ptr, ws_bytes, _raw_stream(idx))
+        rc = _on_device(idx, _lib.load().gptq_forward_a8, self._layer_ref, x2.data_ptr(), out.data_ptr(), M, ws_ptr, ws_bytes, _raw_stream(idx))
         if rc:
             _lib.check(rc)
 
@@ -565,18 +579,13 @@ class QuantLinear(nn.Module):
         """``(xq, sx)`` of the int8-activation path for ``x`` [.., infeatures]: xq int8 [M, infeatures] in NATURAL k order, sx fp32 [M], with
         ``sx = amax / 127`` and ``xq = rint(x / sx)`` per row in IEEE fp32 (gptq_act_quant; the kernel's own buffer is in the k order of the GEMM's operands
         and, for act-order layers, behind ``perm`` -- both are undone here).  For tests and for users who want to see the rounding."""
-        if self._layer is None:
-            self.post_init()
-        K, dev = self.infeatures, self._dev
-        x2 = x.reshape(-1, K).to(self._w_dtype).contiguous()
-        if x2.data_ptr() & 15:
-            x2 = x2.clone()
-        M = x2.shape[0]
+        self._ensure_init()
+        K, dev, idx = self.infeatures, self._dev, self._dev_index
+        x2, M = _lib._rows16(x, K, self._w_dtype)
         lib = _lib.load()
         need = int(lib.gptq_act_int8_workspace_bytes(self._layer_ref, M))
         ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(self._dev_index):
-            _lib.check(lib.gptq_act_quant(self._layer_ref, x2.data_ptr(), M, ws.data_ptr(), need, _raw_stream(self._dev_index)))
+        _lib.check(_on_device(idx, lib.gptq_act_quant, self._layer_ref, x2.data_ptr(), M, ws.data_ptr(), need, _raw_stream(idx)))
         return unpack_act_int8_workspace(ws, M, K, self.group_size, self._perm)
 
     # ------------------------------------------------------------------ gradients
@@ -584,12 +593,8 @@ class QuantLinear(nn.Module):
         """forward() when grad mode is on and x requires grad: one _GradInput node (dX = dY . W^T through gptq_grad_input; the buffers get no gradient).
         The dtype casts either side are ordinary autograd ops, so x.grad comes back in x.dtype.  A 'silu_mul' / 'gelu_tanh_mul' layer is composed from
         differentiable pieces: its plain [gate | up] product, then act(g) * u; a 'relu' / 'gelu' / 'gelu_tanh' layer from its plain product, then act(y)."""
-        if self._layer is None and getattr(self, "_parts", None) is None:
-            if x.device.type != "cuda":
-                raise RuntimeError("mi355x QuantLinear.forward needs a ROCm GPU tensor "
-                                   f"(got {x.device}); there is no CPU path in this backend.")
-            self.post_init()
-        if getattr(self, "_parts", None) is not None:          # fused-QKV g_idx: forward_multi records one node for the n column blocks
+        self._ensure_init(x)
+        if self._parts is not None:          # fused-QKV g_idx: forward_multi records one node for the n column blocks
             return torch.cat(forward_multi(self._parts, x, tuning), dim=-1)
         w_dtype = self._w_dtype
         xw = x.to(w_dtype) if x.dtype != w_dtype else x
@@ -605,7 +610,7 @@ class QuantLinear(nn.Module):
 
     def _plain_product(self, x: torch.Tensor, tuning=None) -> torch.Tensor:
         """x @ W + b of a layer with an epilogue BEFORE that epilogue ([.., outfeatures]): gptq_forward_ex on a copy of the layer struct with EPI_NONE."""
-        L = getattr(self, "_layer_plain", None)
+        L = self._layer_plain
         if L is None or L[0] is not self._layer:
             c = _lib.GptqLayer()
             ctypes.pointer(c)[0] = self._layer
@@ -616,72 +621,52 @@ class QuantLinear(nn.Module):
         if self._released:
             self._rebuild_rows_now()
         L.qweight = self._layer.qweight
-        x2 = x.reshape(-1, K).contiguous()
-        if x2.data_ptr() & 15:
-            x2 = x2.clone()
-        M = x2.shape[0]
+        x2, M = _lib._rows16(x, K, self._w_dtype)      # (the callers pass the layer dtype: no cast)
         out = torch.empty((M, N), dtype=self._w_dtype, device=self._dev)
         if M:
             lib = _lib.load()
+            idx = self._dev_index
             tref = ctypes.byref(tuning) if tuning is not None else None
             need = int(lib.gptq_workspace_bytes_ex(ctypes.byref(L), M, tref))
             ws = reserve_workspace(self._dev, need) if need else None
             if ws is not None:
                 exchange_tick(self._dev)
-            with torch.cuda.device(self._dev_index):
-                _lib.check(lib.gptq_forward_ex(ctypes.byref(L), x2.data_ptr(), out.data_ptr(), M, _lib.ptr(ws), ws.numel() if ws is not None else 0,
-                                               _raw_stream(self._dev_index), tref))
+            _lib.check(_on_device(idx, lib.gptq_forward_ex, ctypes.byref(L), x2.data_ptr(), out.data_ptr(), M, _lib.ptr(ws),
+                                  ws.numel() if ws is not None else 0, _raw_stream(idx), tref))
         return out.reshape(x.shape[:-1] + (N,))
-
-    def _rebuild_rows_now(self) -> None:
-        """Released layers: the packed rows back into the device's shared scratch (gptq_unprepack_decode), in stream order, whatever kernel comes next."""
-        buf = reserve_rows_scratch(self._dev, self._qweight_rows_bytes)
-        self._layer.qweight = buf.data_ptr()
-        with torch.cuda.device(self._dev_index):
-            _lib.check(_lib.load().gptq_unprepack_decode(self._qweight_tiled.data_ptr(), self.infeatures, self.outfeatures, self.bits, buf.data_ptr(),
-                                                         _raw_stream(self._dev_index)))
 
     def grad_input(self, dy: torch.Tensor, dx: "torch.Tensor | None" = None) -> torch.Tensor:
         """dX = dY . W^T (W = dequantize(), exactly) through gptq_grad_input; ``dx`` given: dX += dY . W^T in place (fp32 sum, one rounding).
         dy: [.., outfeatures] of the product BEFORE any epilogue, in the layer dtype.  Returns dX as [M, infeatures]."""
-        if self._layer is None and getattr(self, "_parts", None) is None:
-            self.post_init()
-        if getattr(self, "_parts", None) is not None:
+        self._ensure_init()
+        if self._parts is not None:
             K = self.infeatures
             dy2 = dy.reshape(-1, dy.shape[-1])
             for i, p in enumerate(self._parts):
                 dx = p.grad_input(dy2[:, i * K:(i + 1) * K], dx)
             return dx
-        K, N, dev = self.infeatures, self.outfeatures, self._dev
-        dy2 = dy.reshape(-1, N)
-        if dy2.dtype != self._w_dtype:
-            dy2 = dy2.to(self._w_dtype)
-        if not dy2.is_contiguous() or dy2.data_ptr() % 16:
-            dy2 = dy2.clone(memory_format=torch.contiguous_format)
-        M = dy2.shape[0]
-        acc = dx is not None
+        K, N, idx = self.infeatures, self.outfeatures, self._dev_index
+        dy2, M = _lib._rows16(dy, N, self._w_dtype)
+        acc = 1 if dx is not None else 0
         if dx is None:
-            dx = torch.empty((M, K), dtype=self._w_dtype, device=dev)
+            dx = torch.empty((M, K), dtype=self._w_dtype, device=self._dev)
         if M:
+            flags = self._grad_flags        # opt-in: the kernel on the decode copy where the plan takes the layer (a released one then needs no rows)
+            if self._released and not (flags and self.describe_grad_plan(M).startswith("kernel=grad_copy")):
+                self._rebuild_rows_now()    # the checkpoint rows, into the shared scratch right in front of the kernel (stream order)
             lib = _lib.load()
-            with torch.cuda.device(self._dev_index):
-                if self._grad_flags:        # opt-in: the kernel on the decode copy where the plan takes the layer (a released one then needs no rows)
-                    if self._released and not self.describe_grad_plan(M).startswith("kernel=grad_copy"):
-                        self._rebuild_rows_now()
-                    _lib.check(lib.gptq_grad_input_ex(self._layer_ref, dy2.data_ptr(), dx.data_ptr(), M, 1 if acc else 0, self._grad_flags,
-                                                      _raw_stream(self._dev_index)))
-                    return dx
-                if self._released:          # the checkpoint rows are rebuilt into the shared scratch right in front of the kernel (stream order)
-                    self._rebuild_rows_now()
-                _lib.check(lib.gptq_grad_input(self._layer_ref, dy2.data_ptr(), dx.data_ptr(), M, 1 if acc else 0, _raw_stream(self._dev_index)))
+            if flags:
+                rc = _on_device(idx, lib.gptq_grad_input_ex, self._layer_ref, dy2.data_ptr(), dx.data_ptr(), M, acc, flags, _raw_stream(idx))
+            else:                           # flags off: the plain entry point, as ever
+                rc = _on_device(idx, lib.gptq_grad_input, self._layer_ref, dy2.data_ptr(), dx.data_ptr(), M, acc, _raw_stream(idx))
+            _lib.check(rc)
         return dx
 
     def describe_grad_plan(self, M: int) -> str:
         """The kernel grad_input() launches for M rows of dY (gptq_describe_grad_input_plan; host-only, cached per M): "kernel=grad_copy bm=.. stages=.. gm=..
         act=.." or "kernel=grad_rows reason=..".  A fused-QKV module answers for its first column block (the blocks share every property the plan reads)."""
-        if self._layer is None and getattr(self, "_parts", None) is None:
-            self.post_init()
-        if getattr(self, "_parts", None) is not None:
+        self._ensure_init()
+        if self._parts is not None:
             return self._parts[0].describe_grad_plan(M)
         d = self._grad_plans.get(M)
         if d is None:
@@ -691,23 +676,14 @@ class QuantLinear(nn.Module):
     # ------------------------------------------------------------------ dequant / unpack helpers
     def dequantize(self) -> torch.Tensor:
         """[K, N] dequantised weight in the scales dtype (bit-exact w.r.t. the reference's `weights`)."""
-        if self._layer is None and getattr(self, "_parts", None) is None:
-            self.post_init()
-        if getattr(self, "_parts", None) is not None:
+        self._ensure_init()
+        if self._parts is not None:
             return torch.cat([p.dequantize() for p in self._parts], dim=1)
-        dev = self.scales.device
         if self._released:
-            self._rows_need.pop(-1, None)
-            self._rows_need[-1] = True
-            buf = reserve_rows_scratch(dev, self._qweight_rows_bytes)
-            self._layer.qweight = buf.data_ptr()
-            with torch.cuda.device(dev):
-                _lib.check(_lib.load().gptq_unprepack_decode(self._qweight_tiled.data_ptr(), self.infeatures, self.outfeatures, self.bits, buf.data_ptr(),
-                                                             _lib.current_stream_handle(dev)))
-        W = torch.empty((self.infeatures, self.outfeatures), dtype=self.scales.dtype, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().gptq_dequant(ctypes.byref(self._layer), W.data_ptr(),
-                                                _lib.current_stream_handle(dev)))
+            self._rebuild_rows_now()
+        idx = self._dev_index
+        W = torch.empty((self.infeatures, self.outfeatures), dtype=self._w_dtype, device=self._dev)
+        _lib.check(_on_device(idx, _lib.load().gptq_dequant, self._layer_ref, W.data_ptr(), _raw_stream(idx)))
         return W
 
     # ------------------------------------------------------------------ pack
@@ -770,7 +746,7 @@ class QuantLinear(nn.Module):
         qweight = torch.empty((K // 32 * bits, N), dtype=torch.int32, device=dev)
         qzeros = torch.empty((sd.shape[0], N // 32 * bits), dtype=torch.int32, device=dev)
         scales_out = torch.empty(sd.shape, dtype=W.dtype, device=dev)
-        st = _lib.current_stream_handle(dev)
+        st = _raw_stream(dev.index)
         _lib.check(lib.gptq_pack_weights(Wd.data_ptr(), sd.data_ptr(), zd.data_ptr(), gd.data_ptr(), K, N, bits,
                                          self.group_size, _lib.DTYPE_ENUM[W.dtype], _lib.DTYPE_ENUM[sd.dtype],
                                          qweight.data_ptr(), scales_out.data_ptr(), st))
@@ -905,7 +881,7 @@ def forward_multi(layers, x: torch.Tensor, tuning: "_lib.GptqTuning | None" = No
         return [o.to(x.dtype) for o in outs] if x.dtype != w_dtype else list(outs)
     a = layers[0]
     n = len(layers)
-    released = any(getattr(l, "_released", False) for l in layers)
+    released = any(l._released for l in layers)
     if released and tuning is not None:
         # a forced kernel family may read the packed ROWS, which released layers only have in the one shared scratch (whichever layer was rebuilt last):
         # the grouped entry points refuse the override instead of returning another layer's weights (single calls rebuild the rows: QuantLinear.forward)
@@ -914,11 +890,10 @@ def forward_multi(layers, x: torch.Tensor, tuning: "_lib.GptqTuning | None" = No
         # layers whose checkpoint rows left the HBM share ONE rows scratch: beyond the decode rows (which run from the copies) they are called one by one
         return [l(x, tuning, act_int8=False) for l in layers]      # (a grouped call keeps the 16-bit kernels)
     key = tuple([id(l._layer) for l in layers]) if a._layer is not None else None
-    ent = _MULTI.get(key) if key is not None else None
-    if ent is None:
+    g = _MULTI.get(key) if key is not None else None
+    if g is None:
         for l in layers:
-            if l._layer is None:
-                l.post_init()
+            l._ensure_init()
         if any(l.infeatures != a.infeatures for l in layers):
             raise RuntimeError("forward_multi: every layer must take the input's feature count")
         if any(l._w_dtype != a._w_dtype for l in layers):
@@ -928,63 +903,46 @@ def forward_multi(layers, x: torch.Tensor, tuning: "_lib.GptqTuning | None" = No
         share_act_order(layers)
         key = tuple([id(l._layer) for l in layers])
         arr = (ctypes.POINTER(_lib.GptqLayer) * n)(*[ctypes.pointer(l._layer) for l in layers])
-        optr_arr = (ctypes.c_void_p * n)()
-        ent = _MULTI[key] = (arr, {}, [l._layer for l in layers], optr_arr, ctypes.addressof(arr), ctypes.addressof(optr_arr),
-                             a._dev, a.infeatures, a._w_dtype, tuple(l._n_out for l in layers), a._dev_index, sum(l._n_out for l in layers))
-    arr, need_by_m, _, optrs, arr_addr, optr_addr, dev, K, w_dtype, n_outs, idx = ent[:11]
-    if tuning is None:
-        mask = need_by_m.get(-1)           # row counts of this group known to need no workspace: the C++ fast path (cext/fastfwd.cpp) serves them
-        if mask:
-            r = _lib.fwd.forward_multi(arr_addr, n, x, K, n_outs, a._dt_code, idx, optr_addr, mask)
-            if r is not None:
-                if r.__class__ is int:
-                    _lib.check(r)
-                return list(r)
+        optrs = (ctypes.c_void_p * n)()
+        g = _MULTI[key] = _Group(arr, optrs, layers)
+    K, n_outs, idx = g.K, g.n_outs, g.idx
+    mask = g.ws0_mask
+    if mask and tuning is None:
+        r = _lib.fwd.forward_multi(g.arr_addr, n, x, K, n_outs, a._dt_code, idx, g.optr_addr, mask)
+        if r is not None:
+            if r.__class__ is int:
+                _lib.check(r)
+            return list(r)
+    dev, w_dtype = g.dev, g.w_dtype
     if x.device != dev:
         raise RuntimeError(f"mi355x forward_multi: input is on {x.device}, the layers on {dev}")
     if x.shape[-1] != K:
         raise RuntimeError("forward_multi: every layer must take the input's feature count")
     x_dtype = x.dtype
-    x2 = x.to(w_dtype) if x_dtype != w_dtype else x
-    if x2.dim() != 2:
-        x2 = x2.reshape(-1, K)
-    if not x2.is_contiguous():
-        x2 = x2.contiguous()
-    if x2.data_ptr() & 15:                # a contiguous view at an odd element offset: the C ABI takes 16-byte aligned x
-        x2 = x2.clone()
-    M = x2.shape[0]
+    x2, M = _lib._rows16(x, K, w_dtype)
     if M == 1:      # one decode row: ONE allocation, the outputs are its column slices (contiguous for a single row) -- torch.empty is 1.9 us of a ~10 us call
-        outs = list(torch.empty((1, ent[11]), dtype=w_dtype, device=dev).split(n_outs, dim=1))
+        outs = list(torch.empty((1, g.n_out_sum), dtype=w_dtype, device=dev).split(n_outs, dim=1))
     else:
         outs = [torch.empty((M, no), dtype=w_dtype, device=dev) for no in n_outs]
     if M:
-        need = need_by_m.get(M) if tuning is None else None
-        if need is None:
-            tref = ctypes.byref(tuning) if tuning is not None else None
-            need = int(_lib.load().gptq_workspace_bytes_multi_ex(arr, n, M, tref))
-            if tuning is None:
-                need_by_m[M] = need
-                if need == 0 and 0 < M < 64 and _lib.fwd is not None:
-                    need_by_m[-1] = need_by_m.get(-1, 0) | (1 << M)
+        need = _cached_need(g.need_by_m, M, tuning, lambda: int(_lib.load().gptq_workspace_bytes_multi_ex(
+            g.arr, n, M, ctypes.byref(tuning) if tuning is not None else None)))
+        if need == 0 and tuning is None and 0 < M < 64 and _lib.fwd is not None:
+            g.ws0_mask |= 1 << M
         ws_ptr, ws_bytes = 0, 0
         if need:
             buf = reserve_workspace(dev, need)
             ws_ptr, ws_bytes = buf.data_ptr(), buf.numel()
             exchange_tick(dev)
+        optrs = g.optrs
         for i in range(n):
             optrs[i] = outs[i].data_ptr()
         fast = _lib.fast
-        def launch():
-            if fast is not None:
-                return fast.forward_multi(arr_addr, n, x2.data_ptr(), optr_addr, M, ws_ptr, ws_bytes, _raw_stream(idx),
-                                          ctypes.addressof(tuning) if tuning is not None else 0)
-            return _lib.load().gptq_forward_multi_ex(arr, n, x2.data_ptr(), optrs, M, ws_ptr or None, ws_bytes, _raw_stream(idx),
-                                                     ctypes.byref(tuning) if tuning is not None else None)
-        if idx != torch.cuda.current_device():              # rare: the layers' device is not the current one
-            with torch.cuda.device(idx):
-                rc = launch()
+        if fast is not None:               # METH_FASTCALL trampoline: integers only
+            fn, arr, optrs, tn = fast.forward_multi, g.arr_addr, g.optr_addr, ctypes.addressof(tuning) if tuning is not None else 0
         else:
-            rc = launch()
+            fn, arr, ws_ptr, tn = _lib.load().gptq_forward_multi_ex, g.arr, ws_ptr or None, ctypes.byref(tuning) if tuning is not None else None
+        rc = _on_device(idx, fn, arr, n, x2.data_ptr(), optrs, M, ws_ptr, ws_bytes, _raw_stream(idx), tn)
         if rc:
             _lib.check(rc)
     if x_dtype != w_dtype:
@@ -992,6 +950,22 @@ def forward_multi(layers, x: torch.Tensor, tuning: "_lib.GptqTuning | None" = No
     if x.dim() != 2:
         outs = [o.reshape(x.shape[:-1] + (o.shape[-1],)) for o in outs]
     return outs
+
+
+class _Group:
+    """What forward_multi resolves once per group of layers (kept in _MULTI under the ids of the layers' C structs).  Slots: the fields are read on every call."""
+    __slots__ = ("arr", "arr_addr", "optrs", "optr_addr", "structs", "need_by_m", "ws0_mask", "dev", "idx", "K", "w_dtype", "n_outs", "n_out_sum")
+
+    def __init__(self, arr, optrs, layers):
+        a = layers[0]
+        self.arr, self.arr_addr = arr, ctypes.addressof(arr)              # POINTER(GptqLayer) * n ...
+        self.structs = [l._layer for l in layers]                         # ... and the structs it points at (kept alive)
+        self.optrs, self.optr_addr = optrs, ctypes.addressof(optrs)       # c_void_p * n: the output pointers of a call
+        self.need_by_m = {}                                               # M -> workspace bytes
+        self.ws0_mask = 0                  # bit M set: M rows need no workspace -- what the C++ fast path (cext/fastfwd.cpp) serves
+        self.dev, self.idx, self.K, self.w_dtype = a._dev, a._dev_index, a.infeatures, a._w_dtype
+        self.n_outs = tuple(l._n_out for l in layers)
+        self.n_out_sum = sum(self.n_outs)
 
 
 _MULTI: dict = {}
@@ -1008,12 +982,11 @@ def mlp_forward(gate: QuantLinear, up: QuantLinear, down: QuantLinear, x: torch.
     if tuning is not None and act != "silu":
         raise RuntimeError("mlp_forward: a tuning override goes through gptq_mlp_forward_ex, which is the SiLU call")
     for l in (gate, up, down):
-        if l._layer is None:
-            l.post_init()
+        l._ensure_init()
     if x.requires_grad and torch.is_grad_enabled():      # composed from differentiable pieces (gate | up as one node)
         g, u = forward_multi([gate, up], x)
         return down(act_fn(g) * u)
-    if any(getattr(l, "_released", False) for l in (gate, up, down)):
+    if gate._released or up._released or down._released:
         if tuning is not None:
             raise RuntimeError("mlp_forward: layers with release_checkpoint_layout=True take no tuning override")
         if x.numel() // max(1, gate.infeatures) > 4:
@@ -1029,14 +1002,7 @@ def mlp_forward(gate: QuantLinear, up: QuantLinear, down: QuantLinear, x: torch.
     if up._w_dtype != w_dtype or down._w_dtype != w_dtype:
         raise RuntimeError("mlp_forward: the three layers must share the weight dtype")
     x_dtype = x.dtype
-    x2 = x.to(w_dtype) if x_dtype != w_dtype else x
-    if x2.dim() != 2:
-        x2 = x2.reshape(-1, K)
-    if not x2.is_contiguous():
-        x2 = x2.contiguous()
-    if x2.data_ptr() & 15:
-        x2 = x2.clone()
-    M = x2.shape[0]
+    x2, M = _lib._rows16(x, K, w_dtype)
     out = torch.empty((M, down.outfeatures), dtype=w_dtype, device=dev)
     if M:
         lib = _lib.load()
@@ -1046,30 +1012,20 @@ def mlp_forward(gate: QuantLinear, up: QuantLinear, down: QuantLinear, x: torch.
             need_by_m = _MULTI[key] = {}
             share_act_order([gate, up])                 # act-order gate / up with one g_idx: one permuted x for both
         tref = ctypes.byref(tuning) if tuning is not None else None
-        need = need_by_m.get(M) if tuning is None else None
-        if need is None:
-            need = int(lib.gptq_workspace_bytes_mlp_ex(gate._layer_ref, up._layer_ref, down._layer_ref, M, tref))
-            if tuning is None:
-                need_by_m[M] = need
+        refs = (gate._layer_ref, up._layer_ref, down._layer_ref)
+        need = _cached_need(need_by_m, M, tuning, lambda: int(lib.gptq_workspace_bytes_mlp_ex(*refs, M, tref)))
         buf = reserve_workspace(dev, max(need, 1))
         exchange_tick(dev)
         idx = gate._dev_index
         fast = _lib.fast
-
-        def launch():
-            if tuning is None and (act_code != _lib.EPI_SILU_MUL or fast is None or not hasattr(fast, "mlp_forward")):
-                return lib.gptq_mlp_forward_act(gate._layer_ref, up._layer_ref, down._layer_ref, act_code, x2.data_ptr(), out.data_ptr(), M,
-                                                buf.data_ptr(), buf.numel(), _raw_stream(idx))
-            if tuning is None:                              # the trampoline calls gptq_mlp_forward = gptq_mlp_forward_act(SILU_MUL)
-                return fast.mlp_forward(gate._layer_addr, up._layer_addr, down._layer_addr, x2.data_ptr(), out.data_ptr(), M,
-                                        buf.data_ptr(), buf.numel(), _raw_stream(idx))
-            return lib.gptq_mlp_forward_ex(gate._layer_ref, up._layer_ref, down._layer_ref, x2.data_ptr(), out.data_ptr(), M,
-                                           buf.data_ptr(), buf.numel(), _raw_stream(idx), tref)
-        if idx != torch.cuda.current_device():
-            with torch.cuda.device(idx):
-                rc = launch()
-        else:
-            rc = launch()
+        tail = (x2.data_ptr(), out.data_ptr(), M, buf.data_ptr(), buf.numel(), _raw_stream(idx))
+        if tuning is not None:
+            fn, args = lib.gptq_mlp_forward_ex, refs + tail + (tref,)
+        elif act_code != _lib.EPI_SILU_MUL or fast is None or not hasattr(fast, "mlp_forward"):
+            fn, args = lib.gptq_mlp_forward_act, refs + (act_code,) + tail
+        else:                                           # the trampoline calls gptq_mlp_forward = gptq_mlp_forward_act(SILU_MUL)
+            fn, args = fast.mlp_forward, (gate._layer_addr, up._layer_addr, down._layer_addr) + tail
+        rc = _on_device(idx, fn, *args)
         if rc:
             _lib.check(rc)
     if x_dtype != w_dtype:

@@ -109,10 +109,7 @@ class ColumnParallelQuantLinear(nn.Module):
             self._px = PeerExchange(max(M, self.max_rows), self.world * nl, q.scales.dtype, x.device, group=self.group)
         if not self._px.fused_ok(q, M):
             return None
-        x2 = x.reshape(-1, K)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
-        out = self._px.forward_gather(q, x2).reshape(x.shape[:-1] + (self.world * nl,))
+        out = self._px.forward_gather(q, x.reshape(-1, K)).reshape(x.shape[:-1] + (self.world * nl,))      # (forward_gather makes x dense and aligned)
         self.fused_calls += 1
         self._calls += 1
         if self.check_timeout_every and self._calls % self.check_timeout_every == 0:
